@@ -12,16 +12,23 @@ camera (cameras are the shard; no data-path collective -- SURVEY.md 8e), value =
 / max-over-ranks time, scaling "weak".  `--gpus N` without a launcher (WORLD_SIZE unset) starts the N
 ranks itself, one process per device ordinal -- the reference's scheme (`watsor/detection/detector.py:34-50`).
 
-The timed region of exactly K steps (barrier + device synchronise on both sides, max over ranks) is
-repeated for >= 25 rounds; `value` / `ms_per_step` are the MEDIAN round, min / max beside them (one
+The timed region is exactly K steps (barrier + device synchronise on both sides, max over ranks);
+`value` / `ms_per_step` are taken from it.  `--rounds R` repeats the region R times and reports the
+MEDIAN region, min / max beside it; `--rounds 0` repeats it >= 25 times, until 1 s of them (one
 K = 20 region lasts ~4 ms: a single sample of it is noise).
+
+`--dump-outputs DIR` writes the detection rows the last timed step handed back (rank 0; ROW_DTYPE's
+fields, one float64 array [batch, 100, ...] each) as DIR/<field>.npy.  The inputs are seeded: two
+runs with the same arguments see the same frames and weights.
 
 Rank 0 prints ONE JSON line (contract in the task description) extended with
   "p50_ms"      : median latency of synchronous batch-8 steps, frames in HBM
+and, with `--full` only (each part can be left out again with its --no-* option):
   "parity"      : the north star's criterion checked LIVE on the engine that was timed: max |score - oracle score|
                   over the detection rows of 8 of the benchmark's frames (bar: 1e-3)
   "roofline"    : dominant kernel of the step, timed live with HIP events on the engine's own stream
   "legs"        : the other BASELINE configs as per-GPU shares (frames/s + p50), host-frame and plugin paths
+  "default_program_engine" / "plain_fp16_engine" / "fp32_engine": the same workload on the other programs
   "cpu_baseline": the oracle (CPU restatement of the reference's TF detector) on this host's cores
 """
 from __future__ import annotations
@@ -1086,6 +1093,15 @@ def cpu_baseline(weights, frames, budget_s=12.0):
                 published_reference="README.md:455 quotes ~24 FPS for the TF CPU detector (v1 model) on a desktop CPU")
 
 
+def dump_outputs(rows, out_dir):
+    """What the timed path handed back in one step: the rows of its batch (ROW_DTYPE [batch, 100]), every field but the padding as
+    `out_dir/<field>.npy`, float64 (labels, zone flags and pixel coordinates are small integers: exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name in rows.dtype.names:
+        if not name.startswith("_"):
+            np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(rows[name], dtype=np.float64))
+
+
 class _StubEngine:
     """GPU-less stand-in used only by --dry-run: same surface as HipEngine, a step is a 2 ms sleep."""
     num_slots = 2
@@ -1183,7 +1199,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=0, help="timed regions of --steps steps (0: >= 25, until 1 s of them)")
+    ap.add_argument("--rounds", type=int, default=1, help="timed regions of --steps steps, the median one reported (0: >= 25, until 1 s of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the detection rows of the last timed step as DIR/<field>.npy (float64; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: live parity, per-kernel roofline, counters, lane overlap, the other configs, "
+                         "host-frame / plugin legs, the other programs and the CPU baseline (the --no-* options trim these)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-legs", action="store_true", help="skip the other BASELINE configs / host-frame / plugin legs")
     ap.add_argument("--no-fp32-leg", action="store_true", help="skip the -p 32 and --plain-fp16 engine legs (profiling runs: one engine's kernels only)")
@@ -1198,6 +1219,10 @@ def main():
                     help="harness self-test without a GPU: a stub engine that sleeps 2 ms per step (used by the "
                          "world_size-2 tests; its output is marked invalid)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.table and not args.full:
+        ap.error("--table is written by the roofline pass of --full")
 
     if args.pmc_child:
         return pmc_child()
@@ -1310,6 +1335,10 @@ def main():
             break
     elapsed = float(np.median(rounds))
     note("timed: %d rounds of %d steps, median %.4f s (min %.4f, max %.4f)" % (len(rounds), args.steps, elapsed, min(rounds), max(rounds)))
+    if args.dump_outputs and rank == 0:
+        # the last timed step ran on lane (steps - 1) % lanes; the loops below reuse that lane's rows
+        dump_outputs(eng.slot_rows((args.steps - 1) % lanes, BATCH), args.dump_outputs)
+        note("outputs of the last timed step written to %s" % args.dump_outputs)
 
     # per-step latency (synchronous steps), outside the timed regions
     lat = []
@@ -1322,7 +1351,7 @@ def main():
     detections_per_frame = float((rows["confidence"] > 0).sum()) / BATCH
 
     rank_legs = None
-    if world > 1 and not args.dry_run and not args.no_legs:
+    if world > 1 and not args.dry_run and args.full and not args.no_legs:
         # every rank: its timed engine away first (one engine's streams at a time), then the host-side legs TOGETHER
         if rank != 0:
             eng.close()
@@ -1338,7 +1367,7 @@ def main():
     elif rank == 0:
         note("latency loop done")
         parity = None
-        if not args.no_parity:
+        if args.full and not args.no_parity:
             parity = parity_leg(eng, host_frames, d_frames, weights)
             note("parity: max |dscore| %.6f, max |dbox| %d px over %d rows; %d rows without a partner (%d unexplained)"
                  % (parity["max_dscore"], parity["max_dbox_px"], parity["rows_compared"], parity["rows_without_partner"], parity["rows_unexplained"]))
@@ -1347,21 +1376,23 @@ def main():
         graph_nodes = eng.graph_nodes(0)   # as captured: kernel launches (+ a descriptor copy where the resize kernel does not take them as arguments)
         input_size, hp_blocks = eng.input_size, eng.hp_blocks
         eng.close()                        # (one engine's streams at a time: eight live streams leave later engines sharing hardware queues)
-        # per-kernel durations: HIP events around every launch (wz_profile_stages) -- an entry point of the DEVELOPMENT library
-        # (the same sources built with -DWZ_DEV_BUILD; the headline above was timed on libwatsor_hip.so, which has no such hooks)
-        prof = HipEngine(engine_path, local_rank, BATCH, WIDTH, HEIGHT, dev=True)
-        pd = [prof.upload(f) for f in host_frames[:BATCH]]
-        ops = prof.ops()
-        stages = prof.profile_device(pd, ws, hs, reps=10, inner=PROFILE_INNER)
-        single = prof.profile_device(pd, ws, hs, reps=10, inner=1)
-        prof.close()
-        note("stage profiles done")
-        table, overhead = aggregate_stages(stages, ops, BATCH, WIDTH * HEIGHT * 3, input_size, hp_blocks, PROFILE_INNER)
-        single_table, _ = aggregate_stages(single, ops, BATCH, WIDTH * HEIGHT * 3, input_size, hp_blocks, 1)
-        roof = roofline_object(table, overhead, single_table, PROFILE_INNER, robust=hp_blocks >= 17)
-        if args.table:
-            json.dump(dict(stages=stages, stages_single_bracket=single, inner=PROFILE_INNER, kernels=table,
-                           kernels_single_bracket=single_table), open(args.table, "w"), indent=1)
+        roof = None
+        if args.full:
+            # per-kernel durations: HIP events around every launch (wz_profile_stages) -- an entry point of the DEVELOPMENT library
+            # (the same sources built with -DWZ_DEV_BUILD; the headline above was timed on libwatsor_hip.so, which has no such hooks)
+            prof = HipEngine(engine_path, local_rank, BATCH, WIDTH, HEIGHT, dev=True)
+            pd = [prof.upload(f) for f in host_frames[:BATCH]]
+            ops = prof.ops()
+            stages = prof.profile_device(pd, ws, hs, reps=10, inner=PROFILE_INNER)
+            single = prof.profile_device(pd, ws, hs, reps=10, inner=1)
+            prof.close()
+            note("stage profiles done")
+            table, overhead = aggregate_stages(stages, ops, BATCH, WIDTH * HEIGHT * 3, input_size, hp_blocks, PROFILE_INNER)
+            single_table, _ = aggregate_stages(single, ops, BATCH, WIDTH * HEIGHT * 3, input_size, hp_blocks, 1)
+            roof = roofline_object(table, overhead, single_table, PROFILE_INNER, robust=hp_blocks >= 17)
+            if args.table:
+                json.dump(dict(stages=stages, stages_single_bracket=single, inner=PROFILE_INNER, kernels=table,
+                               kernels_single_bracket=single_table), open(args.table, "w"), indent=1)
         out = {
             "metric": "detected frames/sec (whole node) + p50 per-frame latency, SSD-MobileNet 300x300",
             "value": round(frames_per_round / elapsed, 2), "unit": "frames/s",
@@ -1381,12 +1412,13 @@ def main():
                        "batch": BATCH, "frame": "%dx%d" % (WIDTH, HEIGHT), "parallelism": "replica-per-gpu x%d" % world, "batches_in_flight": lanes,
                        "graph_nodes_per_batch": graph_nodes, "detections_per_frame": detections_per_frame,
                        **({"n_gpus_note": "value = %d independent replicas, each on frames resident in its own HBM: linear by construction (no collective, no "
-                                          "shared resource but the host); the shared-host measurement of an N > 1 run is legs_all_ranks_concurrently "
+                                          "shared resource but the host); the shared-host measurement of an N > 1 run is legs_all_ranks_concurrently (--full) "
                                           "(page-locked host frames, every rank at the same time)" % world} if world > 1 else {})},
-            "parity": parity,
-            "roofline": roof,
         }
-        if world == 1 and not args.no_live_pmc:
+        if args.full:
+            out["parity"] = parity
+            out["roofline"] = roof
+        if world == 1 and args.full and not args.no_live_pmc:
             live = live_pmc_traffic()
             note("live counter passes %s" % ("done" if live else "unavailable (committed json kept)"))
             if live and roof["kernel"] in live:
@@ -1394,7 +1426,7 @@ def main():
                 roof["frac_counter_traffic"] = round(roof["traffic"]["bytes"] / (roof["avg_launch_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 5)
                 roof["traffic_over_fused_min"] = round(roof["traffic"]["bytes"] / max(roof["fused_min_bytes_per_launch"], 1), 3)
                 out["roofline"] = roof
-        if world == 1 and not args.no_live_pmc:
+        if world == 1 and args.full and not args.no_live_pmc:
             lo = lane_overlap()
             note("lane overlap %s" % ("measured" if lo and lo["source"].startswith("live") else "from the committed file" if lo else "unavailable"))
             if lo:
@@ -1402,7 +1434,7 @@ def main():
                 out["roofline"]["concurrency_mean"] = lo["kernels_in_flight_mean_while_busy"]
                 out["roofline"]["cu_slot_time_us_per_step"] = lo["cu_slot_time_us_per_step"]
                 out["roofline"]["lane_overlap"] = lo
-        if world == 1 and not args.no_legs:
+        if world == 1 and args.full and not args.no_legs:
             legs = {}
             legs.update(host_legs(engine_path, model_dir, local_rank, host_frames))
             note("host-frame legs done")
@@ -1417,7 +1449,7 @@ def main():
             legs.update(worker_legs(model_dir))
             note("worker legs done")
             out["legs"] = legs
-        if world == 1 and not args.no_fp32_leg:
+        if world == 1 and args.full and not args.no_fp32_leg:
             out["default_program_engine"] = default_program_leg(weights, host_frames, rank)
             try:     # the dominant kernel of THAT program under the same rule (13 launches of wz_k_mbconv_hp: the large and the 19x19 maps only)
                 builder.save_engine(builder.build_engine(weights), engine_path)
@@ -1436,10 +1468,10 @@ def main():
             out["plain_fp16_engine"] = plain_fp16_leg(weights, host_frames, rank)
             out["fp32_engine"] = fp32_engine_leg(weights, host_frames, rank)
             note("other-precision legs done")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(weights, host_frames[:BATCH])
             note("cpu baseline done")
-    if world > 1 and not args.no_legs:
+    if world > 1 and args.full and not args.no_legs:
         stub = [("stub", lambda: {"host_frames_pinned_b8": dict(value=1000.0 + rank, p50_ms=1.0, workload="dry-run stub")})] if args.dry_run else None
         gathered = all_rank_legs(engine_path, model_dir, local_rank, host_frames, dist, world, plan=stub,
                                  rank_info=numa_info or dict(device=local_rank, numa_node=-1, pinned=False))
@@ -1450,7 +1482,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if out is not None:
-        if world > 1:
+        if world > 1 and args.full:
             out["only_at_n_gpus_1"] = "cpu_baseline, live counter traffic, lane overlap, the other-engine legs and the single-process legs run at N = 1 only"
         print(json.dumps(out), flush=True)
     try:

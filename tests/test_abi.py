@@ -1,5 +1,6 @@
 """Row ABI: our ctypes mirror == the reference's shared-memory structs (watsor/stream/share.py:11-32)."""
 import ctypes
+import json
 import re
 import os
 
@@ -43,18 +44,22 @@ def test_c_header_struct_matches():
                       "int32_t x_min, y_min, x_max, y_max;"]
 
 
-@pytest.mark.reference
-def test_against_reference_structs(reference_on_path):
-    from watsor.stream import share as ref
+def test_against_reference_structs():
+    """Against the reference's own structs as recorded from its sources (tests/golden/make_reference_golden.py)."""
+    ref = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "reference_layout.json")))["structs"]
     for name in ("BoundingBox", "Detection", "Header"):
-        ours, theirs = getattr(share, name), getattr(ref, name)
-        assert ctypes.sizeof(ours) == ctypes.sizeof(theirs)
-        for (fn, _), (rn, _) in zip(ours._fields_, theirs._fields_):
-            assert fn == rn
-            assert getattr(ours, fn).offset == getattr(theirs, rn).offset
-            assert getattr(ours, fn).size == getattr(theirs, rn).size
-    # a reference Detection array is accepted wherever ours is (same memory layout)
-    arr = (ref.Detection * 100)()
-    a = np.frombuffer(arr, dtype=ROW_DTYPE)
-    arr[1].bounding_box.y_min = 11
-    assert a[1]["y_min"] == 11
+        ours, theirs = getattr(share, name), ref[name]
+        assert ctypes.sizeof(ours) == theirs["size"]
+        assert len(ours._fields_) == len(theirs["fields"])
+        for (fn, ft), (rn, rt, roff, rsize) in zip(ours._fields_, theirs["fields"]):
+            assert (fn, ft.__name__) == (rn, rt)
+            assert getattr(ours, fn).offset == roff
+            assert getattr(ours, fn).size == rsize
+    # a reference Detection array is accepted wherever ours is (same memory layout): every row field at the reference's offset
+    det = {n: off for n, _, off, _ in ref["Detection"]["fields"]}
+    box = {n: off for n, _, off, _ in ref["BoundingBox"]["fields"]}
+    assert ROW_DTYPE.itemsize == ref["Detection"]["size"]
+    for n in ("label", "zones", "confidence"):
+        assert ROW_DTYPE.fields[n][1] == det[n]
+    for n in ("x_min", "y_min", "x_max", "y_max"):
+        assert ROW_DTYPE.fields[n][1] == det["bounding_box"] + box[n]

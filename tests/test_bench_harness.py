@@ -23,11 +23,24 @@ def test_single_process_dry_run():
     assert 1500 < out["value"] < 8100                 # 8 frames per 2 ms step, two stub lanes in flight
 
 
+def test_plain_run_times_steps_once_and_dumps_the_last_step(tmp_path):
+    """A plain run times exactly --steps steps (one region) and `--dump-outputs` leaves the last step's rows as float .npy files."""
+    import numpy as np
+    out = run([sys.executable, "bench.py", "--gpus", "1", "--steps", "12", "--warmup", "2", "--dry-run",
+               "--dump-outputs", str(tmp_path / "out")])
+    assert out["steps"] == 12 and out["rounds"] == 1 and out["ms_per_step"] > 0
+    assert "legs" not in out and "cpu_baseline" not in out
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files and all(f.endswith(".npy") for f in files)
+    for f in files:
+        assert np.load(tmp_path / "out" / f).dtype in (np.float32, np.float64)
+
+
 def test_two_ranks_over_gloo():
     port = 29500 + os.getpid() % 400
     out = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "40",
-               "--warmup", "4", "--dry-run"])
+               "--warmup", "4", "--dry-run", "--full"])
     assert out["n_gpus"] == 2
     assert out["camera_seeds"] == [1234, 2234]        # every rank serves its own camera (cameras are the shard)
     # the host-side legs run on EVERY rank at the same time when N > 1 and come back per rank and summed (stubbed in a dry run)
@@ -47,7 +60,7 @@ def test_gpus_flag_starts_the_ranks_itself():
     env_keys = ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")
     saved = {k: os.environ.pop(k) for k in env_keys if k in os.environ}
     try:
-        out = run([sys.executable, "bench.py", "--gpus", "2", "--steps", "40", "--warmup", "4", "--dry-run"])
+        out = run([sys.executable, "bench.py", "--gpus", "2", "--steps", "40", "--warmup", "4", "--rounds", "0", "--dry-run"])
     finally:
         os.environ.update(saved)
     assert out["n_gpus"] == 2 and out["camera_seeds"] == [1234, 2234] and out["rounds"] >= 3
@@ -61,7 +74,7 @@ def test_eight_ranks_dry_run():
     env_keys = ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")
     saved = {k: os.environ.pop(k) for k in env_keys if k in os.environ}
     try:
-        out = run([sys.executable, "bench.py", "--gpus", "8", "--steps", "10", "--warmup", "2", "--dry-run"])
+        out = run([sys.executable, "bench.py", "--gpus", "8", "--steps", "10", "--warmup", "2", "--dry-run", "--full"])
     finally:
         os.environ.update(saved)
     assert out["n_gpus"] == 8 and out["camera_seeds"] == [1234 + 1000 * r for r in range(8)]

@@ -82,22 +82,22 @@ def test_confidence_area_match_reference_fixture():
     assert 30 < sum(r["conf_pass"] for r in g["rows"]) < 370
 
 
-@pytest.mark.reference
-def test_coco_table_and_filters_against_reference(reference_on_path):
-    from watsor.config.coco import COCO_CLASSES as ref
-    from watsor.filter.area import AreaFilter
-    from watsor.filter.confidence import ConfidenceFilter
+def test_coco_table_and_filters_against_reference():
+    """The reference's COCO table and its ConfidenceFilter / AreaFilter verdicts on 300 seeded detections, as recorded from its
+    sources (tests/golden/make_reference_golden.py)."""
     from watsor_amd.coco import COCO_CLASSES
-    assert list(ref) == list(COCO_CLASSES)
+    ref = json.load(open(os.path.join(GOLDEN, "reference_layout.json")))
+    assert ref["coco_classes"] == list(COCO_CLASSES)
     cfg = json.load(open(os.path.join(GOLDEN, "filters.json")))["config"]
+    b, d = of.ConfidenceFilter(cfg), of.AreaFilter(cfg)
     rng = np.random.default_rng(5)
-    a, b = ConfidenceFilter(cfg), of.ConfidenceFilter(cfg)
-    c, d = AreaFilter(cfg), of.AreaFilter(cfg)
-    for _ in range(300):
-        x0, y0 = int(rng.integers(0, 600)), int(rng.integers(0, 440))
-        dd = det(int(rng.choice([0, 1, 3, 8, 5])), float(np.float32(rng.random())),
-                 (x0, y0, int(rng.integers(x0, 640)), int(rng.integers(y0, 480))))
-        assert a(dd) == b(dd) and c(dd) == d(dd)
+    assert len(ref["filter_cases"]) == 300
+    for r in ref["filter_cases"]:
+        x0, y0 = int(rng.integers(0, 600)), int(rng.integers(0, 440))      # the recorded cases are these seeded detections
+        label, score = int(rng.choice([0, 1, 3, 8, 5])), float(np.float32(rng.random()))
+        assert (r["label"], r["confidence"], r["box"]) == (label, score, [x0, y0, int(rng.integers(x0, 640)), int(rng.integers(y0, 480))])
+        dd = det(r["label"], r["confidence"], r["box"])
+        assert r["conf_pass"] == b(dd) and r["area_pass"] == d(dd), r
 
 
 # ---- zones: host extraction (C++, raster) vs oracle (Python, polygons) -------------------------------

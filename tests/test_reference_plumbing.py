@@ -18,9 +18,11 @@ pytestmark = pytest.mark.reference
 
 
 class FakeBatchDetector:
-    """Plugin-protocol detector that needs no model: row d of a frame carries the frame's first pixel."""
+    """Plugin-protocol detector that needs no model: row d of a frame carries the frame's first pixel.  A call takes longer than a
+    source's frame period (`busy_s` > the sources' 5 ms), so while it runs frames of the other cameras queue up, also on a loaded host."""
     max_batch = 4
     calls = []
+    busy_s = 0.01
 
     def __init__(self, model_path, device=0):
         self.model_path = model_path
@@ -43,11 +45,13 @@ class FakeBatchDetector:
 
     def detect(self, image_shape, image_np, detections):
         FakeBatchDetector.calls.append(1)
+        time.sleep(self.busy_s)
         self._fill(image_np, detections)
         return 1.0
 
     def detect_batch(self, shapes, images, detections):
         FakeBatchDetector.calls.append(len(images))
+        time.sleep(self.busy_s)
         for im, d in zip(images, detections):
             self._fill(im, d)
         return 2.0
@@ -290,8 +294,10 @@ def test_worker_class_survives_the_spawn_start_method(reference_on_path):
 class AddressEngine:
     """Stand-in for `HipEngine` under the real `HipObjectDetector`: it keeps what `bind_frames` was given -- raw addresses of the
     reference's shared-memory pixels and `header.detections` -- and, like the library, reads and writes THROUGH those addresses
-    when a bound batch is collected.  Row 0 of a frame carries the frame's first pixel."""
+    when a bound batch is collected.  Row 0 of a frame carries the frame's first pixel.  Collecting a batch takes longer than a
+    source's frame period (`busy_s`), so frames of several cameras are queued by the time the worker takes the next ones."""
     instances = []
+    busy_s = 0.01
 
     def __init__(self, path, device, max_batch, max_width, max_height, schedule=None):
         self.max_batch, self.num_slots, self.device_name, self.schedule = 4, 2, "stub", schedule or "throughput"
@@ -315,6 +321,7 @@ class AddressEngine:
     def collect_bound(self, lane):
         import ctypes
         from watsor_amd.share import DetectionArray
+        time.sleep(self.busy_s)
         for e in self.busy.pop(lane):
             pix, w, h, fmt, cam, rows = self.table[e]
             d = DetectionArray.from_address(rows)

@@ -7,7 +7,7 @@ OUT=$PWD/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 ROOT=$PWD
-BENCH="python $ROOT/bench.py --steps 40 --warmup 10 --rounds 3 --no-cpu-baseline --no-legs --no-fp32-leg --no-parity --no-live-pmc"
+BENCH="python $ROOT/bench.py --full --steps 40 --warmup 10 --rounds 3 --no-cpu-baseline --no-legs --no-fp32-leg --no-parity --no-live-pmc"
 cd /tmp
 for V in $A $B; do
   rm -rf /tmp/wzprof_$V && mkdir -p /tmp/wzprof_$V
