@@ -59,7 +59,7 @@ def traffic_json(agg, path):
             c = "wz_k_mbconv_hp"                  # the split-operand blocks (0 .. 12 of the default -p 16 program)
         elif c.startswith("wz_k_mbconv"):
             c = "wz_k_mbconv"                     # the plain fused-block kernels serve one op class
-        if c == "wz_k_conv_lds" or c == "wz_k_conv":
+        if c == "wz_k_conv":
             c = "wz_k_conv<%s>" % k.split("<")[1].split(",")[0].split(">")[0]
         if "FETCH_SIZE" in counters:
             cls[c]["fetch_kib"] += counters["FETCH_SIZE"][0]; cls[c]["nf"] += counters["FETCH_SIZE"][1]

@@ -82,7 +82,7 @@ def main(path, out=None, js=None):
                 k = "wz_k_mbconv_hp"
             elif k.startswith("wz_k_mbconv"):
                 k = "wz_k_mbconv"
-            if k in ("wz_k_conv_lds", "wz_k_conv"):
+            if k == "wz_k_conv":
                 k = "wz_k_conv<%s>" % name.split("<")[1].split(",")[0].split(">")[0]
             a = agg.setdefault(k, [0.0, 0])
             a[0] += avg * calls                                # the `average` column is what the table prints as avg_us

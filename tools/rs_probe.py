@@ -22,4 +22,4 @@ _lib.check(e._lib.wz_debug_mbconv(e._h, C.c_void_p(out.ctypes.data), C.c_void_p(
 for i, o in enumerate(ops):
     if o["kind"] == 4 or not out[i].any(): continue
     t = out[i].astype(np.int64)
-    print("%-32s pairs %2d | first half-step cycles: ds_write(wait rb) %5d  load_b issue %5d  compute %5d  load_a issue %5d  barrier %5d | mover wave: ds_write %5d load_b %5d barrier %5d" % (o["name"].split("/")[-1][:32], t[5], t[0], t[1], t[2], t[3], t[4], t[8], t[9], t[12]))
+    print("%-32s pairs %2d | first half-step cycles: ds_write(wait rb) %5d  load_b issue %5d  compute %5d  load_a issue %5d  barrier %5d" % (o["name"].split("/")[-1][:32], t[5], t[0], t[1], t[2], t[3], t[4]))

@@ -1,4 +1,4 @@
-"""Cycle counts of the wide head kernel wz_k_conv_wide_group (first workgroup, wave 0), batch 8 by default.
+"""Cycle counts of the wide head kernel wz_k_conv_wide_group3 (first workgroup, wave 0), batch 8 by default.
 
 The counters are compiled in only with -DWZ_WIDE_STAMPS=1:
     make -C watsor_amd/csrc clean && make -C watsor_amd/csrc CXXFLAGS_EXTRA=-DWZ_WIDE_STAMPS=1

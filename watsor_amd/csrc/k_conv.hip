@@ -192,7 +192,7 @@ __device__ __forceinline__ void wz_decode_anchor(const float4_t e, const float4_
 
 // Everything that happens to four finished output columns n4 .. n4+3 of pixel m of an SSD head (v = the K sum, bias not yet
 // added): the epilogue proper (bias, store into the box-encoding / class-logit buffers), and optionally the candidate
-// marking for wz_k_nms and the box decode.  Shared by the grouped reduce launch and by the in-launch reduction.
+// marking for wz_k_nms and the box decode.
 __device__ __forceinline__ void wz_head_finish(const WzConvArgs& a, int m, int n4, float4_t v, bool list, bool decode,
                                                const float* __restrict__ hint_logit, uint32_t* __restrict__ cbits,
                                                int cbits_words, const WzPostConsts& pc, const float* __restrict__ anchors,
@@ -229,20 +229,6 @@ __device__ __forceinline__ void wz_head_finish(const WzConvArgs& a, int m, int n
         const size_t i = (size_t)b * pc.num_anchors + anchor;
         wz_decode_anchor(enc, *reinterpret_cast<const float4_t*>(anchors + (size_t)anchor * 4), pc, boxes + i * 4, valid + i);
     }
-}
-
-// ---- in-launch split-K reduction (see WzConvArgs::inline_reduce) ----------------------------------------------------
-// publish: write-through (sc1) stores, then the issuing wave waits for them (the compiler knows nothing of asm stores)
-__device__ __forceinline__ void wz_store_partial_sc1(float* p, const float4_t v) {
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-}
-__device__ __forceinline__ void wz_wait_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// the head's finish for the summed K slices of (m, n4) (summed in slice order: wz_k_splitk_reduce's arithmetic)
-__device__ __forceinline__ void wz_inline_finish(const WzConvArgs& a, int m, int n4, const float4_t v) {
-    if (m >= a.M || n4 >= a.n_pad) return;
-    const WzHeadFinish& f = *a.fin;
-    wz_head_finish(a, m, n4, v, (a.fin_flags & 2) != 0, (a.fin_flags & 1) != 0, f.hint_logit, f.cbits, f.cbits_words, f.pc,
-                   f.anchors, f.boxes, f.valid);
 }
 
 
@@ -354,52 +340,6 @@ __device__ __forceinline__ void wz_conv_body(const WzConvArgs& a, int bx, int by
     }
 
     // D layout: lane holds rows (n) g*4..g*4+3 of column (m) r16
-    if (a.splitk > 1 && a.inline_reduce) {
-        // in-launch reduction, one WAVE tile at a time (the waves of this kernel never meet): publish, take a ticket,
-        // and the wave that finds the other K slices already there sums them all in slice order and finishes
-        float* const ws = a.ws;   // (a.out is where the FINISHED columns go)
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const int m = m_base + mt * 16 + r16;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                if (m < a.M) wz_store_partial_sc1(ws + ((size_t)bz * a.M + m) * a.n_pad + (nt0 + nt) * 16 + g * 4, acc[mt][nt]);
-        }
-        wz_wait_stores();
-        int32_t* const tk = a.tickets + ((int)(by * a.grid_m + bx) * 4 + (int)(threadIdx.x >> 6));
-        int t = 0;
-        if (lane == 0) t = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        t = __builtin_amdgcn_readfirstlane(t);
-        if (t != a.splitk - 1) return;
-        if (lane == 0) __hip_atomic_store(tk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = (float4_t){0.f, 0.f, 0.f, 0.f};
-        for (int z = 0; z < a.splitk; ++z) {   // a slice's fragments are all requested before the first is added
-            float4_t pz[MT][NT];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                const int m = m_base + mt * 16 + r16;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    pz[mt][nt] = m < a.M ? *reinterpret_cast<const float4_t*>(ws + ((size_t)z * a.M + m) * a.n_pad + (nt0 + nt) * 16 + g * 4)
-                                         : (float4_t){0.f, 0.f, 0.f, 0.f};
-            }
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[mt][nt][r] += pz[mt][nt][r];
-        }
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) wz_inline_finish(a, m_base + mt * 16 + r16, (nt0 + nt) * 16 + g * 4, acc[mt][nt]);
-        return;
-    }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         const int m = m_base + mt * 16 + r16;
@@ -532,12 +472,6 @@ __global__ __launch_bounds__(256) void wz_k_splitk_reduce(const WzConvArgs a, co
 // exactly what wz_k_splitk_reduce does (same order over the splits: bit-identical results).
 __global__ __launch_bounds__(256) void wz_k_splitk_reduce_group(const WzReduceGroup g) {
     WZ_LANE_STAMP(g.stamp);
-    if (g.decode && !g.list) {   // first kernel of the histogram-based post chain: clear its per-frame scratch
-        const int i = blockIdx.x * 256 + threadIdx.x;
-        if (i < g.n_frames * WZ_HIST_BINS) g.hist[i] = 0u;
-        if (i < g.n_frames) g.count[i] = 0u;
-        if (i < 2 * g.n_frames) g.band[i] = 0u;
-    }
     int e = 0;
     while (e + 1 < g.n && (int)blockIdx.x >= g.first[e + 1]) ++e;   // wave-uniform
     const WzConvArgs& a = g.a[e];
@@ -583,231 +517,25 @@ __global__ __launch_bounds__(256) void wz_k_splitk_reduce_group(const WzReduceGr
 }
 
 // --------------------------------------------------------------------------------------------
-// LDS-tiled implicit GEMM for the layers with a long K loop (the 3x3 SSD heads, the 3x3 extras, Conv_1):
-// workgroup = 128 pixels x 64 channels, K step = 64 (two MFMA K chunks), 4 waves as 2 (pixels) x 2
-// (channels), wave tile 64 x 32.  Both operands go global -> LDS with `global_load_lds_dwordx4`
-// (no staging registers): the LDS image of a tile is a list of 1 KiB MFMA fragments, lane l's 16 bytes
-// at l*16, which is exactly what the DMA writes (wave-uniform base + lane * 16) and what `ds_read_b128`
-// reads back conflict-free.  Weight fragments are contiguous in the packed layout; an activation
-// tile is staged pixel-major in full 128-byte lines (see the kernel) with out-of-frame pixels read from a
-// zero page.  Two LDS buffers: the DMA of step s+1 runs under the MFMAs of step s, one barrier per step.
+// Tiled implicit GEMM for the layers with a long K loop (the 3x3 SSD heads, the 3x3 extras, Conv_1): workgroup = 128
+// pixels x 64 or 128 channels, K step = 64 (two MFMA K chunks); the kernel is wz_k_conv_rs (k_conv_rs.h).
 // --------------------------------------------------------------------------------------------
 #define WZ_LDS_TM 128
-// NW = 16-channel tiles per wave: 2 -> workgroup tile 128 x 64, 4 -> 128 x 128 (twice the MFMAs per DMA byte)
+// NW = 16-channel tiles per wave pair: 2 -> workgroup tile 128 x 64, 4 -> 128 x 128 (twice the MFMAs per byte staged)
 #define WZ_LDS_TN(NW) (2 * (NW) * 16)
-#define WZ_LDS_BUF(NW) ((4 * (NW) + 16) * 1024)   // A fragments + 16 B fragments of 1 KiB
-
-__device__ __forceinline__ void wz_glds16(const void* gsrc, unsigned char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-// NBUF LDS buffers = NBUF - 1 K steps of DMA in flight per workgroup.  With one step in flight the kernel is bound by
-// latency, not bandwidth (bytes in flight per CU / L2 latency); the waits are explicit `s_waitcnt vmcnt(n)` on the
-// wave's own DMA instructions (NW + 4 per step, always issued, completing in order) followed by a bare `s_barrier`:
-// `__syncthreads()` would drain every outstanding DMA.
-template <int N>
-__device__ __forceinline__ void wz_wait_dma_then_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-
-// SPEC: producer / consumer wavefronts.  In-kernel cycle counts (tools/conv_probe.py) showed a K step of the plain
-// variant costing 2 360 cycles per wave = 1 140 to ISSUE its eight DMA instructions (each stalls ~140 cycles in the
-// address path while others are in flight) + 960 for the fragment reads and 32 MFMAs + 250 waiting -- serialised,
-// because a wave issues in order and there is one wave per SIMD.  With SPEC the workgroup has eight waves: 4..7 only
-// issue the DMAs of step s + D, 0..3 only compute step s; the two halves meet at one barrier per step.
-template <int KS, int NW, int NBUF, bool SPEC>
-__global__ __launch_bounds__(SPEC ? 512 : 256) void wz_k_conv_lds(const WzConvArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char wz_cl_smem[];
-    constexpr int taps = KS * KS;
-    constexpr int ABYTES = 4 * NW * 1024, BUF = WZ_LDS_BUF(NW);
-    const int n_tiles = a.n_pad >> 4;   // packed 16-channel tiles; a partial last workgroup tile stages zeros beyond
-    const int lane = threadIdx.x & 63, wave = (threadIdx.x >> 6) & 3;
-    const bool producer = !SPEC || threadIdx.x >= 256, consumer = !SPEC || threadIdx.x < 256;   // wave-uniform
-    const int r16 = lane & 15, g = lane >> 4;
-    const int wm = wave >> 1, wn = wave & 1;
-    // diagnostics (a.dbg != nullptr only in engines created with WZ_MB_DEBUG=1): phase timestamps (100 MHz) of the
-    // first workgroup (slots 0..7) and of the last one (8..15)
-    const bool stamp = !WZ_LANE_STAMPS && a.dbg && threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1);
-    unsigned long long* const dbg = a.dbg + (blockIdx.x == 0 ? 0 : 8);
-    WZ_LANE_STAMP(a.dbg);
-#define CL_STAMP(i) do { if (stamp) dbg[i] = wall_clock64(); } while (0)
-    CL_STAMP(0);
-    // XCD-aware tile order: workgroup L runs on XCD L % 8 (each XCD has its own L2).  Renumber so that
-    // the workgroups of one XCD are CONSECUTIVE tiles, pixel tile fastest: the tiles that stream the same
-    // weight slice (same channel tile, same K split) then share one L2 instead of pulling it eight times.
-    int bx, by, bz;
-    {
-        const int total = a.grid_m * a.grid_n * a.splitk;
-        const int L = blockIdx.x, xcd = L & 7, slot = L >> 3;
-        const int qd = total >> 3, rm = total & 7;
-        const int V = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + slot;
-        bx = V % a.grid_m;
-        const int rest = V / a.grid_m;
-        by = rest % a.grid_n;
-        bz = rest / a.grid_n;
-    }
-    const int m_base = bx * WZ_LDS_TM;
-    const int nt0 = by * (2 * NW);
-
-    // Activations are staged in FULL 128-byte lines: one DMA instruction = 8 pixels x 64 channels (a K step), lane l
-    // fetching 16-byte chunk (l & 7) of pixel (l >> 3) -- 8 cache lines per instruction instead of the 16 half lines a
-    // fragment-shaped gather (16 pixels x 64 bytes) touches, which halves the address-path work per byte.  The LDS
-    // image is pixel-major, 128 bytes per pixel; a B fragment (16 pixels at a 128-byte stride) would hit two bank
-    // groups 8 ways, so chunk j of pixel P is stored at slot j ^ ((P >> 1) & 7): the swizzle is applied to the SOURCE
-    // address (the DMA writes lane-linearly) and again when the fragment is read.
-    // This wave stages pixels [wave * 32, wave * 32 + 32) of the tile, 8 per instruction.
-    const int hw = a.hout * a.wout;
-    int iy0[4], ix0[4], boff[4];
-    bool mv[4];
-    const int dma_j = lane & 7;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m_base + wave * 32 + i * 8 + (lane >> 3);
-        mv[i] = m < a.M;
-        const int mm = mv[i] ? m : 0;
-        const int b = mm / hw, rem = mm - b * hw;
-        const int oy = rem / a.wout, ox = rem - oy * a.wout;
-        iy0[i] = oy * a.stride - a.pad_t;
-        ix0[i] = ox * a.stride - a.pad_l;
-        boff[i] = b * a.hin;
-    }
-    // (P >> 1) & 7 of the pixel this lane fetches in instruction i: P = wave*32 + i*8 + (lane>>3)  ->  (i*4 + (lane>>4)) & 7
-    const int dma_swz = lane >> 4;   // + i * 4, & 7 below
-
-    // K steps of this split (a step = 2 consecutive 32-channel chunks of one filter tap; kc is even)
-    const int nsteps = a.kchunks >> 1;
-    const int per = (nsteps + a.splitk - 1) / a.splitk;
-    const int s0 = bz * per, s1 = min(s0 + per, nsteps);
-
-    auto stage = [&](int s, int buf) {
-        unsigned char* base = wz_cl_smem + buf * BUF;
-        // K order: channel pair outermost, filter tap innermost -- the nine taps of a channel pair read (almost) the same
-        // pixel lines, 21 KiB per tile, which then stay in the 32 KiB L1 instead of being fetched from L2 nine times
-        // (tap-major order puts 9 steps x every workgroup's traffic between two uses of a line)
-        const int t = (KS == 1) ? 0 : ((a.order & 4) ? (s * 2) / a.kc : s % taps);
-        const int c = (KS == 1) ? s * 2 : ((a.order & 4) ? s * 2 - t * a.kc : (s / taps) * 2);
-        const int ky = (KS == 1) ? 0 : t / KS, kx = (KS == 1) ? 0 : t - ky * KS;
-        // A: this wave stages NW/2 channel tiles x (kc = 0/1): each 2 KiB contiguous in the packed weights
-#pragma unroll
-        for (int i = 0; i < NW / 2; ++i) {
-            const int ntl = wave * (NW / 2) + i;
-            const bool have = nt0 + ntl < n_tiles;   // wave-uniform
-            const half_t* wsrc = have ? a.w + ((size_t)((nt0 + ntl) * taps + t) * a.kc + c) * 512 + lane * 8
-                                      : a.zeros + lane * 8;
-            wz_glds16(wsrc, base + (ntl * 2 + 0) * 1024);
-            wz_glds16(have ? wsrc + 512 : wsrc, base + (ntl * 2 + 1) * 1024);
-        }
-        // B: 8 pixels x 128 bytes per instruction
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int iy = iy0[i] + ky, ix = ix0[i] + kx;
-            const bool ok = mv[i] && iy >= 0 && iy < a.hin && ix >= 0 && ix < a.win;
-            const int chunk = dma_j ^ ((i * 4 + dma_swz) & 7);
-            const half_t* src = ok ? a.in + ((size_t)(boff[i] + iy) * a.win + ix) * a.cin + c * 32 + chunk * 8 : a.zeros;
-            wz_glds16(src, base + ABYTES + (wave * 4 + i) * 1024);
-        }
-    };
-
-    float4_t acc[4][NW];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NW; ++nt) acc[mt][nt] = (float4_t){0.f, 0.f, 0.f, 0.f};
-
-    constexpr int D = NBUF - 1, PER = NW + 4;   // prefetch distance; DMA instructions per wave per step
-    if (producer) {
-#pragma unroll
-        for (int d = 0; d < D; ++d)
-            if (s0 + d < s1) stage(s0 + d, d);
-    }
-    CL_STAMP(1);
-    long long cyc_wait = 0, cyc_stage = 0, cyc_loop = stamp ? clock64() : 0;
-    int buf = 0;
-    for (int s = s0; s < s1; ++s) {
-        const long long c0 = stamp ? clock64() : 0;
-        // step s has landed once at most the DMAs of the steps issued after it are outstanding (in-order completion);
-        // past the barrier every wave is done reading the buffer of step s - 1, which step s + D reuses
-        const int later = min(D - 1, s1 - 1 - s);
-        if (NBUF == 2 || later == 0)
-            wz_wait_dma_then_barrier<0>();
-        else if (NBUF == 3 || later == 1)
-            wz_wait_dma_then_barrier<PER>();
-        else
-            wz_wait_dma_then_barrier<2 * PER>();
-        if (s == s0) CL_STAMP(2);
-        const long long c1 = stamp ? clock64() : 0;
-        if (producer && s + D < s1) stage(s + D, buf == 0 ? NBUF - 1 : buf - 1);
-        if (stamp) {
-            const long long c2 = clock64();
-            cyc_wait += c1 - c0;
-            cyc_stage += c2 - c1;
-        }
-        const unsigned char* base = wz_cl_smem + buf * BUF;
-        buf = buf + 1 == NBUF ? 0 : buf + 1;
-        if (!consumer) continue;
-#pragma unroll
-        for (int kc = 0; kc < 2; ++kc) {
-            half8_t fa[NW], fb[4];
-#pragma unroll
-            for (int nt = 0; nt < NW; ++nt)
-                fa[nt] = *reinterpret_cast<const half8_t*>(base + ((wn * NW + nt) * 2 + kc) * 1024 + lane * 16);
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)   // pixel P = (wm*4 + mt)*16 + r16, chunk kc*4 + g, slot swizzled by (P >> 1) & 7
-                fb[mt] = *reinterpret_cast<const half8_t*>(base + ABYTES + ((wm * 4 + mt) * 16 + r16) * 128 +
-                                                           (((kc * 4 + g) ^ ((r16 >> 1) & 7)) * 16));
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < NW; ++nt)
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[nt], fb[mt], acc[mt][nt], 0, 0, 0);
-        }
-    }
-
-    if (!consumer) return;
-    CL_STAMP(3);
-    if (stamp) {
-        dbg[5] = (unsigned long long)cyc_wait;
-        dbg[7] = (unsigned long long)cyc_stage;
-        dbg[6] = (unsigned long long)(s1 - s0) | ((unsigned long long)(clock64() - cyc_loop) << 16);
-    }
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-        const int m = m_base + (wm * 4 + mt) * 16 + r16;
-#pragma unroll
-        for (int nt = 0; nt < NW; ++nt) {
-            const int n4 = (nt0 + wn * NW + nt) * 16 + g * 4;
-            if (a.splitk > 1) {
-                if (m < a.M && n4 < a.n_pad)
-                    *reinterpret_cast<float4_t*>(reinterpret_cast<float*>(a.out) +
-                                                 ((size_t)bz * a.M + m) * a.n_pad + n4) = acc[mt][nt];
-            } else {
-                wz_epilogue4(a, m, n4, acc[mt][nt]);
-            }
-        }
-    }
-    if (stamp) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        dbg[4] = wall_clock64();
-    }
-#undef CL_STAMP
-}
 
 #include "k_conv_rs.h"
 
 struct WzEpiF16 {
     static __device__ __forceinline__ void apply(const WzConvArgs& a, int m, int n4, float4_t v) { wz_epilogue4(a, m, n4, v); }
     static __device__ __forceinline__ float* partials(const WzConvArgs& a) { return reinterpret_cast<float*>(a.out); }
-    static constexpr bool INLINE = true;   // supports WzConvArgs::inline_reduce
-    static __device__ __forceinline__ void publish(float* p, const float4_t v) { wz_store_partial_sc1(p, v); }
-    static __device__ __forceinline__ void finish(const WzConvArgs& a, int m, int n4, const float4_t v) { wz_inline_finish(a, m, n4, v); }
 };
 
-template <int KS, int NW, bool SPEC>
-__global__ __launch_bounds__(SPEC ? 512 : 256, 2) void wz_k_conv_rs(const WzConvArgs a) {   // <= 256 registers: two waves per SIMD
+template <int KS, int NW>
+__global__ __launch_bounds__(256, 2) void wz_k_conv_rs(const WzConvArgs a) {   // <= 256 registers: two waves per SIMD
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 16384];
     WZ_LANE_STAMP(a.dbg);
-    wz_conv_rs_body<KS, NW, SPEC, false, WzEpiF16>(a, smem, blockIdx.x);
+    wz_conv_rs_body<KS, NW, false, WzEpiF16>(a, smem, blockIdx.x);
 }
 
 // The SSD heads served by the register-staged tile kernel (the two big ones with 128 x 128 tiles, the 5x5 one with
@@ -821,9 +549,9 @@ __global__ __launch_bounds__(256, 2) void wz_k_conv_rs_group(const WzConvGroup g
     while (e + 1 < g.n && (int)blockIdx.x >= g.first[e + 1]) ++e;   // wave-uniform
     const int L = (int)blockIdx.x - g.first[e];
     if (g.gx[e] == 4)   // channel tiles per wave pair of this entry (wave-uniform)
-        wz_conv_rs_body<3, 4, false, false, WzEpiF16>(g.a[e], smem, L);
+        wz_conv_rs_body<3, 4, false, WzEpiF16>(g.a[e], smem, L);
     else
-        wz_conv_rs_body<3, 2, false, false, WzEpiF16>(g.a[e], smem, L);
+        wz_conv_rs_body<3, 2, false, WzEpiF16>(g.a[e], smem, L);
 }
 
 static int wz_env_int(const char* name, int dflt) {
@@ -845,19 +573,12 @@ int wz_lds_nw(int M, int n_pad, int kchunks) {
     return (n_pad >= 256 && M >= 512 && kchunks >= 64) ? 4 : 2;   // measured: the two big heads gain, Conv_1 (K = 320) loses
 }
 
-static int wz_lds_nbuf();
-static int wz_lds_spec();
 int wz_choose_splitk_lds(int M, int n_pad, int kchunks) {
     static const int target = wz_env_int("WZ_LDS_WGS", 192);   // measured 64 .. 512: fewer, longer K slices win (less partial-sum traffic); 192 best
     const int tn = WZ_LDS_TN(wz_lds_nw(M, n_pad, kchunks));
     const int wgs = ((M + WZ_LDS_TM - 1) / WZ_LDS_TM) * ((n_pad + tn - 1) / tn);
     const int nsteps = kchunks / 2;
     int s = (target + wgs - 1) / wgs;
-    // with more than 80 KiB of LDS per workgroup only one fits a CU: a grid beyond 256 workgroups would need a second,
-    // nearly empty round
-    static const int rs_mode = wz_env_int("WZ_LDS_RS", 1);
-    const bool one_per_cu = rs_mode ? wz_lds_spec() != 0 : wz_lds_nbuf() * WZ_LDS_BUF(wz_lds_nw(M, n_pad, kchunks)) > 80 * 1024;
-    if (one_per_cu && s * wgs > 256) s = 256 / wgs;
     if (s > nsteps / 4) s = nsteps / 4;   // >= 4 steps per split
     if (s > 32) s = 32;
     return s < 1 ? 1 : s;
@@ -893,41 +614,10 @@ static void wz_launch_conv_cfg(const WzConvArgs& a, hipStream_t s) {
         WZ_LAUNCH((wz_k_conv<3, MT, NT, U>), grid, dim3(256), 0, s, a);
 }
 
-static int wz_lds_nbuf() { return 2; }
-
-static int wz_lds_spec() {
-    static const int v = wz_env_int("WZ_LDS_SPEC", 0);
-    return v;
-}
-
-template <int KS, int NW, int NBUF, bool SPEC>
-static void wz_conv_lds_attr() {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wz_k_conv_lds<KS, NW, NBUF, SPEC>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, NBUF * WZ_LDS_BUF(NW));
-}
-template <int KS, int NW>
-static void wz_conv_lds_attrs() {
-    wz_conv_lds_attr<KS, NW, 2, false>();
-}
-void wz_conv_init() {   // kernel attributes (before any stream capture)
-    wz_conv_lds_attrs<1, 2>();
-    wz_conv_lds_attrs<3, 2>();
-    wz_conv_lds_attrs<1, 4>();
-    wz_conv_lds_attrs<3, 4>();
-}
-
-// Default: the register-staged kernel (wz_k_conv_rs).  WZ_LDS_RS=0 selects the LDS-DMA kernel (two buffers), kept for
-// comparison; its deeper rings (WZ_LDS_NBUF 3/4) and its producer/consumer form are instantiated only with
-// -DWZ_LDS_VARIANTS=1 -- they measured no faster.
+// the register-staged tile kernel (k_conv_rs.h); the LDS-DMA form of the same tile it replaced is described in DESIGN.md section 5
 template <int KS, int NW>
 static void wz_launch_conv_lds(const WzConvArgs& a, dim3 grid, hipStream_t s) {
-    static const int rs = wz_env_int("WZ_LDS_RS", 1);
-    if (rs && wz_lds_spec())
-        WZ_LAUNCH((wz_k_conv_rs<KS, NW, true>), grid, dim3(512), 0, s, a);
-    else if (rs)
-        WZ_LAUNCH((wz_k_conv_rs<KS, NW, false>), grid, dim3(256), 0, s, a);
-    else
-        WZ_LAUNCH((wz_k_conv_lds<KS, NW, 2, false>), grid, dim3(256), 2 * WZ_LDS_BUF(NW), s, a);
+    WZ_LAUNCH((wz_k_conv_rs<KS, NW>), grid, dim3(256), 0, s, a);
 }
 
 void wz_launch_conv(const WzConvArgs& a0, hipStream_t s) {
@@ -936,8 +626,6 @@ void wz_launch_conv(const WzConvArgs& a0, hipStream_t s) {
         a.grid_m = (a.M + WZ_LDS_TM - 1) / WZ_LDS_TM;
         const int nw = wz_lds_nw(a.M, a.n_pad, a.kchunks);
         a.grid_n = (a.n_pad + WZ_LDS_TN(nw) - 1) / WZ_LDS_TN(nw);
-        static const int order = wz_env_int("WZ_LDS_ORDER", 0);
-        a.order = order;
         dim3 grid(a.grid_m * a.grid_n * a.splitk);
         if (nw == 4) {
             if (a.ksize == 1)
@@ -998,8 +686,6 @@ void wz_conv_group_add(WzConvGroup& g, const WzConvArgs& a) {
     g.first[i + 1] = g.first[i] + g.gx[i] * g.gy[i] * a.splitk;
     g.a[i].grid_m = g.gx[i];
     g.a[i].grid_n = g.gy[i];
-    g.a[i].tickets = g.tickets ? g.tickets + g.ticket_off : nullptr;   // one counter per wave tile
-    g.ticket_off += g.gx[i] * g.gy[i] * 4;
 }
 void wz_launch_conv_group(const WzConvGroup& g, hipStream_t s) {
     WZ_LAUNCH(wz_k_conv_group, dim3(g.first[g.n]), dim3(256), 0, s, g);
@@ -1007,8 +693,7 @@ void wz_launch_conv_group(const WzConvGroup& g, hipStream_t s) {
 
 // the convolutions wz_launch_conv would give to wz_k_conv_rs<3, 4>
 bool wz_conv_rs_groupable(const WzConvArgs& a) {
-    static const int rs = wz_env_int("WZ_LDS_RS", 1);
-    return rs && !wz_lds_spec() && a.ksize == 3 && wz_conv_use_lds(a);
+    return a.ksize == 3 && wz_conv_use_lds(a);
 }
 // Returns the number of entries added (0: the group is full).  A head whose packed columns are an odd number of 64-column
 // tiles (BoxPredictor_0: 320 = 2 x 128 + 64, BoxPredictor_1: 576 = 4 x 128 + 64) goes in as TWO entries -- the 128-column
@@ -1027,12 +712,9 @@ int wz_conv_rs_group_add(WzConvGroup& g, const WzConvArgs& a0) {
         a.grid_m = (a.M + WZ_LDS_TM - 1) / WZ_LDS_TM;
         a.nt_base = (two && part == 1) ? (a.n_pad / 128) * 8 : 0;
         a.grid_n = two ? (part == 0 ? a.n_pad / 128 : 1) : (a.n_pad + WZ_LDS_TN(nw) - 1) / WZ_LDS_TN(nw);
-        a.order = 0;
         g.gx[i] = pnw;
         g.gy[i] = 0;
         g.first[i + 1] = g.first[i] + ((a.grid_m * a.grid_n * a.splitk + 7) & ~7);   // entries start on an XCD boundary
-        a.tickets = g.tickets ? g.tickets + g.ticket_off : nullptr;                  // one counter per workgroup tile
-        g.ticket_off += a.grid_m * a.grid_n;
     }
     return two ? 2 : 1;
 }

@@ -3,10 +3,11 @@
 #include "wz_common.h"
 
 // --------------------------------------------------------------------------------------------
-// Register-staged variant of the LDS-tiled implicit GEMM (same tile, same XCD-aware order, same LDS image of the
-// activations).  Why: the `global_load_lds` path measured ~16 bytes per clock per CU no matter how it was driven (more
-// buffers in flight, dedicated producer waves, full-line sources -- tools/conv_probe.py), i.e. ~2 000 cycles for the
-// 32 KiB of a K step against 512 cycles of MFMA.  Here nothing goes through the DMA engine:
+// Register-staged LDS-tiled implicit GEMM: workgroup = 128 pixels x 64 or 128 channels, K step = 64 (two MFMA K chunks),
+// XCD-aware tile order, the activation tile in LDS as full 128-byte pixel lines with a chunk swizzle.  It replaced a form of
+// the same tile that staged both operands by `global_load_lds` DMA: that path measured ~16 bytes per clock per CU no matter
+// how it was driven (more buffers in flight, dedicated producer waves, full-line sources), i.e. ~2 000 cycles for the 32 KiB
+// of a K step against 512 cycles of MFMA.  Here nothing goes through the DMA engine:
 //   * waves are laid out 1 (pixels) x 4 (channels): a wave owns NW/2 channel tiles for all 128 pixels, so its weight
 //     fragments are needed by no other wave -- they are loaded straight into VGPRs (the packed layout IS fragment order:
 //     one coalesced 1 KiB load per fragment), two K steps ahead, and never touch LDS;
@@ -27,12 +28,9 @@ typedef __attribute__((ext_vector_type(4))) unsigned int uint4_t;
 // k_f32.hip).  At 32 cycles per MFMA a step is 4 096 cycles of matrix work: this variant IS MFMA-bound.
 // EPI: static `apply(a, m, n4, v)` (final epilogue) and `partials(a)` (fp32 split-K workspace).
 
-// SPEC: eight waves; 0..3 only compute (and fetch their own weight fragments), 4..7 only move the activation tile
-// (global -> VGPR -> LDS).  A wave issues in order, so with four waves the ~1 000 cycles of loads, waits and LDS writes
-// of a step sit in front of its ~750 cycles of fragment reads and MFMAs; split over two waves per SIMD they overlap.
 // L = index of this workgroup within the convolution's own grid (blockIdx.x, or blockIdx.x minus the entry's first
 // workgroup in a grouped launch, where entries start at multiples of 8 so that L & 7 is still the XCD).
-template <int KS, int NW, bool SPEC, bool F32, class EPI>
+template <int KS, int NW, bool F32, class EPI>
 __device__ __forceinline__ void wz_conv_rs_body(const WzConvArgs& a, unsigned char* smem, const int L) {
     constexpr int EB = F32 ? 4 : 2;   // bytes per element
     constexpr int taps = KS * KS;
@@ -40,18 +38,16 @@ __device__ __forceinline__ void wz_conv_rs_body(const WzConvArgs& a, unsigned ch
     constexpr unsigned OOB = 0x7ffffff0u;   // buffer offset beyond every tensor: the load returns zeros
     const int n_tiles = a.n_pad >> 4;
     const int lane = threadIdx.x & 63;
-    const int wave8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // provably wave-uniform
-    const int wave = wave8 & 3;
-    const bool mover = !SPEC || wave8 >= 4, worker = !SPEC || wave8 < 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // provably wave-uniform
     const int r16 = lane & 15, g = lane >> 4;
     int bx, by, bz;
-    {   // XCD-aware tile order, as in wz_k_conv_lds
+    {   // XCD-aware tile order: workgroup L runs on XCD L % 8 (each XCD has its own L2); renumbered so that the workgroups of
+        // one XCD are consecutive tiles, pixel tile fastest -- the tiles that stream the same weight slice share one L2
         const int total = a.grid_m * a.grid_n * a.splitk;
         if (L >= total) return;   // padding workgroup of a grouped launch
         const int xcd = L & 7, slot = L >> 3;
         const int qd = total >> 3, rm = total & 7;
-        int V = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + slot;
-        if (a.order == 1) V = L;
+        const int V = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + slot;
         bx = V % a.grid_m;
         const int rest = V / a.grid_m;
         by = rest % a.grid_n;
@@ -175,121 +171,42 @@ __device__ __forceinline__ void wz_conv_rs_body(const WzConvArgs& a, unsigned ch
     half8_t fa0[NTW][2], fa1[NTW][2];
     const int last = s1 - 1, pairs = (s1 - s0) >> 1;
     if (s0 < s1) {
-        if (mover) {
-            load_b(s0, rb);
-            store_b(0, rb);
-            load_b(min(s0 + 1, last), rb);
-        }
-        if (worker) {
-            load_a(s0, fa0);
-            load_a(min(s0 + 1, last), fa1);
-        }
+        load_b(s0, rb);
+        store_b(0, rb);
+        load_b(min(s0 + 1, last), rb);
+        load_a(s0, fa0);
+        load_a(min(s0 + 1, last), fa1);
         __syncthreads();
         int s = s0;
         // phase cycle counts for tools/rs_probe.py: compiled in only with -DWZ_RS_STAMPS=1 (they cost registers)
-        const bool stamp = WZ_RS_STAMPS && a.dbg && (threadIdx.x & 255) == 0 && L == 0;
+        const bool stamp = WZ_RS_STAMPS && a.dbg && threadIdx.x == 0 && L == 0;
         long long cy[5] = {0, 0, 0, 0, 0};
         for (int p = 0; p < pairs; ++p, s += 2) {
             const long long c0 = stamp ? clock64() : 0;
-            long long c1 = c0, c2 = c0, c3 = c0;
-            if (mover) {
-                store_b(1, rb);   // buffer 1 was last read before the previous barrier
-                c1 = stamp ? clock64() : 0;
-                load_b(min(s + 2, last), rb);
-                c2 = c3 = stamp ? clock64() : 0;
-            }
-            if (worker) {
-                if (SPEC) c1 = c2 = stamp ? clock64() : 0;
-                compute(0, fa0);
-                c3 = stamp ? clock64() : 0;
-                load_a(min(s + 2, last), fa0);
-            }
+            store_b(1, rb);   // buffer 1 was last read before the previous barrier
+            const long long c1 = stamp ? clock64() : 0;
+            load_b(min(s + 2, last), rb);
+            const long long c2 = stamp ? clock64() : 0;
+            compute(0, fa0);
+            const long long c3 = stamp ? clock64() : 0;
+            load_a(min(s + 2, last), fa0);
             const long long c4 = stamp ? clock64() : 0;
             __syncthreads();
             if (stamp) {
                 const long long c5 = clock64();
                 cy[0] += c1 - c0; cy[1] += c2 - c1; cy[2] += c3 - c2; cy[3] += c4 - c3; cy[4] += c5 - c4;
             }
-            if (mover) {
-                store_b(0, rb);
-                load_b(min(s + 3, last), rb);
-            }
-            if (worker) {
-                compute(1, fa1);
-                load_a(min(s + 3, last), fa1);
-            }
+            store_b(0, rb);
+            load_b(min(s + 3, last), rb);
+            compute(1, fa1);
+            load_a(min(s + 3, last), fa1);
             __syncthreads();
         }
-        if (worker && ((s1 - s0) & 1)) compute(0, fa0);
+        if ((s1 - s0) & 1) compute(0, fa0);
         if (stamp && pairs > 0) {
-            unsigned long long* const d = a.dbg + (threadIdx.x == 0 ? 0 : 8);   // slots 8.. = a mover wave
 #pragma unroll
-            for (int i = 0; i < 5; ++i) d[i] = (unsigned long long)(cy[i] / pairs);
-            d[5] = (unsigned long long)pairs;
-        }
-    }
-    if (!worker) return;
-
-    if constexpr (!SPEC && !F32) {
-        if (a.splitk > 1 && a.inline_reduce) {
-            // in-launch reduction (WzConvArgs::inline_reduce): every K slice publishes its partial tile write-through and
-            // takes a ticket on the tile's counter; the workgroup that finds the other slices already there sums them
-            // all in slice order (wz_k_splitk_reduce's arithmetic: bit-identical) and finishes the head's outputs
-            float* const ws = a.ws;   // (a.out is where the FINISHED columns go)
-#pragma unroll
-            for (int mt = 0; mt < 8; ++mt) {
-                const int m = m_base + mt * 16 + r16;
-#pragma unroll
-                for (int nt = 0; nt < NTW; ++nt) {
-                    const int n4 = (nt_w + nt) * 16 + g * 4;
-                    if (m < a.M && n4 < a.n_pad) EPI::publish(ws + ((size_t)bz * a.M + m) * a.n_pad + n4, acc[mt][nt]);
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();                       // every wave's stores have landed (and nobody reads the LDS tiles any more)
-            int* const flag = reinterpret_cast<int*>(smem);
-            if (threadIdx.x == 0) {
-                int32_t* const tk = a.tickets + (by * a.grid_m + bx);
-                const int t = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (t == a.splitk - 1) {
-                    __hip_atomic_store(tk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                        // this CU reads the slabs fresh
-                }
-                *flag = t;
-            }
-            __syncthreads();
-            if (*flag != a.splitk - 1) return;
-            // slice by slice, all of a slice's fragments requested before the first is added (one memory latency per
-            // slice, not per fragment); the sum order per element is slice 0, 1, 2 ... as in wz_k_splitk_reduce
-#pragma unroll
-            for (int mt = 0; mt < 8; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < NTW; ++nt) acc[mt][nt] = (float4_t){0.f, 0.f, 0.f, 0.f};
-            for (int z = 0; z < a.splitk; ++z) {
-                float4_t pz[8][NTW];
-#pragma unroll
-                for (int mt = 0; mt < 8; ++mt) {
-                    const int m = m_base + mt * 16 + r16;
-#pragma unroll
-                    for (int nt = 0; nt < NTW; ++nt) {
-                        const int n4 = (nt_w + nt) * 16 + g * 4;
-                        pz[mt][nt] = (m < a.M && n4 < a.n_pad)
-                                         ? *reinterpret_cast<const float4_t*>(ws + ((size_t)z * a.M + m) * a.n_pad + n4)
-                                         : (float4_t){0.f, 0.f, 0.f, 0.f};
-                    }
-                }
-#pragma unroll
-                for (int mt = 0; mt < 8; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < NTW; ++nt)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) acc[mt][nt][r] += pz[mt][nt][r];
-            }
-#pragma unroll
-            for (int mt = 0; mt < 8; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < NTW; ++nt) EPI::finish(a, m_base + mt * 16 + r16, (nt_w + nt) * 16 + g * 4, acc[mt][nt]);
-            return;
+            for (int i = 0; i < 5; ++i) a.dbg[i] = (unsigned long long)(cy[i] / pairs);
+            a.dbg[5] = (unsigned long long)pairs;
         }
     }
 

@@ -7,12 +7,12 @@
 // 544 cycles of MFMA -- three pipes loaded alike, executed one after the other by four waves that run in lockstep between
 // barriers (measured 1 750 cycles per step, profiles/r01zy_*): 0.2 of the MFMA peak, at any batch size
 // (profiles/r02v_batch_sweep.txt).  The operand traffic per MFMA falls with the number of channels a wave owns:
-//   * here a wave owns 128 pixels x 80 channels (five 16-channel tiles; accumulators: 160 registers, the kernel runs one
-//     wave per SIMD with the unified 512-register file): 80 MFMAs (1 280 cycles) per 16 KiB of LDS reads -- LDS 512,
-//     vector memory <= 900 (16 KiB activations + <= 40 KiB weights), MFMA 1 280 cycles per workgroup step;
-//     -- since round 5 the DEFAULT is the same body with THREE tiles per wave (wz_k_conv_wide_group3: 96 accumulator registers, 248 in all, two
-//     workgroups per CU and two waves per SIMD that cover each other's barrier waits): 48 MFMAs per 16 KiB of LDS reads, 1.5 - 2 x the activation
-//     tiles through LDS, and a launch that is 27 % shorter (38.0 -> 27.9 us at batch 8) -- see wz_conv_wide_ntw() below;
+//   * here a wave owns 128 pixels x 48 channels (three 16-channel tiles: 96 accumulator registers, 248 in all, two workgroups per
+//     CU and two waves per SIMD that cover each other's barrier waits): 48 MFMAs per 16 KiB of LDS reads.  Rounds 2 .. 4 ran
+//     the same body with FIVE tiles per wave (160 accumulator registers, one wave per SIMD, 80 MFMAs per 16 KiB of LDS reads);
+//     the three-tile form's launch is 27 % shorter alone (38.0 -> 27.9 us at batch 8) and frames/s with four lanes in flight
+//     were equal (47.7 - 47.8 k both ways, profiles/r05_heads_three_tiles_per_wave.txt), so only it is built -- see
+//     wz_k_conv_wide_group3 below;
 //   * and the step is software-pipelined in two halves (the two 32-channel MFMA K chunks of the step): while the MFMAs
 //     of one half run, the LDS fragment reads of the next half, the LDS write of the next step's activations and the
 //     global loads of the step after are in flight.  One `s_barrier` per step, preceded by `lgkmcnt(0)` only: the weight
@@ -21,9 +21,9 @@
 // a wave's fragments are needed by no other wave), activations global -> VGPR -> LDS in full 128-byte lines through a
 // buffer descriptor (out-of-frame taps read zeros), same XOR-swizzled LDS image (conflict-free fragment reads), same
 // K order (channel pair outermost, tap innermost), same XCD-aware tile order.
-// Output: fp32 partial sums for wz_k_splitk_reduce_group, in fragment order [K slice][M / 16][n_pad / 16][64 lanes][4] (WzConvArgs::frag_ws;
-// [K slice][M][n_pad] without it) -- always, also with one K slice: this
-// kernel only serves the heads, whose epilogue (bias, scatter, box decode, candidate marking) lives in that launch.
+// Output: fp32 partial sums for wz_k_splitk_reduce_group, in fragment order [K slice][M / 16][n_pad / 16][64 lanes][4] (WzConvArgs::frag_ws)
+// -- always, also with one K slice: this kernel only serves the heads, whose epilogue (bias, scatter, box decode, candidate marking) lives in
+// that launch.
 #include "wz_common.h"
 
 typedef __attribute__((ext_vector_type(4))) unsigned int uint4_t;
@@ -328,32 +328,19 @@ __device__ __forceinline__ void wz_conv_wide_body(const WzConvArgs& a, unsigned 
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
+    // fragment order: an accumulator tile is 1 KiB in one piece (lane l's four values at l * 16) -- whole lines per store instruction, where
+    // [slice][pixel][column] order (tried first) makes sixteen 64-byte pieces of it, one per pixel row (the epilogue of a workgroup was 9.9 k
+    // cycles of a 65 k-cycle launch: profiles/r02zf_wide_heads_phase_cycles.txt).  The grouped reduce reads the fragments back the same way.
     float* const ws = reinterpret_cast<float*>(a.out);
-    if (a.frag_ws) {
-        // fragment order: an accumulator tile is 1 KiB in one piece (lane l's four values at l * 16) -- whole lines per store instruction, where
-        // [slice][pixel][column] order makes sixteen 64-byte pieces of it, one per pixel row (the epilogue of a workgroup was 9.9 k cycles
-        // of a 65 k-cycle launch: profiles/r02zf_wide_heads_phase_cycles.txt).  The grouped reduce reads the fragments back the same way.
-        const int mtt = (a.M + 15) >> 4, ntt = a.n_pad >> 4;
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) {
-            if (nt >= cnt) break;   // wave-uniform
-#pragma unroll
-            for (int mt = 0; mt < 8; ++mt) {
-                const int mtg = (m_base >> 4) + mt;
-                if (mtg < mtt) *reinterpret_cast<float4_t*>(ws + (((size_t)bz * mtt + mtg) * ntt + (nt_w + nt)) * 256 + lane * 4) = acc[mt][nt];
-            }
-        }
-    } else {
+    const int mtt = (a.M + 15) >> 4, ntt = a.n_pad >> 4;
 #pragma unroll
     for (int nt = 0; nt < NTW; ++nt) {
         if (nt >= cnt) break;   // wave-uniform
-        const int n4 = (nt_w + nt) * 16 + g * 4;
 #pragma unroll
         for (int mt = 0; mt < 8; ++mt) {
-            const int m = m_base + mt * 16 + r16;
-            if (m < a.M) *reinterpret_cast<float4_t*>(ws + ((size_t)bz * a.M + m) * a.n_pad + n4) = acc[mt][nt];
+            const int mtg = (m_base >> 4) + mt;
+            if (mtg < mtt) *reinterpret_cast<float4_t*>(ws + (((size_t)bz * mtt + mtg) * ntt + (nt_w + nt)) * 256 + lane * 4) = acc[mt][nt];
         }
-    }
     }
     if (WZ_WIDE_STAMPS) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -361,33 +348,18 @@ __device__ __forceinline__ void wz_conv_wide_body(const WzConvArgs& a, unsigned 
     }
 }
 
-__global__ __launch_bounds__(256, 1) void wz_k_conv_wide_group(const WzConvGroup g) {
+// THREE channel tiles per wave (128 pixels x up to 192 channels per workgroup, WZ_WIDE_TILES) at <= 256 registers: two workgroups share a CU,
+// two waves a SIMD.  The five-tile form of rounds 2 .. 4 did more matrix work per LDS byte (80 against 48 MFMAs per 16 KiB of fragment reads);
+// what this form is for is the four-lane case: a 344-register workgroup needs a WHOLE free CU and, with three other lanes' workgroups scattered
+// over the chip, waits for one (the launch takes 55 us under load against 26.5 us alone: profiles/r05zz_lane_overlap_robust.txt), a 256-register
+// one moves in beside whatever holds the other half.  Since round 5: the heads' launch 38.0 -> 27.9 us alone, a lone batch of eight
+// 0.391 -> 0.379 ms, frames/s with four lanes unchanged (profiles/r05_heads_three_tiles_per_wave.txt).
+__global__ __launch_bounds__(256, 2) void wz_k_conv_wide_group3(const WzConvGroup g) {
     WZ_LANE_STAMP(g.stamp);
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 16384 + WZ_WIDE_TM * 8];   // two activation tiles + the pixel table
     int e = 0;
     while (e + 1 < g.n && (int)blockIdx.x >= g.first[e + 1]) ++e;   // wave-uniform
-    wz_conv_wide_body<3, 5>(g.a[e], smem, (int)blockIdx.x - g.first[e]);
-}
-
-// The same body with THREE channel tiles per wave (128 pixels x up to 192 channels per workgroup) at <= 256 registers: two workgroups share a
-// CU, two waves a SIMD (round 5; WZ_WIDE_NTW=3).  Alone the five-tile form does more matrix work per LDS byte (80 against 48 MFMAs per 16 KiB of fragment
-// reads); what this form is for is the four-lane case: a 344-register workgroup needs a WHOLE free CU and, with three other lanes' workgroups scattered over
-// the chip, waits for one (the launch takes 55 us under load against 26.5 us alone: profiles/r05zz_lane_overlap_robust.txt), a 256-register one moves in
-// beside whatever holds the other half.
-__global__ __launch_bounds__(256, 2) void wz_k_conv_wide_group3(const WzConvGroup g) {
-    WZ_LANE_STAMP(g.stamp);
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 16384 + WZ_WIDE_TM * 8];
-    int e = 0;
-    while (e + 1 < g.n && (int)blockIdx.x >= g.first[e + 1]) ++e;   // wave-uniform
-    wz_conv_wide_body<3, 3>(g.a[e], smem, (int)blockIdx.x - g.first[e]);
-}
-
-// channel tiles per wave of the build in use (5: one workgroup per CU; 3: two) -- the workgroup's tile is four times that
-int wz_conv_wide_ntw() {
-    // default 3 since round 5: the heads' launch 38.0 -> 27.9 us alone, a lone batch of eight 0.391 -> 0.379 ms, frames/s with four lanes unchanged
-    // (47.7 - 47.8 k both ways; under load the launch takes ~55 us either way: profiles/r05_heads_three_tiles_per_wave.txt).  WZ_WIDE_NTW=5: the round-2 .. 4 build.
-    static const int ntw = [] { const char* e = wz_dev_getenv("WZ_WIDE_NTW"); const int v = (e && e[0]) ? atoi(e) : 3; return v == 5 ? 5 : 3; }();
-    return ntw;
+    wz_conv_wide_body<3, WZ_WIDE_TILES / 4>(g.a[e], smem, (int)blockIdx.x - g.first[e]);
 }
 
 // 3x3 heads with a K loop worth tiling (the conditions of the LDS-tiled kernels); the engine's WZ_CONV_WIDE=0 gives them back to
@@ -402,8 +374,7 @@ bool wz_conv_wide_applies(const WzConvArgs& a) {
 
 void wz_conv_wide_shape(const WzConvArgs& a, int* tiles, int* steps) {
     const int live = (a.cout + 15) >> 4;
-    const int per = 4 * wz_conv_wide_ntw();
-    const int groups = (live + per - 1) / per;
+    const int groups = (live + WZ_WIDE_TILES - 1) / WZ_WIDE_TILES;
     *tiles = ((a.M + WZ_WIDE_TM - 1) / WZ_WIDE_TM) * groups;
     *steps = a.kchunks >> 1;
 }
@@ -442,7 +413,7 @@ int wz_conv_wide_group_add(WzConvGroup& g, const WzConvArgs& a0) {
     WzConvArgs& a = g.a[i];
     a = a0;
     a.nt_live = (a.cout + 15) >> 4;
-    a.grid_n = (a.nt_live + 4 * wz_conv_wide_ntw() - 1) / (4 * wz_conv_wide_ntw());
+    a.grid_n = (a.nt_live + WZ_WIDE_TILES - 1) / WZ_WIDE_TILES;
     a.nt_group = (a.nt_live + a.grid_n - 1) / a.grid_n;
     a.grid_m = (a.M + WZ_WIDE_TM - 1) / WZ_WIDE_TM;
     g.gx[i] = g.gy[i] = 0;
@@ -451,8 +422,5 @@ int wz_conv_wide_group_add(WzConvGroup& g, const WzConvArgs& a0) {
 }
 
 void wz_launch_conv_wide_group(const WzConvGroup& g, hipStream_t s) {
-    if (wz_conv_wide_ntw() == 3)
-        WZ_LAUNCH(wz_k_conv_wide_group3, dim3(g.first[g.n]), dim3(256), 0, s, g);
-    else
-        WZ_LAUNCH(wz_k_conv_wide_group, dim3(g.first[g.n]), dim3(256), 0, s, g);
+    WZ_LAUNCH(wz_k_conv_wide_group3, dim3(g.first[g.n]), dim3(256), 0, s, g);
 }

@@ -373,7 +373,7 @@ struct WzEpiF32 {
 template <int KS, int NW>
 __global__ __launch_bounds__(256, 2) void wz_k_conv_rs_f32(const WzConvArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 16384];
-    wz_conv_rs_body<KS, NW, false, true, WzEpiF32>(a, smem, blockIdx.x);
+    wz_conv_rs_body<KS, NW, true, WzEpiF32>(a, smem, blockIdx.x);
 }
 
 // whole 64-column tiles, whole 32-channel K steps, enough pixels and a K loop long enough to pay for the tile
@@ -403,7 +403,6 @@ void wz_launch_conv_f32(const WzConvArgs& a0, hipStream_t s, bool reduce) {
         const int nw = wz_lds_nw(a.M, a.n_pad, a.kchunks);
         a.grid_m = (a.M + WZ_RS_TM - 1) / WZ_RS_TM;
         a.grid_n = (a.n_pad + nw * 32 - 1) / (nw * 32);
-        a.order = 0;
         const dim3 grid(a.grid_m * a.grid_n * a.splitk);
         if (nw == 4) {
             if (a.ksize == 1)

@@ -9,12 +9,13 @@
 // score and keeps max_total.  A candidate's fate depends only on higher-scored boxes of its own class,
 // so walking ALL (anchor, class) candidates once in global order (score desc, class asc, anchor asc),
 // suppressing only against kept boxes of the same class and stopping at max_total kept, yields exactly
-// the same rows.  The walk needs the head of that order only: a 1024-bin histogram of the score bits
-// picks a threshold that admits >= WZ_CAND_TARGET candidates, they are compacted, bitonic-sorted in LDS
-// and walked by one wavefront (lanes = already kept boxes, `__any` = "suppressed").  If that head is
-// exhausted before max_total rows are kept (or the threshold bin overflows WZ_CAND_CAP) the kernel
-// continues with an exact, slower "next best candidate below the bound" scan, so the result never
-// depends on the tuning constants.
+// the same rows.  The walk needs the head of that order only: one workgroup per frame collects the
+// candidates of a band of score bins (the top 12 bits of the score) into an LDS list, sorts and walks
+// it (wz_k_nms), and reaches further down band by band until max_total rows are kept; a band that
+// overflows WZ_CAND_CAP is narrowed, down to one bin, which then takes an exact, slower "next best
+// candidate below the bound" scan -- so the result never depends on the tuning constants.  (The
+// first form put a 1024-bin histogram kernel and a compaction kernel, two 256-CU scans, in front of
+// the walk: DESIGN.md section 5.)
 //
 // All comparisons the result depends on (score order, IoU > thr, area > 0, truncation) use fp32/fp64
 // operations rounded once each in the oracle's order: contraction is disabled for this file.
@@ -28,11 +29,6 @@ __device__ __forceinline__ float wz_sigmoid(float x) { return 1.0f / (1.0f + exp
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void wz_k_decode(WzPostBuffers b, WzPostConsts k, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    // first kernel of the post-processing chain: it also clears the per-frame histogram, candidate count and band
-    // record (num_anchors > WZ_HIST_BINS threads per frame exist) -- one launch less than a memset node
-    if (i < n * WZ_HIST_BINS) b.hist[i] = 0u;
-    if (i < n) b.count[i] = 0u;
-    if (i < 2 * n) b.band[i] = 0u;
     if (i >= n * k.num_anchors) return;
     const int a = i % k.num_anchors;
     const float4_t e = *reinterpret_cast<const float4_t*>(b.box_enc + (size_t)i * 4);
@@ -69,128 +65,6 @@ __device__ __forceinline__ bool wz_candidate(const WzPostBuffers& b, const WzPos
     key = __float_as_uint(s);
     tie = (uint32_t)(col - 1) * (uint32_t)k.num_anchors + (uint32_t)a;   // class asc, then anchor asc
     return true;
-}
-
-// Entries per thread of the two scans over the 1917 x 91 class logits (measured: 32 per thread, i.e. 22 fat
-// workgroups per frame, triples both kernels' time -- the scans want every CU).
-#ifndef POST_ITEMS
-#define POST_ITEMS 8
-#endif
-#ifndef COMPACT_ITEMS
-#define COMPACT_ITEMS 8    // (16 per thread measured slower: 15 vs 11 us)
-#endif
-#define POST_LIST 1024   // candidates one workgroup stages in LDS before publishing them (more go straight to HBM)
-__global__ __launch_bounds__(256) void wz_k_hist(WzPostBuffers b, WzPostConsts k) {
-    __shared__ uint32_t h[WZ_HIST_BINS];
-    for (int i = threadIdx.x; i < WZ_HIST_BINS; i += 256) h[i] = 0;
-    __syncthreads();
-    const int f = blockIdx.y, total = k.num_anchors * k.num_classes;
-    const int base = blockIdx.x * 256 * POST_ITEMS;
-#pragma unroll 4
-    for (int it = 0; it < POST_ITEMS; ++it) {
-        const int j = base + it * 256 + threadIdx.x;
-        uint32_t key, tie;
-        if (j < total && wz_candidate(b, k, f, j, key, tie)) atomicAdd(&h[key >> 20], 1u);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < WZ_HIST_BINS; i += 256)
-        if (h[i]) atomicAdd(&b.hist[(size_t)f * WZ_HIST_BINS + i], h[i]);
-}
-
-// threshold bin: the largest b < hi with (number of candidates in bins [b, hi)) >= target, else 0;
-// *total_out = candidates in bins [0, hi).
-// Called by every thread of the block (blockDim.x in {256, 1024}); `sh` = 64 uint32 of LDS scratch.
-// Thread t owns bins [t*per, (t+1)*per); suffix sums run across lanes (shuffles) and waves (LDS).
-__device__ int wz_threshold_bin(const uint32_t* __restrict__ ghist, uint32_t* sh, uint32_t target,
-                                uint32_t* total_out, int hi = WZ_HIST_BINS) {
-    const int nth = blockDim.x, per = WZ_HIST_BINS / nth;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = nth >> 6;
-    uint32_t v[4] = {0, 0, 0, 0};
-    uint32_t sum = 0;
-    for (int i = 0; i < per; ++i) {
-        v[i] = (tid * per + i < hi) ? ghist[tid * per + i] : 0u;   // bins >= hi are already consumed
-        sum += v[i];
-    }
-    uint32_t s = sum;   // -> sum over lanes >= lane of this wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t x = __shfl_down(s, o);
-        if (lane + o < 64) s += x;
-    }
-    if (lane == 0) sh[wave] = s;
-    if (tid == 0) sh[32] = 0;
-    __syncthreads();
-    uint32_t higher = 0, total = 0;
-    for (int w = 0; w < nw; ++w) {
-        total += sh[w];
-        if (w > wave) higher += sh[w];
-    }
-    uint32_t run = s + higher - sum;   // candidates in bins above this thread's bins
-    int best = -1;
-    for (int i = per - 1; i >= 0; --i) {
-        run += v[i];
-        if (run >= target) {
-            best = tid * per + i;
-            break;
-        }
-    }
-    if (best >= 0) atomicMax(&sh[32], (uint32_t)(best + 1));
-    __syncthreads();
-    if (total_out) *total_out = total;
-    const uint32_t r = sh[32];
-    __syncthreads();
-    return r ? (int)r - 1 : 0;
-}
-
-__global__ __launch_bounds__(256) void wz_k_compact(WzPostBuffers b, WzPostConsts k) {
-    __shared__ uint32_t sh[64];
-    __shared__ uint32_t s_cnt, s_base;
-    const int f = blockIdx.y, total = k.num_anchors * k.num_classes;
-    if (threadIdx.x == 0) s_cnt = 0;
-    // the scan's loads go out first: they land while the threshold bin is being derived from the histogram (two
-    // barriers and a dependent chain of its own)
-    const int base = blockIdx.x * 256 * COMPACT_ITEMS;
-    float lg[COMPACT_ITEMS];
-    bool live[COMPACT_ITEMS];
-#pragma unroll
-    for (int it = 0; it < COMPACT_ITEMS; ++it) {
-        const int j = base + it * 256 + threadIdx.x;
-        const int a = j / k.num_classes, col = j - a * k.num_classes;
-        live[it] = j < total && col != 0 && b.valid[(size_t)f * k.num_anchors + a];
-        lg[it] = live[it] ? b.logits[(size_t)f * total + j] : 0.0f;
-    }
-    uint32_t all = 0;
-    const uint32_t thr = (uint32_t)wz_threshold_bin(b.hist + (size_t)f * WZ_HIST_BINS, sh, WZ_CAND_TARGET, &all);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {   // every block computes the same band; one publishes it for wz_k_nms
-        b.band[2 * f] = thr;
-        b.band[2 * f + 1] = all;
-    }
-    __shared__ uint2 s_list[POST_LIST];
-#pragma unroll
-    for (int it = 0; it < COMPACT_ITEMS; ++it) {
-        const int j = base + it * 256 + threadIdx.x;
-        const float sc = wz_sigmoid(lg[it]);                  // exactly wz_candidate()'s arithmetic
-        const uint32_t key = __float_as_uint(sc);
-        if (live[it] && sc > k.score_thr && (key >> 20) >= thr) {
-            const int a = j / k.num_classes, col = j - a * k.num_classes;
-            const uint32_t tie = (uint32_t)(col - 1) * (uint32_t)k.num_anchors + (uint32_t)a;
-            const uint32_t p = atomicAdd(&s_cnt, 1u);     // LDS atomic: order is irrelevant, the list gets sorted
-            if (p < POST_LIST) {
-                s_list[p] = make_uint2(key, tie);
-            } else {                                      // a dense band: publish this one directly
-                const uint32_t q = atomicAdd(&b.count[f], 1u);
-                if (q < WZ_CAND_CAP) b.cand[(size_t)f * WZ_CAND_CAP + q] = make_uint2(key, tie);
-            }
-        }
-    }
-    __syncthreads();
-    const uint32_t n_list = min(s_cnt, (uint32_t)POST_LIST);
-    if (threadIdx.x == 0 && n_list) s_base = atomicAdd(&b.count[f], n_list);   // one global atomic per block
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < n_list; i += 256) {
-        const uint32_t p = s_base + i;
-        if (p < WZ_CAND_CAP) b.cand[(size_t)f * WZ_CAND_CAP + p] = s_list[i];
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -819,7 +693,7 @@ __device__ int wz_nms_band_serial(NmsShared* S, const WzPostBuffers& b, const Wz
 __device__ void wz_make_row(const WzFrameDesc& fd, const WzCamFilter* __restrict__ cams, bool on, const float4_t bx,
                             float score, int label, wz_detection_t* __restrict__ row, uint8_t* __restrict__ pass);
 
-// Self-scan mode: one pass of the frame's workgroup over its 1917 x 91 logits collects the candidates of a band of score
+// Candidate selection: one pass of the frame's workgroup over its 1917 x 91 logits collects the candidates of a band of score
 // bins [lo, hi) into the LDS list -- no histogram, no compaction kernel, no 256-CU launches in front of the walk.
 //   * A logit below `logit_floor(lo)` cannot reach bin lo (sigmoid is monotone; the floor is lowered by a margin four
 //     orders of magnitude above its rounding error), so all but a few hundred entries cost one load and one compare;
@@ -897,21 +771,20 @@ __device__ uint32_t wz_nms_scan_band(NmsShared* S, const WzPostBuffers& b, const
 // uses a slot of its class, but is no row --, then the kept boxes are clipped and the first max_total that still have an area are
 // the rows.  `status[f]` = 1 if the kept list filled up before max_total rows with an area were found (more than
 // NMS_KEEP_MAX - max_total selected boxes entirely outside the image: the frame's rows may be short; wz_collect reports it).
-// SELF / CLIP: the two run-time modes as template parameters (`self_scan`, WzPostConsts::clip_after): one copy of the band walk per
-// kernel instead of four inlined ones -- the kernel lives at 128 registers (1024 threads) and spills; what is not there cannot.
-template <bool SELF, bool CLIP, bool COUNT>
+// CLIP / COUNT: run-time modes as template parameters (WzPostConsts::clip_after, a per-class cap that can bind): one copy of the band
+// walk per kernel instead of inlined alternatives -- the kernel lives at 128 registers (1024 threads) and spills; what is not there cannot.
+template <bool CLIP, bool COUNT>
 __global__ __launch_bounds__(NMS_THREADS) void wz_k_nms(WzPostBuffers b, WzPostConsts kc,
                                                         const WzFrameDesc* __restrict__ frames,
                                                         const WzCamFilter* __restrict__ cams,
                                                         wz_detection_t* __restrict__ rows, uint8_t* __restrict__ pass,
-                                                        int self_scan, int listed, uint32_t* __restrict__ status) {
+                                                        int listed, uint32_t* __restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     NmsShared* S = reinterpret_cast<NmsShared*>(smem);
     const int f = blockIdx.x, tid = threadIdx.x;
     const int out_total = kc.max_total;
     WzPostConsts k = kc;
     if (CLIP) k.max_total = NMS_KEEP_MAX;                    // the walk's "enough" (and the kept list's capacity)
-    const int A = k.num_anchors;
 #define NMS_STAMP(i) do { if (tid == 0) b.dbg[(size_t)f * 16 + (i)] = wall_clock64(); } while (0)
     NMS_STAMP(0);
 #if WZ_LANE_STAMPS
@@ -948,159 +821,108 @@ __global__ __launch_bounds__(NMS_THREADS) void wz_k_nms(WzPostBuffers b, WzPostC
     uint32_t processed = 0;
     int kept = 0;
     if (tid == 0) S->kept = 0;
-    if constexpr (SELF) {
-        // the bit map of the listed candidates is requested before anything else: with the hint, the logits and the
-        // validity bytes behind it the first band is a chain of global-memory latencies (~2 us each on a busy chip)
-        constexpr int WPT = 8;                               // words per thread (the launcher checks that this covers the map)
-        uint32_t mw[WPT];
-        {
-            const int words = (k.num_anchors * k.num_classes + 31) >> 5;
+    // the bit map of the listed candidates is requested before anything else: with the hint, the logits and the
+    // validity bytes behind it the first band is a chain of global-memory latencies (~2 us each on a busy chip)
+    constexpr int WPT = 8;                               // words per thread (the launcher checks that this covers the map)
+    uint32_t mw[WPT];
+    {
+        const int words = (k.num_anchors * k.num_classes + 31) >> 5;
+#pragma unroll
+        for (int u = 0; u < WPT; ++u) {
+            const int w = tid + u * NMS_THREADS;
+            mw[u] = (listed && w < words) ? b.cbits[(size_t)f * words + w] : 0u;
+        }
+    }
+    NMS_STAMP(1);
+    int hi_bin = WZ_HIST_BINS;
+    int lo_bin = min((int)b.hint[f], WZ_HIST_BINS - 1);
+    int reach = 4;                                     // bins the next band extends below the current one
+    uint32_t first_cnt = 0;
+    int first_lo = lo_bin;
+    bool first = true;
+    for (;;) {
+        uint32_t cnt;
+        if (first && listed) {
+            // the grouped head reduce marked every class logit >= wz_logit_floor(hint) of this frame while it still
+            // had it in registers: the first band [hint, 1024) needs no scan of the logits, only of the bit map
+            // (22 KiB per frame; read and cleared here).  Same tests as wz_nms_scan_band.
+            if (tid == 0) { S->ncand = 0; S->pad[0] = 0; }
+            __syncthreads();
+            const int C = k.num_classes, n_entries = k.num_anchors * C, words = (n_entries + 31) >> 5;
+            uint32_t* const bits = b.cbits + (size_t)f * words;   // (words <= WPT * NMS_THREADS: checked by the launcher)
+            const float* __restrict__ lg = b.logits + (size_t)f * n_entries;
+            // one listed entry: the tests of wz_nms_scan_band, the key into the band's list
+            auto take = [&](int j) {
+                const int a = j / C, col = j - a * C;
+                const float x = lg[j];                      // both loads issued before either is used
+                const uint8_t ok = b.valid[(size_t)f * k.num_anchors + a];
+                if (col == 0 || !ok) return;
+                const float sc = wz_sigmoid(x);
+                if (!(sc > k.score_thr)) return;
+                const uint32_t key = __float_as_uint(sc);
+                const int bin = (int)(key >> 20);
+                if (bin < lo_bin || bin >= hi_bin) return;
+                const uint32_t tie = (uint32_t)(col - 1) * (uint32_t)k.num_anchors + (uint32_t)a;
+                const uint32_t pos = atomicAdd(&S->ncand, 1u);
+                if (pos < WZ_CAND_CAP)
+                    S->keys[pos] = ((unsigned long long)key << 32) | (unsigned long long)(0xFFFFFFFFu - tie);
+            };
+            // Two passes since late round 6.  A thread that found several bits in its words used to walk them one after the other, a global round trip
+            // (logit + validity byte) each -- the slowest thread's chain was 2 - 4 of them (6 - 8 us).  Now the set bits are first written as entry numbers
+            // into LDS (the rank sort's destination buffer is idle here: 8 192 entries), then dealt out one per thread: ONE round trip for all of them.
+            // Which thread takes which entry changes nothing: the band's list is sorted on unique keys before anything reads it.
+            uint32_t* const elist = reinterpret_cast<uint32_t*>(S->keys2);
+            constexpr uint32_t ELIST_CAP = 2 * WZ_CAND_CAP;
 #pragma unroll
             for (int u = 0; u < WPT; ++u) {
                 const int w = tid + u * NMS_THREADS;
-                mw[u] = (listed && w < words) ? b.cbits[(size_t)f * words + w] : 0u;
-            }
-        }
-        NMS_STAMP(1);
-        int hi_bin = WZ_HIST_BINS;
-        int lo_bin = min((int)b.hint[f], WZ_HIST_BINS - 1);
-        int reach = 4;                                     // bins the next band extends below the current one
-        uint32_t first_cnt = 0;
-        int first_lo = lo_bin;
-        bool first = true;
-        for (;;) {
-            uint32_t cnt;
-            if (first && listed) {
-                // the grouped head reduce marked every class logit >= wz_logit_floor(hint) of this frame while it still
-                // had it in registers: the first band [hint, 1024) needs no scan of the logits, only of the bit map
-                // (22 KiB per frame; read and cleared here).  Same tests as wz_nms_scan_band.
-                if (tid == 0) { S->ncand = 0; S->pad[0] = 0; }
-                __syncthreads();
-                const int C = k.num_classes, n_entries = k.num_anchors * C, words = (n_entries + 31) >> 5;
-                uint32_t* const bits = b.cbits + (size_t)f * words;   // (words <= WPT * NMS_THREADS: checked by the launcher)
-                const float* __restrict__ lg = b.logits + (size_t)f * n_entries;
-                // one listed entry: the tests of wz_nms_scan_band, the key into the band's list
-                auto take = [&](int j) {
-                    const int a = j / C, col = j - a * C;
-                    const float x = lg[j];                      // both loads issued before either is used
-                    const uint8_t ok = b.valid[(size_t)f * k.num_anchors + a];
-                    if (col == 0 || !ok) return;
-                    const float sc = wz_sigmoid(x);
-                    if (!(sc > k.score_thr)) return;
-                    const uint32_t key = __float_as_uint(sc);
-                    const int bin = (int)(key >> 20);
-                    if (bin < lo_bin || bin >= hi_bin) return;
-                    const uint32_t tie = (uint32_t)(col - 1) * (uint32_t)k.num_anchors + (uint32_t)a;
-                    const uint32_t pos = atomicAdd(&S->ncand, 1u);
-                    if (pos < WZ_CAND_CAP)
-                        S->keys[pos] = ((unsigned long long)key << 32) | (unsigned long long)(0xFFFFFFFFu - tie);
-                };
-                // Two passes since late round 6.  A thread that found several bits in its words used to walk them one after the other, a global round trip
-                // (logit + validity byte) each -- the slowest thread's chain was 2 - 4 of them (6 - 8 us).  Now the set bits are first written as entry numbers
-                // into LDS (the rank sort's destination buffer is idle here: 8 192 entries), then dealt out one per thread: ONE round trip for all of them.
-                // Which thread takes which entry changes nothing: the band's list is sorted on unique keys before anything reads it.
-                uint32_t* const elist = reinterpret_cast<uint32_t*>(S->keys2);
-                constexpr uint32_t ELIST_CAP = 2 * WZ_CAND_CAP;
-#pragma unroll
-                for (int u = 0; u < WPT; ++u) {
-                    const int w = tid + u * NMS_THREADS;
-                    uint32_t m = mw[u];
-                    if (m) bits[w] = 0u;
-                    while (m) {
-                        const int j = w * 32 + __builtin_ctz(m);
-                        m &= m - 1;
-                        const uint32_t q = atomicAdd(reinterpret_cast<uint32_t*>(&S->pad[0]), 1u);
-                        if (q < ELIST_CAP) elist[q] = (uint32_t)j;
-                        else take(j);                               // (more listed entries than the buffer holds: the old way, nothing is lost)
-                    }
+                uint32_t m = mw[u];
+                if (m) bits[w] = 0u;
+                while (m) {
+                    const int j = w * 32 + __builtin_ctz(m);
+                    m &= m - 1;
+                    const uint32_t q = atomicAdd(reinterpret_cast<uint32_t*>(&S->pad[0]), 1u);
+                    if (q < ELIST_CAP) elist[q] = (uint32_t)j;
+                    else take(j);                               // (more listed entries than the buffer holds: the old way, nothing is lost)
                 }
-                __syncthreads();
-                const uint32_t nl = min((uint32_t)S->pad[0], ELIST_CAP);
-                for (uint32_t q = tid; q < nl; q += NMS_THREADS) take((int)elist[q]);
-                __syncthreads();
-                cnt = S->ncand;
-                __syncthreads();
-            } else {
-                cnt = wz_nms_scan_band(S, b, k, f, lo_bin, hi_bin);
             }
-            while (cnt > WZ_CAND_CAP && lo_bin + 1 < hi_bin) {   // too many for the list: raise the band's lower edge
-                lo_bin += (hi_bin - lo_bin + 1) >> 1;
-                cnt = wz_nms_scan_band(S, b, k, f, lo_bin, hi_bin);
-            }
-            if (first) {
-                first_cnt = cnt;
-                first_lo = lo_bin;
-                NMS_STAMP(2);
-            }
-            if (cnt > WZ_CAND_CAP)                           // one bin holds more than the list: exact serial walk
-                kept = wz_nms_band_serial(S, b, k, f, kept, (unsigned long long)((uint32_t)lo_bin << 20) << 32,
-                                          (unsigned long long)((uint32_t)hi_bin << 20) << 32);
-            else if (cnt > 0)
-                kept = wz_nms_band<CLIP, COUNT>(S, b, k, f, (int)cnt, kept);
-            processed += cnt;
-            if (first) { NMS_STAMP(3); if (tid == 0) { b.dbg[(size_t)f * 16 + 8] = cnt; b.dbg[(size_t)f * 16 + 9] = kept; } }
-            first = false;
-            if (kept >= k.max_total || lo_bin == 0) break;
-            hi_bin = lo_bin;
-            lo_bin = max(lo_bin - reach, 0);
-            reach *= 2;
-        }
-        if (tid == 0) {   // where to start next time: a first band of roughly 200 .. 800 candidates
-            int h = first_lo;
-            if (first_cnt < WZ_CAND_TARGET) h = max(first_lo - 2, 1);
-            else if (first_cnt > 4 * WZ_CAND_TARGET) h = min(first_lo + 1, WZ_HIST_BINS - 1);
-            b.hint[f] = (uint32_t)h;
-            b.hint_logit[f] = wz_logit_floor(h);
-        }
-    } else {
-    // Bands of the score histogram, highest first.  Band 0 = bins [thr, 1024) was compacted by
-    // wz_k_compact; further bands (needed only when NMS suppresses so much that band 0 runs dry
-    // before max_total rows are kept) are collected here by one scan over the frame's candidates.
-    const uint32_t total = b.band[2 * f + 1];
-    int lo_bin = (int)b.band[2 * f];
-    NMS_STAMP(1);
-    int hi_bin = WZ_HIST_BINS;
-    bool first = true;
-    while (total > 0) {
-        uint32_t cnt_raw;
-        if (first) {
-            cnt_raw = b.count[f];
-            for (int i = tid; i < (int)min(cnt_raw, (uint32_t)WZ_CAND_CAP); i += NMS_THREADS) {
-                const uint2 c = b.cand[(size_t)f * WZ_CAND_CAP + i];
-                S->keys[i] = ((unsigned long long)c.x << 32) | (unsigned long long)(0xFFFFFFFFu - c.y);
-            }
+            __syncthreads();
+            const uint32_t nl = min((uint32_t)S->pad[0], ELIST_CAP);
+            for (uint32_t q = tid; q < nl; q += NMS_THREADS) take((int)elist[q]);
+            __syncthreads();
+            cnt = S->ncand;
+            __syncthreads();
         } else {
-            if (tid == 0) S->ncand = 0;
-            __syncthreads();
-            const int n_entries = A * k.num_classes;
-            for (int j = tid; j < n_entries; j += NMS_THREADS) {
-                uint32_t key, tie;
-                if (wz_candidate(b, k, f, j, key, tie)) {
-                    const int bin = (int)(key >> 20);
-                    if (bin >= lo_bin && bin < hi_bin) {
-                        const uint32_t pos = atomicAdd(&S->ncand, 1u);
-                        if (pos < WZ_CAND_CAP)
-                            S->keys[pos] = ((unsigned long long)key << 32) | (unsigned long long)(0xFFFFFFFFu - tie);
-                    }
-                }
-            }
-            __syncthreads();
-            cnt_raw = S->ncand;
+            cnt = wz_nms_scan_band(S, b, k, f, lo_bin, hi_bin);
         }
-        __syncthreads();
-        if (first) NMS_STAMP(2);
-        if (cnt_raw > WZ_CAND_CAP)
+        while (cnt > WZ_CAND_CAP && lo_bin + 1 < hi_bin) {   // too many for the list: raise the band's lower edge
+            lo_bin += (hi_bin - lo_bin + 1) >> 1;
+            cnt = wz_nms_scan_band(S, b, k, f, lo_bin, hi_bin);
+        }
+        if (first) {
+            first_cnt = cnt;
+            first_lo = lo_bin;
+            NMS_STAMP(2);
+        }
+        if (cnt > WZ_CAND_CAP)                           // one bin holds more than the list: exact serial walk
             kept = wz_nms_band_serial(S, b, k, f, kept, (unsigned long long)((uint32_t)lo_bin << 20) << 32,
                                       (unsigned long long)((uint32_t)hi_bin << 20) << 32);
-        else if (cnt_raw > 0)
-            kept = wz_nms_band<CLIP, COUNT>(S, b, k, f, (int)cnt_raw, kept);
-        processed += cnt_raw;
-        if (first) { NMS_STAMP(3); if (tid == 0) { b.dbg[(size_t)f * 16 + 8] = cnt_raw; b.dbg[(size_t)f * 16 + 9] = kept; } }
-        if (kept >= k.max_total || processed >= total || lo_bin == 0) break;
-        hi_bin = lo_bin;
-        lo_bin = wz_threshold_bin(b.hist + (size_t)f * WZ_HIST_BINS, S->hist, WZ_CAND_TARGET, nullptr, hi_bin);
+        else if (cnt > 0)
+            kept = wz_nms_band<CLIP, COUNT>(S, b, k, f, (int)cnt, kept);
+        processed += cnt;
+        if (first) { NMS_STAMP(3); if (tid == 0) { b.dbg[(size_t)f * 16 + 8] = cnt; b.dbg[(size_t)f * 16 + 9] = kept; } }
         first = false;
+        if (kept >= k.max_total || lo_bin == 0) break;
+        hi_bin = lo_bin;
+        lo_bin = max(lo_bin - reach, 0);
+        reach *= 2;
     }
+    if (tid == 0) {   // where to start next time: a first band of roughly 200 .. 800 candidates
+        int h = first_lo;
+        if (first_cnt < WZ_CAND_TARGET) h = max(first_lo - 2, 1);
+        else if (first_cnt > 4 * WZ_CAND_TARGET) h = min(first_lo + 1, WZ_HIST_BINS - 1);
+        b.hint[f] = (uint32_t)h;
+        b.hint_logit[f] = wz_logit_floor(h);
     }
     __syncthreads();
 
@@ -1298,37 +1120,21 @@ void wz_launch_decode(const WzPostBuffers& b, const WzPostConsts& c, int n, hipS
     const int total = n * c.num_anchors;
     hipLaunchKernelGGL(wz_k_decode, dim3((total + 255) / 256), dim3(256), 0, s, b, c, n);
 }
-void wz_launch_hist(const WzPostBuffers& b, const WzPostConsts& c, int n, hipStream_t s) {
-    const int total = c.num_anchors * c.num_classes;
-    dim3 grid((total + 256 * POST_ITEMS - 1) / (256 * POST_ITEMS), n);
-    hipLaunchKernelGGL(wz_k_hist, grid, dim3(256), 0, s, b, c);
-}
-void wz_launch_compact(const WzPostBuffers& b, const WzPostConsts& c, int n, hipStream_t s) {
-    const int total = c.num_anchors * c.num_classes;
-    dim3 grid((total + 256 * COMPACT_ITEMS - 1) / (256 * COMPACT_ITEMS), n);
-    hipLaunchKernelGGL(wz_k_compact, grid, dim3(256), 0, s, b, c);
-}
 void wz_post_init() {
-#define WZ_NMS_ATTR(SELF, CLIP, COUNT) \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wz_k_nms<SELF, CLIP, COUNT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(NmsShared))
-    WZ_NMS_ATTR(true, false, false); WZ_NMS_ATTR(true, false, true); WZ_NMS_ATTR(true, true, false); WZ_NMS_ATTR(true, true, true);
-    WZ_NMS_ATTR(false, false, false); WZ_NMS_ATTR(false, false, true); WZ_NMS_ATTR(false, true, false); WZ_NMS_ATTR(false, true, true);
+#define WZ_NMS_ATTR(CLIP, COUNT) \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wz_k_nms<CLIP, COUNT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(NmsShared))
+    WZ_NMS_ATTR(false, false); WZ_NMS_ATTR(false, true); WZ_NMS_ATTR(true, false); WZ_NMS_ATTR(true, true);
 #undef WZ_NMS_ATTR
 }
 void wz_launch_nms(const WzPostBuffers& b, const WzPostConsts& c, int n, hipStream_t s, const WzFrameDesc* d_frames,
-                   const WzCamFilter* d_cams, wz_detection_t* rows, uint8_t* pass, bool self_scan, bool listed, uint32_t* status) {
+                   const WzCamFilter* d_cams, wz_detection_t* rows, uint8_t* pass, bool listed, uint32_t* status) {
     if (((c.num_anchors * c.num_classes + 31) >> 5) > 8 * NMS_THREADS) listed = false;   // bit map larger than one pass: scan instead
-    const int ls = (self_scan && listed) ? 1 : 0;
+    const int ls = listed ? 1 : 0;
     const bool count = c.max_per_class < c.max_total;   // the per-class cap can bind: one thread per class walks its chain (wz_nms_band)
-#define WZ_NMS_GO(SELF, CLIP, COUNT) \
-    WZ_LAUNCH((wz_k_nms<SELF, CLIP, COUNT>), dim3(n), dim3(NMS_THREADS), sizeof(NmsShared), s, b, c, d_frames, d_cams, rows, pass, SELF ? 1 : 0, SELF ? ls : 0, status)
-    if (self_scan) {
-        if (!c.clip_after) { if (!count) WZ_NMS_GO(true, false, false); else WZ_NMS_GO(true, false, true); }
-        else { if (!count) WZ_NMS_GO(true, true, false); else WZ_NMS_GO(true, true, true); }
-    } else {
-        if (!c.clip_after) { if (!count) WZ_NMS_GO(false, false, false); else WZ_NMS_GO(false, false, true); }
-        else { if (!count) WZ_NMS_GO(false, true, false); else WZ_NMS_GO(false, true, true); }
-    }
+#define WZ_NMS_GO(CLIP, COUNT) \
+    WZ_LAUNCH((wz_k_nms<CLIP, COUNT>), dim3(n), dim3(NMS_THREADS), sizeof(NmsShared), s, b, c, d_frames, d_cams, rows, pass, ls, status)
+    if (!c.clip_after) { if (!count) WZ_NMS_GO(false, false); else WZ_NMS_GO(false, true); }
+    else { if (!count) WZ_NMS_GO(true, false); else WZ_NMS_GO(true, true); }
 #undef WZ_NMS_GO
 }
 void wz_launch_rows(const WzPostBuffers& b, const WzFrameDesc* d_frames, const WzCamFilter* d_cams, int n,

@@ -55,21 +55,13 @@ struct WzConvArgs {
     float* out2;                // WZ_OUT_HEAD: class-logit buffer (out = box-encoding buffer)
     int64_t out2_batch_stride, out2_off;
     int32_t n_box;              // WZ_OUT_HEAD: columns [0, n_box) are box encodings, the rest class logits
-    const half_t* zeros;        // 4 KiB of zeros in HBM: source of out-of-frame lanes / absent tiles in the LDS-tiled kernel
+    const half_t* zeros;        // 4 KiB of zeros in HBM (the engine's; the LDS-tiled kernels take a conv only where it is set)
     int32_t grid_m, grid_n;     // LDS-tiled kernel: pixel tiles x channel tiles (filled in by the launcher)
     float* ws;                  // fp32 engine: split-K workspace (the fp16 kernels get it through `out`)
     unsigned long long* dbg;    // WZ_MB_DEBUG=1: 16 slots of phase timestamps (LDS-tiled kernel), else nullptr
-    int32_t order;              // tile order of the LDS-tiled kernels (experiment knob WZ_LDS_ORDER)
-    // In-launch split-K reduction of the SSD heads (splitk > 1 && inline_reduce): every K slice publishes its fp32 partial tile
-    // write-through, takes a ticket on the tile's counter, and the LAST arriver sums the slices in slice order (the order of
-    // wz_k_splitk_reduce: bit-identical) and finishes the outputs -- no reduce launch behind the convolution.
     int32_t nt_base;            // tile kernel: first 16-channel tile this launch entry serves (a head split along N, see wz_conv_rs_group_add)
     int32_t nt_live, nt_group;  // wide tile kernel (k_conv_wide.hip): 16-channel tiles that hold real columns / tiles per workgroup
-    int32_t inline_reduce;
     int32_t frag_ws;            // the K slices' partial sums lie in FRAGMENT order: [z][M / 16][n_pad / 16][64 lanes][4] (wide tile kernel -> grouped reduce)
-    int32_t fin_flags;          // bit 0: decode the boxes, bit 1: mark the NMS candidates (see WzHeadFinish)
-    int32_t* tickets;           // one counter per output tile of this convolution, zero between launches
-    const struct WzHeadFinish* fin;   // device-resident, per lane
 };
 
 
@@ -80,17 +72,6 @@ struct WzPostConsts {
     float scale_y, scale_x, scale_h, scale_w;
     int32_t clip_after;   // 1: the per-class NMS sees the boxes as decoded, what it selects is clipped afterwards (WzBlobHeader::post_flags)
     int32_t _pad;
-};
-
-// What finishing a head output needs beyond the convolution's own arguments (static per lane, lives in HBM).
-struct WzHeadFinish {
-    const float* hint_logit;    // [n] see WzPostBuffers
-    uint32_t* cbits;            // [n][cbits_words]
-    int32_t cbits_words, _pad;
-    WzPostConsts pc;
-    const float* anchors;       // [A][4]
-    float* boxes;               // [n][A][4] decoded + clipped
-    uint8_t* valid;             // [n][A]
 };
 
 // One fused inverted-residual block (k_mbconv.hip).  cin/kc/n_pad/cout describe the project conv.
@@ -235,8 +216,8 @@ struct WzReduceGroup {
     WzConvArgs a[WZ_REDUCE_GROUP_MAX];
     const float* ws[WZ_REDUCE_GROUP_MAX];
     // decode != 0: the thread that finishes the four box-encoding columns of an anchor also decodes + clips the box
-    // (exactly wz_k_decode's arithmetic) and the launch clears hist / count / band -- wz_k_decode is then not launched
-    int32_t decode, n_frames;
+    // (exactly wz_k_decode's arithmetic) -- wz_k_decode is then not launched
+    int32_t decode;
     // list != 0: class logits at or above the frame's hint_logit get their bit set in cbits[f] -- the first band of
     // wz_k_nms then needs no scan of the logits at all
     int32_t list, cbits_words;
@@ -247,7 +228,6 @@ struct WzReduceGroup {
     const float* anchors;
     float* boxes;
     uint8_t* valid;
-    uint32_t *hist, *count, *band;
 };
 void wz_reduce_group_add(WzReduceGroup& g, const WzConvArgs& a, const float* ws);
 // several independent small 3x3 convolutions (wz_k_conv<3, 2, 2, 4> shapes) in ONE launch
@@ -257,8 +237,6 @@ struct WzConvGroup {
     int32_t first[WZ_CONV_GROUP_MAX + 1];
     int32_t gx[WZ_CONV_GROUP_MAX], gy[WZ_CONV_GROUP_MAX];
     WzConvArgs a[WZ_CONV_GROUP_MAX];
-    int32_t* tickets;           // host side only: the lane's counter block and how much of it the entries added so far use
-    int32_t ticket_off;
     unsigned long long* stamp;  // WZ_LANE_STAMPS builds: this launch's block of the lane's stamps, else nullptr
 };
 // split-K across the waves of a workgroup (no partials in HBM, no reduce launch): the extras chain
@@ -273,7 +251,7 @@ int wz_conv_rs_group_add(WzConvGroup& g, const WzConvArgs& a);   // entries adde
 void wz_launch_conv_rs_group(const WzConvGroup& g, hipStream_t s);
 // ... and the wide tile kernel (k_conv_wide.hip: 128 pixels x up to 320 channels per workgroup), which serves the big heads by default
 bool wz_conv_wide_applies(const WzConvArgs& a);
-int wz_conv_wide_ntw();                                                 // channel tiles per wave of the build in use (5, or 3: two workgroups per CU)
+#define WZ_WIDE_TILES 12   // 16-channel tiles per workgroup of that kernel: three per wave (<= 256 registers: two workgroups per CU)
 void wz_conv_wide_shape(const WzConvArgs& a, int* tiles, int* steps);   // workgroup tiles and K steps (of 64 channels x one tap)
 int wz_choose_wide_T(const int* tiles, const int* steps, const long long* tile_bytes, int n, int cus);   // steps per K slice
 int wz_conv_wide_group_add(WzConvGroup& g, const WzConvArgs& a);         // a.splitk set by the caller; 0 = the group is full
@@ -287,7 +265,6 @@ bool wz_conv_f32_use_rs(const WzConvArgs& a);            // fp32 engine: the reg
 int wz_choose_splitk_rs_f32(int M, int n_pad, int kchunks);
 bool wz_conv_ws_f32_applies(const WzConvArgs& a);         // fp32 engine: the extras chain on the wave-split kernel
 void wz_launch_conv_ws_f32(const WzConvArgs& a, hipStream_t s);
-void wz_conv_init();
 // a 1x1 convolution and the 3x3 stride-2 convolution behind it on the small maps of the extras chain, in one launch (k_extras_pair.hip)
 bool wz_extras_pair_applies(const WzConvArgs& a, const WzConvArgs& b);
 void wz_launch_extras_pair(const WzConvArgs& a, const WzConvArgs& b, int n, hipStream_t s);
@@ -311,20 +288,17 @@ int wz_launch_mbconv_hp2(const WzMbArgs& a, int n, hipStream_t s, bool prepare, 
 #define WZ_CAND_CAP 4096
 #define WZ_NMS_KEEP_MAX 128   // capacity of the NMS walk's kept list (k_post.hip); >= max_total (100)
 #define WZ_CAND_TARGET 192
+// (wz_k_nms, which takes this by value, runs at its register limit: of the field orders tried, this one spills least)
 struct WzPostBuffers {
+    uint32_t* hint;           // [n] wz_k_nms: the score bin the first band of this frame slot started at last time
+    float* hint_logit;        // [n] wz_logit_floor(hint): what the grouped head reduce compares the finished logits with
+    uint32_t* cbits;          // [n][ceil(A*C/32)] one bit per class logit: set by the grouped head reduce where the logit can
+                              // reach the frame's first band (fire-and-forget atomicOr), read and cleared by wz_k_nms
     const float* box_enc;     // [n][A][4]
     const float* logits;      // [n][A][C]
     const float* anchors;     // [A][4] (ycenter, xcenter, h, w)
     float* boxes;             // [n][A][4] decoded + clipped
     uint8_t* valid;           // [n][A]   clipped area > 0
-    uint32_t* hist;           // [n][WZ_HIST_BINS]
-    uint32_t* count;          // [n]  (directly behind hist so one memset clears both)
-    uint32_t* band;           // [n][2] threshold bin of band 0 and the frame's candidate total (written by wz_k_compact)
-    uint32_t* hint;           // [n] self-scan mode of wz_k_nms: the score bin the first band of this frame slot started at last time
-    float* hint_logit;        // [n] wz_logit_floor(hint): what the grouped head reduce compares the finished logits with
-    uint32_t* cbits;          // [n][ceil(A*C/32)] one bit per class logit: set by the grouped head reduce where the logit can
-                              // reach the frame's first band (fire-and-forget atomicOr), read and cleared by wz_k_nms
-    uint2* cand;              // [n][WZ_CAND_CAP] (score bits, tie index c*A + a)
     float* det_boxes;         // [n][100][4]
     float* det_scores;        // [n][100]
     int32_t* det_classes;     // [n][100] 1-based
@@ -339,13 +313,11 @@ struct WzPostBuffers {
     int32_t stamps_n, _stamps_pad;
 };
 void wz_launch_decode(const WzPostBuffers& b, const WzPostConsts& c, int n, hipStream_t s);
-void wz_launch_hist(const WzPostBuffers& b, const WzPostConsts& c, int n, hipStream_t s);
-void wz_launch_compact(const WzPostBuffers& b, const WzPostConsts& c, int n, hipStream_t s);
 // d_frames != nullptr: the kernel also writes the Detection rows + pass bytes (then no wz_launch_rows is needed)
-// self_scan: the kernel selects its candidates itself (no wz_k_hist / wz_k_compact in front of it)
+// listed: the grouped head reduce marked the candidates of the first band in cbits (no scan of the logits for it)
 void wz_launch_nms(const WzPostBuffers& b, const WzPostConsts& c, int n, hipStream_t s, const WzFrameDesc* d_frames = nullptr,
                    const WzCamFilter* d_cams = nullptr, wz_detection_t* rows = nullptr, uint8_t* pass = nullptr,
-                   bool self_scan = false, bool listed = false, uint32_t* status = nullptr);   // status: see wz_k_nms
+                   bool listed = false, uint32_t* status = nullptr);   // status: see wz_k_nms
 void wz_launch_rows(const WzPostBuffers& b, const WzFrameDesc* d_frames, const WzCamFilter* d_cams, int n,
                     int max_total, wz_detection_t* rows, uint8_t* pass, hipStream_t s);
 int wz_set_error(int code, const char* fmt, ...);   // sets wz_last_error() of the calling thread, returns code

@@ -47,8 +47,6 @@ int wz_set_error(int code, const char* fmt, ...) {
                                              __FILE__, __LINE__);                                     \
     } while (0)
 
-#define WZ_TICKETS 8192   // tile counters per lane: first half the tile-kernel heads, second half the small ones
-
 struct StageTimer {
     std::vector<hipEvent_t> ev;
     size_t used = 0;
@@ -74,9 +72,6 @@ struct wz_engine {
     int max_batch = 0, max_w = 0, max_h = 0;
     bool no_reuse = false, use_graph = true, use_splitk = true;
     bool graph_adaptive = false;   // use_graph && WZ_GRAPH unset: a batch that finds every other lane idle is launched kernel by kernel (wz_create)
-    bool wide_frag = true;     // the wide head kernel's partial sums in fragment order (WZ_WIDE_FRAG=0: [slice][pixel][column])
-    bool list_cands = true;    // WZ_LIST_CANDS=0: the self-scanning NMS kernel always scans
-    bool post_self = true;     // WZ_POST_SELF=0: histogram + compaction kernels in front of the NMS kernel
     bool fuse_decode = true;   // WZ_FUSE_DECODE=0: keep wz_k_decode as its own launch
     bool defer_heads = true;   // the SSD heads' split-K reductions run as one launch after the last head (WZ_DEFER_HEADS=0: one each)
     bool conv_wide = true;     // the big SSD heads on the wide tile kernel (k_conv_wide.hip); WZ_CONV_WIDE=0: on wz_k_conv_rs
@@ -96,11 +91,6 @@ struct wz_engine {
     std::vector<HostRange> host_ranges;   // what wz_host_register page-locked, with the address the device sees it at
     int wide_cus = 128;        // CUs the wide head kernel's K slices are sized for when several lanes are in flight (WZ_WIDE_CUS)
     int num_cus = 256;         // compute units of the device (the wide head kernel sizes its K slices for one round over them)
-    bool head_inline = false;  // WZ_HEAD_INLINE=1: ... or inside the head convolutions themselves, by each tile's last K slice.
-                               // Bit-identical and one launch less, but measured SLOWER (profiles/r02l_*: heads 76 + 18 us against
-                               // 33 + 7 + 10 us, 37.4 k against 41.5 k frames/s): the reduction of a tile then runs on ONE workgroup at
-                               // the tail of the launch and its epilogue stores from the MFMA fragment layout (16 pixels x 4 columns per
-                               // instruction) instead of row-contiguous as the reduce kernel does.  Off by default.
 
     uint8_t* d_weights = nullptr;
     half_t* d_zeros = nullptr;               // 4 KiB of zeros
@@ -126,15 +116,13 @@ struct wz_engine {
         float* d_box_enc = nullptr;
         float* d_logits = nullptr;
         float* d_ws = nullptr;
-        int32_t* d_tickets = nullptr;        // tile counters of the in-launch head reductions (zero between launches)
-        WzHeadFinish* d_fin = nullptr;       // what finishing a head output needs (static)
         int launch_failed = 0;               // op index + 1 of a block no kernel took at launch time (enqueue_network), else 0
         bool decode_fused = false;           // set by enqueue_network: the grouped head reduce decoded the boxes
         bool cands_listed = false;           // ... and listed the candidates of the NMS kernel's first band
         uint8_t* d_frames = nullptr;         // staging for host frames of this lane [max_batch][frame_stride] (lazy)
         std::map<int, int> graph_nodes;      // batch size -> nodes of the captured graph (kernels + the descriptor copy)
         WzPostBuffers post;
-        void* d_post_scratch = nullptr;      // hist + count (memset per batch)
+        void* d_post_scratch = nullptr;      // post.hint, post.hint_logit, post.cbits
         WzFrameDesc* h_desc = nullptr;       // pinned
         WzFrameDesc* h_desc_dev = nullptr;   // ... and its address as the device sees it (nullptr: not mapped)
         WzFrameDesc* d_desc = nullptr;
@@ -282,19 +270,13 @@ static void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool wi
     WzConvGroup small, big;
     small.n = big.n = 0;
     small.first[0] = big.first[0] = 0;
-    big.tickets = L.d_tickets;
-    small.tickets = L.d_tickets ? L.d_tickets + WZ_TICKETS / 2 : nullptr;
-    big.ticket_off = small.ticket_off = 0;
-    int heads_in_groups = 0;                // entries of `heads` whose convolution sits in `big` or `small`
     // The heads with a long K loop run on the wide tile kernel (k_conv_wide.hip), all in one launch; their K slices are chosen
     // together, for the whole launch (one round over the CUs, slices of equal length), before the first one is enqueued.
     WzConvGroup wide;
     wide.n = 0;
     wide.first[0] = 0;
-    wide.tickets = nullptr;
-    wide.ticket_off = 0;
     int wide_T = 0;   // K steps per slice (0: no head goes there)
-    if (!f32 && e->conv_wide && e->use_splitk && e->defer_heads && !e->head_inline) {
+    if (!f32 && e->conv_wide && e->use_splitk && e->defer_heads) {
         int tiles[WZ_CONV_GROUP_MAX], steps[WZ_CONV_GROUP_MAX], cnt = 0;
         long long tile_bytes[WZ_CONV_GROUP_MAX];
         for (uint32_t i = 0; i < e->hdr.n_ops && cnt < WZ_CONV_GROUP_MAX; ++i) {
@@ -309,15 +291,14 @@ static void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool wi
             a.zeros = e->d_zeros;
             if (!wz_conv_wide_applies(a) || a.M < e->wide_min_m) continue;
             wz_conv_wide_shape(a, &tiles[cnt], &steps[cnt]);
-            tile_bytes[cnt] = 128ll * 4 * (((a.cout + 15) & ~15) / (((a.cout + 15) / 16 + 4 * wz_conv_wide_ntw() - 1) / (4 * wz_conv_wide_ntw())));
+            tile_bytes[cnt] = 128ll * 4 * (((a.cout + 15) & ~15) / (((a.cout + 15) / 16 + WZ_WIDE_TILES - 1) / WZ_WIDE_TILES));
             ++cnt;
         }
         // (K slices sized for HALF the chip when other lanes are there to use the rest: at batch 8 T = 27 -> 41 steps per slice, 179 -> ~120
         // workgroups of this one-wave-per-SIMD kernel, a third fewer fp32 partial tiles: 49.8 k -> 50.5 k frames/s, p50 +8 us)
-        // (the three-tile build puts two workgroups on a CU: twice the slots in the same part of the chip)
-        if (cnt > 0) wide_T = e->wide_T > 0 ? e->wide_T : wz_choose_wide_T(tiles, steps, tile_bytes, cnt, (e->n_lanes > 1 ? e->wide_cus : e->num_cus) * (wz_conv_wide_ntw() == 3 ? 2 : 1));
+        // (two workgroups of that kernel share a CU: twice the slots in the same part of the chip)
+        if (cnt > 0) wide_T = e->wide_T > 0 ? e->wide_T : wz_choose_wide_T(tiles, steps, tile_bytes, cnt, (e->n_lanes > 1 ? e->wide_cus : e->num_cus) * 2);
     }
-    int big_head[WZ_CONV_GROUP_MAX] = {0}, small_head[WZ_CONV_GROUP_MAX] = {0};   // ... and which entry
     for (uint32_t i = 0; i < e->hdr.n_ops; ++i) {
         const WzOpDesc& op = e->ops[i];
         const uint8_t* wbase = e->d_weights;
@@ -490,7 +471,7 @@ static void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool wi
                 else
                     to_wide = false;
             }
-            a.frag_ws = (to_wide && e->wide_frag) ? 1 : 0;
+            a.frag_ws = to_wide ? 1 : 0;
             const size_t slab = (((size_t)sk * (to_wide ? m16 : (size_t)a.M) * a.n_pad * 4) + 255) & ~(size_t)255;
             if ((sk > 1 || to_wide) && e->defer_heads && op.out_mode != WZ_OUT_ACT && heads.n < WZ_REDUCE_GROUP_MAX &&
                 slab + (e->ws_bytes >> 1) <= ws_top) {   // keep at least half of the workspace for the other ops
@@ -501,13 +482,8 @@ static void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool wi
                 if (to_wide) {
                     wz_conv_wide_group_add(wide, a);
                 } else if (small.n < WZ_CONV_GROUP_MAX && wz_conv_groupable(a)) {
-                    small_head[small.n] = heads.n;
                     wz_conv_group_add(small, a);   // launched with the other small heads after the last op
-                    ++heads_in_groups;
-                } else if (int added = wz_conv_rs_groupable(a) ? wz_conv_rs_group_add(big, a) : 0) {
-                    for (int k = 0; k < added; ++k) big_head[big.n - 1 - k] = heads.n;   // the heads on the tile kernel: one launch, too
-                    ++heads_in_groups;
-                } else {
+                } else if (!(wz_conv_rs_groupable(a) && wz_conv_rs_group_add(big, a))) {   // (the heads on the tile kernel: one launch, too)
                     WZ_STAMP_ARG(a);
                     wz_launch_conv(a, s);
                 }
@@ -548,23 +524,8 @@ static void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool wi
     }
     // every box encoding is finished by the grouped reduce: let it decode the boxes as well (one launch less)
     L.decode_fused = heads.n > 0 && box_ops > 0 && box_ops == box_ops_grouped && e->fuse_decode;
-    // ... and, when the NMS kernel selects its own candidates, list the class logits that can reach its first band
-    L.cands_listed = with_post && L.decode_fused && e->post_self && head_ops == heads.n && e->list_cands;
-    // With WZ_HEAD_INLINE=1 (and all of the above) the reduction does not take a launch of its own: the head convolutions do
-    // it themselves, tile by tile, in the workgroup (wave) that publishes a tile's last K slice
-    const bool inline_heads = e->head_inline && !f32 && L.cands_listed && L.d_tickets && L.d_fin && heads.n > 0 &&
-                              heads_in_groups == heads.n && big.ticket_off <= WZ_TICKETS / 2 && small.ticket_off <= WZ_TICKETS / 2;
-    if (inline_heads) {
-        for (int i = 0; i < big.n + small.n; ++i) {
-            WzConvArgs& a = i < big.n ? big.a[i] : small.a[i - big.n];
-            const WzConvArgs& fin = heads.a[i < big.n ? big_head[i] : small_head[i - big.n]];
-            a.ws = reinterpret_cast<float*>(a.out);     // the slab of partial tiles ...
-            a.out = fin.out;                            // ... and where the finished columns go
-            a.inline_reduce = 1;
-            a.fin_flags = 3;                            // decode + list
-            a.fin = L.d_fin;
-        }
-    }
+    // ... and list the class logits that can reach the NMS kernel's first band
+    L.cands_listed = with_post && L.decode_fused && head_ops == heads.n;
     wide.stamp = big.stamp = small.stamp = heads.stamp = nullptr;   // (set per launch in the stamps build only)
     if (wide.n > 0) { WZ_STAMP_GROUP(wide); wz_launch_conv_wide_group(wide, s); }
     if (big.n > 0) { WZ_STAMP_GROUP(big); wz_launch_conv_rs_group(big, s); }
@@ -573,14 +534,10 @@ static void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool wi
     if (t) t->mark();
     if (L.decode_fused) {
         heads.decode = 1;
-        heads.n_frames = n;
         heads.pc = e->pc;
         heads.anchors = L.post.anchors;
         heads.boxes = L.post.boxes;
         heads.valid = L.post.valid;
-        heads.hist = L.post.hist;
-        heads.count = L.post.count;
-        heads.band = L.post.band;
     }
     heads.list = L.cands_listed ? 1 : 0;
     if (L.cands_listed) {
@@ -588,20 +545,15 @@ static void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool wi
         heads.cbits = L.post.cbits;
         heads.cbits_words = (e->pc.num_anchors * e->pc.num_classes + 31) >> 5;
     }
-    if (heads.n > 0 && !inline_heads) { WZ_STAMP_GROUP(heads); wz_launch_splitk_reduce_group(heads, s); }
+    if (heads.n > 0) { WZ_STAMP_GROUP(heads); wz_launch_splitk_reduce_group(heads, s); }
     if (t) t->mark();
 }
 
 static void enqueue_post(wz_engine* e, Lane& L, bool rows, int n, StageTimer* t, bool decode_done = false, bool listed = false) {
     hipStream_t s = L.stream;
-    if (!decode_done) wz_launch_decode(L.post, e->pc, n, s);   // (also clears hist / count / band)
+    if (!decode_done) wz_launch_decode(L.post, e->pc, n, s);
     if (t) t->mark();
-    // default: the NMS kernel selects its candidates itself, one workgroup per frame; WZ_POST_SELF=0 puts the two
-    // 256-CU scans (histogram of the scores, compaction of the band above its threshold) back in front of it
-    if (!e->post_self) wz_launch_hist(L.post, e->pc, n, s);
-    if (t) t->mark();
-    if (!e->post_self) wz_launch_compact(L.post, e->pc, n, s);
-    if (t) t->mark();
+    // the NMS kernel selects its candidates itself, one workgroup per frame
     // with `rows` the NMS kernel also fills the Detection rows (straight into the lane's pinned, device-mapped host
     // block: no D2H copy node, no separate row kernel); the "post/rows" stage slot stays empty
 #if WZ_LANE_STAMPS
@@ -609,9 +561,9 @@ static void enqueue_post(wz_engine* e, Lane& L, bool rows, int n, StageTimer* t,
     L.post.stamps_host = rows && L.post.stamps_n ? L.m_stamps : nullptr;
 #endif
     if (rows)
-        wz_launch_nms(L.post, e->pc, n, s, L.d_desc, e->d_cams, L.m_rows, L.m_pass, e->post_self, listed, L.m_status);
+        wz_launch_nms(L.post, e->pc, n, s, L.d_desc, e->d_cams, L.m_rows, L.m_pass, listed, L.m_status);
     else
-        wz_launch_nms(L.post, e->pc, n, s, nullptr, nullptr, nullptr, nullptr, e->post_self, listed);
+        wz_launch_nms(L.post, e->pc, n, s, nullptr, nullptr, nullptr, nullptr, listed);
     if (t) t->mark();
     if (rows && t) t->mark();
 }
@@ -936,12 +888,8 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
     e->use_graph = env ? atoi(env) != 0 : !wz_latency_schedule();
     e->graph_adaptive = e->use_graph && !env;   // (throughput schedule, nothing said: graphs while the lanes are busy, kernel by kernel for a lone batch)
     e->use_splitk = !((env = wz_dev_getenv("WZ_SPLITK")) && atoi(env) == 0);
-    e->wide_frag = !((env = wz_dev_getenv("WZ_WIDE_FRAG")) && atoi(env) == 0);
     e->defer_heads = !((env = wz_dev_getenv("WZ_DEFER_HEADS")) && atoi(env) == 0);
     e->fuse_decode = !((env = wz_dev_getenv("WZ_FUSE_DECODE")) && atoi(env) == 0);
-    e->post_self = !((env = wz_dev_getenv("WZ_POST_SELF")) && atoi(env) == 0);
-    e->list_cands = !((env = wz_dev_getenv("WZ_LIST_CANDS")) && atoi(env) == 0);
-    e->head_inline = (env = wz_dev_getenv("WZ_HEAD_INLINE")) && atoi(env) != 0;
     e->conv_wide = !((env = wz_dev_getenv("WZ_CONV_WIDE")) && atoi(env) == 0);
     e->desc_zero_copy = !((env = wz_dev_getenv("WZ_DESC_COPY")) && atoi(env) != 0);
     e->desc_by_value = !((env = wz_dev_getenv("WZ_DESC_ARGS")) && atoi(env) == 0);
@@ -980,7 +928,6 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
     wz_device_name_of(device, nm, sizeof(nm));
     e->name = nm;
     wz_post_init();
-    wz_conv_init();
     for (uint32_t i = 0; i < e->hdr.n_ops; ++i)   // kernel attributes of the fused-block kernels, on THIS device
         if (e->ops[i].kind == WZ_OP_MBCONV) {
             wz_engine::Lane none;
@@ -1018,7 +965,7 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
     e->pc.scale_y = h.scale_y; e->pc.scale_x = h.scale_x; e->pc.scale_h = h.scale_h; e->pc.scale_w = h.scale_w;
     e->pc.clip_after = (h.post_flags & WZ_POSTF_CLIP_AFTER) ? 1 : 0;
     e->pc._pad = 0;
-    e->post_scratch_bytes = (size_t)max_batch * (WZ_HIST_BINS + 5 + ((h.num_anchors * h.num_classes + 31) >> 5)) * 4;   // hist, count, band[2], hint, hint_logit, cbits
+    e->post_scratch_bytes = (size_t)max_batch * (2 + ((h.num_anchors * h.num_classes + 31) >> 5)) * 4;   // hint, hint_logit, cbits
 
     for (uint32_t i = 0; i < h.n_tensors; ++i)
         if (e->tensors[i].slot < 0 || e->tensors[i].slot >= (int)h.n_slots) {
@@ -1066,9 +1013,6 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
         CK(hipMalloc((void**)&L.d_box_enc, (size_t)max_batch * h.num_anchors * 4 * 4));
         CK(hipMalloc((void**)&L.d_logits, (size_t)max_batch * h.num_anchors * h.num_classes * 4));
         CK(hipMalloc((void**)&L.d_ws, e->ws_bytes));
-        CK(hipMalloc((void**)&L.d_tickets, WZ_TICKETS * 4));
-        CK(hipMemset(L.d_tickets, 0, WZ_TICKETS * 4));
-        CK(hipMalloc((void**)&L.d_fin, sizeof(WzHeadFinish)));
         CK(hipMalloc((void**)&L.d_frames, e->frame_stride * max_batch));
         WzPostBuffers& pb = L.post;
         pb.box_enc = L.d_box_enc;
@@ -1077,11 +1021,8 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
         CK(hipMalloc((void**)&pb.boxes, (size_t)max_batch * h.num_anchors * 16));
         CK(hipMalloc((void**)&pb.valid, (size_t)max_batch * h.num_anchors));
         CK(hipMalloc(&L.d_post_scratch, e->post_scratch_bytes));
-        pb.hist = (uint32_t*)L.d_post_scratch;
-        pb.count = pb.hist + (size_t)max_batch * WZ_HIST_BINS;
-        pb.band = pb.count + max_batch;
-        pb.hint = pb.band + 2 * max_batch;
-        {   // first band of the self-scanning NMS kernel: start at score 0.25 until the frame slot has a history
+        pb.hint = (uint32_t*)L.d_post_scratch;
+        {   // first band of the NMS kernel: start at score 0.25 until the frame slot has a history
             const uint32_t bin0 = 0x3E800000u >> 20;
             std::vector<uint32_t> hint0((size_t)max_batch, bin0);
             CK(hipMemcpy(pb.hint, hint0.data(), hint0.size() * 4, hipMemcpyHostToDevice));
@@ -1095,19 +1036,6 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
             pb.cbits = reinterpret_cast<uint32_t*>(pb.hint_logit + max_batch);
             CK(hipMemset(pb.cbits, 0, (size_t)max_batch * ((h.num_anchors * h.num_classes + 31) >> 5) * 4));
         }
-        {
-            WzHeadFinish hf;
-            memset(&hf, 0, sizeof(hf));
-            hf.hint_logit = pb.hint_logit;
-            hf.cbits = pb.cbits;
-            hf.cbits_words = (int32_t)((h.num_anchors * h.num_classes + 31) >> 5);
-            hf.pc = e->pc;
-            hf.anchors = pb.anchors;
-            hf.boxes = pb.boxes;
-            hf.valid = pb.valid;
-            CK(hipMemcpy(L.d_fin, &hf, sizeof(hf), hipMemcpyHostToDevice));
-        }
-        CK(hipMalloc((void**)&pb.cand, (size_t)max_batch * WZ_CAND_CAP * sizeof(uint2)));
         CK(hipMalloc((void**)&pb.det_boxes, (size_t)max_batch * h.max_total * 16));
         CK(hipMalloc((void**)&pb.det_scores, (size_t)max_batch * h.max_total * 4));
         CK(hipMalloc((void**)&pb.det_classes, (size_t)max_batch * h.max_total * 4));
@@ -1176,8 +1104,6 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
     e->stage_names.push_back("heads#small_convs");
     e->stage_names.push_back("heads#splitk_reduce");
     e->stage_names.push_back("post/decode");
-    e->stage_names.push_back("post/hist");
-    e->stage_names.push_back("post/compact");
     e->stage_names.push_back("post/nms");
     e->stage_names.push_back("post/rows");
     CK(hipDeviceSynchronize());
@@ -1206,7 +1132,7 @@ extern "C" void wz_destroy(wz_engine_t* e) {
         for (auto& kv : L.graphs) (void)hipGraphExecDestroy(kv.second);
         for (auto& kv : L.graph_src) (void)hipGraphDestroy(kv.second);
         for (void* p : L.bufs) (void)hipFree(p);
-        void* lp[] = {L.d_frames, L.d_box_enc, L.d_logits, L.d_ws, L.d_tickets, L.d_fin, L.post.boxes, L.post.valid, L.d_post_scratch, L.post.cand,
+        void* lp[] = {L.d_frames, L.d_box_enc, L.d_logits, L.d_ws, L.post.boxes, L.post.valid, L.d_post_scratch,
                       L.post.det_boxes, L.post.det_scores, L.post.det_classes, L.post.det_num, L.post.dbg,
                       L.d_stamp_raw ? (void*)L.d_stamp_raw : (void*)L.d_desc, L.d_rows, L.d_pass};
         for (void* p : lp)
