@@ -21,9 +21,11 @@ FE = "FeatureExtractor/MobilenetV2/"
 
 # op kinds understood by the runtime (keep in sync with csrc/wz_program.h)
 OP_STEM, OP_DW, OP_CONV, OP_MBCONV = 1, 2, 3, 4   # OP_MBCONV: fused inverted-residual block (csrc/k_mbconv.hip)
+OP_POOL, OP_STEM7 = 5, 6   # 3x3 max / average pool, 7x7 stride-2 stem conv on the network input (the Inception program, inception.py)
 # output modes of OP_CONV
 OUT_ACT, OUT_BOX, OUT_CLS, OUT_HEAD = 0, 1, 2, 3   # OUT_HEAD: box columns then class columns, one launch
 ACT_NONE, ACT_RELU6 = 0, 1
+STEM7_MULTIPLIER = 8       # depth multiplier of the Inception stem's separable 7x7 conv
 
 _INVERTED_RESIDUAL = [  # (t, c, n, s) rows of the MobileNetV2 paper, depth multiplier 1.0
     (1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1),
@@ -89,6 +91,9 @@ class Op:
                                # weights over the first copy | lo halves over the second] -- W.x with ~22 significant bits of W on the plain kernels
     dst2: Optional[str] = None  # OP_MBCONV that also WRITES its expanded tensor (hin x win x cmid, plain fp16): block 13, whose expand
                                 # output is the first SSD feature map -- the block stores what it computes anyway, no launch of its own
+    coff: int = 0              # OP_CONV / OP_POOL / OP_STEM7: first channel of the slice of `dst` this op writes (concat by slice)
+    cdst: int = 0              # ... and the channels per pixel of `dst` (0: cout, the op writes the whole tensor)
+    pool_max: bool = False     # OP_POOL: max (padding ignored) instead of average (divided by the in-image taps)
 
 
 @dataclass
@@ -106,6 +111,14 @@ class Program:
         for op in self.ops:
             flat.extend(op.parts if op.kind == OP_MBCONV else [op])
         for op in flat:
+            if op.kind == OP_POOL:
+                continue
+            if op.kind == OP_STEM7:                        # separable in the graph: depthwise [k,k,3,8] then pointwise [1,1,24,cout]
+                out[op.scope + "/depthwise_weights"] = (op.k, op.k, op.cin, STEM7_MULTIPLIER)
+                out[op.scope + "/pointwise_weights"] = (1, 1, op.cin * STEM7_MULTIPLIER, op.cout)
+                for v in ("gamma", "beta", "moving_mean", "moving_variance"):
+                    out[op.scope + "/BatchNorm/" + v] = (op.cout,)
+                continue
             if op.out_mode == OUT_HEAD:
                 for sub, cols in (("BoxEncodingPredictor", op.n_box), ("ClassPredictor", op.cout - op.n_box)):
                     out["%s/%s/weights" % (op.scope, sub)] = (op.k, op.k, op.cin, cols)

@@ -140,7 +140,9 @@ __device__ __forceinline__ void wz_epilogue4(const WzConvArgs& a, int m, int n4,
             for (int r = 0; r < 4; ++r) v[r] += (float)rv[r];
         }
         half4_t h = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
-        *reinterpret_cast<half4_t*>(reinterpret_cast<half_t*>(a.out) + o) = h;
+        // (a channel slice of a wider tensor: an Inception branch writing its part of the module's concat)
+        const size_t os = a.out_cstride ? (size_t)m * a.out_cstride + a.out_coff + n4 : o;
+        *reinterpret_cast<half4_t*>(reinterpret_cast<half_t*>(a.out) + os) = h;
     } else {
         const int hw = a.hout * a.wout;
         const int b = m / hw, pix = m - b * hw;

@@ -119,7 +119,8 @@ __device__ __forceinline__ void wz_epilogue4_f32(const WzConvArgs& a, int m, int
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] += rv[r];
         }
-        *reinterpret_cast<float4_t*>(reinterpret_cast<float*>(a.out) + o) = v;
+        const size_t os = a.out_cstride ? (size_t)m * a.out_cstride + a.out_coff + n4 : o;   // (channel-slice output)
+        *reinterpret_cast<float4_t*>(reinterpret_cast<float*>(a.out) + os) = v;
     } else {
         const int hw = a.hout * a.wout;
         const int b = m / hw, pix = m - b * hw;

@@ -62,6 +62,8 @@ struct WzConvArgs {
     int32_t nt_base;            // tile kernel: first 16-channel tile this launch entry serves (a head split along N, see wz_conv_rs_group_add)
     int32_t nt_live, nt_group;  // wide tile kernel (k_conv_wide.hip): 16-channel tiles that hold real columns / tiles per workgroup
     int32_t frag_ws;            // the K slices' partial sums lie in FRAGMENT order: [z][M / 16][n_pad / 16][64 lanes][4] (wide tile kernel -> grouped reduce)
+    int32_t out_coff, out_cstride;   // WZ_OUT_ACT: the output is channels [out_coff, out_coff + cout) of a tensor with out_cstride channels per
+                                     // pixel (0: cout -- the whole tensor); the residual keeps the cout pitch
 };
 
 
@@ -274,6 +276,16 @@ void wz_launch_stem_f32(const half_t* in, const float* w, const float* bias, flo
 void wz_launch_dw_f32(const float* in, const float* w, const float* bias, float* out, int n, int hin, int win, int c,
                       int hout, int wout, int stride, int pad_t, int pad_l, int act, hipStream_t s);
 void wz_launch_conv_f32(const WzConvArgs& a, hipStream_t s, bool reduce = true);   // + its split-K reduce when a.splitk > 1 (unless !reduce)
+// SSD-Inception-v2 (k_inception.hip): the 7x7 stride-2 stem (64 channels) and the 3x3 pools, each writing channels [coff, coff + C) of an
+// output tensor with cstride channels per pixel
+void wz_launch_stem7(const half_t* in, const half_t* w, const float* bias, half_t* out, int n, int hin, int win, int hout, int wout,
+                     int pad_t, int pad_l, int cstride, int coff, hipStream_t s);
+void wz_launch_stem7_f32(const half_t* in, const float* w, const float* bias, float* out, int n, int hin, int win, int hout, int wout,
+                         int pad_t, int pad_l, int cstride, int coff, bool pair, hipStream_t s);
+void wz_launch_pool3(const half_t* in, half_t* out, int n, int hin, int win, int c, int hout, int wout, int stride, int pad_t, int pad_l,
+                     bool is_max, int cstride, int coff, hipStream_t s);
+void wz_launch_pool3_f32(const float* in, float* out, int n, int hin, int win, int c, int hout, int wout, int stride, int pad_t, int pad_l,
+                         bool is_max, int cstride, int coff, hipStream_t s);
 int wz_launch_mbconv(const WzMbArgs& a, int n, hipStream_t s, bool prepare);   // -1: no kernel; else #channel groups
 int wz_launch_mbconv_wave(const WzMbArgs& a, int n, hipStream_t s, bool prepare);   // wave-per-tile variant; -2: not applicable
 int wz_launch_mbconv_cs(const WzMbArgs& a, int n, hipStream_t s, bool prepare);     // channels split over waves (small maps); -2: n/a

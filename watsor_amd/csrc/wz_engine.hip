@@ -281,7 +281,7 @@ static void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool wi
         long long tile_bytes[WZ_CONV_GROUP_MAX];
         for (uint32_t i = 0; i < e->hdr.n_ops && cnt < WZ_CONV_GROUP_MAX; ++i) {
             const WzOpDesc& op = e->ops[i];
-            if (op.kind == WZ_OP_STEM || op.kind == WZ_OP_DW || op.kind == WZ_OP_MBCONV) continue;
+            if (op.kind != WZ_OP_CONV) continue;
             WzConvArgs a;
             memset(&a, 0, sizeof(a));
             a.M = n * op.hout * op.wout;
@@ -316,6 +316,23 @@ static void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool wi
             wz_launch_dw(L.tptr[op.src], (const half_t*)(wbase + op.w_off), (const float*)(wbase + op.b_off),
                          L.tptr[op.dst], n, op.hin, op.win, op.cin, op.hout, op.wout, op.stride, op.pad_t,
                          op.pad_l, op.act, s);
+        } else if (op.kind == WZ_OP_POOL) {   // (Inception: writes its slice of the module tensor, or a tensor of its own)
+            const int cs = op.dst_c ? op.dst_c : op.cout;
+            const bool is_max = !(op.flags & WZ_OPF_POOL_AVG);
+            if (f32)
+                wz_launch_pool3_f32((const float*)L.tptr[op.src], (float*)L.tptr[op.dst], n, op.hin, op.win, op.cin, op.hout, op.wout,
+                                    op.stride, op.pad_t, op.pad_l, is_max, cs, op.dst_coff, s);
+            else
+                wz_launch_pool3(L.tptr[op.src], L.tptr[op.dst], n, op.hin, op.win, op.cin, op.hout, op.wout, op.stride, op.pad_t,
+                                op.pad_l, is_max, cs, op.dst_coff, s);
+        } else if (op.kind == WZ_OP_STEM7) {
+            const int cs = op.dst_c ? op.dst_c : op.cout;
+            if (f32)
+                wz_launch_stem7_f32(L.tptr[op.src], (const float*)(wbase + op.w_off), (const float*)(wbase + op.b_off), (float*)L.tptr[op.dst],
+                                    n, op.hin, op.win, op.hout, op.wout, op.pad_t, op.pad_l, cs, op.dst_coff, input_is_pair(e), s);
+            else
+                wz_launch_stem7(L.tptr[op.src], (const half_t*)(wbase + op.w_off), (const float*)(wbase + op.b_off), L.tptr[op.dst], n,
+                                op.hin, op.win, op.hout, op.wout, op.pad_t, op.pad_l, cs, op.dst_coff, s);
         } else if (op.kind == WZ_OP_MBCONV) {
             WzMbArgs a = mb_args(e, L, op);
             a.M = n * op.hout * op.wout;
@@ -356,9 +373,11 @@ static void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool wi
         } else {
             // Two convolutions of the extras chain in one launch (k_extras_pair.hip): a 1x1 whose output only the 3x3 stride-2 convolution behind it
             // reads, on the 5x5 / 3x3 / 2x2 maps -- three launches and three boundaries less per batch
-            if (!f32 && op.out_mode == WZ_OUT_ACT && op.ksize == 1 && i + 1 < e->hdr.n_ops) {
+            // (not for slice outputs: the pair kernel stores whole tensors)
+            if (!f32 && op.out_mode == WZ_OUT_ACT && op.ksize == 1 && op.dst_c == 0 && i + 1 < e->hdr.n_ops) {
                 const WzOpDesc& nx = e->ops[i + 1];
-                bool only = nx.kind == WZ_OP_CONV && nx.src == op.dst && nx.out_mode == WZ_OUT_ACT && op.res < 0 && nx.res < 0;
+                bool only = nx.kind == WZ_OP_CONV && nx.src == op.dst && nx.out_mode == WZ_OUT_ACT && op.res < 0 && nx.res < 0 &&
+                            nx.dst_c == 0;
                 for (uint32_t j = 0; only && j < e->hdr.n_ops; ++j)
                     if (j != i + 1 && (e->ops[j].src == op.dst || e->ops[j].res == op.dst)) only = false;
                 if (only) {
@@ -401,6 +420,10 @@ static void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool wi
             a.ksize = op.ksize; a.stride = op.stride; a.pad_t = op.pad_t; a.pad_l = op.pad_l; a.kc = op.kc;
             a.act = op.act; a.out_mode = op.out_mode;
             a.kchunks = op.ksize * op.ksize * op.kc;
+            if (op.out_mode == WZ_OUT_ACT && op.dst_c != 0) {   // a channel slice of the output tensor (load_blob checked it)
+                a.out_cstride = op.dst_c;
+                a.out_coff = op.dst_coff;
+            }
             void* final_out;
             if (op.out_mode == WZ_OUT_ACT) {
                 final_out = L.tptr[op.dst];
@@ -765,6 +788,36 @@ extern "C" int wz_device_name_of(int device, char* buf, int buflen) {
 
 extern "C" const char* wz_last_error(void) { return g_err; }
 
+// The Inception op kinds and the channel-slice outputs (format 12): every bound the kernels rely on, since they index by these fields
+// alone.  Returns false for a malformed op.
+static bool slice_op_ok(const wz_engine* e, const WzOpDesc& op) {
+    const WzBlobHeader& h = e->hdr;
+    const bool is_new = op.kind == WZ_OP_POOL || op.kind == WZ_OP_STEM7;
+    if (!is_new && !(op.kind == WZ_OP_CONV && op.dst_c != 0)) return true;   // (the MobileNet ops: checked as before)
+    if (op.out_mode != WZ_OUT_ACT || op.dst < 0 || op.res >= 0 || op.dst == op.src) return false;
+    const WzTensorDesc& in = e->tensors[op.src];
+    const WzTensorDesc& out = e->tensors[op.dst];
+    const int cs = op.dst_c ? op.dst_c : op.cout;
+    // the slice: whole 16-byte channel groups, inside the tensor, which has the op's output map
+    if (op.dst_c < 0 || cs != out.c || op.dst_coff < 0 || op.dst_coff % 8 != 0 || op.cout % 8 != 0 || op.dst_coff + op.cout > cs ||
+        out.h != op.hout || out.w != op.wout || (out.flags & WZ_TENSOR_HP))
+        return false;
+    if (in.h != op.hin || in.w != op.win || op.stride < 1 || op.stride > 2 || op.hout != (op.hin + op.stride - 1) / op.stride ||
+        op.wout != (op.win + op.stride - 1) / op.stride)
+        return false;
+    if (op.kind == WZ_OP_POOL)
+        return op.ksize == 3 && op.cin == op.cout && in.c == op.cin && !(in.flags & WZ_TENSOR_HP) && op.pad_t >= 0 && op.pad_t <= 1 &&
+               op.pad_l >= 0 && op.pad_l <= 1 && (op.flags & ~(int64_t)WZ_OPF_POOL_AVG) == 0;
+    if (op.kind == WZ_OP_STEM7) {
+        const uint64_t wbytes = h.precision == 32 ? 49ull * 3 * 64 * 4 : 64ull * 7 * 32 * 2;
+        return op.ksize == 7 && op.stride == 2 && op.cin == 3 && op.cout == 64 && in.c == 4 && op.src == e->ops[0].src &&
+               op.pad_t >= 0 && op.pad_t <= 3 && op.pad_l >= 0 && op.pad_l <= 3 &&
+               ((in.flags & WZ_TENSOR_HP) != 0) == (h.precision == 32) && (h.precision == 32 || (op.kc == 7 && op.n_pad == 64)) &&
+               op.w_off >= 0 && (uint64_t)op.w_off + wbytes <= h.weights_bytes && op.b_off >= 0 && (uint64_t)op.b_off + 256 <= h.weights_bytes;
+    }
+    return in.c == op.cin;   // a sliced conv reads a whole tensor
+}
+
 static int load_blob(wz_engine* e, const char* path) {
     FILE* f = fopen(path, "rb");
     if (!f) return wz_fail(WZ_ENOENT, "engine file not found: %s", path);
@@ -797,6 +850,8 @@ static int load_blob(wz_engine* e, const char* path) {
     e->ops = reinterpret_cast<const WzOpDesc*>(e->blob.data() + h.ops_off);
     for (uint32_t i = 0; i < h.n_ops; ++i) {
         const WzOpDesc& op = e->ops[i];
+        if (op.kind < WZ_OP_STEM || op.kind > WZ_OP_STEM7)   // (an unknown kind would otherwise run as a conv)
+            return wz_fail(WZ_EFORMAT, "%s: op %u (%s) has kind %d, which this runtime does not know", path, i, op.name, op.kind);
         if (op.src < 0 || op.src >= (int)h.n_tensors || op.dst >= (int)h.n_tensors || op.res >= (int)h.n_tensors ||
             (op.out_mode == WZ_OUT_ACT && op.dst < 0) || op.w_off < 0 || (uint64_t)op.w_off >= h.weights_bytes ||
             (op.kind == WZ_OP_CONV && (op.n_pad % 32 != 0 || op.cin % 8 != 0 || op.n_pad < op.cout ||
@@ -813,6 +868,8 @@ static int load_blob(wz_engine* e, const char* path) {
                                 op.nmid_pad < op.cmid || op.we_off < 0 || (uint64_t)op.we_off >= h.weights_bytes ||
                                 op.be_off < 0 || (uint64_t)op.be_off >= h.weights_bytes)))))
             return wz_fail(WZ_EFORMAT, "%s: op %u (%s) is malformed", path, i, op.name);
+        if (!slice_op_ok(e, op))
+            return wz_fail(WZ_EFORMAT, "%s: op %u (%s): malformed pool / 7x7 stem / channel-slice output", path, i, op.name);
         if (op.dst2 != 0) {
             const WzTensorDesc* t2 = (op.dst2 > 0 && op.dst2 <= (int64_t)h.n_tensors) ? &e->tensors[op.dst2 - 1] : nullptr;
             if (op.kind != WZ_OP_MBCONV || !t2 || op.cin0 <= 0 || t2->h != op.hin || t2->w != op.win ||
@@ -834,7 +891,7 @@ static int load_blob(wz_engine* e, const char* path) {
             wz_engine::Lane none;
             if (wz_launch_mbconv_hp(mb_args(e, none, op), 1, nullptr, true) != 0)
                 return wz_fail(WZ_EFORMAT, "%s: op %u (%s): no split-operand kernel for this shape", path, i, op.name);
-        } else if (op.kind == WZ_OP_STEM && h.precision == 32 && (e->tensors[op.src].flags & WZ_TENSOR_HP) &&
+        } else if ((op.kind == WZ_OP_STEM || op.kind == WZ_OP_STEM7) && h.precision == 32 && (e->tensors[op.src].flags & WZ_TENSOR_HP) &&
                    !(op.dst >= 0 && (e->tensors[op.dst].flags & WZ_TENSOR_HP))) {
             // the fp32 program's stem reads the network input as a hi + lo pair (wz_k_stem_f32)
         } else if ((e->tensors[op.src].flags & WZ_TENSOR_HP) || (op.dst >= 0 && (e->tensors[op.dst].flags & WZ_TENSOR_HP)) ||

@@ -8,9 +8,12 @@
 #include <stdint.h>
 
 #define WZ_MAGIC 0x35335A57u /* "WZ35" */
-#define WZ_FORMAT_VERSION 11u   // 11: the float-form chunk buffer's scaling changed (k_hp_ops.h, round 6): depthwise taps of WZ_OPF_QENC blocks carry 6 * 2^60 / (2 - 2^-13)
+#define WZ_FORMAT_VERSION 12u   // 12: the SSD-Inception-v2 op kinds (WZ_OP_POOL, WZ_OP_STEM7) and channel-slice outputs (dst_coff / dst_c);
+                                // 11: the float-form chunk buffer's scaling changed (k_hp_ops.h): depthwise taps of WZ_OPF_QENC blocks carry 6 * 2^60 / (2 - 2^-13)
 
-enum WzOpKind { WZ_OP_STEM = 1, WZ_OP_DW = 2, WZ_OP_CONV = 3, WZ_OP_MBCONV = 4 };
+// WZ_OP_POOL: 3x3 max / average pool, stride 1 or 2, TF 'SAME' (max ignores the padding, average divides by the in-image taps);
+// WZ_OP_STEM7: 7x7 stride-2 conv (+ bias, relu6) on the 4-channel network input, 64 output channels (k_inception.hip)
+enum WzOpKind { WZ_OP_STEM = 1, WZ_OP_DW = 2, WZ_OP_CONV = 3, WZ_OP_MBCONV = 4, WZ_OP_POOL = 5, WZ_OP_STEM7 = 6 };
 enum WzOutMode { WZ_OUT_ACT = 0, WZ_OUT_BOX = 1, WZ_OUT_CLS = 2, WZ_OUT_HEAD = 3 };
 enum WzAct { WZ_ACT_NONE = 0, WZ_ACT_RELU6 = 1 };
 enum WzTensorFlags { WZ_TENSOR_HP = 1 };
@@ -18,9 +21,10 @@ enum WzOpFlags {
     WZ_OPF_HP = 1, WZ_OPF_HP_OUT = 2,   // split-operand block (k_mbconv_hp.hip) / its output tensor is a hi + lo pair
     WZ_OPF_QENC = 4,                    // ... whose chunk buffer holds the 16-bit float form of relu6(x) / 6 (the robust program; k_hp_ops.h:
                                         // depthwise weights carry 6 * 2^60 / (2 - 2^-13), the depthwise bias is the plain one)
-    WZ_OPF_DUP_OUT = 8                  // ... whose output tensor has 2 * cout PLAIN channels holding the fp16 output twice: the 1x1 conv behind it
+    WZ_OPF_DUP_OUT = 8,                 // ... whose output tensor has 2 * cout PLAIN channels holding the fp16 output twice: the 1x1 conv behind it
                                         // (Conv_1 of the robust program) has K = 2 * cout with the hi halves of its weights over the first copy and
                                         // the lo halves over the second, i.e. split WEIGHTS on the plain convolution kernels
+    WZ_OPF_POOL_AVG = 16                // WZ_OP_POOL: average (else max)
 };
 
 #pragma pack(push, 1)
@@ -60,8 +64,11 @@ struct WzOpDesc {  // 256 bytes
     int32_t n_box;                          // WZ_OUT_HEAD: leading columns that go to the box-encoding buffer
     // WZ_OP_MBCONV (one inverted-residual block = [1x1 expand ->] depthwise 3x3 -> 1x1 project [+ residual]):
     // cin/cout/n_pad/kc/w_off/b_off describe the PROJECT conv (cin = cmid); the fields below the rest.
-    int32_t cmid;                           // depthwise channels (= expanded channels)
-    int32_t cin0;                           // block input channels (expand K); 0 = no expand stage
+    // WZ_OP_CONV / WZ_OP_POOL / WZ_OP_STEM7 use the first two of these fields for a channel-slice output (a concat by slice: each branch
+    // of an Inception module writes its channels of the module's tensor): dst_c = channels per pixel of `dst` (0: cout, the whole
+    // tensor), dst_coff = the slice's first channel
+    union { int32_t cmid; int32_t dst_coff; };   // depthwise channels (= expanded channels)
+    union { int32_t cin0; int32_t dst_c; };      // block input channels (expand K); 0 = no expand stage
     int32_t kc0;                            // 32-channel K chunks of the expand conv
     int32_t cmid_pad;                       // cmid rounded up to 32 (row length of the packed depthwise weights)
     int32_t nmid_pad;                       // packed output columns of the expand conv
@@ -87,5 +94,8 @@ struct WzOpDesc {  // 256 bytes
 //  WZ_OP_CONV : half   w[n_pad/16][taps][kc][64 lanes][8]  where lane l of N-tile t holds
 //               W[k = chunk*32 + (l>>4)*8 + j][n = t*16 + (l&15)], zero beyond cin / cout
 //               (exactly the A-operand fragment of v_mfma_f32_16x16x32_f16), float bias[n_pad]
+//  WZ_OP_STEM7: fp16 engine: the WZ_OP_CONV layout with 1 tap, kc = 7, n_pad = 64 over K = tap * 4 + c (tap = ky * 7 + kx, c < 3;
+//               channel 3 and taps 49 .. 55 zero); fp32 engine: float w[49][3][64]; float bias[64]
+//  WZ_OP_POOL : no weights
 //  WZ_OP_MBCONV: expand + project in the WZ_OP_CONV layout, depthwise as WZ_OP_DW with rows padded to cmid_pad
 //               (WZ_OPF_HP: every GEMM weight twice, hi and lo halves; depthwise weights fp32)

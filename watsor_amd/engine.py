@@ -4,7 +4,8 @@ MI355X analogue of `watsor/engine.py:17-107` (TensorRT engine builder CLI, run o
 application starts, auto-invoked by `watsor/main_for_gpu.py:17-26` when `gpu.uff`/`gpu.onnx` exists
 without `gpu.trt`).  Same command line shape (`-i/--input`, `-p/--precision {32,16}`, `-w`, `-mw`,
 `-mh`, `-o/--output`); the input is an `.npz` of TF variables (names as in the frozen graph of
-`ssd_mobilenet_v2_coco`, TF layouts, BatchNorm unfolded) or the literal `synthetic[:seed]`.
+`ssd_mobilenet_v2_coco` or `ssd_inception_v2_coco`, TF layouts, BatchNorm unfolded), a frozen graph, or the literal
+`synthetic[:seed]` (MobileNet-v2) / `synthetic_inception_v2[:seed]`.  The network family is read from the variable names.
 
 What building does: fold every FusedBatchNorm into its convolution (fp64), round to fp16, lay the
 weights out in the MFMA fragment order the HIP kernels read (csrc/wz_program.h), generate the anchor
@@ -20,11 +21,13 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from . import arch
+from . import arch, inception
 from .anchors import ssd_anchor_table
 
 MAGIC = 0x35335A57
-FORMAT_VERSION = 11
+FORMAT_VERSION = 12
+FAMILIES = {"MobilenetV2": "SSD-MobileNet-v2", "InceptionV2": "SSD-Inception-v2"}   # feature extractor scope -> network
+POOL_AVG = 16              # WzOpFlags::WZ_OPF_POOL_AVG (csrc/wz_program.h)
 BN_EPSILON = 1e-3          # watsor/test/model/prepare.py:48
 
 DEFAULT_POST = dict(max_total=100, max_per_class=100, score_threshold=1e-8, iou_threshold=0.6,
@@ -93,6 +96,26 @@ def _align(n: int, a: int = 256) -> int:
     return (n + a - 1) // a * a
 
 
+def detect_family(weights: Dict[str, np.ndarray]) -> str:
+    """The feature extractor the variables belong to ("MobilenetV2" or "InceptionV2"), from their `FeatureExtractor/<name>/` scope;
+    ValueError for any other (or for a mixture)."""
+    found = sorted({k.split("/")[1] for k in weights if k.startswith("FeatureExtractor/") and k.count("/") >= 2})
+    if len(found) == 1 and found[0] in FAMILIES:
+        return found[0]
+    raise ValueError("the model's feature extractor is %s; this engine builds %s" % (
+        " + ".join(found) if found else "unknown (no FeatureExtractor/ variables)",
+        " and ".join("%s (FeatureExtractor/%s/)" % (v, k) for k, v in FAMILIES.items())))
+
+
+def fold_stem7(W: Dict[str, np.ndarray], op: "arch.Op") -> np.ndarray:
+    """The separable stem (depthwise [k,k,c,m], pointwise [1,1,c*m,cout]) as one dense [k,k,c,cout] kernel, float64:
+    W[ky,kx,c,o] = sum_m dw[ky,kx,c,m] * pw[0,0,c*m_count+m,o] (TF orders the depthwise outputs channel-major)."""
+    dw = W[op.scope + "/depthwise_weights"].astype(np.float64)
+    pw = W[op.scope + "/pointwise_weights"].astype(np.float64)
+    k, _, c, m = dw.shape
+    return np.einsum("yxcm,cmo->yxco", dw, pw[0, 0].reshape(c, m, pw.shape[3]))
+
+
 def fold_batch_norm(W: Dict[str, np.ndarray], op: "arch.Op"):
     """(weights float64 in TF layout, bias float64[cout]) with BatchNorm folded in."""
     if op.out_mode == arch.OUT_HEAD:                                     # [k,k,cin, a*4 | a*91], biases only
@@ -102,6 +125,8 @@ def fold_batch_norm(W: Dict[str, np.ndarray], op: "arch.Op"):
         return w, b.astype(np.float64)
     if op.kind == arch.OP_DW:
         w = W[op.scope + "/depthwise_weights"].astype(np.float64)        # [k,k,C,1]
+    elif op.kind == arch.OP_STEM7:
+        w = fold_stem7(W, op)                                            # [7,7,3,64], before the BatchNorm
     else:
         w = W[op.scope + "/weights"].astype(np.float64)                  # [k,k,cin,cout]
     if not op.has_bn:
@@ -157,6 +182,20 @@ def stem_k_rows(w: np.ndarray) -> np.ndarray:
     return out
 
 
+def stem7_k_rows(w: np.ndarray) -> np.ndarray:
+    """Dense stem weights [7,7,3,cout] -> [224, cout] with k = tap * 4 + c (tap = ky * 7 + kx): a lane group's 8 K values are the
+    4-channel pixels of two taps as they lie in the input tensor (csrc/k_inception.hip); channel 3 and taps 49 .. 55 are zero.
+    49 taps x 4 = 196 rows, seven 32-row MFMA chunks."""
+    k, _, c, cout = w.shape
+    out = np.zeros((STEM7_KC * 32, cout), w.dtype)
+    for t in range(k * k):
+        out[t * 4:t * 4 + c] = w[t // k, t % k]
+    return out
+
+
+STEM7_KC = 7
+
+
 def pack_conv_weights_f32(w: np.ndarray, n_pad: int, kc: int) -> np.ndarray:
     """[k,k,cin,cout] -> fp32 [n_pad/16][taps][kc][64][4]: lane (r16, g) of N-tile t holds W[k = c*16 + 4g + j][n = t*16 + r16]
     (the A operands of four v_mfma_f32_16x16x4_f32, one float4 load per lane; csrc/k_f32.hip)."""
@@ -173,7 +212,11 @@ OP_RECORD_BYTES = 256
 
 
 def _op_record(op, tindex, n_pad, kc, w_off, b_off, mb) -> bytes:
-    """struct WzOpDesc of csrc/wz_program.h."""
+    """struct WzOpDesc of csrc/wz_program.h.  An op that writes a channel slice of its output (Op.cdst) carries the slice in the
+    fields the fused blocks use for cmid / cin0 (dst_coff / dst_c); every op of the MobileNet programs leaves them as they were."""
+    if getattr(op, "cdst", 0):
+        assert op.kind in (arch.OP_CONV, arch.OP_POOL, arch.OP_STEM7) and not mb["cmid"] and not mb["cin0"]
+        mb = dict(mb, cmid=op.coff, cin0=op.cdst)
     return struct.pack(
         "<20i2q8i8q64s",
         op.kind, tindex[op.src], tindex.get(op.dst, -1) if op.out_mode == arch.OUT_ACT else -1,
@@ -190,7 +233,9 @@ def _op_record(op, tindex, n_pad, kc, w_off, b_off, mb) -> bytes:
 
 
 def assign_slots(prog: "arch.Program", tensor_names: List[str]) -> List[int]:
-    """Liveness-based buffer sharing: tensors whose lifetimes do not overlap reuse one HBM buffer."""
+    """Liveness-based buffer sharing: tensors whose lifetimes do not overlap reuse one HBM buffer.  A tensor written by several ops
+    (the concat of an Inception module, one slice per branch) lives from its first writer on; the slot is taken before that op's
+    inputs are released, so no writer's input can share it."""
     index = {n: i for i, n in enumerate(tensor_names)}
     last_use = {n: -1 for n in tensor_names}
     for oi, op in enumerate(prog.ops):
@@ -207,7 +252,7 @@ def assign_slots(prog: "arch.Program", tensor_names: List[str]) -> List[int]:
     for oi, op in enumerate(prog.ops):
         never_read = []                                      # released only after ALL outputs of the op have their slots
         for out in ([op.dst, op.dst2] if op.out_mode == arch.OUT_ACT else []):
-            if out is None:
+            if out is None or slot_of[index[out]] >= 0:     # (a later writer of a concat tensor: the slot is taken)
                 continue
             need = size[out]
             best = None
@@ -256,12 +301,12 @@ def build_engine(weights: Dict[str, np.ndarray], precision: int = 16, model_widt
         fuse = False                 # the fp32 engine runs one op per layer (csrc/k_f32.hip)
     if model_width != model_height:
         raise ValueError("square model input expected")
-    cfg = dict(DEFAULT_POST)
-    cfg.update(post or {})
-    opt = dict(DEFAULT_OPTIONS)
-    opt.update(options or {})
-    if opt["resize"] not in RESIZE_MODES:
-        raise ValueError("resize mode %r: expected one of %s" % (opt["resize"], ", ".join(RESIZE_MODES)))
+    if any(k.startswith("FeatureExtractor/") for k in weights) and detect_family(weights) == "InceptionV2":
+        if robust or hp_upto not in (None, -1) or conv1_split:
+            raise ValueError("the robust, split-operand and fused-block programs are SSD-MobileNet-v2 programs; an SSD-Inception-v2 "
+                             "engine is built with -p 16 or -p 32 only")
+        return build_inception_engine(weights, precision, model_width, model_height, post=post, options=options)
+    cfg, opt = _post_options(post, options)
     if robust and not (precision == 16 and fuse and fuse_stem and hp_upto is None):
         raise ValueError("the robust program is the `-p 16` program with fused blocks")
     if robust and not (-1 <= float_form_upto <= FLOAT_FORM_LAST_BLOCK):
@@ -272,12 +317,7 @@ def build_engine(weights: Dict[str, np.ndarray], precision: int = 16, model_widt
         hp_upto = (arch.HP_ALL_BLOCKS if robust else arch.HP_LAST_BLOCK) if (precision == 16 and fuse and fuse_stem) else -1
     prog = arch.build(model_width, fuse=fuse, fuse_stem=fuse_stem, hp_upto=hp_upto, input_pair=precision == 32, tap_in_block=tap_in_block,
                       conv1_split=robust if conv1_split is None else bool(conv1_split))
-    missing = [n for n in prog.variable_shapes() if n not in weights]
-    if missing:
-        raise KeyError("model is missing %d variables, e.g. %s" % (len(missing), missing[0]))
-    for name, shape in prog.variable_shapes().items():
-        if tuple(weights[name].shape) != tuple(shape):
-            raise ValueError("%s has shape %s, expected %s" % (name, weights[name].shape, shape))
+    _check_variables(prog, weights)
 
     tensor_names = ["input"] + [t for op in prog.ops if op.out_mode == arch.OUT_ACT for t in (op.dst, op.dst2) if t]
     tindex = {n: i for i, n in enumerate(tensor_names)}
@@ -402,8 +442,12 @@ def build_engine(weights: Dict[str, np.ndarray], precision: int = 16, model_widt
         else:
             w_off, b_off, n_pad, kc = put_conv(op)
         op_recs.append(_op_record(op, tindex, n_pad, kc, w_off, b_off, mb))
-    assert all(len(r) == OP_RECORD_BYTES for r in op_recs)
+    return _write_image(prog, precision, model_width, cfg, opt, tensor_names, slots, op_recs, wblob, hp_upto + 1)
 
+
+def _write_image(prog, precision, model_width, cfg, opt, tensor_names, slots, op_recs, wblob, hp_blocks) -> bytes:
+    """Header, tensor table, op records, anchors and weight blob as one image (struct WzBlobHeader of csrc/wz_program.h)."""
+    assert all(len(r) == OP_RECORD_BYTES for r in op_recs)
     tensor_recs = []
     for n, s in zip(tensor_names, slots):
         t = prog.tensors[n]
@@ -426,7 +470,7 @@ def build_engine(weights: Dict[str, np.ndarray], precision: int = 16, model_widt
         cfg["max_total"], cfg["max_per_class"],
         cfg["score_threshold"], cfg["iou_threshold"], sy, sx, sh, sw,
         tensors_off, ops_off, anchors_off, weights_off, len(wblob), total,
-        max(slots) + 1, hp_upto + 1, RESIZE_MODES[opt["resize"]], 1 if opt["clip_after_nms"] else 0, *([0] * 8))
+        max(slots) + 1, hp_blocks, RESIZE_MODES[opt["resize"]], 1 if opt["clip_after_nms"] else 0, *([0] * 8))
     assert len(header) == header_size
     out = bytearray(total)
     out[:header_size] = header
@@ -435,6 +479,92 @@ def build_engine(weights: Dict[str, np.ndarray], precision: int = 16, model_widt
     out[anchors_off:anchors_off + anchors.nbytes] = anchors.tobytes()
     out[weights_off:] = wblob
     return bytes(out)
+
+
+def _post_options(post: Optional[dict], options: Optional[dict]):
+    cfg = dict(DEFAULT_POST)
+    cfg.update(post or {})
+    opt = dict(DEFAULT_OPTIONS)
+    opt.update(options or {})
+    if opt["resize"] not in RESIZE_MODES:
+        raise ValueError("resize mode %r: expected one of %s" % (opt["resize"], ", ".join(RESIZE_MODES)))
+    return cfg, opt
+
+
+def _check_variables(prog: "arch.Program", weights: Dict[str, np.ndarray]) -> None:
+    missing = [n for n in prog.variable_shapes() if n not in weights]
+    if missing:
+        raise KeyError("model is missing %d variables, e.g. %s" % (len(missing), missing[0]))
+    for name, shape in prog.variable_shapes().items():
+        if tuple(weights[name].shape) != tuple(shape):
+            raise ValueError("%s has shape %s, expected %s" % (name, weights[name].shape, shape))
+
+
+def head_kernel_sizes(weights: Dict[str, np.ndarray]) -> List[int]:
+    """Kernel size of each of the six box predictors, from their weights ([k,k,cin,cols], k = 1 or 3)."""
+    ks = []
+    for i in range(6):
+        name = "BoxPredictor_%d/BoxEncodingPredictor/weights" % i
+        if name not in weights:
+            raise KeyError("model is missing %s" % name)
+        shp = weights[name].shape
+        if len(shp) != 4 or shp[0] != shp[1] or shp[0] not in (1, 3):
+            raise ValueError("%s has shape %s: a 1x1 or 3x3 box predictor expected" % (name, tuple(shp)))
+        ks.append(int(shp[0]))
+    return ks
+
+
+def build_inception_engine(weights: Dict[str, np.ndarray], precision: int = 16, model_width: int = 300, model_height: int = 300,
+                           post: Optional[dict] = None, options: Optional[dict] = None) -> bytes:
+    """The SSD-Inception-v2 engine image (inception.py): one op per layer, module branches written by channel slice into the module
+    tensors, the separable stem folded into one dense 7x7 conv (OP_STEM7).  `-p 16`: fp16 weights and tensors, fp32 sums (the plain
+    fp16 program: 3.2e-4 of the scores on the CPU emulation); `-p 32`: fp32 throughout, input as a hi + lo pair."""
+    if precision not in (16, 32):
+        raise ValueError("precision must be 16 or 32")
+    if model_width != model_height:
+        raise ValueError("square model input expected")
+    cfg, opt = _post_options(post, options)
+    prog = inception.build(model_width, input_pair=precision == 32, head_ks=head_kernel_sizes(weights))
+    _check_variables(prog, weights)
+    tensor_names = ["input"] + list(dict.fromkeys(op.dst for op in prog.ops if op.out_mode == arch.OUT_ACT))
+    tindex = {n: i for i, n in enumerate(tensor_names)}
+    slots = assign_slots(prog, tensor_names)
+    wblob = bytearray()
+
+    def put(arr: np.ndarray) -> int:
+        off = _align(len(wblob))
+        wblob.extend(b"\0" * (off - len(wblob)))
+        wblob.extend(arr.tobytes())
+        return off
+
+    op_recs = []
+    for op in prog.ops:
+        mb = dict(cmid=0, cin0=0, kc0=0, cmid_pad=0, nmid_pad=0, we_off=0, be_off=0, wd_off=0, bd_off=0, stem=0, stem_pad=0)
+        n_pad, kc, w_off, b_off = 0, 0, 0, 0
+        if op.kind == arch.OP_POOL:
+            mb["flags"] = 0 if op.pool_max else POOL_AVG
+        elif op.kind == arch.OP_STEM7:
+            w, b = fold_batch_norm(weights, op)                      # dense [7,7,3,64]
+            if precision == 32:                                      # fp32 [tap][c][cout]: the direct kernel (k_inception.hip)
+                w_off = put(w.reshape(op.k * op.k * op.cin, op.cout).astype(np.float32))
+            else:                                                    # one tap, K = tap * 4 + c in 7 chunks of 32
+                n_pad, kc = op.cout, STEM7_KC
+                w_off = put(pack_conv_weights(stem7_k_rows(w).reshape(1, 1, STEM7_KC * 32, op.cout).astype(np.float32), n_pad, kc))
+            b_off = put(b.astype(np.float32))
+        else:
+            w, b = fold_batch_norm(weights, op)
+            n_pad = _align(op.cout, 64 if op.cout >= 256 else 32)
+            if precision == 32:
+                kc = (op.cin + 15) // 16
+                w_off = put(pack_conv_weights_f32(w.astype(np.float32), n_pad, kc))
+            else:
+                kc = (op.cin + 31) // 32
+                w_off = put(pack_conv_weights(w.astype(np.float32), n_pad, kc))
+            bp = np.zeros(n_pad, np.float32)
+            bp[:op.cout] = b
+            b_off = put(bp)
+        op_recs.append(_op_record(op, tindex, n_pad, kc, w_off, b_off, mb))
+    return _write_image(prog, precision, model_width, cfg, opt, tensor_names, slots, op_recs, wblob, 0)
 
 
 # The `-p 16` program's score tolerance (1e-3 against the fp32 detector) was established on weights whose channels all live at one
@@ -450,12 +580,14 @@ ROBUST_VALIDATED_DECADES = 1.5
 
 def channel_spread_decades(weights: Dict[str, np.ndarray]) -> float:
     """Median over the network's expand convolutions (and the stem) of log10(p95 / p5) of the per-output-channel amplitude of
-    the BatchNorm-folded layer, sqrt(sum w^2 + b^2): ~0.2 for He-initialised weights, d for `synth.spread_channel_scales(W, d)`."""
-    prog = arch.build(fuse=False)
+    the BatchNorm-folded layer, sqrt(sum w^2 + b^2): ~0.2 for He-initialised weights, d for `synth.spread_channel_scales(W, d)`.
+    SSD-Inception-v2 weights: the same measure over all of that network's BatchNorm-ReLU6 convolutions, the stem included."""
+    inc = detect_family(weights) == "InceptionV2"
+    prog = inception.build() if inc else arch.build(fuse=False)
     spreads = []
     for op in prog.ops:
-        if op.kind in (arch.OP_CONV, arch.OP_STEM) and op.act == arch.ACT_RELU6 and op.has_bn and \
-                (op.scope.endswith("/expand") or op.scope.endswith("MobilenetV2/Conv")):
+        if op.kind in (arch.OP_CONV, arch.OP_STEM, arch.OP_STEM7) and op.act == arch.ACT_RELU6 and op.has_bn and \
+                (inc or op.scope.endswith("/expand") or op.scope.endswith("MobilenetV2/Conv")):
             w, b = fold_batch_norm(weights, op)
             amp = np.sqrt((w.reshape(-1, w.shape[-1]) ** 2).sum(0) + b ** 2)
             lo, hi = np.percentile(amp, [5, 95])
@@ -481,6 +613,9 @@ def load_model(model_path: str):
 
 
 def load_weights(model_path: str) -> Dict[str, np.ndarray]:
+    if model_path.startswith("synthetic_inception_v2"):
+        from .synth import synthetic_inception_v2
+        return synthetic_inception_v2(int(model_path.split(":")[1]) if ":" in model_path else 1234)
     if model_path.startswith("synthetic"):
         from .synth import synthetic_weights
         seed = int(model_path.split(":")[1]) if ":" in model_path else 1234
@@ -501,7 +636,8 @@ def main(argv=None) -> int:
     parser = argparse.ArgumentParser(description="Utility to build the MI355X engine prior to inference.",
                                      formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     parser.add_argument("-i", "--input", dest="model_path", metavar="MODEL_PATH", required=True,
-                        help="TF variables as .npz, a frozen_inference_graph.pb, or synthetic[:seed]")
+                        help="TF variables as .npz or a frozen_inference_graph.pb of SSD-MobileNet-v2 or SSD-Inception-v2, or "
+                             "synthetic[:seed] (MobileNet-v2) / synthetic_inception_v2[:seed]")
     parser.add_argument("-p", "--precision", type=int, choices=[32, 16], default=16,
                         help="activation/weight storage precision of the engine")
     parser.add_argument("-w", "--workspace", default=1024, type=int,
@@ -536,6 +672,26 @@ def main(argv=None) -> int:
     post, options = apply_graph_settings(settings, args.model_width, args.model_height, None, options)
     if settings:
         print("Settings read from the graph: " + ", ".join("%s=%s" % (k, v) for k, v in sorted(settings.items()) if k != "anchor_vectors"))
+    family = detect_family(weights)
+    print("Network: %s (FeatureExtractor/%s/)." % (FAMILIES[family], family))
+    if family == "InceptionV2":
+        if args.robust == "on" or args.plain_fp16:
+            raise ValueError("--robust on and --plain-fp16 select SSD-MobileNet-v2 programs; an SSD-Inception-v2 engine is built with "
+                             "-p 16 (fp16, scores within 1e-3 of the fp32 detector on He-scaled weights) or -p 32")
+        if args.precision == 16 and args.precision_check != "off":
+            spread = channel_spread_decades(weights)
+            print("Per-channel dynamic range of the folded convolutions: %.2f decades (the -p 16 program's 1e-3 score tolerance is "
+                  "validated up to %.2f)." % (spread, SPREAD_VALIDATED_DECADES))
+            if spread > SPREAD_VALIDATED_DECADES:
+                msg = ("these weights spread their channels over %.2f decades: the -p 16 engine's scores may differ from the fp32 "
+                       "detector's by more than 1e-3; build with -p 32 if that tolerance matters" % spread)
+                if args.precision_check == "error":
+                    raise ValueError(msg)
+                print("WARNING: " + msg, file=sys.stderr)
+        engine = build_engine(weights, args.precision, args.model_width, args.model_height, post=post, options=options)
+        save_engine(engine, args.engine_path)
+        print("MI355X engine saved to {} ({:.1f} MB)".format(args.engine_path, len(engine) / 1e6))
+        return 0
     robust = args.robust == "on"
     if args.precision == 16 and not args.plain_fp16 and (args.precision_check != "off" or args.robust == "auto"):
         spread = channel_spread_decades(weights)
