@@ -22,6 +22,7 @@ FE = "FeatureExtractor/MobilenetV2/"
 # op kinds understood by the runtime (keep in sync with csrc/wz_program.h)
 OP_STEM, OP_DW, OP_CONV, OP_MBCONV = 1, 2, 3, 4   # OP_MBCONV: fused inverted-residual block (csrc/k_mbconv.hip)
 OP_POOL, OP_STEM7 = 5, 6   # 3x3 max / average pool, 7x7 stride-2 stem conv on the network input (the Inception program, inception.py)
+OP_DWSEP = 7               # fused separable layer: depthwise 3x3 -> 1x1 pointwise, both + ReLU6 (the MobileNet-v1 program, mobilenet_v1.py)
 # output modes of OP_CONV
 OUT_ACT, OUT_BOX, OUT_CLS, OUT_HEAD = 0, 1, 2, 3   # OUT_HEAD: box columns then class columns, one launch
 ACT_NONE, ACT_RELU6 = 0, 1
@@ -109,7 +110,7 @@ class Program:
         out: Dict[str, Tuple[int, ...]] = {}
         flat: List[Op] = []
         for op in self.ops:
-            flat.extend(op.parts if op.kind == OP_MBCONV else [op])
+            flat.extend(op.parts if op.kind in (OP_MBCONV, OP_DWSEP) else [op])
         for op in flat:
             if op.kind == OP_POOL:
                 continue

@@ -111,6 +111,21 @@ struct WzMbArgs {
                                 // (only shapes whose results are bit-identical to the throughput shapes' may depend on it)
 };
 
+// One separable layer of MobileNet-v1 (k_dwsep.hip): depthwise 3x3 + ReLU6 -> 1x1 pointwise + ReLU6.  cin = depthwise channels = pointwise K.
+struct WzDwsepArgs {
+    const half_t* in;      // NHWC fp16, cin channels
+    const half_t* wd;      // depthwise weights [9][cin] (the WZ_OP_DW layout)
+    const float* bd;       // [cin]
+    const half_t* wp;      // pointwise weights, MFMA A fragments [n_pad/16][kc][64][8] (the WZ_OP_CONV layout, one tap)
+    const float* bp;       // [n_pad]
+    half_t* out;           // NHWC fp16, cout channels
+    int32_t M;             // n * hout * wout
+    int32_t hin, win, hout, wout;
+    int32_t cin, kc, cout, n_pad;
+    int32_t stride, pad_t, pad_l;
+    unsigned long long* dbg;   // WZ_LANE_STAMPS builds: the launch's stamp block, else nullptr
+};
+
 // Per-camera filter state resident in HBM (see wz_set_camera_filter).
 struct WzCamFilter {
     int32_t enabled, width, height, n_zones;   // enabled: bit 0 = filters on, bit 1 = drop mode (failing rows zeroed)
@@ -295,6 +310,8 @@ int wz_launch_mbconv_hp(const WzMbArgs& a, int n, hipStream_t s, bool prepare); 
 // phase 0: both launches, 1: the first only, 2: the second only; prepare: kernel attributes (phase ignored).  -1: no kernel for this shape
 int wz_mbconv_hp2_applies(const WzMbArgs& a, int n);
 int wz_launch_mbconv_hp2(const WzMbArgs& a, int n, hipStream_t s, bool prepare, int phase);
+// one launch per separable layer (k_dwsep.hip); prepare: evaluate the shape predicate only.  -1: no kernel covers this shape
+int wz_launch_dwsep(const WzDwsepArgs& a, hipStream_t s, bool prepare);
 
 #define WZ_HIST_BINS 1024
 #define WZ_CAND_CAP 4096

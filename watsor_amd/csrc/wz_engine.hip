@@ -252,6 +252,24 @@ static WzMbArgs mb_args(wz_engine* e, const Lane& L, const WzOpDesc& op) {
     return a;
 }
 
+// one separable layer (WZ_OP_DWSEP); `L` without tensors (load-time check): the pointers stay null
+static WzDwsepArgs dwsep_args(wz_engine* e, const Lane& L, const WzOpDesc& op, int n) {
+    const uint8_t* wbase = e->d_weights;
+    WzDwsepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.in = L.tptr.empty() ? nullptr : L.tptr[op.src];
+    a.out = L.tptr.empty() ? nullptr : L.tptr[op.dst];
+    a.wd = (const half_t*)(wbase + op.wd_off);
+    a.bd = (const float*)(wbase + op.bd_off);
+    a.wp = (const half_t*)(wbase + op.w_off);
+    a.bp = (const float*)(wbase + op.b_off);
+    a.M = n * op.hout * op.wout;
+    a.hin = op.hin; a.win = op.win; a.hout = op.hout; a.wout = op.wout;
+    a.cin = op.cin; a.kc = op.kc; a.cout = op.cout; a.n_pad = op.n_pad;
+    a.stride = op.stride; a.pad_t = op.pad_t; a.pad_l = op.pad_l;
+    return a;
+}
+
 // with_post: the post-processing chain follows in the same stream (it consumes -- and resets -- the candidate list)
 static void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool with_post = true) {
     hipStream_t s = L.stream;
@@ -333,6 +351,10 @@ static void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool wi
             else
                 wz_launch_stem7(L.tptr[op.src], (const half_t*)(wbase + op.w_off), (const float*)(wbase + op.b_off), L.tptr[op.dst], n,
                                 op.hin, op.win, op.hout, op.wout, op.pad_t, op.pad_l, cs, op.dst_coff, s);
+        } else if (op.kind == WZ_OP_DWSEP) {   // (load_blob refused every shape wz_launch_dwsep does not cover)
+            WzDwsepArgs a = dwsep_args(e, L, op, n);
+            WZ_STAMP_ARG(a);
+            if (wz_launch_dwsep(a, s, false) != 0) L.launch_failed = (int)i + 1;
         } else if (op.kind == WZ_OP_MBCONV) {
             WzMbArgs a = mb_args(e, L, op);
             a.M = n * op.hout * op.wout;
@@ -620,7 +642,8 @@ static int run_batch(wz_engine* e, int slot, int n) {
     auto failed = [&]() -> int {   // a split-operand block no kernel took (the load-time check prepared batch 1 only): nothing may run on stale data
         const int op = L.launch_failed - 1;
         L.launch_failed = 0;
-        return wz_fail(WZ_EFORMAT, "no split-operand kernel took op %d (%s) at batch %d", op, e->ops[op].name, n);
+        return wz_fail(WZ_EFORMAT, "no %s kernel took op %d (%s) at batch %d",
+                       e->ops[op].kind == WZ_OP_DWSEP ? "depthwise-separable" : "split-operand", op, e->ops[op].name, n);
     };
     const int key = n | (L.rows ? 1 << 16 : 0);
     L.key = key;
@@ -850,7 +873,7 @@ static int load_blob(wz_engine* e, const char* path) {
     e->ops = reinterpret_cast<const WzOpDesc*>(e->blob.data() + h.ops_off);
     for (uint32_t i = 0; i < h.n_ops; ++i) {
         const WzOpDesc& op = e->ops[i];
-        if (op.kind < WZ_OP_STEM || op.kind > WZ_OP_STEM7)   // (an unknown kind would otherwise run as a conv)
+        if (op.kind < WZ_OP_STEM || op.kind > WZ_OP_DWSEP)   // (an unknown kind would otherwise run as a conv)
             return wz_fail(WZ_EFORMAT, "%s: op %u (%s) has kind %d, which this runtime does not know", path, i, op.name, op.kind);
         if (op.src < 0 || op.src >= (int)h.n_tensors || op.dst >= (int)h.n_tensors || op.res >= (int)h.n_tensors ||
             (op.out_mode == WZ_OUT_ACT && op.dst < 0) || op.w_off < 0 || (uint64_t)op.w_off >= h.weights_bytes ||
@@ -897,6 +920,23 @@ static int load_blob(wz_engine* e, const char* path) {
         } else if ((e->tensors[op.src].flags & WZ_TENSOR_HP) || (op.dst >= 0 && (e->tensors[op.dst].flags & WZ_TENSOR_HP)) ||
                    (op.res >= 0 && (e->tensors[op.res].flags & WZ_TENSOR_HP))) {
             return wz_fail(WZ_EFORMAT, "%s: op %u (%s) touches a pair tensor but is not a split-operand block", path, i, op.name);
+        } else if (op.kind == WZ_OP_DWSEP) {
+            // every bound the kernel indexes by: the tensors it reads and writes, both weight blocks, then the shapes it covers --
+            // evaluated here with the predicate of the launch, so that an uncovered shape never reaches run_batch
+            const WzTensorDesc& in = e->tensors[op.src];
+            const WzTensorDesc* out = op.dst >= 0 ? &e->tensors[op.dst] : nullptr;
+            const uint64_t wb = h.weights_bytes;
+            if (h.precision != 16 || !out || op.out_mode != WZ_OUT_ACT || op.res >= 0 || op.dst_c != 0 || op.dst_coff != 0 || op.dst2 != 0 ||
+                op.flags != 0 || op.ksize != 3 || op.act != WZ_ACT_RELU6 || op.dst == op.src || op.cin < 8 || op.cout < 8 || op.kc < 1 ||
+                op.n_pad < op.cout || in.c != op.cin || in.h != op.hin || in.w != op.win || out->c != op.cout || out->h != op.hout ||
+                out->w != op.wout || op.wd_off < 0 || (uint64_t)op.wd_off + 9ull * op.cin * 2 > wb || op.bd_off < 0 ||
+                (uint64_t)op.bd_off + 4ull * op.cin > wb || (uint64_t)op.w_off + 64ull * op.n_pad * op.kc > wb || op.b_off < 0 ||
+                (uint64_t)op.b_off + 4ull * op.n_pad > wb)
+                return wz_fail(WZ_EFORMAT, "%s: op %u (%s): malformed depthwise-separable layer", path, i, op.name);
+            wz_engine::Lane none;
+            if (wz_launch_dwsep(dwsep_args(e, none, op, 1), nullptr, true) != 0)
+                return wz_fail(WZ_EFORMAT, "%s: op %u (%s): no depthwise-separable kernel for this shape (cin %d, cout %d, n_pad %d, %dx%d "
+                               "stride %d)", path, i, op.name, op.cin, op.cout, op.n_pad, op.hin, op.win, op.stride);
         } else if (op.kind == WZ_OP_MBCONV && op.stem) {
             if (e->tensors[op.src].c != 4 || op.cin0 != 32 || op.kc0 != 1 || (e->tensors[op.src].h + 1) / 2 != op.hin ||
                 (e->tensors[op.src].w + 1) / 2 != op.win)

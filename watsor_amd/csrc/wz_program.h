@@ -12,8 +12,11 @@
                                 // 11: the float-form chunk buffer's scaling changed (k_hp_ops.h): depthwise taps of WZ_OPF_QENC blocks carry 6 * 2^60 / (2 - 2^-13)
 
 // WZ_OP_POOL: 3x3 max / average pool, stride 1 or 2, TF 'SAME' (max ignores the padding, average divides by the in-image taps);
-// WZ_OP_STEM7: 7x7 stride-2 conv (+ bias, relu6) on the 4-channel network input, 64 output channels (k_inception.hip)
-enum WzOpKind { WZ_OP_STEM = 1, WZ_OP_DW = 2, WZ_OP_CONV = 3, WZ_OP_MBCONV = 4, WZ_OP_POOL = 5, WZ_OP_STEM7 = 6 };
+// WZ_OP_STEM7: 7x7 stride-2 conv (+ bias, relu6) on the 4-channel network input, 64 output channels (k_inception.hip);
+// WZ_OP_DWSEP: one separable layer of SSD-MobileNet-v1, depthwise 3x3 (+ bias, relu6) -> 1x1 pointwise (+ bias, relu6), fp16 engine only
+// (k_dwsep.hip); cin = depthwise channels = pointwise K, ksize / stride / pads / hin ... wout are the depthwise conv's.  Format 12 still: a
+// runtime without it refuses the kind when the engine loads
+enum WzOpKind { WZ_OP_STEM = 1, WZ_OP_DW = 2, WZ_OP_CONV = 3, WZ_OP_MBCONV = 4, WZ_OP_POOL = 5, WZ_OP_STEM7 = 6, WZ_OP_DWSEP = 7 };
 enum WzOutMode { WZ_OUT_ACT = 0, WZ_OUT_BOX = 1, WZ_OUT_CLS = 2, WZ_OUT_HEAD = 3 };
 enum WzAct { WZ_ACT_NONE = 0, WZ_ACT_RELU6 = 1 };
 enum WzTensorFlags { WZ_TENSOR_HP = 1 };
@@ -97,5 +100,7 @@ struct WzOpDesc {  // 256 bytes
 //  WZ_OP_STEM7: fp16 engine: the WZ_OP_CONV layout with 1 tap, kc = 7, n_pad = 64 over K = tap * 4 + c (tap = ky * 7 + kx, c < 3;
 //               channel 3 and taps 49 .. 55 zero); fp32 engine: float w[49][3][64]; float bias[64]
 //  WZ_OP_POOL : no weights
+//  WZ_OP_DWSEP: depthwise as WZ_OP_DW (half w[9][cin], float bias[cin]) at wd_off / bd_off; pointwise as WZ_OP_CONV with 1 tap,
+//               kc = cin / 32, at w_off / b_off
 //  WZ_OP_MBCONV: expand + project in the WZ_OP_CONV layout, depthwise as WZ_OP_DW with rows padded to cmid_pad
 //               (WZ_OPF_HP: every GEMM weight twice, hi and lo halves; depthwise weights fp32)

@@ -4,8 +4,9 @@ MI355X analogue of `watsor/engine.py:17-107` (TensorRT engine builder CLI, run o
 application starts, auto-invoked by `watsor/main_for_gpu.py:17-26` when `gpu.uff`/`gpu.onnx` exists
 without `gpu.trt`).  Same command line shape (`-i/--input`, `-p/--precision {32,16}`, `-w`, `-mw`,
 `-mh`, `-o/--output`); the input is an `.npz` of TF variables (names as in the frozen graph of
-`ssd_mobilenet_v2_coco` or `ssd_inception_v2_coco`, TF layouts, BatchNorm unfolded), a frozen graph, or the literal
-`synthetic[:seed]` (MobileNet-v2) / `synthetic_inception_v2[:seed]`.  The network family is read from the variable names.
+`ssd_mobilenet_v2_coco`, `ssd_inception_v2_coco` or `ssd_mobilenet_v1_coco`, TF layouts, BatchNorm unfolded), a frozen graph, or the
+literal `synthetic[:seed]` (MobileNet-v2) / `synthetic_inception_v2[:seed]` / `synthetic_mobilenet_v1[:seed]`.  The network family is
+read from the variable names.
 
 What building does: fold every FusedBatchNorm into its convolution (fp64), round to fp16, lay the
 weights out in the MFMA fragment order the HIP kernels read (csrc/wz_program.h), generate the anchor
@@ -21,12 +22,13 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from . import arch, inception
+from . import arch, inception, mobilenet_v1
 from .anchors import ssd_anchor_table
 
 MAGIC = 0x35335A57
 FORMAT_VERSION = 12
-FAMILIES = {"MobilenetV2": "SSD-MobileNet-v2", "InceptionV2": "SSD-Inception-v2"}   # feature extractor scope -> network
+FAMILIES = {"MobilenetV2": "SSD-MobileNet-v2", "InceptionV2": "SSD-Inception-v2",
+            "MobilenetV1": "SSD-MobileNet-v1"}   # feature extractor scope -> network
 POOL_AVG = 16              # WzOpFlags::WZ_OPF_POOL_AVG (csrc/wz_program.h)
 BN_EPSILON = 1e-3          # watsor/test/model/prepare.py:48
 
@@ -96,15 +98,25 @@ def _align(n: int, a: int = 256) -> int:
     return (n + a - 1) // a * a
 
 
+def _families_built() -> str:
+    return " and ".join("%s (FeatureExtractor/%s/)" % (v, k) for k, v in FAMILIES.items())
+
+
 def detect_family(weights: Dict[str, np.ndarray]) -> str:
-    """The feature extractor the variables belong to ("MobilenetV2" or "InceptionV2"), from their `FeatureExtractor/<name>/` scope;
-    ValueError for any other (or for a mixture)."""
+    """The feature extractor the variables belong to ("MobilenetV2", "InceptionV2" or "MobilenetV1"), from their
+    `FeatureExtractor/<name>/` scope; ValueError for any other (or for a mixture).  The MobilenetV1 scope is also that of other
+    MobileNet-v1 detectors: a model under it that lacks any of the SSD-MobileNet-v1 feature extractor's variables is refused here,
+    before anything reads them.  Other float constants under the scope are ignored, as for the other two networks."""
     found = sorted({k.split("/")[1] for k in weights if k.startswith("FeatureExtractor/") and k.count("/") >= 2})
+    if found == ["MobilenetV1"]:
+        missing = sorted(k for k in mobilenet_v1.build(fuse=False).variable_shapes() if k.startswith(mobilenet_v1.FE) and k not in weights)
+        if missing:
+            raise ValueError("the model's FeatureExtractor/MobilenetV1/ variables are not SSD-MobileNet-v1's (%d of its variables missing, "
+                             "e.g. %s); this engine builds %s" % (len(missing), missing[0], _families_built()))
     if len(found) == 1 and found[0] in FAMILIES:
         return found[0]
     raise ValueError("the model's feature extractor is %s; this engine builds %s" % (
-        " + ".join(found) if found else "unknown (no FeatureExtractor/ variables)",
-        " and ".join("%s (FeatureExtractor/%s/)" % (v, k) for k, v in FAMILIES.items())))
+        " + ".join(found) if found else "unknown (no FeatureExtractor/ variables)", _families_built()))
 
 
 def fold_stem7(W: Dict[str, np.ndarray], op: "arch.Op") -> np.ndarray:
@@ -301,10 +313,13 @@ def build_engine(weights: Dict[str, np.ndarray], precision: int = 16, model_widt
         fuse = False                 # the fp32 engine runs one op per layer (csrc/k_f32.hip)
     if model_width != model_height:
         raise ValueError("square model input expected")
-    if any(k.startswith("FeatureExtractor/") for k in weights) and detect_family(weights) == "InceptionV2":
+    family = detect_family(weights) if any(k.startswith("FeatureExtractor/") for k in weights) else None
+    if family in ("InceptionV2", "MobilenetV1"):
         if robust or hp_upto not in (None, -1) or conv1_split:
-            raise ValueError("the robust, split-operand and fused-block programs are SSD-MobileNet-v2 programs; an SSD-Inception-v2 "
-                             "engine is built with -p 16 or -p 32 only")
+            raise ValueError("the robust, split-operand and fused-block programs are SSD-MobileNet-v2 programs; an %s "
+                             "engine is built with -p 16 or -p 32 only" % FAMILIES[family])
+        if family == "MobilenetV1":
+            return build_mobilenet_v1_engine(weights, precision, model_width, model_height, post=post, options=options, fuse=fuse)
         return build_inception_engine(weights, precision, model_width, model_height, post=post, options=options)
     cfg, opt = _post_options(post, options)
     if robust and not (precision == 16 and fuse and fuse_stem and hp_upto is None):
@@ -567,6 +582,67 @@ def build_inception_engine(weights: Dict[str, np.ndarray], precision: int = 16, 
     return _write_image(prog, precision, model_width, cfg, opt, tensor_names, slots, op_recs, wblob, 0)
 
 
+def build_mobilenet_v1_engine(weights: Dict[str, np.ndarray], precision: int = 16, model_width: int = 300, model_height: int = 300,
+                              post: Optional[dict] = None, options: Optional[dict] = None, fuse: bool = True) -> bytes:
+    """The SSD-MobileNet-v1 engine image (mobilenet_v1.py).  `-p 16`: fp16 weights and tensors, fp32 sums (the plain fp16 program,
+    DESIGN.md section 13); fuse=True packs every separable layer as one OP_DWSEP (depthwise weights in the OP_DW layout at wd_off /
+    bd_off, pointwise weights in the OP_CONV layout at w_off / b_off), fuse=False one op per layer.  `-p 32`: fp32 throughout, one op
+    per layer, input as a hi + lo pair."""
+    if precision not in (16, 32):
+        raise ValueError("precision must be 16 or 32")
+    if model_width != model_height:
+        raise ValueError("square model input expected")
+    cfg, opt = _post_options(post, options)
+    prog = mobilenet_v1.build(model_width, input_pair=precision == 32, head_ks=head_kernel_sizes(weights),
+                              fuse=fuse and precision == 16)
+    _check_variables(prog, weights)
+    tensor_names = ["input"] + [op.dst for op in prog.ops if op.out_mode == arch.OUT_ACT]
+    tindex = {n: i for i, n in enumerate(tensor_names)}
+    slots = assign_slots(prog, tensor_names)
+    wblob = bytearray()
+
+    def put(arr: np.ndarray) -> int:
+        off = _align(len(wblob))
+        wblob.extend(b"\0" * (off - len(wblob)))
+        wblob.extend(arr.tobytes())
+        return off
+
+    def put_conv(op):
+        w, b = fold_batch_norm(weights, op)
+        n_pad = _align(op.cout, 64 if op.cout >= 256 else 32)
+        if precision == 32:
+            kc = (op.cin + 15) // 16
+            w_off = put(pack_conv_weights_f32(w.astype(np.float32), n_pad, kc))
+        else:
+            kc = (op.cin + 31) // 32
+            w_off = put(pack_conv_weights(w.astype(np.float32), n_pad, kc))
+        bp = np.zeros(n_pad, np.float32)
+        bp[:op.cout] = b
+        return w_off, put(bp), n_pad, kc
+
+    def put_dw(op):
+        w, b = fold_batch_norm(weights, op)
+        return put(w.reshape(9, op.cin).astype(np.float32 if precision == 32 else np.float16)), put(b.astype(np.float32))
+
+    op_recs = []
+    for op in prog.ops:
+        mb = dict(cmid=0, cin0=0, kc0=0, cmid_pad=0, nmid_pad=0, we_off=0, be_off=0, wd_off=0, bd_off=0, stem=0, stem_pad=0)
+        n_pad, kc = 0, 0
+        if op.kind == arch.OP_STEM:
+            w, b = fold_batch_norm(weights, op)
+            w_off, b_off = put(w.reshape(27, 32).astype(np.float32)), put(b.astype(np.float32))
+        elif op.kind == arch.OP_DW:
+            w_off, b_off = put_dw(op)
+        elif op.kind == arch.OP_DWSEP:
+            dw, pw = op.parts
+            mb["wd_off"], mb["bd_off"] = put_dw(dw)
+            w_off, b_off, n_pad, kc = put_conv(pw)
+        else:
+            w_off, b_off, n_pad, kc = put_conv(op)
+        op_recs.append(_op_record(op, tindex, n_pad, kc, w_off, b_off, mb))
+    return _write_image(prog, precision, model_width, cfg, opt, tensor_names, slots, op_recs, wblob, 0)
+
+
 # The `-p 16` program's score tolerance (1e-3 against the fp32 detector) was established on weights whose channels all live at one
 # scale.  Folding a TRAINED network's BatchNorm spreads the per-channel amplitudes of the expanded tensors over a decade or more, and
 # the fp16 / unorm16 stages of the default program then lose the tolerance (tools/err_budget.py with SPREAD=..., profiles/r03_err_budget_*:
@@ -581,9 +657,11 @@ ROBUST_VALIDATED_DECADES = 1.5
 def channel_spread_decades(weights: Dict[str, np.ndarray]) -> float:
     """Median over the network's expand convolutions (and the stem) of log10(p95 / p5) of the per-output-channel amplitude of
     the BatchNorm-folded layer, sqrt(sum w^2 + b^2): ~0.2 for He-initialised weights, d for `synth.spread_channel_scales(W, d)`.
-    SSD-Inception-v2 weights: the same measure over all of that network's BatchNorm-ReLU6 convolutions, the stem included."""
-    inc = detect_family(weights) == "InceptionV2"
-    prog = inception.build() if inc else arch.build(fuse=False)
+    SSD-Inception-v2 weights: the same measure over all of that network's BatchNorm-ReLU6 convolutions, the stem included; SSD-MobileNet-v1
+    weights: over its BatchNorm-ReLU6 convolutions (stem, pointwise layers, extras)."""
+    family = detect_family(weights)
+    inc = family in ("InceptionV2", "MobilenetV1")
+    prog = inception.build() if family == "InceptionV2" else mobilenet_v1.build(fuse=False) if inc else arch.build(fuse=False)
     spreads = []
     for op in prog.ops:
         if op.kind in (arch.OP_CONV, arch.OP_STEM, arch.OP_STEM7) and op.act == arch.ACT_RELU6 and op.has_bn and \
@@ -613,6 +691,9 @@ def load_model(model_path: str):
 
 
 def load_weights(model_path: str) -> Dict[str, np.ndarray]:
+    if model_path.startswith("synthetic_mobilenet_v1"):
+        from .synth import synthetic_mobilenet_v1
+        return synthetic_mobilenet_v1(int(model_path.split(":")[1]) if ":" in model_path else 1234)
     if model_path.startswith("synthetic_inception_v2"):
         from .synth import synthetic_inception_v2
         return synthetic_inception_v2(int(model_path.split(":")[1]) if ":" in model_path else 1234)
@@ -636,8 +717,9 @@ def main(argv=None) -> int:
     parser = argparse.ArgumentParser(description="Utility to build the MI355X engine prior to inference.",
                                      formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     parser.add_argument("-i", "--input", dest="model_path", metavar="MODEL_PATH", required=True,
-                        help="TF variables as .npz or a frozen_inference_graph.pb of SSD-MobileNet-v2 or SSD-Inception-v2, or "
-                             "synthetic[:seed] (MobileNet-v2) / synthetic_inception_v2[:seed]")
+                        help="TF variables as .npz or a frozen_inference_graph.pb of SSD-MobileNet-v2, SSD-Inception-v2 or "
+                             "SSD-MobileNet-v1, or synthetic[:seed] (MobileNet-v2) / synthetic_inception_v2[:seed] / "
+                             "synthetic_mobilenet_v1[:seed]")
     parser.add_argument("-p", "--precision", type=int, choices=[32, 16], default=16,
                         help="activation/weight storage precision of the engine")
     parser.add_argument("-w", "--workspace", default=1024, type=int,
@@ -674,10 +756,10 @@ def main(argv=None) -> int:
         print("Settings read from the graph: " + ", ".join("%s=%s" % (k, v) for k, v in sorted(settings.items()) if k != "anchor_vectors"))
     family = detect_family(weights)
     print("Network: %s (FeatureExtractor/%s/)." % (FAMILIES[family], family))
-    if family == "InceptionV2":
+    if family in ("InceptionV2", "MobilenetV1"):
         if args.robust == "on" or args.plain_fp16:
-            raise ValueError("--robust on and --plain-fp16 select SSD-MobileNet-v2 programs; an SSD-Inception-v2 engine is built with "
-                             "-p 16 (fp16, scores within 1e-3 of the fp32 detector on He-scaled weights) or -p 32")
+            raise ValueError("--robust on and --plain-fp16 select SSD-MobileNet-v2 programs; an %s engine is built with "
+                             "-p 16 (fp16, scores within 1e-3 of the fp32 detector on He-scaled weights) or -p 32" % FAMILIES[family])
         if args.precision == 16 and args.precision_check != "off":
             spread = channel_spread_decades(weights)
             print("Per-channel dynamic range of the folded convolutions: %.2f decades (the -p 16 program's 1e-3 score tolerance is "

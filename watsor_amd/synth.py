@@ -1,4 +1,4 @@
-"""Seeded synthetic SSD-MobileNet-v2 (and SSD-Inception-v2) weights (TF variable names, TF layouts, unfolded BatchNorm).
+"""Seeded synthetic SSD-MobileNet-v2 (and SSD-Inception-v2, SSD-MobileNet-v1) weights (TF variable names, TF layouts, unfolded BatchNorm).
 
 There is no model file anywhere in the reference tree (`watsor/test/model/cpu.pb` is a stripped
 blob) and no network to fetch `ssd_mobilenet_v2_coco_2018_03_29` (README.md:450), so benchmarks,
@@ -95,6 +95,37 @@ def synthetic_inception_v2(seed: int = 1234) -> Dict[str, np.ndarray]:
             m = arch.STEM7_MULTIPLIER
             W[op.scope + "/depthwise_weights"] = normal((op.k, op.k, op.cin, m), 1.0 / op.k)
             W[op.scope + "/pointwise_weights"] = normal((1, 1, op.cin * m, op.cout), math.sqrt(2.0 / (op.cin * m)))
+        else:
+            W[op.scope + "/weights"] = normal((op.k, op.k, op.cin, op.cout), math.sqrt(2.0 / (op.k * op.k * op.cin)))
+        c = op.cout
+        W[op.scope + "/BatchNorm/gamma"] = (1.0 + 0.1 * rng.standard_normal(c, dtype=np.float32)).astype(np.float32)
+        W[op.scope + "/BatchNorm/beta"] = normal((c,), 0.1) + np.float32(0.2)
+        W[op.scope + "/BatchNorm/moving_mean"] = normal((c,), 0.1)
+        W[op.scope + "/BatchNorm/moving_variance"] = (0.75 + 0.5 * rng.random(c, dtype=np.float32)).astype(np.float32)
+    return W
+
+
+def synthetic_mobilenet_v1(seed: int = 1234) -> Dict[str, np.ndarray]:
+    """Seeded SSD-MobileNet-v1 weights (mobilenet_v1.py) in the style of `synthetic_inception_v2`: He-scaled (the depthwise filters
+    over their 9 taps), BatchNorm unfolded, class bias at logit(0.01).  Drawn in the order of the one-op-per-layer program."""
+    from . import mobilenet_v1
+    prog = mobilenet_v1.build(fuse=False)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    W: Dict[str, np.ndarray] = {}
+
+    def normal(shape, std):
+        return (rng.standard_normal(shape, dtype=np.float32) * np.float32(std)).astype(np.float32)
+
+    for op in prog.ops:
+        if op.out_mode == arch.OUT_HEAD:
+            fan_in = op.k * op.k * op.cin
+            for sub, cols, gain, bias_mean, bias_std in (("BoxEncodingPredictor", op.n_box, 0.4, 0.0, 0.05),
+                                                         ("ClassPredictor", op.cout - op.n_box, 0.45, -4.6, 0.3)):
+                W["%s/%s/weights" % (op.scope, sub)] = normal((op.k, op.k, op.cin, cols), gain / math.sqrt(fan_in))
+                W["%s/%s/biases" % (op.scope, sub)] = (normal((cols,), bias_std) + np.float32(bias_mean)).astype(np.float32)
+            continue
+        if op.kind == arch.OP_DW:
+            W[op.scope + "/depthwise_weights"] = normal((op.k, op.k, op.cin, 1), math.sqrt(2.0 / (op.k * op.k)))
         else:
             W[op.scope + "/weights"] = normal((op.k, op.k, op.cin, op.cout), math.sqrt(2.0 / (op.k * op.k * op.cin)))
         c = op.cout
