@@ -1,0 +1,449 @@
+"""The float64 reference of ONE op of an engine program, the bound on what an fp32-accumulating kernel may differ from it, and the
+walker that checks every op of a program on the tensors an engine actually produced (tests/test_op_reference_cpu.py,
+tests/test_gpu_op_conformance.py).
+
+The method is op-local: an op's reference is computed from the source tensor *as the engine stored it*, with the engine's own
+rounded weights, so upstream error cancels and what is left is the kernel's fp32 summation order and one final rounding.
+
+For every output element `reference()` returns
+  ref  the exact value (float64),
+  T    the sum of the absolute values of every term that entered it (|w.x| over taps and channels, + |bias|, + |residual|),
+  r    the number of fp32 roundings on the way: terms + 2 where the products are exact in fp32 (fp16 x fp16), 2 * terms + 2 where they
+       are not (fp32 weights); terms = the in-image taps x input channels; the average pool has one more (the multiplication by 1 / taps).
+With u = 2^-24:
+  e_acc = min(8 sqrt(r), r) u T          r u T is the worst case of ANY summation order (split-K and grouped reduces included);
+                                         8 sqrt(r) u T the probabilistic bound for round-to-nearest sums (Higham & Mary 2019), exceeded
+                                         with probability below 2 exp(-32) per element
+  tol   = e_acc + ulp16(|ref| + e_acc) / 2     stored as fp16
+  tol   = e_acc                                stored as fp32 (the last rounding is one of the r)
+ReLU6 is 1-Lipschitz, so the bound passes through it.  None of these numbers comes from a kernel.
+
+Exact where the order is a contract: max pool (no arithmetic), and the `-p 16` depthwise conv, whose kernels state their order (the sum
+starts from the fp32 bias and runs fmaf over ky, then kx; an fp16 x fp16 product is exact in fp32, so float32(acc + x * k) IS that
+fmaf): emulated in float32 and compared value for value (a signed zero is the one thing `==` does not tell apart).
+
+Weights come from the model variables through engine.fold_batch_norm and are rounded as the packer rounds them, so a wrong weight
+layout in the engine image shows up as a wrong tensor.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from watsor_amd import arch, engine
+
+U = 2.0 ** -24
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the bound
+# ---------------------------------------------------------------------------------------------------------------------------------
+def ulp16(x):
+    """Spacing of fp16 numbers at |x| (2^-24 in the subnormal range)."""
+    x = np.abs(np.asarray(x, np.float64))
+    return 2.0 ** (np.floor(np.log2(np.maximum(x, 2.0 ** -14))) - 10)
+
+
+def e_acc(T, r):
+    r = np.asarray(r, np.float64)
+    return np.minimum(8.0 * np.sqrt(r), r) * U * np.asarray(T, np.float64)
+
+
+def tolerance(ref, T, r, fp16_store: bool):
+    e = e_acc(T, r)
+    return e + 0.5 * ulp16(np.abs(ref) + e) if fp16_store else e
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# weights as the engine holds them
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _f32(a):
+    return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
+
+
+def _f16_via_f32(a):          # pack_conv_weights: float64 -> float32 -> float16
+    return np.asarray(a, np.float64).astype(np.float32).astype(np.float16).astype(np.float64)
+
+
+def _f16(a):                  # the depthwise taps: float64 -> float16
+    return np.asarray(a, np.float64).astype(np.float16).astype(np.float64)
+
+
+def engine_weights(op: "arch.Op", weights: Dict[str, np.ndarray], precision: int, exact: bool = False):
+    """(w float64 in TF layout, bias float64) of one conv op, BatchNorm folded, rounded as the packer rounds them (exact=True: not
+    rounded at all).  `split_w`: K = [hi halves | lo halves] along the input channels."""
+    w, b = engine.fold_batch_norm(weights, op)
+    if op.split_w:
+        if exact:
+            w = np.concatenate([w, np.zeros_like(w)], axis=2)
+        else:
+            hi, lo = engine.split_halves(w)
+            w = np.concatenate([hi, lo], axis=2)
+    if exact:
+        return w, b
+    if precision == 32 or op.kind == arch.OP_STEM:
+        w = _f32(w)
+    elif op.kind == arch.OP_DW:
+        w = _f16(w)
+    else:
+        w = _f16_via_f32(w)
+    return w, _f32(b)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# plain float64 ops, NHWC in and out
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _pads(n_in: int, k: int, s: int, before: int):
+    n_out = (n_in + s - 1) // s
+    return n_out, max((n_out - 1) * s + k - n_in - before, 0)
+
+
+def _padded(x: np.ndarray, k: int, s: int, pad_t: int, pad_l: int, value: float = 0.0) -> np.ndarray:
+    n, h, w, c = x.shape
+    _, pb = _pads(h, k, s, pad_t)
+    _, pr = _pads(w, k, s, pad_l)
+    return np.pad(x, ((0, 0), (pad_t, pb), (pad_l, pr), (0, 0)), constant_values=value)
+
+
+def _windows(xp: np.ndarray, k: int, s: int, hout: int, wout: int):
+    for ky in range(k):
+        for kx in range(k):
+            yield ky, kx, xp[:, ky:ky + (hout - 1) * s + 1:s, kx:kx + (wout - 1) * s + 1:s, :]
+
+
+def in_image_taps(h: int, w: int, k: int, s: int, pad_t: int, pad_l: int) -> np.ndarray:
+    """[hout, wout]: how many of the k x k taps of each output pixel lie inside the image."""
+    ones = _padded(np.ones((1, h, w, 1)), k, s, pad_t, pad_l)
+    hout, wout = (h + s - 1) // s, (w + s - 1) // s
+    return sum(win for _, _, win in _windows(ones, k, s, hout, wout))[0, :, :, 0]
+
+
+def conv64(x: np.ndarray, w: np.ndarray, stride: int, pad_t: int, pad_l: int, depthwise: bool = False) -> np.ndarray:
+    """x [n,h,w,cin], w [k,k,cin,cout] (depthwise: [k,k,c,1]), TF SAME with the given leading pads -> [n,hout,wout,cout], float64."""
+    k = w.shape[0]
+    xp = torch.from_numpy(np.ascontiguousarray(_padded(np.asarray(x, np.float64), k, stride, pad_t, pad_l).transpose(0, 3, 1, 2)))
+    wt = torch.from_numpy(np.ascontiguousarray(np.asarray(w, np.float64).transpose((2, 3, 0, 1) if depthwise else (3, 2, 0, 1))))
+    y = F.conv2d(xp, wt, None, stride=stride, groups=x.shape[3] if depthwise else 1)
+    return np.ascontiguousarray(y.permute(0, 2, 3, 1).numpy())
+
+
+def _act(y: np.ndarray, act: int) -> np.ndarray:
+    return np.clip(y, 0.0, 6.0) if act == arch.ACT_RELU6 else y
+
+
+def depthwise_fp32_emulated(x: np.ndarray, w: np.ndarray, b: np.ndarray, stride: int, pad_t: int, pad_l: int, act: int) -> np.ndarray:
+    """The `-p 16` depthwise kernels' arithmetic: acc = bias (fp32); acc = fmaf(x, k, acc) over ky, then kx; ReLU6 -- float32, before
+    the fp16 rounding.  x and w hold fp16 values, so x * k is exact in float64 and float32(acc + x * k) is the fmaf; a tap outside the
+    image adds an exact zero."""
+    n, h, wd, c = x.shape
+    hout, wout = (h + stride - 1) // stride, (wd + stride - 1) // stride
+    xp = _padded(np.asarray(x, np.float64), 3, stride, pad_t, pad_l)
+    acc = np.broadcast_to(np.asarray(b, np.float32), (n, hout, wout, c)).copy()
+    for ky, kx, win in _windows(xp, 3, stride, hout, wout):
+        acc = (acc.astype(np.float64) + win * w[ky, kx, :, 0]).astype(np.float32)
+    return np.clip(acc, np.float32(0), np.float32(6)) if act == arch.ACT_RELU6 else acc
+
+
+@dataclass
+class OpResult:
+    ref: np.ndarray                       # [n, hout, wout, cout] float64; exact ops: the value to compare after the cast to the stored type
+    T: Optional[np.ndarray] = None
+    r: Optional[np.ndarray] = None        # broadcastable against ref
+    exact: bool = False
+
+
+def _dense(op, w, b, x, res, inexact_products: bool, want_T: bool, stride=None, pad_t=None, pad_l=None) -> OpResult:
+    stride = op.stride if stride is None else stride
+    pad_t = op.pad_t if pad_t is None else pad_t
+    pad_l = op.pad_l if pad_l is None else pad_l
+    depthwise = op.kind == arch.OP_DW
+    y = _act(conv64(x, w, stride, pad_t, pad_l, depthwise) + b, op.act)
+    if res is not None:
+        y = y + np.asarray(res, np.float64)       # the residual is added after the activation (wz_epilogue4)
+    if not want_T:
+        return OpResult(y)
+    T = conv64(np.abs(x), np.abs(w), stride, pad_t, pad_l, depthwise) + np.abs(b)
+    if res is not None:
+        T = T + np.abs(np.asarray(res, np.float64))
+    terms = in_image_taps(x.shape[1], x.shape[2], w.shape[0], stride, pad_t, pad_l)[None, :, :, None] * (1 if depthwise else w.shape[2])
+    return OpResult(y, T, (2 if inexact_products else 1) * terms + 2)
+
+
+def reference(op: "arch.Op", weights: Dict[str, np.ndarray], src: np.ndarray, res: Optional[np.ndarray] = None, precision: int = 16,
+              exact: bool = False) -> OpResult:
+    """The float64 reference of `op` on `src` ([n,h,w,c], the values as stored; the network input may carry its zero fourth channel).
+    exact=True: weights and biases stay float64, nothing is emulated, no T (the float64 network of the oracle comparison)."""
+    x = np.asarray(src, np.float64)
+    want_T = not exact
+    if op.kind == arch.OP_POOL:
+        hout, wout = (x.shape[1] + op.stride - 1) // op.stride, (x.shape[2] + op.stride - 1) // op.stride
+        if op.pool_max:                                         # padding never wins
+            xp = _padded(x, op.k, op.stride, op.pad_t, op.pad_l, -np.inf)
+            y = None
+            for _, _, win in _windows(xp, op.k, op.stride, hout, wout):
+                y = win.copy() if y is None else np.maximum(y, win)
+            return OpResult(y, exact=True)
+        taps = in_image_taps(x.shape[1], x.shape[2], op.k, op.stride, op.pad_t, op.pad_l)[None, :, :, None]
+        s = sum(win for _, _, win in _windows(_padded(x, op.k, op.stride, op.pad_t, op.pad_l), op.k, op.stride, hout, wout))
+        if not want_T:
+            return OpResult(s / taps)
+        sa = sum(win for _, _, win in _windows(_padded(np.abs(x), op.k, op.stride, op.pad_t, op.pad_l), op.k, op.stride, hout, wout))
+        return OpResult(s / taps, sa / taps, taps + 3)
+    if op.kind == arch.OP_DWSEP:
+        dw, pw = op.parts
+        wd, bd = engine_weights(dw, weights, precision, exact)
+        wp, bp = engine_weights(pw, weights, precision, exact)
+        if exact:
+            mid = _dense(dw, wd, bd, x, None, False, False, op.stride, op.pad_t, op.pad_l).ref
+        else:                                                   # what the kernel keeps in LDS: the emulated depthwise output as fp16
+            mid = depthwise_fp32_emulated(x, wd, bd, op.stride, op.pad_t, op.pad_l, dw.act).astype(np.float16).astype(np.float64)
+        return _dense(pw, wp, bp, mid, None, False, want_T, 1, 0, 0)
+    w, b = engine_weights(op, weights, precision, exact)
+    if op.kind in (arch.OP_STEM, arch.OP_STEM7):
+        x = x[..., :3]                                          # channel 3 of the input is ignored
+        if w.shape[2] != 3:
+            raise AssertionError("%s: stem weights with %d input channels" % (op.scope, w.shape[2]))
+        return _dense(op, w, b, x, None, precision == 32 or op.kind == arch.OP_STEM, want_T)
+    if op.kind == arch.OP_DW:
+        if precision == 16 and not exact:
+            return OpResult(depthwise_fp32_emulated(x, w, b, op.stride, op.pad_t, op.pad_l, op.act).astype(np.float64), exact=True)
+        return _dense(op, w, b, x, None, True, want_T)
+    if op.kind == arch.OP_CONV:
+        if w.shape[2] != x.shape[3]:
+            raise AssertionError("%s: K = %d over a %d-channel source" % (op.scope, w.shape[2], x.shape[3]))
+        return _dense(op, w, b, x, res, precision == 32, want_T)
+    raise AssertionError("no reference for op kind %d (%s)" % (op.kind, op.scope))
+
+
+def head_rows(op: "arch.Op", y: np.ndarray):
+    """[n,h,w, a*4 | a*91] of an OUT_HEAD op -> (box [n, h*w*a, 4], class [n, h*w*a, 91]): pixel p, anchor a is row p * anchors + a."""
+    n = y.shape[0]
+    rows = op.hout * op.wout * op.anchors_per_loc
+    return y[..., :op.n_box].reshape(n, rows, 4), y[..., op.n_box:].reshape(n, rows, (op.cout - op.n_box) // op.anchors_per_loc)
+
+
+def run_program(prog: "arch.Program", weights: Dict[str, np.ndarray], x: np.ndarray, precision: int = 32):
+    """The float64 network: the references chained with exact=True, each op fed with the unrounded result of the op before.
+    -> (tensors name -> [n,h,w,c] float64, box encodings [n,A,4], class logits [n,A,91])."""
+    n = x.shape[0]
+    T: Dict[str, np.ndarray] = {"input": np.asarray(x, np.float64)}
+    be = np.zeros((n, prog.num_anchors, 4))
+    lg = np.zeros((n, prog.num_anchors, arch.NUM_CLASSES))
+    for op in prog.ops:
+        y = reference(op, weights, T[op.src], T[op.res] if op.res else None, precision, exact=True).ref
+        if op.out_mode == arch.OUT_HEAD:
+            b, c = head_rows(op, y)
+            be[:, op.anchor_offset:op.anchor_offset + b.shape[1]] = b
+            lg[:, op.anchor_offset:op.anchor_offset + c.shape[1]] = c
+        elif op.cdst:
+            t = T.setdefault(op.dst, np.zeros(y.shape[:3] + (op.cdst,)))
+            t[..., op.coff:op.coff + op.cout] = y
+        else:
+            T[op.dst] = y
+    return T, be, lg
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the walker
+# ---------------------------------------------------------------------------------------------------------------------------------
+def op_kind_name(op: "arch.Op") -> str:
+    if op.kind == arch.OP_POOL:
+        return "pool_max" if op.pool_max else "pool_avg"
+    if op.kind != arch.OP_CONV:
+        return {arch.OP_STEM: "stem3x3", arch.OP_STEM7: "stem7x7", arch.OP_DW: "depthwise", arch.OP_DWSEP: "dwsep"}[op.kind]
+    if op.out_mode == arch.OUT_HEAD:
+        return "head%dx%d" % (op.k, op.k)
+    return "conv%dx%d%s%s%s%s" % (op.k, op.k, "_s2" if op.stride == 2 else "", "_res" if op.res else "", "_slice" if op.cdst else "",
+                                   "_splitw" if op.split_w else "")
+
+
+@dataclass
+class Report:
+    ops_checked: int = 0
+    ops_mbconv: int = 0
+    ops_unchecked: int = 0
+    elements: int = 0
+    worst: Dict[str, tuple] = field(default_factory=dict)     # op kind -> (worst err / tol, op scope)
+    worst_acc: Dict[str, float] = field(default_factory=dict)  # op kind -> worst (err - the fp16 store's half ulp) / e_acc: a lower bound on
+                                                               # the share of the ACCUMULATION allowance in use (err / tol of an fp16 tensor is
+                                                               # near 1 whenever the final rounding lands near half an ulp)
+    failures: List[str] = field(default_factory=list)
+
+    def summary(self) -> str:
+        kinds = "  ".join("%s %.3g (acc %.3g)" % (k, v[0], self.worst_acc.get(k, 0.0)) for k, v in sorted(self.worst.items()))
+        return "%d ops checked (%d fused blocks left to their own tests, %d unchecked), %d elements; worst err / tol: %s" % (
+            self.ops_checked, self.ops_mbconv, self.ops_unchecked, self.elements, kinds)
+
+
+def _compare(rep: Report, op, idx: int, what: str, got: np.ndarray, ref: np.ndarray, T, r, exact: bool, fp16_store: bool,
+             frames: Sequence[int]):
+    """got / ref / T [n, ..., c] (any middle axes = the pixel), r broadcastable; records a failure with the worst element.
+    -> (worst err / tol, worst share of e_acc in use)."""
+    got64 = got.astype(np.float64)
+    acc_share = 0.0
+    if exact:
+        expected = ref.astype(np.float16 if fp16_store else np.float32).astype(np.float64)
+        bad = ~(got64 == expected)
+        ratio = np.where(bad, np.inf, 0.0)
+        ref = expected
+    else:
+        tol = tolerance(ref, T, r, fp16_store)
+        err = np.abs(got64 - ref)
+        bad = ~(err <= tol)                                   # (a NaN fails)
+        ratio = np.where(bad & ~np.isfinite(err), np.inf, err / np.maximum(tol, 1e-300))
+        e = e_acc(T, r)
+        share = np.where(e > 0, (err - (tol - e)) / np.where(e > 0, e, 1.0), 0.0)
+        acc_share = float(np.nanmax(share)) if share.size else 0.0
+    if not np.isfinite(got64).all():
+        bad = bad | ~np.isfinite(got64)
+        ratio = np.where(np.isfinite(got64), ratio, np.inf)
+    rep.elements += int(got.size)
+    worst = float(ratio.max()) if ratio.size else 0.0
+    if bad.any():
+        at = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+        rep.failures.append("op %d (%s, %s)%s: frame %d, pixel %s, channel %d: got %.9g, ref %.9g, err / tol %.3g%s; %d of %d elements outside"
+                            % (idx, op.scope, op_kind_name(op), what, frames[at[0]], tuple(int(i) for i in at[1:-1]), at[-1], got64[at], ref[at],
+                               ratio[at], " (exact comparison)" if exact else "", int(bad.sum()), bad.size))
+    return worst, max(acc_share, 0.0)
+
+
+def walk(eng, prog: "arch.Program", weights: Dict[str, np.ndarray], x_half: np.ndarray, precision: int = 16,
+         frames: Optional[Sequence[int]] = None, check: bool = True) -> Report:
+    """One forward pass of `eng` (tensors(), stage_forward(), stage_read_tensor(); every tensor must stay readable) on x_half
+    [n,S,S,4] float16, then EVERY op of `prog` on its own: source (and residual) as the engine produced them -> ref, tol -> the
+    destination the engine produced.  `frames`: the frames whose references are computed (default: all).
+    Counts what it covers and asserts that nothing is left out: every op is checked or is a fused block (OP_MBCONV); every channel of
+    every tensor other than the input and those blocks' outputs is written by exactly one checked op; every row of the two head
+    outputs by exactly one head.  check=True raises AssertionError naming every failing op; the Report says what was seen."""
+    n = x_half.shape[0]
+    frames = list(range(n)) if frames is None else sorted(set(int(f) for f in frames))
+    be, lg = eng.stage_forward(x_half)
+    info = {name: (i, h, w, c) for i, (name, h, w, c) in enumerate(eng.tensors())}
+    last_use: Dict[str, int] = {}
+    for i, op in enumerate(prog.ops):
+        for t in (op.src, op.res, None if op.out_mode == arch.OUT_HEAD else op.dst):
+            if t:
+                last_use[t] = i
+    cache: Dict[str, np.ndarray] = {}
+
+    def read(name: str) -> np.ndarray:
+        if name not in cache:
+            cache[name] = np.stack([eng.stage_read_tensor(info[name][0], f) for f in frames])
+        return cache[name]
+
+    rep = Report()
+    cover = {name: np.zeros(c, np.int64) for name, (_, _, _, c) in info.items() if name != "input"}
+    rows_cover = np.zeros(prog.num_anchors, np.int64)
+    block_outputs = set()
+    for idx, op in enumerate(prog.ops):
+        if op.kind == arch.OP_MBCONV:
+            rep.ops_mbconv += 1
+            block_outputs.update(t for t in (op.dst, op.dst2) if t)
+            continue
+        try:
+            res = reference(op, weights, read(op.src), read(op.res) if op.res else None, precision)
+        except AssertionError as e:
+            rep.ops_unchecked += 1
+            rep.failures.append("op %d (%s): %s" % (idx, op.scope, e))
+            continue
+        kind = op_kind_name(op)
+        if op.out_mode == arch.OUT_HEAD:
+            rb, rc = head_rows(op, res.ref)
+            tb, tc = head_rows(op, res.T)
+            r = np.repeat(np.broadcast_to(res.r, (1,) + res.ref.shape[1:3] + (1,)).reshape(-1), op.anchors_per_loc)[None, :, None]
+            sl = slice(op.anchor_offset, op.anchor_offset + rb.shape[1])
+            rows_cover[sl] += 1
+            wb = _compare(rep, op, idx, " box encodings", be[frames][:, sl], rb, tb, r, False, False, frames)
+            wc = _compare(rep, op, idx, " class logits", lg[frames][:, sl], rc, tc, r, False, False, frames)
+            worst, acc = max(wb[0], wc[0]), max(wb[1], wc[1])
+        else:
+            got = read(op.dst)
+            c0, c1 = (op.coff, op.coff + op.cout) if op.cdst else (0, op.cout)
+            if got.shape[1:3] != res.ref.shape[1:3] or got.shape[3] != (op.cdst or op.cout):
+                rep.failures.append("op %d (%s): the engine's tensor %s is %s, the op writes %s of %d channels"
+                                    % (idx, op.scope, op.dst, got.shape[1:], res.ref.shape[1:3], op.cdst or op.cout))
+                rep.ops_unchecked += 1
+                continue
+            cover[op.dst][c0:c1] += 1
+            worst, acc = _compare(rep, op, idx, "", got[..., c0:c1], res.ref, res.T, res.r, res.exact, precision == 16, frames)
+        rep.ops_checked += 1
+        if kind not in rep.worst or worst > rep.worst[kind][0]:
+            rep.worst[kind] = (worst, op.scope)
+        rep.worst_acc[kind] = max(rep.worst_acc.get(kind, 0.0), acc)
+        for t in [t for t in cache if last_use.get(t, -1) <= idx]:
+            del cache[t]
+
+    # nothing left out silently
+    if rep.ops_checked + rep.ops_mbconv != len(prog.ops) or rep.ops_unchecked:
+        rep.failures.append("coverage: %d ops checked + %d fused blocks of %d ops (%d unchecked)"
+                            % (rep.ops_checked, rep.ops_mbconv, len(prog.ops), rep.ops_unchecked))
+    for name, cnt in cover.items():
+        if name in block_outputs:
+            continue
+        if not (cnt == 1).all():
+            rep.failures.append("coverage: tensor %s: channels written by %s checked ops (every channel exactly once expected)"
+                                % (name, sorted(set(int(v) for v in cnt))))
+    if not (rows_cover == 1).all():
+        rep.failures.append("coverage: head rows covered %s times (every one of the %d rows exactly once expected)"
+                            % (sorted(set(int(v) for v in rows_cover)), prog.num_anchors))
+    if check and rep.failures:
+        raise AssertionError("%d failure(s):\n  %s" % (len(rep.failures), "\n  ".join(rep.failures[:20])))
+    return rep
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# inputs of the conformance runs
+# ---------------------------------------------------------------------------------------------------------------------------------
+def impulse_input(size: int, seed: int) -> np.ndarray:
+    """[size,size,4] float16 zeros with pixels of 1.0 (all three channels) in the four corners, on each edge, in the centre, and at
+    one seeded position more (so that two impulse frames of one batch differ)."""
+    x = np.zeros((size, size, 4), np.float16)
+    m, e = size // 2, size - 1
+    rng = np.random.Generator(np.random.PCG64(seed))
+    for y, xx in [(0, 0), (0, e), (e, 0), (e, e), (0, m), (e, m), (m, 0), (m, e), (m, m), tuple(rng.integers(1, e, 2))]:
+        x[y, xx, :3] = 1.0
+    return x
+
+
+def noise_input(size: int, seed: int, amplitude: float = 4.0) -> np.ndarray:
+    """fp16 noise of the given amplitude (beyond the normalised range [-1, 1]): drives ReLU6 into both clamps."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    x = np.zeros((size, size, 4), np.float16)
+    x[..., :3] = (rng.uniform(-amplitude, amplitude, (size, size, 3))).astype(np.float16)
+    return x
+
+
+def conformance_batch(n: int, size: int, start: int, seed: int, frame_input) -> np.ndarray:
+    """[n,size,size,4] float16, a different input in every frame: frame i is kind (i + start) % 4 of (preprocessed synthetic frame,
+    noise, impulses, zeros), each with its own seed; zeros appear once per batch (a second all-zero frame would equal the first: a
+    synthetic frame takes its place).  frame_input(seed) -> [size,size,4] float16 is the preprocessed synthetic frame."""
+    out = np.zeros((n, size, size, 4), np.float16)
+    zeros_used = False
+    for i in range(n):
+        kind = (i + start) % 4
+        s = seed * 100 + i
+        if kind == 3 and not zeros_used:
+            zeros_used = True
+        elif kind == 2:
+            out[i] = impulse_input(size, s)
+        elif kind == 1:
+            out[i] = noise_input(size, s)
+        else:
+            out[i] = frame_input(s)
+    return out
+
+
+def frame_subset(n: int) -> List[int]:
+    """All frames up to batch 8; beyond, frame 0, one in the middle and the last."""
+    return list(range(n)) if n <= 8 else [0, n // 2, n - 1]
+
+
+def old_bound_passes(got: np.ndarray, ref: np.ndarray) -> bool:
+    """The end-to-end tests' per-tensor bound for `-p 16` programs: max|got - ref| <= 0.04 max|ref| + 0.02."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    return bool(np.abs(got - ref).max() <= 0.04 * np.abs(ref).max() + 0.02)
+

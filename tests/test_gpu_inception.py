@@ -74,8 +74,8 @@ def test_every_tensor_close_to_oracle(inc_dirs, oracle_out, precision):
             if name == "input":
                 continue
             got = np.stack([e.stage_read_tensor(idx, f) for f in range(2)]).astype(np.float32)
-            if name not in T:                 # branch intermediates: the oracle keeps module outputs and trunk tensors
-                continue
+            if name not in T:                 # branch intermediates: the oracle keeps module outputs and trunk tensors; each of the 38
+                continue                      # is checked on its own, against its op's float64 reference, in tests/test_gpu_op_conformance.py
             ref = T[name]
             assert got.shape == ref.shape, name
             err, scale = float(np.abs(got - ref).max()), float(np.abs(ref).max())
