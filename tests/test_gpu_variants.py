@@ -205,9 +205,8 @@ def test_latency_schedule_detects_the_same_objects(model_dir, tmp_path):
 
 @pytest.mark.parametrize("knobs", [
     dict(WZ_MB_CS_SPLIT16="0"),                                                     # block 16 on the channel-group kernel + reduce launch
-    dict(WZ_HP_CS19_LEAN4="0", WZ_HP_CS_OCC4="0", WZ_HP_CS6_LEAN4="0"),             # the 256-register builds of the chunk-split blocks
-    dict(WZ_HP_CS19_LEAN4="0", WZ_HP_CS19_NW="8", WZ_MB_CS_MIN_W="11"),             # round 2's shapes
-])
+    dict(WZ_MB_CS_MIN_W="11"),                                                      # blocks 13 .. 16 on the channel-group kernel + reduce launches
+], ids=["knobs0", "knobs2"])                                                        # (knobs1 selected the 256-register builds, which are gone)
 def test_earlier_launch_shapes_detect_the_same_objects(model_dir_default, knobs):
     model_dir = model_dir_default
     """The launch shapes of the split blocks and of blocks 13 .. 16 changed several times this round (DESIGN.md section 5): every one of

@@ -51,12 +51,25 @@ def test_product_library_reads_four_environment_settings():
     read_directly = set(re.findall(r'[^_]getenv\("([A-Z0-9_]+)"\)', text))
     assert read_directly == {"WZ_GRAPH", "WZ_LANES", "WZ_STREAMS", "WZ_SCHEDULE"}, read_directly
     knobs = set(re.findall(r'"(WZ_[A-Z0-9_]+)"', text)) - read_directly
-    assert len(knobs) >= 40
+    assert len(knobs) == 32
     product, dev = open(_lib.LIB_PATH, "rb").read(), open(_lib.DEV_LIB_PATH, "rb").read()
     assert all(k.encode() in product for k in read_directly)
     leaked = sorted(k for k in knobs if k.encode() + b"\0" in product)
     assert not leaked, leaked
-    assert sum(k.encode() + b"\0" in dev for k in knobs) >= 40
+    assert sum(k.encode() + b"\0" in dev for k in knobs) == 32
+
+
+def kernel_descriptors(path):
+    """Names of the kernel-descriptor symbols (`<kernel>.kd`) of the device code in a library, read from the file as bytes."""
+    return set(re.findall(rb"[A-Za-z_][A-Za-z0-9_]*\.kd(?=\0)", open(path, "rb").read()))
+
+
+def test_product_and_development_libraries_hold_the_same_kernels():
+    """The development library adds entry points, diagnostics and knobs that choose AMONG the product's kernels -- not kernels of its own: a
+    stage-level parity test that loads it then exercises device code the product ships."""
+    product, dev = kernel_descriptors(_lib.LIB_PATH), kernel_descriptors(_lib.DEV_LIB_PATH)
+    assert len(product) >= 100
+    assert product == dev, (sorted(product - dev), sorted(dev - product))
 
 
 def test_no_gpu_calls_fail_cleanly():

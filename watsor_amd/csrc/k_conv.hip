@@ -556,27 +556,22 @@ __global__ __launch_bounds__(256, 2) void wz_k_conv_rs_group(const WzConvGroup g
         wz_conv_rs_body<3, 2, false, WzEpiF16>(g.a[e], smem, L);
 }
 
-static int wz_env_int(const char* name, int dflt) {
-    const char* e = wz_dev_getenv(name);
-    return (e && atoi(e) >= 0 && e[0]) ? atoi(e) : dflt;
-}
-
 // the LDS-tiled kernel needs whole 64-column tiles, whole 2-chunk K steps and enough pixels to fill a tile
 bool wz_conv_use_lds(const WzConvArgs& a) {
-    static const int min_m = wz_env_int("WZ_LDS_MIN_M", 128);
-    static const int min_k = wz_env_int("WZ_LDS_MIN_KCHUNKS", 8);
+    static const int min_m = wz_dev_env_int("WZ_LDS_MIN_M", 128);
+    static const int min_k = wz_dev_env_int("WZ_LDS_MIN_KCHUNKS", 8);
     return a.zeros && a.n_pad % 64 == 0 && a.kc % 2 == 0 && a.M >= min_m && a.kchunks >= min_k && a.cin % 32 == 0;
 }
 
 // 128 x 128 workgroup tiles where there are enough channels and pixels for them to pay
 int wz_lds_nw(int M, int n_pad, int kchunks) {
-    static const int force = wz_env_int("WZ_LDS_NW", 0);
+    static const int force = wz_dev_env_int("WZ_LDS_NW", 0);
     if (force == 2 || force == 4) return force;
     return (n_pad >= 256 && M >= 512 && kchunks >= 64) ? 4 : 2;   // measured: the two big heads gain, Conv_1 (K = 320) loses
 }
 
 int wz_choose_splitk_lds(int M, int n_pad, int kchunks) {
-    static const int target = wz_env_int("WZ_LDS_WGS", 192);   // measured 64 .. 512: fewer, longer K slices win (less partial-sum traffic); 192 best
+    static const int target = wz_dev_env_int("WZ_LDS_WGS", 192);   // measured 64 .. 512: fewer, longer K slices win (less partial-sum traffic); 192 best
     const int tn = WZ_LDS_TN(wz_lds_nw(M, n_pad, kchunks));
     const int wgs = ((M + WZ_LDS_TM - 1) / WZ_LDS_TM) * ((n_pad + tn - 1) / tn);
     const int nsteps = kchunks / 2;
@@ -651,7 +646,7 @@ void wz_launch_conv(const WzConvArgs& a0, hipStream_t s) {
 
 // small maps, a K loop long enough for eight slices, whole 32-channel tiles
 bool wz_conv_ws_applies(const WzConvArgs& a) {
-    static const int on = wz_env_int("WZ_CONV_WS", 1);
+    static const int on = wz_dev_env_int("WZ_CONV_WS", 1);
     return on && a.out_mode == WZ_OUT_ACT && a.M <= 1024 && a.kchunks >= 8 && a.n_pad % 32 == 0;
 }
 void wz_launch_conv_ws(const WzConvArgs& a, hipStream_t s) {
@@ -660,7 +655,7 @@ void wz_launch_conv_ws(const WzConvArgs& a, hipStream_t s) {
     // two chunks per load group (109 registers: two workgroups per CU) are 500 workgroups in ONE round: 6.9 us.  Measured beside it
     // (profiles/r04_conv1_tiles.txt): 32 x 32 at 109 registers 8.1 us, 64 x 64 (K in halves) 11.9 us, 64 x 64 at 173 registers 12.8 us (260
     // workgroups on 256 CUs: a second round for four of them).  WZ_CONV_WS64=0: the 32 x 32 tiles everywhere.
-    static const int wide_tiles = wz_env_int("WZ_CONV_WS64", 1);
+    static const int wide_tiles = wz_dev_env_int("WZ_CONV_WS64", 1);
     if (wide_tiles && a.ksize == 1 && a.M >= 512 && a.n_pad >= 512 && a.n_pad % 64 == 0 && a.kchunks >= 8) {
         WZ_LAUNCH((wz_k_conv_ws<1, 1, 2>), dim3((a.M + 31) / 32, a.n_pad / 64), dim3(512), 0, s, a);
         return;
@@ -702,7 +697,7 @@ bool wz_conv_rs_groupable(const WzConvArgs& a) {
 // tiles and one 64-column tile behind them -- instead of rounding up to 128-column tiles (384 / 640 columns of MFMA work: 20 % /
 // 11 % of it on padding).  Both write the same partial-sum slab ([z][M][n_pad], absolute columns) with the same split count.
 int wz_conv_rs_group_add(WzConvGroup& g, const WzConvArgs& a0) {
-    static const int split_n = wz_env_int("WZ_HEAD_SPLIT_N", 1);
+    static const int split_n = wz_dev_env_int("WZ_HEAD_SPLIT_N", 1);
     const int nw = wz_lds_nw(a0.M, a0.n_pad, a0.kchunks);
     const bool two = split_n && nw == 4 && (a0.n_pad % 128) == 64 && a0.n_pad > 128;
     if (g.n + (two ? 2 : 1) > WZ_CONV_GROUP_MAX) return 0;

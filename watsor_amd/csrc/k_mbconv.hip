@@ -13,7 +13,7 @@
 //     depthwise INPUT), one barrier, then every lane computes the depthwise 3x3 of 8 channels of one
 //     output pixel from LDS -- which is exactly the B-operand fragment of the project GEMM -- and feeds
 //     it to the project MFMAs; the project accumulators (fp32) live in registers across all chunks;
-//   * the chunk buffer in LDS is double-buffered, so there is one barrier per chunk;
+//   * one chunk buffer in LDS (WzMbArgs::ebufs = 1), two barriers per chunk;
 //   * epilogue: + bias, + residual, fp16 NHWC store.
 //
 // Rounding points (fp16 after expand, fp16 after depthwise, fp32 accumulation in the same order) are the
@@ -220,9 +220,9 @@ __global__ __launch_bounds__(256) void wz_k_mbconv(const WzMbArgs a) {
                     }
                 }
             }
-            // two chunk buffers: no barrier here -- the next chunk's expand writes the OTHER buffer, and a wave
-            // can only reach the chunk after that (same buffer again) through the barrier above, i.e. after
-            // every wave has finished reading this one.  One buffer (less LDS, more workgroups per CU):
+            // every wave has finished reading the buffer before the next chunk's expand writes it.  (a.ebufs is 1 in every launch: the expressions that
+            // read it stay because taking them out moves the register allocation -- <true, 64, 3, 2, 1, 10> from 2 waves per SIMD to 1,
+            // profiles/block_cleanup_resource_usage.txt)
             if (a.ebufs == 1 && ch + 1 < ch_end) __syncthreads();
         }
     } else {
@@ -330,28 +330,21 @@ struct MbCfg {
     int th, tw, ce, mp, mq, nsplit, cpg;
 };
 
-static int wz_mb_env(const char* name, int dflt) {
-    const char* e = wz_dev_getenv(name);
-    return (e && atoi(e) > 0) ? atoi(e) : dflt;
-}
-
 // Tile of output pixels per workgroup and the split of the expanded channels over blockIdx.y.
 // Output m-tiles (16 pixels) per wave MQ <= 2, halo m-tiles per wave MP <= 5.  The small late layers
 // (19x19, 10x10) have few tiles and many channel chunks: a serial walk over the chunks is one exposed
 // memory latency after the other, so the chunks are spread over workgroups instead (fp32 partial sums,
 // summed in a fixed order by wz_k_splitk_reduce).
+constexpr int MB_MAX_SPLIT = 16;
+constexpr size_t MB_STAGE_BYTES = 96 * 1024;   // a channel group's GEMM weights are staged in LDS when everything fits this
 static MbCfg wz_mb_choose(const WzMbArgs& a, int n) {
     MbCfg c;
-    int th = 8, tw = 8;
-    if (a.wout <= 19 && a.stride == 1) { th = 5; tw = 10; }   // 10x10: 2 tiles, 19x19: 4 x 2 tiles per frame
-    else if (a.wout <= 10) { th = 5; tw = 10; }
-    c.th = wz_mb_env("WZ_MB_TH", th);
-    c.tw = wz_mb_env("WZ_MB_TW", tw);
-    if (a.wout <= 10) { c.th = wz_mb_env("WZ_MB_TH10", c.th); c.tw = wz_mb_env("WZ_MB_TW10", c.tw); }
-    else if (a.wout <= 19) { c.th = wz_mb_env("WZ_MB_TH19", c.th); c.tw = wz_mb_env("WZ_MB_TW19", c.tw); }
-    else if (a.wout <= 38) { c.th = wz_mb_env("WZ_MB_TH38", c.th); c.tw = wz_mb_env("WZ_MB_TW38", c.tw); }
-    else if (a.wout <= 75) { c.th = wz_mb_env("WZ_MB_TH75", c.th); c.tw = wz_mb_env("WZ_MB_TW75", c.tw); }
-    else { c.th = wz_mb_env("WZ_MB_TH150", c.th); c.tw = wz_mb_env("WZ_MB_TW150", c.tw); }
+    // 8 x 8 outputs; 5 x 10 on the small maps (10x10: 2 tiles, 19x19 at stride 1: 4 x 2 tiles per frame).  WZ_MB_TH / WZ_MB_TW: another tile,
+    // same tensors (tests/test_gpu_parity.py)
+    const bool small = a.wout <= 10 || (a.wout <= 19 && a.stride == 1);
+    const int th = wz_dev_env_int("WZ_MB_TH", 0), tw = wz_dev_env_int("WZ_MB_TW", 0);
+    c.th = th > 0 ? th : small ? 5 : 8;
+    c.tw = tw > 0 ? tw : small ? 10 : 8;
     if (c.th > a.hout) c.th = a.hout;
     if (c.tw > a.wout) c.tw = a.wout;
     for (;;) {
@@ -365,13 +358,12 @@ static MbCfg wz_mb_choose(const WzMbArgs& a, int n) {
     c.ce = (c.mp > 3) ? 32 : 64;
     const int units = a.cin0 ? (a.cmid + c.ce - 1) / c.ce : a.kc;   // chunks (expand) or 32-channel K steps (no expand)
     const int tiles = ((a.hout + c.th - 1) / c.th) * ((a.wout + c.tw - 1) / c.tw) * n;
-    // workgroups wanted per launch: half the chip.  256 (round 1 / 2) gives the shortest launch (block 16: 9.1 + 4.4 us against
-    // 15.8 + 2.8) -- and 50.9 k frames/s against 52.0 k with four lanes in flight: the other lanes' launches want the CUs
+    // workgroups wanted per launch: half the chip.  256 gives the shortest launch (block 16: 9.1 + 4.4 us against 15.8 + 2.8) -- the latency
+    // schedule's choice -- and 50.9 k frames/s against 52.0 k with four lanes in flight: the other lanes' launches want the CUs
     // (profiles/r03_wave_counts_and_cu_footprints.txt)
-    const int target = wz_mb_env("WZ_MB_WGS", wz_latency_schedule() ? 256 : 128);
+    const int target = wz_latency_schedule() ? 256 : 128;
     int nsplit = (target + tiles - 1) / tiles;
-    const int max_split = wz_mb_env("WZ_MB_MAXSPLIT", 16);
-    if (nsplit > max_split) nsplit = max_split;
+    if (nsplit > MB_MAX_SPLIT) nsplit = MB_MAX_SPLIT;
     if (nsplit > units) nsplit = units;
     if (nsplit < 1 || !a.ws) nsplit = 1;
     while (nsplit > 1 && (size_t)nsplit * a.M * a.n_pad * 4 > a.ws_bytes) --nsplit;
@@ -388,16 +380,14 @@ static int wz_mb_launch(WzMbArgs a, const MbCfg& c, int n, hipStream_t s, bool p
     a.tiles_x = (a.wout + c.tw - 1) / c.tw;
     a.nsplit = c.nsplit;
     a.cpg = c.cpg;
-    size_t lds = 0;
+    a.ebufs = 1;
     a.stage = 0;
+    size_t lds = 0;
     if (EXPAND) {
-        const int P = ((c.th - 1) * a.stride + 3) * ((c.tw - 1) * a.stride + 3);
-        (void)P;
-        a.ebufs = (c.cpg > 1 && wz_mb_env("WZ_MB_EBUFS", 1) == 2) ? 2 : 1;
-        lds = (size_t)a.ebufs * MP * 64 * (CE + 8) * sizeof(half_t)              // chunk buffer(s)
+        lds = (size_t)MP * 64 * (CE + 8) * sizeof(half_t)                        // chunk buffer
               + (size_t)c.cpg * CE * (9 * sizeof(half_t) + 2 * sizeof(float));   // depthwise weights + bias, expand bias
         const size_t wbytes = (size_t)(c.cpg * CE / 16) * KCI * 1024 + (size_t)NTO * (c.cpg * CE / 32) * 1024;
-        if (lds + wbytes <= (size_t)wz_mb_env("WZ_MB_STAGE_KB", 96) * 1024) {    // GEMM weights of the group fit in LDS
+        if (lds + wbytes <= MB_STAGE_BYTES) {    // GEMM weights of the group fit in LDS
             a.stage = 1;
             lds += wbytes;
         }

@@ -17,8 +17,8 @@
 #include "wz_common.h"
 
 
-// CS_WAVES: waves per workgroup / tile (8; 4: half a CU per workgroup, a longer chunk walk)
-template <bool EXPAND, int MPW, int MQW, int KCI, int NTO, int CS_WAVES = 8>
+constexpr int CS_WAVES = 8;   // waves per workgroup / tile
+template <bool EXPAND, int MPW, int MQW, int KCI, int NTO>
 __global__ __launch_bounds__(CS_WAVES * 64) void wz_k_mbconv_cs(const WzMbArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char wz_cs_smem[];
     WZ_LANE_STAMP(a.dbg);
@@ -255,19 +255,14 @@ __global__ __launch_bounds__(CS_WAVES * 64) void wz_k_mbconv_cs(const WzMbArgs a
 }
 
 // ---------------------------------------------------------------------------------------------
-static int wz_cs_env(const char* name, int dflt) {
-    const char* e = wz_dev_getenv(name);
-    return (e && atoi(e) > 0) ? atoi(e) : dflt;
-}
-
-template <bool EXPAND, int MPW, int MQW, int KCI, int NTO, int CS_WAVES = 8>
+template <bool EXPAND, int MPW, int MQW, int KCI, int NTO>
 static int wz_cs_launch(WzMbArgs a, int n, hipStream_t s, bool prepare) {
     constexpr int EB = EXPAND ? MPW * 16 * 40 * 2 : 0;
     constexpr int NTC = NTO > 10 ? 10 : NTO;
     constexpr int RED = CS_WAVES * MQW * NTC * 1024;
     const size_t region = (size_t)(CS_WAVES * EB > RED ? CS_WAVES * EB : RED);
     const size_t lds = region + (size_t)a.cmid_pad * (9 * 2 + 2 * 4);
-    auto k = wz_k_mbconv_cs<EXPAND, MPW, MQW, KCI, NTO, CS_WAVES>;
+    auto k = wz_k_mbconv_cs<EXPAND, MPW, MQW, KCI, NTO>;
     if (prepare) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         return lds <= 160 * 1024 ? 0 : -1;
@@ -276,64 +271,39 @@ static int wz_cs_launch(WzMbArgs a, int n, hipStream_t s, bool prepare) {
     return 1;
 }
 
-// Serves the blocks with 19x19 outputs (blocks 6 .. 12); the 10x10 ones on request (WZ_MB_CS_MIN_W).  -2: does not apply (caller falls back to wz_launch_mbconv).
+// Serves the blocks with 19x19 outputs (blocks 6 .. 12) and, under the throughput schedule, the 10x10 ones.  -2: does not apply (the caller falls
+// back to wz_launch_mbconv).
 int wz_launch_mbconv_cs(const WzMbArgs& a0, int n, hipStream_t s, bool prepare) {
-    static const int enabled = wz_cs_env("WZ_MB_CS", 1);
-    // On the 10x10 maps (blocks 13 .. 16: 9 tiles per frame, 18 - 30 chunks) this kernel takes longer alone than channel groups
-    // over 256 workgroups + a reduce launch (block 16: 31 us against 10 + 4) -- every workgroup streams all of the block's
-    // 0.6 - 0.9 MB of weights -- but it occupies 72 CUs instead of all of them, writes no fp32 partial sums (80 MB per batch
-    // out and back) and needs no reduce launches (31 graph nodes instead of 35): 49.1 k -> 50.1 k frames/s with four lanes in flight,
-    // p50 0.380 -> 0.394 ms (profiles/r03_wave_counts_*; round 1 measured the same trade at +1 %, round 2 at +0.6 %).  Default since
-    // round 3; WZ_MB_CS_MIN_W=11 brings the channel-group kernel back for the 10x10 maps.
-    static const int min_w = wz_cs_env("WZ_MB_CS_MIN_W", wz_latency_schedule() ? 11 : 1);
-    if (a0.stem || a0.wout > 19 || ((enabled != 1 || a0.wout < min_w) && !a0.has_out2)) return -2;   // (a block with a second output runs here or nowhere)
+    // On the 10x10 maps (blocks 13 .. 16: 9 tiles per frame, 18 - 30 chunks) this kernel takes longer alone than channel groups over 256
+    // workgroups + a reduce launch (block 16: 31 us against 10 + 4) but occupies 72 CUs instead of all of them, writes no fp32 partial sums and
+    // needs no reduce launches: 49.1 k -> 50.1 k frames/s with four lanes in flight, p50 0.380 -> 0.394 ms (profiles/r03_wave_counts_*) -- the
+    // throughput schedule's choice.  The latency schedule (WZ_MB_CS_MIN_W=11) keeps the channel-group kernel for the 10x10 maps.
+    static const int min_w = wz_dev_env_int("WZ_MB_CS_MIN_W", wz_latency_schedule() ? 11 : 1);
+    // Block 16 (320 output channels: 20 output tiles) runs here as TWO workgroups per tile with 10 output tiles each -- the expand and depthwise
+    // stages are done twice, on 72 tiles that costs nothing: 15.8 + 2.8 us and a kernel boundary -> 12.7 us, 51.8 k -> 52.8 k frames/s
+    // (profiles/r03_four_waves_per_simd.txt (e)).  WZ_MB_CS_SPLIT16=0, the latency schedule's choice: the channel-group kernel + reduce.
+    static const int split16 = wz_dev_env_int("WZ_MB_CS_SPLIT16", wz_latency_schedule() ? 0 : 1);
+    if (a0.stem || a0.wout > 19 || (a0.wout < min_w && !a0.has_out2)) return -2;   // (a block with a second output runs here or nowhere)
     const int nto = a0.n_pad / 16;
-    // ... except block 16 (320 output channels, 0.9 MB of weights per workgroup: 31 us alone against 9 + 4): it stays on the channel-group
-    // kernel -- 50.0 k frames/s either way, p50 0.380 instead of 0.395 ms (WZ_MB_CS_MAX_NTO=20: on this kernel as well)
-    static const int max_nto = wz_cs_env("WZ_MB_CS_MAX_NTO", 10);   // blocks with more output tiles than this stay on the channel-group kernel
-    // ... until late round 3: block 16 runs on this kernel as TWO workgroups per tile with 10 output tiles each (WZ_MB_CS_SPLIT16, default 1;
-    // the expand and depthwise stages are done twice -- on 72 tiles that costs nothing): 15.8 + 2.8 us and a kernel boundary -> 12.7 us,
-    // no fp32 partial sums of any block in HBM any more, 31 graph nodes; 51.8 k -> 52.8 k frames/s, p50 0.383 -> 0.376 ms
-    // (profiles/r03_four_waves_per_simd.txt (e)).  0: the channel-group kernel + reduce as before.
-    static const int split16 = [] {
-        const char* e = wz_dev_getenv("WZ_MB_CS_SPLIT16");   // (0 is a value here, unlike with wz_cs_env)
-        return (e && e[0]) ? atoi(e) : (wz_latency_schedule() ? 0 : 1);
-    }();
-    if (!prepare && nto > max_nto && !(split16 == 1 && nto == 20 && a0.kc0 == 5 && a0.stride == 1)) return -2;
     WzMbArgs a = a0;
     a.nsplit = 1;
     a.th = 4; a.tw = 4;
     a.tiles_y = (a.hout + a.th - 1) / a.th;
     a.tiles_x = (a.wout + a.tw - 1) / a.tw;
-    static const int nw10 = wz_cs_env("WZ_MB_CS_NW", 8);   // waves per tile on the 10x10 maps (4 or 8)
-    if (a.cin0 == 0) {   // no expand stage (block 13)
-        if (nto == 10) {
-            if (prepare) (void)wz_cs_launch<false, 1, 1, 1, 10, 4>(a, n, s, true);
-            if (!prepare && nw10 == 4) return wz_cs_launch<false, 1, 1, 1, 10, 4>(a, n, s, false);
-            return wz_cs_launch<false, 1, 1, 1, 10>(a, n, s, prepare);
-        }
-        return -2;
-    }
+    if (a.cin0 == 0) return nto == 10 ? wz_cs_launch<false, 1, 1, 1, 10>(a, n, s, prepare) : -2;   // no expand stage (block 13)
     if (a.stride == 2) {   // halo 9 x 9 = 81 pixels -> 6 m-tiles
         if (a.kc0 == 1 && nto == 4) return wz_cs_launch<true, 6, 1, 1, 4>(a, n, s, prepare);
         if (a.kc0 == 3 && nto == 10) return wz_cs_launch<true, 6, 1, 3, 10>(a, n, s, prepare);   // block 13 with its expand stage (19x19 -> 10x10)
         return -2;
     }
     // stride 1: halo 6 x 6 = 36 pixels -> 3 m-tiles
-#define CS_CASE(K, N) if (a.kc0 == K && nto == N) return wz_cs_launch<true, 3, 1, K, N>(a, n, s, prepare)
-    CS_CASE(2, 4);
-    CS_CASE(2, 6);
-    CS_CASE(3, 6);
-    if (a.kc0 == 5 && nto == 10) {
-        if (prepare) (void)wz_cs_launch<true, 3, 1, 5, 10, 4>(a, n, s, true);
-        if (!prepare && nw10 == 4) return wz_cs_launch<true, 3, 1, 5, 10, 4>(a, n, s, false);
-    }
-    CS_CASE(5, 10);
-    if (!prepare && split16 == 1 && a.kc0 == 5 && nto == 20) {
+    if (a.kc0 == 2 && nto == 4) return wz_cs_launch<true, 3, 1, 2, 4>(a, n, s, prepare);
+    if (a.kc0 == 2 && nto == 6) return wz_cs_launch<true, 3, 1, 2, 6>(a, n, s, prepare);
+    if (a.kc0 == 3 && nto == 6) return wz_cs_launch<true, 3, 1, 3, 6>(a, n, s, prepare);
+    if (a.kc0 == 5 && nto == 10) return wz_cs_launch<true, 3, 1, 5, 10>(a, n, s, prepare);
+    if (a.kc0 == 5 && nto == 20 && split16 == 1) {
         a.nsplit = 2;
-        return wz_cs_launch<true, 3, 1, 5, 10>(a, n, s, false);
+        return wz_cs_launch<true, 3, 1, 5, 10>(a, n, s, prepare);
     }
-    CS_CASE(5, 20);
-#undef CS_CASE
     return -2;
 }

@@ -23,13 +23,13 @@
 //   CS = false  one WAVEFRONT per pixel tile, 4 independent waves per workgroup (150x150 ... 38x38 maps);
 //               at stride 1 the lane's two output pixels are vertically adjacent, so the 4 x 3 taps under them
 //               are read once for both (12 LDS reads instead of 18);
-//   CS = true   8 waves on ONE 4x4 tile, the expanded channels dealt out over the waves, partial accumulators
-//               summed through LDS in wave order (19x19 maps).
+//   CS = true   3 - 8 waves on ONE tile, the expanded channels dealt out over the waves, the tile's halo fetched once per
+//               workgroup and shared through LDS, partial accumulators summed through LDS in wave order (19x19 maps,
+//               the stride-1 38x38 blocks, the larger maps when a batch has too few tiles to fill the chip).
 #include "wz_common.h"
 
 #include "k_hp_ops.h"
 
-#define HP_CS_WAVES 8
 #ifndef WZ_HP_STAMPS
 #define WZ_HP_STAMPS 0   // 1: cycle counts of the first workgroup's wave 0 into WzMbArgs::dbg (tools/hp_probe.py)
 #endif
@@ -52,13 +52,13 @@
 // whose waves spend their time waiting rather than issuing).
 // ONEPASS (CS only): the workgroup has at least as many waves as the block has chunks, every wave walks at most ONE -- the
 // halo fragments and the expand weights are then dead after the expand stage and the kernel fits 3 waves per SIMD.
-// SH (CS only): the halo fragments are fetched ONCE per workgroup -- each wave loads its share of the MPW x KCI x 2 fragments,
-// they meet in LDS, every wave reads all of them back -- instead of once per wave (8 or 12 times the same 13 .. 18 KiB through
-// the vector memory path of one CU: the prologue of the 19x19 blocks was bound by exactly that, profiles/r02zq_*).
+// CS: the halo fragments are fetched ONCE per workgroup -- each wave loads its share of the MPW x KCI x 2 fragments, they meet
+// in LDS, every wave reads all of them back -- instead of once per wave (the same 13 .. 18 KiB through the vector memory path
+// of one CU for every wave: the prologue of the 19x19 blocks was bound by exactly that, profiles/r02zq_*, r02zt_*).
 // QE: the chunk buffer holds the 16-bit FLOAT form of v / 6 (above) instead of unorm16 of v / 6 (the ROBUST program, WzMbArgs::qenc): a
 // relative step -- what channels of very different scale need.  Round 3 kept square roots there (one v_sqrt_f32
 // per stored value, one multiply per tap): coarser for small channels and slower to encode.
-// LEAN (CS + SH, one output m-tile; MQW = 1): the shapes behind the 19x19 maps (block 13: 96 -> 576 -> 160 at stride 2; blocks 14 .. 16:
+// LEAN (CS, one output m-tile; MQW = 1): the shapes behind the 19x19 maps (block 13: 96 -> 576 -> 160 at stride 2; blocks 14 .. 16:
 // 160 -> 960 -> 160 / 320 on 10x10) do not fit 256 registers the way the others are written -- MPW x KCI x 2 halo fragments alone are
 // 144 / 120 of them -- so the halo fragments of ONE m-tile at a time come back from LDS inside the expand stage, and a workgroup
 // finishes NTO of the block's n-tiles: blockIdx.x % nsplit picks which (the expand and depthwise stages are repeated per group:
@@ -66,10 +66,10 @@
 // (Rounds 4 / 5 also dealt a 10x10 block's chunks over several WORKGROUPS per tile -- channel groups with a ticketed last-arriver sum -- and stored
 // block 13's second output from here; since round 6 the 10x10 blocks of the robust program run as two GEMM-shaped launches at every batch size
 // (k_mbconv_hp2.hip: faster from one frame up, profiles/r06_hp2_by_batch_size.txt) and both mechanisms left this kernel.)
-template <int NW, bool CS, bool STEM, int MPW, int MQW, int KCI, int NTO, int OCC = 2, bool ONEPASS = false, bool SH = false,
-          bool QE = false, bool LEAN = false>
+template <int NW, bool CS, bool STEM, int MPW, int MQW, int KCI, int NTO, int OCC = 2, bool ONEPASS = false, bool QE = false,
+          bool LEAN = false>
 __global__ __launch_bounds__(NW * 64, OCC) void wz_k_mbconv_hp(const WzMbArgs a) {
-    static_assert(!LEAN || (CS && SH && !ONEPASS && !STEM), "lean: chunk-split, shared halo");
+    static_assert(!LEAN || (CS && !ONEPASS && !STEM), "lean: chunk-split");
     static_assert(!LEAN || MQW == 1, "lean builds: 4 x 4 tiles (the 4 x 8 lean builds of round 5 lost their A/B: profiles/r05_blocks_13_16_tile_4x8.txt)");
     extern __shared__ __attribute__((aligned(16))) unsigned char wz_hp_smem[];
     WZ_LANE_STAMP(a.dbg);
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void wz_k_mbconv_hp(const WzMbArgs a)
             const half_t e0l = g == 0 ? v8[4] : g == 1 ? v8[6] : z16, e1l = g == 0 ? v8[5] : z16;
             xh[i][0] = (half8_t){va[0], va[1], va[2], e0h, vb[0], vb[1], vb[2], e1h};
             xl[i][0] = (half8_t){va[4], va[5], va[6], e0l, vb[4], vb[5], vb[6], e1l};
-        } else if constexpr (!SH) {
+        } else if constexpr (!CS) {
             const half_t* src = a.in + ((size_t)(b * a.hin + (ok ? iy : 0)) * a.win + (ok ? ix : 0)) * (2 * a.cin0);
 #pragma unroll
             for (int c = 0; c < KCI; ++c) {
@@ -171,16 +171,16 @@ __global__ __launch_bounds__(NW * 64, OCC) void wz_k_mbconv_hp(const WzMbArgs a)
             }
         }
     }
-    // SH: fragment f = (i * KCI + c) * 2 + (0: hi, 1: lo) is fetched by wave f % NW and parked at f KiB of the halo area
+    // CS: fragment f = (i * KCI + c) * 2 + (0: hi, 1: lo) is fetched by wave f % NW and parked at f KiB of the halo area
     constexpr int NFRAG = MPW * KCI * 2;
     unsigned char* const halo_l = wz_hp_smem + REGION + (size_t)a.cmid_pad * (LDSW ? 44 : 8);
     // (its LDS stores wait for the loads: they come behind the ISSUE of the staging loads and of the first expand weights below -- the
     //  prologue of these kernels used to take two memory round trips one after the other, `s_waitcnt vmcnt(0)` in front of the halo's
     //  ds_write and again in front of the staged biases', round 4)
-    constexpr int PERW = SH ? (NFRAG + NW - 1) / NW : 1;
+    constexpr int PERW = CS ? (NFRAG + NW - 1) / NW : 1;
     half8_t part[PERW];
-    if constexpr (SH) {
-        static_assert(!STEM && CS, "shared halo: chunk-split kernels only");
+    if constexpr (CS) {
+        static_assert(!STEM, "the stem block runs one wave per tile");
 #pragma unroll
         for (int k = 0; k < PERW; ++k) {
             const int f = wave + k * NW;     // wave-uniform
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void wz_k_mbconv_hp(const WzMbArgs a)
         }
     }
     auto park_halo = [&]() {
-        if constexpr (SH) {
+        if constexpr (CS) {
 #pragma unroll
             for (int k = 0; k < PERW; ++k) {
                 const int f = wave + k * NW;
@@ -239,10 +239,10 @@ __global__ __launch_bounds__(NW * 64, OCC) void wz_k_mbconv_hp(const WzMbArgs a)
     };
     constexpr bool WA_AHEAD = !((LEAN || !CS) && OCC >= 4);   // the next pass's expand fragments requested a stage ahead (4 waves per SIMD: at the
                                                      // top of the pass instead -- the other waves cover the wait, the registers are not there)
-    if (!SH && WA_AHEAD && ps0 < c_hi) load_wa(ps0);
+    if (!CS && WA_AHEAD && ps0 < c_hi) load_wa(ps0);
     {   // biases (and, LDSW, depthwise weights) into LDS: every load of a thread in flight before its first store
         constexpr int NT = NW * 64;
-        constexpr int WD_IT = LEAN ? (NW >= 8 ? 5 : 9) : NW >= 8 ? 3 : 8;   // 9 * cmid_pad / 4 float4s over NT threads: at most this many each (checked by the launcher)
+        constexpr int WD_IT = LEAN ? (NW >= 8 ? 5 : 9) : 8;   // 9 * cmid_pad / 4 float4s over NT threads: at most this many each (checked by the launcher)
         const int nb4 = a.cmid_pad >> 2;
         float4_t sw[WD_IT], sb, se;
         if constexpr (LDSW) {
@@ -256,7 +256,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void wz_k_mbconv_hp(const WzMbArgs a)
         const bool hb = ib < nb4;
         sb = hb ? *reinterpret_cast<const float4_t*>(a.bd + ib * 4) : (float4_t){0.f, 0.f, 0.f, 0.f};
         se = (hb && ib * 4 < a.nmid_pad) ? *reinterpret_cast<const float4_t*>(a.be + ib * 4) : (float4_t){0.f, 0.f, 0.f, 0.f};
-        if constexpr (SH) {   // shared halo: the first expand weights are requested LAST (nothing in front of the barrier waits for them) ...
+        if constexpr (CS) {   // shared halo: the first expand weights are requested LAST (nothing in front of the barrier waits for them) ...
             __builtin_amdgcn_sched_barrier(0);
             if (WA_AHEAD && ps0 < c_hi) load_wa(ps0);
             __builtin_amdgcn_sched_barrier(0);
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void wz_k_mbconv_hp(const WzMbArgs a)
         }
     }
     const long long t_issued = WZ_HP_STAMPS ? __builtin_readcyclecounter() : 0;
-    __syncthreads();   // staged biases (SH: and halo fragments) visible; the only workgroup barrier in front of the loop
+    __syncthreads();   // staged biases (CS: and halo fragments) visible; the only workgroup barrier in front of the loop
     if (!CS && !live) return;
 
     long long t_loop = 0, t_first = 0, cy_expand = 0, cy_dw = 0, cy_proj = 0;
@@ -309,7 +309,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void wz_k_mbconv_hp(const WzMbArgs a)
                 wt1[tp] = *reinterpret_cast<const float4_t*>(wd32 + (size_t)tp * a.cmid_pad + coff + 4);
             }
         }
-        if constexpr (SH && !LEAN) {   // the halo fragments come back from LDS for every pass: they are dead behind the expand stage, which is
+        if constexpr (CS && !LEAN) {   // the halo fragments come back from LDS for every pass: they are dead behind the expand stage, which is
                               // what lets a multi-pass wave fit 168 registers (3 waves per SIMD, 12 per tile)
 #pragma unroll
             for (int i = 0; i < MPW; ++i)
@@ -661,13 +661,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void wz_k_mbconv_hp(const WzMbArgs a)
 }
 
 // ---------------------------------------------------------------------------------------------
-static int wz_hp_env(const char* name, int dflt) {
-    const char* e = wz_dev_getenv(name);
-    return (e && e[0] && atoi(e) >= 0) ? atoi(e) : dflt;
-}
-
-template <int NW, bool CS, bool STEM, int MPW, int MQW, int KCI, int NTO, int OCC = 2, bool ONEPASS = false, bool SH = false,
-          bool QE = false, bool LEAN = false>
+template <int NW, bool CS, bool STEM, int MPW, int MQW, int KCI, int NTO, int OCC = 2, bool ONEPASS = false, bool QE = false,
+          bool LEAN = false>
 static int wz_hp_launch(WzMbArgs a, int n, hipStream_t s, bool prepare) {
     if (ONEPASS && (a.cmid_pad >> 5) > NW) return -1;
     if (QE != (a.qenc != 0)) return -1;
@@ -682,9 +677,9 @@ static int wz_hp_launch(WzMbArgs a, int n, hipStream_t s, bool prepare) {
     constexpr int EB = MPW * 16 * 40 * 2;
     constexpr int RED = CS ? NW * (MQW * NTO / ((LEAN && OCC >= 4 && NTO % 2 == 0 && NTO >= 6) ? 2 : 1)) * 1024 : 0;
     const size_t region = (size_t)(NW * EB > RED ? NW * EB : RED);
-    const size_t lds = region + (size_t)a.cmid_pad * ((CS || OCC > 2) ? 8 + 36 : 8) + (SH ? (size_t)MPW * KCI * 2 * 1024 : 0);
-    if ((a.cmid_pad >> 2) > NW * 64 || 9 * (a.cmid_pad >> 2) > (LEAN ? (NW >= 8 ? 5 : 9) : NW >= 8 ? 3 : 8) * NW * 64) return -1;   // the staging code's fixed trip counts
-    auto k = wz_k_mbconv_hp<NW, CS, STEM, MPW, MQW, KCI, NTO, OCC, ONEPASS, SH, QE, LEAN>;
+    const size_t lds = region + (size_t)a.cmid_pad * ((CS || OCC > 2) ? 8 + 36 : 8) + (CS ? (size_t)MPW * KCI * 2 * 1024 : 0);
+    if ((a.cmid_pad >> 2) > NW * 64 || 9 * (a.cmid_pad >> 2) > (LEAN ? (NW >= 8 ? 5 : 9) : 8) * NW * 64) return -1;   // the staging code's fixed trip counts
+    auto k = wz_k_mbconv_hp<NW, CS, STEM, MPW, MQW, KCI, NTO, OCC, ONEPASS, QE, LEAN>;
     if (prepare) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         return lds <= 160 * 1024 ? 0 : -1;
@@ -694,281 +689,102 @@ static int wz_hp_launch(WzMbArgs a, int n, hipStream_t s, bool prepare) {
     return 1;
 }
 
-// The ROBUST program (WzMbArgs::qenc, `python -m watsor_amd.engine --robust`): all 17 blocks on this kernel with the float-form chunk
-// buffer, one launch shape per block shape -- the throughput defaults of the dispatcher below, plus the lean builds for blocks 13 .. 16.
-static int wz_launch_mbconv_hp_q(WzMbArgs a, int n, hipStream_t s, bool prepare) {
-    const int nto = a.n_pad / 16;
-    a.nsplit = 1;
-    if (a.nmid_pad != a.cmid_pad || (a.cmid_pad & 31) || a.kc != (a.cmid_pad >> 5) || !a.we_lo || !a.wp_lo) return -1;
-    // One or two frames per batch: 4 x 4 tiles instead of 4 x 8 on the stride-1 blocks of the 75x75 and 38x38 maps (block 2; blocks 4 / 5), whose 4 x 8 grids are
-    // 48 - 95 / 50 - 100 workgroups then.  Twice the waves, 36 halo pixels each instead of 60, the same arithmetic in the same order for every output pixel
-    // (bit-identical tensors: a tile shape only decides which lane holds a pixel).  Batch 1: block 2 10.4 -> 7.4 us, blocks 4 / 5 5.0 / 4.5 -> 3.1 / 2.9 us, a single
-    // frame's p50 0.269 -> 0.262 ms and +2.5 % frames/s from four lanes; batch 2 the same; from three frames up the 20 % more halo work costs what the fuller grid
-    // gains (batch 4: p50 -2 us, -0.6 % frames/s; batch 6: -2 % frames/s), and block 0's 150x150 grid is large enough at batch 1 (4.9 -> 5.9 us with 4 x 4):
-    // profiles/r06_small_batch_tiles_4x4.txt.  WZ_HP_TILES44=0 / 1: never / always (development library; read per launch).
-    const int tiles44 = wz_hp_env("WZ_HP_TILES44", 2);
-    auto small44 = [&]() { return tiles44 == 1 || (tiles44 == 2 && n <= 2); };
-    if (a.stem) {
-        if (!(a.kc0 == 1 && nto == 2 && a.stride == 1)) return -1;
-        return wz_hp_launch<4, false, true, 4, 2, 1, 2, 3, false, false, true>(a, n, s, prepare);
-    }
-    if (a.cin0 == 0) return -1;
-    if (a.wout > 19 && a.kc0 == 1 && nto == 2) {
-        const int nk32 = a.cmid_pad >> 5;
-        // One or two frames per batch, blocks 1 .. 3 (150 -> 75 stride 2, 75x75 stride 1, 75 -> 38 stride 2): the chunks of a 4 x 4 tile dealt over the waves of a
-        // workgroup -- one chunk per wave, halo fetched once and shared through LDS, partial accumulators summed through LDS in wave order: the shape of the
-        // 38x38 / 19x19 blocks -- instead of one wave per tile walking 3 - 5 chunks: 3 - 5 times the waves on grids of 25 - 95 workgroups.  Batch 1: blocks 1 / 2 / 3
-        // 6.4 / 7.2 / 8.5 -> 4.3 / 3.9 / 3.7 us, a single frame's p50 0.263 -> 0.254 ms, +3 % frames/s from four lanes; batch 2: p50 0.272 -> 0.264 ms.  From
-        // three frames up the repeated halo work and the accumulators' trip through LDS cost more CU time than the chip has to spare (batch 3: p50 -4 us, -5 %
-        // frames/s; batch 4: -8 %): profiles/r06_small_batch_chunk_split.txt.  The sum over a tile's chunks is taken in another order than at batch >= 3 (fp32
-        // partials in wave order instead of one running accumulator): tensors agree to fp32 rounding, not bit for bit -- as batch sizes differ elsewhere
-        // (split-K choices follow the pixel count).  WZ_HP_SMALL_CS=0 / 1: never / always (development library; read per launch).
-        const int small_cs = wz_hp_env("WZ_HP_SMALL_CS", 2);
-        const bool scs = small_cs == 1 || (small_cs == 2 && n <= 2);
-        if (a.stride == 2 && nk32 == 3) {
-            if (prepare && wz_hp_launch<3, true, false, 6, 1, 1, 2, 3, true, true, true>(a, n, s, true) < 0) return -1;
-            if (!prepare && scs) return wz_hp_launch<3, true, false, 6, 1, 1, 2, 3, true, true, true>(a, n, s, false);
-        }
-        if (a.stride == 2 && nk32 == 5) {
-            if (prepare && wz_hp_launch<5, true, false, 6, 1, 1, 2, 3, true, true, true>(a, n, s, true) < 0) return -1;
-            if (!prepare && scs) return wz_hp_launch<5, true, false, 6, 1, 1, 2, 3, true, true, true>(a, n, s, false);
-        }
-        if (a.stride == 1 && a.wout > 38 && nk32 == 5) {
-            if (prepare && wz_hp_launch<5, true, false, 3, 1, 1, 2, 3, true, true, true>(a, n, s, true) < 0) return -1;
-            if (!prepare && scs) return wz_hp_launch<5, true, false, 3, 1, 1, 2, 3, true, true, true>(a, n, s, false);
-        }
-        if (a.stride == 2) return wz_hp_launch<4, false, false, 6, 1, 1, 2, 3, false, false, true>(a, n, s, prepare);
-        if (a.wout <= 38 && nk32 == 6) {
-            if (prepare && wz_hp_launch<6, true, false, 3, 1, 1, 2, 4, false, true, true>(a, n, s, true) < 0) return -1;
-            if (!prepare && small44()) return wz_hp_launch<6, true, false, 3, 1, 1, 2, 4, false, true, true>(a, n, s, false);
-            return wz_hp_launch<6, true, false, 4, 2, 1, 2, 4, false, true, true>(a, n, s, prepare);
-        }
-        if (a.wout <= 38 && nk32 >= 4 && nk32 <= 5) return wz_hp_launch<3, true, false, 4, 2, 1, 2, 2, false, true, true>(a, n, s, prepare);
-        if (a.wout > 38) {
-            if (prepare && wz_hp_launch<4, false, false, 3, 1, 1, 2, 3, false, false, true>(a, n, s, true) < 0) return -1;
-            if (!prepare && small44()) return wz_hp_launch<4, false, false, 3, 1, 1, 2, 3, false, false, true>(a, n, s, false);
-        }
-        return wz_hp_launch<4, false, false, 4, 2, 1, 2, 3, false, false, true>(a, n, s, prepare);
-    }
-    if (a.wout > 10) {
-        if (a.stride == 2) return (a.kc0 == 1 && nto == 4) ? wz_hp_launch<6, true, false, 6, 1, 1, 4, 4, false, true, true, true>(a, n, s, prepare) : -1;
-        if (a.kc0 == 2 && nto == 4) return wz_hp_launch<8, true, false, 3, 1, 2, 4, 4, false, true, true, true>(a, n, s, prepare);
-        if (a.kc0 == 2 && nto == 6) return wz_hp_launch<8, true, false, 3, 1, 2, 6, 4, false, true, true, true>(a, n, s, prepare);
-        if (a.kc0 == 3 && nto == 6) return wz_hp_launch<8, true, false, 3, 1, 3, 6, 4, false, true, true, true>(a, n, s, prepare);
-        return -1;
-    }
-    return -1;   // (the 10x10 maps -- blocks 13 .. 16 -- keep the linear chunk buffer in the robust program: wz_launch_mbconv_hp below)
+// ---- the decision lists: block shape (+ what depends on the batch size) -> the ONE instantiation that runs it ----------------------
+// HP(...): wz_hp_launch<NW, CS, STEM, MPW, MQW, KCI, NTO, OCC, ONEPASS, QE, LEAN> on the arguments in scope.  MPW / MQW follow the tile:
+// 4 x 8 outputs at stride 1 (halo 6 x 10 = 60 pixels: 4, 2), 4 x 4 at stride 1 (6 x 6 = 36: 3, 1), 4 x 4 at stride 2 (9 x 9 = 81: 6, 1).
+// The launch shapes that lost their A/B are listed, one line each with their profile, in DESIGN.md section 5 and tools/README.md.
+#define HP(...) wz_hp_launch<__VA_ARGS__>(a, n, s, prepare)
+
+// a rule for batches of one or two frames; its development knob (read per launch): 0 = never, 1 = always
+static bool wz_hp_small_batch(const char* knob, int n) {
+    const int k = wz_dev_env_int(knob, 2);
+    return k == 1 || (k == 2 && n <= 2);
 }
 
-// Blocks 0 (with the stem) .. 12 of SSD-MobileNet-v2 300x300.  prepare: 0 = a kernel exists (its attributes are set),
-// -1 = no kernel for this shape; launch: 1.
-//   maps wider than WZ_HP_CS_MAX_W (default 19): one wavefront per tile, every wave walks all chunks;
-//   19x19: 8 waves per 4x4 tile, 2 - 3 chunks per wave;
-//   WZ_HP_CS_MAX_W=38 / 75 puts the 38x38 / 75x75 maps on workgroups of 5 / 6 waves per tile with ONE chunk per wave as
-//     well.  Measured (profiles/r02c_*): the 38x38 stride-1 blocks get faster alone (13.6 -> 11.0 us: 100 tiles x 8 frames of
-//     waves walking 6 chunks each leave most of the GPU idle) but every wave repeats the halo load and the accumulators
-//     take a trip through LDS, and with four lanes in flight CU x time is what counts: 37.2 k frames/s against 40.2 k
-//     with one wave per tile (75x75 on it as well: 35.0 k).
-// The launch shapes that lost their A/B (rounds 2 .. 5: HISTORY.md part B, each with its profile) stay reachable through their knobs in the DEVELOPMENT
-// library only: HP_DEV(...) compiles its argument there and to nothing in the product library, which instantiates the ~20 shapes its defaults can reach
-// at some batch size and nothing else (tests/test_gpu_parity.py holds the two libraries' rows bit-equal).
-#ifdef WZ_DEV_BUILD
-#define HP_DEV(...) __VA_ARGS__
-#else
-#define HP_DEV(...)
-#endif
+// The ROBUST program (WzMbArgs::qenc, `python -m watsor_amd.engine --robust`): blocks 0 .. 12 with the float-form chunk buffer.
+//   scs  (n <= 2, WZ_HP_SMALL_CS): blocks 1 .. 3 chunk-split, one chunk per wave, instead of one wave per tile walking 3 - 5 chunks on grids of
+//        25 - 95 workgroups -- batch 1: 6.4 / 7.2 / 8.5 -> 4.3 / 3.9 / 3.7 us; from three frames up the repeated halo work costs more CU time than
+//        the chip has to spare (batch 3: -5 % frames/s): profiles/r06_small_batch_chunk_split.txt.  The chunk sum is taken in wave order there:
+//        tensors agree with the batch >= 3 shapes to fp32 rounding, not bit for bit.
+//   t44  (n <= 2, WZ_HP_TILES44): 4 x 4 tiles instead of 4 x 8 on the stride-1 blocks of the 75x75 and 38x38 maps (blocks 2, 4, 5) -- twice the
+//        waves, 36 halo pixels each instead of 60, bit-identical tensors; batch 1: block 2 10.4 -> 7.4 us; from three frames up the 20 % more halo
+//        work costs what the fuller grid gains: profiles/r06_small_batch_tiles_4x4.txt.
+static int wz_hp_pick_q(const WzMbArgs& a, int n, hipStream_t s, bool prepare, bool scs, bool t44) {
+    const int nto = a.n_pad / 16, nk32 = a.cmid_pad >> 5;
+    if (a.stem) return (a.kc0 == 1 && nto == 2 && a.stride == 1) ? HP(4, false, true, 4, 2, 1, 2, 3, false, true) : -1;
+    if (a.cin0 == 0 || a.wout <= 10) return -1;   // (the 10x10 blocks keep the linear chunk buffer in the robust program: wz_hp_pick)
+    if (a.wout > 19 && a.kc0 == 1 && nto == 2) {
+        if (a.stride == 2) {
+            if (scs && nk32 == 3) return HP(3, true, false, 6, 1, 1, 2, 3, true, true);
+            if (scs && nk32 == 5) return HP(5, true, false, 6, 1, 1, 2, 3, true, true);
+            return HP(4, false, false, 6, 1, 1, 2, 3, false, true);
+        }
+        if (scs && a.wout > 38 && nk32 == 5) return HP(5, true, false, 3, 1, 1, 2, 3, true, true);
+        if (a.wout <= 38 && nk32 == 6) return t44 ? HP(6, true, false, 3, 1, 1, 2, 4, false, true) : HP(6, true, false, 4, 2, 1, 2, 4, false, true);
+        if (a.wout <= 38 && nk32 >= 4 && nk32 <= 5) return HP(3, true, false, 4, 2, 1, 2, 2, false, true);
+        if (a.wout > 38 && t44) return HP(4, false, false, 3, 1, 1, 2, 3, false, true);
+        return HP(4, false, false, 4, 2, 1, 2, 3, false, true);
+    }
+    if (a.wout > 19) return -1;
+    // 19x19 outputs: the lean builds (wz_hp_pick)
+    if (a.stride == 2) return (a.kc0 == 1 && nto == 4) ? HP(6, true, false, 6, 1, 1, 4, 4, false, true, true) : -1;
+    if (a.kc0 == 2 && nto == 4) return HP(8, true, false, 3, 1, 2, 4, 4, false, true, true);
+    if (a.kc0 == 2 && nto == 6) return HP(8, true, false, 3, 1, 2, 6, 4, false, true, true);
+    if (a.kc0 == 3 && nto == 6) return HP(8, true, false, 3, 1, 3, 6, 4, false, true, true);
+    return -1;
+}
+
+// Blocks 0 (with the stem) .. 12 of the default `-p 16` program (linear unorm16 chunk buffer).
+//   few: one wave per tile would give at most HP_CS_FEW_WGS workgroups (a single camera's frame at a time is the reference's normal load,
+//        detector.py:102-112) and leave most CUs empty with every wave walking 5 - 6 chunks -- the chunks go to the waves of a workgroup instead
+//        (batch 1, profiles/r02t_*).  With the chip filled by the batch one wave per tile wins: every chunk-split wave repeats halo work and the
+//        accumulators take a trip through LDS (37.2 k against 40.2 k frames/s, profiles/r02c_*).
+constexpr int HP_CS_FEW_WGS = 64;
+constexpr int HP_CS_S1_MAX_W = 38;   // stride-1 blocks on maps up to this width are chunk-split at every batch size (profiles/r03_wave_counts_*)
+static int wz_hp_pick(const WzMbArgs& a, int n, hipStream_t s, bool prepare, bool few) {
+    const int nto = a.n_pad / 16, nk32 = a.cmid_pad >> 5;
+    // one wave per tile at 3 waves per SIMD where the waves wait for the halo gather and for LDS (stem 22.4 -> 18.1 us, stride-2 blocks 16.5 / 10.5 ->
+    // 11.9 / 9.9 us), at 2 on the 38x38 maps (too few waves to fill even two per SIMD): profiles/r02g_*
+    if (a.stem) return (a.kc0 == 1 && nto == 2 && a.stride == 1) ? HP(4, false, true, 4, 2, 1, 2, 3) : -1;
+    if (a.cin0 == 0) return -1;
+    if (a.wout > 19 && a.kc0 == 1 && nto == 2) {
+        const bool cs = ((a.stride == 1 && a.wout <= HP_CS_S1_MAX_W) || few) && nk32 >= 4 && nk32 <= 6;
+        if (a.stride == 2) return (cs && nk32 <= 5) ? HP(5, true, false, 6, 1, 1, 2, 2) : HP(4, false, false, 6, 1, 1, 2, 3);
+        // 38x38: one chunk per wave at 128 registers, 4 waves per SIMD (profiles/r03_four_waves_per_simd.txt); few frames on the 75x75 map: three
+        // waves per tile, two chunks each, so that two workgroups share a CU (profiles/r02t_*, r03_wave_counts_*)
+        if (cs && a.wout <= 38) return nk32 <= 5 ? HP(5, true, false, 4, 2, 1, 2, 4) : HP(6, true, false, 4, 2, 1, 2, 4);
+        if (cs) return HP(3, true, false, 4, 2, 1, 2, 2);
+        return a.wout >= 75 ? HP(4, false, false, 4, 2, 1, 2, 3) : HP(4, false, false, 4, 2, 1, 2, 2);
+    }
+    if (a.wout > 19) return -1;
+    // 19x19 outputs: lean builds at 128 registers -- six waves, one chunk each, behind the 38x38 map; EIGHT waves per tile on the 19x19 map (halo
+    // fragments per pixel tile, no weight prefetch, accumulators through LDS in two rounds): as many waves as the lowest-latency shape with the CU
+    // footprint of the four-wave one, 52.1 -> 52.5 k frames/s, p50 0.399 -> 0.386 ms (profiles/r03_four_waves_per_simd.txt)
+    if (a.stride == 2) return (a.kc0 == 1 && nto == 4) ? HP(6, true, false, 6, 1, 1, 4, 4, false, false, true) : -1;
+    if (a.kc0 == 2 && nto == 4) return HP(8, true, false, 3, 1, 2, 4, 4, false, false, true);
+    if (a.kc0 == 2 && nto == 6) return HP(8, true, false, 3, 1, 2, 6, 4, false, false, true);
+    if (a.kc0 == 3 && nto == 6) return HP(8, true, false, 3, 1, 3, 6, 4, false, false, true);
+    return -1;
+}
+#undef HP
+
+// prepare: 0 = every instantiation that some batch size can pick for this block exists and has its attributes set, -1 = no kernel for this
+// shape; launch: 1.  The 10x10 blocks (13 .. 16 of the robust program; the default program runs them on wz_k_mbconv_cs) are two GEMM-shaped
+// launches, k_mbconv_hp2.hip: the engine asks wz_mbconv_hp2_applies() and enqueues them itself, this entry only prepares their kernels.
 int wz_launch_mbconv_hp(const WzMbArgs& a0, int n, hipStream_t s, bool prepare) {
-    static const int cs_max_w = wz_hp_env("WZ_HP_CS_MAX_W", 19);
-    static const int cs_few_wgs = wz_hp_env("WZ_HP_CS_FEW_WGS", 64);   // chunk-split when one wave per tile gives at most this many workgroups
-    // WZ_HP_SH (default 1): chunk-split workgroups fetch the halo once and share it through LDS.  Measured at batch 8
-    // (profiles/r02zt_*): the 19x19 blocks 8.0 -> 6.95 us (cmid 384) and 12.3 -> 10.5 us (cmid 576), 45.6 k -> 47.3 k frames/s.
-    // WZ_HP_W12 (default 0): 12 waves per 19x19 tile (3 per SIMD, re-reading the halo from LDS every pass) instead of 8 -- the
-    // cmid-384 blocks 6.95 -> 6.76 us, no gain in frames/s; the cmid-576 shape does not fit 168 registers (spills: 16 us) and stays on 8.
-    static const int sh = wz_hp_env("WZ_HP_SH", 1);
-    static const int w12 = wz_hp_env("WZ_HP_W12", 0);
-    if (a0.qenc) return wz_launch_mbconv_hp_q(a0, n, s, prepare);
-    const int nto = a0.n_pad / 16;
     WzMbArgs a = a0;
     a.nsplit = 1;
     if (a.nmid_pad != a.cmid_pad || (a.cmid_pad & 31) || a.kc != (a.cmid_pad >> 5) || !a.we_lo || !a.wp_lo) return -1;
-    const int nk32 = a.cmid_pad >> 5;
-    // waves per SIMD of the one-wave-per-tile kernels.  Measured (profiles/r02g_*, batch 8): 3 instead of 2 takes the stem
-    // block from 22.4 to 18.1 us and the stride-2 blocks from 16.5 / 10.5 to 11.9 / 9.9 us (their waves wait for the halo
-    // gather and for LDS, a third wave fills the gaps), leaves the 75x75 stride-1 block where it is and costs the 38x38
-    // ones 0.7 us (too few waves to fill even two per SIMD); 4 spills and loses everywhere.  WZ_HP_OCC=2|3|4 forces one.
-    static const int occ_env = wz_hp_env("WZ_HP_OCC", 0);
-    const int occ = occ_env ? occ_env : (a.stem || a.stride == 2 || a.wout >= 75) ? 3 : 2;
-    if (a.stem) {
-        if (!(a.kc0 == 1 && nto == 2 && a.stride == 1)) return -1;
-        if (prepare) {
-            HP_DEV((void)wz_hp_launch<4, false, true, 4, 2, 1, 2, 4>(a, n, s, true); (void)wz_hp_launch<4, false, true, 4, 2, 1, 2>(a, n, s, true);)
-            return wz_hp_launch<4, false, true, 4, 2, 1, 2, 3>(a, n, s, true);
-        }
-        HP_DEV(if (occ == 4) return wz_hp_launch<4, false, true, 4, 2, 1, 2, 4>(a, n, s, false);
-               if (occ != 3) return wz_hp_launch<4, false, true, 4, 2, 1, 2>(a, n, s, false);)
-        return wz_hp_launch<4, false, true, 4, 2, 1, 2, 3>(a, n, s, false);
+    if (a.qenc) {
+        if (!prepare) return wz_hp_pick_q(a, n, s, false, wz_hp_small_batch("WZ_HP_SMALL_CS", n), wz_hp_small_batch("WZ_HP_TILES44", n));
+        int r = 0;
+        for (int v = 0; v < 4; ++v) r |= wz_hp_pick_q(a, n, s, true, v & 1, v >> 1);   // (each rule on and off: the knobs set them apart)
+        return r;
     }
-    if (a.cin0 == 0) return -1;
-    if (a.wout <= 10) {
-        // 10x10 maps (blocks 13 .. 16 of the ROBUST program; the default program runs them on wz_k_mbconv_cs): two GEMM-shaped launches per block,
-        // k_mbconv_hp2.hip -- the engine asks wz_mbconv_hp2_applies() and enqueues them itself (one stage-timer slot each); this entry only
-        // prepares their kernels at load time.  (Rounds 3 .. 5 ran them here: lean builds, 8 waves per 4 x 4 tile streaming all of the block's split
-        // weights, channel groups over workgroups for few frames -- 65 us for the four at batch 8 against 42, 41 against 33 at batch 1.)
-        return prepare ? wz_launch_mbconv_hp2(a, n, s, true, 0) : -1;
-    }
-    if (a.wout > 19 && a.kc0 == 1 && nto == 2) {
-        // Few frames (a single camera's frame at a time is the reference's normal load, detector.py:102-112): one wave per tile
-        // would leave most CUs empty and every wave walking 5 - 6 chunks, ~2 us each -- there the chunks go to the waves of a
-        // workgroup instead (measured at batch 1, profiles/r02t_*).  With the GPU filled by the batch it is the other way
-        // round (comment above wz_launch_mbconv_hp).
-        const int tiles_s1 = ((a.hout + 3) / 4) * ((a.wout + (a.stride == 1 ? 7 : 3)) / (a.stride == 1 ? 8 : 4));
-        const bool few = (tiles_s1 * n + 3) / 4 <= cs_few_wgs;
-        // Stride-1 blocks on the 38x38 maps: THREE waves per tile, two chunks each, halo shared through LDS.  One wave per tile walks
-        // six chunks in a row on a chip that 400 such waves leave almost empty (11.3 us per block); six waves with one chunk each
-        // are fastest alone but every workgroup then fills most of a CU (8.0 - 9.0 us, 45.9 k frames/s against 47.3 k); three waves
-        // take 6.7 - 7.0 us and two workgroups share a CU: 47.7 k frames/s, p50 0.378 -> 0.369 ms (profiles/r03_wave_counts_*).
-        static const int cs_s1_max_w = wz_hp_env("WZ_HP_CS_S1_MAX_W", 38);   // the same threshold for the stride-1 blocks alone
-        const bool cs = (prepare || a.wout <= cs_max_w || (a.stride == 1 && a.wout <= cs_s1_max_w) || few) && nk32 >= 4 && nk32 <= 6;
-        if (a.stride == 1) {        // 4 x 8 tiles, halo 6 x 10 = 60 pixels
-            static const int cs_nw = wz_hp_env("WZ_HP_CS_NW", 3);   // 2 / 3 / 4: that many waves per tile, several chunks each (shared halo); 0: one chunk per wave
-            if (prepare) {
-                // live with the defaults: 3 waves per tile (few frames on the 75x75 map), 5 / 6 waves at four per SIMD (38x38), one wave per tile at
-                // three per SIMD (75x75 and wider) or two (a 38x38 block whose chunk count the chunk-split builds do not take)
-                (void)wz_hp_launch<3, true, false, 4, 2, 1, 2, 2, false, true>(a, n, s, true);
-                (void)wz_hp_launch<5, true, false, 4, 2, 1, 2, 4, false, true>(a, n, s, true);
-                (void)wz_hp_launch<6, true, false, 4, 2, 1, 2, 4, false, true>(a, n, s, true);
-                (void)wz_hp_launch<4, false, false, 4, 2, 1, 2, 3>(a, n, s, true);
-                HP_DEV((void)wz_hp_launch<2, true, false, 4, 2, 1, 2, 2, false, true>(a, n, s, true);
-                       (void)wz_hp_launch<4, true, false, 4, 2, 1, 2, 2, false, true>(a, n, s, true);
-                       (void)wz_hp_launch<5, true, false, 4, 2, 1, 2>(a, n, s, true);
-                       (void)wz_hp_launch<6, true, false, 4, 2, 1, 2>(a, n, s, true);
-                       (void)wz_hp_launch<5, true, false, 4, 2, 1, 2, 2, false, true>(a, n, s, true);
-                       (void)wz_hp_launch<6, true, false, 4, 2, 1, 2, 2, false, true>(a, n, s, true);
-                       (void)wz_hp_launch<4, false, false, 4, 2, 1, 2, 4>(a, n, s, true);)
-                return wz_hp_launch<4, false, false, 4, 2, 1, 2>(a, n, s, true);
-            }
-            static const int cs75_nw = wz_hp_env("WZ_HP_CS75_NW", 0);   // the 75x75 stride-1 block: 2 / 3 waves per tile (0: one wave per tile)
-            static const int cs_occ4 = wz_hp_env("WZ_HP_CS_OCC4", 1);   // chunk-split stride-1 tiles: one chunk per wave at 128 registers (4 waves per SIMD)
-            HP_DEV(if (!prepare && sh && a.wout > 38 && a.wout <= 75 && nk32 >= 4 && nk32 <= 6) {
-                if (cs75_nw == 2) return wz_hp_launch<2, true, false, 4, 2, 1, 2, 2, false, true>(a, n, s, false);
-                if (cs75_nw == 3) return wz_hp_launch<3, true, false, 4, 2, 1, 2, 2, false, true>(a, n, s, false);
-                if (cs75_nw == 5 && nk32 <= 5) return wz_hp_launch<5, true, false, 4, 2, 1, 2, 4, false, true>(a, n, s, false);
-            })
-            (void)cs75_nw;
-            if (!prepare && cs && sh && cs_occ4 && a.wout <= 38)
-                return nk32 <= 5 ? wz_hp_launch<5, true, false, 4, 2, 1, 2, 4, false, true>(a, n, s, false)
-                                 : wz_hp_launch<6, true, false, 4, 2, 1, 2, 4, false, true>(a, n, s, false);
-            HP_DEV(if (cs && sh && cs_nw == 2) return wz_hp_launch<2, true, false, 4, 2, 1, 2, 2, false, true>(a, n, s, false);)
-            if (cs && sh && cs_nw == 3) return wz_hp_launch<3, true, false, 4, 2, 1, 2, 2, false, true>(a, n, s, false);
-            HP_DEV(if (cs && sh && cs_nw == 4) return wz_hp_launch<4, true, false, 4, 2, 1, 2, 2, false, true>(a, n, s, false);
-                   if (cs && sh && nk32 <= 5) return wz_hp_launch<5, true, false, 4, 2, 1, 2, 2, false, true>(a, n, s, false);
-                   if (cs && sh) return wz_hp_launch<6, true, false, 4, 2, 1, 2, 2, false, true>(a, n, s, false);
-                   if (cs && nk32 <= 5) return wz_hp_launch<5, true, false, 4, 2, 1, 2>(a, n, s, false);
-                   if (cs) return wz_hp_launch<6, true, false, 4, 2, 1, 2>(a, n, s, false);)
-            if (occ == 3) return wz_hp_launch<4, false, false, 4, 2, 1, 2, 3>(a, n, s, false);
-            HP_DEV(if (occ == 4) return wz_hp_launch<4, false, false, 4, 2, 1, 2, 4>(a, n, s, false);)
-            return wz_hp_launch<4, false, false, 4, 2, 1, 2>(a, n, s, false);
-        }
-        // stride 2: 4 x 4 tiles, halo 9 x 9 = 81 pixels
-        static const int cs2_nw = wz_hp_env("WZ_HP_CS2_NW", 0);   // stride-2 blocks on maps up to WZ_HP_CS2_MAX_W: that many waves per tile
-        static const int cs2_max_w = wz_hp_env("WZ_HP_CS2_MAX_W", 0);
-        if (prepare) {
-            (void)wz_hp_launch<5, true, false, 6, 1, 1, 2, 2, false, true>(a, n, s, true);     // (few frames)
-            HP_DEV((void)wz_hp_launch<2, true, false, 6, 1, 1, 2, 2, false, true>(a, n, s, true);
-                   (void)wz_hp_launch<3, true, false, 6, 1, 1, 2, 2, false, true>(a, n, s, true);
-                   (void)wz_hp_launch<5, true, false, 6, 1, 1, 2>(a, n, s, true);
-                   (void)wz_hp_launch<4, false, false, 6, 1, 1, 2, 4>(a, n, s, true);
-                   (void)wz_hp_launch<4, false, false, 6, 1, 1, 2>(a, n, s, true);)
-            return wz_hp_launch<4, false, false, 6, 1, 1, 2, 3>(a, n, s, true);
-        }
-        HP_DEV(if (sh && cs2_nw == 3 && a.wout <= cs2_max_w && nk32 >= 4 && nk32 <= 6)
-                   return wz_hp_launch<3, true, false, 6, 1, 1, 2, 2, false, true>(a, n, s, false);
-               if (sh && cs2_nw == 2 && a.wout <= cs2_max_w && nk32 >= 3 && nk32 <= 6)
-                   return wz_hp_launch<2, true, false, 6, 1, 1, 2, 2, false, true>(a, n, s, false);)
-        (void)cs2_nw; (void)cs2_max_w;
-        if (cs && sh && nk32 <= 5) return wz_hp_launch<5, true, false, 6, 1, 1, 2, 2, false, true>(a, n, s, false);
-        HP_DEV(if (cs && nk32 <= 5) return wz_hp_launch<5, true, false, 6, 1, 1, 2>(a, n, s, false);
-               if (occ == 4) return wz_hp_launch<4, false, false, 6, 1, 1, 2, 4>(a, n, s, false);
-               if (occ != 3) return wz_hp_launch<4, false, false, 6, 1, 1, 2>(a, n, s, false);)
-        return wz_hp_launch<4, false, false, 6, 1, 1, 2, 3>(a, n, s, false);
-    }
-    if (a.wout > 19) return -1;
-    if (a.stride == 2) {
-        if (a.kc0 == 1 && nto == 4) {
-            static const int cs6_nw = wz_hp_env("WZ_HP_CS6_NW", wz_latency_schedule() ? 8 : 3);   // waves per tile of the 38x38 -> 19x19 block (6 chunks): 3 with two chunks
-                                                                      // each (49.8 k -> 50.5 k frames/s; 8: two waves idle, a CU per workgroup)
-            static const int cs6_lean4 = wz_hp_env("WZ_HP_CS6_LEAN4", 1);   // six waves (one chunk each) at 128 registers
-            if (prepare) {
-                HP_DEV((void)wz_hp_launch<HP_CS_WAVES, true, false, 6, 1, 1, 4, 2, false, true>(a, n, s, true);
-                       (void)wz_hp_launch<3, true, false, 6, 1, 1, 4, 2, false, true>(a, n, s, true);
-                       (void)wz_hp_launch<6, true, false, 6, 1, 1, 4, 2, false, true>(a, n, s, true);
-                       (void)wz_hp_launch<HP_CS_WAVES, true, false, 6, 1, 1, 4>(a, n, s, true);)
-                return wz_hp_launch<6, true, false, 6, 1, 1, 4, 4, false, true, false, true>(a, n, s, true);
-            }
-            HP_DEV(if (!(sh && cs6_lean4)) {
-                if (sh && cs6_nw == 3) return wz_hp_launch<3, true, false, 6, 1, 1, 4, 2, false, true>(a, n, s, false);
-                if (sh && cs6_nw == 6) return wz_hp_launch<6, true, false, 6, 1, 1, 4, 2, false, true>(a, n, s, false);
-                if (sh) return wz_hp_launch<HP_CS_WAVES, true, false, 6, 1, 1, 4, 2, false, true>(a, n, s, false);
-                return wz_hp_launch<HP_CS_WAVES, true, false, 6, 1, 1, 4>(a, n, s, false);
-            })
-            (void)cs6_nw; (void)cs6_lean4;
-            return wz_hp_launch<6, true, false, 6, 1, 1, 4, 4, false, true, false, true>(a, n, s, false);
-        }
-        return -1;
-    }
-    // 12 chunks (cmid 384), WZ_HP_ONEPASS=1: 12 waves with one chunk each instead of 8 waves with up to two.  Measured
-    // (profiles/r02r_*, A/B in one run): 8.97 against 8.0 us per block -- four more waves repeat the halo load and the
-    // accumulators of twelve waves meet in LDS; the chunk walk is not what these launches wait for.  Off by default.
-    static const int onepass = wz_hp_env("WZ_HP_ONEPASS", 0);
-    HP_DEV(if (nk32 <= 12 && a.kc0 == 2 && (nto == 4 || nto == 6)) {
-        if (prepare) {
-            (void)wz_hp_launch<12, true, false, 3, 1, 2, 4, 3, true>(a, n, s, true);
-            (void)wz_hp_launch<12, true, false, 3, 1, 2, 6, 3, true>(a, n, s, true);
-        } else if (onepass == 1) {
-            return nto == 4 ? wz_hp_launch<12, true, false, 3, 1, 2, 4, 3, true>(a, n, s, false)
-                            : wz_hp_launch<12, true, false, 3, 1, 2, 6, 3, true>(a, n, s, false);
-        }
-    })
-    (void)onepass;
-    // 19x19 blocks: FOUR waves per tile (3 - 5 chunks each) instead of eight.  Alone a block gets slower (5.2 -> 6.5 us, 9.3 -> 11.5 us:
-    // the chunk walk is longer) -- but a workgroup of four 256-register waves takes half a CU's register file, so two of them (of
-    // this lane's launch or of another lane's) share a CU, where eight waves own it: 47.5 k -> 49.1 k frames/s with four lanes in
-    // flight.  3 waves: 48.2 k; 5: 45.8 k; 6: 46.8 k (workgroups that neither fill a CU nor leave room for a second one);
-    // WZ_HP_CS19_NW=8 is the lowest-latency setting (p50 0.372 against 0.380 ms).  profiles/r03_wave_counts_*.
-    static const int cs19_nw = wz_hp_env("WZ_HP_CS19_NW", wz_latency_schedule() ? 8 : 4);
-    // WZ_HP_CS19_LEAN4=1 (default, later in round 3): EIGHT waves per tile at 128 registers (4 per SIMD; halo fragments per pixel tile, no
-    // weight prefetch, accumulators through LDS in two rounds): as many waves as the lowest-latency setting, the CU footprint of the
-    // four-wave one -- 6.7 / 5.9 / 6.2 / 7.7 / 11.7 / 10.3 -> 5.7 / 5.0 / 5.2 / 6.3 / 10.1 / 9.0 us, 52.1 -> 52.5 k frames/s, p50 0.399 ->
-    // 0.386 ms (profiles/r03_four_waves_per_simd.txt).  0: the wave counts below.
-    static const int cs19_lean4 = wz_hp_env("WZ_HP_CS19_LEAN4", 1);
-#define HP_CASE(K, N)                                                                                         \
-    if (a.kc0 == K && nto == N) {                                                                             \
-        if (prepare) {                                                                                        \
-            HP_DEV((void)wz_hp_launch<3, true, false, 3, 1, K, N, 2, false, true>(a, n, s, true);            \
-                   (void)wz_hp_launch<4, true, false, 3, 1, K, N, 2, false, true>(a, n, s, true);            \
-                   (void)wz_hp_launch<5, true, false, 3, 1, K, N, 2, false, true>(a, n, s, true);            \
-                   (void)wz_hp_launch<6, true, false, 3, 1, K, N, 2, false, true>(a, n, s, true);            \
-                   (void)wz_hp_launch<HP_CS_WAVES, true, false, 3, 1, K, N, 2, false, true>(a, n, s, true);  \
-                   if (K == 2) (void)wz_hp_launch<12, true, false, 3, 1, 2, N, 3, false, true>(a, n, s, true); \
-                   (void)wz_hp_launch<HP_CS_WAVES, true, false, 3, 1, K, N>(a, n, s, true);)                 \
-            return wz_hp_launch<8, true, false, 3, 1, K, N, 4, false, true, false, true>(a, n, s, true);     \
-        }                                                                                                     \
-        HP_DEV(if (!(sh && cs19_lean4)) {                                                                     \
-            if (sh && cs19_nw == 3) { const int r = wz_hp_launch<3, true, false, 3, 1, K, N, 2, false, true>(a, n, s, false); if (r >= 0) return r; } \
-            if (sh && cs19_nw == 5) { const int r = wz_hp_launch<5, true, false, 3, 1, K, N, 2, false, true>(a, n, s, false); if (r >= 0) return r; } \
-            if (sh && cs19_nw == 4) { const int r = wz_hp_launch<4, true, false, 3, 1, K, N, 2, false, true>(a, n, s, false); if (r >= 0) return r; } \
-            if (sh && cs19_nw == 6) { const int r = wz_hp_launch<6, true, false, 3, 1, K, N, 2, false, true>(a, n, s, false); if (r >= 0) return r; } \
-            if (sh && w12 && K == 2) return wz_hp_launch<12, true, false, 3, 1, 2, N, 3, false, true>(a, n, s, false); \
-            if (sh) return wz_hp_launch<HP_CS_WAVES, true, false, 3, 1, K, N, 2, false, true>(a, n, s, false); \
-            return wz_hp_launch<HP_CS_WAVES, true, false, 3, 1, K, N>(a, n, s, false);                        \
-        })                                                                                                    \
-        return wz_hp_launch<8, true, false, 3, 1, K, N, 4, false, true, false, true>(a, n, s, false);        \
-    }
-    HP_CASE(2, 4);
-    HP_CASE(2, 6);
-    HP_CASE(3, 6);
-#undef HP_CASE
-    (void)cs19_nw; (void)cs19_lean4; (void)w12; (void)sh;
-    return -1;
+    if (!a.stem && a.cin0 != 0 && a.wout <= 10) return prepare ? wz_launch_mbconv_hp2(a, n, s, true, 0) : -1;
+    // workgroups of the one-wave-per-tile launch (4 waves each): falls with the batch size, so `few` takes the values of the two ends
+    const int tiles_s1 = ((a.hout + 3) / 4) * ((a.wout + (a.stride == 1 ? 7 : 3)) / (a.stride == 1 ? 8 : 4));
+    auto few = [&](int nb) { return (tiles_s1 * nb + 3) / 4 <= HP_CS_FEW_WGS; };
+    if (!prepare) return wz_hp_pick(a, n, s, false, few(n));
+    return wz_hp_pick(a, n, s, true, few(1)) | wz_hp_pick(a, n, s, true, few(4095));
 }
-#undef HP_DEV

@@ -29,14 +29,18 @@
 
 #define HP2_ES 40   // unorm16 per pixel of the chunk buffer: 32 channels + 8 of padding (as in k_mbconv_hp.hip)
 
-// S: stride; KCI: 32-channel K chunks of the expand conv; NW: waves per workgroup; OHR: output rows per band;
+constexpr int HP2_NW = 4;   // waves per workgroup of launch A (3, 5 and 6 lost: profiles/r06_hp2_by_batch_size.txt)
+constexpr int HP2_PW = 8;   // waves per workgroup of launch B: K is dealt out over them
+
+// S: stride; KCI: 32-channel K chunks of the expand conv; OHR: output rows per band;
 // MPW / MQW: 16-pixel tiles that cover a band's in-frame input pixels / its output pixels; TAP: the expanded tensor is a second output.
 // PAIR: TWO waves per chunk (NW / 2 chunks per workgroup) -- wave 2c + h expands the 16-channel tile h of chunk c for all of the band's pixels into the
 // chunk's shared buffer and, behind a second barrier, runs the depthwise stage for every other output tile: twice the workgroups, half the serial
 // chain per wave.  For the launches that leave the chip half empty (128 workgroups of 4 waves at batch 8: a wave per SIMD on half of the CUs).
-template <int S, int KCI, int NW, int OHR, int MPW, int MQW, bool TAP, bool PAIR = false>
-__global__ __launch_bounds__(NW * 64, 2) void wz_k_hp2_expdw(const WzMbArgs a) {
+template <int S, int KCI, int OHR, int MPW, int MQW, bool TAP, bool PAIR>
+__global__ __launch_bounds__(HP2_NW * 64, 2) void wz_k_hp2_expdw(const WzMbArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char wz_hp2_smem[];
+    constexpr int NW = HP2_NW;
     WZ_LANE_STAMP(a.dbg);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int r16 = lane & 15, g = lane >> 4;
@@ -219,12 +223,14 @@ __global__ __launch_bounds__(NW * 64, 2) void wz_k_hp2_expdw(const WzMbArgs a) {
     }
 }
 
-// out[pixel][n] = sum_k Wp[n][k] D[pixel][k] (+ bias, + residual): MT x NT tiles per workgroup, K over the NW waves (CPW chunks each at most).
+// out[pixel][n] = sum_k Wp[n][k] D[pixel][k] (+ bias, + residual): MT x NT = 1 x 2 tiles per workgroup (122 registers: two workgroups per CU;
+// 2 x 2 lost, profiles/r06_hp2_by_batch_size.txt), K over the NW waves (CPW chunks each at most).
 // Workgroups are dealt round-robin over the 8 XCDs (id % 8): the m-groups are dealt the same way, so that an XCD's L2 holds a
 // disjoint eighth of D and every m-group's NT-groups meet in one L2.
-template <int MT, int NT, int NW, int CPW>
-__global__ __launch_bounds__(NW * 64, 1) void wz_k_hp2_proj(const WzMbArgs a) {
+template <int CPW>
+__global__ __launch_bounds__(HP2_PW * 64, 1) void wz_k_hp2_proj(const WzMbArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char wz_hp2_smem[];
+    constexpr int MT = 1, NT = 2, NW = HP2_PW;
     WZ_LANE_STAMP(a.dbg);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int r16 = lane & 15, g = lane >> 4;
@@ -327,15 +333,10 @@ __global__ __launch_bounds__(NW * 64, 1) void wz_k_hp2_proj(const WzMbArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-static int wz_hp2_env(const char* name, int dflt) {
-    const char* e = wz_dev_getenv(name);
-    return (e && e[0] && atoi(e) >= 0) ? atoi(e) : dflt;
-}
-
-template <int S, int KCI, int NW, int OHR, int MPW, int MQW, bool TAP, bool PAIR = false>
+template <int S, int KCI, int OHR, int MPW, int MQW, bool TAP, bool PAIR>
 static int wz_hp2_launch_a(const WzMbArgs& a, int n, hipStream_t s, bool prepare) {
-    auto k = wz_k_hp2_expdw<S, KCI, NW, OHR, MPW, MQW, TAP, PAIR>;
-    constexpr int CPWG = PAIR ? NW / 2 : NW;
+    auto k = wz_k_hp2_expdw<S, KCI, OHR, MPW, MQW, TAP, PAIR>;
+    constexpr int NW = HP2_NW, CPWG = PAIR ? NW / 2 : NW;
     const int EW = (a.wout - 1) * S + 3, EH = (OHR - 1) * S + 3;
     const size_t ebytes = ((size_t)EH * EW * HP2_ES * 2 + 15) & ~(size_t)15;
     const size_t lds = (size_t)MPW * KCI * 2 * 1024 + (size_t)CPWG * ebytes;
@@ -361,9 +362,10 @@ static int wz_hp2_launch_a(const WzMbArgs& a, int n, hipStream_t s, bool prepare
     return 1;
 }
 
-template <int MT, int NT, int NW, int CPW>
+template <int CPW>
 static int wz_hp2_launch_b(const WzMbArgs& a, int n, hipStream_t s, bool prepare) {
-    auto k = wz_k_hp2_proj<MT, NT, NW, CPW>;
+    auto k = wz_k_hp2_proj<CPW>;
+    constexpr int MT = 1, NT = 2, NW = HP2_PW;
     const int nk32 = a.cmid_pad >> 5;
     if ((a.n_pad >> 4) % NT || (nk32 + NW - 1) / NW > CPW) return -1;
     const size_t lds = (size_t)NW * MT * NT * 1024;
@@ -397,61 +399,36 @@ int wz_mbconv_hp2_applies(const WzMbArgs& a, int n) {
     return 0;
 }
 
-// phase 0: both launches; 1: launch A only; 2: launch B only (the engine's stage timer brackets them separately).  prepare: kernel attributes.
+// Launch A with two waves per chunk (PAIR: twice the workgroups, half the serial chain per wave -- 7.0 -> 5.2 us at batch 8, 6.1 -> 3.8 us at batch 1)
+// when the batch runs ALONE on the chip (WzMbArgs::lone: every other lane idle, run_batch) and one wave per chunk leaves at least half of the CUs
+// empty (<= 128 workgroups of four waves: batch <= 8 on the 10x10 maps, <= 5 for block 13's bands), or when it leaves three quarters of them empty
+// whatever the other lanes do (<= 64).  With four lanes in flight at batch 8 the pairs cost 1 % of the throughput (49.6 against 50.2 k frames/s:
+// twice the workgroups hold the CUs), hence the condition.  Both shapes compute bit-identical tensors (a chunk's two 16-channel tiles are
+// independent MFMA chains either way), so a batch's rows do not depend on which one ran (tests/test_gpu_variants.py).
+constexpr int HP2_PAIR_WGS = 128, HP2_PAIR_ALWAYS_WGS = 64;
+
+// Launch A of a block; bands: bands of output rows per frame
+template <int S, int KCI, int OHR, int MPW, int MQW, bool TAP>
+static int wz_hp2_a(const WzMbArgs& a, int n, hipStream_t s, bool prepare, int bands) {
+    if (prepare) return wz_hp2_launch_a<S, KCI, OHR, MPW, MQW, TAP, false>(a, n, s, true) | wz_hp2_launch_a<S, KCI, OHR, MPW, MQW, TAP, true>(a, n, s, true);
+    const int wgs = n * bands * (((a.cmid_pad >> 5) + HP2_NW - 1) / HP2_NW);   // of the one-wave-per-chunk launch
+    return wgs <= (a.lone ? HP2_PAIR_WGS : HP2_PAIR_ALWAYS_WGS) ? wz_hp2_launch_a<S, KCI, OHR, MPW, MQW, TAP, true>(a, n, s, false)
+                                                                : wz_hp2_launch_a<S, KCI, OHR, MPW, MQW, TAP, false>(a, n, s, false);
+}
+
+// phase 0: both launches; 1: launch A only; 2: launch B only (the engine's stage timer brackets them separately).  prepare: the attributes and the
+// verdict (0 / -1) of every kernel some batch size can pick.
 int wz_launch_mbconv_hp2(const WzMbArgs& a, int n, hipStream_t s, bool prepare, int phase) {
-    static const int nw1 = wz_hp2_env("WZ_HP2_NW1", 4), nw2 = wz_hp2_env("WZ_HP2_NW2", 4);
-    static const int mt = wz_hp2_env("WZ_HP2_MT", 1);
-    // Two waves per chunk (PAIR: twice the workgroups, half the serial chain per wave -- launch A 7.0 -> 5.2 us at batch 8, 6.1 -> 3.8 us at batch 1) when the
-    // batch runs ALONE on the chip (WzMbArgs::lone: every other lane idle, run_batch) and the one-wave-per-chunk launch leaves at least half of the CUs empty
-    // (<= 128 workgroups of four waves: batch <= 8 on the 10x10 maps, <= 5 for block 13's bands), or when it leaves three quarters of them empty whatever the
-    // other lanes do (<= 64).  With four lanes in flight at batch 8 the pairs cost 1 % of the throughput (49.6 against 50.2 k frames/s: twice the workgroups
-    // hold the CUs), hence the condition.  Both shapes compute bit-identical tensors (a chunk's two 16-channel tiles are independent MFMA chains either way),
-    // so a batch's rows do not depend on which one ran (tests/test_gpu_variants.py: graph against kernel-by-kernel launches).
-    static const int pair_wgs = wz_hp2_env("WZ_HP2_PAIR_WGS", 128), pair_always_wgs = wz_hp2_env("WZ_HP2_PAIR_ALWAYS_WGS", 64);
-    const int nk32_ = a.cmid_pad >> 5;   // pixel tiles per workgroup of launch B: 1 (122 registers: two workgroups per CU) or 2
-    int ra = 1, rb = 1;
     if (prepare || phase != 2) {
-        if (a.stride == 1 && a.kc0 == 5) {
-            if (prepare) {
-                (void)wz_hp2_launch_a<1, 5, 3, 5, 4, 4, false>(a, n, s, true);
-                (void)wz_hp2_launch_a<1, 5, 4, 5, 4, 4, false>(a, n, s, true);
-                (void)wz_hp2_launch_a<1, 5, 4, 5, 4, 4, false, true>(a, n, s, true);
-                (void)wz_hp2_launch_a<1, 5, 6, 5, 4, 4, false>(a, n, s, true);
-                ra = wz_hp2_launch_a<1, 5, 5, 5, 4, 4, false>(a, n, s, true);
-            } else
-                if (nw1 == 4 && n * 2 * ((nk32_ + 3) / 4) <= (a.lone ? pair_wgs : pair_always_wgs)) ra = wz_hp2_launch_a<1, 5, 4, 5, 4, 4, false, true>(a, n, s, false);
-                else
-                ra = nw1 == 3 ? wz_hp2_launch_a<1, 5, 3, 5, 4, 4, false>(a, n, s, false)
-                   : nw1 == 5 ? wz_hp2_launch_a<1, 5, 5, 5, 4, 4, false>(a, n, s, false)
-                   : nw1 == 6 ? wz_hp2_launch_a<1, 5, 6, 5, 4, 4, false>(a, n, s, false)
-                              : wz_hp2_launch_a<1, 5, 4, 5, 4, 4, false>(a, n, s, false);
-        } else if (a.stride == 2 && a.kc0 == 3) {
-            if (prepare) {
-                (void)wz_hp2_launch_a<2, 3, 3, 2, 6, 2, true>(a, n, s, true);
-                (void)wz_hp2_launch_a<2, 3, 4, 2, 6, 2, true>(a, n, s, true);
-                (void)wz_hp2_launch_a<2, 3, 4, 2, 6, 2, true, true>(a, n, s, true);
-                ra = wz_hp2_launch_a<2, 3, 6, 2, 6, 2, true>(a, n, s, true);
-            } else
-                if (nw2 == 4 && n * 5 * ((nk32_ + 3) / 4) <= (a.lone ? pair_wgs : pair_always_wgs)) ra = wz_hp2_launch_a<2, 3, 4, 2, 6, 2, true, true>(a, n, s, false);
-                else
-                ra = nw2 == 3 ? wz_hp2_launch_a<2, 3, 3, 2, 6, 2, true>(a, n, s, false)
-                   : nw2 == 6 ? wz_hp2_launch_a<2, 3, 6, 2, 6, 2, true>(a, n, s, false)
-                              : wz_hp2_launch_a<2, 3, 4, 2, 6, 2, true>(a, n, s, false);
-        } else
-            return -1;
+        int ra;
+        if (a.stride == 1 && a.kc0 == 5) ra = wz_hp2_a<1, 5, 5, 4, 4, false>(a, n, s, prepare, 2);       // blocks 14 .. 16: two bands of 5 rows
+        else if (a.stride == 2 && a.kc0 == 3) ra = wz_hp2_a<2, 3, 2, 6, 2, true>(a, n, s, prepare, 5);   // block 13: five bands of 2 rows, + the feature map
+        else return -1;
         if (ra < 0) return -1;
     }
     if (prepare || phase != 1) {
-        const bool c3 = ((a.cmid_pad >> 5) + 7) / 8 <= 3;   // chunks per wave: 3 (block 13: 18 chunks) or 4 (30)
-        if (prepare) {
-            (void)wz_hp2_launch_b<1, 2, 8, 4>(a, n, s, true);
-            (void)wz_hp2_launch_b<1, 2, 8, 3>(a, n, s, true);
-            (void)wz_hp2_launch_b<2, 2, 8, 3>(a, n, s, true);
-            rb = wz_hp2_launch_b<2, 2, 8, 4>(a, n, s, true);
-        } else if (c3)
-            rb = mt == 1 ? wz_hp2_launch_b<1, 2, 8, 3>(a, n, s, false) : wz_hp2_launch_b<2, 2, 8, 3>(a, n, s, false);
-        else
-            rb = mt == 1 ? wz_hp2_launch_b<1, 2, 8, 4>(a, n, s, false) : wz_hp2_launch_b<2, 2, 8, 4>(a, n, s, false);
+        // chunks per wave: 3 (block 13: 18 chunks) or 4 (30)
+        const int rb = ((a.cmid_pad >> 5) + HP2_PW - 1) / HP2_PW <= 3 ? wz_hp2_launch_b<3>(a, n, s, prepare) : wz_hp2_launch_b<4>(a, n, s, prepare);
         if (rb < 0) return -1;
     }
     return prepare ? 0 : 1;

@@ -18,16 +18,15 @@
 #include "wz_common.h"
 
 // MPW: halo m-tiles (16 pixels) per wave, MQW: output m-tiles per wave, KCI: K chunks of the expand conv,
-// NTO: 16-column tiles of the project output, NKK: 32-channel chunks per pass (their two dependency chains --
-// expand -> LDS -> depthwise -> project -- are independent, so a pass of 2 costs about the latency of 1).
+// NTO: 16-column tiles of the project output.  A pass walks ONE 32-channel chunk (two per pass cost occupancy and gained nothing).
 // STEM: the block is the network's first one and its "expand" stage is the stem convolution (3x3 s2, 3 -> 32,
 // K = 27 padded to 32): the B fragment of a halo pixel is the im2col of its 3x3x3 window, gathered straight from
 // the normalised 300x300x4 input -- the 150x150x32 stem output never exists in HBM.
-template <int MPW, int MQW, int KCI, int NTO, int NKK, bool STEM>
+template <int MPW, int MQW, int KCI, int NTO, bool STEM>
 __global__ __launch_bounds__(256, 4) void wz_k_mbconv_wave(const WzMbArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char wz_mbw_smem[];
     WZ_LANE_STAMP(a.dbg);
-    constexpr int CE = 32 * NKK, ES = CE + 8;   // NKK 32-channel K chunks of the project conv per pass
+    constexpr int CE = 32, ES = CE + 8;   // one 32-channel K chunk of the project conv per pass
     constexpr int EBYTES = MPW * 16 * ES * 2;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r16 = lane & 15, g = lane >> 4;
@@ -127,46 +126,40 @@ __global__ __launch_bounds__(256, 4) void wz_k_mbconv_wave(const WzMbArgs a) {
 #pragma unroll
         for (int nt = 0; nt < NTO; ++nt) acc[j][nt] = (float4_t){0.f, 0.f, 0.f, 0.f};
 
-    // GEMM weight fragments of a pass: 2 NKK expand channel tiles x KCI and NKK x NTO project tiles, straight from L2
-    const int nk32 = a.cmid_pad >> 5;                       // 32-channel chunks in all
-    const int npass = (nk32 + NKK - 1) / NKK;
+    // GEMM weight fragments of a pass: 2 expand channel tiles x KCI and NTO project tiles, straight from L2
+    const int npass = a.cmid_pad >> 5;                      // 32-channel chunks in all, one per pass
     const int ntiles_e = a.nmid_pad >> 4;
-    half8_t wa[2 * NKK][KCI], wp[NKK][NTO];
+    half8_t wa[2][KCI], wp[NTO];
     auto load_weights = [&](int ps) {
 #pragma unroll
-        for (int nt = 0; nt < 2 * NKK; ++nt) {
-            const int tn = min(ps * 2 * NKK + nt, ntiles_e - 1);   // beyond the packed tiles: clamped, never used (see `have`)
+        for (int nt = 0; nt < 2; ++nt) {
+            const int tn = min(ps * 2 + nt, ntiles_e - 1);   // beyond the packed tiles: clamped, never used (see `have`)
             const half_t* wsrc = a.we + ((size_t)tn * a.kc0 * 64 + lane) * 8;
 #pragma unroll
             for (int c = 0; c < KCI; ++c) wa[nt][c] = *reinterpret_cast<const half8_t*>(wsrc + (size_t)c * 512);
         }
+        const int kg = min(ps, npass - 1);   // (never binds, nor does the clamp of the bias index below; without them the 4 x 8 builds allocate other registers)
 #pragma unroll
-        for (int kk = 0; kk < NKK; ++kk) {
-            const int kg = min(ps * NKK + kk, nk32 - 1);
-#pragma unroll
-            for (int nt = 0; nt < NTO; ++nt)
-                wp[kk][nt] = *reinterpret_cast<const half8_t*>(a.wp + ((size_t)(nt * a.kc + kg) * 64 + lane) * 8);
-        }
+        for (int nt = 0; nt < NTO; ++nt)
+            wp[nt] = *reinterpret_cast<const half8_t*>(a.wp + ((size_t)(nt * a.kc + kg) * 64 + lane) * 8);
     };
     load_weights(0);
     __syncthreads();   // staged depthwise weights / biases visible; the only workgroup barrier
     if (!live) return;
 
     for (int ps = 0; ps < npass; ++ps) {
-        half8_t wa_c[2 * NKK][KCI], wp_c[NKK][NTO];
+        half8_t wa_c[2][KCI], wp_c[NTO];
 #pragma unroll
-        for (int nt = 0; nt < 2 * NKK; ++nt)
+        for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
             for (int c = 0; c < KCI; ++c) wa_c[nt][c] = wa[nt][c];
 #pragma unroll
-        for (int kk = 0; kk < NKK; ++kk)
-#pragma unroll
-            for (int nt = 0; nt < NTO; ++nt) wp_c[kk][nt] = wp[kk][nt];
+        for (int nt = 0; nt < NTO; ++nt) wp_c[nt] = wp[nt];
         if (ps + 1 < npass) load_weights(ps + 1);   // in flight under this pass
         const int ce0 = ps * CE;
         // ---- expand: E[p][ce] = in-frame ? relu6(sum_k X[p][k] We[k][ce] + be[ce]) : 0
 #pragma unroll
-        for (int nt = 0; nt < 2 * NKK; ++nt) {
+        for (int nt = 0; nt < 2; ++nt) {
             const bool have = ce0 + nt * 16 < a.nmid_pad;    // this 16-channel tile exists (wave-uniform)
             const float4_t bv = *reinterpret_cast<const float4_t*>(be_l + min(ce0 + nt * 16, a.cmid_pad - 16) + g * 4);
 #pragma unroll
@@ -184,37 +177,31 @@ __global__ __launch_bounds__(256, 4) void wz_k_mbconv_wave(const WzMbArgs a) {
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         // ---- depthwise (lane = output pixel x 8 channels) feeding the project MFMAs
+        const int coff = ce0 + g * 8;
+        half8_t wt[9];
 #pragma unroll
-        for (int kk = 0; kk < NKK; ++kk) {
-            if (ps * NKK + kk < nk32) {   // wave-uniform (the last pass may hold fewer chunks)
-                const int coff = ce0 + kk * 32 + g * 8;
-                half8_t wt[9];
+        for (int tp = 0; tp < 9; ++tp) wt[tp] = *reinterpret_cast<const half8_t*>(wd_l + tp * a.cmid_pad + coff);
+        const float4_t b0 = *reinterpret_cast<const float4_t*>(bd_l + coff);
+        const float4_t b1 = *reinterpret_cast<const float4_t*>(bd_l + coff + 4);
 #pragma unroll
-                for (int tp = 0; tp < 9; ++tp) wt[tp] = *reinterpret_cast<const half8_t*>(wd_l + tp * a.cmid_pad + coff);
-                const float4_t b0 = *reinterpret_cast<const float4_t*>(bd_l + coff);
-                const float4_t b1 = *reinterpret_cast<const float4_t*>(bd_l + coff + 4);
+        for (int j = 0; j < MQW; ++j) {
+            float d[8];
 #pragma unroll
-                for (int j = 0; j < MQW; ++j) {
-                    float d[8];
+            for (int r = 0; r < 4; ++r) { d[r] = b0[r]; d[4 + r] = b1[r]; }
+            const half_t* ep = E + hp0[j] * ES + g * 8;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) { d[r] = b0[r]; d[4 + r] = b1[r]; }
-                    const half_t* ep = E + hp0[j] * ES + kk * 32 + g * 8;
+            for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-                    for (int ky = 0; ky < 3; ++ky)
+                for (int kx = 0; kx < 3; ++kx) {
+                    const half8_t x = *reinterpret_cast<const half8_t*>(ep + (ky * hw_ + kx) * ES);
 #pragma unroll
-                        for (int kx = 0; kx < 3; ++kx) {
-                            const half8_t x = *reinterpret_cast<const half8_t*>(ep + (ky * hw_ + kx) * ES);
-#pragma unroll
-                            for (int r = 0; r < 8; ++r) d[r] = fmaf((float)x[r], (float)wt[ky * 3 + kx][r], d[r]);
-                        }
-                    half8_t bf;
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) bf[r] = (half_t)fminf(fmaxf(d[r], 0.0f), 6.0f);
-#pragma unroll
-                    for (int nt = 0; nt < NTO; ++nt)
-                        acc[j][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wp_c[kk][nt], bf, acc[j][nt], 0, 0, 0);
+                    for (int r = 0; r < 8; ++r) d[r] = fmaf((float)x[r], (float)wt[ky * 3 + kx][r], d[r]);
                 }
-            }
+            half8_t bf;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) bf[r] = (half_t)fminf(fmaxf(d[r], 0.0f), 6.0f);
+#pragma unroll
+            for (int nt = 0; nt < NTO; ++nt) acc[j][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wp_c[nt], bf, acc[j][nt], 0, 0, 0);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();   // (the next pass's E stores stay behind these reads)
@@ -246,16 +233,11 @@ __global__ __launch_bounds__(256, 4) void wz_k_mbconv_wave(const WzMbArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-static int wz_mbw_env(const char* name, int dflt) {
-    const char* e = wz_dev_getenv(name);
-    return (e && atoi(e) > 0) ? atoi(e) : dflt;
-}
-
-template <int MPW, int MQW, int KCI, int NTO, int NKK, bool STEM = false>
+template <int MPW, int MQW, int KCI, int NTO, bool STEM = false>
 static int wz_mbw_launch(WzMbArgs a, int n, hipStream_t s, bool prepare) {
     a.nb = n;
-    const size_t lds = (size_t)4 * MPW * 16 * (32 * NKK + 8) * 2 + (size_t)a.cmid_pad * (9 * 2 + 2 * 4);
-    auto k = wz_k_mbconv_wave<MPW, MQW, KCI, NTO, NKK, STEM>;
+    const size_t lds = (size_t)4 * MPW * 16 * (32 + 8) * 2 + (size_t)a.cmid_pad * (9 * 2 + 2 * 4);
+    auto k = wz_k_mbconv_wave<MPW, MQW, KCI, NTO, STEM>;
     if (prepare) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         return lds <= 160 * 1024 ? 0 : -1;
@@ -265,40 +247,28 @@ static int wz_mbw_launch(WzMbArgs a, int n, hipStream_t s, bool prepare) {
     return 1;
 }
 
+constexpr int MBW_MIN_W = 38;   // narrower maps have too few pixel tiles to fill the GPU: wz_launch_mbconv_cs / wz_launch_mbconv
+
 // Serves a block iff it has an expand stage with one K chunk (cin0 <= 32), few project tiles and a map large
 // enough that pixel tiles alone fill the GPU.  Returns -2 when it does not apply (the caller falls back to
 // wz_launch_mbconv), -1 on an unsupported shape, else 1.
 int wz_launch_mbconv_wave(const WzMbArgs& a0, int n, hipStream_t s, bool prepare) {
-    static const int enabled = wz_mbw_env("WZ_MB_WAVE", 1);
-    static const int min_w = wz_mbw_env("WZ_MB_WAVE_MIN_W", 38);
+    static const int enabled = wz_dev_env_int("WZ_MB_WAVE", 1);   // anything but 1: the workgroup-per-tile kernel instead (tests/test_gpu_parity.py)
     const int nto = a0.n_pad / 16;
     if (a0.stem) {   // stem + first block: only this kernel implements it
         if (a0.kc0 != 1 || a0.stride != 1 || nto != 2) return -1;
-        WzMbArgs a = a0;
-        a.nsplit = 1;
-        static const int big = wz_mbw_env("WZ_MB_WAVE_STEM_TILE", 1);   // 1: 4x8 outputs per wave, 2: 8x8, 3: 4x4
-        a.th = big == 2 ? 8 : 4; a.tw = big == 3 ? 4 : 8;
-        a.tiles_y = (a.hout + a.th - 1) / a.th;
-        a.tiles_x = (a.wout + a.tw - 1) / a.tw;
-        if (big == 2) return wz_mbw_launch<7, 4, 1, 2, 1, true>(a, n, s, prepare);   // halo 10 x 10 = 100 pixels
-        if (big == 3) return wz_mbw_launch<3, 1, 1, 2, 1, true>(a, n, s, prepare);   // 4x4 outputs, halo 6 x 6 = 36
-        return wz_mbw_launch<4, 2, 1, 2, 1, true>(a, n, s, prepare);
+    } else if (enabled != 1 || a0.cin0 == 0 || a0.kc0 != 1 || a0.wout < MBW_MIN_W || (nto != 2 && nto != 4)) {
+        return -2;
     }
-    if (enabled != 1 || a0.cin0 == 0 || a0.kc0 != 1 || a0.wout < min_w) return -2;
-    if (nto != 2 && nto != 4) return -2;
     WzMbArgs a = a0;
     a.nsplit = 1;
-    if (a.stride == 1) { a.th = 4; a.tw = 8; } else { a.th = 4; a.tw = 4; }
+    a.th = 4;
+    a.tw = a.stride == 1 ? 8 : 4;
     a.tiles_y = (a.hout + a.th - 1) / a.th;
     a.tiles_x = (a.wout + a.tw - 1) / a.tw;
-    static const int nkk = wz_mbw_env("WZ_MB_WAVE_NKK", 1);   // measured: 2 chunks per pass cost occupancy and gain nothing
-    if (nkk == 2) {
-        if (a.stride == 1)   // halo 6 x 10 = 60 pixels -> 4 m-tiles, 32 outputs -> 2 m-tiles
-            return nto == 2 ? wz_mbw_launch<4, 2, 1, 2, 2>(a, n, s, prepare) : wz_mbw_launch<4, 2, 1, 4, 2>(a, n, s, prepare);
-        // stride 2: halo 9 x 9 = 81 pixels -> 6 m-tiles, 16 outputs -> 1 m-tile
-        return nto == 2 ? wz_mbw_launch<6, 1, 1, 2, 2>(a, n, s, prepare) : wz_mbw_launch<6, 1, 1, 4, 2>(a, n, s, prepare);
-    }
-    if (a.stride == 1)
-        return nto == 2 ? wz_mbw_launch<4, 2, 1, 2, 1>(a, n, s, prepare) : wz_mbw_launch<4, 2, 1, 4, 1>(a, n, s, prepare);
-    return nto == 2 ? wz_mbw_launch<6, 1, 1, 2, 1>(a, n, s, prepare) : wz_mbw_launch<6, 1, 1, 4, 1>(a, n, s, prepare);
+    if (a.stem) return wz_mbw_launch<4, 2, 1, 2, true>(a, n, s, prepare);
+    if (a.stride == 1)   // 4 x 8 outputs per wave: halo 6 x 10 = 60 pixels -> 4 m-tiles, 32 outputs -> 2 m-tiles
+        return nto == 2 ? wz_mbw_launch<4, 2, 1, 2>(a, n, s, prepare) : wz_mbw_launch<4, 2, 1, 4>(a, n, s, prepare);
+    // stride 2, 4 x 4 outputs: halo 9 x 9 = 81 pixels -> 6 m-tiles, 16 outputs -> 1 m-tile
+    return nto == 2 ? wz_mbw_launch<6, 1, 1, 2>(a, n, s, prepare) : wz_mbw_launch<6, 1, 1, 4>(a, n, s, prepare);
 }

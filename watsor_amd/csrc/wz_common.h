@@ -153,6 +153,11 @@ static inline const char* wz_dev_getenv(const char* name) {
     return nullptr;
 #endif
 }
+// a knob as a non-negative integer ("0" is a value); unset, empty or negative: the default
+static inline int wz_dev_env_int(const char* name, int dflt) {
+    const char* e = wz_dev_getenv(name);
+    return (e && e[0] && atoi(e) >= 0) ? atoi(e) : dflt;
+}
 
 // The SCHEDULE of a process (wz_set_schedule() before its first engine, else WZ_SCHEDULE in the environment, else throughput; fixed the
 // first time anything asks): "latency" = the launch shapes that make ONE batch finish soonest on an otherwise idle GPU -- eight waves
