@@ -112,12 +112,26 @@ int wz_submit_host(wz_engine_t* e, int slot, int n, const uint8_t* const* rgb, c
 /* ---- other pixel formats (the decoder side).  The reference's decoders write rawvideo RGB24 because its schema
  * says so (`watsor/config/schema.py:161`, `watsor/stream/ffmpeg.py:78-88` reads whatever the decoder writes into the
  * FrameBuffer); a decoder told `-pix_fmt nv12` / `yuv420p` writes half the bytes, and the colour conversion ffmpeg would have
- * done on the host happens in the resize kernel (8-bit BT.601 limited range, nearest chroma; csrc/k_preprocess.hip).
- *   fmt[i]  WZ_FMT_* of frame i; fmt == NULL: all RGB24.  NV12 / I420 frames are w*h*3/2 bytes and need even w and h.
+ * done on the host happens in the resize kernel (8-bit, nearest chroma, 8.8 fixed point; csrc/k_preprocess.hip).  A USB / V4L2
+ * camera or capture card writes packed 4:2:2 (`yuyv422` / `uyvy422`), an IR / thermal camera `gray`, an OpenCV producer `bgr24`.
+ *   fmt[i]  the format word of frame i: a base format WZ_FMT_* in bits 0-7, or'ed with colour flags; fmt == NULL: all RGB24.
+ *           NV12 / I420 frames are w*h*3/2 bytes and need even w and h; YUYV422 / UYVY422 are 2*w*h bytes and need even w;
+ *           GRAY8 is w*h bytes, BGR24 3*w*h.
+ *   flags   how the four YUV formats (NV12, I420, YUYV422, UYVY422) turn into RGB.  No flag: BT.601 limited range (what the
+ *           words 1 and 2 have always meant).  WZ_CSP_BT709: the BT.709 matrix (what swscale applies to a 720p / 1080p stream tagged
+ *           bt709).  WZ_RANGE_FULL: Y, U, V use 0..255 (ffmpeg's yuvj* formats: MJPEG cameras).  A flag on RGB24, BGR24 or GRAY8,
+ *           any other bit, and a base format above WZ_FMT_BGR24 are refused (WZ_EINVAL).
  * The three calls are the ones above with that one argument more. */
 #define WZ_FMT_RGB24 0
 #define WZ_FMT_NV12 1   /* h x w luma, then h/2 x w/2 interleaved (U, V) */
 #define WZ_FMT_I420 2   /* h x w luma, then the h/2 x w/2 U plane, then the V plane (ffmpeg's yuv420p) */
+#define WZ_FMT_YUYV422 3   /* packed Y0 U Y1 V, 2 bytes per pixel, even w (ffmpeg's yuyv422) */
+#define WZ_FMT_UYVY422 4   /* packed U Y0 V Y1 (ffmpeg's uyvy422) */
+#define WZ_FMT_GRAY8 5     /* one byte per pixel, R = G = B = Y, no scaling (ffmpeg's `gray` is full range) */
+#define WZ_FMT_BGR24 6     /* RGB24 with the first and third byte swapped */
+#define WZ_FMT_BASE_MASK 0xff
+#define WZ_CSP_BT709 0x100    /* matrix; absent: BT.601 */
+#define WZ_RANGE_FULL 0x200   /* Y, U, V use 0..255 (the yuvj* formats); absent: limited range */
 int wz_detect_batch_fmt(wz_engine_t* e, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt,
                         const int* cam, wz_detection_t* const* out, uint8_t* const* pass, float* ms);
 int wz_submit_device_fmt(wz_engine_t* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h,

@@ -1,4 +1,4 @@
-// Resize + normalise: a frame of any resolution (packed RGB24, or NV12 / I420) -> 300x300 fp16 network input.
+// Resize + normalise: a frame of any resolution (packed RGB24 / BGR24, NV12 / I420, packed YUYV422 / UYVY422, GRAY8) -> 300x300 fp16 network input.
 //
 // Stands in for the first nodes of the TF graph the reference's CPU plugin runs on the full
 // resolution frame (`watsor/detection/tensorflow_cpu.py:113-115`):
@@ -17,26 +17,73 @@
 // Pixel formats (WzFrameDesc::fmt; SURVEY 8f-3, the decoder side: `watsor/stream/ffmpeg.py:78-88` reads rawvideo frames
 // of whatever `-pix_fmt` the decoder was told to write).  RGB24 is what the reference's schema asks for
 // (`watsor/config/schema.py:161`); NV12 / I420 are what a video decoder produces natively and half the bytes per
-// frame on PCIe.  For those the RGB value of a source pixel is worked out here, where ffmpeg's swscale would have
-// done it on the host: 8-bit BT.601 limited range, the chroma sample of the pixel's 2x2 block (no chroma
-// interpolation), the usual 8.8 fixed-point form
-//     C = Y - 16, D = U - 128, E = V - 128
-//     R = clip8((298 C + 409 E + 128) >> 8),  G = clip8((298 C - 100 D - 208 E + 128) >> 8),  B = clip8((298 C + 516 D + 128) >> 8)
-// -- integer arithmetic, bit-exact against oracle/yuv.py; the bytes equal a host-side conversion by that formula, they
-// are NOT pinned against a particular swscale code path (its C and SIMD converters differ from each other by one LSB).
-__device__ __forceinline__ void wz_fetch_rgb(const WzFrameDesc& f, int x, int y, float (&c)[3]) {
-    if (f.fmt == WZ_FMT_RGB24) {
+// frame on PCIe; packed 4:2:2 (YUYV422 / UYVY422) is what USB / V4L2 cameras and capture cards write, two thirds of the bytes.
+// For those the RGB value of a source pixel is worked out here, where ffmpeg's swscale would have done it on the host: 8-bit,
+// the chroma sample of the pixel's 2x2 block (4:2:0) or of its macropixel (4:2:2: x >> 1, same row) -- no chroma interpolation --
+// and the usual 8.8 fixed-point form, in integers:
+//     D = U - 128, E = V - 128
+//     R = clip8((cy C + rv E + 128) >> 8),  G = clip8((cy C + gu D + gv E + 128) >> 8),  B = clip8((cy C + bu D + 128) >> 8)
+// with coefficients round(256 x exact) from Kr / Kb (0.299 / 0.114: BT.601; 0.2126 / 0.0722: BT.709), limited range scaled by
+// 255/219 (luma) and 255/224 (chroma):
+//     matrix / range                       C        cy    rv     gu     gv    bu
+//     601 limited (no flag)                Y - 16   298   409   -100   -208   516
+//     601 full    (WZ_RANGE_FULL)          Y        256   359    -88   -183   454
+//     709 limited (WZ_CSP_BT709)           Y - 16   298   459    -55   -136   541
+//     709 full    (both)                   Y        256   403    -48   -120   475
+// -- integer arithmetic, bit-exact against oracle/yuv.py (no flag) and tests/pixfmt_oracle.py (which derives the table); the
+// bytes equal a host-side conversion by that formula, they are NOT pinned against a particular swscale code path (its C and SIMD
+// converters differ from each other by one LSB).  GRAY8 is R = G = B = Y unscaled, BGR24 is RGB24 with bytes 0 and 2 swapped.
+// The format word is the same for every pixel of a frame (blockIdx.y picks the frame): the kernels take it into a scalar register
+// once (`wz_format_word`), so the choice of the format's path is a scalar branch -- an RGB24 frame pays two compares for the other
+// formats being there -- and the coefficients are scalar values, selected where a YUV path needs them.
+__device__ __forceinline__ int wz_format_word(const WzFrameDesc& f) { return __builtin_amdgcn_readfirstlane(f.fmt); }
+struct WzYuvCoef { int yoff, cy, rv, gu, gv, bu; };
+__device__ __forceinline__ WzYuvCoef wz_yuv_coef(int fmt) {
+    const bool full = fmt & WZ_RANGE_FULL;
+    if (fmt & WZ_CSP_BT709) return full ? WzYuvCoef{0, 256, 403, -48, -120, 475} : WzYuvCoef{16, 298, 459, -55, -136, 541};
+    return full ? WzYuvCoef{0, 256, 359, -88, -183, 454} : WzYuvCoef{16, 298, 409, -100, -208, 516};
+}
+__device__ __forceinline__ void wz_yuv_to_rgb(int word, int Y, int U, int V, float (&c)[3]) {
+    const WzYuvCoef k = wz_yuv_coef(word);   // (only the YUV paths work these out: nothing of it is on the RGB24 path)
+    const int C = Y - k.yoff, D = U - 128, E = V - 128;
+    c[0] = (float)min(max((k.cy * C + k.rv * E + 128) >> 8, 0), 255);
+    c[1] = (float)min(max((k.cy * C + k.gu * D + k.gv * E + 128) >> 8, 0), 255);
+    c[2] = (float)min(max((k.cy * C + k.bu * D + 128) >> 8, 0), 255);
+}
+// one 4:2:2 macropixel as a little-endian dword (YUYV: Y0 U Y1 V; UYVY: U Y0 V Y1) -> the pixel `odd` (x & 1) of it
+__device__ __forceinline__ void wz_yuv422_to_rgb(int word, bool uyvy, unsigned m, int odd, float (&c)[3]) {
+    const int Y = (m >> ((uyvy ? 8 : 0) + odd * 16)) & 0xff;
+    const int U = (m >> (uyvy ? 0 : 8)) & 0xff;
+    const int V = (m >> (uyvy ? 16 : 24)) & 0xff;
+    wz_yuv_to_rgb(word, Y, U, V, c);
+}
+
+// one source pixel, byte by byte: every format at every address
+__device__ __forceinline__ void wz_fetch_rgb(const WzFrameDesc& f, int word, int x, int y, float (&c)[3]) {
+    const int fmt = word & WZ_FMT_BASE_MASK;
+    if (fmt == WZ_FMT_RGB24 || fmt == WZ_FMT_BGR24) {
         const uint8_t* p = f.rgb + ((size_t)y * f.w + x) * 3;
-        c[0] = (float)p[0];
+        const bool bgr = fmt == WZ_FMT_BGR24;
+        c[0] = (float)p[bgr ? 2 : 0];
         c[1] = (float)p[1];
-        c[2] = (float)p[2];
+        c[2] = (float)p[bgr ? 0 : 2];
+        return;
+    }
+    if (fmt == WZ_FMT_GRAY8) {
+        c[0] = c[1] = c[2] = (float)f.rgb[(size_t)y * f.w + x];
+        return;
+    }
+    if (fmt == WZ_FMT_YUYV422 || fmt == WZ_FMT_UYVY422) {
+        const uint8_t* p = f.rgb + ((size_t)y * f.w + (x & ~1)) * 2;   // the pixel's macropixel (w is even)
+        const unsigned m = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16) | ((unsigned)p[3] << 24);
+        wz_yuv422_to_rgb(word, fmt == WZ_FMT_UYVY422, m, x & 1, c);
         return;
     }
     const int Y = f.rgb[(size_t)y * f.w + x];
     const size_t cw = (size_t)(f.w >> 1);
     const uint8_t* chroma = f.rgb + (size_t)f.w * f.h;
     int U, V;
-    if (f.fmt == WZ_FMT_NV12) {
+    if (fmt == WZ_FMT_NV12) {
         const uint8_t* uv = chroma + ((size_t)(y >> 1) * cw + (x >> 1)) * 2;
         U = uv[0];
         V = uv[1];
@@ -45,17 +92,19 @@ __device__ __forceinline__ void wz_fetch_rgb(const WzFrameDesc& f, int x, int y,
         U = up[0];
         V = up[cw * (size_t)(f.h >> 1)];
     }
-    const int C = Y - 16, D = U - 128, E = V - 128;
-    c[0] = (float)min(max((298 * C + 409 * E + 128) >> 8, 0), 255);
-    c[1] = (float)min(max((298 * C - 100 * D - 208 * E + 128) >> 8, 0), 255);
-    c[2] = (float)min(max((298 * C + 516 * D + 128) >> 8, 0), 255);
+    wz_yuv_to_rgb(word, Y, U, V, c);
 }
 
 // The two horizontal taps of one source row.  RGB24: pixels x_lo and x_hi = x_lo (+1) are 6 contiguous bytes, so ONE 12-byte load
 // from the 4-byte boundary below them replaces six byte loads (the kernel was bound by the number of vector-memory instructions:
 // twelve byte loads per output pixel); the last few bytes of a frame, where those 12 bytes could reach past it, are read byte-wise.
-__device__ __forceinline__ void wz_fetch_row_pair(const WzFrameDesc& f, int x_lo, int x_hi, int y, float (&a)[3], float (&b)[3]) {
-    if (f.fmt == WZ_FMT_RGB24) {
+// BGR24 is the same window with the channels swapped.  4:2:2: a macropixel is 4 bytes at a multiple of 4 from the frame's start (w is
+// even), the two taps lie in one macropixel or in two adjacent ones: ONE 8-byte load from x_lo's macropixel, or a 4-byte load where
+// those 8 bytes would reach past the frame (the frame's last macropixel: x_hi is then in it as well); byte-wise where the frame's
+// address is not a multiple of 4.  GRAY8 is one byte per tap, NV12 / I420 three.
+__device__ __forceinline__ void wz_fetch_row_pair(const WzFrameDesc& f, int word, int x_lo, int x_hi, int y, float (&a)[3], float (&b)[3]) {
+    const int fmt = word & WZ_FMT_BASE_MASK;
+    if (fmt == WZ_FMT_RGB24 || fmt == WZ_FMT_BGR24) {
         const size_t off = ((size_t)y * f.w + x_lo) * 3;
         const size_t base = off & ~(size_t)3;
         if (base + 12 <= (size_t)f.w * f.h * 3 && ((uintptr_t)f.rgb & 3) == 0) {
@@ -77,11 +126,34 @@ __device__ __forceinline__ void wz_fetch_row_pair(const WzFrameDesc& f, int x_lo
             } else {
                 b[0] = a[0]; b[1] = a[1]; b[2] = a[2];
             }
+            if (fmt == WZ_FMT_BGR24) {
+                float t = a[0]; a[0] = a[2]; a[2] = t;
+                t = b[0]; b[0] = b[2]; b[2] = t;
+            }
+            return;
+        }
+    } else if (fmt == WZ_FMT_YUYV422 || fmt == WZ_FMT_UYVY422) {
+        if (((uintptr_t)f.rgb & 3) == 0) {
+            const size_t off = ((size_t)y * f.w + (x_lo & ~1)) * 2;
+            const uint8_t* const p = f.rgb + off;
+            unsigned m_lo, m_hi;
+            if (off + 8 <= (size_t)f.w * f.h * 2) {
+                typedef __attribute__((ext_vector_type(2))) unsigned int u2;   // (4-byte aligned only: see the 12-byte load above)
+                u2 v;
+                __builtin_memcpy(&v, __builtin_assume_aligned(p, 4), 8);
+                m_lo = v[0];
+                m_hi = (x_hi >> 1) != (x_lo >> 1) ? v[1] : v[0];
+            } else {
+                m_lo = m_hi = *reinterpret_cast<const unsigned*>(p);
+            }
+            const bool uyvy = fmt == WZ_FMT_UYVY422;
+            wz_yuv422_to_rgb(word, uyvy, m_lo, x_lo & 1, a);
+            wz_yuv422_to_rgb(word, uyvy, m_hi, x_hi & 1, b);
             return;
         }
     }
-    wz_fetch_rgb(f, x_lo, y, a);
-    wz_fetch_rgb(f, x_hi, y, b);
+    wz_fetch_rgb(f, word, x_lo, y, a);
+    wz_fetch_rgb(f, word, x_hi, y, b);
 }
 
 // HP: the network input is stored as a hi + lo pair of halves per value (hi = RN16(v), lo = RN16(v - hi), both
@@ -117,9 +189,15 @@ __global__ __launch_bounds__(256) void wz_k_preprocess(const WzFrameDesc* __rest
     const int x_hi = min((int)ceilf(in_x), f.w - 1);
     const float lx = in_x - fl_x;
 
+    const int word = wz_format_word(f);
     float tap[4][3];   // top-left, top-right, bottom-left, bottom-right
-    wz_fetch_row_pair(f, x_lo, x_hi, y_lo, tap[0], tap[1]);
-    wz_fetch_row_pair(f, x_lo, x_hi, y_hi, tap[2], tap[3]);
+    if (word == WZ_FMT_RGB24) {   // the reference's own format on a path of its own (the word is a constant there: the code of the other
+        wz_fetch_row_pair(f, WZ_FMT_RGB24, x_lo, x_hi, y_lo, tap[0], tap[1]);   // formats folds away): one scalar compare is all it pays for them
+        wz_fetch_row_pair(f, WZ_FMT_RGB24, x_lo, x_hi, y_hi, tap[2], tap[3]);
+    } else {
+        wz_fetch_row_pair(f, word, x_lo, x_hi, y_lo, tap[0], tap[1]);
+        wz_fetch_row_pair(f, word, x_lo, x_hi, y_hi, tap[2], tap[3]);
+    }
     half_t v[4], vl[4];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -178,17 +256,11 @@ __device__ __forceinline__ void wz_lds_row_pair(const uint8_t* __restrict__ run,
     }
 }
 
-__device__ __forceinline__ void wz_yuv_to_rgb(int Y, int U, int V, float (&c)[3]) {
-    const int C = Y - 16, D = U - 128, E = V - 128;
-    c[0] = (float)min(max((298 * C + 409 * E + 128) >> 8, 0), 255);
-    c[1] = (float)min(max((298 * C - 100 * D - 208 * E + 128) >> 8, 0), 255);
-    c[2] = (float)min(max((298 * C + 516 * D + 128) >> 8, 0), 255);
-}
-
 #define WZ_PRE_ROWS_THREADS 320   // 5 waves: 300 output pixels of a row, one per thread
 #define WZ_PRE_ROWS_MAX 8         // output rows a workgroup takes at most
-// A workgroup takes R consecutive output rows and stages the SPAN of source rows they tap -- one contiguous byte run (rows are packed),
-// plus the span of chroma rows under it (NV12: one run, I420: a U and a V run).  R = 1 where the resize skips rows (vertical scale >= 2: the
+// A workgroup takes R consecutive output rows and stages the SPAN of source rows they tap -- one contiguous byte run (rows are packed:
+// 3w bytes each for RGB24 / BGR24, 2w for YUYV422 / UYVY422 -- the chroma travels inside the macropixels --, w for GRAY8 and for luma),
+// plus, for the planar formats only, the span of chroma rows under it (NV12: one run, I420: a U and a V run).  R = 1 where the resize skips rows (vertical scale >= 2: the
 // span is the two adjacent rows an output row taps, nothing is fetched that is not used); below that every source row is tapped, by one
 // or two output rows, and R is as many rows as the LDS budget holds (up to 8): every source byte crosses PCIe once, in runs of 15 - 40 KiB
 // (640x480: 5 output rows = 8 - 9 source rows; one row at a time read 1.25 x the frame in 1 920-byte runs).  The grid is one workgroup per
@@ -205,16 +277,21 @@ __global__ __launch_bounds__(WZ_PRE_ROWS_THREADS) void wz_k_preprocess_rows(cons
     const WzFrameDesc f = frames ? frames[blockIdx.y] : pack.d[blockIdx.y];
     if (keep && blockIdx.x == 0 && threadIdx.x == 0) keep[blockIdx.y] = f;
     const int tid = threadIdx.x;
-    const int rowb = f.fmt == WZ_FMT_RGB24 ? f.w * 3 : f.w;          // bytes of a luma / RGB row
+    const int word = wz_format_word(f);
+    const int fmt = word & WZ_FMT_BASE_MASK;
+    const bool rgb3 = fmt == WZ_FMT_RGB24 || fmt == WZ_FMT_BGR24;
+    const bool yuv422 = fmt == WZ_FMT_YUYV422 || fmt == WZ_FMT_UYVY422;
+    const bool planar = fmt == WZ_FMT_NV12 || fmt == WZ_FMT_I420;    // the formats with chroma runs of their own
+    const int rowb = rgb3 ? f.w * 3 : yuv422 ? f.w * 2 : f.w;        // bytes of an RGB / BGR, a 4:2:2, a luma / gray row
     const int cw = f.w >> 1;
-    const int crowb = f.fmt == WZ_FMT_NV12 ? f.w : cw;               // bytes of a chroma row (NV12: interleaved; I420: per plane)
+    const int crowb = fmt == WZ_FMT_NV12 ? f.w : cw;                 // bytes of a chroma row (NV12: interleaved; I420: per plane)
 
     auto in_row = [&](int oy) { return half_pixel ? ((float)oy + 0.5f) * f.scale_y - 0.5f : (float)oy * f.scale_y; };
     // LDS bytes of R output rows' spans, from above: (R - 1) scale + 3 source rows, half as many + 2 chroma rows per chroma run, 32 per run
     auto need = [&](int R) {
         const int rows = (int)((float)(R - 1) * f.scale_y) + 3;
         int b = rows * rowb + 32;
-        if (f.fmt != WZ_FMT_RGB24) b += (f.fmt == WZ_FMT_NV12 ? 1 : 2) * (((rows >> 1) + 2) * crowb + 32);
+        if (planar) b += (fmt == WZ_FMT_NV12 ? 1 : 2) * (((rows >> 1) + 2) * crowb + 32);
         return b;
     };
     int R = 1;
@@ -231,14 +308,19 @@ __global__ __launch_bounds__(WZ_PRE_ROWS_THREADS) void wz_k_preprocess_rows(cons
     // (Over-read: a run is fetched as the whole aligned 16-byte chunks that COVER it -- up to 15 bytes in front of its first and behind its
     //  last byte.  Every chunk holds at least one byte of the run and an aligned 16-byte chunk never straddles a page, so the extra bytes
     //  lie in a page the run itself lies in: inside what wz_host_register() page-locked (pinning is page-granular) or inside the lane's
-    //  staging allocation, whatever the alignment of the registered range or of frame_stride.  They are never used.  ADVICE r4.)
+    //  staging allocation, whatever the alignment of the registered range or of frame_stride.  They are never used.  ADVICE r4.
+    //  The argument does not depend on the width of a row: it needs a run of at least one byte that lies inside the frame, and run 0
+    //  is rows y0 .. y1 of a frame of h rows of `rowb` >= 1 bytes -- 3w, 2w (w >= 2) or w bytes -- whose size wz_frame_bytes gives as
+    //  h * rowb for the single-run formats; YUYV422 / UYVY422, GRAY8 and BGR24 have no chroma run (nb1 = nb2 = 0: no chunk of src1 / src2
+    //  is ever requested).  LDS: run 0 of one output row is at most 2 rows + 31 bytes <= 3 * rowb + 32 <= 9 * max_w + 32, the RGB24
+    //  case that sizes wz_preprocess_rows_lds.)
     const uint8_t* const chroma = f.rgb + (size_t)f.w * f.h;
     const uint8_t* const src0 = f.rgb + (size_t)y0 * rowb;
     const uint8_t* const src1 = chroma + (size_t)cy0 * crowb;
     const uint8_t* const src2 = chroma + (size_t)cw * (f.h >> 1) + (size_t)cy0 * crowb;   // I420: the V plane
     const int nb0 = (y1 - y0 + 1) * rowb;
-    const int nb1 = f.fmt != WZ_FMT_RGB24 ? (cy1 - cy0 + 1) * crowb : 0;
-    const int nb2 = f.fmt == WZ_FMT_I420 ? nb1 : 0;
+    const int nb1 = planar ? (cy1 - cy0 + 1) * crowb : 0;
+    const int nb2 = fmt == WZ_FMT_I420 ? nb1 : 0;
     const int sh0 = (int)(reinterpret_cast<uintptr_t>(src0) & 15), sh1 = (int)(reinterpret_cast<uintptr_t>(src1) & 15);
     const int sh2 = (int)(reinterpret_cast<uintptr_t>(src2) & 15);
     const int n0 = (sh0 + nb0 + 15) >> 4, n1 = nb1 ? (sh1 + nb1 + 15) >> 4 : 0, n2 = nb2 ? (sh2 + nb2 + 15) >> 4 : 0;   // 16-byte chunks
@@ -281,11 +363,42 @@ __global__ __launch_bounds__(WZ_PRE_ROWS_THREADS) void wz_k_preprocess_rows(cons
             const int x_hi = min((int)ceilf(in_x), f.w - 1);
             const float lx = in_x - fl_x;
             float tap[4][3];   // top-left, top-right, bottom-left, bottom-right
-            if (f.fmt == WZ_FMT_RGB24) {
+            if (fmt == WZ_FMT_RGB24) {
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     const int y = q == 0 ? y_lo : y_hi;
                     wz_lds_row_pair(wz_pre_lds, sh0 + (y - y0) * rowb + x_lo * 3, x_hi != x_lo, tap[2 * q], tap[2 * q + 1]);
+                }
+            } else if (fmt == WZ_FMT_BGR24) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const int y = q == 0 ? y_lo : y_hi;
+                    wz_lds_row_pair(wz_pre_lds, sh0 + (y - y0) * rowb + x_lo * 3, x_hi != x_lo, tap[2 * q], tap[2 * q + 1]);
+                    {
+#pragma unroll
+                        for (int t = 0; t < 2; ++t) {
+                            const float s = tap[2 * q + t][0];
+                            tap[2 * q + t][0] = tap[2 * q + t][2];
+                            tap[2 * q + t][2] = s;
+                        }
+                    }
+                }
+            } else if (!planar) {   // 4:2:2 and gray: everything a tap needs lies in the one run (byte reads: the run starts at any address)
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const int y = q == 0 ? y_lo : y_hi;
+                    const uint8_t* const row = wz_pre_lds + sh0 + (y - y0) * rowb;
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) {
+                        const int x = t == 0 ? x_lo : x_hi;
+                        if (yuv422) {
+                            const uint8_t* const p = row + (x & ~1) * 2;
+                            const unsigned m = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16) | ((unsigned)p[3] << 24);
+                            wz_yuv422_to_rgb(word, fmt == WZ_FMT_UYVY422, m, x & 1, tap[2 * q + t]);
+                        } else {
+                            tap[2 * q + t][0] = tap[2 * q + t][1] = tap[2 * q + t][2] = (float)row[x];
+                        }
+                    }
                 }
             } else {
 #pragma unroll
@@ -297,7 +410,7 @@ __global__ __launch_bounds__(WZ_PRE_ROWS_THREADS) void wz_k_preprocess_rows(cons
                     for (int t = 0; t < 2; ++t) {
                         const int x = t == 0 ? x_lo : x_hi;
                         int U, V;
-                        if (f.fmt == WZ_FMT_NV12) {
+                        if (fmt == WZ_FMT_NV12) {
                             const uint8_t* const uv = wz_pre_lds + lds1 + sh1 + crow + (x >> 1) * 2;
                             U = uv[0];
                             V = uv[1];
@@ -305,7 +418,7 @@ __global__ __launch_bounds__(WZ_PRE_ROWS_THREADS) void wz_k_preprocess_rows(cons
                             U = wz_pre_lds[lds1 + sh1 + crow + (x >> 1)];
                             V = wz_pre_lds[lds2 + sh2 + crow + (x >> 1)];
                         }
-                        wz_yuv_to_rgb(yrow[x], U, V, tap[2 * q + t]);
+                        wz_yuv_to_rgb(word, yrow[x], U, V, tap[2 * q + t]);
                     }
                 }
             }
@@ -335,7 +448,8 @@ __global__ __launch_bounds__(WZ_PRE_ROWS_THREADS) void wz_k_preprocess_rows(cons
 }
 
 // LDS bytes of the row-staged kernel for frames up to `max_w` wide: what one output row of the widest frame needs (3 RGB rows, or 3 luma rows
-// and 2 x 3 chroma rows, + 32 per run), and at least 40 KiB so that frames whose resize skips no rows get several output rows per workgroup
+// and 2 x 3 chroma rows, + 32 per run), and at least 40 KiB so that frames whose resize skips no rows get several output rows per workgroup.
+// RGB24's 9 * max_w is the widest case: BGR24 is the same, the single runs of 4:2:2 (3 rows of 2w) and GRAY8 (3 rows of w) are narrower.
 size_t wz_preprocess_rows_lds(int max_w) {
     const size_t rgb = 3 * (size_t)max_w * 3 + 32;
     const size_t yuv = 3 * (size_t)max_w + 32 + 2 * (3 * (size_t)max_w + 32);

@@ -30,12 +30,14 @@ __device__ __forceinline__ half4_t wz_relu6_pack(const float4_t d, const float4_
 
 // One frame handed to the pre-processing kernel.
 struct WzFrameDesc {
-    const uint8_t* rgb;   // the frame (device): packed RGB24 h x w x 3, or NV12 / I420 (h x w luma, then the 2x2-subsampled chroma)
+    const uint8_t* rgb;   // the frame (device): packed RGB24 / BGR24 h x w x 3, NV12 / I420 (h x w luma, then the 2x2-subsampled chroma),
+                          // packed YUYV422 / UYVY422 h x w x 2, or GRAY8 h x w
     int32_t w, h;
     float scale_x, scale_y;   // (float)w / (float)size, TF legacy ResizeBilinear scale
     int32_t cam;              // camera filter index or -1
-    int32_t fmt;              // WZ_FMT_* (include/watsor_hip.h)
+    int32_t fmt;              // the format word: WZ_FMT_* in bits 0-7 | WZ_CSP_BT709 | WZ_RANGE_FULL (include/watsor_hip.h), validated by wz_frame_bytes
 };
+static_assert(sizeof(WzFrameDesc) == 32, "WzFrameDesc is 32 bytes (WzDescPack, the lanes' descriptor blocks)");
 
 struct WzConvArgs {
     const half_t* in;

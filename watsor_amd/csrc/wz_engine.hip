@@ -1250,11 +1250,29 @@ extern "C" const char* wz_device_name(wz_engine_t* e) { return e ? e->name.c_str
 // ------------------------------------------------------------------------------------------------
 // the hot call
 // ------------------------------------------------------------------------------------------------
+// Why a format word (include/watsor_hip.h: a base format in bits 0-7 | WZ_CSP_BT709 | WZ_RANGE_FULL) is not taken at this size, or
+// nullptr when it is.  The one place that knows the rules: wz_frame_bytes -- by which every frame is sized and checked -- is 0
+// exactly where this gives a reason.
+static const char* fmt_refusal(int w, int h, int fmt) {
+    if (w < 1 || h < 1) return "width and height must be positive";
+    if (fmt & ~(WZ_FMT_BASE_MASK | WZ_CSP_BT709 | WZ_RANGE_FULL)) return "unknown flag bits in the format word";
+    const int base = fmt & WZ_FMT_BASE_MASK;
+    if (base > WZ_FMT_BGR24) return "unknown base format";
+    const bool yuv = base == WZ_FMT_NV12 || base == WZ_FMT_I420 || base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422;
+    if (!yuv && (fmt & (WZ_CSP_BT709 | WZ_RANGE_FULL))) return "WZ_CSP_BT709 / WZ_RANGE_FULL apply to the YUV formats only, not to RGB24, BGR24 or GRAY8";
+    if ((base == WZ_FMT_NV12 || base == WZ_FMT_I420) && ((w | h) & 1)) return "NV12 / I420 need even sides";
+    if ((base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422) && (w & 1)) return "YUYV422 / UYVY422 need an even width";
+    return nullptr;
+}
 extern "C" uint64_t wz_frame_bytes(int w, int h, int fmt) {
-    if (w < 1 || h < 1) return 0;
-    if (fmt == WZ_FMT_RGB24) return (uint64_t)w * h * 3;
-    if ((fmt == WZ_FMT_NV12 || fmt == WZ_FMT_I420) && !(w & 1) && !(h & 1)) return (uint64_t)w * h * 3 / 2;
-    return 0;
+    if (fmt_refusal(w, h, fmt)) return 0;
+    const uint64_t px = (uint64_t)w * h;
+    switch (fmt & WZ_FMT_BASE_MASK) {
+        case WZ_FMT_RGB24: case WZ_FMT_BGR24: return px * 3;
+        case WZ_FMT_NV12: case WZ_FMT_I420: return px * 3 / 2;
+        case WZ_FMT_YUYV422: case WZ_FMT_UYVY422: return px * 2;
+        default: return px;   // WZ_FMT_GRAY8
+    }
 }
 
 static int fill_desc(wz_engine* e, int slot, int n, const uint8_t* const* d_rgb, const int* w, const int* h,
@@ -1267,7 +1285,7 @@ static int fill_desc(wz_engine* e, int slot, int n, const uint8_t* const* d_rgb,
         if (w[i] < 1 || h[i] < 1 || !d_rgb[i]) return wz_fail(WZ_EINVAL, "frame %d: bad pointer or size", i);
         const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
         if (!wz_frame_bytes(w[i], h[i], pf))
-            return wz_fail(WZ_EINVAL, "frame %d: pixel format %d at %dx%d (NV12 / I420 need even sides)", i, pf, w[i], h[i]);
+            return wz_fail(WZ_EINVAL, "frame %d: pixel format 0x%x at %dx%d: %s", i, pf, w[i], h[i], fmt_refusal(w[i], h[i], pf));
         const int c = cam ? cam[i] : -1;
         if (c >= WZ_MAX_CAMS) return wz_fail(WZ_ELIMIT, "camera id %d >= %d", c, WZ_MAX_CAMS);
         if (c >= 0 && e->h_cams[c].enabled && (e->h_cams[c].width != w[i] || e->h_cams[c].height != h[i]))
@@ -1366,7 +1384,7 @@ extern "C" int wz_detect_batch_fmt(wz_engine_t* e, int n, const uint8_t* const* 
             return wz_fail(WZ_ELIMIT, "frame %d is %dx%d, engine was created for at most %dx%d", i, w[i], h[i],
                            e->max_w, e->max_h);
         const uint64_t bytes = wz_frame_bytes(w[i], h[i], fmt ? fmt[i] : WZ_FMT_RGB24);
-        if (!bytes) return wz_fail(WZ_EINVAL, "frame %d: pixel format %d at %dx%d (NV12 / I420 need even sides)", i, fmt[i], w[i], h[i]);
+        if (!bytes) return wz_fail(WZ_EINVAL, "frame %d: pixel format 0x%x at %dx%d: %s", i, fmt[i], w[i], h[i], fmt_refusal(w[i], h[i], fmt[i]));
         uint8_t* dst = e->d_frames + e->frame_stride * i;
         HIPCHK(hipMemcpyAsync(dst, rgb[i], bytes, hipMemcpyHostToDevice, e->lanes[0].stream));
         dptr[i] = dst;
@@ -1431,7 +1449,7 @@ extern "C" int wz_submit_host_fmt(wz_engine_t* e, int slot, int n, const uint8_t
             return wz_fail(WZ_ELIMIT, "frame %d is %dx%d, engine was created for at most %dx%d", i, w[i], h[i],
                            e->max_w, e->max_h);
         const uint64_t bytes = wz_frame_bytes(w[i], h[i], fmt ? fmt[i] : WZ_FMT_RGB24);
-        if (!bytes) return wz_fail(WZ_EINVAL, "frame %d: pixel format %d at %dx%d (NV12 / I420 need even sides)", i, fmt[i], w[i], h[i]);
+        if (!bytes) return wz_fail(WZ_EINVAL, "frame %d: pixel format 0x%x at %dx%d: %s", i, fmt[i], w[i], h[i], fmt_refusal(w[i], h[i], fmt[i]));
         // pageable source: the runtime stages it (slow, synchronous); registered / pinned source: one DMA -- or no copy at all
         const uint8_t* dv = read_in_place(e, h[i]) ? device_view(e, rgb[i], bytes) : nullptr;
         if (dv) {
@@ -1496,7 +1514,7 @@ extern "C" int wz_bind_frames(wz_engine_t* e, int n, const uint8_t* const* pixel
         const int c = cam ? cam[i] : -1;
         if (!pixels[i] || !rows[i] || w[i] < 1 || h[i] < 1) return wz_fail(WZ_EINVAL, "frame-table entry %d: bad pointer or size", i);
         const uint64_t bytes = wz_frame_bytes(w[i], h[i], pf);
-        if (!bytes) return wz_fail(WZ_EINVAL, "frame-table entry %d: pixel format %d at %dx%d (NV12 / I420 need even sides)", i, pf, w[i], h[i]);
+        if (!bytes) return wz_fail(WZ_EINVAL, "frame-table entry %d: pixel format 0x%x at %dx%d: %s", i, pf, w[i], h[i], fmt_refusal(w[i], h[i], pf));
         if (w[i] > e->max_w || h[i] > e->max_h || (size_t)w[i] * h[i] * 3 > e->frame_stride)
             return wz_fail(WZ_ELIMIT, "frame-table entry %d is %dx%d, engine was created for at most %dx%d", i, w[i], h[i], e->max_w, e->max_h);
         if (c >= WZ_MAX_CAMS) return wz_fail(WZ_ELIMIT, "camera id %d >= %d", c, WZ_MAX_CAMS);
@@ -1833,7 +1851,7 @@ extern "C" int wz_stage_preprocess_fmt(wz_engine_t* e, const uint8_t* rgb, int w
     if (!e || !rgb || !out_half) return wz_fail(WZ_EINVAL, "wz_stage_preprocess: null argument");
     if (w > e->max_w || h > e->max_h || (size_t)w * h * 3 > e->frame_stride) return wz_fail(WZ_ELIMIT, "frame too large");
     const uint64_t bytes = wz_frame_bytes(w, h, fmt);
-    if (!bytes) return wz_fail(WZ_EINVAL, "pixel format %d at %dx%d (NV12 / I420 need even sides)", fmt, w, h);
+    if (!bytes) return wz_fail(WZ_EINVAL, "pixel format 0x%x at %dx%d: %s", fmt, w, h, fmt_refusal(w, h, fmt));
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipMemcpy(e->d_frames, rgb, bytes, hipMemcpyHostToDevice));

@@ -448,7 +448,8 @@ def create_object_detectors(delegate_class, stop_event, log_queue, frame_queue, 
       hip_drop     True: rows failing those filters come back as all-zero rows (for `hip_detection_sieve()`)
       hip_options  dict(max_batch=, max_width=, max_height=) overriding what is derived from the frame buffers (the largest
                    frame; max_batch 16 for more than 8 cameras unless WATSOR_HIP_MAX_BATCH says otherwise, else the plugin's 8);
-                   pixel_format= "rgb24" | "nv12" | "yuv420p" (or {camera name: ...}): what the decoders write (hip_gpu.py);
+                   pixel_format= "rgb24" | "nv12" | "yuv420p" | "yuvj420p" | "yuyv422" | "uyvy422" | "gray" (or {camera name: ...}): what the decoders write,
+                   color_matrix= "bt601" | "bt709", color_range= "limited" | "full" (likewise): how their YUV converts (hip_gpu.py);
                    schedule= "latency" | "throughput" | "auto" (default: latency for up to 4 cameras per detector, WZ_SCHEDULE wins);
                    numa= True | False | "auto" (default: pin each detector process to its GPU's NUMA node on multi-GPU hosts)
       hip_lanes    batches kept in flight per GPU by the worker (default: the engine's lanes, 4)

@@ -22,12 +22,19 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from ..runtime import FMT_I420, FMT_NV12, FMT_RGB24, HipEngine
+from ..runtime import (CSP_BT709, FMT_BASE_MASK, FMT_GRAY8, FMT_I420, FMT_NV12, FMT_RGB24, FMT_UYVY422, FMT_YUYV422, RANGE_FULL,
+                       YUV_FORMATS, HipEngine)
 from ..share import Detection
 
 # what a decoder's `-pix_fmt` may say (watsor/stream/ffmpeg.py:78-88 reads whatever it writes; the reference's schema asks for
-# rgb24, `watsor/config/schema.py:161` -- NV12 / yuv420p frames are half the bytes and are converted on the GPU)
-PIXEL_FORMATS = {"rgb24": FMT_RGB24, "nv12": FMT_NV12, "yuv420p": FMT_I420, "i420": FMT_I420}
+# rgb24, `watsor/config/schema.py:161` -- NV12 / yuv420p frames are half the bytes and are converted on the GPU, SURVEY 8f-3;
+# yuyv422 / uyvy422 is what USB / V4L2 cameras and capture cards write, gray what IR / thermal cameras do, yuvj420p -- yuv420p with
+# full-range levels -- what MJPEG cameras decode to)
+PIXEL_FORMATS = {"rgb24": FMT_RGB24, "nv12": FMT_NV12, "yuv420p": FMT_I420, "i420": FMT_I420, "yuyv422": FMT_YUYV422,
+                 "uyvy422": FMT_UYVY422, "gray": FMT_GRAY8, "yuvj420p": FMT_I420 | RANGE_FULL}
+# how a camera's YUV frames turn into RGB (include/watsor_hip.h: the colour flags of the format word)
+COLOR_MATRICES = {"bt601": 0, "bt709": CSP_BT709}
+COLOR_RANGES = {"limited": 0, "full": RANGE_FULL}
 
 ENGINE_FILE = "mi355x.bin"       # the analogue of gpu.trt (watsor/detection/detector.py:44)
 
@@ -39,10 +46,43 @@ def pixel_format_code(name) -> int:
         raise ValueError("pixel_format %r: expected one of %s" % (name, ", ".join(sorted(PIXEL_FORMATS)))) from None
 
 
+def _option_code(option: str, table: dict, name) -> int:
+    try:
+        return table[str(name).lower()]
+    except KeyError:
+        raise ValueError("%s %r: expected one of %s" % (option, name, ", ".join(sorted(table)))) from None
+
+
+def format_words(options: dict):
+    """(default format word, {camera name: format word}) from the plugin options `pixel_format`, `color_matrix` ("bt601" | "bt709") and
+    `color_range` ("limited" | "full"), each a single value or {camera name: value}.  The matrix and the range only mean something
+    for a YUV format: an RGB24 or gray camera under a detector-wide "bt709" keeps its plain word.  Unknown names, options and values
+    raise ValueError."""
+    tables = (("pixel_format", PIXEL_FORMATS, "rgb24"), ("color_matrix", COLOR_MATRICES, "bt601"), ("color_range", COLOR_RANGES, "limited"))
+    defaults, by_name = [], []
+    for option, table, plain in tables:
+        v = options.get(option) or plain
+        per = {str(k): _option_code(option, table, x) for k, x in v.items()} if isinstance(v, dict) else {}
+        defaults.append(table[plain] if isinstance(v, dict) else _option_code(option, table, v))
+        by_name.append(per)
+
+    def word(fmt, matrix, rng):
+        return fmt | matrix | rng if (fmt & FMT_BASE_MASK) in YUV_FORMATS else fmt
+
+    names = set().union(*by_name)
+    return word(*defaults), {n: word(*[per.get(n, dflt) for per, dflt in zip(by_name, defaults)]) for n in names}
+
+
+def _planar_format(default: int, by_camera: dict) -> int:
+    """What a one-channel buffer shaped (H*3/2, W) holds when its camera says RGB24: the one planar 4:2:0 format that is configured
+    (NV12 if none is).  Only NV12 / I420 have that shape -- a configured gray or 4:2:2 camera is never the answer."""
+    return next((f for f in [default] + list(by_camera.values()) if (f & FMT_BASE_MASK) in (FMT_NV12, FMT_I420)), FMT_NV12)
+
+
 def frame_formats(frames: Sequence[np.ndarray], cameras: Optional[Sequence[int]], default: int, by_camera: dict):
-    """Pixel format of every frame of a call: the camera's configured one, else the detector's; a planar (2-D) array that would
-    be read as RGB24 takes the one YUV format that is configured (NV12 if none is).  None = all RGB24."""
-    yuv = next((f for f in [default] + list(by_camera.values()) if f != FMT_RGB24), FMT_NV12)
+    """Format word of every frame of a call: the camera's configured one, else the detector's; a planar (2-D) array that would
+    be read as RGB24 takes the one planar YUV format that is configured (NV12 if none is).  None = all RGB24."""
+    yuv = _planar_format(default, by_camera)
     out = []
     for i, f in enumerate(frames):
         fmt = by_camera.get(cameras[i], default) if cameras is not None else default
@@ -60,9 +100,13 @@ class HipObjectDetector:
         """`options` (third positional argument, what `create_object_detectors` passes in `detector_args`):
         dict(max_batch=, max_width=, max_height=) -- the factory derives the frame size from the cameras' frame buffers;
         the keyword forms and the WATSOR_HIP_MAX_* environment variables are the fallbacks.
-        `options["pixel_format"]`: "rgb24" (default) | "nv12" | "yuv420p", or {camera name: one of these} -- what the cameras'
-        decoders write into their frame buffers.  An NV12 / yuv420p frame is handed over as the (H*3/2, W) uint8 array of its
-        bytes (that is its `image_shape`).
+        `options["pixel_format"]`: "rgb24" (default) | "nv12" | "yuv420p" | "yuvj420p" | "yuyv422" | "uyvy422" | "gray", or
+        {camera name: one of these} -- what the cameras' decoders write into their frame buffers.  An NV12 / yuv420p frame is handed
+        over as the (H*3/2, W) uint8 array of its bytes (that is its `image_shape`), a yuyv422 / uyvy422 frame as (H, W, 2) or
+        (H, 2W), a gray frame as (H, W) or (H, W, 1).
+        `options["color_matrix"]`: "bt601" (default) | "bt709", `options["color_range"]`: "limited" (default) | "full", each a single
+        value or {camera name: value} -- how the YUV formats are converted (an HD stream tagged bt709; a full-range MJPEG camera);
+        "yuvj420p" is "yuv420p" with the full range.
         `options["schedule"]`: "latency" | "throughput" | "auto" (default) -- the launch shapes of this detector PROCESS
         (include/watsor_hip.h: wz_set_schedule).  "latency" makes a lone batch finish soonest -- the reference's normal load is one
         frame at a time (`_next_frame`, detector.py:102-112); "throughput" gets the most frames per second out of four batches in
@@ -101,9 +145,7 @@ class HipObjectDetector:
         max_batch = max_batch or options.get("max_batch") or int(os.environ.get("WATSOR_HIP_MAX_BATCH", "8"))
         max_width = max_width or options.get("max_width") or int(os.environ.get("WATSOR_HIP_MAX_WIDTH", "1920"))
         max_height = max_height or options.get("max_height") or int(os.environ.get("WATSOR_HIP_MAX_HEIGHT", "1080"))
-        pf = options.get("pixel_format") or "rgb24"
-        self.__fmt_by_name = {str(k): pixel_format_code(v) for k, v in pf.items()} if isinstance(pf, dict) else {}
-        self.__fmt_default = FMT_RGB24 if isinstance(pf, dict) else pixel_format_code(pf)
+        self.__fmt_default, self.__fmt_by_name = format_words(options)
         self.__fmt_by_cam = {}
         self.__engine = HipEngine(engine_path, device, max_batch, max_width, max_height, schedule=schedule)
         self.__device = device
@@ -205,7 +247,9 @@ class HipObjectDetector:
         after the buffers exist.  Returns {camera name: (index of its frame 0 in the table, [frame.latch.next, ...])}."""
         import ctypes
         pix, ws, hs, fmts, cams, rows, table = [], [], [], [], [], [], {}
-        yuv = next((f for f in [self.__fmt_default] + list(self.__fmt_by_cam.values()) if f != FMT_RGB24), FMT_NV12)
+        from .. import _lib
+        frame_bytes = _lib.load().wz_frame_bytes              # (the library sizes a frame: one rule for the table and the engine)
+        yuv = _planar_format(self.__fmt_default, self.__fmt_by_cam)
         for name in sorted(frame_buffers, key=str):
             cam = ids.get(name, -1)
             fmt0 = self.__fmt_by_cam.get(cam, self.__fmt_default) if cam >= 0 else self.__fmt_default
@@ -215,15 +259,28 @@ class HipObjectDetector:
                 hdr = frame.header.get_obj() if hasattr(frame.header, "get_obj") else frame.header
                 obj = frame.image.get_obj() if hasattr(frame.image, "get_obj") else frame.image
                 w, h, fmt = int(hdr.width), int(hdr.height), fmt0
-                if fmt == FMT_RGB24 and int(hdr.channels) == 1:      # a planar buffer read as RGB24: the configured YUV format
+                channels = int(hdr.channels)
+                if fmt == FMT_RGB24 and channels == 1:               # a planar buffer read as RGB24: the configured planar YUV format
                     fmt = yuv
-                if fmt != FMT_RGB24:                                 # (H * 3 / 2, W) bytes of a W x H picture
-                    if int(hdr.channels) != 1 or h % 3 or w % 2 or (h // 3 * 2) % 2:
+                base = fmt & FMT_BASE_MASK
+                if base in (FMT_NV12, FMT_I420):                     # (H * 3 / 2, W) bytes of a W x H picture
+                    if channels != 1 or h % 3 or w % 2 or (h // 3 * 2) % 2:
                         raise ValueError("camera %r: an NV12 / I420 frame buffer must be (H*3/2, W, 1) with even H and W" % (name,))
                     h = h // 3 * 2
-                elif int(hdr.channels) != 3:
-                    raise ValueError("camera %r: an RGB24 frame buffer must have 3 channels" % (name,))
-                if ctypes.sizeof(obj) < (w * h * 3 if fmt == FMT_RGB24 else w * h * 3 // 2):
+                elif base in (FMT_YUYV422, FMT_UYVY422):             # (H, W, 2), or (H, 2W, 1)
+                    if channels == 1 and w % 4 == 0:
+                        w //= 2
+                    elif channels != 2 or w % 2:
+                        raise ValueError("camera %r: a YUYV422 / UYVY422 frame buffer must be (H, W, 2) or (H, 2W, 1) with even W" % (name,))
+                elif base == FMT_GRAY8:
+                    if channels != 1:
+                        raise ValueError("camera %r: a gray frame buffer must have 1 channel" % (name,))
+                elif channels != 3:
+                    raise ValueError("camera %r: an RGB24 / BGR24 frame buffer must have 3 channels" % (name,))
+                need = int(frame_bytes(w, h, fmt))
+                if not need:
+                    raise ValueError("camera %r: pixel format word 0x%x is not taken at %dx%d" % (name, fmt, w, h))
+                if ctypes.sizeof(obj) < need:
                     raise ValueError("camera %r: frame memory smaller than its header says" % (name,))
                 pix.append(ctypes.addressof(obj))
                 ws.append(w)

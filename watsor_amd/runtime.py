@@ -18,6 +18,11 @@ ROW_DTYPE = np.dtype([("label", "<i4"), ("zones", "<i4", (10,)), ("_pad", "<i4")
                       ("x_min", "<i4"), ("y_min", "<i4"), ("x_max", "<i4"), ("y_max", "<i4")])
 assert ROW_DTYPE.itemsize == C.sizeof(Detection) == 72
 FMT_RGB24, FMT_NV12, FMT_I420 = _lib.WZ_FMT_RGB24, _lib.WZ_FMT_NV12, _lib.WZ_FMT_I420   # pixel formats of a frame (include/watsor_hip.h)
+FMT_YUYV422, FMT_UYVY422, FMT_GRAY8, FMT_BGR24 = _lib.WZ_FMT_YUYV422, _lib.WZ_FMT_UYVY422, _lib.WZ_FMT_GRAY8, _lib.WZ_FMT_BGR24
+# a frame's format WORD is one of the above or'ed with colour flags (the four YUV formats only): BT.709 matrix instead of BT.601,
+# full range (ffmpeg's yuvj*) instead of limited
+CSP_BT709, RANGE_FULL, FMT_BASE_MASK = _lib.WZ_CSP_BT709, _lib.WZ_RANGE_FULL, _lib.WZ_FMT_BASE_MASK
+YUV_FORMATS = (FMT_NV12, FMT_I420, FMT_YUYV422, FMT_UYVY422)
 
 
 def device_count() -> int:
@@ -122,14 +127,22 @@ class HipEngine:
 
     @staticmethod
     def frame_geometry(f: np.ndarray, fmt: int = FMT_RGB24):
-        """(width, height) of a frame array: (H,W,3) uint8 for RGB24; for NV12 / I420 the usual planar view (H*3/2, W) [or (H*3/2, W, 1)] uint8
-        -- H rows of luma, then H/2 rows holding the subsampled chroma (the bytes a decoder writes with `-pix_fmt nv12` /
-        `yuv420p`).  Raises ValueError for anything else."""
+        """(width, height) of a frame array.  `fmt` is a format word: a base format, for the YUV ones or'ed with CSP_BT709 / RANGE_FULL.
+        RGB24 / BGR24: (H,W,3) uint8.  NV12 / I420: the usual planar view (H*3/2, W) [or (H*3/2, W, 1)] uint8 -- H rows of luma, then
+        H/2 rows holding the subsampled chroma (the bytes a decoder writes with `-pix_fmt nv12` / `yuv420p`).  YUYV422 / UYVY422:
+        (H, W, 2) or (H, 2W), W even.  GRAY8: (H, W) or (H, W, 1).  Raises ValueError for anything else, and for a format word the
+        library refuses (unknown bits, a colour flag on a format that is not YUV)."""
         if f.dtype != np.uint8:
             raise ValueError("frames are uint8 arrays")
-        if fmt == FMT_RGB24:
+        fmt = int(fmt)
+        flags, fmt = fmt & ~FMT_BASE_MASK, fmt & FMT_BASE_MASK
+        if flags & ~(CSP_BT709 | RANGE_FULL) or fmt < 0:
+            raise ValueError("unknown flag bits in pixel format word 0x%x" % (flags | fmt,))
+        if flags and fmt not in YUV_FORMATS:
+            raise ValueError("colour flags (BT.709 / full range) apply to the YUV pixel formats only")
+        if fmt in (FMT_RGB24, FMT_BGR24):
             if f.ndim != 3 or f.shape[2] != 3:
-                raise ValueError("an RGB24 frame must be (H,W,3) uint8")
+                raise ValueError("an RGB24 / BGR24 frame must be (H,W,3) uint8")
             return f.shape[1], f.shape[0]
         if fmt in (FMT_NV12, FMT_I420):
             if f.ndim == 3 and f.shape[2] == 1:      # (H*3/2, W, 1): a one-"channel" frame buffer of the reference (share.py:37-40)
@@ -137,12 +150,22 @@ class HipEngine:
             if f.ndim != 2 or f.shape[0] % 3 or (f.shape[0] // 3 * 2) % 2 or f.shape[1] % 2:
                 raise ValueError("an NV12 / I420 frame must be (H*3/2, W) uint8 with even H and W")
             return f.shape[1], f.shape[0] // 3 * 2
+        if fmt in (FMT_YUYV422, FMT_UYVY422):
+            if f.ndim == 3 and f.shape[2] == 2 and f.shape[1] % 2 == 0:
+                return f.shape[1], f.shape[0]
+            if f.ndim == 2 and f.shape[1] % 4 == 0:
+                return f.shape[1] // 2, f.shape[0]
+            raise ValueError("a YUYV422 / UYVY422 frame must be (H,W,2) or (H,2W) uint8 with even W")
+        if fmt == FMT_GRAY8:
+            if f.ndim == 2 or (f.ndim == 3 and f.shape[2] == 1):
+                return f.shape[1], f.shape[0]
+            raise ValueError("a GRAY8 frame must be (H,W) or (H,W,1) uint8")
         raise ValueError("unknown pixel format %r" % (fmt,))
 
     def detect_batch(self, frames: Sequence[np.ndarray], out_rows: Sequence, cams: Optional[Sequence[int]] = None,
                      out_pass: Optional[Sequence[np.ndarray]] = None, formats: Optional[Sequence[int]] = None) -> float:
         """frames: (H,W,3) uint8 C-contiguous arrays (host) -- or, with `formats[i]` = FMT_NV12 / FMT_I420, (H*3/2, W) planar
-        views; out_rows[i]: ctypes Detection[100] (or a ROW_DTYPE array of 100) written in place.  Returns the batch wall
+        views, or any other format word `frame_geometry` describes; out_rows[i]: ctypes Detection[100] (or a ROW_DTYPE array of 100) written in place.  Returns the batch wall
         time in ms."""
         n = len(frames)
         ptrs = (C.c_void_p * n)()
@@ -183,7 +206,7 @@ class HipEngine:
 
     def submit_host(self, slot: int, frames: Sequence[np.ndarray], cams: Optional[Sequence[int]] = None,
                     formats: Optional[Sequence[int]] = None) -> None:
-        """Asynchronous detect of host frames ((H,W,3) uint8, C-contiguous; NV12 / I420: see `frame_geometry`) on lane
+        """Asynchronous detect of host frames ((H,W,3) uint8, C-contiguous; other pixel formats: see `frame_geometry`) on lane
         `slot`; collect with `collect()` / `slot_rows()`.  The arrays must stay alive and unchanged until the slot is collected."""
         n = len(frames)
         ws = (C.c_int32 * n)()
