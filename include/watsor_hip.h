@@ -146,6 +146,34 @@ uint64_t wz_frame_bytes(int w, int h, int fmt);   /* bytes of one frame; 0 for a
 int wz_host_register(wz_engine_t* e, void* ptr, uint64_t bytes);
 int wz_host_unregister(wz_engine_t* e, void* ptr);
 int wz_collect(wz_engine_t* e, int slot, wz_detection_t* const* out, uint8_t* const* pass);
+/* ---- tiled detection.  The network sees 300 x 300 pixels whatever the camera delivers: in a 1080p frame a person
+ * 40 pixels tall arrives 11 pixels tall.  A tiled call runs the detector on rectangles of the frame instead -- a grid of overlapping tiles,
+ * the whole frame as one more tile, a single region of interest -- and reports ONE list of Detection[100] rows per frame, in frame
+ * coordinates.  On the lane's stream: a crop launch copies every tile into a contiguous image of the frame's own pixel format (the
+ * colour flags of the format word carry over), the tiles run as an ordinary batch without cameras, and a merge launch (one workgroup per
+ * frame) shifts each tile's rows by the tile's origin, thins them and applies the frame's camera filter to the 100 rows it keeps.
+ *   n_tiles[i], tiles[i]   the rectangles of frame i, in pixels: 1 .. WZ_MAX_TILES of them; all the tiles of a call are one batch, so
+ *                          their number may not exceed max_batch, and no tile may be larger than max_width x max_height
+ *   iou_thr, ios_thr       the merge: the tiles' rows with label > 0 and confidence > 0, ordered by confidence (ties: tile, then row), are
+ *                          walked in that order; a row is dropped iff a row already kept with the SAME label overlaps it by more than
+ *                          iou_thr (intersection over union) or by more than ios_thr of the smaller of the two boxes (an object cut by a
+ *                          tile's border against its whole box from the neighbouring or the full-frame tile).  Box sides are x_max - x_min
+ *                          and y_max - y_min, in int64; a threshold >= 1 switches its test off.  100 rows are kept, zones 0; the rest are the
+ *                          engine's padding rows (label 1, confidence 0, box 0); then the camera filter runs as wz_filter_rows does.
+ * fmt / cam / pass may be NULL as in wz_detect_batch_fmt / wz_submit_device_fmt; host frames are staged whole and cropped from that
+ * copy.  A tiled slot is collected like any other (wz_collect, or wz_wait + wz_slot_rows): n frames' merged rows.  Refused, with no row
+ * written and nothing enqueued: n or the tiles of the call beyond max_batch, n_tiles[i] outside 1 .. WZ_MAX_TILES (WZ_ELIMIT); a
+ * rectangle that is empty or leaves the frame, one the format cannot cut (NV12 / I420: even x0, y0, w, h; YUYV422 / UYVY422: even x0, w),
+ * one wz_frame_bytes() refuses as a frame, a threshold that is NaN or negative (WZ_EINVAL).  The worker's frame table (wz_bind_frames /
+ * wz_submit_bound) has no tiled form. */
+#define WZ_MAX_TILES 64                       /* tiles of one frame */
+typedef struct wz_tile { int32_t x0, y0, w, h; } wz_tile_t;   /* a rectangle of the frame, pixels */
+int wz_detect_tiled(wz_engine_t* e, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt,
+                    const int* cam, const int* n_tiles, const wz_tile_t* const* tiles, double iou_thr, double ios_thr,
+                    wz_detection_t* const* out, uint8_t* const* pass, float* ms);
+int wz_submit_tiled_device(wz_engine_t* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h,
+                           const int* fmt, const int* cam, const int* n_tiles, const wz_tile_t* const* tiles,
+                           double iou_thr, double ios_thr);      /* collected with wz_collect / wz_wait + wz_slot_rows */
 /* ---- the worker's frame table.  The reference worker resolves every payload to `frame_buffers[sender].frames[index]`, asks
  * the frame for a numpy view of its pixels and hands the frame header's `Detection[100]` array to the plugin
  * (watsor/detection/detector.py:102-109); pixels, size and rows of a Frame never move after the FrameBuffers are created
@@ -159,7 +187,7 @@ int wz_submit_bound(wz_engine_t* e, int slot, int n, const int32_t* entries);
 int wz_collect_bound(wz_engine_t* e, int slot);   /* waits for `slot`, writes its rows into the bound frames' rows */
 /* Wait for `slot` without copying rows out (rows stay readable via wz_slot_rows). */
 int wz_wait(wz_engine_t* e, int slot);
-const wz_detection_t* wz_slot_rows(wz_engine_t* e, int slot); /* pinned host, [n][100] */
+const wz_detection_t* wz_slot_rows(wz_engine_t* e, int slot); /* pinned host, [n][100]; after a tiled submit: the n frames' merged rows */
 int wz_sync(wz_engine_t* e);
 int wz_graph_nodes(wz_engine_t* e, int slot);   /* nodes of the hipGraph last replayed on `slot` (kernel launches; no copy node unless the lane's descriptor block has no device address); 0 without graphs */
 int wz_num_slots(wz_engine_t* e);   /* lanes actually created (WZ_SLOTS unless WZ_LANES in the environment says fewer) */
@@ -220,6 +248,7 @@ int wz_precision(wz_engine_t* e);   /* 16: fp16 storage / fp16 MFMA; 32: fp32 st
 /* leading inverted-residual blocks that run with split (hi + lo) matrix operands; 0 = plain fp16 program
  * (`python -m watsor_amd.engine --plain-fp16`), whose scores miss the 1e-3 tolerance */
 int wz_hp_blocks(wz_engine_t* e);
+double wz_nms_iou(wz_engine_t* e);  /* the IoU threshold of the engine's own non-maximum suppression (what a tiled call merges with by default) */
 
 /* ---- device memory helpers so callers need no other GPU runtime binding */
 int wz_dev_alloc(wz_engine_t* e, uint64_t bytes, void** d_ptr);
@@ -295,6 +324,18 @@ int wz_stage_postprocess(wz_engine_t* e, int n, const float* box_enc, const floa
 /* row fill (tensorflow_cpu.py:79-90) for caller-provided detections of one frame of size w x h */
 int wz_stage_rows(wz_engine_t* e, int w, int h, const float* boxes, const float* scores,
                   const int32_t* classes, wz_detection_t* rows);
+/* tiled detection, stage by stage: one rectangle of one host frame through the crop kernel -> out[wz_frame_bytes(tile->w, tile->h, fmt)]
+ * (byte for byte the contiguous copy of the same slices) ... */
+int wz_stage_crop_tile(wz_engine_t* e, const uint8_t* frame, int w, int h, int fmt, const wz_tile_t* tile, uint8_t* out);
+/* ... and the merge kernel + camera filter on caller-provided rows of the tiles of one w x h frame (cam: a camera id or -1) */
+int wz_stage_merge_tiles(wz_engine_t* e, int w, int h, int cam, int n_tiles, const wz_tile_t* tiles,
+                         const wz_detection_t* tile_rows /* [n_tiles][100] */, double iou_thr, double ios_thr,
+                         wz_detection_t* rows /* [100] */, uint8_t* pass /* [100] */);
+/* HIP-event time (ms, mean of reps) of the crop launch alone and of the merge launch alone, behind one tiled call of these arguments on lane 0;
+ * empty_ms: the same pair of event records with nothing between them */
+int wz_profile_tiled(wz_engine_t* e, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
+                     const int* n_tiles, const wz_tile_t* const* tiles, double iou_thr, double ios_thr, int reps,
+                     float* crop_ms, float* merge_ms, float* empty_ms);
 
 #endif /* WZ_DEV_BUILD */
 

@@ -24,6 +24,7 @@ WZ_FMT_YUYV422, WZ_FMT_UYVY422, WZ_FMT_GRAY8, WZ_FMT_BGR24 = 3, 4, 5, 6   # base
 WZ_FMT_BASE_MASK, WZ_CSP_BT709, WZ_RANGE_FULL = 0xFF, 0x100, 0x200        # ... or'ed with the colour flags of the YUV formats
 WZ_NUM_LABELS = 91
 WZ_MAX_CAMS = 256
+WZ_MAX_TILES = 64
 WZ_SCHEDULE_THROUGHPUT, WZ_SCHEDULE_LATENCY = 0, 1
 
 c_u8p = C.POINTER(C.c_uint8)
@@ -55,6 +56,10 @@ SIGNATURES = {
     "wz_frame_bytes": (C.c_uint64, [C.c_int, C.c_int, C.c_int]),
     "wz_host_register": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "wz_host_unregister": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "wz_detect_tiled": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, c_i32p,
+                                  C.POINTER(C.c_void_p), C.c_double, C.c_double, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_f32p]),
+    "wz_submit_tiled_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, c_i32p,
+                                         C.POINTER(C.c_void_p), C.c_double, C.c_double]),
     "wz_collect": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "wz_bind_frames": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, C.POINTER(C.c_void_p)]),
     "wz_submit_bound": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_i32p]),
@@ -82,6 +87,7 @@ SIGNATURES = {
     "wz_num_anchors": (C.c_int, [C.c_void_p]),
     "wz_num_classes": (C.c_int, [C.c_void_p]),
     "wz_hp_blocks": (C.c_int, [C.c_void_p]),
+    "wz_nms_iou": (C.c_double, [C.c_void_p]),
     "wz_dev_alloc": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "wz_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "wz_dev_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
@@ -112,6 +118,11 @@ DEV_SIGNATURES = {
     "wz_stage_postprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "wz_stage_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "wz_stage_crop_tile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "wz_profile_tiled": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, C.POINTER(C.c_void_p),
+                                   C.c_double, C.c_double, C.c_int, c_f32p, c_f32p, c_f32p]),
+    "wz_stage_merge_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                       C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -360,3 +360,23 @@ int wz_set_error(int code, const char* fmt, ...);   // sets wz_last_error() of t
 void wz_post_init();   // one-time kernel attributes (must run before any stream capture)
 void wz_launch_filter_rows(const WzCamFilter* d_cams, int cam, wz_detection_t* rows, uint8_t* pass, hipStream_t s);
 void wz_launch_sat(const uint8_t* fill, int32_t* sat, int width, int height, int n_zones, hipStream_t s);
+
+// ---- tiled detection (k_tiles.hip): the crop launch in front of a batch and the merge launch behind it --------------------------------
+// One rectangular byte copy: `rows` runs of `row_bytes` bytes, `src_pitch` bytes apart in the frame, contiguous in the tile image.
+struct WzCropPlane {
+    const uint8_t* src;
+    uint8_t* dst;
+    int32_t src_pitch, row_bytes, rows, _pad;
+};
+#define WZ_CROP_PACK 48
+struct WzCropPack { WzCropPlane p[WZ_CROP_PACK]; };   // plane descriptors as kernel arguments (1536 bytes); grid.y = planes in use
+struct WzMergeFrame { int32_t first, n_tiles, cam, _pad; };   // the frame's tiles are tiles [first, first + n_tiles) of the batch
+struct WzMergeCand {                                  // a tile's row in frame coordinates (the merge kernel's scratch, 32 bytes)
+    int32_t label, x_min, y_min, x_max, y_max, _pad;
+    double confidence;
+};
+void wz_launch_crop_tiles(const WzCropPlane* planes, int n, hipStream_t s);   // one launch per WZ_CROP_PACK planes
+// frames[n], origins[tiles][2] = (x0, y0), tile_rows[tiles][100], cands[tiles][100] scratch -> rows[n][100], pass[n][100] (pass = label > 0);
+// max_tiles: the most tiles any of the n frames has
+void wz_launch_merge_tiles(const WzMergeFrame* frames, const int32_t* origins, const wz_detection_t* tile_rows, WzMergeCand* cands, int n,
+                           int max_tiles, double iou_thr, double ios_thr, wz_detection_t* rows, uint8_t* pass, hipStream_t s);

@@ -135,6 +135,16 @@ struct wz_engine {
         uint32_t* h_status = nullptr;        // pinned, device-mapped: one word per frame, non-zero = the frame's rows may be short (wz_k_nms)
         uint32_t* m_status = nullptr;
         std::vector<int32_t> bound_idx;      // frame-table entries of the batch in flight (empty: not a bound batch)
+        // tiled detection (wz_submit_tiled_device / wz_detect_tiled), all allocated the first time the lane sees a tiled call (ensure_tiled):
+        uint8_t* d_tiles = nullptr;          // tile staging [max_batch][frame_stride]: the crop launch's output, the batch's frames
+        WzMergeCand* d_tcand = nullptr;      // the merge kernel's scratch [max_batch][100]
+        wz_detection_t* h_trows = nullptr;   // pinned, device-mapped: the merged rows [max_batch][100] ...
+        uint8_t* h_tpass = nullptr;          // ... and their pass bytes, written by the merge launch (and the filter launches behind it)
+        WzMergeFrame* h_tmeta = nullptr;     // pinned, device-mapped: WzMergeFrame[max_batch], then the tiles' origins int32[max_batch][2]
+        wz_detection_t* m_trows = nullptr;   // device addresses of the three
+        uint8_t* m_tpass = nullptr;
+        WzMergeFrame* m_tmeta = nullptr;
+        int tiled = 0;                       // frames of the tiled batch in flight (its rows are in h_trows); 0: the batch is not tiled
         hipEvent_t done = nullptr;
         int n = 0;
         bool rows = false;                       // the batch being enqueued runs the row-staged resize kernel (a frame of it is read in place)
@@ -1239,6 +1249,11 @@ extern "C" void wz_destroy(wz_engine_t* e) {
         if (L.h_pass) (void)hipHostFree(L.h_pass);
         if (L.h_status) (void)hipHostFree(L.h_status);
         if (L.h_stamps) (void)hipHostFree(L.h_stamps);
+        if (L.d_tiles) (void)hipFree(L.d_tiles);
+        if (L.d_tcand) (void)hipFree(L.d_tcand);
+        if (L.h_trows) (void)hipHostFree(L.h_trows);
+        if (L.h_tpass) (void)hipHostFree(L.h_tpass);
+        if (L.h_tmeta) (void)hipHostFree(L.h_tmeta);
         if (L.done) (void)hipEventDestroy(L.done);
         if (L.stream && L.owns_stream) (void)hipStreamDestroy(L.stream);
     }
@@ -1281,6 +1296,7 @@ static int fill_desc(wz_engine* e, int slot, int n, const uint8_t* const* d_rgb,
     if (n < 1 || n > e->max_batch) return wz_fail(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
     const float size = (float)e->hdr.input_size;
     e->lanes[slot].bound_idx.clear();
+    e->lanes[slot].tiled = 0;
     for (int i = 0; i < n; ++i) {
         if (w[i] < 1 || h[i] < 1 || !d_rgb[i]) return wz_fail(WZ_EINVAL, "frame %d: bad pointer or size", i);
         const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
@@ -1337,17 +1353,21 @@ static int lane_status(wz_engine* e, int slot) {
 
 extern "C" const wz_detection_t* wz_slot_rows(wz_engine_t* e, int slot) {
     if (!e || slot < 0 || slot >= e->n_lanes) return nullptr;
-    return e->lanes[slot].h_rows;
+    return e->lanes[slot].tiled ? e->lanes[slot].h_trows : e->lanes[slot].h_rows;   // (a tiled batch: the merged rows, one block per frame)
 }
 
 extern "C" int wz_collect(wz_engine_t* e, int slot, wz_detection_t* const* out, uint8_t* const* pass) {
     int rc = wz_wait(e, slot);
     if (rc != WZ_OK) return rc;
     const Lane& L = e->lanes[slot];
-    for (int i = 0; i < L.n; ++i) {
+    // a tiled batch hands over its frames' merged rows, not the L.n tiles' (lane_status still looks at every tile)
+    const int n = L.tiled ? L.tiled : L.n;
+    const wz_detection_t* rows = L.tiled ? L.h_trows : L.h_rows;
+    const uint8_t* passes = L.tiled ? L.h_tpass : L.h_pass;
+    for (int i = 0; i < n; ++i) {
         if (out && out[i])
-            memcpy(out[i], L.h_rows + (size_t)i * WZ_MAX_DETECTIONS, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS);
-        if (pass && pass[i]) memcpy(pass[i], L.h_pass + (size_t)i * WZ_MAX_DETECTIONS, WZ_MAX_DETECTIONS);
+            memcpy(out[i], rows + (size_t)i * WZ_MAX_DETECTIONS, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS);
+        if (pass && pass[i]) memcpy(pass[i], passes + (size_t)i * WZ_MAX_DETECTIONS, WZ_MAX_DETECTIONS);
     }
     return lane_status(e, slot);
 }
@@ -1495,6 +1515,204 @@ extern "C" int wz_host_unregister(wz_engine_t* e, void* ptr) {
         if (f.dev && f.host >= static_cast<const uint8_t*>(ptr)) f.dev = device_view(e, f.host, f.bytes);   // (re-resolved: stale views must not survive)
     HIPCHK(hipHostUnregister(ptr));
     return WZ_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// tiled detection: crop launch -> an ordinary batch over the tiles -> merge launch (k_tiles.hip)
+// ------------------------------------------------------------------------------------------------
+// Everything a lane needs for tiled calls, allocated the first time it sees one (an engine that never does uses no byte of it).
+static int ensure_tiled(wz_engine* e, Lane& L) {
+    if (L.d_tiles) return WZ_OK;
+    const size_t nb = (size_t)e->max_batch, rows = nb * WZ_MAX_DETECTIONS;
+    uint8_t* tiles = nullptr;
+    WzMergeCand* cand = nullptr;
+    wz_detection_t* hr = nullptr;
+    uint8_t* hp = nullptr;
+    WzMergeFrame* hm = nullptr;
+    hipError_t err = hipMalloc((void**)&tiles, e->frame_stride * nb);
+    if (err == hipSuccess) err = hipMalloc((void**)&cand, sizeof(WzMergeCand) * rows);
+    if (err == hipSuccess) err = hipHostMalloc((void**)&hr, sizeof(wz_detection_t) * rows, hipHostMallocMapped);
+    if (err == hipSuccess) err = hipHostMalloc((void**)&hp, rows, hipHostMallocMapped);
+    if (err == hipSuccess) err = hipHostMalloc((void**)&hm, (sizeof(WzMergeFrame) + 8) * nb, hipHostMallocMapped);
+    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&L.m_trows, hr, 0);
+    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&L.m_tpass, hp, 0);
+    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&L.m_tmeta, hm, 0);
+    if (err != hipSuccess) {
+        if (tiles) (void)hipFree(tiles);
+        if (cand) (void)hipFree(cand);
+        if (hr) (void)hipHostFree(hr);
+        if (hp) (void)hipHostFree(hp);
+        if (hm) (void)hipHostFree(hm);
+        return wz_fail(WZ_EHIP, "tile staging of a lane (%zu bytes): %s", e->frame_stride * nb, hipGetErrorString(err));
+    }
+    L.d_tiles = tiles; L.d_tcand = cand; L.h_trows = hr; L.h_tpass = hp; L.h_tmeta = hm;
+    return WZ_OK;
+}
+
+// Why rectangle t of a w x h frame of format word fmt cannot be cut, or nullptr
+static const char* tile_refusal(const wz_tile_t& t, int w, int h, int fmt) {
+    if (t.w < 1 || t.h < 1 || t.x0 < 0 || t.y0 < 0) return "origin and size must not be negative, the size not zero";
+    if ((int64_t)t.x0 + t.w > w || (int64_t)t.y0 + t.h > h) return "the rectangle leaves the frame";
+    const int base = fmt & WZ_FMT_BASE_MASK;
+    if ((base == WZ_FMT_NV12 || base == WZ_FMT_I420) && ((t.x0 | t.y0 | t.w | t.h) & 1)) return "NV12 / I420 need even x0, y0, w and h";
+    if ((base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422) && ((t.x0 | t.w) & 1)) return "YUYV422 / UYVY422 need even x0 and w";
+    if (!wz_frame_bytes(t.w, t.h, fmt)) return fmt_refusal(t.w, t.h, fmt);
+    return nullptr;
+}
+
+// The one to three rectangular byte copies that cut rectangle t out of a w x h frame at `src` into a contiguous image at `dst`.
+static void tile_planes(const uint8_t* src, int w, int h, int fmt, const wz_tile_t& t, uint8_t* dst, std::vector<WzCropPlane>& out) {
+    const int base = fmt & WZ_FMT_BASE_MASK;
+    const size_t W = (size_t)w, H = (size_t)h;
+    if (base == WZ_FMT_NV12 || base == WZ_FMT_I420) {
+        out.push_back({src + (size_t)t.y0 * W + t.x0, dst, w, t.w, t.h, 0});
+        const uint8_t* chroma = src + W * H;
+        uint8_t* dc = dst + (size_t)t.w * t.h;
+        if (base == WZ_FMT_NV12) {
+            out.push_back({chroma + (size_t)(t.y0 / 2) * W + t.x0, dc, w, t.w, t.h / 2, 0});
+        } else {
+            const size_t cw = W / 2, ch = H / 2, off = (size_t)(t.y0 / 2) * cw + t.x0 / 2;
+            out.push_back({chroma + off, dc, w / 2, t.w / 2, t.h / 2, 0});
+            out.push_back({chroma + cw * ch + off, dc + (size_t)(t.w / 2) * (t.h / 2), w / 2, t.w / 2, t.h / 2, 0});
+        }
+        return;
+    }
+    const int bpp = (base == WZ_FMT_RGB24 || base == WZ_FMT_BGR24) ? 3 : (base == WZ_FMT_GRAY8 ? 1 : 2);
+    out.push_back({src + ((size_t)t.y0 * W + t.x0) * bpp, dst, w * bpp, t.w * bpp, t.h, 0});
+}
+
+// Every refusal of a tiled call (include/watsor_hip.h), before anything is enqueued or written.  host: the frames are host frames that
+// go through the lane's staging area, which holds max_width x max_height.
+static int tiled_check(wz_engine* e, const char* who, int slot, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt,
+                       const int* cam, const int* n_tiles, const wz_tile_t* const* tiles, double iou_thr, double ios_thr, bool host, int* total) {
+    if (!e || !frames || !w || !h || !n_tiles || !tiles) return wz_fail(WZ_EINVAL, "%s: null argument", who);
+    if (slot < 0 || slot >= e->n_lanes) return wz_fail(WZ_EINVAL, "slot %d out of range [0,%d)", slot, e->n_lanes);
+    if (n < 1 || n > e->max_batch) return wz_fail(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
+    int64_t sum = 0;
+    for (int i = 0; i < n; ++i) {
+        if (n_tiles[i] < 1 || n_tiles[i] > WZ_MAX_TILES)
+            return wz_fail(WZ_ELIMIT, "frame %d: %d tiles, a frame takes 1 to %d", i, n_tiles[i], WZ_MAX_TILES);
+        sum += n_tiles[i];
+    }
+    if (sum > e->max_batch) return wz_fail(WZ_ELIMIT, "%lld tiles in one call exceed max_batch %d", (long long)sum, e->max_batch);
+    for (int i = 0; i < n; ++i) {
+        if (!frames[i] || !tiles[i] || w[i] < 1 || h[i] < 1) return wz_fail(WZ_EINVAL, "frame %d: bad pointer or size", i);
+        const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
+        if (!wz_frame_bytes(w[i], h[i], pf))
+            return wz_fail(WZ_EINVAL, "frame %d: pixel format 0x%x at %dx%d: %s", i, pf, w[i], h[i], fmt_refusal(w[i], h[i], pf));
+        if (host && (w[i] > e->max_w || h[i] > e->max_h || (size_t)w[i] * h[i] * 3 > e->frame_stride))
+            return wz_fail(WZ_ELIMIT, "frame %d is %dx%d, engine was created for at most %dx%d", i, w[i], h[i], e->max_w, e->max_h);
+        const int c = cam ? cam[i] : -1;
+        if (c >= WZ_MAX_CAMS) return wz_fail(WZ_ELIMIT, "camera id %d >= %d", c, WZ_MAX_CAMS);
+        if (c >= 0 && e->h_cams[c].enabled && (e->h_cams[c].width != w[i] || e->h_cams[c].height != h[i]))
+            return wz_fail(WZ_EINVAL, "frame %d is %dx%d but camera %d filter was set for %dx%d", i, w[i], h[i], c,
+                           e->h_cams[c].width, e->h_cams[c].height);
+        for (int t = 0; t < n_tiles[i]; ++t) {
+            const wz_tile_t& r = tiles[i][t];
+            const char* why = tile_refusal(r, w[i], h[i], pf);
+            if (why) return wz_fail(WZ_EINVAL, "frame %d (%dx%d, format 0x%x), tile %d (%d, %d, %d x %d): %s", i, w[i], h[i], pf, t, r.x0, r.y0, r.w, r.h, why);
+            if (r.w > e->max_w || r.h > e->max_h || (size_t)r.w * r.h * 3 > e->frame_stride)
+                return wz_fail(WZ_ELIMIT, "frame %d, tile %d is %dx%d, engine was created for at most %dx%d", i, t, r.w, r.h, e->max_w, e->max_h);
+        }
+    }
+    if (!(iou_thr >= 0.0) || !(ios_thr >= 0.0)) return wz_fail(WZ_EINVAL, "%s: the merge thresholds must be numbers >= 0", who);
+    *total = (int)sum;
+    return WZ_OK;
+}
+
+// What a checked tiled call launches: the crop launch's planes, the tiles as the batch's frames (in the lane's tile staging area, tile k
+// at k * frame_stride), and -- written into the lane's pinned block -- the merge launch's frames and origins.
+struct TiledLayout {
+    std::vector<WzCropPlane> planes;
+    std::vector<const uint8_t*> tptr;
+    std::vector<int> tw, th, tf;
+    int most = 0;   // the most tiles any frame has
+};
+static void tiled_layout(wz_engine* e, Lane& L, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt, const int* cam,
+                         const int* n_tiles, const wz_tile_t* const* tiles, int total, TiledLayout& y) {
+    y.tptr.resize(total); y.tw.resize(total); y.th.resize(total); y.tf.resize(total);
+    int32_t* origins = reinterpret_cast<int32_t*>(L.h_tmeta + e->max_batch);
+    int k = 0;
+    for (int i = 0; i < n; ++i) {
+        const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
+        const int c = cam ? cam[i] : -1;
+        L.h_tmeta[i] = {k, n_tiles[i], c < 0 ? -1 : c, 0};
+        y.most = std::max(y.most, n_tiles[i]);
+        for (int t = 0; t < n_tiles[i]; ++t, ++k) {
+            const wz_tile_t& r = tiles[i][t];
+            uint8_t* dst = L.d_tiles + e->frame_stride * k;
+            tile_planes(d_frames[i], w[i], h[i], pf, r, dst, y.planes);
+            y.tptr[k] = dst; y.tw[k] = r.w; y.th[k] = r.h; y.tf[k] = pf;   // (the colour flags of the frame's format word are its tiles')
+            origins[2 * k] = r.x0;
+            origins[2 * k + 1] = r.y0;
+        }
+    }
+}
+
+// A checked tiled call on a drained lane, frames in device memory: crop, batch, merge (+ the cameras' filters), the lane's event behind them.
+static int tiled_enqueue(wz_engine* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
+                         const int* cam, const int* n_tiles, const wz_tile_t* const* tiles, double iou_thr, double ios_thr, int total) {
+    Lane& L = e->lanes[slot];
+    int rc = ensure_tiled(e, L);
+    if (rc != WZ_OK) return rc;
+    TiledLayout y;
+    tiled_layout(e, L, n, d_frames, w, h, fmt, cam, n_tiles, tiles, total, y);
+    std::vector<const uint8_t*>& tptr = y.tptr;
+    std::vector<int>&tw = y.tw, &th = y.th, &tf = y.tf;
+    const int most = y.most;
+    wz_launch_crop_tiles(y.planes.data(), (int)y.planes.size(), L.stream);
+    // the tiles as an ordinary batch without cameras: 100 unfiltered rows per tile, in tile pixel coordinates, in L.h_rows
+    rc = fill_desc(e, slot, total, tptr.data(), tw.data(), th.data(), tf.data(), nullptr);
+    if (rc != WZ_OK) return rc;
+    L.rows = e->pre_rows;
+    rc = run_batch(e, slot, total);
+    if (rc != WZ_OK) return rc;
+    const int32_t* m_origins = reinterpret_cast<const int32_t*>(L.m_tmeta + e->max_batch);
+    wz_launch_merge_tiles(L.m_tmeta, m_origins, L.m_rows, L.d_tcand, n, most, iou_thr, ios_thr, L.m_trows, L.m_tpass, L.stream);
+    for (int i = 0; i < n; ++i)   // the frame's camera filter on its merged rows, exactly as wz_filter_rows applies it
+        if (cam && cam[i] >= 0 && e->h_cams[cam[i]].enabled)
+            wz_launch_filter_rows(e->d_cams, cam[i], L.m_trows + (size_t)i * WZ_MAX_DETECTIONS, L.m_tpass + (size_t)i * WZ_MAX_DETECTIONS, L.stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(L.done, L.stream));   // (run_batch recorded it behind the batch: wz_wait / wz_collect must see the merge)
+    L.tiled = n;
+    return WZ_OK;
+}
+
+extern "C" int wz_submit_tiled_device(wz_engine_t* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h,
+                                      const int* fmt, const int* cam, const int* n_tiles, const wz_tile_t* const* tiles,
+                                      double iou_thr, double ios_thr) {
+    int total = 0;
+    int rc = tiled_check(e, "wz_submit_tiled_device", slot, n, d_frames, w, h, fmt, cam, n_tiles, tiles, iou_thr, ios_thr, false, &total);
+    if (rc != WZ_OK) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipEventSynchronize(e->lanes[slot].done));   // the lane's previous batch has fully drained
+    return tiled_enqueue(e, slot, n, d_frames, w, h, fmt, cam, n_tiles, tiles, iou_thr, ios_thr, total);
+}
+
+extern "C" int wz_detect_tiled(wz_engine_t* e, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt,
+                               const int* cam, const int* n_tiles, const wz_tile_t* const* tiles, double iou_thr, double ios_thr,
+                               wz_detection_t* const* out, uint8_t* const* pass, float* ms) {
+    int total = 0;
+    int rc = tiled_check(e, "wz_detect_tiled", 0, n, frames, w, h, fmt, cam, n_tiles, tiles, iou_thr, ios_thr, true, &total);
+    if (rc != WZ_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(e->device));
+    Lane& L = e->lanes[0];
+    HIPCHK(hipEventSynchronize(L.done));
+    std::vector<const uint8_t*> dptr(n);
+    for (int i = 0; i < n; ++i) {   // the whole frame into the lane's staging area, as wz_submit_host_fmt stages it; the tiles are cut from that copy
+        rc = stage_frame(e, L, i, frames[i], wz_frame_bytes(w[i], h[i], fmt ? fmt[i] : WZ_FMT_RGB24), &dptr[i]);
+        if (rc != WZ_OK) return rc;
+    }
+    rc = tiled_enqueue(e, 0, n, dptr.data(), w, h, fmt, cam, n_tiles, tiles, iou_thr, ios_thr, total);
+    if (rc != WZ_OK) return rc;
+    rc = wz_collect(e, 0, out, pass);
+    if (rc != WZ_OK && rc != WZ_EINCOMPLETE) return rc;
+    const float el = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (ms)
+        for (int i = 0; i < n; ++i) ms[i] = el;
+    return rc;   // WZ_OK, or WZ_EINCOMPLETE: the merged rows are written, a tile's rows may have been short
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1666,6 +1884,7 @@ extern "C" int wz_precision(wz_engine_t* e) { return e ? (int)e->hdr.precision :
 extern "C" int wz_num_anchors(wz_engine_t* e) { return e ? (int)e->hdr.num_anchors : 0; }
 extern "C" int wz_num_classes(wz_engine_t* e) { return e ? (int)e->hdr.num_classes : 0; }
 extern "C" int wz_hp_blocks(wz_engine_t* e) { return e ? (int)e->hdr.hp_blocks : 0; }
+extern "C" double wz_nms_iou(wz_engine_t* e) { return e ? (double)e->hdr.iou_threshold : 0.0; }
 
 #ifdef WZ_DEV_BUILD   // ---- everything below this line exists in libwatsor_hip_dev.so only (include/watsor_hip.h, last section)
 extern "C" int wz_num_tensors(wz_engine_t* e) { return e ? (int)e->hdr.n_tensors : 0; }
@@ -1937,6 +2156,115 @@ extern "C" int wz_stage_rows(wz_engine_t* e, int w, int h, const float* boxes, c
     wz_launch_rows(e->lanes[0].post, e->lanes[0].d_desc, e->d_cams, 1, e->pc.max_total, e->lanes[0].d_rows, e->lanes[0].d_pass, e->stream);
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipMemcpy(rows, e->lanes[0].d_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS, hipMemcpyDeviceToHost));
+    return WZ_OK;
+}
+// one tile of one host frame through wz_k_crop_tiles; the device copy of the frame starts at the host pointer's offset within 16 bytes, so
+// that what a caller does to the source's alignment reaches the kernel
+extern "C" int wz_stage_crop_tile(wz_engine_t* e, const uint8_t* frame, int w, int h, int fmt, const wz_tile_t* tile, uint8_t* out) {
+    if (!e || !frame || !tile || !out) return wz_fail(WZ_EINVAL, "wz_stage_crop_tile: null argument");
+    const uint64_t bytes = wz_frame_bytes(w, h, fmt);
+    if (!bytes) return wz_fail(WZ_EINVAL, "pixel format 0x%x at %dx%d: %s", fmt, w, h, fmt_refusal(w, h, fmt));
+    const char* why = tile_refusal(*tile, w, h, fmt);
+    if (why) return wz_fail(WZ_EINVAL, "tile (%d, %d, %d x %d) of a %dx%d frame: %s", tile->x0, tile->y0, tile->w, tile->h, w, h, why);
+    const uint64_t tbytes = wz_frame_bytes(tile->w, tile->h, fmt);
+    if (bytes >> 31) return wz_fail(WZ_ELIMIT, "frame too large");
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    uint8_t* d_src = nullptr;
+    uint8_t* d_dst = nullptr;
+    const size_t skew = reinterpret_cast<uintptr_t>(frame) & 15u;
+    hipError_t err = hipMalloc((void**)&d_src, bytes + 16);
+    if (err == hipSuccess) err = hipMalloc((void**)&d_dst, tbytes);
+    if (err == hipSuccess) err = hipMemcpy(d_src + skew, frame, bytes, hipMemcpyHostToDevice);
+    if (err == hipSuccess) {
+        std::vector<WzCropPlane> planes;
+        tile_planes(d_src + skew, w, h, fmt, *tile, d_dst, planes);
+        wz_launch_crop_tiles(planes.data(), (int)planes.size(), e->stream);
+        err = hipStreamSynchronize(e->stream);
+    }
+    if (err == hipSuccess) err = hipMemcpy(out, d_dst, tbytes, hipMemcpyDeviceToHost);
+    if (d_src) (void)hipFree(d_src);
+    if (d_dst) (void)hipFree(d_dst);
+    if (err != hipSuccess) return wz_fail(WZ_EHIP, "wz_stage_crop_tile: %s", hipGetErrorString(err));
+    return WZ_OK;
+}
+
+// wz_k_merge_tiles (+ the camera's filter) on caller-provided tile rows of one w x h frame
+extern "C" int wz_stage_merge_tiles(wz_engine_t* e, int w, int h, int cam, int n_tiles, const wz_tile_t* tiles, const wz_detection_t* tile_rows,
+                                    double iou_thr, double ios_thr, wz_detection_t* rows, uint8_t* pass) {
+    if (!e || !tiles || !tile_rows || !rows || !pass || w < 1 || h < 1) return wz_fail(WZ_EINVAL, "wz_stage_merge_tiles: bad argument");
+    if (n_tiles < 1 || n_tiles > WZ_MAX_TILES) return wz_fail(WZ_ELIMIT, "%d tiles, a frame takes 1 to %d", n_tiles, WZ_MAX_TILES);
+    if (cam >= WZ_MAX_CAMS) return wz_fail(WZ_ELIMIT, "camera id %d >= %d", cam, WZ_MAX_CAMS);
+    if (cam >= 0 && e->h_cams[cam].enabled && (e->h_cams[cam].width != w || e->h_cams[cam].height != h))
+        return wz_fail(WZ_EINVAL, "the frame is %dx%d but camera %d filter was set for %dx%d", w, h, cam, e->h_cams[cam].width, e->h_cams[cam].height);
+    for (int t = 0; t < n_tiles; ++t)
+        if (tiles[t].w < 1 || tiles[t].h < 1 || tiles[t].x0 < 0 || tiles[t].y0 < 0 || (int64_t)tiles[t].x0 + tiles[t].w > w || (int64_t)tiles[t].y0 + tiles[t].h > h)
+            return wz_fail(WZ_EINVAL, "tile %d (%d, %d, %d x %d) is no rectangle of a %dx%d frame", t, tiles[t].x0, tiles[t].y0, tiles[t].w, tiles[t].h, w, h);
+    if (!(iou_thr >= 0.0) || !(ios_thr >= 0.0)) return wz_fail(WZ_EINVAL, "wz_stage_merge_tiles: the merge thresholds must be numbers >= 0");
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const size_t nr = (size_t)n_tiles * WZ_MAX_DETECTIONS;
+    const size_t off_meta = sizeof(wz_detection_t) * nr, off_org = off_meta + sizeof(WzMergeFrame), off_cand = off_org + 8 * (size_t)n_tiles,
+                 off_rows = off_cand + sizeof(WzMergeCand) * nr, off_pass = off_rows + sizeof(wz_detection_t) * WZ_MAX_DETECTIONS,
+                 all = off_pass + WZ_MAX_DETECTIONS;   // (every block's size is a multiple of 8: the offsets stay aligned)
+    uint8_t* d = nullptr;
+    HIPCHK(hipMalloc((void**)&d, all));
+    const WzMergeFrame fr = {0, n_tiles, cam < 0 ? -1 : cam, 0};
+    std::vector<int32_t> org(2 * (size_t)n_tiles);
+    for (int t = 0; t < n_tiles; ++t) org[2 * t] = tiles[t].x0, org[2 * t + 1] = tiles[t].y0;
+    hipError_t err = hipMemcpy(d, tile_rows, off_meta, hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(d + off_meta, &fr, sizeof(fr), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(d + off_org, org.data(), org.size() * 4, hipMemcpyHostToDevice);
+    if (err == hipSuccess) {
+        wz_detection_t* d_rows = reinterpret_cast<wz_detection_t*>(d + off_rows);
+        wz_launch_merge_tiles(reinterpret_cast<const WzMergeFrame*>(d + off_meta), reinterpret_cast<const int32_t*>(d + off_org),
+                              reinterpret_cast<const wz_detection_t*>(d), reinterpret_cast<WzMergeCand*>(d + off_cand), 1, n_tiles, iou_thr,
+                              ios_thr, d_rows, d + off_pass, e->stream);
+        if (cam >= 0 && e->h_cams[cam].enabled) wz_launch_filter_rows(e->d_cams, cam, d_rows, d + off_pass, e->stream);
+        err = hipStreamSynchronize(e->stream);
+    }
+    if (err == hipSuccess) err = hipMemcpy(rows, d + off_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS, hipMemcpyDeviceToHost);
+    if (err == hipSuccess) err = hipMemcpy(pass, d + off_pass, WZ_MAX_DETECTIONS, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (err != hipSuccess) return wz_fail(WZ_EHIP, "wz_stage_merge_tiles: %s", hipGetErrorString(err));
+    return WZ_OK;
+}
+// HIP-event time of the crop launch alone and of the merge launch alone (no filter launch), on lane 0 behind one whole tiled call of the
+// same arguments (so that the merge reads real tile rows): the mean of `reps` brackets each, in milliseconds; empty_ms: the same bracket around nothing
+extern "C" int wz_profile_tiled(wz_engine_t* e, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
+                                const int* n_tiles, const wz_tile_t* const* tiles, double iou_thr, double ios_thr, int reps,
+                                float* crop_ms, float* merge_ms, float* empty_ms) {
+    if (reps < 1 || !crop_ms || !merge_ms || !empty_ms) return wz_fail(WZ_EINVAL, "wz_profile_tiled: bad argument");
+    int rc = wz_submit_tiled_device(e, 0, n, d_frames, w, h, fmt, nullptr, n_tiles, tiles, iou_thr, ios_thr);
+    if (rc != WZ_OK) return rc;
+    rc = wz_wait(e, 0);
+    if (rc != WZ_OK) return rc;
+    Lane& L = e->lanes[0];
+    int total = 0;
+    for (int i = 0; i < n; ++i) total += n_tiles[i];
+    TiledLayout y;
+    tiled_layout(e, L, n, d_frames, w, h, fmt, nullptr, n_tiles, tiles, total, y);
+    hipEvent_t a, b;
+    HIPCHK(hipEventCreate(&a));
+    HIPCHK(hipEventCreate(&b));
+    double sum[3] = {0.0, 0.0, 0.0};   // crop, merge, two event records with nothing between them (the bracket's own cost)
+    const int32_t* m_origins = reinterpret_cast<const int32_t*>(L.m_tmeta + e->max_batch);
+    for (int which = 0; which < 3; ++which)
+        for (int r = 0; r < reps + 3; ++r) {   // (three unmeasured launches first)
+            HIPCHK(hipEventRecord(a, L.stream));
+            if (which == 0) wz_launch_crop_tiles(y.planes.data(), (int)y.planes.size(), L.stream);
+            else if (which == 1) wz_launch_merge_tiles(L.m_tmeta, m_origins, L.m_rows, L.d_tcand, n, y.most, iou_thr, ios_thr, L.m_trows, L.m_tpass, L.stream);
+            HIPCHK(hipEventRecord(b, L.stream));
+            HIPCHK(hipEventSynchronize(b));
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, a, b));
+            if (r >= 3) sum[which] += ms;
+        }
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+    *crop_ms = (float)(sum[0] / reps);
+    *merge_ms = (float)(sum[1] / reps);
+    *empty_ms = (float)(sum[2] / reps);
     return WZ_OK;
 }
 #endif   // WZ_DEV_BUILD

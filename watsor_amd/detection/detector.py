@@ -100,6 +100,11 @@ class BatchedWorkerMixin:
                               logger=getattr(self, "_logger", None))
         if hasattr(object_detector, "submit_host") and hasattr(object_detector, "collect"):
             st["asynchronous"] = kwargs.get("hip_async", True)
+            if st["asynchronous"] and getattr(object_detector, "tiled", False):
+                # tiled detection (plugin option `tiles`) exists on detect() / detect_batch() only: neither the frame table nor the
+                # asynchronous host path has a tiled form, and nothing may be detected untiled in silence
+                st["asynchronous"] = False
+                self._info("tiles are configured: batches go through detect_batch(), one call at a time")
             lanes = getattr(object_detector, "num_lanes", 1)
             st["lanes"] = max(1, min(int(kwargs.get("hip_lanes", lanes)), lanes))
         if st["asynchronous"] and kwargs.get("hip_frame_table", True) and hasattr(object_detector, "bind_frame_table"):

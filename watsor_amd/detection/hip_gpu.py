@@ -23,7 +23,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ..runtime import (CSP_BT709, FMT_BASE_MASK, FMT_GRAY8, FMT_I420, FMT_NV12, FMT_RGB24, FMT_UYVY422, FMT_YUYV422, RANGE_FULL,
-                       YUV_FORMATS, HipEngine)
+                       YUV_FORMATS, HipEngine, tile_grid)
+from .._lib import WZ_MAX_TILES
 from ..share import Detection
 
 # what a decoder's `-pix_fmt` may say (watsor/stream/ffmpeg.py:78-88 reads whatever it writes; the reference's schema asks for
@@ -92,6 +93,61 @@ def frame_formats(frames: Sequence[np.ndarray], cameras: Optional[Sequence[int]]
     return out if any(f != FMT_RGB24 for f in out) else None
 
 
+_TILE_KEYS = {"grid", "overlap", "full_frame", "iou", "ios", "rects"}
+
+
+def _tile_spec(spec, where: str) -> dict:
+    """One checked `tiles` option: {"grid": [cols, rows], "overlap": 0.2, "full_frame": True, "iou": ..., "ios": ...} or
+    {"rects": [[x0, y0, w, h], ...], "iou": ..., "ios": ...}.  Anything else raises ValueError."""
+    if not isinstance(spec, dict) or ("grid" in spec) == ("rects" in spec):
+        raise ValueError("%s: expected {\"grid\": [cols, rows], ...} or {\"rects\": [[x0, y0, w, h], ...]}, got %r" % (where, spec))
+    if set(spec) - _TILE_KEYS:
+        raise ValueError("%s: unknown key(s) %s" % (where, ", ".join(sorted(map(str, set(spec) - _TILE_KEYS)))))
+    out = {"iou": spec.get("iou"), "ios": spec.get("ios")}
+    for k in ("iou", "ios"):
+        v = out[k]
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float)) or not v >= 0):
+            raise ValueError("%s: %s %r, expected a number >= 0" % (where, k, v))
+    def whole(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+    if "grid" in spec:
+        g = spec["grid"]
+        if not isinstance(g, (list, tuple)) or len(g) != 2 or not all(whole(v) and v >= 1 for v in g):
+            raise ValueError("%s: grid %r, expected [cols, rows] with both >= 1" % (where, g))
+        ov = spec.get("overlap", 0.0)
+        if isinstance(ov, bool) or not isinstance(ov, (int, float)) or not 0.0 <= ov < 1.0:
+            raise ValueError("%s: overlap %r, expected 0 <= overlap < 1" % (where, ov))
+        full = spec.get("full_frame", True)
+        if not isinstance(full, bool):
+            raise ValueError("%s: full_frame %r, expected true or false" % (where, full))
+        out.update(grid=(g[0], g[1]), overlap=float(ov), full_frame=full, count=g[0] * g[1] + (1 if full and g[0] * g[1] > 1 else 0))
+    else:
+        if "overlap" in spec or "full_frame" in spec:
+            raise ValueError("%s: overlap / full_frame belong to a grid, not to rects" % where)
+        r = spec["rects"]
+        if not isinstance(r, (list, tuple)) or not r or not all(
+                isinstance(t, (list, tuple)) and len(t) == 4 and all(whole(v) for v in t) and t[0] >= 0 and t[1] >= 0 and t[2] >= 1 and t[3] >= 1
+                for t in r):
+            raise ValueError("%s: rects %r, expected a non-empty list of [x0, y0, w, h] with x0, y0 >= 0 and w, h >= 1" % (where, r))
+        out.update(rects=[tuple(t) for t in r], count=len(r))
+    if out["count"] > WZ_MAX_TILES:
+        raise ValueError("%s: %d tiles, a frame takes at most %d" % (where, out["count"], WZ_MAX_TILES))
+    return out
+
+
+def tile_options(options: dict):
+    """(the detector's tiles or None, {camera name: tiles}) from the plugin option `tiles`: one description (see `_tile_spec`) for
+    every camera, or {camera name: description}.  Bad options raise ValueError."""
+    v = options.get("tiles")
+    if v is None:
+        return None, {}
+    if isinstance(v, dict) and ("grid" in v or "rects" in v):
+        return _tile_spec(v, "tiles"), {}
+    if not isinstance(v, dict) or not v:
+        raise ValueError("tiles: expected a description of the tiles or {camera name: description}, got %r" % (v,))
+    return None, {str(name): _tile_spec(spec, "tiles[%r]" % (name,)) for name, spec in v.items()}
+
+
 class HipObjectDetector:
     """Performs object detection on AMD Instinct MI355X GPUs (hand-written HIP kernels)."""
 
@@ -107,6 +163,14 @@ class HipObjectDetector:
         `options["color_matrix"]`: "bt601" (default) | "bt709", `options["color_range"]`: "limited" (default) | "full", each a single
         value or {camera name: value} -- how the YUV formats are converted (an HD stream tagged bt709; a full-range MJPEG camera);
         "yuvj420p" is "yuv420p" with the full range.
+        `options["tiles"]`: run the detector on rectangles of every frame instead of the whole frame squeezed into the network's
+        input, and report one merged list of rows in frame coordinates (include/watsor_hip.h: wz_detect_tiled).
+        {"grid": [cols, rows], "overlap": 0.2, "full_frame": True, "iou": ..., "ios": ...} -- `tile_grid` of every frame's size; "iou" /
+        "ios": a row goes when a more confident row of its label overlaps it by more than `iou` (intersection over union, default: the
+        engine's NMS threshold) or by more than `ios` of the smaller box (default 1.0: off; 0.5 - 0.7 merges an object cut by a tile's
+        border with its whole box) -- or explicit {"rects": [[x0, y0, w, h], ...]}, or {camera name: one of these}.  The tiles of one
+        frame must fit max_batch; `detect_batch` cuts a batch into as many calls as its tiles need.  The batched worker's frame table
+        has no tiled form: `bind_frame_table` raises for a camera with tiles.
         `options["schedule"]`: "latency" | "throughput" | "auto" (default) -- the launch shapes of this detector PROCESS
         (include/watsor_hip.h: wz_set_schedule).  "latency" makes a lone batch finish soonest -- the reference's normal load is one
         frame at a time (`_next_frame`, detector.py:102-112); "throughput" gets the most frames per second out of four batches in
@@ -147,6 +211,12 @@ class HipObjectDetector:
         max_height = max_height or options.get("max_height") or int(os.environ.get("WATSOR_HIP_MAX_HEIGHT", "1080"))
         self.__fmt_default, self.__fmt_by_name = format_words(options)
         self.__fmt_by_cam = {}
+        self.__tiles_default, self.__tiles_by_name = tile_options(options)
+        self.__tiles_by_cam = {}
+        self.__tile_rects = {}
+        for where, spec in [("tiles", self.__tiles_default)] + [("tiles[%r]" % n, t) for n, t in self.__tiles_by_name.items()]:
+            if spec is not None and spec["count"] > max_batch:
+                raise ValueError("%s: %d tiles per frame exceed max_batch %d" % (where, spec["count"], max_batch))
         self.__engine = HipEngine(engine_path, device, max_batch, max_width, max_height, schedule=schedule)
         self.__device = device
         self.__filters = []
@@ -166,6 +236,11 @@ class HipObjectDetector:
 
     def _formats(self, frames: Sequence[np.ndarray], cameras: Optional[Sequence[int]]):
         return frame_formats(frames, cameras, self.__fmt_default, self.__fmt_by_cam)
+
+    @property
+    def tiled(self) -> bool:
+        """A `tiles` option is set (for every camera or for some): frames go through `detect()` / `detect_batch()` only."""
+        return self.__tiles_default is not None or bool(self.__tiles_by_name)
 
     @property
     def engine(self) -> HipEngine:
@@ -212,13 +287,14 @@ class HipObjectDetector:
         from ..filter.hip_filter import HipCameraFilter
         from .._lib import WZ_MAX_CAMS
         names = sorted(frame_buffers, key=str)
-        need = [n for n in names if n in (camera_configs or {}) or str(n) in self.__fmt_by_name]
+        need = [n for n in names if n in (camera_configs or {}) or str(n) in self.__fmt_by_name or str(n) in self.__tiles_by_name]
         if len(need) > WZ_MAX_CAMS:
             raise ValueError("%d cameras with GPU filters / pixel formats of their own on one detector: the engine has %d slots"
                              % (len(need), WZ_MAX_CAMS))
         ids = {name: -1 for name in names}
         ids.update({name: i for i, name in enumerate(need)})
         self.__fmt_by_cam = {i: self.__fmt_by_name.get(str(name), self.__fmt_default) for name, i in ids.items() if i >= 0}
+        self.__tiles_by_cam = {i: self.__tiles_by_name[str(name)] for name, i in ids.items() if i >= 0 and str(name) in self.__tiles_by_name}
         for name, cfg in (camera_configs or {}).items():
             if name in ids:
                 self.__filters.append(HipCameraFilter(self.__engine, ids[name], cfg, drop=drop))
@@ -251,6 +327,9 @@ class HipObjectDetector:
         frame_bytes = _lib.load().wz_frame_bytes              # (the library sizes a frame: one rule for the table and the engine)
         yuv = _planar_format(self.__fmt_default, self.__fmt_by_cam)
         for name in sorted(frame_buffers, key=str):
+            if self.__tiles_default is not None or str(name) in self.__tiles_by_name:
+                raise ValueError("camera %r has tiles configured: tiled detection does not go through the worker's frame table "
+                                 "(bind_frame_table / submit_bound); use detect() / detect_batch() for it" % (name,))
             cam = ids.get(name, -1)
             fmt0 = self.__fmt_by_cam.get(cam, self.__fmt_default) if cam >= 0 else self.__fmt_default
             latches = []
@@ -296,17 +375,64 @@ class HipObjectDetector:
 
     def submit_host(self, lane: int, images: Sequence[np.ndarray], cameras: Optional[Sequence[int]] = None) -> None:
         """Asynchronous `detect_batch`: the frames (views of shared memory, unchanged until `collect`) are enqueued on `lane`."""
+        if self.tiled:
+            raise ValueError("this detector has tiles configured: the asynchronous host path (submit_host / collect) detects untiled; "
+                             "use detect() / detect_batch()")
         self.__engine.submit_host(lane, images, cameras, self._formats(images, cameras))
 
     def collect(self, lane: int, detections: Sequence) -> None:
         """Waits for `lane` and writes its rows into the given `Detection[100]` arrays (the frame headers)."""
         self.__engine.collect(lane, detections)
 
+    def _rects(self, spec: dict, frame: np.ndarray, fmt: int):
+        """The rectangles of a frame under a `tiles` option (a grid is laid out once per frame size and format)."""
+        if "rects" in spec:
+            return spec["rects"]
+        w, h = self.__engine.frame_geometry(frame, fmt)
+        key = (id(spec), w, h, fmt & FMT_BASE_MASK)
+        rects = self.__tile_rects.get(key)
+        if rects is None:
+            cols, rows = spec["grid"]
+            rects = self.__tile_rects[key] = tile_grid(w, h, cols, rows, spec["overlap"], spec["full_frame"],
+                                                       even=(fmt & FMT_BASE_MASK) in YUV_FORMATS)
+        return rects
+
+    def _detect(self, frames, detections, cameras, passes):
+        formats = self._formats(frames, cameras)
+        specs = [self.__tiles_by_cam.get(cameras[i], self.__tiles_default) if cameras is not None else self.__tiles_default
+                 for i in range(len(frames))]
+        if not any(s is not None for s in specs):
+            return self.__engine.detect_batch(frames, detections, cameras, passes, formats)
+        pick = lambda seq, idx: None if seq is None else [seq[i] for i in idx]      # noqa: E731
+        ms = 0.0
+        plain = [i for i, s in enumerate(specs) if s is None]
+        if plain:
+            ms += self.__engine.detect_batch(pick(frames, plain), pick(detections, plain), pick(cameras, plain), pick(passes, plain),
+                                             pick(formats, plain))
+        # frames with the same thresholds share a call while their tiles fit max_batch (all the tiles of a call are one batch)
+        call, rects, used, key = [], [], 0, None
+        def flush():
+            nonlocal ms
+            if call:
+                ms += self.__engine.detect_tiled(pick(frames, call), rects, pick(detections, call), pick(cameras, call), pick(passes, call),
+                                                 pick(formats, call), iou=key[0], ios=key[1])
+        for i, s in enumerate(specs):
+            if s is None:
+                continue
+            r = self._rects(s, frames[i], formats[i] if formats is not None else FMT_RGB24)
+            if call and (used + len(r) > self.max_batch or (s["iou"], s["ios"]) != key):
+                flush()
+                call, rects, used = [], [], 0
+            key = (s["iou"], s["ios"])
+            call.append(i)
+            rects.append(r)
+            used += len(r)
+        flush()
+        return ms
+
     def detect(self, image_shape, image_np, detections: List[Detection]):
-        frames = [image_np.reshape(image_shape)]
-        return self.__engine.detect_batch(frames, [detections], formats=self._formats(frames, None))
+        return self._detect([image_np.reshape(image_shape)], [detections], None, None)
 
     def detect_batch(self, image_shapes: Sequence, images: Sequence[np.ndarray], detections: Sequence,
                      cameras: Optional[Sequence[int]] = None, passes: Optional[Sequence[np.ndarray]] = None):
-        frames = [im.reshape(sh) for sh, im in zip(image_shapes, images)]
-        return self.__engine.detect_batch(frames, detections, cameras, passes, self._formats(frames, cameras))
+        return self._detect([im.reshape(sh) for sh, im in zip(image_shapes, images)], detections, cameras, passes)

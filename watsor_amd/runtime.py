@@ -55,6 +55,40 @@ def device_name(device: int) -> str:
     return buf.value.decode()
 
 
+class Tile(C.Structure):
+    """`wz_tile_t`: a rectangle of a frame, in pixels."""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
+
+
+def tile_grid(width: int, height: int, cols: int, rows: int, overlap: float = 0.0, full_frame: bool = True, even: bool = False):
+    """The rectangles [(x0, y0, w, h), ...] of a cols x rows grid over a width x height frame, row by row.  The frame is split into cells
+    of ceil(width / cols) x ceil(height / rows) pixels (the last column / row takes what is left); every cell then grows by half of
+    `overlap` times the cell size on each side, clipped to the frame, so that neighbours share `overlap` of a tile.  even=True: origins
+    and sizes are even numbers (what NV12 / I420 tiles need, and the 4:2:2 formats in x).  full_frame=True: the whole frame is one more
+    tile, the last one -- the tile that sees the objects larger than a cell."""
+    width, height, cols, rows, overlap = int(width), int(height), int(cols), int(rows), float(overlap)
+    if width < 1 or height < 1 or cols < 1 or rows < 1:
+        raise ValueError("tile_grid: width, height, cols and rows must be positive")
+    if not 0.0 <= overlap < 1.0:
+        raise ValueError("tile_grid: overlap %r, expected 0 <= overlap < 1" % (overlap,))
+    if even:
+        width, height = width & ~1, height & ~1
+        if width < 2 or height < 2:
+            raise ValueError("tile_grid: no even rectangle fits the frame")
+
+    def spans(size, parts):
+        cell = -(-size // parts)
+        grow = int(np.ceil(overlap * cell / 2.0))
+        if even:
+            cell, grow = cell + (cell & 1), grow + (grow & 1)
+        return [(max(0, a - grow), min(size, a + cell + grow)) for a in range(0, size, cell)][:parts]
+
+    out = [(x0, y0, x1 - x0, y1 - y0) for y0, y1 in spans(height, rows) for x0, x1 in spans(width, cols)]
+    if full_frame and (0, 0, width, height) not in out:
+        out.append((0, 0, width, height))
+    return out
+
+
 class HipEngine:
     def __init__(self, engine_path: str, device: int = 0, max_batch: int = 8, max_width: int = 1920,
                  max_height: int = 1080, dev: Optional[bool] = None, schedule: Optional[str] = None):
@@ -79,6 +113,7 @@ class HipEngine:
         self.num_classes = self._lib.wz_num_classes(self._h)
         self.num_slots = self._lib.wz_num_slots(self._h)
         self.hp_blocks = self._lib.wz_hp_blocks(self._h)   # leading blocks with split (hi + lo) matrix operands
+        self.nms_iou = float(self._lib.wz_nms_iou(self._h))   # the IoU threshold of the engine's own NMS (engine file)
         self.schedule = get_schedule(dev=self.dev)
         self._dev_allocs: List[int] = []
         self._bound_arrays = {}                            # (submit_bound before any bind_frames: the engine's EINVAL, not an AttributeError)
@@ -193,6 +228,68 @@ class HipEngine:
         ms = (C.c_float * n)()
         self._ck(self._lib.wz_detect_batch_fmt(self._h, n, ptrs, ws, hs, fmtv, camv, outs, passv, ms))
         return float(ms[0])
+
+    # -- tiled detection (include/watsor_hip.h: wz_detect_tiled) ------------------------------------
+    def _tile_args(self, tiles, n: int, iou, ios):
+        """(n_tiles, pointers to the frames' wz_tile_t arrays, what keeps them alive, iou, ios) of a tiled call."""
+        if len(tiles) != n:
+            raise ValueError("tiles: one list of rectangles per frame (%d frames, %d lists)" % (n, len(tiles)))
+        counts = (C.c_int32 * n)()
+        ptrs = (C.c_void_p * n)()
+        keep = []
+        for i, rects in enumerate(tiles):
+            arr = (Tile * max(1, len(rects)))()
+            for k, r in enumerate(rects):
+                if len(r) != 4:
+                    raise ValueError("frame %d, tile %d: expected (x0, y0, w, h)" % (i, k))
+                arr[k] = Tile(*[int(v) for v in r])
+            keep.append(arr)
+            counts[i] = len(rects)
+            ptrs[i] = C.addressof(arr)
+        return counts, ptrs, keep, float(self.nms_iou if iou is None else iou), float(1.0 if ios is None else ios)
+
+    def detect_tiled(self, frames: Sequence[np.ndarray], tiles: Sequence, out_rows: Sequence, cams: Optional[Sequence[int]] = None,
+                     passes: Optional[Sequence[np.ndarray]] = None, formats: Optional[Sequence[int]] = None,
+                     iou: Optional[float] = None, ios: Optional[float] = None) -> float:
+        """`detect_batch` on rectangles of the frames: tiles[i] = [(x0, y0, w, h), ...] of frame i (`tile_grid`), all the tiles of the
+        call at most max_batch; out_rows[i] receives ONE merged list of 100 rows in frame coordinates.  iou / ios: a row is dropped when
+        a more confident row of the same label overlaps it by more than `iou` (intersection over union; None: the engine's own NMS
+        threshold) or by more than `ios` of the smaller box (None: 1.0 = off).  Returns the wall time in ms."""
+        n = len(frames)
+        ptrs = (C.c_void_p * n)()
+        ws = (C.c_int32 * n)()
+        hs = (C.c_int32 * n)()
+        outs = (C.c_void_p * n)()
+        keep = []
+        for i, f in enumerate(frames):
+            try:
+                ws[i], hs[i] = self.frame_geometry(f, formats[i] if formats is not None else FMT_RGB24)
+            except ValueError as exc:
+                raise ValueError("frame %d: %s" % (i, exc)) from None
+            if not f.flags["C_CONTIGUOUS"]:
+                f = np.ascontiguousarray(f)
+            keep.append(f)
+            ptrs[i] = f.ctypes.data
+            outs[i] = self._addr(out_rows[i])
+        counts, tptrs, tkeep, iou, ios = self._tile_args(tiles, n, iou, ios)
+        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
+        camv = (C.c_int32 * n)(*[int(c) for c in cams]) if cams is not None else None
+        passv = (C.c_void_p * n)(*[p.ctypes.data for p in passes]) if passes is not None else None
+        ms = (C.c_float * n)()
+        self._ck(self._lib.wz_detect_tiled(self._h, n, ptrs, ws, hs, fmtv, camv, counts, tptrs, iou, ios, outs, passv, ms))
+        return float(ms[0])
+
+    def submit_tiled_device(self, slot: int, d_frames: Sequence[int], widths: Sequence[int], heights: Sequence[int], tiles: Sequence,
+                            cams: Optional[Sequence[int]] = None, formats: Optional[Sequence[int]] = None,
+                            iou: Optional[float] = None, ios: Optional[float] = None) -> None:
+        """Asynchronous `detect_tiled` of frames resident in HBM on lane `slot`; `collect()` / `wait()` + `slot_rows()` hand over one
+        merged list of rows per FRAME."""
+        n = len(d_frames)
+        counts, tptrs, tkeep, iou, ios = self._tile_args(tiles, n, iou, ios)
+        camv = (C.c_int32 * n)(*cams) if cams is not None else None
+        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
+        self._ck(self._lib.wz_submit_tiled_device(self._h, slot, n, (C.c_void_p * n)(*d_frames), (C.c_int32 * n)(*widths),
+                                                  (C.c_int32 * n)(*heights), fmtv, camv, counts, tptrs, iou, ios))
 
     def submit_device(self, slot: int, d_frames: Sequence[int], widths: Sequence[int], heights: Sequence[int],
                       cams: Optional[Sequence[int]] = None, formats: Optional[Sequence[int]] = None) -> None:
@@ -431,6 +528,45 @@ class HipEngine:
             self._h, n, C.c_void_p(be.ctypes.data), C.c_void_p(lg.ctypes.data), C.c_void_p(boxes.ctypes.data),
             C.c_void_p(scores.ctypes.data), C.c_void_p(classes.ctypes.data), C.c_void_p(num.ctypes.data)))
         return boxes, scores, classes, num
+
+    def stage_crop_tile(self, frame: np.ndarray, tile, fmt: int = FMT_RGB24) -> np.ndarray:
+        """The bytes of rectangle `tile` = (x0, y0, w, h) of `frame` as the crop kernel writes them (a flat uint8 array).  The frame
+        is read where it lies: a view at an odd address reaches the kernel at an odd address."""
+        self._dev_only("stage_crop_tile()")
+        if not frame.flags["C_CONTIGUOUS"]:
+            frame = np.ascontiguousarray(frame)
+        w, h = self.frame_geometry(frame, fmt)
+        t = Tile(*[int(v) for v in tile])
+        out = np.empty(max(1, int(self._lib.wz_frame_bytes(max(t.w, 0), max(t.h, 0), int(fmt)))), np.uint8)
+        self._ck(self._lib.wz_stage_crop_tile(self._h, C.c_void_p(frame.ctypes.data), w, h, int(fmt), C.byref(t),
+                                                C.c_void_p(out.ctypes.data)))
+        return out
+
+    def stage_merge_tiles(self, width: int, height: int, tiles, tile_rows: np.ndarray, iou: float, ios: float, cam: int = -1):
+        """The merge kernel on caller-provided rows: tiles = [(x0, y0, w, h), ...], tile_rows ROW_DTYPE [len(tiles), 100] ->
+        (rows ROW_DTYPE [100], pass uint8 [100])."""
+        self._dev_only("stage_merge_tiles()")
+        n = len(tiles)
+        arr = (Tile * max(1, n))(*[Tile(*[int(v) for v in r]) for r in tiles])
+        src = np.ascontiguousarray(tile_rows, ROW_DTYPE).reshape(n, MAX_DETECTIONS)
+        rows = np.zeros(MAX_DETECTIONS, ROW_DTYPE)
+        ok = np.zeros(MAX_DETECTIONS, np.uint8)
+        self._ck(self._lib.wz_stage_merge_tiles(self._h, int(width), int(height), int(cam), n, C.byref(arr), C.c_void_p(src.ctypes.data),
+                                                  float(iou), float(ios), C.c_void_p(rows.ctypes.data), C.c_void_p(ok.ctypes.data)))
+        return rows, ok
+
+    def profile_tiled(self, d_frames: Sequence[int], widths: Sequence[int], heights: Sequence[int], tiles: Sequence,
+                      formats: Optional[Sequence[int]] = None, iou: Optional[float] = None, ios: Optional[float] = None, reps: int = 50):
+        """(ms of the crop launch alone, ms of the merge launch alone, ms of an empty bracket): HIP-event brackets on lane 0, the mean of
+        `reps` each."""
+        self._dev_only("profile_tiled()")
+        n = len(d_frames)
+        counts, tptrs, tkeep, iou, ios = self._tile_args(tiles, n, iou, ios)
+        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
+        crop, merge, empty = C.c_float(), C.c_float(), C.c_float()
+        self._ck(self._lib.wz_profile_tiled(self._h, n, (C.c_void_p * n)(*d_frames), (C.c_int32 * n)(*widths), (C.c_int32 * n)(*heights),
+                                              fmtv, counts, tptrs, iou, ios, int(reps), C.byref(crop), C.byref(merge), C.byref(empty)))
+        return float(crop.value), float(merge.value), float(empty.value)
 
     def stage_rows(self, width: int, height: int, boxes: np.ndarray, scores: np.ndarray, classes: np.ndarray):
         self._dev_only("stage_rows()")
