@@ -174,6 +174,42 @@ int wz_detect_tiled(wz_engine_t* e, int n, const uint8_t* const* frames, const i
 int wz_submit_tiled_device(wz_engine_t* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h,
                            const int* fmt, const int* cam, const int* n_tiles, const wz_tile_t* const* tiles,
                            double iou_thr, double ios_thr);      /* collected with wz_collect / wz_wait + wz_slot_rows */
+/* ---- gated tiled detection.  A fixed camera shows an unchanged picture in most tiles most of the time.  A camera
+ * whose tiles are set once (wz_set_camera_tiles) keeps, per tile and in device memory, a REFERENCE -- the sum of the lumas of every cell of
+ * WZ_GATE_CELL x WZ_GATE_CELL pixels (anchored at the tile's origin; the last column and row of cells are partial) in the picture the
+ * tile last ran on, uint16 a cell -- and the 100 rows the tile produced on that picture.  A gated call measures every tile of its frames
+ * in one launch, runs the network on the tiles that drifted and gives the merge launch of a tiled call fresh rows for those and the
+ * cached rows for the others; the result is what wz_detect_tiled defines, on those rows, in tile order, then the camera filter.
+ *   luma of a pixel   on the bytes as stored (the colour flags of the format word play no part): GRAY8 the byte; NV12 / I420 the byte of
+ *                     the luma plane -- the chroma planes are not read, a change of chroma alone is not seen; YUYV422 / UYVY422 the Y byte;
+ *                     RGB24 / BGR24 (77 R + 150 G + 29 B + 128) >> 8
+ *   changed cell      |S_now - S_ref| > pixel_thr * (pixels of the cell), in integers; a tile's activity = its number of changed cells
+ *   a tile runs iff   it has no reference (first call, after wz_reset_camera_tiles, after its layout was set), or activity >= min_cells,
+ *                     or max_age > 0 and it was skipped in the last max_age consecutive gated calls of its camera
+ * Reference and cached rows of a tile are replaced together and only when the tile runs: the cached rows always describe the picture the
+ * reference was taken from, and slow drift adds up against that picture until it crosses the threshold.  If no tile of a call runs, no
+ * crop and no batch are launched; merge and filters still run.  WZ_EINCOMPLETE is reported by the call in which the short tile RAN; a
+ * later call that reuses its rows returns WZ_OK.
+ * wz_set_camera_tiles waits for every lane, checks the rectangles as a tiled call does (inside the width x height frame of format fmt, the
+ * format's even-ness, none larger than max_width x max_height), n_tiles in 1 .. min(WZ_MAX_TILES, max_batch) (WZ_ELIMIT), pixel_thr
+ * in 0 .. 255, min_cells >= 1, max_age >= 0 (WZ_EINVAL) and allocates the camera's state; on failure the camera keeps the layout it had.
+ * A gated call is refused, with nothing enqueued, no row written and no state changed: cam NULL, a camera id of -1 or without a layout,
+ * a frame whose size or base format differs from the layout's, the same camera twice in one call, thresholds a tiled call refuses
+ * (WZ_EINVAL); the cameras' CONFIGURED tile counts summing to more than max_batch (WZ_ELIMIT) -- never the running ones: a refusal does
+ * not depend on pixels.  wz_submit_gated_device returns once the decision is made: it waits for the activity launch of its own lane and
+ * for any other lane still running a gated batch of one of its cameras; everything behind stays asynchronous and the slot is collected
+ * like any tiled slot.  wz_gate_stats: what the last gated call accepted on `slot` decided, for its n frames. */
+#define WZ_GATE_CELL 16
+typedef struct wz_tile_gate { int32_t pixel_thr, min_cells, max_age, _reserved; } wz_tile_gate_t;
+int wz_set_camera_tiles(wz_engine_t* e, int cam, int width, int height, int fmt, int n_tiles, const wz_tile_t* tiles, const wz_tile_gate_t* gate);
+int wz_reset_camera_tiles(wz_engine_t* e, int cam);   /* forget references and cached rows, keep the layout */
+int wz_clear_camera_tiles(wz_engine_t* e, int cam);
+int wz_detect_gated(wz_engine_t* e, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt, const int* cam,
+                    double iou_thr, double ios_thr, wz_detection_t* const* out, uint8_t* const* pass, float* ms);
+int wz_submit_gated_device(wz_engine_t* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
+                           const int* cam, double iou_thr, double ios_thr);
+int wz_gate_stats(wz_engine_t* e, int slot, int n, uint64_t* ran_mask /* [n], bit t: tile t ran */,
+                  int32_t* activity /* [sum of tiles]; 0 for a tile without a reference; may be NULL */);
 /* ---- the worker's frame table.  The reference worker resolves every payload to `frame_buffers[sender].frames[index]`, asks
  * the frame for a numpy view of its pixels and hands the frame header's `Detection[100]` array to the plugin
  * (watsor/detection/detector.py:102-109); pixels, size and rows of a Frame never move after the FrameBuffers are created
@@ -336,6 +372,14 @@ int wz_stage_merge_tiles(wz_engine_t* e, int w, int h, int cam, int n_tiles, con
 int wz_profile_tiled(wz_engine_t* e, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
                      const int* n_tiles, const wz_tile_t* const* tiles, double iou_thr, double ios_thr, int reps,
                      float* crop_ms, float* merge_ms, float* empty_ms);
+/* the activity kernel on one rectangle of one host frame, synchronous: sums_out[cell rows][cell columns] (uint16) and, against the grid `ref`
+ * (NULL: no reference, 0 changed), the number of changed cells */
+int wz_stage_tile_activity(wz_engine_t* e, const uint8_t* frame, int w, int h, int fmt, const wz_tile_t* tile, const uint16_t* ref, int pixel_thr,
+                           uint16_t* sums_out, int32_t* changed_out);
+/* HIP-event time (ms, mean of reps) of the activity launch alone and of the commit launch alone, as one gated call of these arguments on lane 0
+ * issued them (the call runs first, with whatever state its cameras have); empty_ms: the same bracket around nothing */
+int wz_profile_gated(wz_engine_t* e, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt, const int* cam,
+                     double iou_thr, double ios_thr, int reps, float* activity_ms, float* commit_ms, float* empty_ms);
 
 #endif /* WZ_DEV_BUILD */
 

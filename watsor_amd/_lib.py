@@ -25,6 +25,7 @@ WZ_FMT_BASE_MASK, WZ_CSP_BT709, WZ_RANGE_FULL = 0xFF, 0x100, 0x200        # ... 
 WZ_NUM_LABELS = 91
 WZ_MAX_CAMS = 256
 WZ_MAX_TILES = 64
+WZ_GATE_CELL = 16
 WZ_SCHEDULE_THROUGHPUT, WZ_SCHEDULE_LATENCY = 0, 1
 
 c_u8p = C.POINTER(C.c_uint8)
@@ -60,6 +61,14 @@ SIGNATURES = {
                                   C.POINTER(C.c_void_p), C.c_double, C.c_double, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_f32p]),
     "wz_submit_tiled_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, c_i32p,
                                          C.POINTER(C.c_void_p), C.c_double, C.c_double]),
+    "wz_set_camera_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "wz_reset_camera_tiles": (C.c_int, [C.c_void_p, C.c_int]),
+    "wz_clear_camera_tiles": (C.c_int, [C.c_void_p, C.c_int]),
+    "wz_detect_gated": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, C.c_double, C.c_double,
+                                  C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_f32p]),
+    "wz_submit_gated_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, C.c_double,
+                                         C.c_double]),
+    "wz_gate_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "wz_collect": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "wz_bind_frames": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, C.POINTER(C.c_void_p)]),
     "wz_submit_bound": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_i32p]),
@@ -121,6 +130,10 @@ DEV_SIGNATURES = {
     "wz_stage_crop_tile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "wz_profile_tiled": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, C.POINTER(C.c_void_p),
                                    C.c_double, C.c_double, C.c_int, c_f32p, c_f32p, c_f32p]),
+    "wz_stage_tile_activity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_void_p]),
+    "wz_profile_gated": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, C.c_double, C.c_double, C.c_int,
+                                   c_f32p, c_f32p, c_f32p]),
     "wz_stage_merge_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                                        C.c_void_p, C.c_void_p]),
 }

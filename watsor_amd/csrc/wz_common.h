@@ -380,3 +380,28 @@ void wz_launch_crop_tiles(const WzCropPlane* planes, int n, hipStream_t s);   //
 // max_tiles: the most tiles any of the n frames has
 void wz_launch_merge_tiles(const WzMergeFrame* frames, const int32_t* origins, const wz_detection_t* tile_rows, WzMergeCand* cands, int n,
                            int max_tiles, double iou_thr, double ios_thr, wz_detection_t* rows, uint8_t* pass, hipStream_t s);
+
+// ---- gated tiled detection (k_gate.hip): the activity launch in front of the decision, the commit launch behind the batch
+// The luma-bearing bytes of one tile: `th` runs of `row_bytes` bytes, `pitch` bytes apart, cut into cells of WZ_GATE_CELL x WZ_GATE_CELL pixels.
+#define WZ_GATE_GRAY 0   // every byte is a luma (GRAY8, the luma plane of NV12 / I420)
+#define WZ_GATE_YUYV 1   // the even bytes of a row
+#define WZ_GATE_UYVY 2   // the odd bytes
+#define WZ_GATE_RGB 3    // three bytes a pixel: (77 R + 150 G + 29 B + 128) >> 8
+#define WZ_GATE_BGR 4
+struct WzGateTile {
+    const uint8_t* src;    // the first luma-bearing byte of the rectangle's first row
+    const uint16_t* ref;   // the reference grid [crows][cols], or nullptr: the tile has none (its activity is reported as 0)
+    uint16_t* now;         // the new grid [crows][cols]
+    int32_t pitch, row_bytes, tw, th, cols, crows, mode, thr;
+};
+struct WzGateCommit {      // one tile of a gated call, in tile order
+    uint16_t* ref;         // the camera's reference grid of the tile ...
+    const uint16_t* now;   // ... and the grid the activity launch wrote
+    wz_detection_t* cache; // the camera's cached rows of the tile [100]
+    int32_t cells, fresh;  // fresh: the tile's image in the batch that ran, or -1: the tile was skipped
+};
+// tiles[n] (device-readable) -> every tile's new grid, activity[n] = cells changed against the reference; counters: int32[n][2], zero before the
+// first launch (the kernel leaves them zero); max_crows / max_cols: the most cell rows / columns any of the n tiles has
+void wz_launch_tile_activity(const WzGateTile* tiles, int n, int max_crows, int max_cols, int32_t* counters, int32_t* activity, hipStream_t s);
+// the tiles that ran: new grid -> reference, batch_rows[fresh] -> cache; every tile: fresh or cached rows -> out[t][100]
+void wz_launch_gate_commit(const WzGateCommit* tiles, int n, const wz_detection_t* batch_rows, wz_detection_t* out, hipStream_t s);

@@ -145,6 +145,15 @@ struct wz_engine {
         uint8_t* m_tpass = nullptr;
         WzMergeFrame* m_tmeta = nullptr;
         int tiled = 0;                       // frames of the tiled batch in flight (its rows are in h_trows); 0: the batch is not tiled
+        // gated tiled detection (wz_submit_gated_device / wz_detect_gated), allocated the first time the lane sees a gated call (ensure_gated):
+        uint16_t* d_gnow = nullptr;          // the activity launch's new grids [max_batch][gate_cells]
+        wz_detection_t* d_grows = nullptr;   // fresh or cached rows of every tile of the call, in tile order [max_batch][100]: what the merge reads
+        int32_t* d_gcount = nullptr;         // the activity kernel's counters [max_batch][2]
+        WzGateTile* h_gmeta = nullptr;       // pinned, device-mapped: WzGateTile[max_batch], WzGateCommit[max_batch], activity int32[max_batch]
+        WzGateTile* m_gmeta = nullptr;       // ... as the device sees it
+        std::vector<uint64_t> g_ran;         // the last gated call accepted on this lane (wz_gate_stats): per frame, bit t = tile t ran ...
+        std::vector<int32_t> g_act;          // ... and every tile's activity, in tile order
+        int g_tiles = 0, g_crows = 0, g_cols = 0;   // that call's launches: tiles, the most cell rows / columns of a tile
         hipEvent_t done = nullptr;
         int n = 0;
         bool rows = false;                       // the batch being enqueued runs the row-staged resize kernel (a frame of it is read in place)
@@ -189,6 +198,21 @@ struct wz_engine {
     std::vector<int32_t*> cam_sat;
     wz_detection_t* d_tmp_rows = nullptr;
     uint8_t* d_tmp_pass = nullptr;
+
+    // gated tiled detection: a camera's tile layout and its state in device memory (wz_set_camera_tiles); empty until a camera is set
+    struct GateCam {
+        int w = 0, h = 0, base = 0;              // the frames this layout was set for: size and base format
+        wz_tile_gate_t gate = {0, 1, 0, 0};
+        std::vector<wz_tile_t> tiles;
+        std::vector<int> cols, crows;            // cells of every tile
+        std::vector<size_t> grid_off;            // first cell of every tile's reference grid in d_ref
+        uint16_t* d_ref = nullptr;               // the tiles' reference grids, one after the other
+        wz_detection_t* d_rows = nullptr;        // the tiles' cached rows [tiles][100]
+        std::vector<uint8_t> has_ref;            // the tile has a reference (and cached rows)
+        std::vector<int> skipped;                // gated calls of this camera in a row that skipped the tile
+        int lane = -1;                           // the lane whose gated batch last wrote this state
+    };
+    std::map<int, GateCam> gate_cams;
 
     std::vector<std::string> stage_names;
 };
@@ -1231,6 +1255,10 @@ extern "C" void wz_destroy(wz_engine_t* e) {
     (void)sync_all(e);
     for (int32_t* p : e->cam_sat)
         if (p) (void)hipFree(p);
+    for (auto& kv : e->gate_cams) {
+        if (kv.second.d_ref) (void)hipFree(kv.second.d_ref);
+        if (kv.second.d_rows) (void)hipFree(kv.second.d_rows);
+    }
     void* devp[] = {e->d_weights, e->d_zeros, e->d_mbdbg, e->d_anchors, e->d_frames, e->d_cams, e->d_tmp_rows, e->d_tmp_pass};
     for (void* p : devp)
         if (p) (void)hipFree(p);
@@ -1254,6 +1282,10 @@ extern "C" void wz_destroy(wz_engine_t* e) {
         if (L.h_trows) (void)hipHostFree(L.h_trows);
         if (L.h_tpass) (void)hipHostFree(L.h_tpass);
         if (L.h_tmeta) (void)hipHostFree(L.h_tmeta);
+        if (L.d_gnow) (void)hipFree(L.d_gnow);
+        if (L.d_grows) (void)hipFree(L.d_grows);
+        if (L.d_gcount) (void)hipFree(L.d_gcount);
+        if (L.h_gmeta) (void)hipHostFree(L.h_gmeta);
         if (L.done) (void)hipEventDestroy(L.done);
         if (L.stream && L.owns_stream) (void)hipStreamDestroy(L.stream);
     }
@@ -1713,6 +1745,323 @@ extern "C" int wz_detect_tiled(wz_engine_t* e, int n, const uint8_t* const* fram
     if (ms)
         for (int i = 0; i < n; ++i) ms[i] = el;
     return rc;   // WZ_OK, or WZ_EINCOMPLETE: the merged rows are written, a tile's rows may have been short
+}
+
+// ------------------------------------------------------------------------------------------------
+// gated tiled detection: activity launch -> the host decides which tiles run -> crop + batch of those -> commit + merge (k_gate.hip,
+// DESIGN.md section 16).  Eager launches around run_batch, as tiled detection is; nothing above this line knows about it.
+// ------------------------------------------------------------------------------------------------
+typedef wz_engine::GateCam GateCam;
+static size_t gate_cells_of(int w, int h) {
+    return (size_t)((w + WZ_GATE_CELL - 1) / WZ_GATE_CELL) * (size_t)((h + WZ_GATE_CELL - 1) / WZ_GATE_CELL);
+}
+// the pinned block of a lane: the activity launch's tiles, the commit launch's tiles, the activity counts
+static WzGateCommit* gate_commits(wz_engine* e, WzGateTile* meta) { return reinterpret_cast<WzGateCommit*>(meta + e->max_batch); }
+static int32_t* gate_activity(wz_engine* e, WzGateTile* meta) { return reinterpret_cast<int32_t*>(gate_commits(e, meta) + e->max_batch); }
+
+static int ensure_gated(wz_engine* e, Lane& L) {
+    if (L.d_gnow) return WZ_OK;
+    const size_t nb = (size_t)e->max_batch, cells = gate_cells_of(e->max_w, e->max_h);
+    uint16_t* now = nullptr;
+    wz_detection_t* rows = nullptr;
+    int32_t* cnt = nullptr;
+    WzGateTile* hm = nullptr;
+    hipError_t err = hipMalloc((void**)&now, cells * 2 * nb);
+    if (err == hipSuccess) err = hipMalloc((void**)&rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS * nb);
+    if (err == hipSuccess) err = hipMalloc((void**)&cnt, 8 * nb);
+    if (err == hipSuccess) err = hipMemset(cnt, 0, 8 * nb);
+    if (err == hipSuccess) err = hipHostMalloc((void**)&hm, (sizeof(WzGateTile) + sizeof(WzGateCommit) + 4) * nb, hipHostMallocMapped);
+    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&L.m_gmeta, hm, 0);
+    if (err != hipSuccess) {
+        if (now) (void)hipFree(now);
+        if (rows) (void)hipFree(rows);
+        if (cnt) (void)hipFree(cnt);
+        if (hm) (void)hipHostFree(hm);
+        return wz_fail(WZ_EHIP, "gate scratch of a lane: %s", hipGetErrorString(err));
+    }
+    L.d_gnow = now; L.d_grows = rows; L.d_gcount = cnt; L.h_gmeta = hm;
+    return WZ_OK;
+}
+
+// What the activity kernel reads of rectangle t of a frame w pixels wide at `src`: the luma-bearing bytes of its rows
+static void gate_tile(const uint8_t* src, int w, int fmt, const wz_tile_t& t, WzGateTile& g) {
+    const int base = fmt & WZ_FMT_BASE_MASK;
+    const bool rgb = base == WZ_FMT_RGB24 || base == WZ_FMT_BGR24, yuy = base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422;
+    const int bpp = rgb ? 3 : yuy ? 2 : 1;   // (NV12 / I420: the luma plane is the frame's first w x h bytes)
+    g.src = src + ((size_t)t.y0 * (size_t)w + t.x0) * bpp;
+    g.pitch = w * bpp;
+    g.row_bytes = t.w * bpp;
+    g.tw = t.w;
+    g.th = t.h;
+    g.cols = (t.w + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
+    g.crows = (t.h + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
+    g.mode = base == WZ_FMT_RGB24 ? WZ_GATE_RGB : base == WZ_FMT_BGR24 ? WZ_GATE_BGR : base == WZ_FMT_YUYV422 ? WZ_GATE_YUYV
+             : base == WZ_FMT_UYVY422 ? WZ_GATE_UYVY : WZ_GATE_GRAY;
+}
+
+extern "C" int wz_set_camera_tiles(wz_engine_t* e, int cam, int width, int height, int fmt, int n_tiles, const wz_tile_t* tiles,
+                                   const wz_tile_gate_t* gate) {
+    if (!e || !tiles || !gate) return wz_fail(WZ_EINVAL, "wz_set_camera_tiles: null argument");
+    if (cam < 0 || cam >= WZ_MAX_CAMS) return wz_fail(WZ_ELIMIT, "camera id %d out of range [0,%d)", cam, WZ_MAX_CAMS);
+    if (!wz_frame_bytes(width, height, fmt))
+        return wz_fail(WZ_EINVAL, "camera %d: pixel format 0x%x at %dx%d: %s", cam, fmt, width, height, fmt_refusal(width, height, fmt));
+    if (n_tiles < 1 || n_tiles > WZ_MAX_TILES) return wz_fail(WZ_ELIMIT, "camera %d: %d tiles, a frame takes 1 to %d", cam, n_tiles, WZ_MAX_TILES);
+    if (n_tiles > e->max_batch) return wz_fail(WZ_ELIMIT, "camera %d: %d tiles exceed max_batch %d", cam, n_tiles, e->max_batch);
+    if (gate->pixel_thr < 0 || gate->pixel_thr > 255 || gate->min_cells < 1 || gate->max_age < 0)
+        return wz_fail(WZ_EINVAL, "camera %d: gate (%d, %d, %d): pixel_thr must be 0 .. 255, min_cells >= 1, max_age >= 0", cam, gate->pixel_thr,
+                       gate->min_cells, gate->max_age);
+    GateCam g;
+    g.w = width; g.h = height; g.base = fmt & WZ_FMT_BASE_MASK;
+    g.gate = *gate;
+    g.gate._reserved = 0;
+    size_t cells = 0;
+    for (int t = 0; t < n_tiles; ++t) {
+        const wz_tile_t& r = tiles[t];
+        const char* why = tile_refusal(r, width, height, fmt);
+        if (why) return wz_fail(WZ_EINVAL, "camera %d (%dx%d, format 0x%x), tile %d (%d, %d, %d x %d): %s", cam, width, height, fmt, t, r.x0, r.y0, r.w, r.h, why);
+        if (r.w > e->max_w || r.h > e->max_h || (size_t)r.w * r.h * 3 > e->frame_stride)
+            return wz_fail(WZ_ELIMIT, "camera %d, tile %d is %dx%d, engine was created for at most %dx%d", cam, t, r.w, r.h, e->max_w, e->max_h);
+        g.tiles.push_back(r);
+        g.cols.push_back((r.w + WZ_GATE_CELL - 1) / WZ_GATE_CELL);
+        g.crows.push_back((r.h + WZ_GATE_CELL - 1) / WZ_GATE_CELL);
+        g.grid_off.push_back(cells);
+        cells += (gate_cells_of(r.w, r.h) + 7) & ~(size_t)7;   // (every grid begins at a 16-byte boundary)
+    }
+    g.has_ref.assign(n_tiles, 0);
+    g.skipped.assign(n_tiles, 0);
+    HIPCHK(hipSetDevice(e->device));
+    { int _rc = sync_all(e); if (_rc != WZ_OK) return _rc; }
+    // the new state is allocated aside: a failure leaves the camera with the layout (and the references) it had
+    hipError_t err = hipMalloc((void**)&g.d_ref, cells * 2);
+    if (err == hipSuccess) err = hipMalloc((void**)&g.d_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS * n_tiles);
+    if (err != hipSuccess) {
+        if (g.d_ref) (void)hipFree(g.d_ref);
+        return wz_fail(WZ_EHIP, "wz_set_camera_tiles: %s (camera %d keeps its previous tiles)", hipGetErrorString(err), cam);
+    }
+    auto it = e->gate_cams.find(cam);
+    if (it != e->gate_cams.end()) {   // nothing in flight reads the old state: every lane was synchronised above
+        (void)hipFree(it->second.d_ref);
+        (void)hipFree(it->second.d_rows);
+    }
+    e->gate_cams[cam] = std::move(g);
+    return WZ_OK;
+}
+
+extern "C" int wz_reset_camera_tiles(wz_engine_t* e, int cam) {
+    if (!e) return wz_fail(WZ_EINVAL, "wz_reset_camera_tiles: null engine");
+    auto it = e->gate_cams.find(cam);
+    if (it == e->gate_cams.end()) return wz_fail(WZ_EINVAL, "camera %d has no tiles (wz_set_camera_tiles first)", cam);
+    HIPCHK(hipSetDevice(e->device));
+    { int _rc = sync_all(e); if (_rc != WZ_OK) return _rc; }
+    std::fill(it->second.has_ref.begin(), it->second.has_ref.end(), (uint8_t)0);
+    std::fill(it->second.skipped.begin(), it->second.skipped.end(), 0);
+    return WZ_OK;
+}
+
+extern "C" int wz_clear_camera_tiles(wz_engine_t* e, int cam) {
+    if (!e || cam < 0 || cam >= WZ_MAX_CAMS) return wz_fail(WZ_EINVAL, "wz_clear_camera_tiles: bad argument");
+    auto it = e->gate_cams.find(cam);
+    if (it == e->gate_cams.end()) return WZ_OK;
+    HIPCHK(hipSetDevice(e->device));
+    { int _rc = sync_all(e); if (_rc != WZ_OK) return _rc; }
+    (void)hipFree(it->second.d_ref);
+    (void)hipFree(it->second.d_rows);
+    e->gate_cams.erase(it);
+    return WZ_OK;
+}
+
+// Every refusal of a gated call (include/watsor_hip.h), before anything is enqueued, written or decided
+static int gated_check(wz_engine* e, const char* who, int slot, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt,
+                       const int* cam, double iou_thr, double ios_thr, bool host, int* total) {
+    if (!e || !frames || !w || !h) return wz_fail(WZ_EINVAL, "%s: null argument", who);
+    if (slot < 0 || slot >= e->n_lanes) return wz_fail(WZ_EINVAL, "slot %d out of range [0,%d)", slot, e->n_lanes);
+    if (n < 1 || n > e->max_batch) return wz_fail(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
+    if (!cam) return wz_fail(WZ_EINVAL, "%s: a gated call needs the frames' camera ids", who);
+    int64_t sum = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!frames[i] || w[i] < 1 || h[i] < 1) return wz_fail(WZ_EINVAL, "frame %d: bad pointer or size", i);
+        auto it = cam[i] < 0 ? e->gate_cams.end() : e->gate_cams.find(cam[i]);
+        if (it == e->gate_cams.end()) return wz_fail(WZ_EINVAL, "frame %d: camera %d has no tiles (wz_set_camera_tiles first)", i, cam[i]);
+        for (int j = 0; j < i; ++j)
+            if (cam[j] == cam[i]) return wz_fail(WZ_EINVAL, "frames %d and %d are both camera %d's: one frame of a camera per gated call", j, i, cam[i]);
+        const GateCam& g = it->second;
+        const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
+        if (!wz_frame_bytes(w[i], h[i], pf))
+            return wz_fail(WZ_EINVAL, "frame %d: pixel format 0x%x at %dx%d: %s", i, pf, w[i], h[i], fmt_refusal(w[i], h[i], pf));
+        if (w[i] != g.w || h[i] != g.h || (pf & WZ_FMT_BASE_MASK) != g.base)
+            return wz_fail(WZ_EINVAL, "frame %d is %dx%d in base format %d but camera %d's tiles were set for %dx%d in base format %d", i, w[i], h[i],
+                           pf & WZ_FMT_BASE_MASK, cam[i], g.w, g.h, g.base);
+        if (host && (w[i] > e->max_w || h[i] > e->max_h || (size_t)w[i] * h[i] * 3 > e->frame_stride))
+            return wz_fail(WZ_ELIMIT, "frame %d is %dx%d, engine was created for at most %dx%d", i, w[i], h[i], e->max_w, e->max_h);
+        if (e->h_cams[cam[i]].enabled && (e->h_cams[cam[i]].width != w[i] || e->h_cams[cam[i]].height != h[i]))
+            return wz_fail(WZ_EINVAL, "frame %d is %dx%d but camera %d filter was set for %dx%d", i, w[i], h[i], cam[i],
+                           e->h_cams[cam[i]].width, e->h_cams[cam[i]].height);
+        sum += (int64_t)g.tiles.size();
+    }
+    if (sum > e->max_batch) return wz_fail(WZ_ELIMIT, "the %lld tiles configured for the cameras of one call exceed max_batch %d", (long long)sum, e->max_batch);
+    if (!(iou_thr >= 0.0) || !(ios_thr >= 0.0)) return wz_fail(WZ_EINVAL, "%s: the merge thresholds must be numbers >= 0", who);
+    *total = (int)sum;
+    return WZ_OK;
+}
+
+// The host's rule: does tile t of camera g run, given its activity?
+static bool gate_runs(const GateCam& g, int t, int activity) {
+    return !g.has_ref[t] || activity >= g.gate.min_cells || (g.gate.max_age > 0 && g.skipped[t] >= g.gate.max_age);
+}
+
+// A checked gated call on a drained lane, frames in device memory.  Returns once the decision is made; crop, batch, commit, merge and
+// filters are enqueued behind it and the lane's event behind them.
+static int gated_enqueue(wz_engine* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
+                         const int* cam, double iou_thr, double ios_thr, int total) {
+    Lane& L = e->lanes[slot];
+    int rc = ensure_tiled(e, L);
+    if (rc == WZ_OK) rc = ensure_gated(e, L);
+    if (rc != WZ_OK) return rc;
+    std::vector<GateCam*> cams(n);
+    for (int i = 0; i < n; ++i) {
+        cams[i] = &e->gate_cams.find(cam[i])->second;
+        // another lane's commit launch may still be writing this camera's references and cached rows
+        if (cams[i]->lane >= 0 && cams[i]->lane != slot) HIPCHK(hipEventSynchronize(e->lanes[cams[i]->lane].done));
+    }
+    // 1. activity of every tile, one launch
+    const size_t lane_cells = gate_cells_of(e->max_w, e->max_h);
+    WzGateCommit* commits = gate_commits(e, L.h_gmeta);
+    int32_t* act = gate_activity(e, L.h_gmeta);
+    int k = 0, crows = 0, cols = 0;
+    for (int i = 0; i < n; ++i) {
+        GateCam& g = *cams[i];
+        const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
+        for (size_t t = 0; t < g.tiles.size(); ++t, ++k) {
+            WzGateTile& d = L.h_gmeta[k];
+            gate_tile(d_frames[i], w[i], pf, g.tiles[t], d);
+            d.ref = g.has_ref[t] ? g.d_ref + g.grid_off[t] : nullptr;
+            d.now = L.d_gnow + lane_cells * k;
+            d.thr = g.gate.pixel_thr;
+            crows = std::max(crows, d.crows);
+            cols = std::max(cols, d.cols);
+            act[k] = 0;
+        }
+    }
+    wz_launch_tile_activity(L.m_gmeta, total, crows, cols, L.d_gcount, gate_activity(e, L.m_gmeta), L.stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(L.stream));   // the batch size is a host-side quantity: the decision waits for the counts
+    // 2. the decision; the cameras' state changes only once everything is enqueued
+    std::vector<uint8_t> runs(total);
+    std::vector<WzCropPlane> planes;
+    std::vector<const uint8_t*> tptr;
+    std::vector<int> tw, th, tf;
+    int32_t* origins = reinterpret_cast<int32_t*>(L.h_tmeta + e->max_batch);
+    int most = 0;
+    k = 0;
+    for (int i = 0; i < n; ++i) {
+        GateCam& g = *cams[i];
+        const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
+        const int nt = (int)g.tiles.size();
+        L.h_tmeta[i] = {k, nt, cam[i], 0};
+        most = std::max(most, nt);
+        for (int t = 0; t < nt; ++t, ++k) {
+            const wz_tile_t& r = g.tiles[t];
+            runs[k] = gate_runs(g, t, act[k]) ? 1 : 0;
+            commits[k].ref = g.d_ref + g.grid_off[t];
+            commits[k].now = L.h_gmeta[k].now;
+            commits[k].cache = g.d_rows + (size_t)t * WZ_MAX_DETECTIONS;
+            commits[k].cells = L.h_gmeta[k].cols * L.h_gmeta[k].crows;
+            commits[k].fresh = -1;
+            if (runs[k]) {
+                commits[k].fresh = (int)tptr.size();
+                uint8_t* dst = L.d_tiles + e->frame_stride * tptr.size();
+                tile_planes(d_frames[i], w[i], h[i], pf, r, dst, planes);
+                tptr.push_back(dst); tw.push_back(r.w); th.push_back(r.h); tf.push_back(pf);
+            }
+            origins[2 * k] = r.x0;
+            origins[2 * k + 1] = r.y0;
+        }
+    }
+    // 3. the tiles that run, as an ordinary batch without cameras (none: no crop, no batch)
+    const int running = (int)tptr.size();
+    if (running) {
+        wz_launch_crop_tiles(planes.data(), (int)planes.size(), L.stream);
+        rc = fill_desc(e, slot, running, tptr.data(), tw.data(), th.data(), tf.data(), nullptr);
+        if (rc != WZ_OK) return rc;
+        L.rows = e->pre_rows;
+        rc = run_batch(e, slot, running);
+        if (rc != WZ_OK) return rc;
+    } else {
+        L.bound_idx.clear();
+        L.n = 0;   // (no tile ran: no status word is this call's)
+    }
+    // 4. commit, merge, filters
+    wz_launch_gate_commit(gate_commits(e, L.m_gmeta), total, L.m_rows, L.d_grows, L.stream);
+    const int32_t* m_origins = reinterpret_cast<const int32_t*>(L.m_tmeta + e->max_batch);
+    wz_launch_merge_tiles(L.m_tmeta, m_origins, L.d_grows, L.d_tcand, n, most, iou_thr, ios_thr, L.m_trows, L.m_tpass, L.stream);
+    for (int i = 0; i < n; ++i)
+        if (e->h_cams[cam[i]].enabled)
+            wz_launch_filter_rows(e->d_cams, cam[i], L.m_trows + (size_t)i * WZ_MAX_DETECTIONS, L.m_tpass + (size_t)i * WZ_MAX_DETECTIONS, L.stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(L.done, L.stream));
+    L.tiled = n;
+    // 5. the state the commit launch leaves behind, and what wz_gate_stats reports
+    L.g_ran.assign(n, 0);
+    L.g_act.assign(act, act + total);
+    L.g_tiles = total; L.g_crows = crows; L.g_cols = cols;
+    k = 0;
+    for (int i = 0; i < n; ++i) {
+        GateCam& g = *cams[i];
+        g.lane = slot;
+        for (size_t t = 0; t < g.tiles.size(); ++t, ++k) {
+            if (runs[k]) {
+                g.has_ref[t] = 1;
+                g.skipped[t] = 0;
+                L.g_ran[i] |= 1ull << t;
+            } else {
+                ++g.skipped[t];
+            }
+        }
+    }
+    return WZ_OK;
+}
+
+extern "C" int wz_submit_gated_device(wz_engine_t* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
+                                      const int* cam, double iou_thr, double ios_thr) {
+    int total = 0;
+    int rc = gated_check(e, "wz_submit_gated_device", slot, n, d_frames, w, h, fmt, cam, iou_thr, ios_thr, false, &total);
+    if (rc != WZ_OK) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipEventSynchronize(e->lanes[slot].done));   // the lane's previous batch has fully drained
+    return gated_enqueue(e, slot, n, d_frames, w, h, fmt, cam, iou_thr, ios_thr, total);
+}
+
+extern "C" int wz_detect_gated(wz_engine_t* e, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt, const int* cam,
+                               double iou_thr, double ios_thr, wz_detection_t* const* out, uint8_t* const* pass, float* ms) {
+    int total = 0;
+    int rc = gated_check(e, "wz_detect_gated", 0, n, frames, w, h, fmt, cam, iou_thr, ios_thr, true, &total);
+    if (rc != WZ_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(e->device));
+    Lane& L = e->lanes[0];
+    HIPCHK(hipEventSynchronize(L.done));
+    std::vector<const uint8_t*> dptr(n);
+    for (int i = 0; i < n; ++i) {   // the whole frame into the lane's staging area, as wz_detect_tiled stages it
+        rc = stage_frame(e, L, i, frames[i], wz_frame_bytes(w[i], h[i], fmt ? fmt[i] : WZ_FMT_RGB24), &dptr[i]);
+        if (rc != WZ_OK) return rc;
+    }
+    rc = gated_enqueue(e, 0, n, dptr.data(), w, h, fmt, cam, iou_thr, ios_thr, total);
+    if (rc != WZ_OK) return rc;
+    rc = wz_collect(e, 0, out, pass);
+    if (rc != WZ_OK && rc != WZ_EINCOMPLETE) return rc;
+    const float el = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (ms)
+        for (int i = 0; i < n; ++i) ms[i] = el;
+    return rc;   // WZ_OK, or WZ_EINCOMPLETE: the merged rows are written, the rows of a tile that ran in this call may have been short
+}
+
+extern "C" int wz_gate_stats(wz_engine_t* e, int slot, int n, uint64_t* ran_mask, int32_t* activity) {
+    if (!e || !ran_mask || slot < 0 || slot >= e->n_lanes) return wz_fail(WZ_EINVAL, "wz_gate_stats: bad argument");
+    const Lane& L = e->lanes[slot];
+    if (n < 1 || n != (int)L.g_ran.size()) return wz_fail(WZ_EINVAL, "wz_gate_stats: the last gated call on lane %d had %d frames, not %d", slot, (int)L.g_ran.size(), n);
+    memcpy(ran_mask, L.g_ran.data(), sizeof(uint64_t) * n);
+    if (activity) memcpy(activity, L.g_act.data(), sizeof(int32_t) * L.g_act.size());
+    return WZ_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2264,6 +2613,81 @@ extern "C" int wz_profile_tiled(wz_engine_t* e, int n, const uint8_t* const* d_f
     (void)hipEventDestroy(b);
     *crop_ms = (float)(sum[0] / reps);
     *merge_ms = (float)(sum[1] / reps);
+    *empty_ms = (float)(sum[2] / reps);
+    return WZ_OK;
+}
+// wz_k_tile_activity on one rectangle of one host frame; the device copy of the frame starts at the host pointer's offset within 16 bytes
+extern "C" int wz_stage_tile_activity(wz_engine_t* e, const uint8_t* frame, int w, int h, int fmt, const wz_tile_t* tile, const uint16_t* ref,
+                                      int pixel_thr, uint16_t* sums_out, int32_t* changed_out) {
+    if (!e || !frame || !tile || !sums_out || !changed_out) return wz_fail(WZ_EINVAL, "wz_stage_tile_activity: null argument");
+    const uint64_t bytes = wz_frame_bytes(w, h, fmt);
+    if (!bytes) return wz_fail(WZ_EINVAL, "pixel format 0x%x at %dx%d: %s", fmt, w, h, fmt_refusal(w, h, fmt));
+    const char* why = tile_refusal(*tile, w, h, fmt);
+    if (why) return wz_fail(WZ_EINVAL, "tile (%d, %d, %d x %d) of a %dx%d frame: %s", tile->x0, tile->y0, tile->w, tile->h, w, h, why);
+    if (pixel_thr < 0 || pixel_thr > 255) return wz_fail(WZ_EINVAL, "pixel_thr %d, expected 0 .. 255", pixel_thr);
+    if (bytes >> 31) return wz_fail(WZ_ELIMIT, "frame too large");
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const size_t cells = gate_cells_of(tile->w, tile->h), skew = reinterpret_cast<uintptr_t>(frame) & 15u;
+    const size_t off_ref = (cells * 2 + 15) & ~(size_t)15, off_desc = 2 * off_ref, off_cnt = off_desc + 64, all = off_cnt + 16;
+    uint8_t* d_src = nullptr;
+    uint8_t* d = nullptr;   // new grid, reference grid, the tile's descriptor, the counters and the count
+    hipError_t err = hipMalloc((void**)&d_src, bytes + 16);
+    if (err == hipSuccess) err = hipMalloc((void**)&d, all);
+    if (err == hipSuccess) err = hipMemset(d, 0, all);
+    if (err == hipSuccess) err = hipMemcpy(d_src + skew, frame, bytes, hipMemcpyHostToDevice);
+    if (err == hipSuccess && ref) err = hipMemcpy(d + off_ref, ref, cells * 2, hipMemcpyHostToDevice);
+    if (err == hipSuccess) {
+        static_assert(sizeof(WzGateTile) <= 64, "the descriptor's slot");
+        WzGateTile g;
+        gate_tile(d_src + skew, w, fmt, *tile, g);
+        g.ref = ref ? reinterpret_cast<const uint16_t*>(d + off_ref) : nullptr;
+        g.now = reinterpret_cast<uint16_t*>(d);
+        g.thr = pixel_thr;
+        err = hipMemcpy(d + off_desc, &g, sizeof(g), hipMemcpyHostToDevice);
+        if (err == hipSuccess) {
+            int32_t* cnt = reinterpret_cast<int32_t*>(d + off_cnt);
+            wz_launch_tile_activity(reinterpret_cast<const WzGateTile*>(d + off_desc), 1, g.crows, g.cols, cnt, cnt + 2, e->stream);
+            err = hipStreamSynchronize(e->stream);
+        }
+    }
+    if (err == hipSuccess) err = hipMemcpy(sums_out, d, cells * 2, hipMemcpyDeviceToHost);
+    if (err == hipSuccess) err = hipMemcpy(changed_out, d + off_cnt + 8, 4, hipMemcpyDeviceToHost);
+    if (d_src) (void)hipFree(d_src);
+    if (d) (void)hipFree(d);
+    if (err != hipSuccess) return wz_fail(WZ_EHIP, "wz_stage_tile_activity: %s", hipGetErrorString(err));
+    return WZ_OK;
+}
+
+// HIP-event time of the activity launch alone and of the commit launch alone, exactly as one gated call of these arguments on lane 0 issued
+// them (their descriptors are still in the lane's block; both launches leave what they wrote the first time): the mean of `reps` brackets
+extern "C" int wz_profile_gated(wz_engine_t* e, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt, const int* cam,
+                                double iou_thr, double ios_thr, int reps, float* activity_ms, float* commit_ms, float* empty_ms) {
+    if (reps < 1 || !activity_ms || !commit_ms || !empty_ms) return wz_fail(WZ_EINVAL, "wz_profile_gated: bad argument");
+    int rc = wz_submit_gated_device(e, 0, n, d_frames, w, h, fmt, cam, iou_thr, ios_thr);
+    if (rc != WZ_OK) return rc;
+    rc = wz_wait(e, 0);
+    if (rc != WZ_OK) return rc;
+    Lane& L = e->lanes[0];
+    hipEvent_t a, b;
+    HIPCHK(hipEventCreate(&a));
+    HIPCHK(hipEventCreate(&b));
+    double sum[3] = {0.0, 0.0, 0.0};
+    for (int which = 0; which < 3; ++which)
+        for (int r = 0; r < reps + 3; ++r) {   // (three unmeasured launches first)
+            HIPCHK(hipEventRecord(a, L.stream));
+            if (which == 0) wz_launch_tile_activity(L.m_gmeta, L.g_tiles, L.g_crows, L.g_cols, L.d_gcount, gate_activity(e, L.m_gmeta), L.stream);
+            else if (which == 1) wz_launch_gate_commit(gate_commits(e, L.m_gmeta), L.g_tiles, L.m_rows, L.d_grows, L.stream);
+            HIPCHK(hipEventRecord(b, L.stream));
+            HIPCHK(hipEventSynchronize(b));
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, a, b));
+            if (r >= 3) sum[which] += ms;
+        }
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+    *activity_ms = (float)(sum[0] / reps);
+    *commit_ms = (float)(sum[1] / reps);
     *empty_ms = (float)(sum[2] / reps);
     return WZ_OK;
 }

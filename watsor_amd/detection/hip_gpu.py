@@ -93,12 +93,15 @@ def frame_formats(frames: Sequence[np.ndarray], cameras: Optional[Sequence[int]]
     return out if any(f != FMT_RGB24 for f in out) else None
 
 
-_TILE_KEYS = {"grid", "overlap", "full_frame", "iou", "ios", "rects"}
+_TILE_KEYS = {"grid", "overlap", "full_frame", "iou", "ios", "rects", "gate"}
+_GATE_KEYS = {"threshold", "min_cells", "max_age"}
 
 
 def _tile_spec(spec, where: str) -> dict:
     """One checked `tiles` option: {"grid": [cols, rows], "overlap": 0.2, "full_frame": True, "iou": ..., "ios": ...} or
-    {"rects": [[x0, y0, w, h], ...], "iou": ..., "ios": ...}.  Anything else raises ValueError."""
+    {"rects": [[x0, y0, w, h], ...], "iou": ..., "ios": ...}, either with "gate": {"threshold": 0 .. 255, "min_cells": >= 1 (default 1),
+    "max_age": >= 0 (default 0)} -- run a tile only where its picture changed (`HipEngine.set_camera_tiles`).  Anything else raises
+    ValueError."""
     if not isinstance(spec, dict) or ("grid" in spec) == ("rects" in spec):
         raise ValueError("%s: expected {\"grid\": [cols, rows], ...} or {\"rects\": [[x0, y0, w, h], ...]}, got %r" % (where, spec))
     if set(spec) - _TILE_KEYS:
@@ -132,6 +135,22 @@ def _tile_spec(spec, where: str) -> dict:
         out.update(rects=[tuple(t) for t in r], count=len(r))
     if out["count"] > WZ_MAX_TILES:
         raise ValueError("%s: %d tiles, a frame takes at most %d" % (where, out["count"], WZ_MAX_TILES))
+    if "gate" in spec:
+        g = spec["gate"]
+        if not isinstance(g, dict) or "threshold" not in g:
+            raise ValueError("%s: gate %r, expected {\"threshold\": 0 .. 255, \"min_cells\": >= 1, \"max_age\": >= 0}" % (where, g))
+        if set(g) - _GATE_KEYS:
+            raise ValueError("%s: gate: unknown key(s) %s" % (where, ", ".join(sorted(map(str, set(g) - _GATE_KEYS)))))
+        gate = (g["threshold"], g.get("min_cells", 1), g.get("max_age", 0))
+        if not all(whole(v) for v in gate):
+            raise ValueError("%s: gate %r, expected whole numbers" % (where, g))
+        if not 0 <= gate[0] <= 255:
+            raise ValueError("%s: gate: threshold %r, expected 0 .. 255" % (where, gate[0]))
+        if gate[1] < 1:
+            raise ValueError("%s: gate: min_cells %r, expected >= 1" % (where, gate[1]))
+        if gate[2] < 0:
+            raise ValueError("%s: gate: max_age %r, expected >= 0" % (where, gate[2]))
+        out["gate"] = gate
     return out
 
 
@@ -169,7 +188,11 @@ class HipObjectDetector:
         "ios": a row goes when a more confident row of its label overlaps it by more than `iou` (intersection over union, default: the
         engine's NMS threshold) or by more than `ios` of the smaller box (default 1.0: off; 0.5 - 0.7 merges an object cut by a tile's
         border with its whole box) -- or explicit {"rects": [[x0, y0, w, h], ...]}, or {camera name: one of these}.  The tiles of one
-        frame must fit max_batch; `detect_batch` cuts a batch into as many calls as its tiles need.  The batched worker's frame table
+        frame must fit max_batch; `detect_batch` cuts a batch into as many calls as its tiles need.  With "gate": {"threshold": 0 .. 255,
+        "min_cells": 1, "max_age": 0} in a description, a frame that comes with a camera id runs only the tiles whose picture changed
+        since they last ran (include/watsor_hip.h: wz_detect_gated; the luma sum of a 16 x 16 cell must move by more than `threshold`
+        per pixel, in `min_cells` cells; `max_age` > 0 runs a tile after that many skipped calls whatever it shows) and reuses the
+        other tiles' rows; a frame without a camera id runs every tile as before.  The batched worker's frame table
         has no tiled form: `bind_frame_table` raises for a camera with tiles.
         `options["schedule"]`: "latency" | "throughput" | "auto" (default) -- the launch shapes of this detector PROCESS
         (include/watsor_hip.h: wz_set_schedule).  "latency" makes a lone batch finish soonest -- the reference's normal load is one
@@ -214,6 +237,7 @@ class HipObjectDetector:
         self.__tiles_default, self.__tiles_by_name = tile_options(options)
         self.__tiles_by_cam = {}
         self.__tile_rects = {}
+        self.__gate_layouts = {}        # camera id -> what its tiles were last set for: (width, height, base format, rectangles, gate)
         for where, spec in [("tiles", self.__tiles_default)] + [("tiles[%r]" % n, t) for n, t in self.__tiles_by_name.items()]:
             if spec is not None and spec["count"] > max_batch:
                 raise ValueError("%s: %d tiles per frame exceed max_batch %d" % (where, spec["count"], max_batch))
@@ -287,7 +311,8 @@ class HipObjectDetector:
         from ..filter.hip_filter import HipCameraFilter
         from .._lib import WZ_MAX_CAMS
         names = sorted(frame_buffers, key=str)
-        need = [n for n in names if n in (camera_configs or {}) or str(n) in self.__fmt_by_name or str(n) in self.__tiles_by_name]
+        gate_all = self.__tiles_default is not None and "gate" in self.__tiles_default      # (a gate keeps state per camera: every camera needs an id)
+        need = [n for n in names if gate_all or n in (camera_configs or {}) or str(n) in self.__fmt_by_name or str(n) in self.__tiles_by_name]
         if len(need) > WZ_MAX_CAMS:
             raise ValueError("%d cameras with GPU filters / pixel formats of their own on one detector: the engine has %d slots"
                              % (len(need), WZ_MAX_CAMS))
@@ -409,26 +434,43 @@ class HipObjectDetector:
         if plain:
             ms += self.__engine.detect_batch(pick(frames, plain), pick(detections, plain), pick(cameras, plain), pick(passes, plain),
                                              pick(formats, plain))
-        # frames with the same thresholds share a call while their tiles fit max_batch (all the tiles of a call are one batch)
+        # frames with the same thresholds share a call while their tiles fit max_batch (all the tiles of a call are one batch); frames of a
+        # gated description that come with a camera id go through detect_gated, one frame per camera and call
         call, rects, used, key = [], [], 0, None
         def flush():
             nonlocal ms
-            if call:
+            if call and key[2]:
+                ms += self.__engine.detect_gated(pick(frames, call), pick(cameras, call), pick(detections, call), pick(passes, call),
+                                                 pick(formats, call), iou=key[0], ios=key[1])
+            elif call:
                 ms += self.__engine.detect_tiled(pick(frames, call), rects, pick(detections, call), pick(cameras, call), pick(passes, call),
                                                  pick(formats, call), iou=key[0], ios=key[1])
         for i, s in enumerate(specs):
             if s is None:
                 continue
-            r = self._rects(s, frames[i], formats[i] if formats is not None else FMT_RGB24)
-            if call and (used + len(r) > self.max_batch or (s["iou"], s["ios"]) != key):
+            fmt = formats[i] if formats is not None else FMT_RGB24
+            r = self._rects(s, frames[i], fmt)
+            gated = "gate" in s and cameras is not None and cameras[i] >= 0
+            k = (s["iou"], s["ios"], gated)
+            if call and (used + len(r) > self.max_batch or k != key or (gated and cameras[i] in [cameras[j] for j in call])):
                 flush()
                 call, rects, used = [], [], 0
-            key = (s["iou"], s["ios"])
+            if gated:
+                self._gate_layout(cameras[i], frames[i], fmt, r, s["gate"])
+            key = k
             call.append(i)
             rects.append(r)
             used += len(r)
         flush()
         return ms
+
+    def _gate_layout(self, cam: int, frame: np.ndarray, fmt: int, rects, gate) -> None:
+        """Camera `cam`'s tiles in the engine: set the first time a frame of it is seen, and again when its size, format or tiles change."""
+        w, h = self.__engine.frame_geometry(frame, fmt)
+        layout = (w, h, fmt & FMT_BASE_MASK, tuple(rects), gate)
+        if self.__gate_layouts.get(cam) != layout:
+            self.__engine.set_camera_tiles(cam, w, h, rects, gate[0], gate[1], gate[2], fmt)
+            self.__gate_layouts[cam] = layout
 
     def detect(self, image_shape, image_np, detections: List[Detection]):
         return self._detect([image_np.reshape(image_shape)], [detections], None, None)

@@ -116,6 +116,8 @@ class HipEngine:
         self.nms_iou = float(self._lib.wz_nms_iou(self._h))   # the IoU threshold of the engine's own NMS (engine file)
         self.schedule = get_schedule(dev=self.dev)
         self._dev_allocs: List[int] = []
+        self._gate_tiles = {}                              # camera id -> tiles of its layout (set_camera_tiles)
+        self._gate_last = {}                               # lane -> the camera ids of the last gated call accepted on it
         self._bound_arrays = {}                            # (submit_bound before any bind_frames: the engine's EINVAL, not an AttributeError)
 
     def _ck(self, rc: int, what: str = "") -> None:
@@ -290,6 +292,82 @@ class HipEngine:
         fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
         self._ck(self._lib.wz_submit_tiled_device(self._h, slot, n, (C.c_void_p * n)(*d_frames), (C.c_int32 * n)(*widths),
                                                   (C.c_int32 * n)(*heights), fmtv, camv, counts, tptrs, iou, ios))
+
+    # -- gated tiled detection (include/watsor_hip.h: wz_set_camera_tiles / wz_detect_gated) ----------------
+    def set_camera_tiles(self, cam: int, width: int, height: int, tiles, threshold: int, min_cells: int = 1, max_age: int = 0,
+                         fmt: int = FMT_RGB24) -> None:
+        """The tile layout of camera `cam` for width x height frames of format `fmt`, and its gate: a cell of 16 x 16 pixels has
+        changed when its luma sum moved by more than `threshold` (0 .. 255) per pixel, a tile runs when at least `min_cells` cells
+        changed, when it has no reference yet, or -- max_age > 0 -- after `max_age` gated calls in a row that skipped it.  Waits for
+        every lane; the camera starts without references (its next gated call runs every tile)."""
+        arr = (Tile * max(1, len(tiles)))(*[Tile(*[int(v) for v in r]) for r in tiles])
+        gate = (C.c_int32 * 4)(int(threshold), int(min_cells), int(max_age), 0)
+        self._ck(self._lib.wz_set_camera_tiles(self._h, int(cam), int(width), int(height), int(fmt), len(tiles), C.byref(arr), C.byref(gate)))
+        self._gate_tiles[int(cam)] = len(tiles)
+
+    def reset_camera_tiles(self, cam: int) -> None:
+        """Forget the references and cached rows of camera `cam` (its next gated call runs every tile); the layout stays."""
+        self._ck(self._lib.wz_reset_camera_tiles(self._h, int(cam)))
+
+    def clear_camera_tiles(self, cam: int) -> None:
+        self._ck(self._lib.wz_clear_camera_tiles(self._h, int(cam)))
+        self._gate_tiles.pop(int(cam), None)
+
+    def detect_gated(self, frames: Sequence[np.ndarray], cams: Sequence[int], out_rows: Sequence,
+                     passes: Optional[Sequence[np.ndarray]] = None, formats: Optional[Sequence[int]] = None,
+                     iou: Optional[float] = None, ios: Optional[float] = None) -> float:
+        """`detect_tiled` with the tiles `set_camera_tiles` gave the frames' cameras, run only where the picture changed: a tile that
+        did not drift from the picture it last ran on contributes the rows it produced then.  One frame per camera and call; the
+        cameras' configured tiles together at most max_batch.  Returns the wall time in ms; `gate_stats()` tells which tiles ran."""
+        n = len(frames)
+        ptrs = (C.c_void_p * n)()
+        ws = (C.c_int32 * n)()
+        hs = (C.c_int32 * n)()
+        outs = (C.c_void_p * n)()
+        keep = []
+        for i, f in enumerate(frames):
+            try:
+                ws[i], hs[i] = self.frame_geometry(f, formats[i] if formats is not None else FMT_RGB24)
+            except ValueError as exc:
+                raise ValueError("frame %d: %s" % (i, exc)) from None
+            if not f.flags["C_CONTIGUOUS"]:
+                f = np.ascontiguousarray(f)
+            keep.append(f)
+            ptrs[i] = f.ctypes.data
+            outs[i] = self._addr(out_rows[i])
+        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
+        camv = (C.c_int32 * n)(*[int(c) for c in cams])
+        passv = (C.c_void_p * n)(*[p.ctypes.data for p in passes]) if passes is not None else None
+        ms = (C.c_float * n)()
+        self._ck(self._lib.wz_detect_gated(self._h, n, ptrs, ws, hs, fmtv, camv, float(self.nms_iou if iou is None else iou),
+                                           float(1.0 if ios is None else ios), outs, passv, ms))
+        self._gate_last[0] = [int(c) for c in cams]
+        return float(ms[0])
+
+    def submit_gated_device(self, slot: int, d_frames: Sequence[int], widths: Sequence[int], heights: Sequence[int], cams: Sequence[int],
+                            formats: Optional[Sequence[int]] = None, iou: Optional[float] = None, ios: Optional[float] = None) -> None:
+        """`detect_gated` of frames resident in HBM on lane `slot`.  Returns once the engine has decided which tiles run (it waits for
+        the activity launch); the batch behind is asynchronous and collected like a tiled slot's."""
+        n = len(d_frames)
+        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
+        self._ck(self._lib.wz_submit_gated_device(self._h, slot, n, (C.c_void_p * n)(*d_frames), (C.c_int32 * n)(*widths), (C.c_int32 * n)(*heights),
+                                                  fmtv, (C.c_int32 * n)(*[int(c) for c in cams]), float(self.nms_iou if iou is None else iou),
+                                                  float(1.0 if ios is None else ios)))
+        self._gate_last[slot] = [int(c) for c in cams]
+
+    def gate_stats(self, slot: int = 0):
+        """What the last gated call accepted on lane `slot` decided: ([per frame: bit t set = tile t ran], [per frame: the tiles'
+        activity = changed cells, 0 for a tile that had no reference])."""
+        cams = self._gate_last.get(slot)
+        if not cams:
+            raise ValueError("no gated call was made on lane %d" % slot)
+        n = len(cams)
+        counts = [self._gate_tiles[c] for c in cams]
+        ran = (C.c_uint64 * n)()
+        act = (C.c_int32 * max(1, sum(counts)))()
+        self._ck(self._lib.wz_gate_stats(self._h, slot, n, C.byref(ran), C.byref(act)))
+        flat = np.array(act[:sum(counts)], np.int32)
+        return [int(m) for m in ran], [a.copy() for a in np.split(flat, np.cumsum(counts)[:-1])]
 
     def submit_device(self, slot: int, d_frames: Sequence[int], widths: Sequence[int], heights: Sequence[int],
                       cams: Optional[Sequence[int]] = None, formats: Optional[Sequence[int]] = None) -> None:
@@ -541,6 +619,41 @@ class HipEngine:
         self._ck(self._lib.wz_stage_crop_tile(self._h, C.c_void_p(frame.ctypes.data), w, h, int(fmt), C.byref(t),
                                                 C.c_void_p(out.ctypes.data)))
         return out
+
+    def stage_tile_activity(self, frame: np.ndarray, tile, fmt: int = FMT_RGB24, ref: Optional[np.ndarray] = None, pixel_thr: int = 0):
+        """The activity kernel on rectangle `tile` = (x0, y0, w, h) of `frame`: (luma sums of its 16 x 16 cells, uint16 [cell rows, cell
+        columns]; the number of cells that moved by more than pixel_thr a pixel against the grid `ref`, 0 without one).  The frame is
+        read where it lies: a view at an odd address reaches the kernel at an odd address."""
+        self._dev_only("stage_tile_activity()")
+        if not frame.flags["C_CONTIGUOUS"]:
+            frame = np.ascontiguousarray(frame)
+        w, h = self.frame_geometry(frame, fmt)
+        t = Tile(*[int(v) for v in tile])
+        shape = (max(1, -(-t.h // _lib.WZ_GATE_CELL)), max(1, -(-t.w // _lib.WZ_GATE_CELL)))
+        sums = np.zeros(shape, np.uint16)
+        changed = C.c_int32(-1)
+        if ref is not None:
+            ref = np.ascontiguousarray(ref, np.uint16)
+            if ref.shape != shape:
+                raise ValueError("ref: expected a uint16 grid of shape %r, got %r" % (shape, ref.shape))
+        self._ck(self._lib.wz_stage_tile_activity(self._h, C.c_void_p(frame.ctypes.data), w, h, int(fmt), C.byref(t),
+                                                  C.c_void_p(ref.ctypes.data) if ref is not None else None, int(pixel_thr),
+                                                  C.c_void_p(sums.ctypes.data), C.byref(changed)))
+        return sums, int(changed.value)
+
+    def profile_gated(self, d_frames: Sequence[int], widths: Sequence[int], heights: Sequence[int], cams: Sequence[int],
+                      formats: Optional[Sequence[int]] = None, iou: Optional[float] = None, ios: Optional[float] = None, reps: int = 50):
+        """(ms of the activity launch alone, ms of the commit launch alone, ms of an empty bracket) of one gated call on lane 0: HIP-event
+        brackets, the mean of `reps` each."""
+        self._dev_only("profile_gated()")
+        n = len(d_frames)
+        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
+        act, commit, empty = C.c_float(), C.c_float(), C.c_float()
+        self._ck(self._lib.wz_profile_gated(self._h, n, (C.c_void_p * n)(*d_frames), (C.c_int32 * n)(*widths), (C.c_int32 * n)(*heights), fmtv,
+                                            (C.c_int32 * n)(*[int(c) for c in cams]), float(self.nms_iou if iou is None else iou),
+                                            float(1.0 if ios is None else ios), int(reps), C.byref(act), C.byref(commit), C.byref(empty)))
+        self._gate_last[0] = [int(c) for c in cams]
+        return float(act.value), float(commit.value), float(empty.value)
 
     def stage_merge_tiles(self, width: int, height: int, tiles, tile_rows: np.ndarray, iou: float, ios: float, cam: int = -1):
         """The merge kernel on caller-provided rows: tiles = [(x0, y0, w, h), ...], tile_rows ROW_DTYPE [len(tiles), 100] ->
