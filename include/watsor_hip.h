@@ -164,8 +164,8 @@ int wz_collect(wz_engine_t* e, int slot, wz_detection_t* const* out, uint8_t* co
  * copy.  A tiled slot is collected like any other (wz_collect, or wz_wait + wz_slot_rows): n frames' merged rows.  Refused, with no row
  * written and nothing enqueued: n or the tiles of the call beyond max_batch, n_tiles[i] outside 1 .. WZ_MAX_TILES (WZ_ELIMIT); a
  * rectangle that is empty or leaves the frame, one the format cannot cut (NV12 / I420: even x0, y0, w, h; YUYV422 / UYVY422: even x0, w),
- * one wz_frame_bytes() refuses as a frame, a threshold that is NaN or negative (WZ_EINVAL).  The worker's frame table (wz_bind_frames /
- * wz_submit_bound) has no tiled form. */
+ * one wz_frame_bytes() refuses as a frame, a threshold that is NaN or negative (WZ_EINVAL).  The worker's frame table takes the same
+ * rectangles per entry: wz_bind_tiles, below. */
 #define WZ_MAX_TILES 64                       /* tiles of one frame */
 typedef struct wz_tile { int32_t x0, y0, w, h; } wz_tile_t;   /* a rectangle of the frame, pixels */
 int wz_detect_tiled(wz_engine_t* e, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt,
@@ -216,11 +216,37 @@ int wz_gate_stats(wz_engine_t* e, int slot, int n, uint64_t* ran_mask /* [n], bi
  * (watsor/stream/share.py:27-41,76-81).  So they are described ONCE (entry i = one Frame: pixels, w, h, WZ_FMT_*, camera id or
  * -1, its rows), a batch is then n table indices, and the rows land in the frames' own headers.  fmt / cam may be NULL (RGB24 /
  * no camera).  The pixels travel as wz_submit_host moves them (one copy per frame on the lane's stream: DMA from
- * wz_host_register()ed memory).  wz_bind_frames replaces the whole table (waits for the lanes first). */
+ * wz_host_register()ed memory).  wz_bind_frames replaces the whole table (waits for the lanes first) and with it every tiled
+ * description wz_bind_tiles gave its entries. */
 int wz_bind_frames(wz_engine_t* e, int n, const uint8_t* const* pixels, const int* w, const int* h, const int* fmt,
                    const int* cam, wz_detection_t* const* rows);
+/* Tiled and gated detection through the frame table: entries first .. first + count - 1 of the current table --
+ * normally the frames of one camera's FrameBuffer -- get a tiled description.  Waits for every lane first; on any refusal no entry changes.
+ *   gated == 0, n_tiles >= 1   tiles[0 .. n_tiles) are the entries' rectangles, iou_thr / ios_thr their merge thresholds (wz_detect_tiled).
+ *                              Checked against EVERY entry's own width, height and format word as a tiled call checks them (inside the
+ *                              frame, the format's even-ness, none larger than max_width x max_height: WZ_EINVAL / WZ_ELIMIT); n_tiles
+ *                              outside 1 .. min(WZ_MAX_TILES, max_batch): WZ_ELIMIT; a threshold that is NaN or negative: WZ_EINVAL.
+ *   gated != 0                 tiles must be NULL and n_tiles 0 (WZ_EINVAL): rectangles and gate are the ones wz_set_camera_tiles gave the
+ *                              entries' camera -- all entries of the range must carry the same camera id >= 0 (WZ_EINVAL).  The layout is
+ *                              looked up when a batch is submitted: it may be set or replaced after this call.
+ *   gated == 0, n_tiles == 0, tiles == NULL   the entries are untiled again.
+ * first / count outside the table: WZ_EINVAL. */
+int wz_bind_tiles(wz_engine_t* e, int first, int count, int n_tiles, const wz_tile_t* tiles, double iou_thr, double ios_thr, int gated);
+/* A batch of table entries on lane `slot`.  All entries untiled: an ordinary batch, as wz_submit_host runs it.  All entries tiled: the
+ * tiled call wz_detect_tiled defines, with every refusal of one (the tiles of the batch beyond max_batch: WZ_ELIMIT; a camera filter set
+ * for another size: WZ_EINVAL), made before anything is enqueued; the entries' thresholds must be equal (WZ_EINVAL: the merge launch takes one pair).  All entries
+ * gated: the gated call wz_detect_gated defines, with its refusals (one frame per camera and call, a camera without a layout or with one
+ * of another size or base format: WZ_EINVAL; the configured tile counts beyond max_batch: WZ_ELIMIT) and equal thresholds; the call
+ * returns once the decision is made, as wz_submit_gated_device does, and wz_gate_stats describes the slot.  A batch that mixes two of
+ * the three kinds: WZ_EINVAL.  A refusal leaves the lane, the cameras' gate state and every row as they were.
+ * Where the pixels of a tiled or gated entry come from: a frame inside a wz_host_register()ed range is read IN PLACE by the crop and
+ * activity kernels (which read the rectangles' rows and nothing else) when the rectangles' bytes -- wz_frame_bytes(tile w, tile h, fmt)
+ * summed over the frame's tiles, twice that for a gated entry, whose tiles are measured and then read again when they run -- are at
+ * most half of the frame's; otherwise the frame is staged whole by one DMA and cut from that copy. */
 int wz_submit_bound(wz_engine_t* e, int slot, int n, const int32_t* entries);
-int wz_collect_bound(wz_engine_t* e, int slot);   /* waits for `slot`, writes its rows into the bound frames' rows */
+/* waits for `slot`, writes its rows into the bound frames' rows: the batch's own rows or, after a tiled or gated submit, the frames'
+ * merged rows (also when no tile of a gated batch ran).  WZ_EINCOMPLETE is returned after the rows are written, as by wz_collect. */
+int wz_collect_bound(wz_engine_t* e, int slot);
 /* Wait for `slot` without copying rows out (rows stay readable via wz_slot_rows). */
 int wz_wait(wz_engine_t* e, int slot);
 const wz_detection_t* wz_slot_rows(wz_engine_t* e, int slot); /* pinned host, [n][100]; after a tiled submit: the n frames' merged rows */
@@ -380,6 +406,9 @@ int wz_stage_tile_activity(wz_engine_t* e, const uint8_t* frame, int w, int h, i
  * issued them (the call runs first, with whatever state its cameras have); empty_ms: the same bracket around nothing */
 int wz_profile_gated(wz_engine_t* e, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt, const int* cam,
                      double iou_thr, double ios_thr, int reps, float* activity_ms, float* commit_ms, float* empty_ms);
+/* in_place[i] = 1 where frame i of the last tiled or gated wz_submit_bound on `slot` was read in place through its device view, 0 where it
+ * was staged by DMA (n values: the frames of that batch); WZ_EINVAL when the lane has seen no such batch */
+int wz_debug_bound_source(wz_engine_t* e, int slot, int32_t* in_place /* [n] */);
 
 #endif /* WZ_DEV_BUILD */
 

@@ -71,6 +71,7 @@ SIGNATURES = {
     "wz_gate_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "wz_collect": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "wz_bind_frames": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, C.POINTER(C.c_void_p)]),
+    "wz_bind_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int]),
     "wz_submit_bound": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_i32p]),
     "wz_collect_bound": (C.c_int, [C.c_void_p, C.c_int]),
     "wz_wait": (C.c_int, [C.c_void_p, C.c_int]),
@@ -134,6 +135,7 @@ DEV_SIGNATURES = {
                                          C.c_void_p]),
     "wz_profile_gated": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, C.c_double, C.c_double, C.c_int,
                                    c_f32p, c_f32p, c_f32p]),
+    "wz_debug_bound_source": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "wz_stage_merge_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                                        C.c_void_p, C.c_void_p]),
 }

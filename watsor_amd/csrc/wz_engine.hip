@@ -135,6 +135,7 @@ struct wz_engine {
         uint32_t* h_status = nullptr;        // pinned, device-mapped: one word per frame, non-zero = the frame's rows may be short (wz_k_nms)
         uint32_t* m_status = nullptr;
         std::vector<int32_t> bound_idx;      // frame-table entries of the batch in flight (empty: not a bound batch)
+        std::vector<int32_t> bound_src;      // the last tiled or gated bound batch accepted on this lane: 1 = frame i was read in place, 0 = staged
         // tiled detection (wz_submit_tiled_device / wz_detect_tiled), all allocated the first time the lane sees a tiled call (ensure_tiled):
         uint8_t* d_tiles = nullptr;          // tile staging [max_batch][frame_stride]: the crop launch's output, the batch's frames
         WzMergeCand* d_tcand = nullptr;      // the merge kernel's scratch [max_batch][100]
@@ -192,6 +193,15 @@ struct wz_engine {
         wz_detection_t* rows;  // Header.detections of that frame (host), written by wz_collect_bound
     };
     std::vector<BoundFrame> bound;
+    // the tiled description of a table entry (wz_bind_tiles).  Kept beside the table, and EMPTY while no entry has one: the untiled
+    // wz_submit_bound looks at nothing but that.
+    enum { BOUND_PLAIN = 0, BOUND_TILED = 1, BOUND_GATED = 2 };
+    struct BoundTiles {
+        int kind = BOUND_PLAIN;
+        std::vector<wz_tile_t> tiles;   // BOUND_TILED: the entry's rectangles (BOUND_GATED: its camera's, looked up at submit)
+        double iou = 0.0, ios = 0.0;    // the merge thresholds of both kinds
+    };
+    std::vector<BoundTiles> bound_tiles;   // [bound.size()] or empty
 
     std::vector<WzCamFilter> h_cams;
     WzCamFilter* d_cams = nullptr;
@@ -2089,6 +2099,135 @@ extern "C" int wz_bind_frames(wz_engine_t* e, int n, const uint8_t* const* pixel
     }
     for (int li = 0; li < e->n_lanes; ++li) e->lanes[li].bound_idx.clear();
     e->bound.swap(tbl);
+    e->bound_tiles.clear();   // (the table is replaced: so is every tiled description of its entries)
+    return WZ_OK;
+}
+
+// Entries first .. first + count - 1 get a tiled description (include/watsor_hip.h); checked against every entry as tiled_check checks a
+// call, nothing changes on a refusal.
+extern "C" int wz_bind_tiles(wz_engine_t* e, int first, int count, int n_tiles, const wz_tile_t* tiles, double iou_thr, double ios_thr, int gated) {
+    if (!e) return wz_fail(WZ_EINVAL, "wz_bind_tiles: null engine");
+    HIPCHK(hipSetDevice(e->device));
+    int rc = sync_all(e);   // no batch in flight was planned with the old descriptions
+    if (rc != WZ_OK) return rc;
+    const int64_t size = (int64_t)e->bound.size();
+    if (first < 0 || count < 1 || (int64_t)first + count > size)
+        return wz_fail(WZ_EINVAL, "wz_bind_tiles: entries %d .. %lld lie outside the frame table of %lld entries", first, (long long)first + count - 1,
+                       (long long)size);
+    wz_engine::BoundTiles d;
+    if (gated) {
+        if (tiles || n_tiles != 0)
+            return wz_fail(WZ_EINVAL, "wz_bind_tiles: a gated description takes its %d rectangles from wz_set_camera_tiles: tiles must be NULL and n_tiles 0", n_tiles);
+        const int c = e->bound[first].cam;
+        for (int i = first; i < first + count; ++i)
+            if (e->bound[i].cam < 0 || e->bound[i].cam != c)
+                return wz_fail(WZ_EINVAL, "wz_bind_tiles: gated entries %d .. %d must carry one camera id >= 0, entry %d has %d and entry %d has %d", first,
+                               first + count - 1, first, c, i, e->bound[i].cam);
+        d.kind = wz_engine::BOUND_GATED;
+    } else if (n_tiles == 0 && !tiles) {
+        d.kind = wz_engine::BOUND_PLAIN;
+    } else {
+        const int most = std::min(WZ_MAX_TILES, e->max_batch);
+        if (n_tiles < 1 || n_tiles > most) return wz_fail(WZ_ELIMIT, "wz_bind_tiles: %d tiles, an entry of this engine takes 1 to %d", n_tiles, most);
+        if (!tiles) return wz_fail(WZ_EINVAL, "wz_bind_tiles: %d tiles but no rectangles", n_tiles);
+        for (int i = first; i < first + count; ++i) {
+            const wz_engine::BoundFrame& f = e->bound[i];
+            for (int t = 0; t < n_tiles; ++t) {
+                const wz_tile_t& r = tiles[t];
+                const char* why = tile_refusal(r, f.w, f.h, f.fmt);
+                if (why) return wz_fail(WZ_EINVAL, "frame-table entry %d (%dx%d, format 0x%x), tile %d (%d, %d, %d x %d): %s", i, f.w, f.h, f.fmt, t, r.x0, r.y0, r.w, r.h, why);
+                if (r.w > e->max_w || r.h > e->max_h || (size_t)r.w * r.h * 3 > e->frame_stride)
+                    return wz_fail(WZ_ELIMIT, "frame-table entry %d, tile %d is %dx%d, engine was created for at most %dx%d", i, t, r.w, r.h, e->max_w, e->max_h);
+            }
+        }
+        d.kind = wz_engine::BOUND_TILED;
+        d.tiles.assign(tiles, tiles + n_tiles);
+    }
+    if (d.kind != wz_engine::BOUND_PLAIN) {
+        if (!(iou_thr >= 0.0) || !(ios_thr >= 0.0)) return wz_fail(WZ_EINVAL, "wz_bind_tiles: the merge thresholds (%g, %g) must be numbers >= 0", iou_thr, ios_thr);
+        d.iou = iou_thr;
+        d.ios = ios_thr;
+        if (e->bound_tiles.empty()) e->bound_tiles.resize(e->bound.size());
+    }
+    if (e->bound_tiles.empty()) return WZ_OK;   // (untiled entries of a table without descriptions)
+    for (int i = first; i < first + count; ++i) e->bound_tiles[i] = d;
+    bool any = false;
+    for (const auto& b : e->bound_tiles) any = any || b.kind != wz_engine::BOUND_PLAIN;
+    if (!any) e->bound_tiles.clear();
+    return WZ_OK;
+}
+
+// The bytes the crop kernel (and, gated, the activity kernel before it) reads of a frame: what decides between reading a page-locked frame in
+// place and staging it whole.  Break-even by bandwidth is near 0.8 of the frame's bytes (a kernel reads mapped memory at 23 GB/s beside the
+// other lanes' kernels, the copies move 29 GB/s: see stage_frame above); one half is the margin read_in_place() uses for the resize kernel.
+// Measured for the crop kernel (profiles/bound_tiles.txt; one 640 x 480 rectangle of a 1080p frame, four lanes busy):
+// RGB24, cost 0.15 of the frame: 5600 frames/s in place against 5565 staged -- level -- and a lone call 0.326 against 0.426 ms; NV12, cost
+// 0.15: 5825 in place against 8247 staged, a lone call 0.318 against 0.374 ms.  So at a cost well under one half, reading in place is
+// SLOWER than staging with every lane busy once the whole frame is small (3.1 MB): both in-place legs sit at ~0.175 ms a step whatever
+// they read.  The constant stays at one half here; moving it (or bounding it by the frame's bytes) needs that plateau explained first.
+static bool tiles_in_place(const wz_engine* e, const wz_engine::BoundFrame& f, const std::vector<wz_tile_t>& tiles, bool gated) {
+    if (!f.dev || e->host_read == 0) return false;
+    if (e->host_read == 1) return true;
+    uint64_t cost = 0;
+    for (const wz_tile_t& t : tiles) cost += wz_frame_bytes(t.w, t.h, f.fmt);
+    if (gated) cost *= 2;   // a gated tile is measured, and read again when it runs
+    return e->host_read == 2 && 2 * cost <= f.bytes;
+}
+
+static const char* bound_kind_name(int kind) { return kind == wz_engine::BOUND_TILED ? "tiled" : kind == wz_engine::BOUND_GATED ? "gated" : "untiled"; }
+
+// wz_submit_bound of a batch with a tiled or gated entry (slot, n and the entries' range are checked): one kind, one pair of thresholds,
+// the refusals of the tiled / gated call, then every frame staged whole or handed over in place, then tiled_enqueue / gated_enqueue.
+static int submit_bound_tiles(wz_engine* e, int slot, int n, const int32_t* entries) {
+    const wz_engine::BoundTiles& d0 = e->bound_tiles[entries[0]];
+    for (int i = 1; i < n; ++i) {
+        const wz_engine::BoundTiles& d = e->bound_tiles[entries[i]];
+        if (d.kind != d0.kind)
+            return wz_fail(WZ_EINVAL, "wz_submit_bound: frame-table entry %d is %s and entry %d is %s: a batch holds one kind", entries[0], bound_kind_name(d0.kind),
+                           entries[i], bound_kind_name(d.kind));
+    }
+    for (int i = 1; i < n; ++i) {
+        const wz_engine::BoundTiles& d = e->bound_tiles[entries[i]];
+        if (d.iou != d0.iou || d.ios != d0.ios)
+            return wz_fail(WZ_EINVAL, "wz_submit_bound: frame-table entry %d merges with thresholds (%g, %g) and entry %d with (%g, %g): a batch takes one pair",
+                           entries[0], d0.iou, d0.ios, entries[i], d.iou, d.ios);
+    }
+    const bool gated = d0.kind == wz_engine::BOUND_GATED;
+    std::vector<const uint8_t*> hptr(n), dptr(n);
+    std::vector<int> ws(n), hs(n), fmts(n), cams(n), nt(n);
+    std::vector<const wz_tile_t*> tp(n);
+    for (int i = 0; i < n; ++i) {
+        const wz_engine::BoundFrame& f = e->bound[entries[i]];
+        hptr[i] = f.host; ws[i] = f.w; hs[i] = f.h; fmts[i] = f.fmt; cams[i] = f.cam;
+        nt[i] = (int)e->bound_tiles[entries[i]].tiles.size();
+        tp[i] = e->bound_tiles[entries[i]].tiles.data();
+    }
+    int total = 0;
+    int rc = gated ? gated_check(e, "wz_submit_bound", slot, n, hptr.data(), ws.data(), hs.data(), fmts.data(), cams.data(), d0.iou, d0.ios, true, &total)
+                   : tiled_check(e, "wz_submit_bound", slot, n, hptr.data(), ws.data(), hs.data(), fmts.data(), cams.data(), nt.data(), tp.data(), d0.iou, d0.ios,
+                                 true, &total);
+    if (rc != WZ_OK) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    Lane& L = e->lanes[slot];
+    HIPCHK(hipEventSynchronize(L.done));   // the lane's previous batch (and its reads of the staging area) drained
+    if (!L.d_frames) return wz_fail(WZ_EINVAL, "wz_submit_bound: lane %d has no staging area", slot);
+    std::vector<int32_t> src(n);
+    for (int i = 0; i < n; ++i) {
+        const wz_engine::BoundFrame& f = e->bound[entries[i]];
+        const std::vector<wz_tile_t>& tiles = gated ? e->gate_cams.find(f.cam)->second.tiles : e->bound_tiles[entries[i]].tiles;
+        if (tiles_in_place(e, f, tiles, gated)) {
+            dptr[i] = f.dev;
+            src[i] = 1;
+            continue;
+        }
+        rc = stage_frame(e, L, i, f.host, f.bytes, &dptr[i]);
+        if (rc != WZ_OK) return rc;
+    }
+    rc = gated ? gated_enqueue(e, slot, n, dptr.data(), ws.data(), hs.data(), fmts.data(), cams.data(), d0.iou, d0.ios, total)
+               : tiled_enqueue(e, slot, n, dptr.data(), ws.data(), hs.data(), fmts.data(), cams.data(), nt.data(), tp.data(), d0.iou, d0.ios, total);
+    if (rc != WZ_OK) return rc;
+    L.bound_idx.assign(entries, entries + n);   // (L.tiled == n says that their rows are the merged ones)
+    L.bound_src.swap(src);
     return WZ_OK;
 }
 
@@ -2099,6 +2238,9 @@ extern "C" int wz_submit_bound(wz_engine_t* e, int slot, int n, const int32_t* e
     for (int i = 0; i < n; ++i)
         if (entries[i] < 0 || (size_t)entries[i] >= e->bound.size())
             return wz_fail(WZ_EINVAL, "frame-table entry %d out of range [0,%zu)", entries[i], e->bound.size());
+    if (!e->bound_tiles.empty())           // some entry of the table has a tiled description (wz_bind_tiles): does one of these?
+        for (int i = 0; i < n; ++i)
+            if (e->bound_tiles[entries[i]].kind != wz_engine::BOUND_PLAIN) return submit_bound_tiles(e, slot, n, entries);
     HIPCHK(hipSetDevice(e->device));
     Lane& L = e->lanes[slot];
     HIPCHK(hipEventSynchronize(L.done));   // the lane's previous batch (and its reads of the staging area) drained
@@ -2131,9 +2273,12 @@ extern "C" int wz_collect_bound(wz_engine_t* e, int slot) {
     int rc = wz_wait(e, slot);
     if (rc != WZ_OK) return rc;
     Lane& L = e->lanes[slot];
-    if (L.bound_idx.empty() || (int)L.bound_idx.size() != L.n) return wz_fail(WZ_EINVAL, "wz_collect_bound: lane %d holds no bound batch", slot);
-    for (int i = 0; i < L.n; ++i)
-        memcpy(e->bound[L.bound_idx[i]].rows, L.h_rows + (size_t)i * WZ_MAX_DETECTIONS, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS);
+    // a tiled or gated bound batch hands over its FRAMES' merged rows: L.tiled of them, whatever L.n says (the tiles that ran; none: 0)
+    const int n = L.tiled ? L.tiled : L.n;
+    const wz_detection_t* rows = L.tiled ? L.h_trows : L.h_rows;
+    if (L.bound_idx.empty() || (int)L.bound_idx.size() != n) return wz_fail(WZ_EINVAL, "wz_collect_bound: lane %d holds no bound batch", slot);
+    for (int i = 0; i < n; ++i)
+        memcpy(e->bound[L.bound_idx[i]].rows, rows + (size_t)i * WZ_MAX_DETECTIONS, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS);
     L.bound_idx.clear();
     return lane_status(e, slot);
 }
@@ -2580,6 +2725,14 @@ extern "C" int wz_stage_merge_tiles(wz_engine_t* e, int w, int h, int cam, int n
 }
 // HIP-event time of the crop launch alone and of the merge launch alone (no filter launch), on lane 0 behind one whole tiled call of the
 // same arguments (so that the merge reads real tile rows): the mean of `reps` brackets each, in milliseconds; empty_ms: the same bracket around nothing
+extern "C" int wz_debug_bound_source(wz_engine_t* e, int slot, int32_t* in_place) {
+    if (!e || !in_place || slot < 0 || slot >= e->n_lanes) return wz_fail(WZ_EINVAL, "wz_debug_bound_source: bad argument");
+    const Lane& L = e->lanes[slot];
+    if (L.bound_src.empty()) return wz_fail(WZ_EINVAL, "wz_debug_bound_source: lane %d has seen no tiled or gated bound batch", slot);
+    memcpy(in_place, L.bound_src.data(), sizeof(int32_t) * L.bound_src.size());
+    return WZ_OK;
+}
+
 extern "C" int wz_profile_tiled(wz_engine_t* e, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
                                 const int* n_tiles, const wz_tile_t* const* tiles, double iou_thr, double ios_thr, int reps,
                                 float* crop_ms, float* merge_ms, float* empty_ms) {

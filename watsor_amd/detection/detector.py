@@ -29,7 +29,10 @@ differences, all inside the worker process:
     `fps_max = 1000 / inference_time` from it (`watsor/main.py:242-251`) and the gauge is a mean over its observations
     (`watsor/stream/share.py:225-238`);
   * with `HipObjectDetector` every Frame of every FrameBuffer is described to the engine once (`wz_bind_frames`), so a
-    batch costs the worker one call with a list of table indices and one call to collect.
+    batch costs the worker one call with a list of table indices and one call to collect;
+  * a detector with a `tiles` option goes through `detect_batch()`, one call at a time -- or, with `kwargs['hip_tiled_table']`, stays
+    asynchronous: its frame table carries the tiles (`wz_bind_tiles`), a batch is cut by the detector's `plan_bound()` into tiled / gated
+    calls, each on a lane of its own.
 
 This module needs the reference package (`watsor.stream`) at run time -- it is a drop-in for an
 installed Watsor, see INTEGRATION.md.  Everything below `detect_batch()` does not.
@@ -80,7 +83,7 @@ class BatchedWorkerMixin:
         st = getattr(self, "_hip_worker_state", None)
         if st is not None and st["detector"] is object_detector:
             return st
-        st = dict(detector=object_detector, inflight=deque(), next_lane=0, cams=None, lanes=1, asynchronous=False, table=None, affinity=None,
+        st = dict(detector=object_detector, inflight=deque(), next_lane=0, cams=None, lanes=1, asynchronous=False, table=None, plan=None, affinity=None,
                   limit=getattr(object_detector, "max_batch", 1) if hasattr(object_detector, "detect_batch") else 1,
                   last_retire=0.0, acc_ms=0.0, acc_frames=0, last_flush=0.0,
                   metric_interval=float(kwargs.get("hip_metric_interval", 0.005)))
@@ -101,13 +104,22 @@ class BatchedWorkerMixin:
         if hasattr(object_detector, "submit_host") and hasattr(object_detector, "collect"):
             st["asynchronous"] = kwargs.get("hip_async", True)
             if st["asynchronous"] and getattr(object_detector, "tiled", False):
-                # tiled detection (plugin option `tiles`) exists on detect() / detect_batch() only: neither the frame table nor the
-                # asynchronous host path has a tiled form, and nothing may be detected untiled in silence
-                st["asynchronous"] = False
-                self._info("tiles are configured: batches go through detect_batch(), one call at a time")
+                if kwargs.get("hip_tiled_table", False) and kwargs.get("hip_frame_table", True) and hasattr(object_detector, "bind_tiled_frame_table"):
+                    # opt-in: the frame table with tiled descriptions (wz_bind_tiles) -- batches stay asynchronous, cut by plan_bound()
+                    try:
+                        st["table"] = object_detector.bind_tiled_frame_table(frame_buffers, st["cams"] or {})
+                        st["plan"] = object_detector.plan_bound
+                    except ValueError as e:       # the asynchronous host path detects untiled: a tiled detector never goes there
+                        st["asynchronous"] = False
+                        self._warn("tiled frame table not bound (%s): batches go through detect_batch(), one call at a time" % (e,))
+                else:
+                    # tiled detection (plugin option `tiles`) through detect() / detect_batch(): the asynchronous host path has no tiled
+                    # form, the frame table only on request (`hip_tiled_table`), and nothing may be detected untiled in silence
+                    st["asynchronous"] = False
+                    self._info("tiles are configured: batches go through detect_batch(), one call at a time")
             lanes = getattr(object_detector, "num_lanes", 1)
             st["lanes"] = max(1, min(int(kwargs.get("hip_lanes", lanes)), lanes))
-        if st["asynchronous"] and kwargs.get("hip_frame_table", True) and hasattr(object_detector, "bind_frame_table"):
+        if st["asynchronous"] and st["plan"] is None and kwargs.get("hip_frame_table", True) and hasattr(object_detector, "bind_frame_table"):
             try:
                 st["table"] = object_detector.bind_frame_table(frame_buffers, st["cams"] or {})
             except ValueError as e:               # a frame buffer the engine cannot take: per-batch descriptions, which skip only its frames
@@ -297,6 +309,8 @@ class BatchedWorkerMixin:
             latches = [f.latch.next for f in frames]
         if not payloads:
             return
+        if frames is None and st["plan"] is not None:
+            return self._submit_planned(st, payloads, entries, latches, frame_buffers, fps, inference_time, object_detector)
         try:
             lane = st["next_lane"]
             t0 = perf_counter()
@@ -312,6 +326,40 @@ class BatchedWorkerMixin:
             return self._next_frames(payloads, None, frame_buffers, fps, inference_time, object_detector, st)
         st["inflight"].append((lane, latches, t0, frames))
         st["next_lane"] = (lane + 1) % st["lanes"]
+
+    def _submit_planned(self, st, payloads, entries, latches, frame_buffers, fps, inference_time, object_detector):
+        """A batch of a tiled frame table (`hip_tiled_table`): the detector cuts the indices into the calls the engine accepts -- one kind, one
+        pair of thresholds, tiles within max_batch, one frame of a gated camera -- and every piece goes onto a lane of its own, with the
+        latches of its payloads; when every lane is busy the oldest batch is retired first, as between batches."""
+        def retry(off, e):                        # nothing was enqueued for this piece or the ones behind it: synchronous retry, frame by frame
+            self._warn("asynchronous submit of %d frames failed (%s), falling back to synchronous calls" % (len(payloads) - off, e))
+            while st["inflight"]:
+                self._retire_oldest(st, fps, inference_time, object_detector)
+            return self._next_frames(payloads[off:], None, frame_buffers, fps, inference_time, object_detector, st)
+        try:
+            pieces = st["plan"](entries)
+            if [i for p in pieces for i in p] != list(entries):
+                raise ValueError("plan_bound() did not return the %d frames in order" % len(entries))
+        except Exception as e:
+            return retry(0, e)
+        off = 0
+        for piece in pieces:
+            if len(st["inflight"]) >= st["lanes"]:
+                try:
+                    self._retire_oldest(st, fps, inference_time, object_detector)
+                except BaseException:             # a collect that failed propagates (detector.py:99-100): the payloads not yet submitted
+                    for step in latches[off:]:    # are released first, one latch step each
+                        step()
+                    raise
+            lane = st["next_lane"]
+            t0 = perf_counter()
+            try:
+                object_detector.submit_bound(lane, piece)
+            except Exception as e:
+                return retry(off, e)
+            st["inflight"].append((lane, latches[off:off + len(piece)], t0, None))
+            st["next_lane"] = (lane + 1) % st["lanes"]
+            off += len(piece)
 
     def _retire_oldest(self, st, fps, inference_time, object_detector):
         lane, latches, t0, frames = st["inflight"].popleft()
@@ -460,6 +508,8 @@ def create_object_detectors(delegate_class, stop_event, log_queue, frame_queue, 
       hip_lanes    batches kept in flight per GPU by the worker (default: the engine's lanes, 4)
       hip_metric_interval  seconds of batches folded into one `inference_time` observation (default 0.005; 0: one per batch)
       hip_frame_table      False: describe the frames of every batch to the engine instead of binding them once
+      hip_tiled_table      True: a detector with a `tiles` option stays asynchronous -- its frame table carries the tiles (wz_bind_tiles), a
+                           batch is cut into tiled / gated calls on successive lanes (default False: detect_batch(), one call at a time)
       hip_affinity         True (several AMD GPUs): whole cameras are dealt to the detectors (`camera_affinity`): a detector binds and
                            page-locks only its own cameras' frame buffers; payloads drawn by the wrong detector are passed on"""
     _ref = _require_watsor()

@@ -167,8 +167,33 @@ def tile_options(options: dict):
     return None, {str(name): _tile_spec(spec, "tiles[%r]" % (name,)) for name, spec in v.items()}
 
 
+def plan_bound(descriptions, entries, max_batch: int):
+    """Cuts a list of frame-table indices into the calls `wz_submit_bound` accepts, in order (include/watsor_hip.h): every call holds one
+    kind -- untiled, tiled or gated -- and one pair of merge thresholds, at most max_batch frames whose tiles (gated: their cameras'
+    configured tiles) together fit max_batch, and at most one frame of a gated camera.  The calls are consecutive pieces of `entries`, so a
+    camera's frames keep their order.  descriptions[i] = (kind, iou, ios, tiles, camera id) of table entry i with kind "plain" | "tiled" |
+    "gated" (what `bind_tiled_frame_table` recorded); an index beyond them counts as plain.  A pure function."""
+    calls, call, key, used, cams = [], [], None, 0, set()
+    for e in entries:
+        kind, iou, ios, tiles, cam = descriptions[e] if 0 <= e < len(descriptions) else ("plain", None, None, 1, -1)
+        k = (kind, iou, ios) if kind != "plain" else ("plain",)
+        cost = tiles if kind != "plain" else 1
+        if call and (k != key or used + cost > max_batch or len(call) >= max_batch or (kind == "gated" and cam in cams)):
+            calls.append(call)
+            call, used, cams = [], 0, set()
+        key = k
+        call.append(e)
+        used += cost
+        cams.add(cam)
+    if call:
+        calls.append(call)
+    return calls
+
+
 class HipObjectDetector:
     """Performs object detection on AMD Instinct MI355X GPUs (hand-written HIP kernels)."""
+
+    bound_max_batch = None          # the batch limit `plan_bound` cuts for (None: the engine's max_batch)
 
     def __init__(self, model_path, device: int = 0, options: Optional[dict] = None, max_batch: Optional[int] = None,
                  max_width: Optional[int] = None, max_height: Optional[int] = None):
@@ -193,7 +218,7 @@ class HipObjectDetector:
         since they last ran (include/watsor_hip.h: wz_detect_gated; the luma sum of a 16 x 16 cell must move by more than `threshold`
         per pixel, in `min_cells` cells; `max_age` > 0 runs a tile after that many skipped calls whatever it shows) and reuses the
         other tiles' rows; a frame without a camera id runs every tile as before.  The batched worker's frame table
-        has no tiled form: `bind_frame_table` raises for a camera with tiles.
+        takes tiles through `bind_tiled_frame_table` (the worker's `hip_tiled_table`); `bind_frame_table` raises for a camera with tiles.
         `options["schedule"]`: "latency" | "throughput" | "auto" (default) -- the launch shapes of this detector PROCESS
         (include/watsor_hip.h: wz_set_schedule).  "latency" makes a lone batch finish soonest -- the reference's normal load is one
         frame at a time (`_next_frame`, detector.py:102-112); "throughput" gets the most frames per second out of four batches in
@@ -238,6 +263,7 @@ class HipObjectDetector:
         self.__tiles_by_cam = {}
         self.__tile_rects = {}
         self.__gate_layouts = {}        # camera id -> what its tiles were last set for: (width, height, base format, rectangles, gate)
+        self.bound_descriptions = []    # per frame-table entry: (kind, iou, ios, tiles, camera id), see `plan_bound`
         for where, spec in [("tiles", self.__tiles_default)] + [("tiles[%r]" % n, t) for n, t in self.__tiles_by_name.items()]:
             if spec is not None and spec["count"] > max_batch:
                 raise ValueError("%s: %d tiles per frame exceed max_batch %d" % (where, spec["count"], max_batch))
@@ -263,7 +289,8 @@ class HipObjectDetector:
 
     @property
     def tiled(self) -> bool:
-        """A `tiles` option is set (for every camera or for some): frames go through `detect()` / `detect_batch()` only."""
+        """A `tiles` option is set (for every camera or for some): frames go through `detect()` / `detect_batch()`, or through a frame
+        table bound with `bind_tiled_frame_table`."""
         return self.__tiles_default is not None or bool(self.__tiles_by_name)
 
     @property
@@ -346,13 +373,28 @@ class HipObjectDetector:
         (`wz_bind_frames`: pixels, size, pixel format, camera id, the address of `header.detections`) -- what the reference
         worker looks up and rebuilds per payload (`watsor/detection/detector.py:104-106`, `share.py:68-73`) never changes
         after the buffers exist.  Returns {camera name: (index of its frame 0 in the table, [frame.latch.next, ...])}."""
+        return self._bind_table(frame_buffers, ids, tiled=False)
+
+    def bind_tiled_frame_table(self, frame_buffers, ids):
+        """`bind_frame_table` for a detector with a `tiles` option (the worker's `hip_tiled_table`): after the table is bound every camera
+        with a description gets its rectangles -- `tile_grid` of the table's own width, height and format, or the explicit "rects" --
+        through `wz_bind_tiles`; a description with a "gate" on a camera that has an id sets the camera's layout (`set_camera_tiles`) and
+        binds its frames gated; a gate without a camera id is tiled, not gated, as in `detect_batch`.  Batches must then be cut by
+        `plan_bound`.  Returns the same table."""
+        return self._bind_table(frame_buffers, ids, tiled=True)
+
+    def plan_bound(self, entries):
+        """The calls `submit_bound` accepts for these table indices, in order: see the module's `plan_bound`."""
+        return plan_bound(self.bound_descriptions, entries, self.bound_max_batch or self.max_batch)
+
+    def _bind_table(self, frame_buffers, ids, tiled: bool):
         import ctypes
         pix, ws, hs, fmts, cams, rows, table = [], [], [], [], [], [], {}
         from .. import _lib
         frame_bytes = _lib.load().wz_frame_bytes              # (the library sizes a frame: one rule for the table and the engine)
         yuv = _planar_format(self.__fmt_default, self.__fmt_by_cam)
         for name in sorted(frame_buffers, key=str):
-            if self.__tiles_default is not None or str(name) in self.__tiles_by_name:
+            if not tiled and (self.__tiles_default is not None or str(name) in self.__tiles_by_name):
                 raise ValueError("camera %r has tiles configured: tiled detection does not go through the worker's frame table "
                                  "(bind_frame_table / submit_bound); use detect() / detect_batch() for it" % (name,))
             cam = ids.get(name, -1)
@@ -394,9 +436,43 @@ class HipObjectDetector:
                 rows.append(ctypes.addressof(hdr.detections))
                 latches.append(frame.latch.next)
         self.__engine.bind_frames(pix, ws, hs, fmts, cams, rows)
+        self.bound_descriptions = [("plain", None, None, 1, c) for c in cams]
+        if tiled:
+            self._bind_tiles(frame_buffers, table, ws, hs, fmts, cams)
         self.submit_bound = self.__engine.submit_bound      # (the worker calls these once per batch: no wrapper frames in between)
         self.collect_bound = self.__engine.collect_bound
         return table
+
+    def _bind_tiles(self, frame_buffers, table, ws, hs, fmts, cams):
+        """The tiled descriptions of a freshly bound table: per camera with a `tiles` option, one `bind_tiles` per run of frames that share
+        their rectangles (all of them, unless a FrameBuffer holds frames of several sizes)."""
+        eng = self.__engine
+        for name in sorted(frame_buffers, key=str):
+            base, latches = table[name]
+            spec = self.__tiles_by_name.get(str(name), self.__tiles_default)
+            if spec is None or not latches:
+                continue
+            iou = float(eng.nms_iou if spec["iou"] is None else spec["iou"])
+            ios = float(1.0 if spec["ios"] is None else spec["ios"])
+            cam = cams[base]
+            gated = "gate" in spec and cam >= 0
+            first = base
+            while first < base + len(latches):
+                w, h, fmt = ws[first], hs[first], fmts[first]
+                rects = self._rects_of(spec, w, h, fmt)
+                last = first + 1
+                while last < base + len(latches) and (ws[last], hs[last], fmts[last]) == (w, h, fmt):
+                    last += 1
+                if gated:
+                    if first != base:
+                        raise ValueError("camera %r: the frames of a gated camera must share one size and format" % (name,))
+                    self._set_gate_layout(cam, w, h, fmt, rects, spec["gate"])
+                    eng.bind_tiles(first, last - first, None, iou, ios, gated=True)
+                else:
+                    eng.bind_tiles(first, last - first, rects, iou, ios)
+                for i in range(first, last):
+                    self.bound_descriptions[i] = ("gated" if gated else "tiled", iou, ios, len(rects), cam)
+                first = last
 
     def submit_host(self, lane: int, images: Sequence[np.ndarray], cameras: Optional[Sequence[int]] = None) -> None:
         """Asynchronous `detect_batch`: the frames (views of shared memory, unchanged until `collect`) are enqueued on `lane`."""
@@ -413,7 +489,12 @@ class HipObjectDetector:
         """The rectangles of a frame under a `tiles` option (a grid is laid out once per frame size and format)."""
         if "rects" in spec:
             return spec["rects"]
-        w, h = self.__engine.frame_geometry(frame, fmt)
+        return self._rects_of(spec, *self.__engine.frame_geometry(frame, fmt), fmt)
+
+    def _rects_of(self, spec: dict, w: int, h: int, fmt: int):
+        """... of a w x h frame of format word `fmt`"""
+        if "rects" in spec:
+            return spec["rects"]
         key = (id(spec), w, h, fmt & FMT_BASE_MASK)
         rects = self.__tile_rects.get(key)
         if rects is None:
@@ -466,7 +547,9 @@ class HipObjectDetector:
 
     def _gate_layout(self, cam: int, frame: np.ndarray, fmt: int, rects, gate) -> None:
         """Camera `cam`'s tiles in the engine: set the first time a frame of it is seen, and again when its size, format or tiles change."""
-        w, h = self.__engine.frame_geometry(frame, fmt)
+        self._set_gate_layout(cam, *self.__engine.frame_geometry(frame, fmt), fmt, rects, gate)
+
+    def _set_gate_layout(self, cam: int, w: int, h: int, fmt: int, rects, gate) -> None:
         layout = (w, h, fmt & FMT_BASE_MASK, tuple(rects), gate)
         if self.__gate_layouts.get(cam) != layout:
             self.__engine.set_camera_tiles(cam, w, h, rects, gate[0], gate[1], gate[2], fmt)

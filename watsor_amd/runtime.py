@@ -119,6 +119,9 @@ class HipEngine:
         self._gate_tiles = {}                              # camera id -> tiles of its layout (set_camera_tiles)
         self._gate_last = {}                               # lane -> the camera ids of the last gated call accepted on it
         self._bound_arrays = {}                            # (submit_bound before any bind_frames: the engine's EINVAL, not an AttributeError)
+        self._bound_last = {}                              # lane -> frames of the last bound batch accepted on it (bound_source)
+        self._bound_cams = []                              # camera id of every table entry (bind_frames) ...
+        self._bound_tiled = {}                             # ... and entry -> its camera id where bind_tiles(gated=True) described it, -1 where rects did
 
     def _ck(self, rc: int, what: str = "") -> None:
         if rc:
@@ -423,9 +426,44 @@ class HipEngine:
             (C.c_int32 * n)(*[int(f) for f in formats]), (C.c_int32 * n)(*[int(c) for c in cams]),
             (C.c_void_p * n)(*row_addresses)))
         self._bound_arrays = {}
+        self._bound_cams = [int(c) for c in cams]
+        self._bound_tiled = {}
+
+    def bind_tiles(self, first: int, count: int, rects=None, iou: Optional[float] = None, ios: Optional[float] = 1.0, gated: bool = False) -> None:
+        """Table entries first .. first + count - 1 (normally one camera's frames) are detected TILED from now on (include/watsor_hip.h:
+        wz_bind_tiles): `rects` = [(x0, y0, w, h), ...] as `detect_tiled` takes them, or gated=True (and no rects): the tiles and the gate
+        `set_camera_tiles` gave the entries' camera, looked up at every submit.  rects=None without `gated`: untiled again.  iou / ios as in
+        `detect_tiled` (None: the engine's own NMS threshold / 1.0).  Waits for every lane."""
+        n = 0 if rects is None else len(rects)
+        arr = None
+        if rects is not None:
+            arr = (Tile * max(1, n))()
+            for k, r in enumerate(rects):
+                if len(r) != 4:
+                    raise ValueError("tile %d: expected (x0, y0, w, h)" % k)
+                arr[k] = Tile(*[int(v) for v in r])
+        self._ck(self._lib.wz_bind_tiles(self._h, int(first), int(count), n, C.byref(arr) if arr is not None else None,
+                                         float(self.nms_iou if iou is None else iou), float(1.0 if ios is None else ios), 1 if gated else 0))
+        for i in range(int(first), int(first) + int(count)):
+            if gated:
+                self._bound_tiled[i] = self._bound_cams[i]
+            elif rects is not None:
+                self._bound_tiled[i] = -1
+            else:
+                self._bound_tiled.pop(i, None)
+
+    def bound_source(self, slot: int) -> List[int]:
+        """Development library: per frame of the last tiled or gated bound batch on lane `slot`, 1 = read in place from page-locked memory,
+        0 = staged by DMA."""
+        self._dev_only("bound_source")
+        n = self._bound_last.get(slot, 0)
+        out = (C.c_int32 * max(1, n))()
+        self._ck(self._lib.wz_debug_bound_source(self._h, slot, C.byref(out)))
+        return [int(v) for v in out[:n]]
 
     def submit_bound(self, slot: int, entries: Sequence[int]) -> None:
-        """Asynchronous detect of the frames with these table indices on lane `slot` (one C call, no per-frame work here)."""
+        """Asynchronous detect of the frames with these table indices on lane `slot` (one C call, no per-frame work here).  Entries with a
+        tiled description (`bind_tiles`) run tiled / gated; a batch holds one kind."""
         n = len(entries)
         arr_t = self._bound_arrays.get(n)
         if arr_t is None:
@@ -433,6 +471,12 @@ class HipEngine:
         rc = self._lib.wz_submit_bound(self._h, slot, n, arr_t(*entries))
         if rc:
             self._ck(rc)
+        if self._bound_tiled:                                          # (what bound_source / gate_stats need to know about the lane)
+            cam = self._bound_tiled.get(entries[0])
+            if cam is not None:
+                self._bound_last[slot] = n
+                if cam >= 0:
+                    self._gate_last[slot] = [self._bound_tiled[i] for i in entries]
 
     def collect_bound(self, slot: int) -> None:
         """Waits for lane `slot`; its rows are written into the bound frames' own `Detection[100]` arrays."""
