@@ -21,6 +21,9 @@
  * streams they ride, default = lanes, at most 4 pay), WZ_GRAPH=0|1 (launch kernel by kernel / replay a captured graph; unset: under the throughput schedule a captured graph while another lane is busy and
  * kernel by kernel for a batch that finds the other lanes idle, under the latency schedule always kernel by kernel),
  * WZ_SCHEDULE=latency (launch shapes for the shortest lone batch instead of the most frames per second with every lane busy).
+ * GPU_MAX_HW_QUEUES (the HIP runtime's: hardware queues of this process) is WRITTEN when the library loads: four lanes need a queue each
+ * beside the runtime's own, so a value that is unset, empty, not a number or below 8 becomes 8; 8 and more is left as the host set it
+ * (wz_hw_queues()).  It takes effect only where the library is loaded before the process's first HIP call.
  */
 #ifndef WATSOR_HIP_H
 #define WATSOR_HIP_H
@@ -66,6 +69,10 @@ int wz_device_name_of(int device, char* buf, int buflen);
  * a detector process pins itself -- and with it the first-touch placement of the frame memory it page-locks -- to the GPU's NUMA node
  * (the reference starts one detector process per device, watsor/detection/detector.py:34-50, watsor/main.py:414-418). */
 int wz_device_pci_bus_id(int device, char* buf, int buflen);
+/* GPU_MAX_HW_QUEUES in this process's environment after the library loaded (0: not a number) -- what the HIP runtime reads at its
+ * first call.  At least 8 unless the variable was changed afterwards; a process that initialised HIP before it loaded the library
+ * runs on whatever was there then.  An engine wants 2 x wz_num_slots() (hip_gpu.py warns below that). */
+int wz_hw_queues(void);
 
 /* ---- the schedule of this process: which of two sets of launch shapes its engines use.  THROUGHPUT (default): most frames per second
  * with every lane busy.  LATENCY: the shortest lone batch -- the reference's normal load is one frame at a time per detector
@@ -312,7 +319,11 @@ int wz_precision(wz_engine_t* e);   /* 16: fp16 storage / fp16 MFMA; 32: fp32 st
 int wz_hp_blocks(wz_engine_t* e);
 double wz_nms_iou(wz_engine_t* e);  /* the IoU threshold of the engine's own non-maximum suppression (what a tiled call merges with by default) */
 
-/* ---- device memory helpers so callers need no other GPU runtime binding */
+/* ---- device memory helpers so callers need no other GPU runtime binding
+ * Every synchronous copy or fill of the product ABI -- these two, engine creation, the camera-filter setters, the first gated call of a
+ * lane -- is issued on lane 0's stream and waited for there (never on the null stream, whose hardware queue a process that uses only
+ * this ABI therefore never opens): a call made while lane 0 has a batch in flight returns after that batch.  The copy is complete
+ * and the host buffer free when the call returns; the other lanes are not waited for. */
 int wz_dev_alloc(wz_engine_t* e, uint64_t bytes, void** d_ptr);
 int wz_dev_free(wz_engine_t* e, void* d_ptr);
 int wz_dev_upload(wz_engine_t* e, void* d_dst, const void* h_src, uint64_t bytes);

@@ -40,6 +40,7 @@ SIGNATURES = {
     "wz_device_count": (C.c_int, []),
     "wz_device_name_of": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "wz_device_pci_bus_id": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
+    "wz_hw_queues": (C.c_int, []),
     "wz_set_schedule": (C.c_int, [C.c_int]),
     "wz_get_schedule": (C.c_int, []),
     "wz_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

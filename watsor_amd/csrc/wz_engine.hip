@@ -21,8 +21,26 @@
 
 // Lanes are HIP streams; ROCclr multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and two
 // lanes sharing one queue serialise (measured: 4 lanes 23k frames/s on 4 queues, 34k on 8).  The variable is read
-// when the HIP runtime initialises, i.e. at the first HIP call, which cannot precede this constructor.
-__attribute__((constructor)) static void wz_runtime_defaults() { setenv("GPU_MAX_HW_QUEUES", "8", 0); }
+// when the HIP runtime initialises, i.e. at the first HIP call, which cannot precede this constructor -- unless the
+// process initialised HIP before it loaded this library (wz_hw_queues() still tells what the constructor left).
+// The library needs 8 and takes them whatever the host pinned below that (unset, empty, not a number, 1 .. 7: set
+// to 8); a host that chose 8 or more keeps its choice -- never raised, never lowered, nothing above 32 is written.
+static const char kHwQueuesVar[] = "GPU_MAX_HW_QUEUES";
+static const int kHwQueuesNeeded = 8;
+static int wz_env_hw_queues() {   // the variable as a number; 0: unset, empty or not a number
+    const char* v = getenv(kHwQueuesVar);
+    if (!v || !v[0]) return 0;
+    char* end = nullptr;
+    const long n = strtol(v, &end, 10);
+    while (*end == ' ' || *end == '\t') ++end;
+    return (*end || n < 1 || n > 1 << 20) ? 0 : (int)n;
+}
+#ifndef WZ_KEEP_HOST_HW_QUEUES   // (a scratch measurement build leaves the host's value in force: DESIGN.md section 5)
+__attribute__((constructor)) static void wz_runtime_defaults() {
+    if (wz_env_hw_queues() < kHwQueuesNeeded) setenv(kHwQueuesVar, "8", 1);
+}
+#endif
+extern "C" int wz_hw_queues(void) { return wz_env_hw_queues(); }
 
 thread_local int wz_launch_repeat = 1;
 static thread_local char g_err[512] = "";
@@ -998,6 +1016,19 @@ static int load_blob(wz_engine* e, const char* path) {
     return WZ_OK;
 }
 
+// Every synchronous copy and fill of a product path: issued on lane 0's stream and waited for there -- not hipMemcpy / hipMemset,
+// which ride the null stream and make ROCclr open a hardware queue for it that a lane may then have to share (a process that uses
+// only the product ABI never creates that queue).  Waits for whatever lane 0 has in flight, the source is free on return.
+static int sync_all(wz_engine* e);
+static hipError_t lane0_copy(wz_engine* e, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    const hipError_t err = hipMemcpyAsync(dst, src, bytes, kind, e->stream);
+    return err == hipSuccess ? hipStreamSynchronize(e->stream) : err;
+}
+static hipError_t lane0_fill(wz_engine* e, void* dst, int value, size_t bytes) {
+    const hipError_t err = hipMemsetAsync(dst, value, bytes, e->stream);
+    return err == hipSuccess ? hipStreamSynchronize(e->stream) : err;
+}
+
 extern "C" int wz_create(const char* engine_path, int device, int max_batch, int max_width, int max_height,
                          wz_engine_t** out) {
     if (!engine_path || !out || max_batch < 1 || max_batch > 4095 || max_width < 1 || max_height < 1)
@@ -1081,18 +1112,25 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
             (void)wz_launch_mbconv_cs(mb_args(e, none, e->ops[i]), max_batch, nullptr, true);
         }
 
+    // the lanes' streams before anything is copied: the set-up copies below ride lane 0's (lane0_copy)
+    for (int li = 0; li < e->n_streams; ++li) {
+        CK(hipStreamCreateWithFlags(&e->lanes[li].stream, hipStreamNonBlocking));
+        e->lanes[li].owns_stream = true;
+    }
+    e->stream = e->lanes[0].stream;
+
     const WzBlobHeader& h = e->hdr;
     CK(hipMalloc((void**)&e->d_weights, h.weights_bytes));
-    CK(hipMemcpy(e->d_weights, e->blob.data() + h.weights_off, h.weights_bytes, hipMemcpyHostToDevice));
+    CK(lane0_copy(e, e->d_weights, e->blob.data() + h.weights_off, h.weights_bytes, hipMemcpyHostToDevice));
     if ((env = wz_dev_getenv("WZ_MB_DEBUG")) && atoi(env) != 0) {
         CK(hipMalloc((void**)&e->d_mbdbg, (size_t)h.n_ops * 16 * 8));
-        CK(hipMemset(e->d_mbdbg, 0, (size_t)h.n_ops * 16 * 8));
+        CK(lane0_fill(e, e->d_mbdbg, 0, (size_t)h.n_ops * 16 * 8));
         e->mb_groups.assign(h.n_ops, 0);
     }
     CK(hipMalloc((void**)&e->d_zeros, 4096));
-    CK(hipMemset(e->d_zeros, 0, 4096));
+    CK(lane0_fill(e, e->d_zeros, 0, 4096));
     CK(hipMalloc((void**)&e->d_anchors, (size_t)h.num_anchors * 16));
-    CK(hipMemcpy(e->d_anchors, e->blob.data() + h.anchors_off, (size_t)h.num_anchors * 16, hipMemcpyHostToDevice));
+    CK(lane0_copy(e, e->d_anchors, e->blob.data() + h.anchors_off, (size_t)h.num_anchors * 16, hipMemcpyHostToDevice));
     e->frame_stride = ((size_t)max_width * max_height * 3 + 255) & ~(size_t)255;
     e->ws_bytes = std::max<size_t>((size_t)64 << 20, (size_t)max_batch * ((size_t)32 << 20));
     CK(hipMalloc((void**)&e->d_frames, e->frame_stride * max_batch));
@@ -1120,12 +1158,7 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
         // More lanes than streams (WZ_STREAMS, default 4 = what this stack runs side by side): lane i rides the stream of lane
         // i mod streams, with buffers, graph and host blocks of its own -- the stream always has the next batch queued behind the one
         // it is running, so the host's turnaround between a batch's end and the next submit is not idle time on that queue.
-        if (li < e->n_streams) {
-            CK(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
-            L.owns_stream = true;
-        } else {
-            L.stream = e->lanes[li % e->n_streams].stream;
-        }
+        if (li >= e->n_streams) L.stream = e->lanes[li % e->n_streams].stream;   // (the first n_streams lanes own theirs: created above)
         // activation buffers: one per slot (tensors with disjoint lifetimes share), or one per tensor
         L.tptr.assign(h.n_tensors, nullptr);
         if (e->no_reuse) {
@@ -1166,23 +1199,23 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
         {   // first band of the NMS kernel: start at score 0.25 until the frame slot has a history
             const uint32_t bin0 = 0x3E800000u >> 20;
             std::vector<uint32_t> hint0((size_t)max_batch, bin0);
-            CK(hipMemcpy(pb.hint, hint0.data(), hint0.size() * 4, hipMemcpyHostToDevice));
+            CK(lane0_copy(e, pb.hint, hint0.data(), hint0.size() * 4, hipMemcpyHostToDevice));
             pb.hint_logit = reinterpret_cast<float*>(pb.hint + max_batch);
             uint32_t sbits = bin0 << 20;
             float s0;
             memcpy(&s0, &sbits, 4);
             const float l0 = logf(s0 / (1.0f - s0));   // wz_logit_floor(bin0), k_post.hip
             std::vector<float> hl0((size_t)max_batch, l0 - 0.01f - 1e-3f * fabsf(l0));
-            CK(hipMemcpy(pb.hint_logit, hl0.data(), hl0.size() * 4, hipMemcpyHostToDevice));
+            CK(lane0_copy(e, pb.hint_logit, hl0.data(), hl0.size() * 4, hipMemcpyHostToDevice));
             pb.cbits = reinterpret_cast<uint32_t*>(pb.hint_logit + max_batch);
-            CK(hipMemset(pb.cbits, 0, (size_t)max_batch * ((h.num_anchors * h.num_classes + 31) >> 5) * 4));
+            CK(lane0_fill(e, pb.cbits, 0, (size_t)max_batch * ((h.num_anchors * h.num_classes + 31) >> 5) * 4));
         }
         CK(hipMalloc((void**)&pb.det_boxes, (size_t)max_batch * h.max_total * 16));
         CK(hipMalloc((void**)&pb.det_scores, (size_t)max_batch * h.max_total * 4));
         CK(hipMalloc((void**)&pb.det_classes, (size_t)max_batch * h.max_total * 4));
         CK(hipMalloc((void**)&pb.det_num, (size_t)max_batch * 4));
         CK(hipMalloc((void**)&pb.dbg, (size_t)max_batch * 16 * 8));
-        CK(hipMemset(pb.dbg, 0, (size_t)max_batch * 16 * 8));
+        CK(lane0_fill(e, pb.dbg, 0, (size_t)max_batch * 16 * 8));
         CK(hipHostMalloc((void**)&L.h_desc, sizeof(WzFrameDesc) * max_batch, hipHostMallocDefault));
         if (hipHostGetDevicePointer((void**)&L.h_desc_dev, L.h_desc, 0) != hipSuccess) {
             (void)hipGetLastError();
@@ -1198,7 +1231,7 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
             std::vector<unsigned long long> init((blocks + WZ_STAMP_PRE_BYTES) / 8, 0ull);
             for (size_t k = 0; k < init.size(); k += WZ_STAMP_WORDS)
                 for (int j = 0; j < 64; ++j) init[k + WZ_STAMP_ENTRY + j] = ~0ull;
-            CK(hipMemcpy(L.d_stamp_raw, init.data(), init.size() * 8, hipMemcpyHostToDevice));
+            CK(lane0_copy(e, L.d_stamp_raw, init.data(), init.size() * 8, hipMemcpyHostToDevice));
             const size_t host_pairs = (size_t)(WZ_STAMP_SLOTS + 1 + max_batch) * 2 * 8;
             CK(hipHostMalloc((void**)&L.h_stamps, host_pairs, hipHostMallocMapped));
             memset(L.h_stamps, 0, host_pairs);
@@ -1223,13 +1256,12 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
         CK(hipHostGetDevicePointer((void**)&L.m_status, L.h_status, 0));
         CK(hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
     }
-    e->stream = e->lanes[0].stream;
 
     e->h_cams.resize(WZ_MAX_CAMS);
     memset(e->h_cams.data(), 0, sizeof(WzCamFilter) * WZ_MAX_CAMS);
     e->cam_sat.assign(WZ_MAX_CAMS, nullptr);
     CK(hipMalloc((void**)&e->d_cams, sizeof(WzCamFilter) * WZ_MAX_CAMS));
-    CK(hipMemset(e->d_cams, 0, sizeof(WzCamFilter) * WZ_MAX_CAMS));
+    CK(lane0_fill(e, e->d_cams, 0, sizeof(WzCamFilter) * WZ_MAX_CAMS));
     CK(hipMalloc((void**)&e->d_tmp_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS));
     CK(hipMalloc((void**)&e->d_tmp_pass, WZ_MAX_DETECTIONS));
 
@@ -1247,7 +1279,10 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
     e->stage_names.push_back("post/decode");
     e->stage_names.push_back("post/nms");
     e->stage_names.push_back("post/rows");
-    CK(hipDeviceSynchronize());
+    if (sync_all(e) != WZ_OK) {
+        wz_destroy(e);
+        return WZ_EHIP;
+    }
 #undef CK
     *out = e;
     return WZ_OK;
@@ -1779,7 +1814,7 @@ static int ensure_gated(wz_engine* e, Lane& L) {
     hipError_t err = hipMalloc((void**)&now, cells * 2 * nb);
     if (err == hipSuccess) err = hipMalloc((void**)&rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS * nb);
     if (err == hipSuccess) err = hipMalloc((void**)&cnt, 8 * nb);
-    if (err == hipSuccess) err = hipMemset(cnt, 0, 8 * nb);
+    if (err == hipSuccess) err = lane0_fill(e, cnt, 0, 8 * nb);
     if (err == hipSuccess) err = hipHostMalloc((void**)&hm, (sizeof(WzGateTile) + sizeof(WzGateCommit) + 4) * nb, hipHostMallocMapped);
     if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&L.m_gmeta, hm, 0);
     if (err != hipSuccess) {
@@ -2313,7 +2348,7 @@ extern "C" int wz_set_camera_filter(wz_engine_t* e, int cam, int width, int heig
         uint8_t* d_fill = nullptr;
         hipError_t err = hipMalloc((void**)&sat, plane * n_zones * 4);
         if (err == hipSuccess) err = hipMalloc((void**)&d_fill, (size_t)width * height * n_zones);
-        if (err == hipSuccess) err = hipMemcpy(d_fill, zone_fill, (size_t)width * height * n_zones, hipMemcpyHostToDevice);
+        if (err == hipSuccess) err = lane0_copy(e, d_fill, zone_fill, (size_t)width * height * n_zones, hipMemcpyHostToDevice);
         if (err == hipSuccess) {
             wz_launch_sat(d_fill, sat, width, height, n_zones, e->stream);
             err = hipStreamSynchronize(e->stream);
@@ -2325,7 +2360,7 @@ extern "C" int wz_set_camera_filter(wz_engine_t* e, int cam, int width, int heig
         }
         c.sat = sat;
     }
-    hipError_t err = hipMemcpy(e->d_cams + cam, &c, sizeof(WzCamFilter), hipMemcpyHostToDevice);
+    hipError_t err = lane0_copy(e, e->d_cams + cam, &c, sizeof(WzCamFilter), hipMemcpyHostToDevice);
     if (err != hipSuccess) {
         if (sat) (void)hipFree(sat);
         return wz_fail(WZ_EHIP, "wz_set_camera_filter: %s (camera %d keeps its previous filter)", hipGetErrorString(err), cam);
@@ -2342,7 +2377,7 @@ extern "C" int wz_set_camera_drop(wz_engine_t* e, int cam, int drop) {
     HIPCHK(hipSetDevice(e->device));
     { int _rc = sync_all(e); if (_rc != WZ_OK) return _rc; }
     e->h_cams[cam].enabled = (e->h_cams[cam].enabled & ~2) | (drop ? 2 : 0);
-    HIPCHK(hipMemcpy(e->d_cams + cam, &e->h_cams[cam], sizeof(WzCamFilter), hipMemcpyHostToDevice));
+    HIPCHK(lane0_copy(e, e->d_cams + cam, &e->h_cams[cam], sizeof(WzCamFilter), hipMemcpyHostToDevice));
     return WZ_OK;
 }
 
@@ -2351,7 +2386,7 @@ extern "C" int wz_clear_camera_filter(wz_engine_t* e, int cam) {
     HIPCHK(hipSetDevice(e->device));
     { int _rc = sync_all(e); if (_rc != WZ_OK) return _rc; }
     memset(&e->h_cams[cam], 0, sizeof(WzCamFilter));
-    HIPCHK(hipMemcpy(e->d_cams + cam, &e->h_cams[cam], sizeof(WzCamFilter), hipMemcpyHostToDevice));
+    HIPCHK(lane0_copy(e, e->d_cams + cam, &e->h_cams[cam], sizeof(WzCamFilter), hipMemcpyHostToDevice));
     if (e->cam_sat[cam]) {
         (void)hipFree(e->cam_sat[cam]);
         e->cam_sat[cam] = nullptr;
@@ -2543,13 +2578,13 @@ extern "C" int wz_dev_free(wz_engine_t* e, void* d_ptr) {
 extern "C" int wz_dev_upload(wz_engine_t* e, void* d_dst, const void* h_src, uint64_t bytes) {
     if (!e) return wz_fail(WZ_EINVAL, "wz_dev_upload: null engine");
     HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpy(d_dst, h_src, bytes, hipMemcpyHostToDevice));
+    HIPCHK(lane0_copy(e, d_dst, h_src, bytes, hipMemcpyHostToDevice));
     return WZ_OK;
 }
 extern "C" int wz_dev_download(wz_engine_t* e, void* h_dst, const void* d_src, uint64_t bytes) {
     if (!e) return wz_fail(WZ_EINVAL, "wz_dev_download: null engine");
     HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpy(h_dst, d_src, bytes, hipMemcpyDeviceToHost));
+    HIPCHK(lane0_copy(e, h_dst, d_src, bytes, hipMemcpyDeviceToHost));
     return WZ_OK;
 }
 

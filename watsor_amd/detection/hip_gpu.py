@@ -267,10 +267,30 @@ class HipObjectDetector:
         for where, spec in [("tiles", self.__tiles_default)] + [("tiles[%r]" % n, t) for n, t in self.__tiles_by_name.items()]:
             if spec is not None and spec["count"] > max_batch:
                 raise ValueError("%s: %d tiles per frame exceed max_batch %d" % (where, spec["count"], max_batch))
+        self._warn_short_of_queues()
         self.__engine = HipEngine(engine_path, device, max_batch, max_width, max_height, schedule=schedule)
         self.__device = device
         self.__filters = []
         self.__pinned = []
+
+    _queues_warned = False
+
+    def _warn_short_of_queues(self) -> None:
+        """One warning per process when GPU_MAX_HW_QUEUES is below two per lane (include/watsor_hip.h: wz_hw_queues): lanes that share a
+        hardware queue serialise.  The library sets 8 when it loads, so this means the variable was changed afterwards -- or that the
+        process initialised HIP first and the figure below is not even what the runtime uses."""
+        from ..runtime import hw_queues
+        try:
+            lanes = int(os.environ.get("WZ_LANES", ""))        # the lanes wz_create will make: WZ_LANES = 1 .. 8, else 4
+        except ValueError:
+            lanes = 0
+        have, want = hw_queues(), 2 * (lanes if 1 <= lanes <= 8 else 4)
+        if have < want and not HipObjectDetector._queues_warned:
+            HipObjectDetector._queues_warned = True
+            import logging
+            logging.getLogger(__name__).warning(
+                "GPU_MAX_HW_QUEUES is %s, %d lanes want %d hardware queues: lanes that share a queue run one after the other "
+                "(set it to %d or leave it unset before this process's first HIP call)" % (have or "not a number", want // 2, want, want))
 
     @staticmethod
     def _several_gpus() -> bool:

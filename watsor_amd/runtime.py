@@ -29,6 +29,12 @@ def device_count() -> int:
     return int(_lib.load().wz_device_count())
 
 
+def hw_queues(dev: bool = False) -> int:
+    """GPU_MAX_HW_QUEUES in the C environment after the library loaded (include/watsor_hip.h: wz_hw_queues; 0: not a number): the
+    library raises anything below 8 to 8, and an engine wants two per lane."""
+    return int(_lib.load(dev=dev).wz_hw_queues())
+
+
 SCHEDULES = {"throughput": _lib.WZ_SCHEDULE_THROUGHPUT, "latency": _lib.WZ_SCHEDULE_LATENCY}
 
 
@@ -514,6 +520,12 @@ class HipEngine:
         self._dev_allocs.append(p.value)
         self._ck(self._lib.wz_dev_upload(self._h, p, C.c_void_p(arr.ctypes.data), arr.nbytes))
         return p.value
+
+    def download(self, d_ptr: int, nbytes: int) -> np.ndarray:
+        """`nbytes` of device memory at `d_ptr` as a uint8 array (wz_dev_download: waits for lane 0, like `upload`)."""
+        out = np.empty(int(nbytes), np.uint8)
+        self._ck(self._lib.wz_dev_download(self._h, C.c_void_p(out.ctypes.data), C.c_void_p(d_ptr), out.nbytes))
+        return out
 
     def free(self, d_ptr: int) -> None:
         self._dev_allocs.remove(d_ptr)
