@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import conftest
+import refusal_golden
 from pixfmt_oracle import frame_from_rgb
 from test_gpu_bound_frames import arena_with_frames
 from watsor_amd import _lib
@@ -321,10 +322,14 @@ def test_refusals_name_the_numbers_and_change_nothing(eng):
         assert t.run(0, [5])[0].tobytes() == first.tobytes() and eng.gate_stats(0)[0] == [0]
         t.rows.view(np.uint8)[...] = 0xA5
 
+        seen = []
+
         def refused(rc_msg, code, *names):
             rc, msg = rc_msg
             assert rc == code, (rc, msg)
             assert all(str(n) in msg for n in names), msg
+            refusal_golden.check("bound_tiles", len(seen), rc, msg)      # (the cases in the order they stand below)
+            seen.append(msg)
             assert t.untouched()
             with pytest.raises(ValueError):
                 eng.collect_bound(2)                                     # nothing is in flight on the lane

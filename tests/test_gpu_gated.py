@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import gate_oracle as go
+import refusal_golden
 import tile_oracle as to
 from conftest import make_engine
 from test_gpu_tiled import EVEN_RECTS, RECTS, SIZE, crop_cases, nv12_of, random_frame
@@ -295,7 +296,7 @@ def test_refusals_write_nothing_and_keep_the_state(eng, cams):
         ([frame], [cams[0]], None, 0.6, -1.0, _lib.WZ_EINVAL),
         ([], [], None, 0.6, 1.0, _lib.WZ_ELIMIT),
     ]
-    for frames, cam_ids, formats, iou, ios, code in bad:
+    for case, (frames, cam_ids, formats, iou, ios, code) in enumerate(bad):
         before = eng.gate_stats(0)
         n, m = len(frames), max(len(frames), 1)
         rows = np.full((m, 100 * ROW_DTYPE.itemsize), 0xA5, np.uint8)
@@ -309,20 +310,26 @@ def test_refusals_write_nothing_and_keep_the_state(eng, cams):
         pv = (C.c_void_p * m)(*[p.ctypes.data for p in passes])
         rc = lib.wz_detect_gated(h, n, fptr, ws, hs, fmtv, camv, iou, ios, outs, pv, None)
         assert rc == code, (cam_ids, formats, iou, ios, _lib.last_error(lib))
+        refusal_golden.check("gated", "%d/wz_detect_gated" % case, rc, _lib.last_error(lib))
         assert (rows == 0xA5).all() and (passes == 0xA5).all()
         # the device entry point refuses the same way (host pointers stand in: a refused call reads no frame) and enqueues nothing
         rc = lib.wz_submit_gated_device(h, 0, n, fptr, ws, hs, fmtv, camv, iou, ios)
         assert rc == code, (cam_ids, formats, iou, ios, _lib.last_error(lib))
+        refusal_golden.check("gated", "%d/wz_submit_gated_device" % case, rc, _lib.last_error(lib))
         after = eng.gate_stats(0)
         assert after[0] == before[0] and [a.tolist() for a in after[1]] == [b.tolist() for b in before[1]]
         rows, _, ran, act = gated(eng, frame, cams[0])                         # the state is intact: a still frame runs nothing
         assert ran == 0 and act.tolist() == [0, 0, 0] and rows.tobytes() == first.tobytes()
     # a layout the engine refuses leaves the camera with the one it had
-    for tiles, gate, width in (([(0, 0, 200, 10)], (8, 1, 0), 96), (RECTS, (256, 1, 0), 96), (RECTS, (8, 0, 0), 96), (RECTS, (8, 1, -1), 96),
-                               (RECTS * 3, (8, 1, 0), 96), ([(0, 0, 700, 10)], (8, 1, 0), 800)):
+    for case, (tiles, gate, width) in enumerate((([(0, 0, 200, 10)], (8, 1, 0), 96), (RECTS, (256, 1, 0), 96), (RECTS, (8, 0, 0), 96),
+                                                 (RECTS, (8, 1, -1), 96), (RECTS * 3, (8, 1, 0), 96), ([(0, 0, 700, 10)], (8, 1, 0), 800))):
         with pytest.raises(ValueError):
             eng.set_camera_tiles(cams[0], width, 64, tiles, *gate)
         assert gated(eng, frame, cams[0])[2] == 0
+        arr = (C.c_int32 * (4 * len(tiles)))(*[v for r in tiles for v in r])
+        rc = lib.wz_set_camera_tiles(h, cams[0], width, 64, FMT_RGB24, len(tiles), arr, (C.c_int32 * 4)(*gate, 0))
+        refusal_golden.check("gated", "layout/%d" % case, rc, _lib.last_error(lib))
+        assert rc != 0 and gated(eng, frame, cams[0])[2] == 0
 
 
 # ---- 11. plugin -------------------------------------------------------------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import refusal_golden
 import tile_oracle as to
 from conftest import make_engine
 from test_tile_oracle import KNOWN, rows_of
@@ -293,7 +294,7 @@ def test_refusals_write_nothing_and_leave_the_engine_usable(eng):
     lib, h = eng._lib, eng._h
     good = np.zeros(100, ROW_DTYPE)
     eng.detect_tiled([frame], [RECTS], [good], ios=0.6)
-    for frames, tiles, formats, iou, ios, code in bad:
+    for case, (frames, tiles, formats, iou, ios, code) in enumerate(bad):
         n = len(frames)
         rows = np.full((max(n, 1), 100 * 72), 0xA5, np.uint8)
         passes = np.full((max(n, 1), 100), 0xA5, np.uint8)
@@ -306,15 +307,18 @@ def test_refusals_write_nothing_and_leave_the_engine_usable(eng):
         pv = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in passes][:max(n, 1)])
         rc = lib.wz_detect_tiled(h, n, fptr, ws, hs, fmtv, None, counts, tptrs, iou, ios, outs, pv, None)
         assert rc == code, (tiles, formats, iou, ios, _lib.last_error(lib))
+        refusal_golden.check("tiled", "%d/wz_detect_tiled" % case, rc, _lib.last_error(lib))
         assert (rows == 0xA5).all() and (passes == 0xA5).all()
         # the device entry point refuses the same way (host pointers stand in: a refused call reads no frame) and enqueues nothing
         rc = lib.wz_submit_tiled_device(h, 2, n, fptr, ws, hs, fmtv, None, counts, tptrs, iou, ios)
         assert rc == code, (tiles, formats, iou, ios, _lib.last_error(lib))
+        refusal_golden.check("tiled", "%d/wz_submit_tiled_device" % case, rc, _lib.last_error(lib))
     counts, tptrs, keep, _, _ = eng._tile_args([one * 5, one * 4], 2, 0.6, 1.0)
     rc = lib.wz_detect_tiled(h, 2, (C.c_void_p * 2)(frame.ctypes.data, frame.ctypes.data), (C.c_int32 * 2)(96, 96), (C.c_int32 * 2)(64, 64), None,
                              None, counts, tptrs, 0.6, 1.0, None, None, None)
     assert rc == _lib.WZ_ELIMIT
     assert "9" in _lib.last_error(lib) and "8" in _lib.last_error(lib)               # the message names both numbers
+    refusal_golden.check("tiled", "nine_tiles_no_outputs", rc, _lib.last_error(lib))
     again = np.zeros(100, ROW_DTYPE)
     eng.detect_tiled([frame], [RECTS], [again], ios=0.6)
     assert again.tobytes() == good.tobytes()

@@ -1,0 +1,254 @@
+// Internal to the runtime: struct wz_engine, and what wz_tiles.hip (tiled, gated and tiled frame-table detection) takes from
+// wz_engine.hip (everything else).  Nothing here is part of the C ABI: these functions keep their C++ names.
+#pragma once
+#include <map>
+#include <string>
+#include <vector>
+
+#include "wz_common.h"
+
+// leave the calling function with the failure of a HIP call as wz_last_error ...
+#define HIPCHK(expr)                                                                                       \
+    do {                                                                                                   \
+        hipError_t _e = (expr);                                                                            \
+        if (_e != hipSuccess) return wz_set_error(WZ_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(_e), \
+                                                  __FILE__, __LINE__);                                     \
+    } while (0)
+// ... and of a step that answers in the library's own codes (wz_last_error is already set)
+#define WZCHK(expr)                     \
+    do {                                \
+        const int _rc = (expr);         \
+        if (_rc != WZ_OK) return _rc;   \
+    } while (0)
+
+struct wz_engine;
+
+// tiled detection (wz_submit_tiled_device / wz_detect_tiled): a lane's share, allocated the first time the lane sees a tiled call
+struct TileLane {
+    uint8_t* d_tiles = nullptr;          // tile staging [max_batch][frame_stride]: the crop launch's output, the batch's frames
+    WzMergeCand* d_tcand = nullptr;      // the merge kernel's scratch [max_batch][100]
+    wz_detection_t* h_trows = nullptr;   // pinned, device-mapped: the merged rows [max_batch][100] ...
+    uint8_t* h_tpass = nullptr;          // ... and their pass bytes, written by the merge launch (and the filter launches behind it)
+    WzMergeFrame* h_tmeta = nullptr;     // pinned, device-mapped: WzMergeFrame[max_batch], then the tiles' origins int32[max_batch][2]
+    wz_detection_t* m_trows = nullptr;   // device addresses of the three
+    uint8_t* m_tpass = nullptr;
+    WzMergeFrame* m_tmeta = nullptr;
+    int tiled = 0;                       // frames of the tiled batch in flight (its rows are in h_trows); 0: the batch is not tiled
+    int alloc(wz_engine* e);             // (wz_tiles.hip) lazy; all or nothing
+    void release();
+};
+// gated tiled detection (wz_submit_gated_device / wz_detect_gated): allocated the first time the lane sees a gated call
+struct GateLane {
+    uint16_t* d_gnow = nullptr;          // the activity launch's new grids [max_batch][gate_cells]
+    wz_detection_t* d_grows = nullptr;   // fresh or cached rows of every tile of the call, in tile order [max_batch][100]: what the merge reads
+    int32_t* d_gcount = nullptr;         // the activity kernel's counters [max_batch][2]
+    WzGateTile* h_gmeta = nullptr;       // pinned, device-mapped: WzGateTile[max_batch], WzGateCommit[max_batch], activity int32[max_batch]
+    WzGateTile* m_gmeta = nullptr;       // ... as the device sees it
+    std::vector<uint64_t> g_ran;         // the last gated call accepted on this lane (wz_gate_stats): per frame, bit t = tile t ran ...
+    std::vector<int32_t> g_act;          // ... and every tile's activity, in tile order
+    int g_tiles = 0, g_crows = 0, g_cols = 0;   // that call's launches: tiles, the most cell rows / columns of a tile
+    int alloc(wz_engine* e);
+    void release();
+};
+
+struct wz_engine {
+    int device = 0;
+    hipStream_t stream = nullptr;            // = lanes[0].stream (stage-level entry points, filters)
+    std::string name;
+    std::vector<uint8_t> blob;
+    WzBlobHeader hdr;
+    const WzTensorDesc* tensors = nullptr;
+    const WzOpDesc* ops = nullptr;
+    int max_batch = 0, max_w = 0, max_h = 0;
+    bool no_reuse = false, use_graph = true, use_splitk = true;
+    bool graph_adaptive = false;   // use_graph && WZ_GRAPH unset: a batch that finds every other lane idle is launched kernel by kernel (wz_create)
+    bool fuse_decode = true;   // WZ_FUSE_DECODE=0: keep wz_k_decode as its own launch
+    bool defer_heads = true;   // the SSD heads' split-K reductions run as one launch after the last head (WZ_DEFER_HEADS=0: one each)
+    bool conv_wide = true;     // the big SSD heads on the wide tile kernel (k_conv_wide.hip); WZ_CONV_WIDE=0: on wz_k_conv_rs
+    int wide_min_m = 1;        // WZ_WIDE_MIN_M=n: heads with fewer output pixels than this (per batch) stay on wz_k_conv_group
+    int wide_T = 0;            // WZ_WIDE_T=n: K steps per slice of that kernel (0: chosen per launch by wz_choose_wide_T)
+                                  // 2 (round 5): only the chain behind the 3x3 map -- its last four convolutions, 0.8 MB of weights per frame's workgroup
+    bool desc_by_value = true;    // the frame descriptors travel as arguments of the resize kernel (WZ_DESC_ARGS=0: zero-copy / copied)
+    bool desc_zero_copy = true;   // the resize kernel reads the frame descriptors from page-locked host memory (WZ_DESC_COPY=1: copied first)
+    bool pre_rows = false;        // WZ_PRE_ROWS=1: every batch on the row-staged form of the resize kernel (k_preprocess.hip:
+                                  // wz_k_preprocess_rows); default: only batches with a frame that is read in place (the per-pixel form is
+                                  // faster out of HBM: 51.5 k against 48.0 k frames/s on the headline workload, profiles/r04_host_read_ab.txt)
+    int pre_rows_lds = 0;         // ... and its LDS bytes for the widest frame this engine takes
+    int host_read = 2;            // page-locked host frames (WZ_HOST_READ): 0 = staged by one DMA each, 1 = read in place by the resize kernel
+                                  // (no copy), 2 (default) = read in place when the resize skips rows (vertical down-scale >= 2: 1080p RGB24
+                                  // 8.0 k -> 13.0 k frames/s, NV12 15.6 k -> 18.7 k), staged otherwise (640x480 in place: 26 k against 33 k)
+    struct HostRange { const uint8_t* host; uint64_t bytes; const uint8_t* dev; };
+    std::vector<HostRange> host_ranges;   // what wz_host_register page-locked, with the address the device sees it at
+    int wide_cus = 128;        // CUs the wide head kernel's K slices are sized for when several lanes are in flight (WZ_WIDE_CUS)
+    int num_cus = 256;         // compute units of the device (the wide head kernel sizes its K slices for one round over them)
+
+    uint8_t* d_weights = nullptr;
+    half_t* d_zeros = nullptr;               // 4 KiB of zeros
+    unsigned long long* d_mbdbg = nullptr;   // WZ_MB_DEBUG=1: [n_ops][16] phase timestamps of the fused-block kernels
+    std::vector<int> mb_groups;
+    float* d_anchors = nullptr;
+    uint8_t* d_frames = nullptr;             // staging for host frames [max_batch][max_w*max_h*3]
+    size_t frame_stride = 0;
+    WzPostConsts pc;
+    size_t post_scratch_bytes = 0;
+    size_t ws_bytes = 0;       // split-K / channel-group workspace per lane: 32 MiB per frame of max_batch, at least 64 MiB (the heads'
+                               // parked partial sums take ~10 MiB per frame, the other ops keep the lower half)
+
+    // A lane is everything one in-flight batch needs: its own stream, activation buffers, head
+    // outputs, post-processing scratch, descriptor/result blocks and captured graphs.  Lanes run
+    // concurrently on the GPU (a batch-8 layer fills only a fraction of the 256 CUs), slot i of the
+    // API is lane i.
+    struct Lane {
+        hipStream_t stream = nullptr;
+        bool owns_stream = false;            // false: the stream belongs to lane (index mod n_streams)
+        std::vector<void*> bufs;             // owned activation buffers
+        std::vector<half_t*> tptr;           // tensor index -> device pointer
+        float* d_box_enc = nullptr;
+        float* d_logits = nullptr;
+        float* d_ws = nullptr;
+        int launch_failed = 0;               // op index + 1 of a block no kernel took at launch time (enqueue_network), else 0
+        bool decode_fused = false;           // set by enqueue_network: the grouped head reduce decoded the boxes
+        bool cands_listed = false;           // ... and listed the candidates of the NMS kernel's first band
+        uint8_t* d_frames = nullptr;         // staging for host frames of this lane [max_batch][frame_stride] (lazy)
+        std::map<int, int> graph_nodes;      // batch size -> nodes of the captured graph (kernels + the descriptor copy)
+        WzPostBuffers post;
+        void* d_post_scratch = nullptr;      // post.hint, post.hint_logit, post.cbits
+        WzFrameDesc* h_desc = nullptr;       // pinned
+        WzFrameDesc* h_desc_dev = nullptr;   // ... and its address as the device sees it (nullptr: not mapped)
+        WzFrameDesc* d_desc = nullptr;
+        wz_detection_t* d_rows = nullptr;
+        uint8_t* d_pass = nullptr;
+        wz_detection_t* h_rows = nullptr;    // pinned, device-mapped: wz_k_rows writes it directly
+        uint8_t* h_pass = nullptr;
+        wz_detection_t* m_rows = nullptr;    // device addresses of h_rows / h_pass
+        uint8_t* m_pass = nullptr;
+        uint32_t* h_status = nullptr;        // pinned, device-mapped: one word per frame, non-zero = the frame's rows may be short (wz_k_nms)
+        uint32_t* m_status = nullptr;
+        std::vector<int32_t> bound_idx;      // frame-table entries of the batch in flight (empty: not a bound batch)
+        std::vector<int32_t> bound_src;      // the last tiled or gated bound batch accepted on this lane: 1 = frame i was read in place, 0 = staged
+        TileLane tile;
+        GateLane gate;
+        hipEvent_t done = nullptr;
+        int n = 0;
+        bool rows = false;                       // the batch being enqueued runs the row-staged resize kernel (a frame of it is read in place)
+        int key = 0;                             // graph key of the batch in flight: batch size | rows << 16
+        std::map<int, hipGraphExec_t> graphs;    // key = batch size | (row-staged resize kernel) << 16
+        std::map<int, hipGraph_t> graph_src;     // the captured graph itself, kept where one of its node handles is
+        std::map<int, hipGraphNode_t> pre_nodes; // ... and the resize kernel's node in that graph (its arguments carry the frame
+                                                 // descriptors and are rewritten before every replay), if it takes them by value
+        // WZ_LANE_STAMPS builds (wz_common.h): the lane's launch blocks [WZ_STAMP_SLOTS][WZ_STAMP_WORDS], the resize kernel's block and the
+        // descriptors behind it in ONE allocation; the page-locked pairs the host reads; launches stamped so far in the batch being enqueued
+        unsigned char* d_stamp_raw = nullptr;
+        unsigned long long* d_stamps = nullptr;
+        unsigned long long* d_stamps_pre = nullptr;
+        unsigned long long* h_stamps = nullptr;
+        unsigned long long* m_stamps = nullptr;
+        int stamp_next = 1;
+        bool lone = false;                       // the batch being enqueued goes kernel by kernel because the other lanes are idle (run_batch)
+        std::map<int, std::vector<WzLaunchNote>> launch_notes;   // graph key -> what was launched, in order (grid, block, LDS, kernel)
+        WzDescPack pack;                         // storage behind that node's kernelParams
+        const WzFrameDesc* pre_frames = nullptr;
+        int pre_size = 0, pre_half_pixel = 0;
+        half_t* pre_out = nullptr;
+        WzFrameDesc* pre_keep = nullptr;
+        void* pre_kp[6];
+    };
+    Lane lanes[WZ_SLOTS];
+    int n_lanes = 4;   // default; WZ_LANES overrides (1..WZ_SLOTS)
+    int n_streams = 4; // HIP streams the lanes are spread over (WZ_STREAMS); more than 4 run slower on this stack (HISTORY.md part B)
+
+    // the worker's frame table (wz_bind_frames): one entry per Frame of every FrameBuffer, described once instead of once per batch
+    struct BoundFrame {
+        const uint8_t* host;   // the frame's pixels (host address)
+        const uint8_t* dev;    // the same bytes as the device sees them when the frame lies in a wz_host_register range, else nullptr
+        int32_t w, h, fmt, cam;
+        uint64_t bytes;
+        wz_detection_t* rows;  // Header.detections of that frame (host), written by wz_collect_bound
+    };
+    std::vector<BoundFrame> bound;
+    // the tiled description of a table entry (wz_bind_tiles).  Kept beside the table, and EMPTY while no entry has one: the untiled
+    // wz_submit_bound looks at nothing but that.
+    enum { BOUND_PLAIN = 0, BOUND_TILED = 1, BOUND_GATED = 2 };
+    struct BoundTiles {
+        int kind = BOUND_PLAIN;
+        std::vector<wz_tile_t> tiles;   // BOUND_TILED: the entry's rectangles (BOUND_GATED: its camera's, looked up at submit)
+        double iou = 0.0, ios = 0.0;    // the merge thresholds of both kinds
+    };
+    std::vector<BoundTiles> bound_tiles;   // [bound.size()] or empty
+
+    std::vector<WzCamFilter> h_cams;
+    WzCamFilter* d_cams = nullptr;
+    std::vector<int32_t*> cam_sat;
+    wz_detection_t* d_tmp_rows = nullptr;
+    uint8_t* d_tmp_pass = nullptr;
+
+    // gated tiled detection: a camera's tile layout and its state in device memory (wz_set_camera_tiles); empty until a camera is set
+    struct GateCam {
+        int w = 0, h = 0, base = 0;              // the frames this layout was set for: size and base format
+        wz_tile_gate_t gate = {0, 1, 0, 0};
+        std::vector<wz_tile_t> tiles;
+        std::vector<int> cols, crows;            // cells of every tile
+        std::vector<size_t> grid_off;            // first cell of every tile's reference grid in d_ref
+        uint16_t* d_ref = nullptr;               // the tiles' reference grids, one after the other
+        wz_detection_t* d_rows = nullptr;        // the tiles' cached rows [tiles][100]
+        std::vector<uint8_t> has_ref;            // the tile has a reference (and cached rows)
+        std::vector<int> skipped;                // gated calls of this camera in a row that skipped the tile
+        int lane = -1;                           // the lane whose gated batch last wrote this state
+        void release();                          // (wz_tiles.hip) frees the two device blocks
+    };
+    std::map<int, GateCam> gate_cams;
+
+    std::vector<std::string> stage_names;
+};
+typedef wz_engine::Lane Lane;
+
+// ---- wz_engine.hip, for wz_tiles.hip --------------------------------------------------------------------------------------------
+const char* fmt_refusal(int w, int h, int fmt);
+int fill_desc(wz_engine* e, int slot, int n, const uint8_t* const* d_rgb, const int* w, const int* h, const int* fmt, const int* cam);
+int run_batch(wz_engine* e, int slot, int n);
+int stage_frame(wz_engine* e, Lane& L, int i, const uint8_t* host, uint64_t bytes, const uint8_t** where);
+const uint8_t* device_view(wz_engine* e, const uint8_t* host, uint64_t bytes);
+bool read_in_place(const wz_engine* e, int h);
+int sync_all(wz_engine* e);
+hipError_t lane0_fill(wz_engine* e, void* dst, int value, size_t bytes);
+// ---- wz_tiles.hip, for wz_submit_bound: a batch with a tiled or gated entry ---------------------------------------------------------
+int submit_bound_tiles(wz_engine* e, int slot, int n, const int32_t* entries);
+
+// Why frame i of a call is refused (wz_last_error is set, the code returned), or WZ_OK: the checks named in `checks`, in this order.
+// what: "frame" | "frame-table entry"; p: the frame's pointer, null also when another pointer of the frame is; pf: its format word.
+enum { FC_PTR = 1, FC_FMT = 2, FC_LIMIT = 4, FC_CAM_ID = 8, FC_CAM_FILTER = 16 };
+static inline int frame_refusal(const wz_engine* e, const char* what, int i, const void* p, int w, int h, int pf, int cam, unsigned checks) {
+    if ((checks & FC_PTR) && (!p || w < 1 || h < 1)) return wz_set_error(WZ_EINVAL, "%s %d: bad pointer or size", what, i);
+    if ((checks & FC_FMT) && !wz_frame_bytes(w, h, pf))
+        return wz_set_error(WZ_EINVAL, "%s %d: pixel format 0x%x at %dx%d: %s", what, i, pf, w, h, fmt_refusal(w, h, pf));
+    if ((checks & FC_LIMIT) && (w > e->max_w || h > e->max_h || (size_t)w * h * 3 > e->frame_stride))
+        return wz_set_error(WZ_ELIMIT, "%s %d is %dx%d, engine was created for at most %dx%d", what, i, w, h, e->max_w, e->max_h);
+    if ((checks & FC_CAM_ID) && cam >= WZ_MAX_CAMS) return wz_set_error(WZ_ELIMIT, "camera id %d >= %d", cam, WZ_MAX_CAMS);
+    if ((checks & FC_CAM_FILTER) && cam >= 0 && e->h_cams[cam].enabled && (e->h_cams[cam].width != w || e->h_cams[cam].height != h))
+        return wz_set_error(WZ_EINVAL, "%s %d is %dx%d but camera %d filter was set for %dx%d", what, i, w, h, cam, e->h_cams[cam].width,
+                            e->h_cams[cam].height);
+    return WZ_OK;
+}
+
+// A bound batch's table entries as the arrays fill_desc and the tile checks take: one pass over the table, two allocations.
+struct BoundBatch {
+    std::vector<const uint8_t*> ptr;   // the frames' host addresses; the caller replaces each by where the device finds the frame
+    std::vector<int> v;                // w, h, fmt, cam: [4][n]
+    int *w, *h, *fmt, *cam;
+};
+static inline void bound_gather(const wz_engine* e, int n, const int32_t* entries, BoundBatch& b) {
+    b.ptr.resize(n);
+    b.v.resize(4 * (size_t)n);
+    b.w = b.v.data(); b.h = b.w + n; b.fmt = b.h + n; b.cam = b.fmt + n;
+    for (int i = 0; i < n; ++i) {
+        const wz_engine::BoundFrame& f = e->bound[entries[i]];
+        b.ptr[i] = f.host; b.w[i] = f.w; b.h[i] = f.h; b.fmt[i] = f.fmt; b.cam[i] = f.cam;
+    }
+}
+// ... and the lane they go to, drained: its previous batch (and its reads of the staging area) is done
+static inline int bound_drain(wz_engine* e, int slot) {
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipEventSynchronize(e->lanes[slot].done));
+    if (!e->lanes[slot].d_frames) return wz_set_error(WZ_EINVAL, "wz_submit_bound: lane %d has no staging area", slot);
+    return WZ_OK;
+}

@@ -13,11 +13,8 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <map>
-#include <string>
-#include <vector>
 
-#include "wz_common.h"
+#include "wz_engine.h"
 
 // Lanes are HIP streams; ROCclr multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and two
 // lanes sharing one queue serialise (measured: 4 lanes 23k frames/s on 4 queues, 34k on 8).  The variable is read
@@ -44,13 +41,6 @@ extern "C" int wz_hw_queues(void) { return wz_env_hw_queues(); }
 
 thread_local int wz_launch_repeat = 1;
 static thread_local char g_err[512] = "";
-static int wz_fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 int wz_set_error(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -58,12 +48,7 @@ int wz_set_error(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
-#define HIPCHK(expr)                                                                                  \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess) return wz_fail(WZ_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(_e), \
-                                             __FILE__, __LINE__);                                     \
-    } while (0)
+static int (*const wz_fail)(int, const char*, ...) = wz_set_error;   // (this file's older name for it)
 
 struct StageTimer {
     std::vector<hipEvent_t> ev;
@@ -77,172 +62,6 @@ struct StageTimer {
         }
         (void)hipEventRecord(ev[used++], s);
     }
-};
-
-struct wz_engine {
-    int device = 0;
-    hipStream_t stream = nullptr;            // = lanes[0].stream (stage-level entry points, filters)
-    std::string name;
-    std::vector<uint8_t> blob;
-    WzBlobHeader hdr;
-    const WzTensorDesc* tensors = nullptr;
-    const WzOpDesc* ops = nullptr;
-    int max_batch = 0, max_w = 0, max_h = 0;
-    bool no_reuse = false, use_graph = true, use_splitk = true;
-    bool graph_adaptive = false;   // use_graph && WZ_GRAPH unset: a batch that finds every other lane idle is launched kernel by kernel (wz_create)
-    bool fuse_decode = true;   // WZ_FUSE_DECODE=0: keep wz_k_decode as its own launch
-    bool defer_heads = true;   // the SSD heads' split-K reductions run as one launch after the last head (WZ_DEFER_HEADS=0: one each)
-    bool conv_wide = true;     // the big SSD heads on the wide tile kernel (k_conv_wide.hip); WZ_CONV_WIDE=0: on wz_k_conv_rs
-    int wide_min_m = 1;        // WZ_WIDE_MIN_M=n: heads with fewer output pixels than this (per batch) stay on wz_k_conv_group
-    int wide_T = 0;            // WZ_WIDE_T=n: K steps per slice of that kernel (0: chosen per launch by wz_choose_wide_T)
-                                  // 2 (round 5): only the chain behind the 3x3 map -- its last four convolutions, 0.8 MB of weights per frame's workgroup
-    bool desc_by_value = true;    // the frame descriptors travel as arguments of the resize kernel (WZ_DESC_ARGS=0: zero-copy / copied)
-    bool desc_zero_copy = true;   // the resize kernel reads the frame descriptors from page-locked host memory (WZ_DESC_COPY=1: copied first)
-    bool pre_rows = false;        // WZ_PRE_ROWS=1: every batch on the row-staged form of the resize kernel (k_preprocess.hip:
-                                  // wz_k_preprocess_rows); default: only batches with a frame that is read in place (the per-pixel form is
-                                  // faster out of HBM: 51.5 k against 48.0 k frames/s on the headline workload, profiles/r04_host_read_ab.txt)
-    int pre_rows_lds = 0;         // ... and its LDS bytes for the widest frame this engine takes
-    int host_read = 2;            // page-locked host frames (WZ_HOST_READ): 0 = staged by one DMA each, 1 = read in place by the resize kernel
-                                  // (no copy), 2 (default) = read in place when the resize skips rows (vertical down-scale >= 2: 1080p RGB24
-                                  // 8.0 k -> 13.0 k frames/s, NV12 15.6 k -> 18.7 k), staged otherwise (640x480 in place: 26 k against 33 k)
-    struct HostRange { const uint8_t* host; uint64_t bytes; const uint8_t* dev; };
-    std::vector<HostRange> host_ranges;   // what wz_host_register page-locked, with the address the device sees it at
-    int wide_cus = 128;        // CUs the wide head kernel's K slices are sized for when several lanes are in flight (WZ_WIDE_CUS)
-    int num_cus = 256;         // compute units of the device (the wide head kernel sizes its K slices for one round over them)
-
-    uint8_t* d_weights = nullptr;
-    half_t* d_zeros = nullptr;               // 4 KiB of zeros
-    unsigned long long* d_mbdbg = nullptr;   // WZ_MB_DEBUG=1: [n_ops][16] phase timestamps of the fused-block kernels
-    std::vector<int> mb_groups;
-    float* d_anchors = nullptr;
-    uint8_t* d_frames = nullptr;             // staging for host frames [max_batch][max_w*max_h*3]
-    size_t frame_stride = 0;
-    WzPostConsts pc;
-    size_t post_scratch_bytes = 0;
-    size_t ws_bytes = 0;       // split-K / channel-group workspace per lane: 32 MiB per frame of max_batch, at least 64 MiB (the heads'
-                               // parked partial sums take ~10 MiB per frame, the other ops keep the lower half)
-
-    // A lane is everything one in-flight batch needs: its own stream, activation buffers, head
-    // outputs, post-processing scratch, descriptor/result blocks and captured graphs.  Lanes run
-    // concurrently on the GPU (a batch-8 layer fills only a fraction of the 256 CUs), slot i of the
-    // API is lane i.
-    struct Lane {
-        hipStream_t stream = nullptr;
-        bool owns_stream = false;            // false: the stream belongs to lane (index mod n_streams)
-        std::vector<void*> bufs;             // owned activation buffers
-        std::vector<half_t*> tptr;           // tensor index -> device pointer
-        float* d_box_enc = nullptr;
-        float* d_logits = nullptr;
-        float* d_ws = nullptr;
-        int launch_failed = 0;               // op index + 1 of a block no kernel took at launch time (enqueue_network), else 0
-        bool decode_fused = false;           // set by enqueue_network: the grouped head reduce decoded the boxes
-        bool cands_listed = false;           // ... and listed the candidates of the NMS kernel's first band
-        uint8_t* d_frames = nullptr;         // staging for host frames of this lane [max_batch][frame_stride] (lazy)
-        std::map<int, int> graph_nodes;      // batch size -> nodes of the captured graph (kernels + the descriptor copy)
-        WzPostBuffers post;
-        void* d_post_scratch = nullptr;      // post.hint, post.hint_logit, post.cbits
-        WzFrameDesc* h_desc = nullptr;       // pinned
-        WzFrameDesc* h_desc_dev = nullptr;   // ... and its address as the device sees it (nullptr: not mapped)
-        WzFrameDesc* d_desc = nullptr;
-        wz_detection_t* d_rows = nullptr;
-        uint8_t* d_pass = nullptr;
-        wz_detection_t* h_rows = nullptr;    // pinned, device-mapped: wz_k_rows writes it directly
-        uint8_t* h_pass = nullptr;
-        wz_detection_t* m_rows = nullptr;    // device addresses of h_rows / h_pass
-        uint8_t* m_pass = nullptr;
-        uint32_t* h_status = nullptr;        // pinned, device-mapped: one word per frame, non-zero = the frame's rows may be short (wz_k_nms)
-        uint32_t* m_status = nullptr;
-        std::vector<int32_t> bound_idx;      // frame-table entries of the batch in flight (empty: not a bound batch)
-        std::vector<int32_t> bound_src;      // the last tiled or gated bound batch accepted on this lane: 1 = frame i was read in place, 0 = staged
-        // tiled detection (wz_submit_tiled_device / wz_detect_tiled), all allocated the first time the lane sees a tiled call (ensure_tiled):
-        uint8_t* d_tiles = nullptr;          // tile staging [max_batch][frame_stride]: the crop launch's output, the batch's frames
-        WzMergeCand* d_tcand = nullptr;      // the merge kernel's scratch [max_batch][100]
-        wz_detection_t* h_trows = nullptr;   // pinned, device-mapped: the merged rows [max_batch][100] ...
-        uint8_t* h_tpass = nullptr;          // ... and their pass bytes, written by the merge launch (and the filter launches behind it)
-        WzMergeFrame* h_tmeta = nullptr;     // pinned, device-mapped: WzMergeFrame[max_batch], then the tiles' origins int32[max_batch][2]
-        wz_detection_t* m_trows = nullptr;   // device addresses of the three
-        uint8_t* m_tpass = nullptr;
-        WzMergeFrame* m_tmeta = nullptr;
-        int tiled = 0;                       // frames of the tiled batch in flight (its rows are in h_trows); 0: the batch is not tiled
-        // gated tiled detection (wz_submit_gated_device / wz_detect_gated), allocated the first time the lane sees a gated call (ensure_gated):
-        uint16_t* d_gnow = nullptr;          // the activity launch's new grids [max_batch][gate_cells]
-        wz_detection_t* d_grows = nullptr;   // fresh or cached rows of every tile of the call, in tile order [max_batch][100]: what the merge reads
-        int32_t* d_gcount = nullptr;         // the activity kernel's counters [max_batch][2]
-        WzGateTile* h_gmeta = nullptr;       // pinned, device-mapped: WzGateTile[max_batch], WzGateCommit[max_batch], activity int32[max_batch]
-        WzGateTile* m_gmeta = nullptr;       // ... as the device sees it
-        std::vector<uint64_t> g_ran;         // the last gated call accepted on this lane (wz_gate_stats): per frame, bit t = tile t ran ...
-        std::vector<int32_t> g_act;          // ... and every tile's activity, in tile order
-        int g_tiles = 0, g_crows = 0, g_cols = 0;   // that call's launches: tiles, the most cell rows / columns of a tile
-        hipEvent_t done = nullptr;
-        int n = 0;
-        bool rows = false;                       // the batch being enqueued runs the row-staged resize kernel (a frame of it is read in place)
-        int key = 0;                             // graph key of the batch in flight: batch size | rows << 16
-        std::map<int, hipGraphExec_t> graphs;    // key = batch size | (row-staged resize kernel) << 16
-        std::map<int, hipGraph_t> graph_src;     // the captured graph itself, kept where one of its node handles is
-        std::map<int, hipGraphNode_t> pre_nodes; // ... and the resize kernel's node in that graph (its arguments carry the frame
-                                                 // descriptors and are rewritten before every replay), if it takes them by value
-        // WZ_LANE_STAMPS builds (wz_common.h): the lane's launch blocks [WZ_STAMP_SLOTS][WZ_STAMP_WORDS], the resize kernel's block and the
-        // descriptors behind it in ONE allocation; the page-locked pairs the host reads; launches stamped so far in the batch being enqueued
-        unsigned char* d_stamp_raw = nullptr;
-        unsigned long long* d_stamps = nullptr;
-        unsigned long long* d_stamps_pre = nullptr;
-        unsigned long long* h_stamps = nullptr;
-        unsigned long long* m_stamps = nullptr;
-        int stamp_next = 1;
-        bool lone = false;                       // the batch being enqueued goes kernel by kernel because the other lanes are idle (run_batch)
-        std::map<int, std::vector<WzLaunchNote>> launch_notes;   // graph key -> what was launched, in order (grid, block, LDS, kernel)
-        WzDescPack pack;                         // storage behind that node's kernelParams
-        const WzFrameDesc* pre_frames = nullptr;
-        int pre_size = 0, pre_half_pixel = 0;
-        half_t* pre_out = nullptr;
-        WzFrameDesc* pre_keep = nullptr;
-        void* pre_kp[6];
-    };
-    Lane lanes[WZ_SLOTS];
-    int n_lanes = 4;   // default; WZ_LANES overrides (1..WZ_SLOTS)
-    int n_streams = 4; // HIP streams the lanes are spread over (WZ_STREAMS); more than 4 run slower on this stack (HISTORY.md part B)
-
-    // the worker's frame table (wz_bind_frames): one entry per Frame of every FrameBuffer, described once instead of once per batch
-    struct BoundFrame {
-        const uint8_t* host;   // the frame's pixels (host address)
-        const uint8_t* dev;    // the same bytes as the device sees them when the frame lies in a wz_host_register range, else nullptr
-        int32_t w, h, fmt, cam;
-        uint64_t bytes;
-        wz_detection_t* rows;  // Header.detections of that frame (host), written by wz_collect_bound
-    };
-    std::vector<BoundFrame> bound;
-    // the tiled description of a table entry (wz_bind_tiles).  Kept beside the table, and EMPTY while no entry has one: the untiled
-    // wz_submit_bound looks at nothing but that.
-    enum { BOUND_PLAIN = 0, BOUND_TILED = 1, BOUND_GATED = 2 };
-    struct BoundTiles {
-        int kind = BOUND_PLAIN;
-        std::vector<wz_tile_t> tiles;   // BOUND_TILED: the entry's rectangles (BOUND_GATED: its camera's, looked up at submit)
-        double iou = 0.0, ios = 0.0;    // the merge thresholds of both kinds
-    };
-    std::vector<BoundTiles> bound_tiles;   // [bound.size()] or empty
-
-    std::vector<WzCamFilter> h_cams;
-    WzCamFilter* d_cams = nullptr;
-    std::vector<int32_t*> cam_sat;
-    wz_detection_t* d_tmp_rows = nullptr;
-    uint8_t* d_tmp_pass = nullptr;
-
-    // gated tiled detection: a camera's tile layout and its state in device memory (wz_set_camera_tiles); empty until a camera is set
-    struct GateCam {
-        int w = 0, h = 0, base = 0;              // the frames this layout was set for: size and base format
-        wz_tile_gate_t gate = {0, 1, 0, 0};
-        std::vector<wz_tile_t> tiles;
-        std::vector<int> cols, crows;            // cells of every tile
-        std::vector<size_t> grid_off;            // first cell of every tile's reference grid in d_ref
-        uint16_t* d_ref = nullptr;               // the tiles' reference grids, one after the other
-        wz_detection_t* d_rows = nullptr;        // the tiles' cached rows [tiles][100]
-        std::vector<uint8_t> has_ref;            // the tile has a reference (and cached rows)
-        std::vector<int> skipped;                // gated calls of this camera in a row that skipped the tile
-        int lane = -1;                           // the lane whose gated batch last wrote this state
-    };
-    std::map<int, GateCam> gate_cams;
-
-    std::vector<std::string> stage_names;
 };
 
 static int input_tensor_index(wz_engine* e) { return e->ops[0].src; }
@@ -273,7 +92,6 @@ static size_t tensor_frame_bytes(wz_engine* e, int idx) {
     const size_t es = idx == input_tensor_index(e) ? 2 : e->hdr.precision / 8;
     return (size_t)t.h * t.w * t.c * es * (tensor_is_pair(e, idx) ? 2 : 1);
 }
-typedef wz_engine::Lane Lane;
 
 // ------------------------------------------------------------------------------------------------
 // pipeline
@@ -699,7 +517,7 @@ static void enqueue_batch(wz_engine* e, Lane& L, int n, StageTimer* t, int inner
     enqueue_post(e, L, true, n, t, L.decode_fused, L.cands_listed);
 }
 
-static int run_batch(wz_engine* e, int slot, int n) {
+int run_batch(wz_engine* e, int slot, int n) {
     Lane& L = e->lanes[slot];
     auto failed = [&]() -> int {   // a split-operand block no kernel took (the load-time check prepared batch 1 only): nothing may run on stale data
         const int op = L.launch_failed - 1;
@@ -1019,12 +837,11 @@ static int load_blob(wz_engine* e, const char* path) {
 // Every synchronous copy and fill of a product path: issued on lane 0's stream and waited for there -- not hipMemcpy / hipMemset,
 // which ride the null stream and make ROCclr open a hardware queue for it that a lane may then have to share (a process that uses
 // only the product ABI never creates that queue).  Waits for whatever lane 0 has in flight, the source is free on return.
-static int sync_all(wz_engine* e);
 static hipError_t lane0_copy(wz_engine* e, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
     const hipError_t err = hipMemcpyAsync(dst, src, bytes, kind, e->stream);
     return err == hipSuccess ? hipStreamSynchronize(e->stream) : err;
 }
-static hipError_t lane0_fill(wz_engine* e, void* dst, int value, size_t bytes) {
+hipError_t lane0_fill(wz_engine* e, void* dst, int value, size_t bytes) {
     const hipError_t err = hipMemsetAsync(dst, value, bytes, e->stream);
     return err == hipSuccess ? hipStreamSynchronize(e->stream) : err;
 }
@@ -1288,7 +1105,7 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
     return WZ_OK;
 }
 
-static int sync_all(wz_engine* e) {
+int sync_all(wz_engine* e) {
     for (int li = 0; li < e->n_lanes; ++li)
         if (e->lanes[li].stream) HIPCHK(hipStreamSynchronize(e->lanes[li].stream));
     return WZ_OK;
@@ -1300,10 +1117,7 @@ extern "C" void wz_destroy(wz_engine_t* e) {
     (void)sync_all(e);
     for (int32_t* p : e->cam_sat)
         if (p) (void)hipFree(p);
-    for (auto& kv : e->gate_cams) {
-        if (kv.second.d_ref) (void)hipFree(kv.second.d_ref);
-        if (kv.second.d_rows) (void)hipFree(kv.second.d_rows);
-    }
+    for (auto& kv : e->gate_cams) kv.second.release();
     void* devp[] = {e->d_weights, e->d_zeros, e->d_mbdbg, e->d_anchors, e->d_frames, e->d_cams, e->d_tmp_rows, e->d_tmp_pass};
     for (void* p : devp)
         if (p) (void)hipFree(p);
@@ -1322,15 +1136,8 @@ extern "C" void wz_destroy(wz_engine_t* e) {
         if (L.h_pass) (void)hipHostFree(L.h_pass);
         if (L.h_status) (void)hipHostFree(L.h_status);
         if (L.h_stamps) (void)hipHostFree(L.h_stamps);
-        if (L.d_tiles) (void)hipFree(L.d_tiles);
-        if (L.d_tcand) (void)hipFree(L.d_tcand);
-        if (L.h_trows) (void)hipHostFree(L.h_trows);
-        if (L.h_tpass) (void)hipHostFree(L.h_tpass);
-        if (L.h_tmeta) (void)hipHostFree(L.h_tmeta);
-        if (L.d_gnow) (void)hipFree(L.d_gnow);
-        if (L.d_grows) (void)hipFree(L.d_grows);
-        if (L.d_gcount) (void)hipFree(L.d_gcount);
-        if (L.h_gmeta) (void)hipHostFree(L.h_gmeta);
+        L.tile.release();
+        L.gate.release();
         if (L.done) (void)hipEventDestroy(L.done);
         if (L.stream && L.owns_stream) (void)hipStreamDestroy(L.stream);
     }
@@ -1345,7 +1152,7 @@ extern "C" const char* wz_device_name(wz_engine_t* e) { return e ? e->name.c_str
 // Why a format word (include/watsor_hip.h: a base format in bits 0-7 | WZ_CSP_BT709 | WZ_RANGE_FULL) is not taken at this size, or
 // nullptr when it is.  The one place that knows the rules: wz_frame_bytes -- by which every frame is sized and checked -- is 0
 // exactly where this gives a reason.
-static const char* fmt_refusal(int w, int h, int fmt) {
+const char* fmt_refusal(int w, int h, int fmt) {
     if (w < 1 || h < 1) return "width and height must be positive";
     if (fmt & ~(WZ_FMT_BASE_MASK | WZ_CSP_BT709 | WZ_RANGE_FULL)) return "unknown flag bits in the format word";
     const int base = fmt & WZ_FMT_BASE_MASK;
@@ -1367,23 +1174,16 @@ extern "C" uint64_t wz_frame_bytes(int w, int h, int fmt) {
     }
 }
 
-static int fill_desc(wz_engine* e, int slot, int n, const uint8_t* const* d_rgb, const int* w, const int* h,
-                     const int* fmt, const int* cam) {
+int fill_desc(wz_engine* e, int slot, int n, const uint8_t* const* d_rgb, const int* w, const int* h, const int* fmt, const int* cam) {
     if (slot < 0 || slot >= e->n_lanes) return wz_fail(WZ_EINVAL, "slot %d out of range [0,%d)", slot, e->n_lanes);
     if (n < 1 || n > e->max_batch) return wz_fail(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
     const float size = (float)e->hdr.input_size;
     e->lanes[slot].bound_idx.clear();
-    e->lanes[slot].tiled = 0;
+    e->lanes[slot].tile.tiled = 0;
     for (int i = 0; i < n; ++i) {
-        if (w[i] < 1 || h[i] < 1 || !d_rgb[i]) return wz_fail(WZ_EINVAL, "frame %d: bad pointer or size", i);
         const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
-        if (!wz_frame_bytes(w[i], h[i], pf))
-            return wz_fail(WZ_EINVAL, "frame %d: pixel format 0x%x at %dx%d: %s", i, pf, w[i], h[i], fmt_refusal(w[i], h[i], pf));
         const int c = cam ? cam[i] : -1;
-        if (c >= WZ_MAX_CAMS) return wz_fail(WZ_ELIMIT, "camera id %d >= %d", c, WZ_MAX_CAMS);
-        if (c >= 0 && e->h_cams[c].enabled && (e->h_cams[c].width != w[i] || e->h_cams[c].height != h[i]))
-            return wz_fail(WZ_EINVAL, "frame %d is %dx%d but camera %d filter was set for %dx%d", i, w[i], h[i], c,
-                           e->h_cams[c].width, e->h_cams[c].height);
+        WZCHK(frame_refusal(e, "frame", i, d_rgb[i], w[i], h[i], pf, c, FC_PTR | FC_FMT | FC_CAM_ID | FC_CAM_FILTER));
         WzFrameDesc& d = e->lanes[slot].h_desc[i];
         d.rgb = d_rgb[i];
         d.w = w[i];
@@ -1402,8 +1202,7 @@ extern "C" int wz_submit_device_fmt(wz_engine_t* e, int slot, int n, const uint8
     if (slot < 0 || slot >= e->n_lanes) return wz_fail(WZ_EINVAL, "slot %d out of range [0,%d)", slot, e->n_lanes);
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipEventSynchronize(e->lanes[slot].done));   // the lane's previous batch has fully drained
-    int rc = fill_desc(e, slot, n, d_rgb, w, h, fmt, cam);
-    if (rc != WZ_OK) return rc;
+    WZCHK(fill_desc(e, slot, n, d_rgb, w, h, fmt, cam));
     e->lanes[slot].rows = e->pre_rows;
     return run_batch(e, slot, n);
 }
@@ -1428,23 +1227,25 @@ static int lane_status(wz_engine* e, int slot) {
     return WZ_OK;
 }
 
+// What a lane hands over.  A tiled or gated batch: its FRAMES' merged rows, one block per frame -- tile.tiled of them, whatever L.n says
+// (the tiles that ran; none: 0; lane_status still looks at every tile).
+struct LaneResult { int n; const wz_detection_t* rows; const uint8_t* pass; };
+static LaneResult lane_result(const Lane& L) {
+    return L.tile.tiled ? LaneResult{L.tile.tiled, L.tile.h_trows, L.tile.h_tpass} : LaneResult{L.n, L.h_rows, L.h_pass};
+}
+
 extern "C" const wz_detection_t* wz_slot_rows(wz_engine_t* e, int slot) {
     if (!e || slot < 0 || slot >= e->n_lanes) return nullptr;
-    return e->lanes[slot].tiled ? e->lanes[slot].h_trows : e->lanes[slot].h_rows;   // (a tiled batch: the merged rows, one block per frame)
+    return lane_result(e->lanes[slot]).rows;
 }
 
 extern "C" int wz_collect(wz_engine_t* e, int slot, wz_detection_t* const* out, uint8_t* const* pass) {
-    int rc = wz_wait(e, slot);
-    if (rc != WZ_OK) return rc;
-    const Lane& L = e->lanes[slot];
-    // a tiled batch hands over its frames' merged rows, not the L.n tiles' (lane_status still looks at every tile)
-    const int n = L.tiled ? L.tiled : L.n;
-    const wz_detection_t* rows = L.tiled ? L.h_trows : L.h_rows;
-    const uint8_t* passes = L.tiled ? L.h_tpass : L.h_pass;
-    for (int i = 0; i < n; ++i) {
+    WZCHK(wz_wait(e, slot));
+    const LaneResult r = lane_result(e->lanes[slot]);
+    for (int i = 0; i < r.n; ++i) {
         if (out && out[i])
-            memcpy(out[i], rows + (size_t)i * WZ_MAX_DETECTIONS, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS);
-        if (pass && pass[i]) memcpy(pass[i], passes + (size_t)i * WZ_MAX_DETECTIONS, WZ_MAX_DETECTIONS);
+            memcpy(out[i], r.rows + (size_t)i * WZ_MAX_DETECTIONS, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS);
+        if (pass && pass[i]) memcpy(pass[i], r.pass + (size_t)i * WZ_MAX_DETECTIONS, WZ_MAX_DETECTIONS);
     }
     return lane_status(e, slot);
 }
@@ -1476,12 +1277,10 @@ extern "C" int wz_detect_batch_fmt(wz_engine_t* e, int n, const uint8_t* const* 
     HIPCHK(hipEventSynchronize(e->lanes[0].done));
     std::vector<const uint8_t*> dptr(n);
     for (int i = 0; i < n; ++i) {
-        if (!rgb[i] || w[i] < 1 || h[i] < 1) return wz_fail(WZ_EINVAL, "frame %d: bad pointer or size", i);
-        if (w[i] > e->max_w || h[i] > e->max_h || (size_t)w[i] * h[i] * 3 > e->frame_stride)
-            return wz_fail(WZ_ELIMIT, "frame %d is %dx%d, engine was created for at most %dx%d", i, w[i], h[i],
-                           e->max_w, e->max_h);
-        const uint64_t bytes = wz_frame_bytes(w[i], h[i], fmt ? fmt[i] : WZ_FMT_RGB24);
-        if (!bytes) return wz_fail(WZ_EINVAL, "frame %d: pixel format 0x%x at %dx%d: %s", i, fmt[i], w[i], h[i], fmt_refusal(w[i], h[i], fmt[i]));
+        const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
+        WZCHK(frame_refusal(e, "frame", i, rgb[i], w[i], h[i], pf, -1, FC_PTR | FC_LIMIT));
+        const uint64_t bytes = wz_frame_bytes(w[i], h[i], pf);
+        if (!bytes) return frame_refusal(e, "frame", i, rgb[i], w[i], h[i], pf, -1, FC_FMT);
         uint8_t* dst = e->d_frames + e->frame_stride * i;
         HIPCHK(hipMemcpyAsync(dst, rgb[i], bytes, hipMemcpyHostToDevice, e->lanes[0].stream));
         dptr[i] = dst;
@@ -1507,18 +1306,18 @@ extern "C" int wz_detect_batch_fmt(wz_engine_t* e, int n, const uint8_t* const* 
 // 640x480 -- this stack runs four streams side by side, HISTORY.md part B: profiles/r03_host_path_*.)
 // Where the device sees a page-locked host frame, or nullptr: inside a range wz_host_register locked (WzFrameDesc::rgb may then point
 // at the frame itself and the resize kernel reads its tap rows over PCIe, no staging copy -- `host_read`).
-static const uint8_t* device_view(wz_engine* e, const uint8_t* host, uint64_t bytes) {
+const uint8_t* device_view(wz_engine* e, const uint8_t* host, uint64_t bytes) {
     for (const auto& r : e->host_ranges)
         if (host >= r.host && host + bytes <= r.host + r.bytes) return r.dev ? r.dev + (host - r.host) : nullptr;
     return nullptr;
 }
 // host_read policy for one frame: 1 = always in place, 2 = only when the vertical down-scale skips source rows (>= 2: at most half
 // of the rows are tapped; below that nearly every row is, some twice, and one DMA of the whole frame moves fewer bytes)
-static bool read_in_place(const wz_engine* e, int h) {
+bool read_in_place(const wz_engine* e, int h) {
     return e->host_read == 1 || (e->host_read == 2 && h >= 2 * (int)e->hdr.input_size);
 }
 
-static int stage_frame(wz_engine* e, Lane& L, int i, const uint8_t* host, uint64_t bytes, const uint8_t** where) {
+int stage_frame(wz_engine* e, Lane& L, int i, const uint8_t* host, uint64_t bytes, const uint8_t** where) {
     uint8_t* dst = L.d_frames + e->frame_stride * i;
     HIPCHK(hipMemcpyAsync(dst, host, bytes, hipMemcpyHostToDevice, L.stream));
     *where = dst;
@@ -1541,12 +1340,10 @@ extern "C" int wz_submit_host_fmt(wz_engine_t* e, int slot, int n, const uint8_t
     bool in_place = false;
     std::vector<const uint8_t*> dptr(n);
     for (int i = 0; i < n; ++i) {
-        if (!rgb[i] || w[i] < 1 || h[i] < 1) return wz_fail(WZ_EINVAL, "frame %d: bad pointer or size", i);
-        if (w[i] > e->max_w || h[i] > e->max_h || (size_t)w[i] * h[i] * 3 > e->frame_stride)
-            return wz_fail(WZ_ELIMIT, "frame %d is %dx%d, engine was created for at most %dx%d", i, w[i], h[i],
-                           e->max_w, e->max_h);
-        const uint64_t bytes = wz_frame_bytes(w[i], h[i], fmt ? fmt[i] : WZ_FMT_RGB24);
-        if (!bytes) return wz_fail(WZ_EINVAL, "frame %d: pixel format 0x%x at %dx%d: %s", i, fmt[i], w[i], h[i], fmt_refusal(w[i], h[i], fmt[i]));
+        const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
+        WZCHK(frame_refusal(e, "frame", i, rgb[i], w[i], h[i], pf, -1, FC_PTR | FC_LIMIT));
+        const uint64_t bytes = wz_frame_bytes(w[i], h[i], pf);
+        if (!bytes) return frame_refusal(e, "frame", i, rgb[i], w[i], h[i], pf, -1, FC_FMT);
         // pageable source: the runtime stages it (slow, synchronous); registered / pinned source: one DMA -- or no copy at all
         const uint8_t* dv = read_in_place(e, h[i]) ? device_view(e, rgb[i], bytes) : nullptr;
         if (dv) {
@@ -1554,11 +1351,9 @@ extern "C" int wz_submit_host_fmt(wz_engine_t* e, int slot, int n, const uint8_t
             in_place = true;
             continue;
         }
-        int rc = stage_frame(e, L, i, rgb[i], bytes, &dptr[i]);
-        if (rc != WZ_OK) return rc;
+        WZCHK(stage_frame(e, L, i, rgb[i], bytes, &dptr[i]));
     }
-    int rc = fill_desc(e, slot, n, dptr.data(), w, h, fmt, cam);
-    if (rc != WZ_OK) return rc;
+    WZCHK(fill_desc(e, slot, n, dptr.data(), w, h, fmt, cam));
     L.rows = e->pre_rows || in_place;
     return run_batch(e, slot, n);
 }
@@ -1594,521 +1389,6 @@ extern "C" int wz_host_unregister(wz_engine_t* e, void* ptr) {
     return WZ_OK;
 }
 
-
-// ------------------------------------------------------------------------------------------------
-// tiled detection: crop launch -> an ordinary batch over the tiles -> merge launch (k_tiles.hip)
-// ------------------------------------------------------------------------------------------------
-// Everything a lane needs for tiled calls, allocated the first time it sees one (an engine that never does uses no byte of it).
-static int ensure_tiled(wz_engine* e, Lane& L) {
-    if (L.d_tiles) return WZ_OK;
-    const size_t nb = (size_t)e->max_batch, rows = nb * WZ_MAX_DETECTIONS;
-    uint8_t* tiles = nullptr;
-    WzMergeCand* cand = nullptr;
-    wz_detection_t* hr = nullptr;
-    uint8_t* hp = nullptr;
-    WzMergeFrame* hm = nullptr;
-    hipError_t err = hipMalloc((void**)&tiles, e->frame_stride * nb);
-    if (err == hipSuccess) err = hipMalloc((void**)&cand, sizeof(WzMergeCand) * rows);
-    if (err == hipSuccess) err = hipHostMalloc((void**)&hr, sizeof(wz_detection_t) * rows, hipHostMallocMapped);
-    if (err == hipSuccess) err = hipHostMalloc((void**)&hp, rows, hipHostMallocMapped);
-    if (err == hipSuccess) err = hipHostMalloc((void**)&hm, (sizeof(WzMergeFrame) + 8) * nb, hipHostMallocMapped);
-    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&L.m_trows, hr, 0);
-    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&L.m_tpass, hp, 0);
-    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&L.m_tmeta, hm, 0);
-    if (err != hipSuccess) {
-        if (tiles) (void)hipFree(tiles);
-        if (cand) (void)hipFree(cand);
-        if (hr) (void)hipHostFree(hr);
-        if (hp) (void)hipHostFree(hp);
-        if (hm) (void)hipHostFree(hm);
-        return wz_fail(WZ_EHIP, "tile staging of a lane (%zu bytes): %s", e->frame_stride * nb, hipGetErrorString(err));
-    }
-    L.d_tiles = tiles; L.d_tcand = cand; L.h_trows = hr; L.h_tpass = hp; L.h_tmeta = hm;
-    return WZ_OK;
-}
-
-// Why rectangle t of a w x h frame of format word fmt cannot be cut, or nullptr
-static const char* tile_refusal(const wz_tile_t& t, int w, int h, int fmt) {
-    if (t.w < 1 || t.h < 1 || t.x0 < 0 || t.y0 < 0) return "origin and size must not be negative, the size not zero";
-    if ((int64_t)t.x0 + t.w > w || (int64_t)t.y0 + t.h > h) return "the rectangle leaves the frame";
-    const int base = fmt & WZ_FMT_BASE_MASK;
-    if ((base == WZ_FMT_NV12 || base == WZ_FMT_I420) && ((t.x0 | t.y0 | t.w | t.h) & 1)) return "NV12 / I420 need even x0, y0, w and h";
-    if ((base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422) && ((t.x0 | t.w) & 1)) return "YUYV422 / UYVY422 need even x0 and w";
-    if (!wz_frame_bytes(t.w, t.h, fmt)) return fmt_refusal(t.w, t.h, fmt);
-    return nullptr;
-}
-
-// The one to three rectangular byte copies that cut rectangle t out of a w x h frame at `src` into a contiguous image at `dst`.
-static void tile_planes(const uint8_t* src, int w, int h, int fmt, const wz_tile_t& t, uint8_t* dst, std::vector<WzCropPlane>& out) {
-    const int base = fmt & WZ_FMT_BASE_MASK;
-    const size_t W = (size_t)w, H = (size_t)h;
-    if (base == WZ_FMT_NV12 || base == WZ_FMT_I420) {
-        out.push_back({src + (size_t)t.y0 * W + t.x0, dst, w, t.w, t.h, 0});
-        const uint8_t* chroma = src + W * H;
-        uint8_t* dc = dst + (size_t)t.w * t.h;
-        if (base == WZ_FMT_NV12) {
-            out.push_back({chroma + (size_t)(t.y0 / 2) * W + t.x0, dc, w, t.w, t.h / 2, 0});
-        } else {
-            const size_t cw = W / 2, ch = H / 2, off = (size_t)(t.y0 / 2) * cw + t.x0 / 2;
-            out.push_back({chroma + off, dc, w / 2, t.w / 2, t.h / 2, 0});
-            out.push_back({chroma + cw * ch + off, dc + (size_t)(t.w / 2) * (t.h / 2), w / 2, t.w / 2, t.h / 2, 0});
-        }
-        return;
-    }
-    const int bpp = (base == WZ_FMT_RGB24 || base == WZ_FMT_BGR24) ? 3 : (base == WZ_FMT_GRAY8 ? 1 : 2);
-    out.push_back({src + ((size_t)t.y0 * W + t.x0) * bpp, dst, w * bpp, t.w * bpp, t.h, 0});
-}
-
-// Every refusal of a tiled call (include/watsor_hip.h), before anything is enqueued or written.  host: the frames are host frames that
-// go through the lane's staging area, which holds max_width x max_height.
-static int tiled_check(wz_engine* e, const char* who, int slot, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt,
-                       const int* cam, const int* n_tiles, const wz_tile_t* const* tiles, double iou_thr, double ios_thr, bool host, int* total) {
-    if (!e || !frames || !w || !h || !n_tiles || !tiles) return wz_fail(WZ_EINVAL, "%s: null argument", who);
-    if (slot < 0 || slot >= e->n_lanes) return wz_fail(WZ_EINVAL, "slot %d out of range [0,%d)", slot, e->n_lanes);
-    if (n < 1 || n > e->max_batch) return wz_fail(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
-    int64_t sum = 0;
-    for (int i = 0; i < n; ++i) {
-        if (n_tiles[i] < 1 || n_tiles[i] > WZ_MAX_TILES)
-            return wz_fail(WZ_ELIMIT, "frame %d: %d tiles, a frame takes 1 to %d", i, n_tiles[i], WZ_MAX_TILES);
-        sum += n_tiles[i];
-    }
-    if (sum > e->max_batch) return wz_fail(WZ_ELIMIT, "%lld tiles in one call exceed max_batch %d", (long long)sum, e->max_batch);
-    for (int i = 0; i < n; ++i) {
-        if (!frames[i] || !tiles[i] || w[i] < 1 || h[i] < 1) return wz_fail(WZ_EINVAL, "frame %d: bad pointer or size", i);
-        const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
-        if (!wz_frame_bytes(w[i], h[i], pf))
-            return wz_fail(WZ_EINVAL, "frame %d: pixel format 0x%x at %dx%d: %s", i, pf, w[i], h[i], fmt_refusal(w[i], h[i], pf));
-        if (host && (w[i] > e->max_w || h[i] > e->max_h || (size_t)w[i] * h[i] * 3 > e->frame_stride))
-            return wz_fail(WZ_ELIMIT, "frame %d is %dx%d, engine was created for at most %dx%d", i, w[i], h[i], e->max_w, e->max_h);
-        const int c = cam ? cam[i] : -1;
-        if (c >= WZ_MAX_CAMS) return wz_fail(WZ_ELIMIT, "camera id %d >= %d", c, WZ_MAX_CAMS);
-        if (c >= 0 && e->h_cams[c].enabled && (e->h_cams[c].width != w[i] || e->h_cams[c].height != h[i]))
-            return wz_fail(WZ_EINVAL, "frame %d is %dx%d but camera %d filter was set for %dx%d", i, w[i], h[i], c,
-                           e->h_cams[c].width, e->h_cams[c].height);
-        for (int t = 0; t < n_tiles[i]; ++t) {
-            const wz_tile_t& r = tiles[i][t];
-            const char* why = tile_refusal(r, w[i], h[i], pf);
-            if (why) return wz_fail(WZ_EINVAL, "frame %d (%dx%d, format 0x%x), tile %d (%d, %d, %d x %d): %s", i, w[i], h[i], pf, t, r.x0, r.y0, r.w, r.h, why);
-            if (r.w > e->max_w || r.h > e->max_h || (size_t)r.w * r.h * 3 > e->frame_stride)
-                return wz_fail(WZ_ELIMIT, "frame %d, tile %d is %dx%d, engine was created for at most %dx%d", i, t, r.w, r.h, e->max_w, e->max_h);
-        }
-    }
-    if (!(iou_thr >= 0.0) || !(ios_thr >= 0.0)) return wz_fail(WZ_EINVAL, "%s: the merge thresholds must be numbers >= 0", who);
-    *total = (int)sum;
-    return WZ_OK;
-}
-
-// What a checked tiled call launches: the crop launch's planes, the tiles as the batch's frames (in the lane's tile staging area, tile k
-// at k * frame_stride), and -- written into the lane's pinned block -- the merge launch's frames and origins.
-struct TiledLayout {
-    std::vector<WzCropPlane> planes;
-    std::vector<const uint8_t*> tptr;
-    std::vector<int> tw, th, tf;
-    int most = 0;   // the most tiles any frame has
-};
-static void tiled_layout(wz_engine* e, Lane& L, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt, const int* cam,
-                         const int* n_tiles, const wz_tile_t* const* tiles, int total, TiledLayout& y) {
-    y.tptr.resize(total); y.tw.resize(total); y.th.resize(total); y.tf.resize(total);
-    int32_t* origins = reinterpret_cast<int32_t*>(L.h_tmeta + e->max_batch);
-    int k = 0;
-    for (int i = 0; i < n; ++i) {
-        const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
-        const int c = cam ? cam[i] : -1;
-        L.h_tmeta[i] = {k, n_tiles[i], c < 0 ? -1 : c, 0};
-        y.most = std::max(y.most, n_tiles[i]);
-        for (int t = 0; t < n_tiles[i]; ++t, ++k) {
-            const wz_tile_t& r = tiles[i][t];
-            uint8_t* dst = L.d_tiles + e->frame_stride * k;
-            tile_planes(d_frames[i], w[i], h[i], pf, r, dst, y.planes);
-            y.tptr[k] = dst; y.tw[k] = r.w; y.th[k] = r.h; y.tf[k] = pf;   // (the colour flags of the frame's format word are its tiles')
-            origins[2 * k] = r.x0;
-            origins[2 * k + 1] = r.y0;
-        }
-    }
-}
-
-// A checked tiled call on a drained lane, frames in device memory: crop, batch, merge (+ the cameras' filters), the lane's event behind them.
-static int tiled_enqueue(wz_engine* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
-                         const int* cam, const int* n_tiles, const wz_tile_t* const* tiles, double iou_thr, double ios_thr, int total) {
-    Lane& L = e->lanes[slot];
-    int rc = ensure_tiled(e, L);
-    if (rc != WZ_OK) return rc;
-    TiledLayout y;
-    tiled_layout(e, L, n, d_frames, w, h, fmt, cam, n_tiles, tiles, total, y);
-    std::vector<const uint8_t*>& tptr = y.tptr;
-    std::vector<int>&tw = y.tw, &th = y.th, &tf = y.tf;
-    const int most = y.most;
-    wz_launch_crop_tiles(y.planes.data(), (int)y.planes.size(), L.stream);
-    // the tiles as an ordinary batch without cameras: 100 unfiltered rows per tile, in tile pixel coordinates, in L.h_rows
-    rc = fill_desc(e, slot, total, tptr.data(), tw.data(), th.data(), tf.data(), nullptr);
-    if (rc != WZ_OK) return rc;
-    L.rows = e->pre_rows;
-    rc = run_batch(e, slot, total);
-    if (rc != WZ_OK) return rc;
-    const int32_t* m_origins = reinterpret_cast<const int32_t*>(L.m_tmeta + e->max_batch);
-    wz_launch_merge_tiles(L.m_tmeta, m_origins, L.m_rows, L.d_tcand, n, most, iou_thr, ios_thr, L.m_trows, L.m_tpass, L.stream);
-    for (int i = 0; i < n; ++i)   // the frame's camera filter on its merged rows, exactly as wz_filter_rows applies it
-        if (cam && cam[i] >= 0 && e->h_cams[cam[i]].enabled)
-            wz_launch_filter_rows(e->d_cams, cam[i], L.m_trows + (size_t)i * WZ_MAX_DETECTIONS, L.m_tpass + (size_t)i * WZ_MAX_DETECTIONS, L.stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(L.done, L.stream));   // (run_batch recorded it behind the batch: wz_wait / wz_collect must see the merge)
-    L.tiled = n;
-    return WZ_OK;
-}
-
-extern "C" int wz_submit_tiled_device(wz_engine_t* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h,
-                                      const int* fmt, const int* cam, const int* n_tiles, const wz_tile_t* const* tiles,
-                                      double iou_thr, double ios_thr) {
-    int total = 0;
-    int rc = tiled_check(e, "wz_submit_tiled_device", slot, n, d_frames, w, h, fmt, cam, n_tiles, tiles, iou_thr, ios_thr, false, &total);
-    if (rc != WZ_OK) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipEventSynchronize(e->lanes[slot].done));   // the lane's previous batch has fully drained
-    return tiled_enqueue(e, slot, n, d_frames, w, h, fmt, cam, n_tiles, tiles, iou_thr, ios_thr, total);
-}
-
-extern "C" int wz_detect_tiled(wz_engine_t* e, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt,
-                               const int* cam, const int* n_tiles, const wz_tile_t* const* tiles, double iou_thr, double ios_thr,
-                               wz_detection_t* const* out, uint8_t* const* pass, float* ms) {
-    int total = 0;
-    int rc = tiled_check(e, "wz_detect_tiled", 0, n, frames, w, h, fmt, cam, n_tiles, tiles, iou_thr, ios_thr, true, &total);
-    if (rc != WZ_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipSetDevice(e->device));
-    Lane& L = e->lanes[0];
-    HIPCHK(hipEventSynchronize(L.done));
-    std::vector<const uint8_t*> dptr(n);
-    for (int i = 0; i < n; ++i) {   // the whole frame into the lane's staging area, as wz_submit_host_fmt stages it; the tiles are cut from that copy
-        rc = stage_frame(e, L, i, frames[i], wz_frame_bytes(w[i], h[i], fmt ? fmt[i] : WZ_FMT_RGB24), &dptr[i]);
-        if (rc != WZ_OK) return rc;
-    }
-    rc = tiled_enqueue(e, 0, n, dptr.data(), w, h, fmt, cam, n_tiles, tiles, iou_thr, ios_thr, total);
-    if (rc != WZ_OK) return rc;
-    rc = wz_collect(e, 0, out, pass);
-    if (rc != WZ_OK && rc != WZ_EINCOMPLETE) return rc;
-    const float el = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (ms)
-        for (int i = 0; i < n; ++i) ms[i] = el;
-    return rc;   // WZ_OK, or WZ_EINCOMPLETE: the merged rows are written, a tile's rows may have been short
-}
-
-// ------------------------------------------------------------------------------------------------
-// gated tiled detection: activity launch -> the host decides which tiles run -> crop + batch of those -> commit + merge (k_gate.hip,
-// DESIGN.md section 16).  Eager launches around run_batch, as tiled detection is; nothing above this line knows about it.
-// ------------------------------------------------------------------------------------------------
-typedef wz_engine::GateCam GateCam;
-static size_t gate_cells_of(int w, int h) {
-    return (size_t)((w + WZ_GATE_CELL - 1) / WZ_GATE_CELL) * (size_t)((h + WZ_GATE_CELL - 1) / WZ_GATE_CELL);
-}
-// the pinned block of a lane: the activity launch's tiles, the commit launch's tiles, the activity counts
-static WzGateCommit* gate_commits(wz_engine* e, WzGateTile* meta) { return reinterpret_cast<WzGateCommit*>(meta + e->max_batch); }
-static int32_t* gate_activity(wz_engine* e, WzGateTile* meta) { return reinterpret_cast<int32_t*>(gate_commits(e, meta) + e->max_batch); }
-
-static int ensure_gated(wz_engine* e, Lane& L) {
-    if (L.d_gnow) return WZ_OK;
-    const size_t nb = (size_t)e->max_batch, cells = gate_cells_of(e->max_w, e->max_h);
-    uint16_t* now = nullptr;
-    wz_detection_t* rows = nullptr;
-    int32_t* cnt = nullptr;
-    WzGateTile* hm = nullptr;
-    hipError_t err = hipMalloc((void**)&now, cells * 2 * nb);
-    if (err == hipSuccess) err = hipMalloc((void**)&rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS * nb);
-    if (err == hipSuccess) err = hipMalloc((void**)&cnt, 8 * nb);
-    if (err == hipSuccess) err = lane0_fill(e, cnt, 0, 8 * nb);
-    if (err == hipSuccess) err = hipHostMalloc((void**)&hm, (sizeof(WzGateTile) + sizeof(WzGateCommit) + 4) * nb, hipHostMallocMapped);
-    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&L.m_gmeta, hm, 0);
-    if (err != hipSuccess) {
-        if (now) (void)hipFree(now);
-        if (rows) (void)hipFree(rows);
-        if (cnt) (void)hipFree(cnt);
-        if (hm) (void)hipHostFree(hm);
-        return wz_fail(WZ_EHIP, "gate scratch of a lane: %s", hipGetErrorString(err));
-    }
-    L.d_gnow = now; L.d_grows = rows; L.d_gcount = cnt; L.h_gmeta = hm;
-    return WZ_OK;
-}
-
-// What the activity kernel reads of rectangle t of a frame w pixels wide at `src`: the luma-bearing bytes of its rows
-static void gate_tile(const uint8_t* src, int w, int fmt, const wz_tile_t& t, WzGateTile& g) {
-    const int base = fmt & WZ_FMT_BASE_MASK;
-    const bool rgb = base == WZ_FMT_RGB24 || base == WZ_FMT_BGR24, yuy = base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422;
-    const int bpp = rgb ? 3 : yuy ? 2 : 1;   // (NV12 / I420: the luma plane is the frame's first w x h bytes)
-    g.src = src + ((size_t)t.y0 * (size_t)w + t.x0) * bpp;
-    g.pitch = w * bpp;
-    g.row_bytes = t.w * bpp;
-    g.tw = t.w;
-    g.th = t.h;
-    g.cols = (t.w + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
-    g.crows = (t.h + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
-    g.mode = base == WZ_FMT_RGB24 ? WZ_GATE_RGB : base == WZ_FMT_BGR24 ? WZ_GATE_BGR : base == WZ_FMT_YUYV422 ? WZ_GATE_YUYV
-             : base == WZ_FMT_UYVY422 ? WZ_GATE_UYVY : WZ_GATE_GRAY;
-}
-
-extern "C" int wz_set_camera_tiles(wz_engine_t* e, int cam, int width, int height, int fmt, int n_tiles, const wz_tile_t* tiles,
-                                   const wz_tile_gate_t* gate) {
-    if (!e || !tiles || !gate) return wz_fail(WZ_EINVAL, "wz_set_camera_tiles: null argument");
-    if (cam < 0 || cam >= WZ_MAX_CAMS) return wz_fail(WZ_ELIMIT, "camera id %d out of range [0,%d)", cam, WZ_MAX_CAMS);
-    if (!wz_frame_bytes(width, height, fmt))
-        return wz_fail(WZ_EINVAL, "camera %d: pixel format 0x%x at %dx%d: %s", cam, fmt, width, height, fmt_refusal(width, height, fmt));
-    if (n_tiles < 1 || n_tiles > WZ_MAX_TILES) return wz_fail(WZ_ELIMIT, "camera %d: %d tiles, a frame takes 1 to %d", cam, n_tiles, WZ_MAX_TILES);
-    if (n_tiles > e->max_batch) return wz_fail(WZ_ELIMIT, "camera %d: %d tiles exceed max_batch %d", cam, n_tiles, e->max_batch);
-    if (gate->pixel_thr < 0 || gate->pixel_thr > 255 || gate->min_cells < 1 || gate->max_age < 0)
-        return wz_fail(WZ_EINVAL, "camera %d: gate (%d, %d, %d): pixel_thr must be 0 .. 255, min_cells >= 1, max_age >= 0", cam, gate->pixel_thr,
-                       gate->min_cells, gate->max_age);
-    GateCam g;
-    g.w = width; g.h = height; g.base = fmt & WZ_FMT_BASE_MASK;
-    g.gate = *gate;
-    g.gate._reserved = 0;
-    size_t cells = 0;
-    for (int t = 0; t < n_tiles; ++t) {
-        const wz_tile_t& r = tiles[t];
-        const char* why = tile_refusal(r, width, height, fmt);
-        if (why) return wz_fail(WZ_EINVAL, "camera %d (%dx%d, format 0x%x), tile %d (%d, %d, %d x %d): %s", cam, width, height, fmt, t, r.x0, r.y0, r.w, r.h, why);
-        if (r.w > e->max_w || r.h > e->max_h || (size_t)r.w * r.h * 3 > e->frame_stride)
-            return wz_fail(WZ_ELIMIT, "camera %d, tile %d is %dx%d, engine was created for at most %dx%d", cam, t, r.w, r.h, e->max_w, e->max_h);
-        g.tiles.push_back(r);
-        g.cols.push_back((r.w + WZ_GATE_CELL - 1) / WZ_GATE_CELL);
-        g.crows.push_back((r.h + WZ_GATE_CELL - 1) / WZ_GATE_CELL);
-        g.grid_off.push_back(cells);
-        cells += (gate_cells_of(r.w, r.h) + 7) & ~(size_t)7;   // (every grid begins at a 16-byte boundary)
-    }
-    g.has_ref.assign(n_tiles, 0);
-    g.skipped.assign(n_tiles, 0);
-    HIPCHK(hipSetDevice(e->device));
-    { int _rc = sync_all(e); if (_rc != WZ_OK) return _rc; }
-    // the new state is allocated aside: a failure leaves the camera with the layout (and the references) it had
-    hipError_t err = hipMalloc((void**)&g.d_ref, cells * 2);
-    if (err == hipSuccess) err = hipMalloc((void**)&g.d_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS * n_tiles);
-    if (err != hipSuccess) {
-        if (g.d_ref) (void)hipFree(g.d_ref);
-        return wz_fail(WZ_EHIP, "wz_set_camera_tiles: %s (camera %d keeps its previous tiles)", hipGetErrorString(err), cam);
-    }
-    auto it = e->gate_cams.find(cam);
-    if (it != e->gate_cams.end()) {   // nothing in flight reads the old state: every lane was synchronised above
-        (void)hipFree(it->second.d_ref);
-        (void)hipFree(it->second.d_rows);
-    }
-    e->gate_cams[cam] = std::move(g);
-    return WZ_OK;
-}
-
-extern "C" int wz_reset_camera_tiles(wz_engine_t* e, int cam) {
-    if (!e) return wz_fail(WZ_EINVAL, "wz_reset_camera_tiles: null engine");
-    auto it = e->gate_cams.find(cam);
-    if (it == e->gate_cams.end()) return wz_fail(WZ_EINVAL, "camera %d has no tiles (wz_set_camera_tiles first)", cam);
-    HIPCHK(hipSetDevice(e->device));
-    { int _rc = sync_all(e); if (_rc != WZ_OK) return _rc; }
-    std::fill(it->second.has_ref.begin(), it->second.has_ref.end(), (uint8_t)0);
-    std::fill(it->second.skipped.begin(), it->second.skipped.end(), 0);
-    return WZ_OK;
-}
-
-extern "C" int wz_clear_camera_tiles(wz_engine_t* e, int cam) {
-    if (!e || cam < 0 || cam >= WZ_MAX_CAMS) return wz_fail(WZ_EINVAL, "wz_clear_camera_tiles: bad argument");
-    auto it = e->gate_cams.find(cam);
-    if (it == e->gate_cams.end()) return WZ_OK;
-    HIPCHK(hipSetDevice(e->device));
-    { int _rc = sync_all(e); if (_rc != WZ_OK) return _rc; }
-    (void)hipFree(it->second.d_ref);
-    (void)hipFree(it->second.d_rows);
-    e->gate_cams.erase(it);
-    return WZ_OK;
-}
-
-// Every refusal of a gated call (include/watsor_hip.h), before anything is enqueued, written or decided
-static int gated_check(wz_engine* e, const char* who, int slot, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt,
-                       const int* cam, double iou_thr, double ios_thr, bool host, int* total) {
-    if (!e || !frames || !w || !h) return wz_fail(WZ_EINVAL, "%s: null argument", who);
-    if (slot < 0 || slot >= e->n_lanes) return wz_fail(WZ_EINVAL, "slot %d out of range [0,%d)", slot, e->n_lanes);
-    if (n < 1 || n > e->max_batch) return wz_fail(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
-    if (!cam) return wz_fail(WZ_EINVAL, "%s: a gated call needs the frames' camera ids", who);
-    int64_t sum = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!frames[i] || w[i] < 1 || h[i] < 1) return wz_fail(WZ_EINVAL, "frame %d: bad pointer or size", i);
-        auto it = cam[i] < 0 ? e->gate_cams.end() : e->gate_cams.find(cam[i]);
-        if (it == e->gate_cams.end()) return wz_fail(WZ_EINVAL, "frame %d: camera %d has no tiles (wz_set_camera_tiles first)", i, cam[i]);
-        for (int j = 0; j < i; ++j)
-            if (cam[j] == cam[i]) return wz_fail(WZ_EINVAL, "frames %d and %d are both camera %d's: one frame of a camera per gated call", j, i, cam[i]);
-        const GateCam& g = it->second;
-        const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
-        if (!wz_frame_bytes(w[i], h[i], pf))
-            return wz_fail(WZ_EINVAL, "frame %d: pixel format 0x%x at %dx%d: %s", i, pf, w[i], h[i], fmt_refusal(w[i], h[i], pf));
-        if (w[i] != g.w || h[i] != g.h || (pf & WZ_FMT_BASE_MASK) != g.base)
-            return wz_fail(WZ_EINVAL, "frame %d is %dx%d in base format %d but camera %d's tiles were set for %dx%d in base format %d", i, w[i], h[i],
-                           pf & WZ_FMT_BASE_MASK, cam[i], g.w, g.h, g.base);
-        if (host && (w[i] > e->max_w || h[i] > e->max_h || (size_t)w[i] * h[i] * 3 > e->frame_stride))
-            return wz_fail(WZ_ELIMIT, "frame %d is %dx%d, engine was created for at most %dx%d", i, w[i], h[i], e->max_w, e->max_h);
-        if (e->h_cams[cam[i]].enabled && (e->h_cams[cam[i]].width != w[i] || e->h_cams[cam[i]].height != h[i]))
-            return wz_fail(WZ_EINVAL, "frame %d is %dx%d but camera %d filter was set for %dx%d", i, w[i], h[i], cam[i],
-                           e->h_cams[cam[i]].width, e->h_cams[cam[i]].height);
-        sum += (int64_t)g.tiles.size();
-    }
-    if (sum > e->max_batch) return wz_fail(WZ_ELIMIT, "the %lld tiles configured for the cameras of one call exceed max_batch %d", (long long)sum, e->max_batch);
-    if (!(iou_thr >= 0.0) || !(ios_thr >= 0.0)) return wz_fail(WZ_EINVAL, "%s: the merge thresholds must be numbers >= 0", who);
-    *total = (int)sum;
-    return WZ_OK;
-}
-
-// The host's rule: does tile t of camera g run, given its activity?
-static bool gate_runs(const GateCam& g, int t, int activity) {
-    return !g.has_ref[t] || activity >= g.gate.min_cells || (g.gate.max_age > 0 && g.skipped[t] >= g.gate.max_age);
-}
-
-// A checked gated call on a drained lane, frames in device memory.  Returns once the decision is made; crop, batch, commit, merge and
-// filters are enqueued behind it and the lane's event behind them.
-static int gated_enqueue(wz_engine* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
-                         const int* cam, double iou_thr, double ios_thr, int total) {
-    Lane& L = e->lanes[slot];
-    int rc = ensure_tiled(e, L);
-    if (rc == WZ_OK) rc = ensure_gated(e, L);
-    if (rc != WZ_OK) return rc;
-    std::vector<GateCam*> cams(n);
-    for (int i = 0; i < n; ++i) {
-        cams[i] = &e->gate_cams.find(cam[i])->second;
-        // another lane's commit launch may still be writing this camera's references and cached rows
-        if (cams[i]->lane >= 0 && cams[i]->lane != slot) HIPCHK(hipEventSynchronize(e->lanes[cams[i]->lane].done));
-    }
-    // 1. activity of every tile, one launch
-    const size_t lane_cells = gate_cells_of(e->max_w, e->max_h);
-    WzGateCommit* commits = gate_commits(e, L.h_gmeta);
-    int32_t* act = gate_activity(e, L.h_gmeta);
-    int k = 0, crows = 0, cols = 0;
-    for (int i = 0; i < n; ++i) {
-        GateCam& g = *cams[i];
-        const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
-        for (size_t t = 0; t < g.tiles.size(); ++t, ++k) {
-            WzGateTile& d = L.h_gmeta[k];
-            gate_tile(d_frames[i], w[i], pf, g.tiles[t], d);
-            d.ref = g.has_ref[t] ? g.d_ref + g.grid_off[t] : nullptr;
-            d.now = L.d_gnow + lane_cells * k;
-            d.thr = g.gate.pixel_thr;
-            crows = std::max(crows, d.crows);
-            cols = std::max(cols, d.cols);
-            act[k] = 0;
-        }
-    }
-    wz_launch_tile_activity(L.m_gmeta, total, crows, cols, L.d_gcount, gate_activity(e, L.m_gmeta), L.stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(L.stream));   // the batch size is a host-side quantity: the decision waits for the counts
-    // 2. the decision; the cameras' state changes only once everything is enqueued
-    std::vector<uint8_t> runs(total);
-    std::vector<WzCropPlane> planes;
-    std::vector<const uint8_t*> tptr;
-    std::vector<int> tw, th, tf;
-    int32_t* origins = reinterpret_cast<int32_t*>(L.h_tmeta + e->max_batch);
-    int most = 0;
-    k = 0;
-    for (int i = 0; i < n; ++i) {
-        GateCam& g = *cams[i];
-        const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
-        const int nt = (int)g.tiles.size();
-        L.h_tmeta[i] = {k, nt, cam[i], 0};
-        most = std::max(most, nt);
-        for (int t = 0; t < nt; ++t, ++k) {
-            const wz_tile_t& r = g.tiles[t];
-            runs[k] = gate_runs(g, t, act[k]) ? 1 : 0;
-            commits[k].ref = g.d_ref + g.grid_off[t];
-            commits[k].now = L.h_gmeta[k].now;
-            commits[k].cache = g.d_rows + (size_t)t * WZ_MAX_DETECTIONS;
-            commits[k].cells = L.h_gmeta[k].cols * L.h_gmeta[k].crows;
-            commits[k].fresh = -1;
-            if (runs[k]) {
-                commits[k].fresh = (int)tptr.size();
-                uint8_t* dst = L.d_tiles + e->frame_stride * tptr.size();
-                tile_planes(d_frames[i], w[i], h[i], pf, r, dst, planes);
-                tptr.push_back(dst); tw.push_back(r.w); th.push_back(r.h); tf.push_back(pf);
-            }
-            origins[2 * k] = r.x0;
-            origins[2 * k + 1] = r.y0;
-        }
-    }
-    // 3. the tiles that run, as an ordinary batch without cameras (none: no crop, no batch)
-    const int running = (int)tptr.size();
-    if (running) {
-        wz_launch_crop_tiles(planes.data(), (int)planes.size(), L.stream);
-        rc = fill_desc(e, slot, running, tptr.data(), tw.data(), th.data(), tf.data(), nullptr);
-        if (rc != WZ_OK) return rc;
-        L.rows = e->pre_rows;
-        rc = run_batch(e, slot, running);
-        if (rc != WZ_OK) return rc;
-    } else {
-        L.bound_idx.clear();
-        L.n = 0;   // (no tile ran: no status word is this call's)
-    }
-    // 4. commit, merge, filters
-    wz_launch_gate_commit(gate_commits(e, L.m_gmeta), total, L.m_rows, L.d_grows, L.stream);
-    const int32_t* m_origins = reinterpret_cast<const int32_t*>(L.m_tmeta + e->max_batch);
-    wz_launch_merge_tiles(L.m_tmeta, m_origins, L.d_grows, L.d_tcand, n, most, iou_thr, ios_thr, L.m_trows, L.m_tpass, L.stream);
-    for (int i = 0; i < n; ++i)
-        if (e->h_cams[cam[i]].enabled)
-            wz_launch_filter_rows(e->d_cams, cam[i], L.m_trows + (size_t)i * WZ_MAX_DETECTIONS, L.m_tpass + (size_t)i * WZ_MAX_DETECTIONS, L.stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(L.done, L.stream));
-    L.tiled = n;
-    // 5. the state the commit launch leaves behind, and what wz_gate_stats reports
-    L.g_ran.assign(n, 0);
-    L.g_act.assign(act, act + total);
-    L.g_tiles = total; L.g_crows = crows; L.g_cols = cols;
-    k = 0;
-    for (int i = 0; i < n; ++i) {
-        GateCam& g = *cams[i];
-        g.lane = slot;
-        for (size_t t = 0; t < g.tiles.size(); ++t, ++k) {
-            if (runs[k]) {
-                g.has_ref[t] = 1;
-                g.skipped[t] = 0;
-                L.g_ran[i] |= 1ull << t;
-            } else {
-                ++g.skipped[t];
-            }
-        }
-    }
-    return WZ_OK;
-}
-
-extern "C" int wz_submit_gated_device(wz_engine_t* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
-                                      const int* cam, double iou_thr, double ios_thr) {
-    int total = 0;
-    int rc = gated_check(e, "wz_submit_gated_device", slot, n, d_frames, w, h, fmt, cam, iou_thr, ios_thr, false, &total);
-    if (rc != WZ_OK) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipEventSynchronize(e->lanes[slot].done));   // the lane's previous batch has fully drained
-    return gated_enqueue(e, slot, n, d_frames, w, h, fmt, cam, iou_thr, ios_thr, total);
-}
-
-extern "C" int wz_detect_gated(wz_engine_t* e, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt, const int* cam,
-                               double iou_thr, double ios_thr, wz_detection_t* const* out, uint8_t* const* pass, float* ms) {
-    int total = 0;
-    int rc = gated_check(e, "wz_detect_gated", 0, n, frames, w, h, fmt, cam, iou_thr, ios_thr, true, &total);
-    if (rc != WZ_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipSetDevice(e->device));
-    Lane& L = e->lanes[0];
-    HIPCHK(hipEventSynchronize(L.done));
-    std::vector<const uint8_t*> dptr(n);
-    for (int i = 0; i < n; ++i) {   // the whole frame into the lane's staging area, as wz_detect_tiled stages it
-        rc = stage_frame(e, L, i, frames[i], wz_frame_bytes(w[i], h[i], fmt ? fmt[i] : WZ_FMT_RGB24), &dptr[i]);
-        if (rc != WZ_OK) return rc;
-    }
-    rc = gated_enqueue(e, 0, n, dptr.data(), w, h, fmt, cam, iou_thr, ios_thr, total);
-    if (rc != WZ_OK) return rc;
-    rc = wz_collect(e, 0, out, pass);
-    if (rc != WZ_OK && rc != WZ_EINCOMPLETE) return rc;
-    const float el = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (ms)
-        for (int i = 0; i < n; ++i) ms[i] = el;
-    return rc;   // WZ_OK, or WZ_EINCOMPLETE: the merged rows are written, the rows of a tile that ran in this call may have been short
-}
-
-extern "C" int wz_gate_stats(wz_engine_t* e, int slot, int n, uint64_t* ran_mask, int32_t* activity) {
-    if (!e || !ran_mask || slot < 0 || slot >= e->n_lanes) return wz_fail(WZ_EINVAL, "wz_gate_stats: bad argument");
-    const Lane& L = e->lanes[slot];
-    if (n < 1 || n != (int)L.g_ran.size()) return wz_fail(WZ_EINVAL, "wz_gate_stats: the last gated call on lane %d had %d frames, not %d", slot, (int)L.g_ran.size(), n);
-    memcpy(ran_mask, L.g_ran.data(), sizeof(uint64_t) * n);
-    if (activity) memcpy(activity, L.g_act.data(), sizeof(int32_t) * L.g_act.size());
-    return WZ_OK;
-}
-
 // ------------------------------------------------------------------------------------------------
 // the worker's frame table: every Frame of every FrameBuffer described once (watsor/stream/share.py:27-41,76-81 -- sizes,
 // pixels and rows of a frame never change after the buffers are created), a batch is then a list of indices
@@ -2118,151 +1398,18 @@ extern "C" int wz_bind_frames(wz_engine_t* e, int n, const uint8_t* const* pixel
                               const int* cam, wz_detection_t* const* rows) {
     if (!e || n < 0 || (n && (!pixels || !w || !h || !rows))) return wz_fail(WZ_EINVAL, "wz_bind_frames: bad argument");
     HIPCHK(hipSetDevice(e->device));
-    int rc = sync_all(e);   // no batch in flight refers to the old table
-    if (rc != WZ_OK) return rc;
+    WZCHK(sync_all(e));   // no batch in flight refers to the old table
     std::vector<wz_engine::BoundFrame> tbl((size_t)n);
     for (int i = 0; i < n; ++i) {
         const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
         const int c = cam ? cam[i] : -1;
-        if (!pixels[i] || !rows[i] || w[i] < 1 || h[i] < 1) return wz_fail(WZ_EINVAL, "frame-table entry %d: bad pointer or size", i);
+        WZCHK(frame_refusal(e, "frame-table entry", i, rows[i] ? pixels[i] : nullptr, w[i], h[i], pf, c, FC_PTR | FC_FMT | FC_LIMIT | FC_CAM_ID));
         const uint64_t bytes = wz_frame_bytes(w[i], h[i], pf);
-        if (!bytes) return wz_fail(WZ_EINVAL, "frame-table entry %d: pixel format 0x%x at %dx%d: %s", i, pf, w[i], h[i], fmt_refusal(w[i], h[i], pf));
-        if (w[i] > e->max_w || h[i] > e->max_h || (size_t)w[i] * h[i] * 3 > e->frame_stride)
-            return wz_fail(WZ_ELIMIT, "frame-table entry %d is %dx%d, engine was created for at most %dx%d", i, w[i], h[i], e->max_w, e->max_h);
-        if (c >= WZ_MAX_CAMS) return wz_fail(WZ_ELIMIT, "camera id %d >= %d", c, WZ_MAX_CAMS);
         tbl[i] = {pixels[i], device_view(e, pixels[i], bytes), w[i], h[i], pf, c < 0 ? -1 : c, bytes, rows[i]};
     }
     for (int li = 0; li < e->n_lanes; ++li) e->lanes[li].bound_idx.clear();
     e->bound.swap(tbl);
     e->bound_tiles.clear();   // (the table is replaced: so is every tiled description of its entries)
-    return WZ_OK;
-}
-
-// Entries first .. first + count - 1 get a tiled description (include/watsor_hip.h); checked against every entry as tiled_check checks a
-// call, nothing changes on a refusal.
-extern "C" int wz_bind_tiles(wz_engine_t* e, int first, int count, int n_tiles, const wz_tile_t* tiles, double iou_thr, double ios_thr, int gated) {
-    if (!e) return wz_fail(WZ_EINVAL, "wz_bind_tiles: null engine");
-    HIPCHK(hipSetDevice(e->device));
-    int rc = sync_all(e);   // no batch in flight was planned with the old descriptions
-    if (rc != WZ_OK) return rc;
-    const int64_t size = (int64_t)e->bound.size();
-    if (first < 0 || count < 1 || (int64_t)first + count > size)
-        return wz_fail(WZ_EINVAL, "wz_bind_tiles: entries %d .. %lld lie outside the frame table of %lld entries", first, (long long)first + count - 1,
-                       (long long)size);
-    wz_engine::BoundTiles d;
-    if (gated) {
-        if (tiles || n_tiles != 0)
-            return wz_fail(WZ_EINVAL, "wz_bind_tiles: a gated description takes its %d rectangles from wz_set_camera_tiles: tiles must be NULL and n_tiles 0", n_tiles);
-        const int c = e->bound[first].cam;
-        for (int i = first; i < first + count; ++i)
-            if (e->bound[i].cam < 0 || e->bound[i].cam != c)
-                return wz_fail(WZ_EINVAL, "wz_bind_tiles: gated entries %d .. %d must carry one camera id >= 0, entry %d has %d and entry %d has %d", first,
-                               first + count - 1, first, c, i, e->bound[i].cam);
-        d.kind = wz_engine::BOUND_GATED;
-    } else if (n_tiles == 0 && !tiles) {
-        d.kind = wz_engine::BOUND_PLAIN;
-    } else {
-        const int most = std::min(WZ_MAX_TILES, e->max_batch);
-        if (n_tiles < 1 || n_tiles > most) return wz_fail(WZ_ELIMIT, "wz_bind_tiles: %d tiles, an entry of this engine takes 1 to %d", n_tiles, most);
-        if (!tiles) return wz_fail(WZ_EINVAL, "wz_bind_tiles: %d tiles but no rectangles", n_tiles);
-        for (int i = first; i < first + count; ++i) {
-            const wz_engine::BoundFrame& f = e->bound[i];
-            for (int t = 0; t < n_tiles; ++t) {
-                const wz_tile_t& r = tiles[t];
-                const char* why = tile_refusal(r, f.w, f.h, f.fmt);
-                if (why) return wz_fail(WZ_EINVAL, "frame-table entry %d (%dx%d, format 0x%x), tile %d (%d, %d, %d x %d): %s", i, f.w, f.h, f.fmt, t, r.x0, r.y0, r.w, r.h, why);
-                if (r.w > e->max_w || r.h > e->max_h || (size_t)r.w * r.h * 3 > e->frame_stride)
-                    return wz_fail(WZ_ELIMIT, "frame-table entry %d, tile %d is %dx%d, engine was created for at most %dx%d", i, t, r.w, r.h, e->max_w, e->max_h);
-            }
-        }
-        d.kind = wz_engine::BOUND_TILED;
-        d.tiles.assign(tiles, tiles + n_tiles);
-    }
-    if (d.kind != wz_engine::BOUND_PLAIN) {
-        if (!(iou_thr >= 0.0) || !(ios_thr >= 0.0)) return wz_fail(WZ_EINVAL, "wz_bind_tiles: the merge thresholds (%g, %g) must be numbers >= 0", iou_thr, ios_thr);
-        d.iou = iou_thr;
-        d.ios = ios_thr;
-        if (e->bound_tiles.empty()) e->bound_tiles.resize(e->bound.size());
-    }
-    if (e->bound_tiles.empty()) return WZ_OK;   // (untiled entries of a table without descriptions)
-    for (int i = first; i < first + count; ++i) e->bound_tiles[i] = d;
-    bool any = false;
-    for (const auto& b : e->bound_tiles) any = any || b.kind != wz_engine::BOUND_PLAIN;
-    if (!any) e->bound_tiles.clear();
-    return WZ_OK;
-}
-
-// The bytes the crop kernel (and, gated, the activity kernel before it) reads of a frame: what decides between reading a page-locked frame in
-// place and staging it whole.  Break-even by bandwidth is near 0.8 of the frame's bytes (a kernel reads mapped memory at 23 GB/s beside the
-// other lanes' kernels, the copies move 29 GB/s: see stage_frame above); one half is the margin read_in_place() uses for the resize kernel.
-// Measured for the crop kernel (profiles/bound_tiles.txt; one 640 x 480 rectangle of a 1080p frame, four lanes busy):
-// RGB24, cost 0.15 of the frame: 5600 frames/s in place against 5565 staged -- level -- and a lone call 0.326 against 0.426 ms; NV12, cost
-// 0.15: 5825 in place against 8247 staged, a lone call 0.318 against 0.374 ms.  So at a cost well under one half, reading in place is
-// SLOWER than staging with every lane busy once the whole frame is small (3.1 MB): both in-place legs sit at ~0.175 ms a step whatever
-// they read.  The constant stays at one half here; moving it (or bounding it by the frame's bytes) needs that plateau explained first.
-static bool tiles_in_place(const wz_engine* e, const wz_engine::BoundFrame& f, const std::vector<wz_tile_t>& tiles, bool gated) {
-    if (!f.dev || e->host_read == 0) return false;
-    if (e->host_read == 1) return true;
-    uint64_t cost = 0;
-    for (const wz_tile_t& t : tiles) cost += wz_frame_bytes(t.w, t.h, f.fmt);
-    if (gated) cost *= 2;   // a gated tile is measured, and read again when it runs
-    return e->host_read == 2 && 2 * cost <= f.bytes;
-}
-
-static const char* bound_kind_name(int kind) { return kind == wz_engine::BOUND_TILED ? "tiled" : kind == wz_engine::BOUND_GATED ? "gated" : "untiled"; }
-
-// wz_submit_bound of a batch with a tiled or gated entry (slot, n and the entries' range are checked): one kind, one pair of thresholds,
-// the refusals of the tiled / gated call, then every frame staged whole or handed over in place, then tiled_enqueue / gated_enqueue.
-static int submit_bound_tiles(wz_engine* e, int slot, int n, const int32_t* entries) {
-    const wz_engine::BoundTiles& d0 = e->bound_tiles[entries[0]];
-    for (int i = 1; i < n; ++i) {
-        const wz_engine::BoundTiles& d = e->bound_tiles[entries[i]];
-        if (d.kind != d0.kind)
-            return wz_fail(WZ_EINVAL, "wz_submit_bound: frame-table entry %d is %s and entry %d is %s: a batch holds one kind", entries[0], bound_kind_name(d0.kind),
-                           entries[i], bound_kind_name(d.kind));
-    }
-    for (int i = 1; i < n; ++i) {
-        const wz_engine::BoundTiles& d = e->bound_tiles[entries[i]];
-        if (d.iou != d0.iou || d.ios != d0.ios)
-            return wz_fail(WZ_EINVAL, "wz_submit_bound: frame-table entry %d merges with thresholds (%g, %g) and entry %d with (%g, %g): a batch takes one pair",
-                           entries[0], d0.iou, d0.ios, entries[i], d.iou, d.ios);
-    }
-    const bool gated = d0.kind == wz_engine::BOUND_GATED;
-    std::vector<const uint8_t*> hptr(n), dptr(n);
-    std::vector<int> ws(n), hs(n), fmts(n), cams(n), nt(n);
-    std::vector<const wz_tile_t*> tp(n);
-    for (int i = 0; i < n; ++i) {
-        const wz_engine::BoundFrame& f = e->bound[entries[i]];
-        hptr[i] = f.host; ws[i] = f.w; hs[i] = f.h; fmts[i] = f.fmt; cams[i] = f.cam;
-        nt[i] = (int)e->bound_tiles[entries[i]].tiles.size();
-        tp[i] = e->bound_tiles[entries[i]].tiles.data();
-    }
-    int total = 0;
-    int rc = gated ? gated_check(e, "wz_submit_bound", slot, n, hptr.data(), ws.data(), hs.data(), fmts.data(), cams.data(), d0.iou, d0.ios, true, &total)
-                   : tiled_check(e, "wz_submit_bound", slot, n, hptr.data(), ws.data(), hs.data(), fmts.data(), cams.data(), nt.data(), tp.data(), d0.iou, d0.ios,
-                                 true, &total);
-    if (rc != WZ_OK) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    Lane& L = e->lanes[slot];
-    HIPCHK(hipEventSynchronize(L.done));   // the lane's previous batch (and its reads of the staging area) drained
-    if (!L.d_frames) return wz_fail(WZ_EINVAL, "wz_submit_bound: lane %d has no staging area", slot);
-    std::vector<int32_t> src(n);
-    for (int i = 0; i < n; ++i) {
-        const wz_engine::BoundFrame& f = e->bound[entries[i]];
-        const std::vector<wz_tile_t>& tiles = gated ? e->gate_cams.find(f.cam)->second.tiles : e->bound_tiles[entries[i]].tiles;
-        if (tiles_in_place(e, f, tiles, gated)) {
-            dptr[i] = f.dev;
-            src[i] = 1;
-            continue;
-        }
-        rc = stage_frame(e, L, i, f.host, f.bytes, &dptr[i]);
-        if (rc != WZ_OK) return rc;
-    }
-    rc = gated ? gated_enqueue(e, slot, n, dptr.data(), ws.data(), hs.data(), fmts.data(), cams.data(), d0.iou, d0.ios, total)
-               : tiled_enqueue(e, slot, n, dptr.data(), ws.data(), hs.data(), fmts.data(), cams.data(), nt.data(), tp.data(), d0.iou, d0.ios, total);
-    if (rc != WZ_OK) return rc;
-    L.bound_idx.assign(entries, entries + n);   // (L.tiled == n says that their rows are the merged ones)
-    L.bound_src.swap(src);
     return WZ_OK;
 }
 
@@ -2276,44 +1423,35 @@ extern "C" int wz_submit_bound(wz_engine_t* e, int slot, int n, const int32_t* e
     if (!e->bound_tiles.empty())           // some entry of the table has a tiled description (wz_bind_tiles): does one of these?
         for (int i = 0; i < n; ++i)
             if (e->bound_tiles[entries[i]].kind != wz_engine::BOUND_PLAIN) return submit_bound_tiles(e, slot, n, entries);
-    HIPCHK(hipSetDevice(e->device));
+    WZCHK(bound_drain(e, slot));
     Lane& L = e->lanes[slot];
-    HIPCHK(hipEventSynchronize(L.done));   // the lane's previous batch (and its reads of the staging area) drained
-    if (!L.d_frames) return wz_fail(WZ_EINVAL, "wz_submit_bound: lane %d has no staging area", slot);
     bool in_place = false;
-    std::vector<const uint8_t*> dptr(n);
-    std::vector<int> ws(n), hs(n), fmts(n), cams(n);
+    BoundBatch b;
+    bound_gather(e, n, entries, b);
     for (int i = 0; i < n; ++i) {
         const wz_engine::BoundFrame& f = e->bound[entries[i]];
-        // (the filter of the frame's camera may have been set for another size since the table was built: fill_desc checks)
-        ws[i] = f.w; hs[i] = f.h; fmts[i] = f.fmt; cams[i] = f.cam;
         if (f.dev && read_in_place(e, f.h)) {
-            dptr[i] = f.dev;
+            b.ptr[i] = f.dev;
             in_place = true;
             continue;
         }
-        int rc = stage_frame(e, L, i, f.host, f.bytes, &dptr[i]);
-        if (rc != WZ_OK) return rc;
+        WZCHK(stage_frame(e, L, i, f.host, f.bytes, &b.ptr[i]));
     }
-    int rc = fill_desc(e, slot, n, dptr.data(), ws.data(), hs.data(), fmts.data(), cams.data());
-    if (rc != WZ_OK) return rc;
+    // (the filter of a frame's camera may have been set for another size since the table was built: fill_desc checks)
+    WZCHK(fill_desc(e, slot, n, b.ptr.data(), b.w, b.h, b.fmt, b.cam));
     L.rows = e->pre_rows || in_place;
-    rc = run_batch(e, slot, n);
-    if (rc != WZ_OK) return rc;
+    WZCHK(run_batch(e, slot, n));
     L.bound_idx.assign(entries, entries + n);
     return WZ_OK;
 }
 
 extern "C" int wz_collect_bound(wz_engine_t* e, int slot) {
-    int rc = wz_wait(e, slot);
-    if (rc != WZ_OK) return rc;
+    WZCHK(wz_wait(e, slot));
     Lane& L = e->lanes[slot];
-    // a tiled or gated bound batch hands over its FRAMES' merged rows: L.tiled of them, whatever L.n says (the tiles that ran; none: 0)
-    const int n = L.tiled ? L.tiled : L.n;
-    const wz_detection_t* rows = L.tiled ? L.h_trows : L.h_rows;
-    if (L.bound_idx.empty() || (int)L.bound_idx.size() != n) return wz_fail(WZ_EINVAL, "wz_collect_bound: lane %d holds no bound batch", slot);
-    for (int i = 0; i < n; ++i)
-        memcpy(e->bound[L.bound_idx[i]].rows, rows + (size_t)i * WZ_MAX_DETECTIONS, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS);
+    const LaneResult r = lane_result(L);
+    if (L.bound_idx.empty() || (int)L.bound_idx.size() != r.n) return wz_fail(WZ_EINVAL, "wz_collect_bound: lane %d holds no bound batch", slot);
+    for (int i = 0; i < r.n; ++i)
+        memcpy(e->bound[L.bound_idx[i]].rows, r.rows + (size_t)i * WZ_MAX_DETECTIONS, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS);
     L.bound_idx.clear();
     return lane_status(e, slot);
 }
@@ -2329,7 +1467,7 @@ extern "C" int wz_set_camera_filter(wz_engine_t* e, int cam, int width, int heig
     if (n_zones < 0 || n_zones > WZ_MAX_ZONES_PER_CAM) return wz_fail(WZ_ELIMIT, "%d zones > %d", n_zones, WZ_MAX_ZONES_PER_CAM);
     if (n_zones > 0 && !zone_fill) return wz_fail(WZ_EINVAL, "zone_fill is null");
     HIPCHK(hipSetDevice(e->device));
-    { int _rc = sync_all(e); if (_rc != WZ_OK) return _rc; }
+    WZCHK(sync_all(e));
     // the new state is built aside and committed only when all of it exists: a failure (e.g. no memory for the
     // summed-area tables of a 1080p multi-zone mask) leaves the camera's previous filter intact
     WzCamFilter c;
@@ -2375,7 +1513,7 @@ extern "C" int wz_set_camera_drop(wz_engine_t* e, int cam, int drop) {
     if (!e || cam < 0 || cam >= WZ_MAX_CAMS) return wz_fail(WZ_EINVAL, "wz_set_camera_drop: bad argument");
     if (!(e->h_cams[cam].enabled & 1)) return wz_fail(WZ_EINVAL, "camera %d has no filter (wz_set_camera_filter first)", cam);
     HIPCHK(hipSetDevice(e->device));
-    { int _rc = sync_all(e); if (_rc != WZ_OK) return _rc; }
+    WZCHK(sync_all(e));
     e->h_cams[cam].enabled = (e->h_cams[cam].enabled & ~2) | (drop ? 2 : 0);
     HIPCHK(lane0_copy(e, e->d_cams + cam, &e->h_cams[cam], sizeof(WzCamFilter), hipMemcpyHostToDevice));
     return WZ_OK;
@@ -2384,7 +1522,7 @@ extern "C" int wz_set_camera_drop(wz_engine_t* e, int cam, int drop) {
 extern "C" int wz_clear_camera_filter(wz_engine_t* e, int cam) {
     if (!e || cam < 0 || cam >= WZ_MAX_CAMS) return wz_fail(WZ_EINVAL, "wz_clear_camera_filter: bad argument");
     HIPCHK(hipSetDevice(e->device));
-    { int _rc = sync_all(e); if (_rc != WZ_OK) return _rc; }
+    WZCHK(sync_all(e));
     memset(&e->h_cams[cam], 0, sizeof(WzCamFilter));
     HIPCHK(lane0_copy(e, e->d_cams + cam, &e->h_cams[cam], sizeof(WzCamFilter), hipMemcpyHostToDevice));
     if (e->cam_sat[cam]) {
@@ -2460,7 +1598,7 @@ extern "C" int wz_debug_nms(wz_engine_t* e, int n, uint64_t* out) {
 extern "C" int wz_debug_mbconv(wz_engine_t* e, uint64_t* out, int32_t* groups) {
     if (!e || !out || !e->d_mbdbg) return wz_fail(WZ_EINVAL, "wz_debug_mbconv: create the engine with WZ_MB_DEBUG=1");
     HIPCHK(hipSetDevice(e->device));
-    { int _rc = sync_all(e); if (_rc != WZ_OK) return _rc; }
+    WZCHK(sync_all(e));
     HIPCHK(hipMemcpy(out, e->d_mbdbg, (size_t)e->hdr.n_ops * 16 * 8, hipMemcpyDeviceToHost));
     if (groups) memcpy(groups, e->mb_groups.data(), sizeof(int) * e->hdr.n_ops);
     return WZ_OK;
@@ -2532,9 +1670,8 @@ extern "C" int wz_profile_stages(wz_engine_t* e, int n, const uint8_t* const* d_
                                  int reps, int inner, float* stage_ms) {
     if (!e || !stage_ms || reps < 1 || inner < 1 || inner > 64) return wz_fail(WZ_EINVAL, "wz_profile_stages: bad argument");
     HIPCHK(hipSetDevice(e->device));
-    { int _rc = sync_all(e); if (_rc != WZ_OK) return _rc; }
-    int rc = fill_desc(e, 0, n, d_rgb, w, h, nullptr, nullptr);
-    if (rc != WZ_OK) return rc;
+    WZCHK(sync_all(e));
+    WZCHK(fill_desc(e, 0, n, d_rgb, w, h, nullptr, nullptr));
     e->lanes[0].rows = e->pre_rows;
     const size_t ns = e->stage_names.size();
     std::vector<double> acc(ns, 0.0);
@@ -2604,8 +1741,7 @@ extern "C" int wz_stage_preprocess_fmt(wz_engine_t* e, const uint8_t* rgb, int w
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipMemcpy(e->d_frames, rgb, bytes, hipMemcpyHostToDevice));
     const uint8_t* p = e->d_frames;
-    int rc = fill_desc(e, 0, 1, &p, &w, &h, &fmt, nullptr);
-    if (rc != WZ_OK) return rc;
+    WZCHK(fill_desc(e, 0, 1, &p, &w, &h, &fmt, nullptr));
     HIPCHK(hipMemcpyAsync(e->lanes[0].d_desc, e->lanes[0].h_desc, sizeof(WzFrameDesc), hipMemcpyHostToDevice, e->stream));
     const int S = (int)e->hdr.input_size;
     wz_launch_preprocess(e->lanes[0].d_desc, 1, S, e->lanes[0].tptr[input_tensor_index(e)], e->stream, input_is_pair(e), nullptr,
@@ -2685,198 +1821,6 @@ extern "C" int wz_stage_rows(wz_engine_t* e, int w, int h, const float* boxes, c
     wz_launch_rows(e->lanes[0].post, e->lanes[0].d_desc, e->d_cams, 1, e->pc.max_total, e->lanes[0].d_rows, e->lanes[0].d_pass, e->stream);
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipMemcpy(rows, e->lanes[0].d_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS, hipMemcpyDeviceToHost));
-    return WZ_OK;
-}
-// one tile of one host frame through wz_k_crop_tiles; the device copy of the frame starts at the host pointer's offset within 16 bytes, so
-// that what a caller does to the source's alignment reaches the kernel
-extern "C" int wz_stage_crop_tile(wz_engine_t* e, const uint8_t* frame, int w, int h, int fmt, const wz_tile_t* tile, uint8_t* out) {
-    if (!e || !frame || !tile || !out) return wz_fail(WZ_EINVAL, "wz_stage_crop_tile: null argument");
-    const uint64_t bytes = wz_frame_bytes(w, h, fmt);
-    if (!bytes) return wz_fail(WZ_EINVAL, "pixel format 0x%x at %dx%d: %s", fmt, w, h, fmt_refusal(w, h, fmt));
-    const char* why = tile_refusal(*tile, w, h, fmt);
-    if (why) return wz_fail(WZ_EINVAL, "tile (%d, %d, %d x %d) of a %dx%d frame: %s", tile->x0, tile->y0, tile->w, tile->h, w, h, why);
-    const uint64_t tbytes = wz_frame_bytes(tile->w, tile->h, fmt);
-    if (bytes >> 31) return wz_fail(WZ_ELIMIT, "frame too large");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    uint8_t* d_src = nullptr;
-    uint8_t* d_dst = nullptr;
-    const size_t skew = reinterpret_cast<uintptr_t>(frame) & 15u;
-    hipError_t err = hipMalloc((void**)&d_src, bytes + 16);
-    if (err == hipSuccess) err = hipMalloc((void**)&d_dst, tbytes);
-    if (err == hipSuccess) err = hipMemcpy(d_src + skew, frame, bytes, hipMemcpyHostToDevice);
-    if (err == hipSuccess) {
-        std::vector<WzCropPlane> planes;
-        tile_planes(d_src + skew, w, h, fmt, *tile, d_dst, planes);
-        wz_launch_crop_tiles(planes.data(), (int)planes.size(), e->stream);
-        err = hipStreamSynchronize(e->stream);
-    }
-    if (err == hipSuccess) err = hipMemcpy(out, d_dst, tbytes, hipMemcpyDeviceToHost);
-    if (d_src) (void)hipFree(d_src);
-    if (d_dst) (void)hipFree(d_dst);
-    if (err != hipSuccess) return wz_fail(WZ_EHIP, "wz_stage_crop_tile: %s", hipGetErrorString(err));
-    return WZ_OK;
-}
-
-// wz_k_merge_tiles (+ the camera's filter) on caller-provided tile rows of one w x h frame
-extern "C" int wz_stage_merge_tiles(wz_engine_t* e, int w, int h, int cam, int n_tiles, const wz_tile_t* tiles, const wz_detection_t* tile_rows,
-                                    double iou_thr, double ios_thr, wz_detection_t* rows, uint8_t* pass) {
-    if (!e || !tiles || !tile_rows || !rows || !pass || w < 1 || h < 1) return wz_fail(WZ_EINVAL, "wz_stage_merge_tiles: bad argument");
-    if (n_tiles < 1 || n_tiles > WZ_MAX_TILES) return wz_fail(WZ_ELIMIT, "%d tiles, a frame takes 1 to %d", n_tiles, WZ_MAX_TILES);
-    if (cam >= WZ_MAX_CAMS) return wz_fail(WZ_ELIMIT, "camera id %d >= %d", cam, WZ_MAX_CAMS);
-    if (cam >= 0 && e->h_cams[cam].enabled && (e->h_cams[cam].width != w || e->h_cams[cam].height != h))
-        return wz_fail(WZ_EINVAL, "the frame is %dx%d but camera %d filter was set for %dx%d", w, h, cam, e->h_cams[cam].width, e->h_cams[cam].height);
-    for (int t = 0; t < n_tiles; ++t)
-        if (tiles[t].w < 1 || tiles[t].h < 1 || tiles[t].x0 < 0 || tiles[t].y0 < 0 || (int64_t)tiles[t].x0 + tiles[t].w > w || (int64_t)tiles[t].y0 + tiles[t].h > h)
-            return wz_fail(WZ_EINVAL, "tile %d (%d, %d, %d x %d) is no rectangle of a %dx%d frame", t, tiles[t].x0, tiles[t].y0, tiles[t].w, tiles[t].h, w, h);
-    if (!(iou_thr >= 0.0) || !(ios_thr >= 0.0)) return wz_fail(WZ_EINVAL, "wz_stage_merge_tiles: the merge thresholds must be numbers >= 0");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    const size_t nr = (size_t)n_tiles * WZ_MAX_DETECTIONS;
-    const size_t off_meta = sizeof(wz_detection_t) * nr, off_org = off_meta + sizeof(WzMergeFrame), off_cand = off_org + 8 * (size_t)n_tiles,
-                 off_rows = off_cand + sizeof(WzMergeCand) * nr, off_pass = off_rows + sizeof(wz_detection_t) * WZ_MAX_DETECTIONS,
-                 all = off_pass + WZ_MAX_DETECTIONS;   // (every block's size is a multiple of 8: the offsets stay aligned)
-    uint8_t* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, all));
-    const WzMergeFrame fr = {0, n_tiles, cam < 0 ? -1 : cam, 0};
-    std::vector<int32_t> org(2 * (size_t)n_tiles);
-    for (int t = 0; t < n_tiles; ++t) org[2 * t] = tiles[t].x0, org[2 * t + 1] = tiles[t].y0;
-    hipError_t err = hipMemcpy(d, tile_rows, off_meta, hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(d + off_meta, &fr, sizeof(fr), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(d + off_org, org.data(), org.size() * 4, hipMemcpyHostToDevice);
-    if (err == hipSuccess) {
-        wz_detection_t* d_rows = reinterpret_cast<wz_detection_t*>(d + off_rows);
-        wz_launch_merge_tiles(reinterpret_cast<const WzMergeFrame*>(d + off_meta), reinterpret_cast<const int32_t*>(d + off_org),
-                              reinterpret_cast<const wz_detection_t*>(d), reinterpret_cast<WzMergeCand*>(d + off_cand), 1, n_tiles, iou_thr,
-                              ios_thr, d_rows, d + off_pass, e->stream);
-        if (cam >= 0 && e->h_cams[cam].enabled) wz_launch_filter_rows(e->d_cams, cam, d_rows, d + off_pass, e->stream);
-        err = hipStreamSynchronize(e->stream);
-    }
-    if (err == hipSuccess) err = hipMemcpy(rows, d + off_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS, hipMemcpyDeviceToHost);
-    if (err == hipSuccess) err = hipMemcpy(pass, d + off_pass, WZ_MAX_DETECTIONS, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (err != hipSuccess) return wz_fail(WZ_EHIP, "wz_stage_merge_tiles: %s", hipGetErrorString(err));
-    return WZ_OK;
-}
-// HIP-event time of the crop launch alone and of the merge launch alone (no filter launch), on lane 0 behind one whole tiled call of the
-// same arguments (so that the merge reads real tile rows): the mean of `reps` brackets each, in milliseconds; empty_ms: the same bracket around nothing
-extern "C" int wz_debug_bound_source(wz_engine_t* e, int slot, int32_t* in_place) {
-    if (!e || !in_place || slot < 0 || slot >= e->n_lanes) return wz_fail(WZ_EINVAL, "wz_debug_bound_source: bad argument");
-    const Lane& L = e->lanes[slot];
-    if (L.bound_src.empty()) return wz_fail(WZ_EINVAL, "wz_debug_bound_source: lane %d has seen no tiled or gated bound batch", slot);
-    memcpy(in_place, L.bound_src.data(), sizeof(int32_t) * L.bound_src.size());
-    return WZ_OK;
-}
-
-extern "C" int wz_profile_tiled(wz_engine_t* e, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
-                                const int* n_tiles, const wz_tile_t* const* tiles, double iou_thr, double ios_thr, int reps,
-                                float* crop_ms, float* merge_ms, float* empty_ms) {
-    if (reps < 1 || !crop_ms || !merge_ms || !empty_ms) return wz_fail(WZ_EINVAL, "wz_profile_tiled: bad argument");
-    int rc = wz_submit_tiled_device(e, 0, n, d_frames, w, h, fmt, nullptr, n_tiles, tiles, iou_thr, ios_thr);
-    if (rc != WZ_OK) return rc;
-    rc = wz_wait(e, 0);
-    if (rc != WZ_OK) return rc;
-    Lane& L = e->lanes[0];
-    int total = 0;
-    for (int i = 0; i < n; ++i) total += n_tiles[i];
-    TiledLayout y;
-    tiled_layout(e, L, n, d_frames, w, h, fmt, nullptr, n_tiles, tiles, total, y);
-    hipEvent_t a, b;
-    HIPCHK(hipEventCreate(&a));
-    HIPCHK(hipEventCreate(&b));
-    double sum[3] = {0.0, 0.0, 0.0};   // crop, merge, two event records with nothing between them (the bracket's own cost)
-    const int32_t* m_origins = reinterpret_cast<const int32_t*>(L.m_tmeta + e->max_batch);
-    for (int which = 0; which < 3; ++which)
-        for (int r = 0; r < reps + 3; ++r) {   // (three unmeasured launches first)
-            HIPCHK(hipEventRecord(a, L.stream));
-            if (which == 0) wz_launch_crop_tiles(y.planes.data(), (int)y.planes.size(), L.stream);
-            else if (which == 1) wz_launch_merge_tiles(L.m_tmeta, m_origins, L.m_rows, L.d_tcand, n, y.most, iou_thr, ios_thr, L.m_trows, L.m_tpass, L.stream);
-            HIPCHK(hipEventRecord(b, L.stream));
-            HIPCHK(hipEventSynchronize(b));
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, a, b));
-            if (r >= 3) sum[which] += ms;
-        }
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-    *crop_ms = (float)(sum[0] / reps);
-    *merge_ms = (float)(sum[1] / reps);
-    *empty_ms = (float)(sum[2] / reps);
-    return WZ_OK;
-}
-// wz_k_tile_activity on one rectangle of one host frame; the device copy of the frame starts at the host pointer's offset within 16 bytes
-extern "C" int wz_stage_tile_activity(wz_engine_t* e, const uint8_t* frame, int w, int h, int fmt, const wz_tile_t* tile, const uint16_t* ref,
-                                      int pixel_thr, uint16_t* sums_out, int32_t* changed_out) {
-    if (!e || !frame || !tile || !sums_out || !changed_out) return wz_fail(WZ_EINVAL, "wz_stage_tile_activity: null argument");
-    const uint64_t bytes = wz_frame_bytes(w, h, fmt);
-    if (!bytes) return wz_fail(WZ_EINVAL, "pixel format 0x%x at %dx%d: %s", fmt, w, h, fmt_refusal(w, h, fmt));
-    const char* why = tile_refusal(*tile, w, h, fmt);
-    if (why) return wz_fail(WZ_EINVAL, "tile (%d, %d, %d x %d) of a %dx%d frame: %s", tile->x0, tile->y0, tile->w, tile->h, w, h, why);
-    if (pixel_thr < 0 || pixel_thr > 255) return wz_fail(WZ_EINVAL, "pixel_thr %d, expected 0 .. 255", pixel_thr);
-    if (bytes >> 31) return wz_fail(WZ_ELIMIT, "frame too large");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    const size_t cells = gate_cells_of(tile->w, tile->h), skew = reinterpret_cast<uintptr_t>(frame) & 15u;
-    const size_t off_ref = (cells * 2 + 15) & ~(size_t)15, off_desc = 2 * off_ref, off_cnt = off_desc + 64, all = off_cnt + 16;
-    uint8_t* d_src = nullptr;
-    uint8_t* d = nullptr;   // new grid, reference grid, the tile's descriptor, the counters and the count
-    hipError_t err = hipMalloc((void**)&d_src, bytes + 16);
-    if (err == hipSuccess) err = hipMalloc((void**)&d, all);
-    if (err == hipSuccess) err = hipMemset(d, 0, all);
-    if (err == hipSuccess) err = hipMemcpy(d_src + skew, frame, bytes, hipMemcpyHostToDevice);
-    if (err == hipSuccess && ref) err = hipMemcpy(d + off_ref, ref, cells * 2, hipMemcpyHostToDevice);
-    if (err == hipSuccess) {
-        static_assert(sizeof(WzGateTile) <= 64, "the descriptor's slot");
-        WzGateTile g;
-        gate_tile(d_src + skew, w, fmt, *tile, g);
-        g.ref = ref ? reinterpret_cast<const uint16_t*>(d + off_ref) : nullptr;
-        g.now = reinterpret_cast<uint16_t*>(d);
-        g.thr = pixel_thr;
-        err = hipMemcpy(d + off_desc, &g, sizeof(g), hipMemcpyHostToDevice);
-        if (err == hipSuccess) {
-            int32_t* cnt = reinterpret_cast<int32_t*>(d + off_cnt);
-            wz_launch_tile_activity(reinterpret_cast<const WzGateTile*>(d + off_desc), 1, g.crows, g.cols, cnt, cnt + 2, e->stream);
-            err = hipStreamSynchronize(e->stream);
-        }
-    }
-    if (err == hipSuccess) err = hipMemcpy(sums_out, d, cells * 2, hipMemcpyDeviceToHost);
-    if (err == hipSuccess) err = hipMemcpy(changed_out, d + off_cnt + 8, 4, hipMemcpyDeviceToHost);
-    if (d_src) (void)hipFree(d_src);
-    if (d) (void)hipFree(d);
-    if (err != hipSuccess) return wz_fail(WZ_EHIP, "wz_stage_tile_activity: %s", hipGetErrorString(err));
-    return WZ_OK;
-}
-
-// HIP-event time of the activity launch alone and of the commit launch alone, exactly as one gated call of these arguments on lane 0 issued
-// them (their descriptors are still in the lane's block; both launches leave what they wrote the first time): the mean of `reps` brackets
-extern "C" int wz_profile_gated(wz_engine_t* e, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt, const int* cam,
-                                double iou_thr, double ios_thr, int reps, float* activity_ms, float* commit_ms, float* empty_ms) {
-    if (reps < 1 || !activity_ms || !commit_ms || !empty_ms) return wz_fail(WZ_EINVAL, "wz_profile_gated: bad argument");
-    int rc = wz_submit_gated_device(e, 0, n, d_frames, w, h, fmt, cam, iou_thr, ios_thr);
-    if (rc != WZ_OK) return rc;
-    rc = wz_wait(e, 0);
-    if (rc != WZ_OK) return rc;
-    Lane& L = e->lanes[0];
-    hipEvent_t a, b;
-    HIPCHK(hipEventCreate(&a));
-    HIPCHK(hipEventCreate(&b));
-    double sum[3] = {0.0, 0.0, 0.0};
-    for (int which = 0; which < 3; ++which)
-        for (int r = 0; r < reps + 3; ++r) {   // (three unmeasured launches first)
-            HIPCHK(hipEventRecord(a, L.stream));
-            if (which == 0) wz_launch_tile_activity(L.m_gmeta, L.g_tiles, L.g_crows, L.g_cols, L.d_gcount, gate_activity(e, L.m_gmeta), L.stream);
-            else if (which == 1) wz_launch_gate_commit(gate_commits(e, L.m_gmeta), L.g_tiles, L.m_rows, L.d_grows, L.stream);
-            HIPCHK(hipEventRecord(b, L.stream));
-            HIPCHK(hipEventSynchronize(b));
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, a, b));
-            if (r >= 3) sum[which] += ms;
-        }
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-    *activity_ms = (float)(sum[0] / reps);
-    *commit_ms = (float)(sum[1] / reps);
-    *empty_ms = (float)(sum[2] / reps);
     return WZ_OK;
 }
 #endif   // WZ_DEV_BUILD

@@ -1,0 +1,806 @@
+// Tiled, gated and tiled frame-table detection (include/watsor_hip.h; DESIGN.md sections 15 - 17): eager launches of k_tiles.hip and
+// k_gate.hip around run_batch.  wz_engine.hip knows nothing of this file but TileLane / GateLane / GateCam's release, the lane's
+// `tile.tiled` and submit_bound_tiles (wz_engine.h).
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+
+#include "wz_engine.h"
+
+typedef wz_engine::GateCam GateCam;
+
+// ---- lane and camera state
+// Everything a lane needs for tiled calls, allocated the first time it sees one (an engine that never does uses no byte of it).
+int TileLane::alloc(wz_engine* e) {
+    if (d_tiles) return WZ_OK;
+    const size_t nb = (size_t)e->max_batch, rows = nb * WZ_MAX_DETECTIONS;
+    TileLane t;
+    hipError_t err = hipMalloc((void**)&t.d_tiles, e->frame_stride * nb);
+    if (err == hipSuccess) err = hipMalloc((void**)&t.d_tcand, sizeof(WzMergeCand) * rows);
+    if (err == hipSuccess) err = hipHostMalloc((void**)&t.h_trows, sizeof(wz_detection_t) * rows, hipHostMallocMapped);
+    if (err == hipSuccess) err = hipHostMalloc((void**)&t.h_tpass, rows, hipHostMallocMapped);
+    if (err == hipSuccess) err = hipHostMalloc((void**)&t.h_tmeta, (sizeof(WzMergeFrame) + 8) * nb, hipHostMallocMapped);
+    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&t.m_trows, t.h_trows, 0);
+    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&t.m_tpass, t.h_tpass, 0);
+    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&t.m_tmeta, t.h_tmeta, 0);
+    if (err != hipSuccess) {
+        t.release();
+        return wz_set_error(WZ_EHIP, "tile staging of a lane (%zu bytes): %s", e->frame_stride * nb, hipGetErrorString(err));
+    }
+    t.tiled = tiled;
+    *this = t;
+    return WZ_OK;
+}
+void TileLane::release() {
+    if (d_tiles) (void)hipFree(d_tiles);
+    if (d_tcand) (void)hipFree(d_tcand);
+    if (h_trows) (void)hipHostFree(h_trows);
+    if (h_tpass) (void)hipHostFree(h_tpass);
+    if (h_tmeta) (void)hipHostFree(h_tmeta);
+    *this = TileLane();
+}
+
+static size_t gate_cells_of(int w, int h) {
+    return (size_t)((w + WZ_GATE_CELL - 1) / WZ_GATE_CELL) * (size_t)((h + WZ_GATE_CELL - 1) / WZ_GATE_CELL);
+}
+// the pinned block of a lane: the activity launch's tiles, the commit launch's tiles, the activity counts
+static WzGateCommit* gate_commits(wz_engine* e, WzGateTile* meta) { return reinterpret_cast<WzGateCommit*>(meta + e->max_batch); }
+static int32_t* gate_activity(wz_engine* e, WzGateTile* meta) { return reinterpret_cast<int32_t*>(gate_commits(e, meta) + e->max_batch); }
+
+int GateLane::alloc(wz_engine* e) {
+    if (d_gnow) return WZ_OK;
+    const size_t nb = (size_t)e->max_batch, cells = gate_cells_of(e->max_w, e->max_h);
+    GateLane g;
+    hipError_t err = hipMalloc((void**)&g.d_gnow, cells * 2 * nb);
+    if (err == hipSuccess) err = hipMalloc((void**)&g.d_grows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS * nb);
+    if (err == hipSuccess) err = hipMalloc((void**)&g.d_gcount, 8 * nb);
+    if (err == hipSuccess) err = lane0_fill(e, g.d_gcount, 0, 8 * nb);
+    if (err == hipSuccess) err = hipHostMalloc((void**)&g.h_gmeta, (sizeof(WzGateTile) + sizeof(WzGateCommit) + 4) * nb, hipHostMallocMapped);
+    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&g.m_gmeta, g.h_gmeta, 0);
+    if (err != hipSuccess) {
+        g.release();
+        return wz_set_error(WZ_EHIP, "gate scratch of a lane: %s", hipGetErrorString(err));
+    }
+    d_gnow = g.d_gnow; d_grows = g.d_grows; d_gcount = g.d_gcount; h_gmeta = g.h_gmeta; m_gmeta = g.m_gmeta;
+    return WZ_OK;
+}
+void GateLane::release() {
+    if (d_gnow) (void)hipFree(d_gnow);
+    if (d_grows) (void)hipFree(d_grows);
+    if (d_gcount) (void)hipFree(d_gcount);
+    if (h_gmeta) (void)hipHostFree(h_gmeta);
+    d_gnow = nullptr; d_grows = nullptr; d_gcount = nullptr; h_gmeta = m_gmeta = nullptr;
+}
+
+void GateCam::release() {
+    if (d_ref) (void)hipFree(d_ref);
+    if (d_rows) (void)hipFree(d_rows);
+    d_ref = nullptr, d_rows = nullptr;
+}
+
+// ---- rectangles
+// Why rectangle t of a w x h frame of format word fmt cannot be cut, or nullptr
+static const char* tile_refusal(const wz_tile_t& t, int w, int h, int fmt) {
+    if (t.w < 1 || t.h < 1 || t.x0 < 0 || t.y0 < 0) return "origin and size must not be negative, the size not zero";
+    if ((int64_t)t.x0 + t.w > w || (int64_t)t.y0 + t.h > h) return "the rectangle leaves the frame";
+    const int base = fmt & WZ_FMT_BASE_MASK;
+    if ((base == WZ_FMT_NV12 || base == WZ_FMT_I420) && ((t.x0 | t.y0 | t.w | t.h) & 1)) return "NV12 / I420 need even x0, y0, w and h";
+    if ((base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422) && ((t.x0 | t.w) & 1)) return "YUYV422 / UYVY422 need even x0 and w";
+    if (!wz_frame_bytes(t.w, t.h, fmt)) return fmt_refusal(t.w, t.h, fmt);
+    return nullptr;
+}
+// ... and whether the engine takes it: tile_refusal plus the engine's size limit, for rectangle `idx` of `what` number `id` ("frame" |
+// "camera" | "frame-table entry"), which is w x h in format word fmt.  WZ_OK, or the code with wz_last_error set.
+static int tile_fits(const wz_engine* e, const char* what, int id, int w, int h, int fmt, int idx, const wz_tile_t& r) {
+    const char* why = tile_refusal(r, w, h, fmt);
+    if (why) return wz_set_error(WZ_EINVAL, "%s %d (%dx%d, format 0x%x), tile %d (%d, %d, %d x %d): %s", what, id, w, h, fmt, idx, r.x0, r.y0, r.w, r.h, why);
+    if (r.w > e->max_w || r.h > e->max_h || (size_t)r.w * r.h * 3 > e->frame_stride)
+        return wz_set_error(WZ_ELIMIT, "%s %d, tile %d is %dx%d, engine was created for at most %dx%d", what, id, idx, r.w, r.h, e->max_w, e->max_h);
+    return WZ_OK;
+}
+
+// The one to three rectangular byte copies that cut rectangle t out of a w x h frame at `src` into a contiguous image at `dst`.
+static void tile_planes(const uint8_t* src, int w, int h, int fmt, const wz_tile_t& t, uint8_t* dst, std::vector<WzCropPlane>& out) {
+    const int base = fmt & WZ_FMT_BASE_MASK;
+    const size_t W = (size_t)w, H = (size_t)h;
+    if (base == WZ_FMT_NV12 || base == WZ_FMT_I420) {
+        out.push_back({src + (size_t)t.y0 * W + t.x0, dst, w, t.w, t.h, 0});
+        const uint8_t* chroma = src + W * H;
+        uint8_t* dc = dst + (size_t)t.w * t.h;
+        if (base == WZ_FMT_NV12) {
+            out.push_back({chroma + (size_t)(t.y0 / 2) * W + t.x0, dc, w, t.w, t.h / 2, 0});
+        } else {
+            const size_t cw = W / 2, ch = H / 2, off = (size_t)(t.y0 / 2) * cw + t.x0 / 2;
+            out.push_back({chroma + off, dc, w / 2, t.w / 2, t.h / 2, 0});
+            out.push_back({chroma + cw * ch + off, dc + (size_t)(t.w / 2) * (t.h / 2), w / 2, t.w / 2, t.h / 2, 0});
+        }
+        return;
+    }
+    const int bpp = (base == WZ_FMT_RGB24 || base == WZ_FMT_BGR24) ? 3 : (base == WZ_FMT_GRAY8 ? 1 : 2);
+    out.push_back({src + ((size_t)t.y0 * W + t.x0) * bpp, dst, w * bpp, t.w * bpp, t.h, 0});
+}
+
+// What the activity kernel reads of rectangle t of a frame w pixels wide at `src`: the luma-bearing bytes of its rows
+static void gate_tile(const uint8_t* src, int w, int fmt, const wz_tile_t& t, WzGateTile& g) {
+    const int base = fmt & WZ_FMT_BASE_MASK;
+    const bool rgb = base == WZ_FMT_RGB24 || base == WZ_FMT_BGR24, yuy = base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422;
+    const int bpp = rgb ? 3 : yuy ? 2 : 1;   // (NV12 / I420: the luma plane is the frame's first w x h bytes)
+    g.src = src + ((size_t)t.y0 * (size_t)w + t.x0) * bpp;
+    g.pitch = w * bpp;
+    g.row_bytes = t.w * bpp;
+    g.tw = t.w;
+    g.th = t.h;
+    g.cols = (t.w + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
+    g.crows = (t.h + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
+    g.mode = base == WZ_FMT_RGB24 ? WZ_GATE_RGB : base == WZ_FMT_BGR24 ? WZ_GATE_BGR : base == WZ_FMT_YUYV422 ? WZ_GATE_YUYV
+             : base == WZ_FMT_UYVY422 ? WZ_GATE_UYVY : WZ_GATE_GRAY;
+}
+
+// ---- a call, its checks, its plan
+// A tiled or gated call.  fmt and (tiled) cam may be null; a tiled call brings n_tiles / tiles, a gated one gets them from its cameras'
+// layouts when it is enqueued; `total`, all its tiles, is what its check leaves.
+struct TileCall {
+    int n;
+    const uint8_t* const* frames;
+    const int *w, *h, *fmt, *cam;
+    const int* n_tiles;
+    const wz_tile_t* const* tiles;
+    double iou, ios;
+    int total;
+    int pf(int i) const { return fmt ? fmt[i] : WZ_FMT_RGB24; }
+};
+
+static int call_refusal(const wz_engine* e, const char* who, int slot, const TileCall& c, bool tiled) {
+    if (!e || !c.frames || !c.w || !c.h || (tiled && (!c.n_tiles || !c.tiles))) return wz_set_error(WZ_EINVAL, "%s: null argument", who);
+    if (slot < 0 || slot >= e->n_lanes) return wz_set_error(WZ_EINVAL, "slot %d out of range [0,%d)", slot, e->n_lanes);
+    if (c.n < 1 || c.n > e->max_batch) return wz_set_error(WZ_ELIMIT, "batch %d exceeds max_batch %d", c.n, e->max_batch);
+    return WZ_OK;
+}
+static int thresholds_refusal(const char* who, const TileCall& c) {
+    if (!(c.iou >= 0.0) || !(c.ios >= 0.0)) return wz_set_error(WZ_EINVAL, "%s: the merge thresholds must be numbers >= 0", who);
+    return WZ_OK;
+}
+
+// Every refusal of a tiled call (include/watsor_hip.h), before anything is enqueued or written.  host: the frames are host frames that
+// go through the lane's staging area, which holds max_width x max_height.
+static int tiled_check(wz_engine* e, const char* who, int slot, TileCall& c, bool host) {
+    WZCHK(call_refusal(e, who, slot, c, true));
+    int64_t sum = 0;
+    for (int i = 0; i < c.n; ++i) {
+        if (c.n_tiles[i] < 1 || c.n_tiles[i] > WZ_MAX_TILES)
+            return wz_set_error(WZ_ELIMIT, "frame %d: %d tiles, a frame takes 1 to %d", i, c.n_tiles[i], WZ_MAX_TILES);
+        sum += c.n_tiles[i];
+    }
+    if (sum > e->max_batch) return wz_set_error(WZ_ELIMIT, "%lld tiles in one call exceed max_batch %d", (long long)sum, e->max_batch);
+    for (int i = 0; i < c.n; ++i) {
+        WZCHK(frame_refusal(e, "frame", i, c.tiles[i] ? c.frames[i] : nullptr, c.w[i], c.h[i], c.pf(i), c.cam ? c.cam[i] : -1,
+                            FC_PTR | FC_FMT | (host ? FC_LIMIT : 0) | FC_CAM_ID | FC_CAM_FILTER));
+        for (int t = 0; t < c.n_tiles[i]; ++t) WZCHK(tile_fits(e, "frame", i, c.w[i], c.h[i], c.pf(i), t, c.tiles[i][t]));
+    }
+    c.total = (int)sum;
+    return thresholds_refusal(who, c);
+}
+
+// Every refusal of a gated call (include/watsor_hip.h), before anything is enqueued, written or decided
+static int gated_check(wz_engine* e, const char* who, int slot, TileCall& c, bool host) {
+    int rc = call_refusal(e, who, slot, c, false);
+    if (rc != WZ_OK) return rc;
+    const int* cam = c.cam;
+    if (!cam) return wz_set_error(WZ_EINVAL, "%s: a gated call needs the frames' camera ids", who);
+    int64_t sum = 0;
+    for (int i = 0; i < c.n; ++i) {
+        const int w = c.w[i], h = c.h[i], pf = c.pf(i);
+        auto refused = [&](unsigned checks) { return (rc = frame_refusal(e, "frame", i, c.frames[i], w, h, pf, cam[i], checks)) != WZ_OK; };
+        if (refused(FC_PTR)) return rc;
+        auto it = cam[i] < 0 ? e->gate_cams.end() : e->gate_cams.find(cam[i]);
+        if (it == e->gate_cams.end()) return wz_set_error(WZ_EINVAL, "frame %d: camera %d has no tiles (wz_set_camera_tiles first)", i, cam[i]);
+        for (int j = 0; j < i; ++j)
+            if (cam[j] == cam[i]) return wz_set_error(WZ_EINVAL, "frames %d and %d are both camera %d's: one frame of a camera per gated call", j, i, cam[i]);
+        const GateCam& g = it->second;
+        if (refused(FC_FMT)) return rc;
+        if (w != g.w || h != g.h || (pf & WZ_FMT_BASE_MASK) != g.base)
+            return wz_set_error(WZ_EINVAL, "frame %d is %dx%d in base format %d but camera %d's tiles were set for %dx%d in base format %d", i, w, h,
+                                pf & WZ_FMT_BASE_MASK, cam[i], g.w, g.h, g.base);
+        if (refused((host ? FC_LIMIT : 0) | FC_CAM_FILTER)) return rc;
+        sum += (int64_t)g.tiles.size();
+    }
+    if (sum > e->max_batch)
+        return wz_set_error(WZ_ELIMIT, "the %lld tiles configured for the cameras of one call exceed max_batch %d", (long long)sum, e->max_batch);
+    c.total = (int)sum;
+    return thresholds_refusal(who, c);
+}
+
+// What a checked call launches: the crop launch's planes and the tiles that run as the batch's frames (in the lane's tile staging area,
+// the k-th of them at k * frame_stride), and -- written into the lane's pinned block -- the merge launch's frames and origins.
+struct TilePlan {
+    std::vector<WzCropPlane> planes;
+    std::vector<const uint8_t*> tptr;
+    std::vector<int> tw, th, tf;
+    std::vector<int> fresh;   // per tile of the call: its index in the batch, -1 where it does not run
+    int most = 0;             // the most tiles any frame has
+};
+// runs: one byte per tile of the call, 0 = the tile does not run (gated calls); null: every tile runs
+static void tile_plan(wz_engine* e, Lane& L, const TileCall& c, const uint8_t* runs, TilePlan& y) {
+    int32_t* origins = reinterpret_cast<int32_t*>(L.tile.h_tmeta + e->max_batch);
+    y.fresh.assign(c.total, -1);
+    y.tptr.reserve(c.total); y.tw.reserve(c.total); y.th.reserve(c.total); y.tf.reserve(c.total);
+    int k = 0;
+    for (int i = 0; i < c.n; ++i) {
+        const int pf = c.pf(i), cam = c.cam ? c.cam[i] : -1;
+        L.tile.h_tmeta[i] = {k, c.n_tiles[i], cam < 0 ? -1 : cam, 0};
+        y.most = std::max(y.most, c.n_tiles[i]);
+        for (int t = 0; t < c.n_tiles[i]; ++t, ++k) {
+            const wz_tile_t& r = c.tiles[i][t];
+            if (!runs || runs[k]) {
+                y.fresh[k] = (int)y.tptr.size();
+                uint8_t* dst = L.tile.d_tiles + e->frame_stride * y.tptr.size();
+                tile_planes(c.frames[i], c.w[i], c.h[i], pf, r, dst, y.planes);
+                y.tptr.push_back(dst); y.tw.push_back(r.w); y.th.push_back(r.h); y.tf.push_back(pf);   // (the colour flags of the frame's format word are its tiles')
+            }
+            origins[2 * k] = r.x0;
+            origins[2 * k + 1] = r.y0;
+        }
+    }
+}
+
+// The plan's tiles as an ordinary batch without cameras: crop, then 100 unfiltered rows per tile, in tile pixel coordinates, in L.h_rows
+static int run_tiles(wz_engine* e, int slot, const TilePlan& y) {
+    Lane& L = e->lanes[slot];
+    wz_launch_crop_tiles(y.planes.data(), (int)y.planes.size(), L.stream);
+    WZCHK(fill_desc(e, slot, (int)y.tptr.size(), y.tptr.data(), y.tw.data(), y.th.data(), y.tf.data(), nullptr));
+    L.rows = e->pre_rows;
+    return run_batch(e, slot, (int)y.tptr.size());
+}
+
+// ... and behind it: the merge of `src` (every tile's rows, in tile order), each frame's camera filter on its merged rows exactly as
+// wz_filter_rows applies it, and the lane's event (run_batch recorded it behind the batch: wz_wait / wz_collect must see the merge)
+static int merge_tail(wz_engine* e, Lane& L, const TileCall& c, int most, const wz_detection_t* src) {
+    TileLane& T = L.tile;
+    const int32_t* m_origins = reinterpret_cast<const int32_t*>(T.m_tmeta + e->max_batch);
+    wz_launch_merge_tiles(T.m_tmeta, m_origins, src, T.d_tcand, c.n, most, c.iou, c.ios, T.m_trows, T.m_tpass, L.stream);
+    for (int i = 0; i < c.n; ++i)
+        if (c.cam && c.cam[i] >= 0 && e->h_cams[c.cam[i]].enabled)
+            wz_launch_filter_rows(e->d_cams, c.cam[i], T.m_trows + (size_t)i * WZ_MAX_DETECTIONS, T.m_tpass + (size_t)i * WZ_MAX_DETECTIONS, L.stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(L.done, L.stream));
+    T.tiled = c.n;
+    return WZ_OK;
+}
+
+// ---- tiled detection: crop launch -> an ordinary batch over the tiles -> merge launch (k_tiles.hip)
+// A checked tiled call on a drained lane, frames in device memory
+static int tiled_enqueue(wz_engine* e, int slot, const TileCall& c) {
+    Lane& L = e->lanes[slot];
+    WZCHK(L.tile.alloc(e));
+    TilePlan y;
+    tile_plan(e, L, c, nullptr, y);
+    WZCHK(run_tiles(e, slot, y));
+    return merge_tail(e, L, c, y.most, L.m_rows);
+}
+
+// ---- gated tiled detection: activity launch -> the host decides which tiles run -> crop + batch of those -> commit + merge (k_gate.hip,
+// DESIGN.md section 16)
+// The host's rule: does tile t of camera g run, given its activity?
+static bool gate_runs(const GateCam& g, int t, int activity) {
+    return !g.has_ref[t] || activity >= g.gate.min_cells || (g.gate.max_age > 0 && g.skipped[t] >= g.gate.max_age);
+}
+
+// A checked gated call on a drained lane, frames in device memory.  Returns once the decision is made; crop, batch, commit, merge and
+// filters are enqueued behind it and the lane's event behind them.
+static int gated_enqueue(wz_engine* e, int slot, const TileCall& call) {
+    Lane& L = e->lanes[slot];
+    GateLane& G = L.gate;
+    WZCHK(L.tile.alloc(e));
+    WZCHK(G.alloc(e));
+    const int n = call.n, total = call.total;
+    std::vector<GateCam*> cams(n);
+    std::vector<int> nt(n);
+    std::vector<const wz_tile_t*> tp(n);
+    for (int i = 0; i < n; ++i) {
+        cams[i] = &e->gate_cams.find(call.cam[i])->second;
+        nt[i] = (int)cams[i]->tiles.size();
+        tp[i] = cams[i]->tiles.data();
+        // another lane's commit launch may still be writing this camera's references and cached rows
+        if (cams[i]->lane >= 0 && cams[i]->lane != slot) HIPCHK(hipEventSynchronize(e->lanes[cams[i]->lane].done));
+    }
+    TileCall c = call;   // ... with the cameras' rectangles
+    c.n_tiles = nt.data();
+    c.tiles = tp.data();
+    // 1. activity of every tile, one launch
+    const size_t lane_cells = gate_cells_of(e->max_w, e->max_h);
+    WzGateCommit* commits = gate_commits(e, G.h_gmeta);
+    int32_t* act = gate_activity(e, G.h_gmeta);
+    int k = 0, crows = 0, cols = 0;
+    for (int i = 0; i < n; ++i) {
+        GateCam& g = *cams[i];
+        for (int t = 0; t < nt[i]; ++t, ++k) {
+            WzGateTile& d = G.h_gmeta[k];
+            gate_tile(c.frames[i], c.w[i], c.pf(i), g.tiles[t], d);
+            d.ref = g.has_ref[t] ? g.d_ref + g.grid_off[t] : nullptr;
+            d.now = G.d_gnow + lane_cells * k;
+            d.thr = g.gate.pixel_thr;
+            crows = std::max(crows, d.crows);
+            cols = std::max(cols, d.cols);
+            act[k] = 0;
+            commits[k] = {g.d_ref + g.grid_off[t], d.now, g.d_rows + (size_t)t * WZ_MAX_DETECTIONS, d.cols * d.crows, -1};   // (fresh: step 2)
+        }
+    }
+    wz_launch_tile_activity(G.m_gmeta, total, crows, cols, G.d_gcount, gate_activity(e, G.m_gmeta), L.stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(L.stream));   // the batch size is a host-side quantity: the decision waits for the counts
+    // 2. the decision; the cameras' state changes only once everything is enqueued
+    std::vector<uint8_t> runs(total);
+    k = 0;
+    for (int i = 0; i < n; ++i)
+        for (int t = 0; t < nt[i]; ++t, ++k) runs[k] = gate_runs(*cams[i], t, act[k]) ? 1 : 0;
+    TilePlan y;
+    tile_plan(e, L, c, runs.data(), y);
+    for (k = 0; k < total; ++k) commits[k].fresh = y.fresh[k];
+    // 3. the tiles that run, as an ordinary batch without cameras (none: no crop, no batch)
+    if (!y.tptr.empty()) {
+        WZCHK(run_tiles(e, slot, y));
+    } else {
+        L.bound_idx.clear();
+        L.n = 0;   // (no tile ran: no status word is this call's)
+    }
+    // 4. commit, merge, filters
+    wz_launch_gate_commit(gate_commits(e, G.m_gmeta), total, L.m_rows, G.d_grows, L.stream);
+    WZCHK(merge_tail(e, L, c, y.most, G.d_grows));
+    // 5. the state the commit launch leaves behind, and what wz_gate_stats reports
+    G.g_ran.assign(n, 0);
+    G.g_act.assign(act, act + total);
+    G.g_tiles = total; G.g_crows = crows; G.g_cols = cols;
+    k = 0;
+    for (int i = 0; i < n; ++i) {
+        GateCam& g = *cams[i];
+        g.lane = slot;
+        for (int t = 0; t < nt[i]; ++t, ++k) {
+            if (runs[k]) {
+                g.has_ref[t] = 1;
+                g.skipped[t] = 0;
+                G.g_ran[i] |= 1ull << t;
+            } else {
+                ++g.skipped[t];
+            }
+        }
+    }
+    return WZ_OK;
+}
+
+// ---- the entry points of both kinds
+static int enqueue(wz_engine* e, int slot, const TileCall& c, bool gated) { return gated ? gated_enqueue(e, slot, c) : tiled_enqueue(e, slot, c); }
+
+// a checked call of frames in device memory, on its lane once the lane's previous batch has fully drained
+static int submit_device(wz_engine* e, int slot, const TileCall& c, bool gated) {
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipEventSynchronize(e->lanes[slot].done));
+    return enqueue(e, slot, c, gated);
+}
+
+// a checked call of host frames on lane 0, start to rows: every frame whole into the lane's staging area, as wz_submit_host_fmt stages it
+// (the tiles are cut from that copy), enqueue, collect, the wall time into ms
+static int detect_staged(wz_engine* e, TileCall& c, bool gated, wz_detection_t* const* out, uint8_t* const* pass, float* ms) {
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(e->device));
+    Lane& L = e->lanes[0];
+    HIPCHK(hipEventSynchronize(L.done));
+    std::vector<const uint8_t*> dptr(c.n);
+    for (int i = 0; i < c.n; ++i) WZCHK(stage_frame(e, L, i, c.frames[i], wz_frame_bytes(c.w[i], c.h[i], c.pf(i)), &dptr[i]));
+    c.frames = dptr.data();
+    WZCHK(enqueue(e, 0, c, gated));
+    const int rc = wz_collect(e, 0, out, pass);
+    if (rc != WZ_OK && rc != WZ_EINCOMPLETE) return rc;
+    const float el = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (ms)
+        for (int i = 0; i < c.n; ++i) ms[i] = el;
+    return rc;   // WZ_OK, or WZ_EINCOMPLETE: the merged rows are written, the rows of a tile that ran in this call may have been short
+}
+
+extern "C" int wz_submit_tiled_device(wz_engine_t* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h,
+                                      const int* fmt, const int* cam, const int* n_tiles, const wz_tile_t* const* tiles,
+                                      double iou_thr, double ios_thr) {
+    TileCall c = {n, d_frames, w, h, fmt, cam, n_tiles, tiles, iou_thr, ios_thr, 0};
+    WZCHK(tiled_check(e, "wz_submit_tiled_device", slot, c, false));
+    return submit_device(e, slot, c, false);
+}
+extern "C" int wz_detect_tiled(wz_engine_t* e, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt,
+                               const int* cam, const int* n_tiles, const wz_tile_t* const* tiles, double iou_thr, double ios_thr,
+                               wz_detection_t* const* out, uint8_t* const* pass, float* ms) {
+    TileCall c = {n, frames, w, h, fmt, cam, n_tiles, tiles, iou_thr, ios_thr, 0};
+    WZCHK(tiled_check(e, "wz_detect_tiled", 0, c, true));
+    return detect_staged(e, c, false, out, pass, ms);
+}
+extern "C" int wz_submit_gated_device(wz_engine_t* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
+                                      const int* cam, double iou_thr, double ios_thr) {
+    TileCall c = {n, d_frames, w, h, fmt, cam, nullptr, nullptr, iou_thr, ios_thr, 0};
+    WZCHK(gated_check(e, "wz_submit_gated_device", slot, c, false));
+    return submit_device(e, slot, c, true);
+}
+extern "C" int wz_detect_gated(wz_engine_t* e, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt, const int* cam,
+                               double iou_thr, double ios_thr, wz_detection_t* const* out, uint8_t* const* pass, float* ms) {
+    TileCall c = {n, frames, w, h, fmt, cam, nullptr, nullptr, iou_thr, ios_thr, 0};
+    WZCHK(gated_check(e, "wz_detect_gated", 0, c, true));
+    return detect_staged(e, c, true, out, pass, ms);
+}
+
+extern "C" int wz_gate_stats(wz_engine_t* e, int slot, int n, uint64_t* ran_mask, int32_t* activity) {
+    if (!e || !ran_mask || slot < 0 || slot >= e->n_lanes) return wz_set_error(WZ_EINVAL, "wz_gate_stats: bad argument");
+    const GateLane& G = e->lanes[slot].gate;
+    if (n < 1 || n != (int)G.g_ran.size())
+        return wz_set_error(WZ_EINVAL, "wz_gate_stats: the last gated call on lane %d had %d frames, not %d", slot, (int)G.g_ran.size(), n);
+    memcpy(ran_mask, G.g_ran.data(), sizeof(uint64_t) * n);
+    if (activity) memcpy(activity, G.g_act.data(), sizeof(int32_t) * G.g_act.size());
+    return WZ_OK;
+}
+
+// ---- a camera's layout and gate
+extern "C" int wz_set_camera_tiles(wz_engine_t* e, int cam, int width, int height, int fmt, int n_tiles, const wz_tile_t* tiles,
+                                   const wz_tile_gate_t* gate) {
+    if (!e || !tiles || !gate) return wz_set_error(WZ_EINVAL, "wz_set_camera_tiles: null argument");
+    if (cam < 0 || cam >= WZ_MAX_CAMS) return wz_set_error(WZ_ELIMIT, "camera id %d out of range [0,%d)", cam, WZ_MAX_CAMS);
+    if (!wz_frame_bytes(width, height, fmt))
+        return wz_set_error(WZ_EINVAL, "camera %d: pixel format 0x%x at %dx%d: %s", cam, fmt, width, height, fmt_refusal(width, height, fmt));
+    if (n_tiles < 1 || n_tiles > WZ_MAX_TILES) return wz_set_error(WZ_ELIMIT, "camera %d: %d tiles, a frame takes 1 to %d", cam, n_tiles, WZ_MAX_TILES);
+    if (n_tiles > e->max_batch) return wz_set_error(WZ_ELIMIT, "camera %d: %d tiles exceed max_batch %d", cam, n_tiles, e->max_batch);
+    if (gate->pixel_thr < 0 || gate->pixel_thr > 255 || gate->min_cells < 1 || gate->max_age < 0)
+        return wz_set_error(WZ_EINVAL, "camera %d: gate (%d, %d, %d): pixel_thr must be 0 .. 255, min_cells >= 1, max_age >= 0", cam, gate->pixel_thr,
+                            gate->min_cells, gate->max_age);
+    GateCam g;
+    g.w = width; g.h = height; g.base = fmt & WZ_FMT_BASE_MASK;
+    g.gate = *gate;
+    g.gate._reserved = 0;
+    size_t cells = 0;
+    for (int t = 0; t < n_tiles; ++t) {
+        const wz_tile_t& r = tiles[t];
+        WZCHK(tile_fits(e, "camera", cam, width, height, fmt, t, r));
+        g.tiles.push_back(r);
+        g.cols.push_back((r.w + WZ_GATE_CELL - 1) / WZ_GATE_CELL);
+        g.crows.push_back((r.h + WZ_GATE_CELL - 1) / WZ_GATE_CELL);
+        g.grid_off.push_back(cells);
+        cells += (gate_cells_of(r.w, r.h) + 7) & ~(size_t)7;   // (every grid begins at a 16-byte boundary)
+    }
+    g.has_ref.assign(n_tiles, 0);
+    g.skipped.assign(n_tiles, 0);
+    HIPCHK(hipSetDevice(e->device));
+    WZCHK(sync_all(e));
+    // the new state is allocated aside: a failure leaves the camera with the layout (and the references) it had
+    hipError_t err = hipMalloc((void**)&g.d_ref, cells * 2);
+    if (err == hipSuccess) err = hipMalloc((void**)&g.d_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS * n_tiles);
+    if (err != hipSuccess) {
+        g.release();
+        return wz_set_error(WZ_EHIP, "wz_set_camera_tiles: %s (camera %d keeps its previous tiles)", hipGetErrorString(err), cam);
+    }
+    auto it = e->gate_cams.find(cam);
+    if (it != e->gate_cams.end()) it->second.release();   // nothing in flight reads the old state: every lane was synchronised above
+    e->gate_cams[cam] = std::move(g);
+    return WZ_OK;
+}
+
+extern "C" int wz_reset_camera_tiles(wz_engine_t* e, int cam) {
+    if (!e) return wz_set_error(WZ_EINVAL, "wz_reset_camera_tiles: null engine");
+    auto it = e->gate_cams.find(cam);
+    if (it == e->gate_cams.end()) return wz_set_error(WZ_EINVAL, "camera %d has no tiles (wz_set_camera_tiles first)", cam);
+    HIPCHK(hipSetDevice(e->device));
+    WZCHK(sync_all(e));
+    std::fill(it->second.has_ref.begin(), it->second.has_ref.end(), (uint8_t)0);
+    std::fill(it->second.skipped.begin(), it->second.skipped.end(), 0);
+    return WZ_OK;
+}
+
+extern "C" int wz_clear_camera_tiles(wz_engine_t* e, int cam) {
+    if (!e || cam < 0 || cam >= WZ_MAX_CAMS) return wz_set_error(WZ_EINVAL, "wz_clear_camera_tiles: bad argument");
+    auto it = e->gate_cams.find(cam);
+    if (it == e->gate_cams.end()) return WZ_OK;
+    HIPCHK(hipSetDevice(e->device));
+    WZCHK(sync_all(e));
+    it->second.release();
+    e->gate_cams.erase(it);
+    return WZ_OK;
+}
+
+// ---- the frame table's tiled entries
+// Entries first .. first + count - 1 get a tiled description (include/watsor_hip.h); checked against every entry as tiled_check checks a
+// call, nothing changes on a refusal.
+extern "C" int wz_bind_tiles(wz_engine_t* e, int first, int count, int n_tiles, const wz_tile_t* tiles, double iou_thr, double ios_thr, int gated) {
+    if (!e) return wz_set_error(WZ_EINVAL, "wz_bind_tiles: null engine");
+    HIPCHK(hipSetDevice(e->device));
+    WZCHK(sync_all(e));   // no batch in flight was planned with the old descriptions
+    const int64_t size = (int64_t)e->bound.size();
+    if (first < 0 || count < 1 || (int64_t)first + count > size)
+        return wz_set_error(WZ_EINVAL, "wz_bind_tiles: entries %d .. %lld lie outside the frame table of %lld entries", first, (long long)first + count - 1,
+                            (long long)size);
+    wz_engine::BoundTiles d;
+    if (gated) {
+        if (tiles || n_tiles != 0)
+            return wz_set_error(WZ_EINVAL, "wz_bind_tiles: a gated description takes its %d rectangles from wz_set_camera_tiles: tiles must be NULL and n_tiles 0", n_tiles);
+        const int c = e->bound[first].cam;
+        for (int i = first; i < first + count; ++i)
+            if (e->bound[i].cam < 0 || e->bound[i].cam != c)
+                return wz_set_error(WZ_EINVAL, "wz_bind_tiles: gated entries %d .. %d must carry one camera id >= 0, entry %d has %d and entry %d has %d", first,
+                                    first + count - 1, first, c, i, e->bound[i].cam);
+        d.kind = wz_engine::BOUND_GATED;
+    } else if (n_tiles == 0 && !tiles) {
+        d.kind = wz_engine::BOUND_PLAIN;
+    } else {
+        const int most = std::min(WZ_MAX_TILES, e->max_batch);
+        if (n_tiles < 1 || n_tiles > most) return wz_set_error(WZ_ELIMIT, "wz_bind_tiles: %d tiles, an entry of this engine takes 1 to %d", n_tiles, most);
+        if (!tiles) return wz_set_error(WZ_EINVAL, "wz_bind_tiles: %d tiles but no rectangles", n_tiles);
+        for (int i = first; i < first + count; ++i)
+            for (int t = 0; t < n_tiles; ++t) {
+                const wz_engine::BoundFrame& f = e->bound[i];
+                WZCHK(tile_fits(e, "frame-table entry", i, f.w, f.h, f.fmt, t, tiles[t]));
+            }
+        d.kind = wz_engine::BOUND_TILED;
+        d.tiles.assign(tiles, tiles + n_tiles);
+    }
+    if (d.kind != wz_engine::BOUND_PLAIN) {
+        if (!(iou_thr >= 0.0) || !(ios_thr >= 0.0)) return wz_set_error(WZ_EINVAL, "wz_bind_tiles: the merge thresholds (%g, %g) must be numbers >= 0", iou_thr, ios_thr);
+        d.iou = iou_thr;
+        d.ios = ios_thr;
+        if (e->bound_tiles.empty()) e->bound_tiles.resize(e->bound.size());
+    }
+    if (e->bound_tiles.empty()) return WZ_OK;   // (untiled entries of a table without descriptions)
+    for (int i = first; i < first + count; ++i) e->bound_tiles[i] = d;
+    bool any = false;
+    for (const auto& b : e->bound_tiles) any = any || b.kind != wz_engine::BOUND_PLAIN;
+    if (!any) e->bound_tiles.clear();
+    return WZ_OK;
+}
+
+// The bytes the crop kernel (and, gated, the activity kernel before it) reads of a frame: what decides between reading a page-locked frame in
+// place and staging it whole.  Break-even by bandwidth is near 0.8 of the frame's bytes (a kernel reads mapped memory at 23 GB/s beside the
+// other lanes' kernels, the copies move 29 GB/s: see stage_frame in wz_engine.hip); one half is the margin read_in_place() uses for the resize kernel.
+// Measured for the crop kernel (profiles/bound_tiles.txt; one 640 x 480 rectangle of a 1080p frame, four lanes busy):
+// RGB24, cost 0.15 of the frame: 5600 frames/s in place against 5565 staged -- level -- and a lone call 0.326 against 0.426 ms; NV12, cost
+// 0.15: 5825 in place against 8247 staged, a lone call 0.318 against 0.374 ms.  So at a cost well under one half, reading in place is
+// SLOWER than staging with every lane busy once the whole frame is small (3.1 MB): both in-place legs sit at ~0.175 ms a step whatever
+// they read.  The constant stays at one half here; moving it (or bounding it by the frame's bytes) needs that plateau explained first.
+static bool tiles_in_place(const wz_engine* e, const wz_engine::BoundFrame& f, const std::vector<wz_tile_t>& tiles, bool gated) {
+    if (!f.dev || e->host_read == 0) return false;
+    if (e->host_read == 1) return true;
+    uint64_t cost = 0;
+    for (const wz_tile_t& t : tiles) cost += wz_frame_bytes(t.w, t.h, f.fmt);
+    if (gated) cost *= 2;   // a gated tile is measured, and read again when it runs
+    return e->host_read == 2 && 2 * cost <= f.bytes;
+}
+
+static const char* bound_kind_name(int kind) { return kind == wz_engine::BOUND_TILED ? "tiled" : kind == wz_engine::BOUND_GATED ? "gated" : "untiled"; }
+
+// wz_submit_bound of a batch with a tiled or gated entry (slot, n and the entries' range are checked): one kind, one pair of thresholds,
+// the refusals of the tiled / gated call, then every frame staged whole or handed over in place, then tiled_enqueue / gated_enqueue.
+int submit_bound_tiles(wz_engine* e, int slot, int n, const int32_t* entries) {
+    const wz_engine::BoundTiles& d0 = e->bound_tiles[entries[0]];
+    for (int i = 1; i < n; ++i) {
+        const wz_engine::BoundTiles& d = e->bound_tiles[entries[i]];
+        if (d.kind != d0.kind)
+            return wz_set_error(WZ_EINVAL, "wz_submit_bound: frame-table entry %d is %s and entry %d is %s: a batch holds one kind", entries[0],
+                                bound_kind_name(d0.kind), entries[i], bound_kind_name(d.kind));
+    }
+    for (int i = 1; i < n; ++i) {
+        const wz_engine::BoundTiles& d = e->bound_tiles[entries[i]];
+        if (d.iou != d0.iou || d.ios != d0.ios)
+            return wz_set_error(WZ_EINVAL, "wz_submit_bound: frame-table entry %d merges with thresholds (%g, %g) and entry %d with (%g, %g): a batch takes one pair",
+                                entries[0], d0.iou, d0.ios, entries[i], d.iou, d.ios);
+    }
+    const bool gated = d0.kind == wz_engine::BOUND_GATED;
+    BoundBatch b;
+    bound_gather(e, n, entries, b);
+    std::vector<int> nt(n);
+    std::vector<const wz_tile_t*> tp(n);
+    for (int i = 0; i < n; ++i) {
+        nt[i] = (int)e->bound_tiles[entries[i]].tiles.size();
+        tp[i] = e->bound_tiles[entries[i]].tiles.data();
+    }
+    TileCall c = {n, b.ptr.data(), b.w, b.h, b.fmt, b.cam, nt.data(), tp.data(), d0.iou, d0.ios, 0};
+    WZCHK(gated ? gated_check(e, "wz_submit_bound", slot, c, true) : tiled_check(e, "wz_submit_bound", slot, c, true));
+    WZCHK(bound_drain(e, slot));
+    Lane& L = e->lanes[slot];
+    std::vector<int32_t> src(n);
+    for (int i = 0; i < n; ++i) {
+        const wz_engine::BoundFrame& f = e->bound[entries[i]];
+        const std::vector<wz_tile_t>& tiles = gated ? e->gate_cams.find(f.cam)->second.tiles : e->bound_tiles[entries[i]].tiles;
+        if (tiles_in_place(e, f, tiles, gated)) {
+            b.ptr[i] = f.dev;
+            src[i] = 1;
+            continue;
+        }
+        WZCHK(stage_frame(e, L, i, f.host, f.bytes, &b.ptr[i]));
+    }
+    WZCHK(enqueue(e, slot, c, gated));
+    L.bound_idx.assign(entries, entries + n);   // (L.tile.tiled == n says that their rows are the merged ones)
+    L.bound_src.swap(src);
+    return WZ_OK;
+}
+
+#ifdef WZ_DEV_BUILD   // ---- everything below this line exists in libwatsor_hip_dev.so only (include/watsor_hip.h, last section)
+// ---- stage-level entry points (parity tests) and profiling
+// One rectangle of one host frame for a kernel of its own: the checks, then a device copy of the frame that starts at the host pointer's
+// offset within 16 bytes, so that what a caller does to the source's alignment reaches the kernel.  *base is what to free.
+static int one_tile_check(int w, int h, int fmt, const wz_tile_t* tile) {
+    if (!wz_frame_bytes(w, h, fmt)) return wz_set_error(WZ_EINVAL, "pixel format 0x%x at %dx%d: %s", fmt, w, h, fmt_refusal(w, h, fmt));
+    const char* why = tile_refusal(*tile, w, h, fmt);
+    if (why) return wz_set_error(WZ_EINVAL, "tile (%d, %d, %d x %d) of a %dx%d frame: %s", tile->x0, tile->y0, tile->w, tile->h, w, h, why);
+    return WZ_OK;
+}
+static hipError_t skewed_copy(const uint8_t* frame, uint64_t bytes, uint8_t** base, const uint8_t** at) {
+    hipError_t err = hipMalloc((void**)base, bytes + 16);
+    if (err != hipSuccess) return err;
+    *at = *base + (reinterpret_cast<uintptr_t>(frame) & 15u);
+    return hipMemcpy(const_cast<uint8_t*>(*at), frame, bytes, hipMemcpyHostToDevice);
+}
+
+// one tile of one host frame through wz_k_crop_tiles
+extern "C" int wz_stage_crop_tile(wz_engine_t* e, const uint8_t* frame, int w, int h, int fmt, const wz_tile_t* tile, uint8_t* out) {
+    if (!e || !frame || !tile || !out) return wz_set_error(WZ_EINVAL, "wz_stage_crop_tile: null argument");
+    WZCHK(one_tile_check(w, h, fmt, tile));
+    const uint64_t bytes = wz_frame_bytes(w, h, fmt), tbytes = wz_frame_bytes(tile->w, tile->h, fmt);
+    if (bytes >> 31) return wz_set_error(WZ_ELIMIT, "frame too large");
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    uint8_t* d_src = nullptr;
+    uint8_t* d_dst = nullptr;
+    const uint8_t* src = nullptr;
+    hipError_t err = skewed_copy(frame, bytes, &d_src, &src);
+    if (err == hipSuccess) err = hipMalloc((void**)&d_dst, tbytes);
+    if (err == hipSuccess) {
+        std::vector<WzCropPlane> planes;
+        tile_planes(src, w, h, fmt, *tile, d_dst, planes);
+        wz_launch_crop_tiles(planes.data(), (int)planes.size(), e->stream);
+        err = hipStreamSynchronize(e->stream);
+    }
+    if (err == hipSuccess) err = hipMemcpy(out, d_dst, tbytes, hipMemcpyDeviceToHost);
+    if (d_src) (void)hipFree(d_src);
+    if (d_dst) (void)hipFree(d_dst);
+    if (err != hipSuccess) return wz_set_error(WZ_EHIP, "wz_stage_crop_tile: %s", hipGetErrorString(err));
+    return WZ_OK;
+}
+
+// wz_k_merge_tiles (+ the camera's filter) on caller-provided tile rows of one w x h frame
+extern "C" int wz_stage_merge_tiles(wz_engine_t* e, int w, int h, int cam, int n_tiles, const wz_tile_t* tiles, const wz_detection_t* tile_rows,
+                                    double iou_thr, double ios_thr, wz_detection_t* rows, uint8_t* pass) {
+    if (!e || !tiles || !tile_rows || !rows || !pass || w < 1 || h < 1) return wz_set_error(WZ_EINVAL, "wz_stage_merge_tiles: bad argument");
+    if (n_tiles < 1 || n_tiles > WZ_MAX_TILES) return wz_set_error(WZ_ELIMIT, "%d tiles, a frame takes 1 to %d", n_tiles, WZ_MAX_TILES);
+    if (cam >= WZ_MAX_CAMS) return wz_set_error(WZ_ELIMIT, "camera id %d >= %d", cam, WZ_MAX_CAMS);
+    if (cam >= 0 && e->h_cams[cam].enabled && (e->h_cams[cam].width != w || e->h_cams[cam].height != h))
+        return wz_set_error(WZ_EINVAL, "the frame is %dx%d but camera %d filter was set for %dx%d", w, h, cam, e->h_cams[cam].width, e->h_cams[cam].height);
+    for (int t = 0; t < n_tiles; ++t)
+        if (tiles[t].w < 1 || tiles[t].h < 1 || tiles[t].x0 < 0 || tiles[t].y0 < 0 || (int64_t)tiles[t].x0 + tiles[t].w > w || (int64_t)tiles[t].y0 + tiles[t].h > h)
+            return wz_set_error(WZ_EINVAL, "tile %d (%d, %d, %d x %d) is no rectangle of a %dx%d frame", t, tiles[t].x0, tiles[t].y0, tiles[t].w, tiles[t].h, w, h);
+    if (!(iou_thr >= 0.0) || !(ios_thr >= 0.0)) return wz_set_error(WZ_EINVAL, "wz_stage_merge_tiles: the merge thresholds must be numbers >= 0");
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const size_t nr = (size_t)n_tiles * WZ_MAX_DETECTIONS;
+    const size_t off_meta = sizeof(wz_detection_t) * nr, off_org = off_meta + sizeof(WzMergeFrame), off_cand = off_org + 8 * (size_t)n_tiles,
+                 off_rows = off_cand + sizeof(WzMergeCand) * nr, off_pass = off_rows + sizeof(wz_detection_t) * WZ_MAX_DETECTIONS,
+                 all = off_pass + WZ_MAX_DETECTIONS;   // (every block's size is a multiple of 8: the offsets stay aligned)
+    uint8_t* d = nullptr;
+    HIPCHK(hipMalloc((void**)&d, all));
+    const WzMergeFrame fr = {0, n_tiles, cam < 0 ? -1 : cam, 0};
+    std::vector<int32_t> org(2 * (size_t)n_tiles);
+    for (int t = 0; t < n_tiles; ++t) org[2 * t] = tiles[t].x0, org[2 * t + 1] = tiles[t].y0;
+    hipError_t err = hipMemcpy(d, tile_rows, off_meta, hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(d + off_meta, &fr, sizeof(fr), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(d + off_org, org.data(), org.size() * 4, hipMemcpyHostToDevice);
+    if (err == hipSuccess) {
+        wz_detection_t* d_rows = reinterpret_cast<wz_detection_t*>(d + off_rows);
+        wz_launch_merge_tiles(reinterpret_cast<const WzMergeFrame*>(d + off_meta), reinterpret_cast<const int32_t*>(d + off_org),
+                              reinterpret_cast<const wz_detection_t*>(d), reinterpret_cast<WzMergeCand*>(d + off_cand), 1, n_tiles, iou_thr,
+                              ios_thr, d_rows, d + off_pass, e->stream);
+        if (cam >= 0 && e->h_cams[cam].enabled) wz_launch_filter_rows(e->d_cams, cam, d_rows, d + off_pass, e->stream);
+        err = hipStreamSynchronize(e->stream);
+    }
+    if (err == hipSuccess) err = hipMemcpy(rows, d + off_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS, hipMemcpyDeviceToHost);
+    if (err == hipSuccess) err = hipMemcpy(pass, d + off_pass, WZ_MAX_DETECTIONS, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (err != hipSuccess) return wz_set_error(WZ_EHIP, "wz_stage_merge_tiles: %s", hipGetErrorString(err));
+    return WZ_OK;
+}
+
+// wz_k_tile_activity on one rectangle of one host frame
+extern "C" int wz_stage_tile_activity(wz_engine_t* e, const uint8_t* frame, int w, int h, int fmt, const wz_tile_t* tile, const uint16_t* ref,
+                                      int pixel_thr, uint16_t* sums_out, int32_t* changed_out) {
+    if (!e || !frame || !tile || !sums_out || !changed_out) return wz_set_error(WZ_EINVAL, "wz_stage_tile_activity: null argument");
+    WZCHK(one_tile_check(w, h, fmt, tile));
+    const uint64_t bytes = wz_frame_bytes(w, h, fmt);
+    if (pixel_thr < 0 || pixel_thr > 255) return wz_set_error(WZ_EINVAL, "pixel_thr %d, expected 0 .. 255", pixel_thr);
+    if (bytes >> 31) return wz_set_error(WZ_ELIMIT, "frame too large");
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const size_t cells = gate_cells_of(tile->w, tile->h);
+    const size_t off_ref = (cells * 2 + 15) & ~(size_t)15, off_desc = 2 * off_ref, off_cnt = off_desc + 64, all = off_cnt + 16;
+    uint8_t* d_src = nullptr;
+    const uint8_t* src = nullptr;
+    uint8_t* d = nullptr;   // new grid, reference grid, the tile's descriptor, the counters and the count
+    hipError_t err = skewed_copy(frame, bytes, &d_src, &src);
+    if (err == hipSuccess) err = hipMalloc((void**)&d, all);
+    if (err == hipSuccess) err = hipMemset(d, 0, all);
+    if (err == hipSuccess && ref) err = hipMemcpy(d + off_ref, ref, cells * 2, hipMemcpyHostToDevice);
+    if (err == hipSuccess) {
+        static_assert(sizeof(WzGateTile) <= 64, "the descriptor's slot");
+        WzGateTile g;
+        gate_tile(src, w, fmt, *tile, g);
+        g.ref = ref ? reinterpret_cast<const uint16_t*>(d + off_ref) : nullptr;
+        g.now = reinterpret_cast<uint16_t*>(d);
+        g.thr = pixel_thr;
+        err = hipMemcpy(d + off_desc, &g, sizeof(g), hipMemcpyHostToDevice);
+        if (err == hipSuccess) {
+            int32_t* cnt = reinterpret_cast<int32_t*>(d + off_cnt);
+            wz_launch_tile_activity(reinterpret_cast<const WzGateTile*>(d + off_desc), 1, g.crows, g.cols, cnt, cnt + 2, e->stream);
+            err = hipStreamSynchronize(e->stream);
+        }
+    }
+    if (err == hipSuccess) err = hipMemcpy(sums_out, d, cells * 2, hipMemcpyDeviceToHost);
+    if (err == hipSuccess) err = hipMemcpy(changed_out, d + off_cnt + 8, 4, hipMemcpyDeviceToHost);
+    if (d_src) (void)hipFree(d_src);
+    if (d) (void)hipFree(d);
+    if (err != hipSuccess) return wz_set_error(WZ_EHIP, "wz_stage_tile_activity: %s", hipGetErrorString(err));
+    return WZ_OK;
+}
+
+extern "C" int wz_debug_bound_source(wz_engine_t* e, int slot, int32_t* in_place) {
+    if (!e || !in_place || slot < 0 || slot >= e->n_lanes) return wz_set_error(WZ_EINVAL, "wz_debug_bound_source: bad argument");
+    const Lane& L = e->lanes[slot];
+    if (L.bound_src.empty()) return wz_set_error(WZ_EINVAL, "wz_debug_bound_source: lane %d has seen no tiled or gated bound batch", slot);
+    memcpy(in_place, L.bound_src.data(), sizeof(int32_t) * L.bound_src.size());
+    return WZ_OK;
+}
+
+// The mean HIP-event time of `reps` brackets around launch() on stream s, in milliseconds, after three unmeasured ones
+template <class F>
+static int bracket_ms(hipStream_t s, int reps, F launch, float* mean) {
+    hipEvent_t a, b;
+    HIPCHK(hipEventCreate(&a));
+    HIPCHK(hipEventCreate(&b));
+    double sum = 0.0;
+    for (int r = 0; r < reps + 3; ++r) {
+        HIPCHK(hipEventRecord(a, s));
+        launch();
+        HIPCHK(hipEventRecord(b, s));
+        HIPCHK(hipEventSynchronize(b));
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, a, b));
+        if (r >= 3) sum += ms;
+    }
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+    *mean = (float)(sum / reps);
+    return WZ_OK;
+}
+
+// HIP-event time of the crop launch alone and of the merge launch alone (no filter launch), on lane 0 behind one whole tiled call of the
+// same arguments (so that the merge reads real tile rows): the mean of `reps` brackets each, in milliseconds; empty_ms: the same bracket around nothing
+extern "C" int wz_profile_tiled(wz_engine_t* e, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
+                                const int* n_tiles, const wz_tile_t* const* tiles, double iou_thr, double ios_thr, int reps,
+                                float* crop_ms, float* merge_ms, float* empty_ms) {
+    if (reps < 1 || !crop_ms || !merge_ms || !empty_ms) return wz_set_error(WZ_EINVAL, "wz_profile_tiled: bad argument");
+    WZCHK(wz_submit_tiled_device(e, 0, n, d_frames, w, h, fmt, nullptr, n_tiles, tiles, iou_thr, ios_thr));
+    WZCHK(wz_wait(e, 0));
+    Lane& L = e->lanes[0];
+    TileCall c = {n, d_frames, w, h, fmt, nullptr, n_tiles, tiles, iou_thr, ios_thr, 0};
+    for (int i = 0; i < n; ++i) c.total += n_tiles[i];
+    TilePlan y;
+    tile_plan(e, L, c, nullptr, y);
+    const TileLane& T = L.tile;
+    const int32_t* m_origins = reinterpret_cast<const int32_t*>(T.m_tmeta + e->max_batch);
+    WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_crop_tiles(y.planes.data(), (int)y.planes.size(), L.stream); }, crop_ms));
+    WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_merge_tiles(T.m_tmeta, m_origins, L.m_rows, T.d_tcand, n, y.most, iou_thr, ios_thr, T.m_trows, T.m_tpass, L.stream); },
+                     merge_ms));
+    return bracket_ms(L.stream, reps, [] {}, empty_ms);   // (two event records with nothing between them: the bracket's own cost)
+}
+
+// HIP-event time of the activity launch alone and of the commit launch alone, exactly as one gated call of these arguments on lane 0 issued
+// them (their descriptors are still in the lane's block; both launches leave what they wrote the first time): the mean of `reps` brackets
+extern "C" int wz_profile_gated(wz_engine_t* e, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt, const int* cam,
+                                double iou_thr, double ios_thr, int reps, float* activity_ms, float* commit_ms, float* empty_ms) {
+    if (reps < 1 || !activity_ms || !commit_ms || !empty_ms) return wz_set_error(WZ_EINVAL, "wz_profile_gated: bad argument");
+    WZCHK(wz_submit_gated_device(e, 0, n, d_frames, w, h, fmt, cam, iou_thr, ios_thr));
+    WZCHK(wz_wait(e, 0));
+    Lane& L = e->lanes[0];
+    const GateLane& G = L.gate;
+    WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_tile_activity(G.m_gmeta, G.g_tiles, G.g_crows, G.g_cols, G.d_gcount, gate_activity(e, G.m_gmeta), L.stream); },
+                     activity_ms));
+    WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_gate_commit(gate_commits(e, G.m_gmeta), G.g_tiles, L.m_rows, G.d_grows, L.stream); }, commit_ms));
+    return bracket_ms(L.stream, reps, [] {}, empty_ms);
+}
+#endif   // WZ_DEV_BUILD

@@ -213,12 +213,19 @@ class HipEngine:
         """frames: (H,W,3) uint8 C-contiguous arrays (host) -- or, with `formats[i]` = FMT_NV12 / FMT_I420, (H*3/2, W) planar
         views, or any other format word `frame_geometry` describes; out_rows[i]: ctypes Detection[100] (or a ROW_DTYPE array of 100) written in place.  Returns the batch wall
         time in ms."""
+        n, (ptrs, ws, hs, outs, keep) = len(frames), self._host_frames(frames, formats, out_rows)
+        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
+        camv = (C.c_int32 * n)(*[int(c) for c in cams]) if cams is not None else None
+        passv = (C.c_void_p * n)(*[p.ctypes.data for p in out_pass]) if out_pass is not None else None
+        ms = (C.c_float * n)()
+        self._ck(self._lib.wz_detect_batch_fmt(self._h, n, ptrs, ws, hs, fmtv, camv, outs, passv, ms))
+        return float(ms[0])
+
+    def _host_frames(self, frames, formats, out_rows):
+        """(pointers, widths, heights, addresses of the rows, what keeps the frames alive) of host frames a synchronous call hands over:
+        a frame that is not C-contiguous goes as a copy."""
         n = len(frames)
-        ptrs = (C.c_void_p * n)()
-        ws = (C.c_int32 * n)()
-        hs = (C.c_int32 * n)()
-        outs = (C.c_void_p * n)()
-        keep = []
+        ptrs, ws, hs, outs, keep = (C.c_void_p * n)(), (C.c_int32 * n)(), (C.c_int32 * n)(), (C.c_void_p * n)(), []
         for i, f in enumerate(frames):
             try:
                 ws[i], hs[i] = self.frame_geometry(f, formats[i] if formats is not None else FMT_RGB24)
@@ -229,35 +236,32 @@ class HipEngine:
             keep.append(f)
             ptrs[i] = f.ctypes.data
             outs[i] = self._addr(out_rows[i])
-        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
-        camv = None
-        if cams is not None:
-            camv = (C.c_int32 * n)(*[int(c) for c in cams])
-        passv = None
-        if out_pass is not None:
-            passv = (C.c_void_p * n)(*[p.ctypes.data for p in out_pass])
-        ms = (C.c_float * n)()
-        self._ck(self._lib.wz_detect_batch_fmt(self._h, n, ptrs, ws, hs, fmtv, camv, outs, passv, ms))
-        return float(ms[0])
+        return ptrs, ws, hs, outs, keep
+
+    @staticmethod
+    def _tile_array(rects, where=None):
+        """[(x0, y0, w, h), ...] as a `wz_tile_t` array (of one element at least).  where: what the ValueError for a rectangle that is not
+        four numbers says in front of its number (None: not checked here)."""
+        arr = (Tile * max(1, len(rects)))()
+        for k, r in enumerate(rects):
+            if where is not None and len(r) != 4:
+                raise ValueError("%stile %d: expected (x0, y0, w, h)" % (where, k))
+            arr[k] = Tile(*[int(v) for v in r])
+        return arr
+
+    def _thresholds(self, iou, ios):
+        """The merge thresholds of a call: None = the engine's own NMS threshold / 1.0 (off)."""
+        return float(self.nms_iou if iou is None else iou), float(1.0 if ios is None else ios)
 
     # -- tiled detection (include/watsor_hip.h: wz_detect_tiled) ------------------------------------
     def _tile_args(self, tiles, n: int, iou, ios):
         """(n_tiles, pointers to the frames' wz_tile_t arrays, what keeps them alive, iou, ios) of a tiled call."""
         if len(tiles) != n:
             raise ValueError("tiles: one list of rectangles per frame (%d frames, %d lists)" % (n, len(tiles)))
-        counts = (C.c_int32 * n)()
-        ptrs = (C.c_void_p * n)()
-        keep = []
-        for i, rects in enumerate(tiles):
-            arr = (Tile * max(1, len(rects)))()
-            for k, r in enumerate(rects):
-                if len(r) != 4:
-                    raise ValueError("frame %d, tile %d: expected (x0, y0, w, h)" % (i, k))
-                arr[k] = Tile(*[int(v) for v in r])
-            keep.append(arr)
-            counts[i] = len(rects)
-            ptrs[i] = C.addressof(arr)
-        return counts, ptrs, keep, float(self.nms_iou if iou is None else iou), float(1.0 if ios is None else ios)
+        keep = [self._tile_array(rects, "frame %d, " % i) for i, rects in enumerate(tiles)]
+        counts = (C.c_int32 * n)(*[len(rects) for rects in tiles])
+        ptrs = (C.c_void_p * n)(*[C.addressof(arr) for arr in keep])
+        return (counts, ptrs, keep) + self._thresholds(iou, ios)
 
     def detect_tiled(self, frames: Sequence[np.ndarray], tiles: Sequence, out_rows: Sequence, cams: Optional[Sequence[int]] = None,
                      passes: Optional[Sequence[np.ndarray]] = None, formats: Optional[Sequence[int]] = None,
@@ -266,22 +270,7 @@ class HipEngine:
         call at most max_batch; out_rows[i] receives ONE merged list of 100 rows in frame coordinates.  iou / ios: a row is dropped when
         a more confident row of the same label overlaps it by more than `iou` (intersection over union; None: the engine's own NMS
         threshold) or by more than `ios` of the smaller box (None: 1.0 = off).  Returns the wall time in ms."""
-        n = len(frames)
-        ptrs = (C.c_void_p * n)()
-        ws = (C.c_int32 * n)()
-        hs = (C.c_int32 * n)()
-        outs = (C.c_void_p * n)()
-        keep = []
-        for i, f in enumerate(frames):
-            try:
-                ws[i], hs[i] = self.frame_geometry(f, formats[i] if formats is not None else FMT_RGB24)
-            except ValueError as exc:
-                raise ValueError("frame %d: %s" % (i, exc)) from None
-            if not f.flags["C_CONTIGUOUS"]:
-                f = np.ascontiguousarray(f)
-            keep.append(f)
-            ptrs[i] = f.ctypes.data
-            outs[i] = self._addr(out_rows[i])
+        n, (ptrs, ws, hs, outs, keep) = len(frames), self._host_frames(frames, formats, out_rows)
         counts, tptrs, tkeep, iou, ios = self._tile_args(tiles, n, iou, ios)
         fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
         camv = (C.c_int32 * n)(*[int(c) for c in cams]) if cams is not None else None
@@ -309,9 +298,9 @@ class HipEngine:
         changed when its luma sum moved by more than `threshold` (0 .. 255) per pixel, a tile runs when at least `min_cells` cells
         changed, when it has no reference yet, or -- max_age > 0 -- after `max_age` gated calls in a row that skipped it.  Waits for
         every lane; the camera starts without references (its next gated call runs every tile)."""
-        arr = (Tile * max(1, len(tiles)))(*[Tile(*[int(v) for v in r]) for r in tiles])
         gate = (C.c_int32 * 4)(int(threshold), int(min_cells), int(max_age), 0)
-        self._ck(self._lib.wz_set_camera_tiles(self._h, int(cam), int(width), int(height), int(fmt), len(tiles), C.byref(arr), C.byref(gate)))
+        self._ck(self._lib.wz_set_camera_tiles(self._h, int(cam), int(width), int(height), int(fmt), len(tiles), C.byref(self._tile_array(tiles)),
+                                               C.byref(gate)))
         self._gate_tiles[int(cam)] = len(tiles)
 
     def reset_camera_tiles(self, cam: int) -> None:
@@ -328,28 +317,12 @@ class HipEngine:
         """`detect_tiled` with the tiles `set_camera_tiles` gave the frames' cameras, run only where the picture changed: a tile that
         did not drift from the picture it last ran on contributes the rows it produced then.  One frame per camera and call; the
         cameras' configured tiles together at most max_batch.  Returns the wall time in ms; `gate_stats()` tells which tiles ran."""
-        n = len(frames)
-        ptrs = (C.c_void_p * n)()
-        ws = (C.c_int32 * n)()
-        hs = (C.c_int32 * n)()
-        outs = (C.c_void_p * n)()
-        keep = []
-        for i, f in enumerate(frames):
-            try:
-                ws[i], hs[i] = self.frame_geometry(f, formats[i] if formats is not None else FMT_RGB24)
-            except ValueError as exc:
-                raise ValueError("frame %d: %s" % (i, exc)) from None
-            if not f.flags["C_CONTIGUOUS"]:
-                f = np.ascontiguousarray(f)
-            keep.append(f)
-            ptrs[i] = f.ctypes.data
-            outs[i] = self._addr(out_rows[i])
+        n, (ptrs, ws, hs, outs, keep) = len(frames), self._host_frames(frames, formats, out_rows)
         fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
         camv = (C.c_int32 * n)(*[int(c) for c in cams])
         passv = (C.c_void_p * n)(*[p.ctypes.data for p in passes]) if passes is not None else None
         ms = (C.c_float * n)()
-        self._ck(self._lib.wz_detect_gated(self._h, n, ptrs, ws, hs, fmtv, camv, float(self.nms_iou if iou is None else iou),
-                                           float(1.0 if ios is None else ios), outs, passv, ms))
+        self._ck(self._lib.wz_detect_gated(self._h, n, ptrs, ws, hs, fmtv, camv, *self._thresholds(iou, ios), outs, passv, ms))
         self._gate_last[0] = [int(c) for c in cams]
         return float(ms[0])
 
@@ -360,8 +333,7 @@ class HipEngine:
         n = len(d_frames)
         fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
         self._ck(self._lib.wz_submit_gated_device(self._h, slot, n, (C.c_void_p * n)(*d_frames), (C.c_int32 * n)(*widths), (C.c_int32 * n)(*heights),
-                                                  fmtv, (C.c_int32 * n)(*[int(c) for c in cams]), float(self.nms_iou if iou is None else iou),
-                                                  float(1.0 if ios is None else ios)))
+                                                  fmtv, (C.c_int32 * n)(*[int(c) for c in cams]), *self._thresholds(iou, ios)))
         self._gate_last[slot] = [int(c) for c in cams]
 
     def gate_stats(self, slot: int = 0):
@@ -441,15 +413,8 @@ class HipEngine:
         `set_camera_tiles` gave the entries' camera, looked up at every submit.  rects=None without `gated`: untiled again.  iou / ios as in
         `detect_tiled` (None: the engine's own NMS threshold / 1.0).  Waits for every lane."""
         n = 0 if rects is None else len(rects)
-        arr = None
-        if rects is not None:
-            arr = (Tile * max(1, n))()
-            for k, r in enumerate(rects):
-                if len(r) != 4:
-                    raise ValueError("tile %d: expected (x0, y0, w, h)" % k)
-                arr[k] = Tile(*[int(v) for v in r])
-        self._ck(self._lib.wz_bind_tiles(self._h, int(first), int(count), n, C.byref(arr) if arr is not None else None,
-                                         float(self.nms_iou if iou is None else iou), float(1.0 if ios is None else ios), 1 if gated else 0))
+        arr = C.byref(self._tile_array(rects, "")) if rects is not None else None
+        self._ck(self._lib.wz_bind_tiles(self._h, int(first), int(count), n, arr, *self._thresholds(iou, ios), 1 if gated else 0))
         for i in range(int(first), int(first) + int(count)):
             if gated:
                 self._bound_tiled[i] = self._bound_cams[i]
@@ -706,8 +671,8 @@ class HipEngine:
         fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
         act, commit, empty = C.c_float(), C.c_float(), C.c_float()
         self._ck(self._lib.wz_profile_gated(self._h, n, (C.c_void_p * n)(*d_frames), (C.c_int32 * n)(*widths), (C.c_int32 * n)(*heights), fmtv,
-                                            (C.c_int32 * n)(*[int(c) for c in cams]), float(self.nms_iou if iou is None else iou),
-                                            float(1.0 if ios is None else ios), int(reps), C.byref(act), C.byref(commit), C.byref(empty)))
+                                            (C.c_int32 * n)(*[int(c) for c in cams]), *self._thresholds(iou, ios), int(reps), C.byref(act),
+                                            C.byref(commit), C.byref(empty)))
         self._gate_last[0] = [int(c) for c in cams]
         return float(act.value), float(commit.value), float(empty.value)
 
@@ -716,7 +681,7 @@ class HipEngine:
         (rows ROW_DTYPE [100], pass uint8 [100])."""
         self._dev_only("stage_merge_tiles()")
         n = len(tiles)
-        arr = (Tile * max(1, n))(*[Tile(*[int(v) for v in r]) for r in tiles])
+        arr = self._tile_array(tiles)
         src = np.ascontiguousarray(tile_rows, ROW_DTYPE).reshape(n, MAX_DETECTIONS)
         rows = np.zeros(MAX_DETECTIONS, ROW_DTYPE)
         ok = np.zeros(MAX_DETECTIONS, np.uint8)
