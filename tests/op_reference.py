@@ -24,6 +24,10 @@ fmaf): emulated in float32 and compared value for value (a signed zero is the on
 
 Weights come from the model variables through engine.fold_batch_norm and are rounded as the packer rounds them, so a wrong weight
 layout in the engine image shows up as a wrong tensor.
+
+A fused inverted-residual block (OP_MBCONV) is one op with three stages and two roundings that never reach HBM (the chunk buffer, the
+depthwise output): `block_reference` chains the three float64 stages on the halves the engine stored and carries a worst-case radius and
+a sum of squared radii through them (its docstring has the derivation); `pair_checks` holds what needs no tolerance.
 """
 from __future__ import annotations
 
@@ -44,8 +48,8 @@ U = 2.0 ** -24
 # ---------------------------------------------------------------------------------------------------------------------------------
 def ulp16(x):
     """Spacing of fp16 numbers at |x| (2^-24 in the subnormal range)."""
-    x = np.abs(np.asarray(x, np.float64))
-    return 2.0 ** (np.floor(np.log2(np.maximum(x, 2.0 ** -14))) - 10)
+    _, e = np.frexp(np.maximum(np.abs(np.asarray(x, np.float64)), 2.0 ** -14))     # x = m 2^e, m in [0.5, 1): floor(log2 x) = e - 1
+    return np.ldexp(1.0, e - 11)
 
 
 def e_acc(T, r):
@@ -219,6 +223,224 @@ def reference(op: "arch.Op", weights: Dict[str, np.ndarray], src: np.ndarray, re
     raise AssertionError("no reference for op kind %d (%s)" % (op.kind, op.scope))
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# one fused inverted-residual block (OP_MBCONV)
+# ---------------------------------------------------------------------------------------------------------------------------------
+FORM_FP16, FORM_UNORM16, FORM_FLOAT = "fp16", "unorm16", "float16bit"
+FLOAT_FORM_UPTO = 9          # engine.build_engine's default float_form_upto: the robust program's blocks 0 .. 9
+
+
+def chunk_form(op: "arch.Op", float_form_upto: int = -1) -> str:
+    """How the block keeps its expanded tensor in LDS: fp16 (plain blocks), unorm16 of z = relu6(v) / 6, or the 16-bit float form."""
+    if not op.hp:
+        return FORM_FP16
+    return FORM_FLOAT if op.block <= float_form_upto else FORM_UNORM16
+
+
+def float_form_step(z):
+    """Spacing of the 16-bit float form of k_hp_ops.h at z in [0, 1]: the code is bits 10 .. 25 of the fp32 pattern of t = z T,
+    T = 2^-120 (2 - 2^-13) -- 13 mantissa bits in the normal binades (t >= 2^-126: a relative step of 2^-13, z >= 2^-7), the fp32
+    subnormal spacing 2^-149 * 2^10 below (2^-20 of full scale)."""
+    t = np.clip(np.asarray(z, np.float64), 0.0, 1.0) * engine.FLOAT_FORM_T
+    _, e = np.frexp(np.maximum(t, 2.0 ** -126))
+    return np.ldexp(1.0 / engine.FLOAT_FORM_T, e - 14)
+
+
+def pair_store_radius(v):
+    """hi = RN16(v), lo = RN16(v - hi) (v - hi is exact in fp32): hi + lo misses v by at most half an ulp16 of the remainder, which is
+    itself at most half an ulp16 of v."""
+    return 0.5 * ulp16(0.5 * ulp16(v))
+
+
+@dataclass
+class BlockResult:
+    ref: np.ndarray                       # [n, hout, wout, cout] float64: the block's output
+    tol: np.ndarray
+    acc: np.ndarray                       # the part of tol that is not the final store (min(8 sqrt V, W) + the lo-half term)
+    store: str                            # "pair", "fp16" or "dup"
+    ref2: Optional[np.ndarray] = None     # dst2: the expanded tensor [n, hin, win, cmid] as plain fp16
+    tol2: Optional[np.ndarray] = None
+    acc2: Optional[np.ndarray] = None
+
+
+def _mm(x, w):
+    return np.asarray(x, np.float64) @ np.asarray(w, np.float64)
+
+
+def _dw(x, w, stride, pad_t, pad_l):
+    """depthwise 3x3 of [n,h,w,c] with taps w [3,3,c], zeros outside the frame."""
+    return conv64(x, w[..., None], stride, pad_t, pad_l, depthwise=True)
+
+
+def block_weights(op: "arch.Op", weights: Dict[str, np.ndarray], form: str):
+    """The three stages' weights as engine.build_engine packs them, float64.  -> dict:
+    e_hi, e_lo [k,k,cin,cmid] and e_b (None without an expand stage; split-operand blocks: of w / 6, b / 6), d_w [3,3,cmid] in the units
+    of the chunk buffer's VALUE (z for the 16-bit codes, v for fp16), d_b, p_hi, p_lo [cmid,cout], p_b."""
+    parts = list(op.parts)
+    out = dict(e_hi=None, e_lo=None, e_b=None)
+    if op.stem or op.cin0:
+        ex = parts.pop(0)
+        w, b = engine.fold_batch_norm(weights, ex)
+        if op.hp:                                               # 1 / 6 folded in, then split; the bias as fp32
+            out["e_hi"], out["e_lo"] = engine.split_halves(w / 6.0)
+            out["e_b"] = _f32(b / 6.0)
+        else:
+            out["e_hi"], out["e_lo"], out["e_b"] = _f16_via_f32(w), np.zeros_like(w), _f32(b)
+    dw, pj = parts
+    wd, bd = engine.fold_batch_norm(weights, dw)
+    wd = wd[..., 0]
+    if form == FORM_FP16:
+        out["d_w"] = _f16(wd)
+    elif form == FORM_UNORM16:                                  # the kernel multiplies the CODE (0 .. 65535) by fp32(w * 6 / 65535)
+        out["d_w"] = _f32(wd / engine.UNORM16_PER_6) * 65535.0
+    else:                                                       # ... the decoded t = z T by fp32(w * 6 * 2^60 / (2 - 2^-13)), the sum by 2^60
+        out["d_w"] = _f32(wd * engine.FLOAT_FORM_TAP_SCALE) * (engine.FLOAT_FORM_T * 2.0 ** 60)
+    out["d_b"] = _f32(bd)
+    w, b = engine.fold_batch_norm(weights, pj)
+    w = w[0, 0]
+    if op.hp:
+        out["p_hi"], out["p_lo"] = engine.split_halves(w)
+    else:
+        out["p_hi"], out["p_lo"] = _f16_via_f32(w), np.zeros_like(w)
+    out["p_b"] = _f32(b)
+    return out
+
+
+def block_reference(op: "arch.Op", weights: Dict[str, np.ndarray], src_hi, src_lo=None, res_hi=None, res_lo=None,
+                    form: Optional[str] = None, store: str = "fp16") -> BlockResult:
+    """The float64 reference of one fused block and its element-by-element tolerance.
+
+    Inputs as the engine stored them: the source (and residual) as their two fp16 halves (lo None: a plain tensor), summed in float64.
+    Weights from the model variables, rounded / split / scaled as engine.build_engine does (block_weights).  The contract (k_mbconv*.hip):
+      expand    z = clamp(sum + b, 0, top); split-operand blocks: the sum is Whi.xhi + Whi.xlo + Wlo.xhi in exact arithmetic (Wlo.xlo is
+                dropped by design), W and b carry the 1 / 6, top = 1; plain blocks: fp16 operands, top = 6.  The stem block's expand stage
+                is the 3x3 stride-2 stem conv on the input.  Halo pixels outside the frame are exact zeros (TF pads the depthwise INPUT).
+      buffer    z is kept as fp16, as unorm16 (step 1 / 65535) or in the 16-bit float form (float_form_step)
+      depthwise y = relu6(b + sum over the in-frame taps), fp32 taps; kept as hi + lo (split blocks) or one fp16
+      project   sum over the expanded channels (three products again), + b, + residual (its halves added in fp32); stored as a pair,
+                one fp16, or [hi | hi] (`store`: "pair", "fp16", "dup")
+    The bound carries two radii through the stages: W, the worst case, and V, the sum of the squared radii of independent roundings.
+    An fp32 accumulation of r roundings over terms of absolute sum T adds r u T to W and r (u T)^2 to V (8 sqrt(V) is then the file's
+    8 sqrt(r) u T); r counts three products per term for split operands, one per term otherwise (fp16 x fp16 is exact; the depthwise
+    taps are fused multiply-adds), + 2 for bias and the last rounding, + 1 for the multiplication by T (float form) / by 2^60 (its tap
+    sum), + 2 for a residual (its halves' sum, then the add).  A storage step adds its radius h -- taken at |ref| + W so far -- to W and
+    h^2 to V: half a step for fp16, hi + lo and the float form (wz_hp_fenc4 adds half of the kept ulp to the pattern and truncates:
+    round to nearest by construction), a WHOLE step for unorm16: the codes come from v_cvt_pknorm_u16_f32, and nothing this project can
+    cite promises that the instruction rounds to nearest (a truncating conversion is off by up to a step).  A linear stage maps W -> sum |w| W, V -> sum w^2 V;
+    the clamp and ReLU6 are 1-Lipschitz.  At the end
+        tol = min(8 sqrt(V), W) + L + the final store's radius at |ref| + the rest,
+    with the 8 once (2 exp(-32) per element, as everywhere in this file).  L is the one term that is neither: the kernel's Wlo meets
+    RN16(y_kernel), the reference's RN16(y_ref); where the two lie on different sides of an fp16 rounding boundary the products differ
+    by |Wlo| ulp16(y) -- about 2^-22 |w y| per channel, 4 u T in all and 1 % of the tolerance, added in full.
+    Block 13's dst2 (the expanded tensor, an SSD feature map) is checked as the 1x1 conv it is: e_acc + half an ulp16; the split-operand
+    kernel stores fp16(6 * z), one more rounding."""
+    form = form or chunk_form(op)
+    hp = op.hp
+    bw = block_weights(op, weights, form)
+    xh = np.asarray(src_hi, np.float64)
+    xl = np.zeros_like(xh) if src_lo is None else np.asarray(src_lo, np.float64)
+    top = 1.0 if hp else 6.0
+    nprod = 3 if hp else 1
+    ref2 = tol2 = acc2 = None
+    # ---- expand
+    if bw["e_hi"] is not None:
+        whi, wlo, b = bw["e_hi"], bw["e_lo"], bw["e_b"]
+        if op.stem:
+            xh, xl = xh[..., :3], xl[..., :3]
+            st, sl = op.stem_pad
+            pre = conv64(xh, whi + wlo, 2, st, sl) + conv64(xl, whi, 2, st, sl) + b
+            T1 = conv64(np.abs(xh), np.abs(whi) + np.abs(wlo), 2, st, sl) + conv64(np.abs(xl), np.abs(whi), 2, st, sl) + np.abs(b)
+            terms = in_image_taps(xh.shape[1], xh.shape[2], 3, 2, st, sl)[None, :, :, None] * 3
+        else:
+            whi, wlo = whi[0, 0], wlo[0, 0]
+            pre = _mm(xh, whi + wlo) + _mm(xl, whi) + b
+            T1 = _mm(np.abs(xh), np.abs(whi) + np.abs(wlo)) + _mm(np.abs(xl), np.abs(whi)) + np.abs(b)
+            terms = float(whi.shape[0])
+        r1 = nprod * terms + 2 + (1 if form == FORM_FLOAT else 0)
+        z = np.clip(pre, 0.0, top)
+        W = r1 * U * T1
+        V = r1 * (U * T1) ** 2
+        if op.dst2:
+            scale = 6.0 if hp else 1.0                          # the split-operand kernel stores fp16(6 * z): one more rounding
+            ref2 = scale * z
+            acc2 = e_acc(scale * T1, r1 + (1 if hp else 0)) * np.ones_like(z)
+            tol2 = acc2 + 0.5 * ulp16(ref2 + acc2)
+        at = np.minimum(z + W, top)
+        h = 0.5 * ulp16(at) if form == FORM_FP16 else 0.5 * float_form_step(at) if form == FORM_FLOAT else np.full_like(z, 1.0 / 65535.0)
+        W, V = W + h, V + h * h
+    else:                                                       # no expand stage: the depthwise conv reads the stored tensor itself
+        if hp:
+            raise AssertionError("%s: a split-operand block without an expand stage" % op.scope)
+        z, W, V = xh + xl, np.zeros_like(xh), np.zeros_like(xh)
+    # ---- depthwise
+    wd, bd = bw["d_w"], bw["d_b"]
+    s, pt, pl = op.stride, op.pad_t, op.pad_l
+    y_pre = _dw(z, wd, s, pt, pl) + bd
+    T2 = _dw(np.abs(z), np.abs(wd), s, pt, pl) + np.abs(bd)
+    r2 = in_image_taps(z.shape[1], z.shape[2], 3, s, pt, pl)[None, :, :, None] + 2 + (1 if form == FORM_FLOAT else 0)
+    W = _dw(W, np.abs(wd), s, pt, pl) + r2 * U * T2
+    V = _dw(V, wd * wd, s, pt, pl) + r2 * (U * T2) ** 2
+    y = np.clip(y_pre, 0.0, 6.0)
+    h = pair_store_radius(y + W) if hp else 0.5 * ulp16(y + W)
+    W, V = W + h, V + h * h
+    # ---- project
+    whi, wlo, b = bw["p_hi"], bw["p_lo"], bw["p_b"]
+    if hp:
+        yhi = y.astype(np.float16).astype(np.float64)
+        ylo = y - yhi
+        ref = _mm(y, whi) + _mm(yhi, wlo) + b
+        T3 = _mm(np.abs(yhi) + np.abs(ylo), np.abs(whi)) + _mm(np.abs(yhi), np.abs(wlo)) + np.abs(b)
+        L = _mm(ulp16(y + W), np.abs(wlo))
+    else:
+        ref = _mm(y, whi) + b
+        T3 = _mm(np.abs(y), np.abs(whi)) + np.abs(b)
+        L = 0.0
+    r3 = nprod * whi.shape[0] + 2
+    if op.res:
+        rh = np.asarray(res_hi, np.float64)
+        rl = np.zeros_like(rh) if res_lo is None else np.asarray(res_lo, np.float64)
+        ref = ref + rh + rl
+        T3 = T3 + np.abs(rh) + np.abs(rl)
+        r3 += 2
+    wsum = whi + wlo
+    W = _mm(W, np.abs(wsum)) + r3 * U * T3
+    V = _mm(V, wsum * wsum) + r3 * (U * T3) ** 2
+    acc = np.minimum(8.0 * np.sqrt(V), W) + L
+    last = pair_store_radius(np.abs(ref) + acc) if store == "pair" else 0.5 * ulp16(np.abs(ref) + acc)
+    return BlockResult(ref, acc + last, acc, store, ref2, tol2, acc2)
+
+
+def pair_checks(hi: np.ndarray, lo: np.ndarray):
+    """The exact properties of a stored pair tensor ([n,h,w,c] float16 halves) -> list of messages (empty: all hold).
+      * both halves finite, |lo| <= ulp16(hi) / 2 (lo = RN16(v - hi) with hi = RN16(v));
+      * the lo half is alive: in every (frame, 4 x 4 pixel tile, 16-channel group) with at least eight elements of |hi| >= 2^-10, not
+        every lo is zero (a tile that lost its lo half is 2^-12 relative off: far below any bound)."""
+    msgs = []
+    h64, l64 = hi.astype(np.float64), lo.astype(np.float64)
+    if not (np.isfinite(h64).all() and np.isfinite(l64).all()):
+        msgs.append("pair halves: not finite")
+        return msgs
+    bad = np.abs(l64) > 0.5 * ulp16(h64)
+    if bad.any():
+        at = np.unravel_index(int(np.argmax(bad)), bad.shape)
+        msgs.append("pair halves: |lo| > ulp16(hi) / 2 at %d of %d elements, first at %s: hi %.9g lo %.9g"
+                    % (int(bad.sum()), bad.size, tuple(int(i) for i in at), h64[at], l64[at]))
+    n, h, w, c = hi.shape
+    ph, pw, pc = -h % 4, -w % 4, -c % 16
+    big = np.pad(np.abs(h64) >= 2.0 ** -10, ((0, 0), (0, ph), (0, pw), (0, pc)))
+    nz = np.pad(l64 != 0, ((0, 0), (0, ph), (0, pw), (0, pc)))
+
+    def groups(a):
+        return a.reshape(n, (h + ph) // 4, 4, (w + pw) // 4, 4, (c + pc) // 16, 16).sum(axis=(2, 4, 6))
+
+    dead = (groups(big) >= 8) & (groups(nz) == 0)
+    if dead.any():
+        at = np.unravel_index(int(np.argmax(dead)), dead.shape)
+        msgs.append("lo half dead: %d (frame, 4 x 4 tile, 16-channel group) with eight or more |hi| >= 2^-10 and every lo zero, first at "
+                    "frame index %d, tile (%d, %d), channels %d .. %d" % (int(dead.sum()), at[0], at[1], at[2], at[3] * 16, at[3] * 16 + 15))
+    return msgs
+
+
 def head_rows(op: "arch.Op", y: np.ndarray):
     """[n,h,w, a*4 | a*91] of an OUT_HEAD op -> (box [n, h*w*a, 4], class [n, h*w*a, 91]): pixel p, anchor a is row p * anchors + a."""
     n = y.shape[0]
@@ -250,9 +472,15 @@ def run_program(prog: "arch.Program", weights: Dict[str, np.ndarray], x: np.ndar
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the walker
 # ---------------------------------------------------------------------------------------------------------------------------------
-def op_kind_name(op: "arch.Op") -> str:
+def op_kind_name(op: "arch.Op", float_form_upto: int = -1) -> str:
     if op.kind == arch.OP_POOL:
         return "pool_max" if op.pool_max else "pool_avg"
+    if op.kind == arch.OP_MBCONV:                               # by the kernel family that runs the block
+        if not op.hp:
+            return "block_plain"
+        if chunk_form(op, float_form_upto) == FORM_FLOAT:
+            return "block_hp_q"
+        return "block_hp2" if (not op.stem and op.wout <= 10) else "block_hp"
     if op.kind != arch.OP_CONV:
         return {arch.OP_STEM: "stem3x3", arch.OP_STEM7: "stem7x7", arch.OP_DW: "depthwise", arch.OP_DWSEP: "dwsep"}[op.kind]
     if op.out_mode == arch.OUT_HEAD:
@@ -264,7 +492,8 @@ def op_kind_name(op: "arch.Op") -> str:
 @dataclass
 class Report:
     ops_checked: int = 0
-    ops_mbconv: int = 0
+    blocks_checked: int = 0                                   # the fused blocks (OP_MBCONV) among ops_checked
+    ops_mbconv: int = 0                                       # fused blocks passed over: none, they are checked like any other op
     ops_unchecked: int = 0
     elements: int = 0
     worst: Dict[str, tuple] = field(default_factory=dict)     # op kind -> (worst err / tol, op scope)
@@ -275,13 +504,14 @@ class Report:
 
     def summary(self) -> str:
         kinds = "  ".join("%s %.3g (acc %.3g)" % (k, v[0], self.worst_acc.get(k, 0.0)) for k, v in sorted(self.worst.items()))
-        return "%d ops checked (%d fused blocks left to their own tests, %d unchecked), %d elements; worst err / tol: %s" % (
-            self.ops_checked, self.ops_mbconv, self.ops_unchecked, self.elements, kinds)
+        return "%d ops checked (%d of them fused blocks, %d unchecked), %d elements; worst err / tol: %s" % (
+            self.ops_checked, self.blocks_checked, self.ops_unchecked, self.elements, kinds)
 
 
 def _compare(rep: Report, op, idx: int, what: str, got: np.ndarray, ref: np.ndarray, T, r, exact: bool, fp16_store: bool,
-             frames: Sequence[int]):
+             frames: Sequence[int], tol=None, acc=None, kind: Optional[str] = None):
     """got / ref / T [n, ..., c] (any middle axes = the pixel), r broadcastable; records a failure with the worst element.
+    tol / acc given (a fused block): the tolerance and its part that is not the final store, element by element, instead of T and r.
     -> (worst err / tol, worst share of e_acc in use)."""
     got64 = got.astype(np.float64)
     acc_share = 0.0
@@ -291,11 +521,13 @@ def _compare(rep: Report, op, idx: int, what: str, got: np.ndarray, ref: np.ndar
         ratio = np.where(bad, np.inf, 0.0)
         ref = expected
     else:
-        tol = tolerance(ref, T, r, fp16_store)
+        if tol is None:
+            tol, e = tolerance(ref, T, r, fp16_store), e_acc(T, r)
+        else:
+            e = acc
         err = np.abs(got64 - ref)
         bad = ~(err <= tol)                                   # (a NaN fails)
         ratio = np.where(bad & ~np.isfinite(err), np.inf, err / np.maximum(tol, 1e-300))
-        e = e_acc(T, r)
         share = np.where(e > 0, (err - (tol - e)) / np.where(e > 0, e, 1.0), 0.0)
         acc_share = float(np.nanmax(share)) if share.size else 0.0
     if not np.isfinite(got64).all():
@@ -306,43 +538,104 @@ def _compare(rep: Report, op, idx: int, what: str, got: np.ndarray, ref: np.ndar
     if bad.any():
         at = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
         rep.failures.append("op %d (%s, %s)%s: frame %d, pixel %s, channel %d: got %.9g, ref %.9g, err / tol %.3g%s; %d of %d elements outside"
-                            % (idx, op.scope, op_kind_name(op), what, frames[at[0]], tuple(int(i) for i in at[1:-1]), at[-1], got64[at], ref[at],
-                               ratio[at], " (exact comparison)" if exact else "", int(bad.sum()), bad.size))
+                            % (idx, op.scope, kind or op_kind_name(op), what, frames[at[0]], tuple(int(i) for i in at[1:-1]), at[-1], got64[at],
+                               ref[at], ratio[at], " (exact comparison)" if exact else "", int(bad.sum()), bad.size))
     return worst, max(acc_share, 0.0)
 
 
 def walk(eng, prog: "arch.Program", weights: Dict[str, np.ndarray], x_half: np.ndarray, precision: int = 16,
-         frames: Optional[Sequence[int]] = None, check: bool = True) -> Report:
+         frames: Optional[Sequence[int]] = None, check: bool = True, float_form_upto: int = -1) -> Report:
     """One forward pass of `eng` (tensors(), stage_forward(), stage_read_tensor(); every tensor must stay readable) on x_half
     [n,S,S,4] float16, then EVERY op of `prog` on its own: source (and residual) as the engine produced them -> ref, tol -> the
-    destination the engine produced.  `frames`: the frames whose references are computed (default: all).
-    Counts what it covers and asserts that nothing is left out: every op is checked or is a fused block (OP_MBCONV); every channel of
-    every tensor other than the input and those blocks' outputs is written by exactly one checked op; every row of the two head
-    outputs by exactly one head.  check=True raises AssertionError naming every failing op; the Report says what was seen."""
+    destination the engine produced.  `frames`: the frames whose references are computed (default: all).  float_form_upto: the last
+    split-operand block whose chunk buffer holds the 16-bit float form (the robust program: FLOAT_FORM_UPTO).
+    A fused block (OP_MBCONV) is an op like any other: block_reference on the stored halves of its source and residual
+    (stage_read_tensor(..., halves=True) for the tensors the program marks as pairs), its output -- and block 13's second one, the
+    expanded tensor -- against the element-by-element tolerance, and the exact properties of what it stored: pair_checks on a pair
+    output, bit-equal halves of a `dup_out` one.
+    Counts what it covers and asserts that nothing is left out: every op is checked; every channel of every tensor other than the
+    input is written by exactly one checked op; every row of the two head outputs by exactly one head.  check=True raises
+    AssertionError naming every failing op; the Report says what was seen."""
     n = x_half.shape[0]
     frames = list(range(n)) if frames is None else sorted(set(int(f) for f in frames))
     be, lg = eng.stage_forward(x_half)
     info = {name: (i, h, w, c) for i, (name, h, w, c) in enumerate(eng.tensors())}
     last_use: Dict[str, int] = {}
     for i, op in enumerate(prog.ops):
-        for t in (op.src, op.res, None if op.out_mode == arch.OUT_HEAD else op.dst):
+        for t in (op.src, op.res, None if op.out_mode == arch.OUT_HEAD else op.dst, op.dst2):
             if t:
                 last_use[t] = i
     cache: Dict[str, np.ndarray] = {}
+    hcache: Dict[str, tuple] = {}
 
     def read(name: str) -> np.ndarray:
         if name not in cache:
             cache[name] = np.stack([eng.stage_read_tensor(info[name][0], f) for f in frames])
         return cache[name]
 
+    def halves(name: str):
+        """(hi, lo) float16 as stored; lo None for a tensor that is no pair."""
+        if not prog.tensors[name].hp:
+            return read(name), None
+        if name not in hcache:
+            hl = [eng.stage_read_tensor(info[name][0], f, halves=True) for f in frames]
+            hcache[name] = (np.stack([h for h, _ in hl]), np.stack([l for _, l in hl]))
+        return hcache[name]
+
+    def record(kind, scope, worst, acc):
+        if kind not in rep.worst or worst > rep.worst[kind][0]:
+            rep.worst[kind] = (worst, scope)
+        rep.worst_acc[kind] = max(rep.worst_acc.get(kind, 0.0), acc)
+
     rep = Report()
     cover = {name: np.zeros(c, np.int64) for name, (_, _, _, c) in info.items() if name != "input"}
     rows_cover = np.zeros(prog.num_anchors, np.int64)
-    block_outputs = set()
     for idx, op in enumerate(prog.ops):
         if op.kind == arch.OP_MBCONV:
-            rep.ops_mbconv += 1
-            block_outputs.update(t for t in (op.dst, op.dst2) if t)
+            kind = op_kind_name(op, float_form_upto)
+            store = "dup" if op.dup_out else "pair" if prog.tensors[op.dst].hp else "fp16"
+            try:
+                sh, sl = halves(op.src)
+                rh, rl = halves(op.res) if op.res else (None, None)
+                res = block_reference(op, weights, sh, sl, rh, rl, chunk_form(op, float_form_upto), store)
+            except AssertionError as e:
+                rep.ops_unchecked += 1
+                rep.failures.append("op %d (%s): %s" % (idx, op.scope, e))
+                continue
+            gh, gl = halves(op.dst)
+            want_c = 2 * op.cout if store == "dup" else op.cout
+            if gh.shape[1:] != res.ref.shape[1:3] + (want_c,) or (store == "pair") != (gl is not None) or \
+                    (op.dst2 and read(op.dst2).shape[1:] != res.ref2.shape[1:]):
+                rep.failures.append("op %d (%s): the engine's tensor %s is %s%s, the block writes %s x %d as %s"
+                                    % (idx, op.scope, op.dst, gh.shape[1:], " (a pair)" if gl is not None else "", res.ref.shape[1:3], want_c, store))
+                rep.ops_unchecked += 1
+                continue
+            exact_msgs = []
+            if store == "pair":
+                got = gh.astype(np.float64) + gl.astype(np.float64)
+                exact_msgs = pair_checks(gh, gl)
+            elif store == "dup":
+                got = gh[..., :op.cout]
+                a, b = np.ascontiguousarray(got).view(np.uint16), np.ascontiguousarray(gh[..., op.cout:]).view(np.uint16)
+                if not (a == b).all():
+                    exact_msgs = ["[hi | hi]: the two copies differ in %d of %d elements" % (int((a != b).sum()), a.size)]
+            else:
+                got = gh
+            for m in exact_msgs:
+                rep.failures.append("op %d (%s, %s) %s" % (idx, op.scope, kind, m))
+            cover[op.dst] += 1
+            worst, acc = _compare(rep, op, idx, "", got, res.ref, None, None, False, True, frames, tol=res.tol, acc=res.acc, kind=kind)
+            record(kind, op.scope, worst, acc)
+            if op.dst2:
+                cover[op.dst2] += 1
+                w2, a2 = _compare(rep, op, idx, " expanded tensor", read(op.dst2), res.ref2, None, None, False, True, frames, tol=res.tol2,
+                                  acc=res.acc2, kind="block13_expand")
+                record("block13_expand", op.scope, w2, a2)
+            rep.ops_checked += 1
+            rep.blocks_checked += 1
+            for c_ in (cache, hcache):
+                for t in [t for t in c_ if last_use.get(t, -1) <= idx]:
+                    del c_[t]
             continue
         try:
             res = reference(op, weights, read(op.src), read(op.res) if op.res else None, precision)
@@ -371,19 +664,15 @@ def walk(eng, prog: "arch.Program", weights: Dict[str, np.ndarray], x_half: np.n
             cover[op.dst][c0:c1] += 1
             worst, acc = _compare(rep, op, idx, "", got[..., c0:c1], res.ref, res.T, res.r, res.exact, precision == 16, frames)
         rep.ops_checked += 1
-        if kind not in rep.worst or worst > rep.worst[kind][0]:
-            rep.worst[kind] = (worst, op.scope)
-        rep.worst_acc[kind] = max(rep.worst_acc.get(kind, 0.0), acc)
-        for t in [t for t in cache if last_use.get(t, -1) <= idx]:
-            del cache[t]
+        record(kind, op.scope, worst, acc)
+        for c_ in (cache, hcache):
+            for t in [t for t in c_ if last_use.get(t, -1) <= idx]:
+                del c_[t]
 
     # nothing left out silently
-    if rep.ops_checked + rep.ops_mbconv != len(prog.ops) or rep.ops_unchecked:
-        rep.failures.append("coverage: %d ops checked + %d fused blocks of %d ops (%d unchecked)"
-                            % (rep.ops_checked, rep.ops_mbconv, len(prog.ops), rep.ops_unchecked))
+    if rep.ops_checked != len(prog.ops) or rep.ops_unchecked:
+        rep.failures.append("coverage: %d ops checked of %d ops (%d unchecked)" % (rep.ops_checked, len(prog.ops), rep.ops_unchecked))
     for name, cnt in cover.items():
-        if name in block_outputs:
-            continue
         if not (cnt == 1).all():
             rep.failures.append("coverage: tensor %s: channels written by %s checked ops (every channel exactly once expected)"
                                 % (name, sorted(set(int(v) for v in cnt))))
@@ -437,9 +726,9 @@ def conformance_batch(n: int, size: int, start: int, seed: int, frame_input) -> 
     return out
 
 
-def frame_subset(n: int) -> List[int]:
-    """All frames up to batch 8; beyond, frame 0, one in the middle and the last."""
-    return list(range(n)) if n <= 8 else [0, n // 2, n - 1]
+def frame_subset(n: int, all_upto: int = 8) -> List[int]:
+    """All frames up to batch `all_upto`; beyond, frame 0, one in the middle and the last."""
+    return list(range(n)) if n <= all_upto else [0, n // 2, n - 1]
 
 
 def old_bound_passes(got: np.ndarray, ref: np.ndarray) -> bool:

@@ -603,13 +603,16 @@ class HipEngine:
                                               C.c_void_p(lg.ctypes.data)))
         return be, lg
 
-    def stage_read_tensor(self, idx: int, frame: int = 0) -> np.ndarray:
-        """(h,w,c) array as stored; a pair tensor comes back as float32 hi + lo."""
+    def stage_read_tensor(self, idx: int, frame: int = 0, halves: bool = False):
+        """(h,w,c) array as stored; a pair tensor comes back as float32 hi + lo (not always exact: 1 + 2^-24 needs 25 bits).
+        halves=True: (hi, lo), the two float16 planes of a pair tensor exactly as stored; (the tensor, None) for any other."""
         self._dev_only("stage_read_tensor()")
         name, h, w, c = self.tensors()[idx]
         pair = self.tensor_is_pair(idx)
         out = np.empty((h, w, 2 * c if pair else c), np.float16 if (self.precision == 16 or name == "input") else np.float32)
         self._ck(self._lib.wz_stage_read_tensor(self._h, idx, frame, C.c_void_p(out.ctypes.data)))
+        if halves:
+            return (out[..., :c].copy(), out[..., c:].copy()) if pair else (out, None)
         if pair:
             return out[..., :c].astype(np.float32) + out[..., c:].astype(np.float32)
         return out
