@@ -501,6 +501,13 @@ class Report:
                                                                # the share of the ACCUMULATION allowance in use (err / tol of an fp16 tensor is
                                                                # near 1 whenever the final rounding lands near half an ulp)
     failures: List[str] = field(default_factory=list)
+    subnormal_refs: int = 0                                   # compared elements whose reference is non-zero and below 2^-14 in magnitude
+    dead_elements: int = 0                                    # compared elements in the channels `marks` calls dead / saturated
+    saturated_elements: int = 0
+
+    def populations(self) -> str:
+        return "%d references fp16-subnormal, %d elements in dead channels, %d in saturated channels" % (
+            self.subnormal_refs, self.dead_elements, self.saturated_elements)
 
     def summary(self) -> str:
         kinds = "  ".join("%s %.3g (acc %.3g)" % (k, v[0], self.worst_acc.get(k, 0.0)) for k, v in sorted(self.worst.items()))
@@ -534,6 +541,8 @@ def _compare(rep: Report, op, idx: int, what: str, got: np.ndarray, ref: np.ndar
         bad = bad | ~np.isfinite(got64)
         ratio = np.where(np.isfinite(got64), ratio, np.inf)
     rep.elements += int(got.size)
+    a = np.abs(ref)
+    rep.subnormal_refs += int(((a > 0) & (a < 2.0 ** -14)).sum())
     worst = float(ratio.max()) if ratio.size else 0.0
     if bad.any():
         at = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
@@ -544,7 +553,8 @@ def _compare(rep: Report, op, idx: int, what: str, got: np.ndarray, ref: np.ndar
 
 
 def walk(eng, prog: "arch.Program", weights: Dict[str, np.ndarray], x_half: np.ndarray, precision: int = 16,
-         frames: Optional[Sequence[int]] = None, check: bool = True, float_form_upto: int = -1) -> Report:
+         frames: Optional[Sequence[int]] = None, check: bool = True, float_form_upto: int = -1,
+         marks: Optional[Dict[str, dict]] = None) -> Report:
     """One forward pass of `eng` (tensors(), stage_forward(), stage_read_tensor(); every tensor must stay readable) on x_half
     [n,S,S,4] float16, then EVERY op of `prog` on its own: source (and residual) as the engine produced them -> ref, tol -> the
     destination the engine produced.  `frames`: the frames whose references are computed (default: all).  float_form_upto: the last
@@ -553,6 +563,9 @@ def walk(eng, prog: "arch.Program", weights: Dict[str, np.ndarray], x_half: np.n
     (stage_read_tensor(..., halves=True) for the tensors the program marks as pairs), its output -- and block 13's second one, the
     expanded tensor -- against the element-by-element tolerance, and the exact properties of what it stored: pair_checks on a pair
     output, bit-equal halves of a `dup_out` one.
+    marks (trained_like.marks): stored tensor -> dead / saturated channel masks and the dead channels' constant.  The elements of
+    both kinds are counted; a dead channel of a `-p 16` tensor is compared BIT FOR BIT with its constant fp16(relu6(beta)) (gamma is
+    exactly 0, so the weight column is zero in both halves and nothing but the bias reaches the store).
     Counts what it covers and asserts that nothing is left out: every op is checked; every channel of every tensor other than the
     input is written by exactly one checked op; every row of the two head outputs by exactly one head.  check=True raises
     AssertionError naming every failing op; the Report says what was seen."""
@@ -586,6 +599,26 @@ def walk(eng, prog: "arch.Program", weights: Dict[str, np.ndarray], x_half: np.n
         if kind not in rep.worst or worst > rep.worst[kind][0]:
             rep.worst[kind] = (worst, scope)
         rep.worst_acc[kind] = max(rep.worst_acc.get(kind, 0.0), acc)
+
+    def degenerate(idx, op, name, got, c0, c1):
+        """got [n,h,w,c1 - c0]: channels c0 .. c1 of the stored tensor `name`, as op `idx` wrote them."""
+        m = (marks or {}).get(name)
+        if m is None:
+            return
+        dead, sat = m["dead"][c0:c1], m["saturated"][c0:c1]
+        rep.dead_elements += int(dead.sum()) * int(np.prod(got.shape[:3]))
+        rep.saturated_elements += int(sat.sum()) * int(np.prod(got.shape[:3]))
+        if precision == 16 and dead.any():
+            want = np.ascontiguousarray(m["const"][c0:c1][dead]).view(np.uint16)
+            have = np.ascontiguousarray(got[..., dead]).view(np.uint16)
+            bad = have != want
+            if bad.any():
+                at = np.unravel_index(int(np.argmax(bad)), bad.shape)
+                ch = int(np.flatnonzero(dead)[at[-1]])
+                rep.failures.append("op %d (%s, %s) dead channel: %d of %d elements differ from fp16(relu6(beta)), first at frame %d, pixel %s, "
+                                    "channel %d: bits 0x%04x, constant 0x%04x" % (idx, op.scope, op_kind_name(op, float_form_upto), int(bad.sum()),
+                                                                                  bad.size, frames[at[0]], tuple(int(i) for i in at[1:-1]), ch,
+                                                                                  int(have[at]), int(want[at[-1]])))
 
     rep = Report()
     cover = {name: np.zeros(c, np.int64) for name, (_, _, _, c) in info.items() if name != "input"}
@@ -631,6 +664,7 @@ def walk(eng, prog: "arch.Program", weights: Dict[str, np.ndarray], x_half: np.n
                 w2, a2 = _compare(rep, op, idx, " expanded tensor", read(op.dst2), res.ref2, None, None, False, True, frames, tol=res.tol2,
                                   acc=res.acc2, kind="block13_expand")
                 record("block13_expand", op.scope, w2, a2)
+                degenerate(idx, op, op.dst2, read(op.dst2), 0, op.cmid)
             rep.ops_checked += 1
             rep.blocks_checked += 1
             for c_ in (cache, hcache):
@@ -663,6 +697,7 @@ def walk(eng, prog: "arch.Program", weights: Dict[str, np.ndarray], x_half: np.n
                 continue
             cover[op.dst][c0:c1] += 1
             worst, acc = _compare(rep, op, idx, "", got[..., c0:c1], res.ref, res.T, res.r, res.exact, precision == 16, frames)
+            degenerate(idx, op, op.dst, got[..., c0:c1], c0, c1)
         rep.ops_checked += 1
         record(kind, op.scope, worst, acc)
         for c_ in (cache, hcache):

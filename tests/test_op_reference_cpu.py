@@ -1,6 +1,9 @@
 """tests/op_reference.py proves itself without a GPU: the chained float64 references against the three fp32 oracles, the walker on a
 fake engine with one seeded defect at a time, the fused blocks on an emulator that rounds where the kernels round (three storage
-forms, four summation orders, eight structural and three precision defects), and the bound function on fp32 sums in four orders."""
+forms, four summation orders, eight structural and three precision defects), and the bound function on fp32 sums in four orders.
+The last section does it again on weights spread like a trained checkpoint's (tests/trained_like.py): the generator's properties on
+the small program and the three networks, both emulators inside the unchanged bound at up to two decades, every seeded defect named
+again, and the defects that need fp16-subnormal operands to show."""
 import math
 
 import numpy as np
@@ -10,6 +13,7 @@ import torch.nn.functional as F
 
 import op_reference as R
 import parity_utils as pu
+import trained_like as TL
 from inception_v2_oracle import InceptionOracleNet
 from mobilenet_v1_oracle import MobilenetV1OracleNet
 from oracle.ssd_mobilenet_v2 import OracleNet
@@ -189,6 +193,8 @@ class FakeEngine:
             b[-1] = 0
         elif d == "relu6_clamps_at_6.5":
             hi = np.float32(6.5)
+        elif d == "subnormal_weights_read_as_zero":
+            w = np.where(np.abs(w) < 2.0 ** -14, 0.0, w)
         y = self._conv(x, w, stride, pad_t, pad_l)[:, :op.hout, :op.wout] + b
         if d == "residual_before_activation" and res is not None:
             y, res = y + res.astype(np.float32), None
@@ -236,12 +242,16 @@ class FakeEngine:
                     c = np.roll(c.reshape(n, -1, op.anchors_per_loc, arch.NUM_CLASSES), 1, axis=2).reshape(c.shape)
                 be[:, op.anchor_offset:op.anchor_offset + b.shape[1]] = b
                 lg[:, op.anchor_offset:op.anchor_offset + c.shape[1]] = c
-            elif op.cdst:
-                t = T.setdefault(op.dst, np.zeros(y.shape[:3] + (op.cdst,), np.float16))
-                coff = op.coff + (8 if d == "slice_written_8_channels_late" else 0)
-                t[..., coff:coff + op.cout] = y.astype(np.float16)
             else:
-                T[op.dst] = y.astype(np.float16)
+                y16 = y.astype(np.float16)
+                if d == "store_flushes_subnormals":
+                    y16 = np.where(np.abs(y16) < np.float16(2.0 ** -14), np.float16(0), y16)
+                if op.cdst:
+                    t = T.setdefault(op.dst, np.zeros(y.shape[:3] + (op.cdst,), np.float16))
+                    coff = op.coff + (8 if d == "slice_written_8_channels_late" else 0)
+                    t[..., coff:coff + op.cout] = y16
+                else:
+                    T[op.dst] = y16
         self.be, self.lg = be, lg
         return be, lg
 
@@ -477,6 +487,8 @@ class BlockEngine(FakeEngine):
             whi, wlo = bw["e_hi"].reshape(27, -1), bw["e_lo"].reshape(27, -1)
         else:
             whi, wlo = bw["e_hi"][0, 0], bw["e_lo"][0, 0]
+        if d == "wlo_subnormals_read_as_zero":                                      # ... in both GEMMs of the block
+            wlo = np.where(np.abs(wlo) < 2.0 ** -14, 0.0, wlo)
         terms = [(xh, wlo), (xl, whi), (xh, whi)] if hp else [(xh, whi)]
         dpre = _gemm_f32(bw["e_b"], terms, order)                                   # [n, hin, win, cmid] float32
         top = F32(1) if hp else F32(6)
@@ -525,6 +537,8 @@ class BlockEngine(FakeEngine):
         if hp:
             yh, yl = _split16(y)
             whi, wlo = bw["p_hi"], bw["p_lo"]
+            if d == "wlo_subnormals_read_as_zero":
+                wlo = np.where(np.abs(wlo) < 2.0 ** -14, 0.0, wlo)
             terms = [(yh, wlo), (yl, whi), (yh, whi)]
             if d == "wlo_xhi_dropped":
                 terms = terms[1:]
@@ -548,6 +562,9 @@ class BlockEngine(FakeEngine):
         oh, ol = _split16(acc)
         if d == "output_lo_zeroed_in_one_tile":
             ol[0, 4:8, 4:8] = 0
+        if d == "pair_store_flushes_subnormals":
+            oh = np.where(np.abs(oh) < np.float16(2.0 ** -14), np.float16(0), oh)
+            ol = np.where(np.abs(ol) < np.float16(2.0 ** -14), np.float16(0), ol)
         if self.prog.tensors[op.dst].hp:
             self.T[op.dst] = (oh, ol)
         else:
@@ -736,3 +753,239 @@ def test_bound_pieces():
     assert t[0, 0] == 4 and t[0, 5] == 6 and t[9, 9] == 9 and t[18, 18] == 4
     t = R.in_image_taps(10, 10, 3, 2, 0, 0)                     # even map, stride 2: the padding is bottom / right only
     assert t.shape == (5, 5) and t[0, 0] == 9 and t[4, 4] == 4 and t[0, 4] == 6
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# weights spread like a trained checkpoint's (tests/trained_like.py): the generator's properties, the emulators inside the bound,
+# the seeded defects named again, and the defects that only such weights can show
+# ---------------------------------------------------------------------------------------------------------------------------------
+TL_SEED = 77
+
+
+def _real_program(family):
+    return {"mobilenet_v2": (arch.build(fuse=False), synthetic_weights, 2.0),
+            "inception_v2": (inception.build(), synthetic_inception_v2, 1.5),
+            "mobilenet_v1": (mobilenet_v1.build(fuse=False), synthetic_mobilenet_v1, 1.5)}[family]
+
+
+@pytest.fixture(scope="module")
+def small_spread(small):
+    """decades -> (program, trained-like weights, inputs) of the small program, built once."""
+    prog, W, x = small
+    cache = {}
+
+    def get(decades):
+        if decades not in cache:
+            cache[decades] = (prog, TL.trained_like(W, prog, decades, TL_SEED), x)
+        return cache[decades]
+    return get
+
+
+@pytest.fixture(scope="module")
+def blocks_spread(blocks):
+    """decades -> ({form -> (program, trained-like weights, float_form_upto)}, inputs) of the four-block programs."""
+    progs, x = blocks
+    cache = {}
+
+    def get(decades):
+        if decades not in cache:
+            cache[decades] = {form: (prog, TL.trained_like(W, prog, decades, TL_SEED), ffu) for form, (prog, W, ffu) in progs.items()}
+        return cache[decades], x
+    return get
+
+
+@pytest.mark.parametrize("family", ["small", "mobilenet_v2", "inception_v2", "mobilenet_v1"])
+def test_trained_like_weights_have_the_properties_the_gpu_tests_rely_on(small, family):
+    """In the float64 network on these weights: the per-channel max|activation| of every BatchNorm-produced tensor spans at least
+    0.7 * decades decades between its 5th and 95th percentile; dead channels are exactly constant; saturated channels are 6 at more
+    than 90 % of the pixels; fp16 subnormals exist among the packed `-p 16` weights (the lo halves of the robust program included) and
+    among the activations rounded to fp16; the MobileNet-v2 result is what `--robust auto` packs the robust program for."""
+    if family == "small":
+        prog, W0, x = small
+        decades = 2.0
+    else:
+        prog, make, decades = _real_program(family)
+        W0 = make(SEED)
+        x = pu.oracle_input_half([synthetic_frame(640, 480, 5000)])
+    W = TL.trained_like(W0, prog, decades, TL_SEED)
+    again = TL.trained_like(W0, prog, decades, TL_SEED)
+    assert set(W) == set(W0) and all((W[k] == again[k]).all() and W[k].dtype == np.float32 and W[k].shape == W0[k].shape for k in W)
+    assert any((W[k] != v).any() for k, v in TL.trained_like(W0, prog, decades, TL_SEED + 1).items())
+    T, _, _ = R.run_program(prog, W, x.astype(np.float64))
+    marks = TL.marks(prog, W)
+    spans, n_dead, n_sat = {}, 0, 0
+    for op in prog.ops:
+        if not op.has_bn or op.out_mode == OUT_HEAD or op.kind == OP_POOL:
+            continue
+        c0 = op.coff if op.cdst else 0
+        t = T[op.dst][..., c0:c0 + op.cout]
+        lo, hi = np.percentile(np.abs(t).max(axis=(0, 1, 2)), [5, 95])
+        spans[op.scope] = math.log10(hi / max(lo, 1e-300))
+        m = marks.get(op.dst)
+        if m is None:
+            continue
+        dead, sat = m["dead"][c0:c0 + op.cout], m["saturated"][c0:c0 + op.cout]
+        n_dead, n_sat = n_dead + int(dead.sum()), n_sat + int(sat.sum())
+        td = t[..., dead].reshape(-1, int(dead.sum()))
+        assert (td == td[0]).all(), op.scope                                         # exactly constant: relu6(beta)
+        assert ((td[0] >= 0) & (td[0] <= 6)).all()
+        assert ((t[..., sat] == 6.0).mean(axis=(0, 1, 2)) > 0.9).all(), op.scope
+    worst = min(spans, key=spans.get)
+    assert spans[worst] >= 0.7 * decades, (worst, spans[worst])
+    assert n_dead > 0 and n_sat > 0
+    flat = [p for op in prog.ops for p in (op.parts if op.kind == OP_DWSEP else [op]) if p.kind != OP_POOL]
+    sub_w = sum(TL.count_fp16_subnormal(R.engine_weights(p, W, 16)[0]) for p in flat if p.kind != OP_STEM)
+    if family == "mobilenet_v2":
+        for op in arch.build(hp_upto=arch.HP_ALL_BLOCKS, conv1_split=True).ops:
+            if op.kind == arch.OP_MBCONV:
+                bw = R.block_weights(op, W, R.chunk_form(op, R.FLOAT_FORM_UPTO))
+                sub_w += sum(TL.count_fp16_subnormal(bw[k]) for k in ("e_lo", "p_lo") if bw[k] is not None)
+        spread = R.engine.channel_spread_decades(W)
+        print("\nengine.channel_spread_decades: %.2f" % spread)
+        assert spread > R.engine.SPREAD_VALIDATED_DECADES
+    sub_a = sum(TL.count_fp16_subnormal(t.astype(np.float16)) for name, t in T.items() if name != "input")
+    print("\n%s at %.1f decades: narrowest tensor %s (%.2f decades p5 .. p95); %d dead and %d saturated channels; fp16 subnormals: %d "
+          "packed weights, %d activations" % (family, decades, worst, spans[worst], n_dead, n_sat, sub_w, sub_a))
+    assert sub_w > 0 and sub_a > 0
+
+
+def test_trained_like_is_the_same_function_where_relu6_does_not_clip(small):
+    """Without degenerate channels and on an input small enough that no activation reaches 6, the spread network's head outputs are
+    those of the network it was made from: every consumer divides by what its producer multiplied by."""
+    prog, W0, _ = small
+    W0 = {k: v * np.float32(0.25) if k.endswith(("/gamma", "/beta")) else v for k, v in W0.items()}      # (a network that stays below 6)
+    x = np.stack([R.noise_input(prog.size, 41, 1.0)]).astype(np.float64)
+    T0, be0, lg0 = R.run_program(prog, W0, x)
+    assert max(np.abs(t).max() for n, t in T0.items() if n != "input") < 6.0
+    W = TL.trained_like(W0, prog, 2.0, TL_SEED, dead=0.0, saturated=0.0)
+    _, be, lg = R.run_program(prog, W, x)
+    assert np.abs(be - be0).max() <= 1e-5 * np.abs(be0).max() and np.abs(lg - lg0).max() <= 1e-5 * np.abs(lg0).max()   # (float32 variables)
+
+
+@pytest.mark.parametrize("decades", [1.5, 2.0])
+def test_walker_passes_the_fp32_sum_engine_on_trained_like_weights(small_spread, decades):
+    prog, W, x = small_spread(decades)
+    rep = R.walk(FakeEngine(prog, W), prog, W, x, check=False, marks=TL.marks(prog, W))
+    print("\n%.1f decades: %s\n%s" % (decades, rep.summary(), rep.populations()))
+    assert not rep.failures, rep.failures[:5]
+    assert rep.ops_checked == len(prog.ops) and rep.ops_unchecked == 0
+    assert max(v[0] for v in rep.worst.values()) <= 1.0
+    assert rep.subnormal_refs > 0 and rep.dead_elements > 0 and rep.saturated_elements > 0
+
+
+@pytest.mark.parametrize("decades", [1.0, 2.0])
+@pytest.mark.parametrize("form", sorted(FORMS))
+def test_walker_passes_the_block_emulator_on_trained_like_weights(blocks_spread, form, decades):
+    progs, x = blocks_spread(decades)
+    prog, W, ffu = progs[form]
+    worst, by_order = {}, {}
+    for order in ORDERS:
+        rep = R.walk(BlockEngine(prog, W, ffu, order), prog, W, x, float_form_upto=ffu, check=False, marks=TL.marks(prog, W))
+        assert not rep.failures, (order, rep.failures[:5])
+        assert rep.ops_checked == rep.blocks_checked == len(prog.ops) == 4 and rep.ops_unchecked == 0
+        for k, v in rep.worst.items():
+            worst[k] = max(worst.get(k, 0.0), v[0])
+        by_order[order] = max(v[0] for k, v in rep.worst.items() if k != "block13_expand")
+    print("\n%s at %.0f decade(s): worst err / tol over four orders: %s (the blocks by order: %s); %s"
+          % (form, decades, "  ".join("%s %.3f" % kv for kv in sorted(worst.items())), "  ".join("%s %.3f" % (o, by_order[o]) for o in ORDERS),
+             rep.populations()))
+    assert max(worst.values()) < 1.0
+    assert rep.dead_elements > 0 and rep.saturated_elements > 0                       # (block 3's expanded tensor)
+
+
+def _only(where, msg):
+    lines = [ln for ln in msg.splitlines()[1:] if "coverage" not in ln]
+    assert lines and all("(%s," % where in ln for ln in lines), msg
+
+
+# the two defects that need subnormal operands to show: defect -> op it is put into
+SUBNORMAL_DEFECTS = {"store_flushes_subnormals": "expand", "subnormal_weights_read_as_zero": "mix/b1b"}
+
+
+@pytest.mark.parametrize("defect", sorted(DEFECTS) + sorted(SUBNORMAL_DEFECTS))
+def test_walker_names_the_op_of_every_defect_on_trained_like_weights(small_spread, defect):
+    """The eleven seeded defects at two decades of spread, and two more: an fp16 store that flushes subnormal results to zero, a GEMM
+    that reads subnormal fp16 weights as zero.  Each fails in the op that has it and in no other; the factor is printed."""
+    prog, W, x = small_spread(2.0)
+    where = DEFECTS[defect][0] if defect in DEFECTS else SUBNORMAL_DEFECTS[defect]
+    with pytest.raises(AssertionError) as ei:
+        R.walk(FakeEngine(prog, W, defect, where), prog, W, x)
+    _only(where, str(ei.value))
+    print("\n%s in %s at 2 decades: outside by a factor of %.3g" % (defect, where, _factor(str(ei.value))))
+
+
+@pytest.mark.parametrize("defect,form", STRUCTURAL_CASES, ids=["%s-%s" % c for c in STRUCTURAL_CASES])
+def test_walker_names_the_block_of_every_structural_defect_on_trained_like_weights(blocks_spread, defect, form):
+    progs, x = blocks_spread(2.0)
+    prog, W, ffu = progs[form]
+    where = STRUCTURAL[defect][0]
+    with pytest.raises(AssertionError) as ei:
+        R.walk(BlockEngine(prog, W, ffu, "chunks32", defect, where), prog, W, x, float_form_upto=ffu)
+    _only(where, str(ei.value))
+    print("\n%s in %s (%s) at 2 decades: outside by a factor of %.3g" % (defect, where, form, _factor(str(ei.value))))
+
+
+def test_walker_names_the_block_whose_pair_store_flushes_subnormals(blocks_spread):
+    """hi = RN16(v), lo = RN16(v - hi): below |v| = 2^-3 the lo half is an fp16 subnormal.  A store that flushes it loses up to 2^-15:
+    outside the float-form blocks' bound, in that block and in no other.  The linear unorm16 buffer's bound allows a whole code step
+    (1 / 65535 of full scale) per tap and cannot see it; that figure is printed beside it."""
+    progs, x = blocks_spread(2.0)
+    prog, W, ffu = progs["float_form"]
+    with pytest.raises(AssertionError) as ei:
+        R.walk(BlockEngine(prog, W, ffu, "chunks32", "pair_store_flushes_subnormals", "b1"), prog, W, x, float_form_upto=ffu)
+    _only("b1", str(ei.value))
+    prog, W, ffu = progs["unorm16"]
+    rep = R.walk(BlockEngine(prog, W, ffu, "chunks32", "pair_store_flushes_subnormals", "b1"), prog, W, x, float_form_upto=ffu, check=False)
+    print("\npair_store_flushes_subnormals in b1 at 2 decades: float form outside by a factor of %.3g; unorm16 worst err / tol %.3g"
+          % (_factor(str(ei.value)), rep.worst["block_hp"][0]))
+    assert all("(b1," in f for f in rep.failures), rep.failures
+
+
+@pytest.mark.parametrize("form", ["float_form", "unorm16"])
+@pytest.mark.parametrize("defect", sorted(PRECISION) + ["wlo_subnormals_read_as_zero"])
+def test_precision_defects_are_reported_on_trained_like_weights(blocks_spread, defect, form):
+    """The 2^-12 defects again at two decades, in both 16-bit forms of the chunk buffer, and one more: a split-operand block that reads
+    the subnormal values of its Wlo operands as zero.  Factors printed, not asserted -- except that the lo-half-alive rule must still
+    name the zeroed tile."""
+    progs, x = blocks_spread(2.0)
+    prog, W, ffu = progs[form]
+    where = PRECISION.get(defect, "b2")
+    good = R.walk(BlockEngine(prog, W, ffu, "chunks32"), prog, W, x, float_form_upto=ffu, check=False)
+    rep = R.walk(BlockEngine(prog, W, ffu, "chunks32", defect, where), prog, W, x, float_form_upto=ffu, check=False)
+    kind = R.op_kind_name([o for o in prog.ops if o.scope == where][0], ffu)
+    tol_fail = [f for f in rep.failures if "err / tol" in f]
+    print("\n%s in %s (%s) at 2 decades: worst err / tol %.3g (without the defect %.3g); bound %s, exact checks %s"
+          % (defect, where, form, rep.worst[kind][0], good.worst[kind][0], "FAILS" if tol_fail else "passes",
+             "FAIL" if len(rep.failures) > len(tol_fail) else "pass"))
+    assert not good.failures
+    if defect == "output_lo_zeroed_in_one_tile":
+        assert any("lo half dead" in f and "(%s," % where in f for f in rep.failures), rep.failures
+    assert all("(%s," % where in f for f in rep.failures), rep.failures
+
+
+def test_walker_names_a_dead_channel_that_holds_the_wrong_constant(small_spread):
+    """A dead channel is compared bit for bit: the neighbouring channel's bias (a layout bug) fails in that op, under `dead channel`."""
+    prog, W, x = small_spread(2.0)
+    marks = TL.marks(prog, W)
+    eng = FakeEngine(prog, W)
+    ch = int(np.flatnonzero(marks["e1"]["dead"])[0])
+    forward = eng.stage_forward
+
+    def corrupted(x_half):
+        out = forward(x_half)
+        eng.T["e1"][..., ch] = eng.T["e1"][..., ch] + np.float16(2.0 ** -10)
+        return out
+    eng.stage_forward = corrupted
+    rep = R.walk(eng, prog, W, x, check=False, marks=marks)
+    assert any("dead channel" in f and "(e1," in f for f in rep.failures), rep.failures
+
+
+@pytest.mark.parametrize("decades", [1.0, 2.0])
+def test_the_builder_packs_the_robust_program_for_trained_like_weights(decades):
+    """`--robust auto` decides by engine.channel_spread_decades: above SPREAD_VALIDATED_DECADES at one and two decades, and both
+    `-p 16` programs build (the float-form tap scaling fits)."""
+    W = TL.trained_like(synthetic_weights(SEED), arch.build(fuse=False), decades, TL_SEED)
+    spread = R.engine.channel_spread_decades(W)
+    print("\n%.1f decades: engine.channel_spread_decades %.2f" % (decades, spread))
+    assert spread > R.engine.SPREAD_VALIDATED_DECADES
+    assert len(R.engine.build_engine(W, robust=True)) > 0 and len(R.engine.build_engine(W)) > 0
