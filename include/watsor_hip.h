@@ -123,11 +123,13 @@ int wz_submit_host(wz_engine_t* e, int slot, int n, const uint8_t* const* rgb, c
  * camera or capture card writes packed 4:2:2 (`yuyv422` / `uyvy422`), an IR / thermal camera `gray`, an OpenCV producer `bgr24`.
  *   fmt[i]  the format word of frame i: a base format WZ_FMT_* in bits 0-7, or'ed with colour flags; fmt == NULL: all RGB24.
  *           NV12 / I420 frames are w*h*3/2 bytes and need even w and h; YUYV422 / UYVY422 are 2*w*h bytes and need even w;
- *           GRAY8 is w*h bytes, BGR24 3*w*h.
- *   flags   how the four YUV formats (NV12, I420, YUYV422, UYVY422) turn into RGB.  No flag: BT.601 limited range (what the
+ *           GRAY8 is w*h bytes, BGR24 3*w*h.  The two 10-bit 4:2:0 formats (P010, YUV420P10: what an HEVC Main10 stream decodes
+ *           to) hold one little-endian 16-bit word per sample, are 3*w*h bytes -- as many as RGB24: what they save is the host's
+ *           conversion, not bytes -- and need even w and h; a frame may sit at any byte address.
+ *   flags   how the YUV formats (NV12, I420, YUYV422, UYVY422, P010, YUV420P10) turn into RGB.  No flag: BT.601 limited range (what the
  *           words 1 and 2 have always meant).  WZ_CSP_BT709: the BT.709 matrix (what swscale applies to a 720p / 1080p stream tagged
  *           bt709).  WZ_RANGE_FULL: Y, U, V use 0..255 (ffmpeg's yuvj* formats: MJPEG cameras).  A flag on RGB24, BGR24 or GRAY8,
- *           any other bit, and a base format above WZ_FMT_BGR24 are refused (WZ_EINVAL).
+ *           any other bit, and every other base format (7 to 15, 18 and above) are refused (WZ_EINVAL).
  * The three calls are the ones above with that one argument more. */
 #define WZ_FMT_RGB24 0
 #define WZ_FMT_NV12 1   /* h x w luma, then h/2 x w/2 interleaved (U, V) */
@@ -136,6 +138,8 @@ int wz_submit_host(wz_engine_t* e, int slot, int n, const uint8_t* const* rgb, c
 #define WZ_FMT_UYVY422 4   /* packed U Y0 V Y1 (ffmpeg's uyvy422) */
 #define WZ_FMT_GRAY8 5     /* one byte per pixel, R = G = B = Y, no scaling (ffmpeg's `gray` is full range) */
 #define WZ_FMT_BGR24 6     /* RGB24 with the first and third byte swapped */
+#define WZ_FMT_P010 0x10       /* 10-bit: h x w luma words, the sample in the HIGH bits (word >> 6; the low 6 bits are ignored), then h/2 x w/2 (U, V) word pairs (ffmpeg's p010le) */
+#define WZ_FMT_YUV420P10 0x11  /* 10-bit: h x w luma words, the sample in the LOW bits (word & 0x3ff; the high 6 bits are ignored), then the U plane, then the V plane (ffmpeg's yuv420p10le) */
 #define WZ_FMT_BASE_MASK 0xff
 #define WZ_CSP_BT709 0x100    /* matrix; absent: BT.601 */
 #define WZ_RANGE_FULL 0x200   /* Y, U, V use 0..255 (the yuvj* formats); absent: limited range */
@@ -417,8 +421,8 @@ int wz_stage_tile_activity(wz_engine_t* e, const uint8_t* frame, int w, int h, i
  * issued them (the call runs first, with whatever state its cameras have); empty_ms: the same bracket around nothing */
 int wz_profile_gated(wz_engine_t* e, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt, const int* cam,
                      double iou_thr, double ios_thr, int reps, float* activity_ms, float* commit_ms, float* empty_ms);
-/* in_place[i] = 1 where frame i of the last tiled or gated wz_submit_bound on `slot` was read in place through its device view, 0 where it
- * was staged by DMA (n values: the frames of that batch); WZ_EINVAL when the lane has seen no such batch */
+/* in_place[i] = 1 where frame i of the last wz_submit_bound on `slot` -- untiled, tiled or gated -- was read in place through its device view,
+ * 0 where it was staged by DMA (n values: the frames of that batch); WZ_EINVAL when the lane has seen no such batch */
 int wz_debug_bound_source(wz_engine_t* e, int slot, int32_t* in_place /* [n] */);
 
 #endif /* WZ_DEV_BUILD */

@@ -1,10 +1,11 @@
 """PCIe-inclusive throughput: frames handed over as HOST pointers (the reference's boundary: a view of the shared
 FrameBuffer mmap, watsor/detection/detector.py:104-106), batch = 8, 640x480 (and 1920x1080), pageable vs page-locked.
 
-    python tools/host_path_bench.py  [--out profiles/xxx.json] [--format rgb24,nv12,yuyv422,gray] [--size 1920x1080]
+    python tools/host_path_bench.py  [--out profiles/xxx.json] [--format rgb24,nv12,yuyv422,gray,p010le] [--size 1920x1080]
 
 --format: the pixel format(s) the frames are handed over in (default rgb24) -- what the formats with fewer bytes per frame buy on
-the PCIe-bound leg; one engine and one set of pictures per size, every format measured in the same run.
+the PCIe-bound leg; one engine and one set of pictures per size, every format measured in the same run.  p010le (10-bit, a 16-bit
+word per sample) is as many bytes as rgb24: its line shows what the conversion on the GPU costs, the gain is the host's swscale pass.
 """
 import json
 import os
@@ -18,13 +19,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from watsor_amd import engine as eb                                   # noqa: E402
 from oracle import yuv                                                # noqa: E402
-from watsor_amd.runtime import FMT_GRAY8, FMT_NV12, FMT_RGB24, FMT_YUYV422, HipEngine   # noqa: E402
+from watsor_amd.runtime import FMT_GRAY8, FMT_NV12, FMT_P010, FMT_RGB24, FMT_YUYV422, HipEngine   # noqa: E402
 from watsor_amd.synth import synthetic_frame, synthetic_weights      # noqa: E402
 
 BATCH = 8
 
 
-FORMATS = {"rgb24": FMT_RGB24, "nv12": FMT_NV12, "yuyv422": FMT_YUYV422, "gray": FMT_GRAY8}
+FORMATS = {"rgb24": FMT_RGB24, "nv12": FMT_NV12, "yuyv422": FMT_YUYV422, "gray": FMT_GRAY8, "p010le": FMT_P010}
 
 
 def run(eng, frames, n_steps, fmt=FMT_RGB24):
@@ -52,6 +53,8 @@ def as_format(rgb, name):
         return nv12
     if name == "gray":
         return nv12[:h].copy()
+    if name == "p010le":   # NV12's samples as 10-bit ones (<< 2) in the high bits of a word (<< 6), handed over as the words' bytes
+        return (nv12.astype(np.uint16) << 8).view(np.uint8).reshape(h * 3 // 2, w * 2)
     y = nv12[:h].reshape(h, w // 2, 2)
     uv = np.repeat(nv12[h:].reshape(h // 2, w // 2, 2), 2, axis=0)
     return np.stack([y[..., 0], uv[..., 0], y[..., 1], uv[..., 1]], axis=-1).reshape(h, w, 2)     # Y0 U Y1 V

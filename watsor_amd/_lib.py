@@ -21,6 +21,7 @@ WZ_OK, WZ_EINVAL, WZ_ENOENT, WZ_EFORMAT, WZ_EHIP, WZ_ENODEV, WZ_ELIMIT, WZ_EINCO
 WZ_SLOTS = 8
 WZ_FMT_RGB24, WZ_FMT_NV12, WZ_FMT_I420 = 0, 1, 2
 WZ_FMT_YUYV422, WZ_FMT_UYVY422, WZ_FMT_GRAY8, WZ_FMT_BGR24 = 3, 4, 5, 6   # base formats: bits 0-7 of a frame's format word
+WZ_FMT_P010, WZ_FMT_YUV420P10 = 0x10, 0x11                                # ... 10-bit 4:2:0, a 16-bit word per sample
 WZ_FMT_BASE_MASK, WZ_CSP_BT709, WZ_RANGE_FULL = 0xFF, 0x100, 0x200        # ... or'ed with the colour flags of the YUV formats
 WZ_NUM_LABELS = 91
 WZ_MAX_CAMS = 256

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(WZ_GATE_THREADS) void wz_k_tile_activity(const WzGa
         const int words = (head + rb + 15) >> 4;
         const int mode = t.mode;
         const int cell_shift = mode == WZ_GATE_GRAY ? 4 : 5;   // bytes of a cell in a row: 16, 32 (4:2:2) -- or 48 (three bytes a pixel)
-        const bool three = mode >= WZ_GATE_RGB;
+        const bool three = mode == WZ_GATE_RGB || mode == WZ_GATE_BGR;
         const uint32_t w_first = mode == WZ_GATE_RGB ? 77u : 29u, w_last = mode == WZ_GATE_RGB ? 29u : 77u;
         auto load = [&](int k) -> uint4 {
             uint4 v = make_uint4(0u, 0u, 0u, 0u);
@@ -68,10 +68,14 @@ __global__ __launch_bounds__(WZ_GATE_THREADS) void wz_k_tile_activity(const WzGa
                 cell_a = lo0 >> cell_shift;
                 bnd = ((cell_a + 1) << cell_shift) - lo;
                 // which bytes are lumas: all of them, or those whose offset in the row is even (YUYV) / odd (UYVY)
+                // WZ_GATE_LOW10: the luma of a word lo | hi << 8 is bits 2 .. 9 = (lo >> 2) + ((hi & 3) << 6) -- a sum over its two bytes, which lie
+                // in one cell (a cell's 32 bytes start at an even offset) though not always in one 16-byte word: each byte adds its share
+                const bool low10 = mode == WZ_GATE_LOW10;
                 const int sel = mode == WZ_GATE_GRAY ? -1 : (((mode == WZ_GATE_UYVY) ? 1 : 0) ^ (head & 1));
 #pragma unroll
                 for (int j = 0; j < 16; ++j) {
-                    const uint32_t b = (sel < 0 || (j & 1) == sel) ? wz_gate_byte(v, j) : 0u;
+                    const uint32_t raw = wz_gate_byte(v, j);
+                    const uint32_t b = low10 ? (((j ^ head) & 1) ? (raw & 3u) << 6 : raw >> 2) : (sel < 0 || (j & 1) == sel) ? raw : 0u;
                     sum_a += j < bnd ? b : 0u;
                     sum_b += j < bnd ? 0u : b;
                 }

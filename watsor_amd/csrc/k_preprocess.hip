@@ -1,4 +1,4 @@
-// Resize + normalise: a frame of any resolution (packed RGB24 / BGR24, NV12 / I420, packed YUYV422 / UYVY422, GRAY8) -> 300x300 fp16 network input.
+// Resize + normalise: a frame of any resolution (packed RGB24 / BGR24, NV12 / I420, packed YUYV422 / UYVY422, GRAY8, 10-bit P010 / YUV420P10) -> 300x300 fp16 network input.
 //
 // Stands in for the first nodes of the TF graph the reference's CPU plugin runs on the full
 // resolution frame (`watsor/detection/tensorflow_cpu.py:113-115`):
@@ -33,6 +33,14 @@
 // -- integer arithmetic, bit-exact against oracle/yuv.py (no flag) and tests/pixfmt_oracle.py (which derives the table); the
 // bytes equal a host-side conversion by that formula, they are NOT pinned against a particular swscale code path (its C and SIMD
 // converters differ from each other by one LSB).  GRAY8 is R = G = B = Y unscaled, BGR24 is RGB24 with bytes 0 and 2 swapped.
+// The 10-bit 4:2:0 formats (what an HEVC Main10 stream decodes to: P010 = NV12's layout, YUV420P10 = I420's, one little-endian 16-bit word
+// per sample; P010 keeps the sample in the word's high bits -- word >> 6, the low 6 bits ignored --, YUV420P10 in its low bits -- word & 0x3ff,
+// the high 6 ignored) take the same table, the same nearest chroma sample of the 2x2 block and the full 10 bits into the matrix:
+//     C = Y10 - 4 yoff, D = U10 - 512, E = V10 - 512          (yoff: the 16 or 0 that column C of the table subtracts)
+//     R = clip8((cy C + rv E + 512) >> 10),  G = clip8((cy C + gu D + gv E + 512) >> 10),  B = clip8((cy C + bu D + 512) >> 10)
+// -- for samples whose two low bits are zero exactly the 8-bit formula on sample >> 2 ((4x + 512) >> 10 == (x + 128) >> 8), the largest
+// intermediate is near 2^20: 32-bit integers.  A 10-bit frame is 3 w h bytes, as many as RGB24: what it saves is the host's conversion, not
+// bytes.  A frame lies at any byte address, so a word is put together from two byte reads, never read as a 16-bit value.
 // The format word is the same for every pixel of a frame (blockIdx.y picks the frame): the kernels take it into a scalar register
 // once (`wz_format_word`), so the choice of the format's path is a scalar branch -- an RGB24 frame pays two compares for the other
 // formats being there -- and the coefficients are scalar values, selected where a YUV path needs them.
@@ -49,6 +57,18 @@ __device__ __forceinline__ void wz_yuv_to_rgb(int word, int Y, int U, int V, flo
     c[0] = (float)min(max((k.cy * C + k.rv * E + 128) >> 8, 0), 255);
     c[1] = (float)min(max((k.cy * C + k.gu * D + k.gv * E + 128) >> 8, 0), 255);
     c[2] = (float)min(max((k.cy * C + k.bu * D + 128) >> 8, 0), 255);
+}
+// the 10-bit sample of the little-endian word at p (any address): its high bits (P010) or its low bits (YUV420P10)
+__device__ __forceinline__ int wz_sample10(const uint8_t* __restrict__ p, bool high) {
+    const int wd = (int)p[0] | ((int)p[1] << 8);
+    return high ? wd >> 6 : wd & 0x3ff;
+}
+__device__ __forceinline__ void wz_yuv10_to_rgb(int word, int Y, int U, int V, float (&c)[3]) {
+    const WzYuvCoef k = wz_yuv_coef(word);
+    const int C = Y - 4 * k.yoff, D = U - 512, E = V - 512;
+    c[0] = (float)min(max((k.cy * C + k.rv * E + 512) >> 10, 0), 255);
+    c[1] = (float)min(max((k.cy * C + k.gu * D + k.gv * E + 512) >> 10, 0), 255);
+    c[2] = (float)min(max((k.cy * C + k.bu * D + 512) >> 10, 0), 255);
 }
 // one 4:2:2 macropixel as a little-endian dword (YUYV: Y0 U Y1 V; UYVY: U Y0 V Y1) -> the pixel `odd` (x & 1) of it
 __device__ __forceinline__ void wz_yuv422_to_rgb(int word, bool uyvy, unsigned m, int odd, float (&c)[3]) {
@@ -79,8 +99,18 @@ __device__ __forceinline__ void wz_fetch_rgb(const WzFrameDesc& f, int word, int
         wz_yuv422_to_rgb(word, fmt == WZ_FMT_UYVY422, m, x & 1, c);
         return;
     }
-    const int Y = f.rgb[(size_t)y * f.w + x];
     const size_t cw = (size_t)(f.w >> 1);
+    if (fmt == WZ_FMT_P010 || fmt == WZ_FMT_YUV420P10) {   // NV12's / I420's planes with two bytes a sample
+        const bool high = fmt == WZ_FMT_P010;
+        const uint8_t* chroma = f.rgb + (size_t)f.w * f.h * 2;
+        const int Y = wz_sample10(f.rgb + ((size_t)y * f.w + x) * 2, high);
+        const size_t at = (size_t)(y >> 1) * cw + (x >> 1);
+        const uint8_t* up = high ? chroma + at * 4 : chroma + at * 2;
+        const uint8_t* vp = high ? up + 2 : up + cw * (size_t)(f.h >> 1) * 2;
+        wz_yuv10_to_rgb(word, Y, wz_sample10(up, high), wz_sample10(vp, high), c);
+        return;
+    }
+    const int Y = f.rgb[(size_t)y * f.w + x];
     const uint8_t* chroma = f.rgb + (size_t)f.w * f.h;
     int U, V;
     if (fmt == WZ_FMT_NV12) {
@@ -101,7 +131,7 @@ __device__ __forceinline__ void wz_fetch_rgb(const WzFrameDesc& f, int word, int
 // BGR24 is the same window with the channels swapped.  4:2:2: a macropixel is 4 bytes at a multiple of 4 from the frame's start (w is
 // even), the two taps lie in one macropixel or in two adjacent ones: ONE 8-byte load from x_lo's macropixel, or a 4-byte load where
 // those 8 bytes would reach past the frame (the frame's last macropixel: x_hi is then in it as well); byte-wise where the frame's
-// address is not a multiple of 4.  GRAY8 is one byte per tap, NV12 / I420 three.
+// address is not a multiple of 4.  GRAY8 is one byte per tap, NV12 / I420 three, P010 / YUV420P10 six.
 __device__ __forceinline__ void wz_fetch_row_pair(const WzFrameDesc& f, int word, int x_lo, int x_hi, int y, float (&a)[3], float (&b)[3]) {
     const int fmt = word & WZ_FMT_BASE_MASK;
     if (fmt == WZ_FMT_RGB24 || fmt == WZ_FMT_BGR24) {
@@ -281,17 +311,20 @@ __global__ __launch_bounds__(WZ_PRE_ROWS_THREADS) void wz_k_preprocess_rows(cons
     const int fmt = word & WZ_FMT_BASE_MASK;
     const bool rgb3 = fmt == WZ_FMT_RGB24 || fmt == WZ_FMT_BGR24;
     const bool yuv422 = fmt == WZ_FMT_YUYV422 || fmt == WZ_FMT_UYVY422;
-    const bool planar = fmt == WZ_FMT_NV12 || fmt == WZ_FMT_I420;    // the formats with chroma runs of their own
-    const int rowb = rgb3 ? f.w * 3 : yuv422 ? f.w * 2 : f.w;        // bytes of an RGB / BGR, a 4:2:2, a luma / gray row
+    const bool ten = fmt >= WZ_FMT_P010;                             // P010 / YUV420P10: NV12's / I420's runs, two bytes a sample
+    const bool planar = fmt == WZ_FMT_NV12 || fmt == WZ_FMT_I420 || ten;   // the formats with chroma runs of their own
+    const bool two_planes = fmt == WZ_FMT_I420 || fmt == WZ_FMT_YUV420P10; // ... two of them: a U and a V run
+    const int rowb = rgb3 ? f.w * 3 : (yuv422 || ten) ? f.w * 2 : f.w;     // bytes of an RGB / BGR, a 4:2:2 / 10-bit luma, an 8-bit luma / gray row
     const int cw = f.w >> 1;
-    const int crowb = fmt == WZ_FMT_NV12 ? f.w : cw;                 // bytes of a chroma row (NV12: interleaved; I420: per plane)
+    // bytes of a chroma row (NV12: interleaved, w; I420: per plane, w / 2; P010: interleaved words, 2w; YUV420P10: words per plane, w)
+    const int crowb = fmt == WZ_FMT_P010 ? f.w * 2 : (fmt == WZ_FMT_NV12 || fmt == WZ_FMT_YUV420P10) ? f.w : cw;
 
     auto in_row = [&](int oy) { return half_pixel ? ((float)oy + 0.5f) * f.scale_y - 0.5f : (float)oy * f.scale_y; };
     // LDS bytes of R output rows' spans, from above: (R - 1) scale + 3 source rows, half as many + 2 chroma rows per chroma run, 32 per run
     auto need = [&](int R) {
         const int rows = (int)((float)(R - 1) * f.scale_y) + 3;
         int b = rows * rowb + 32;
-        if (planar) b += (fmt == WZ_FMT_NV12 ? 1 : 2) * (((rows >> 1) + 2) * crowb + 32);
+        if (planar) b += (two_planes ? 2 : 1) * (((rows >> 1) + 2) * crowb + 32);
         return b;
     };
     int R = 1;
@@ -313,14 +346,19 @@ __global__ __launch_bounds__(WZ_PRE_ROWS_THREADS) void wz_k_preprocess_rows(cons
     //  is rows y0 .. y1 of a frame of h rows of `rowb` >= 1 bytes -- 3w, 2w (w >= 2) or w bytes -- whose size wz_frame_bytes gives as
     //  h * rowb for the single-run formats; YUYV422 / UYVY422, GRAY8 and BGR24 have no chroma run (nb1 = nb2 = 0: no chunk of src1 / src2
     //  is ever requested).  LDS: run 0 of one output row is at most 2 rows + 31 bytes <= 3 * rowb + 32 <= 9 * max_w + 32, the RGB24
-    //  case that sizes wz_preprocess_rows_lds.)
-    const uint8_t* const chroma = f.rgb + (size_t)f.w * f.h;
+    //  case that sizes wz_preprocess_rows_lds.
+    //  The 10-bit formats: run 0 is luma rows of rowb = 2w bytes; run 1 is P010's chroma rows of 2w bytes, or YUV420P10's U rows of w
+    //  bytes with run 2 its V rows, each at least one whole row inside a frame of 3 w h bytes: the same argument.  Their LDS is NOT covered
+    //  by wz_preprocess_rows_lds -- one output row takes up to 3 * 2w + 32 and 3 chroma rows + 32 per chroma run: 12w + 64 (P010) or
+    //  12w + 96 (YUV420P10) bytes, wz_preprocess_rows_need -- so the host launches this kernel for a batch only when every 10-bit frame
+    //  of it fits the launch's LDS (wz_engine.hip: rows_fit); other batches take the per-pixel kernel.)
+    const uint8_t* const chroma = f.rgb + (size_t)f.w * f.h * (ten ? 2 : 1);
     const uint8_t* const src0 = f.rgb + (size_t)y0 * rowb;
     const uint8_t* const src1 = chroma + (size_t)cy0 * crowb;
-    const uint8_t* const src2 = chroma + (size_t)cw * (f.h >> 1) + (size_t)cy0 * crowb;   // I420: the V plane
+    const uint8_t* const src2 = chroma + (size_t)crowb * (f.h >> 1) + (size_t)cy0 * crowb;   // I420 / YUV420P10: the V plane (behind h/2 rows of U)
     const int nb0 = (y1 - y0 + 1) * rowb;
     const int nb1 = planar ? (cy1 - cy0 + 1) * crowb : 0;
-    const int nb2 = fmt == WZ_FMT_I420 ? nb1 : 0;
+    const int nb2 = two_planes ? nb1 : 0;
     const int sh0 = (int)(reinterpret_cast<uintptr_t>(src0) & 15), sh1 = (int)(reinterpret_cast<uintptr_t>(src1) & 15);
     const int sh2 = (int)(reinterpret_cast<uintptr_t>(src2) & 15);
     const int n0 = (sh0 + nb0 + 15) >> 4, n1 = nb1 ? (sh1 + nb1 + 15) >> 4 : 0, n2 = nb2 ? (sh2 + nb2 + 15) >> 4 : 0;   // 16-byte chunks
@@ -400,6 +438,21 @@ __global__ __launch_bounds__(WZ_PRE_ROWS_THREADS) void wz_k_preprocess_rows(cons
                         }
                     }
                 }
+            } else if (ten) {   // (byte reads put every word together: a run starts at any address)
+                const bool high = fmt == WZ_FMT_P010;
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const int y = q == 0 ? y_lo : y_hi;
+                    const uint8_t* const yrow = wz_pre_lds + sh0 + (y - y0) * rowb;
+                    const int crow = ((y >> 1) - cy0) * crowb;
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) {
+                        const int x = t == 0 ? x_lo : x_hi;
+                        const uint8_t* const up = wz_pre_lds + lds1 + sh1 + crow + (high ? (x >> 1) * 4 : (x >> 1) * 2);
+                        const uint8_t* const vp = high ? up + 2 : wz_pre_lds + lds2 + sh2 + crow + (x >> 1) * 2;
+                        wz_yuv10_to_rgb(word, wz_sample10(yrow + x * 2, high), wz_sample10(up, high), wz_sample10(vp, high), tap[2 * q + t]);
+                    }
+                }
             } else {
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
@@ -456,6 +509,14 @@ size_t wz_preprocess_rows_lds(int max_w) {
     size_t b = rgb > yuv ? rgb : yuv;
     if (b < 40 * 1024) b = 40 * 1024;
     return (b + 255) & ~(size_t)255;
+}
+
+// LDS bytes one output row of a 10-bit frame `w` wide needs in the row-staged kernel (its need(1): 3 luma rows of 2w bytes + 32, and per
+// chroma run 3 rows + 32): 12w + 64 as P010, 12w + 96 as YUV420P10.  wz_preprocess_rows_lds above does NOT count these formats -- it sizes every
+// engine's launch, and 8-bit workloads keep their occupancy; with its 40 KiB floor a 10-bit frame up to 3405 pixels wide fits.
+size_t wz_preprocess_rows_need(int w, int fmt) {
+    const size_t runs = (fmt & WZ_FMT_BASE_MASK) == WZ_FMT_YUV420P10 ? 3 : 2;
+    return 12 * (size_t)w + 32 * runs;
 }
 
 // the kernels' last argument: bit 0 = half-pixel centres, bits 8 ..: the row-staged kernel's LDS budget in units of 256 bytes

@@ -223,6 +223,7 @@ void wz_launch_preprocess(const WzFrameDesc* d_frames, int n, int size, half_t* 
                           WzFrameDesc* keep = nullptr, bool half_pixel = false, const WzFrameDesc* by_value = nullptr, int rows_lds = 0);
 // rows_lds > 0: the row-staged form of the kernel (one workgroup per output row, `rows_lds` bytes of LDS = wz_preprocess_rows_lds(widest frame))
 size_t wz_preprocess_rows_lds(int max_w);
+size_t wz_preprocess_rows_need(int w, int fmt);   // LDS bytes of one output row of a frame `w` wide in a 10-bit format (the host's rule: wz_engine.hip: rows_fit)
 int wz_preprocess_flags(bool half_pixel, int rows_lds);   // the resize kernels' last argument (k_preprocess.hip)
 int wz_preprocess_rows_threads();
 const void* wz_preprocess_func(bool hp, bool rows = false);   // the kernel's host-side address (to find its node in a captured graph)
@@ -388,6 +389,7 @@ void wz_launch_merge_tiles(const WzMergeFrame* frames, const int32_t* origins, c
 #define WZ_GATE_UYVY 2   // the odd bytes
 #define WZ_GATE_RGB 3    // three bytes a pixel: (77 R + 150 G + 29 B + 128) >> 8
 #define WZ_GATE_BGR 4
+#define WZ_GATE_LOW10 5  // two bytes a pixel, a little-endian word with a 10-bit sample in its low bits (YUV420P10): the luma is bits 2 .. 9
 struct WzGateTile {
     const uint8_t* src;    // the first luma-bearing byte of the rectangle's first row
     const uint16_t* ref;   // the reference grid [crows][cols], or nullptr: the tile has none (its activity is reported as 0)

@@ -125,7 +125,7 @@ struct wz_engine {
         uint32_t* h_status = nullptr;        // pinned, device-mapped: one word per frame, non-zero = the frame's rows may be short (wz_k_nms)
         uint32_t* m_status = nullptr;
         std::vector<int32_t> bound_idx;      // frame-table entries of the batch in flight (empty: not a bound batch)
-        std::vector<int32_t> bound_src;      // the last tiled or gated bound batch accepted on this lane: 1 = frame i was read in place, 0 = staged
+        std::vector<int32_t> bound_src;      // the last tiled or gated bound batch accepted on this lane (development library: the last bound batch of any kind): 1 = frame i was read in place, 0 = staged
         TileLane tile;
         GateLane gate;
         hipEvent_t done = nullptr;
@@ -209,6 +209,7 @@ int run_batch(wz_engine* e, int slot, int n);
 int stage_frame(wz_engine* e, Lane& L, int i, const uint8_t* host, uint64_t bytes, const uint8_t** where);
 const uint8_t* device_view(wz_engine* e, const uint8_t* host, uint64_t bytes);
 bool read_in_place(const wz_engine* e, int h);
+bool rows_fit(const wz_engine* e, int n, const int* w, const int* fmt);
 int sync_all(wz_engine* e);
 hipError_t lane0_fill(wz_engine* e, void* dst, int value, size_t bytes);
 // ---- wz_tiles.hip, for wz_submit_bound: a batch with a tiled or gated entry ---------------------------------------------------------

@@ -1156,10 +1156,12 @@ const char* fmt_refusal(int w, int h, int fmt) {
     if (w < 1 || h < 1) return "width and height must be positive";
     if (fmt & ~(WZ_FMT_BASE_MASK | WZ_CSP_BT709 | WZ_RANGE_FULL)) return "unknown flag bits in the format word";
     const int base = fmt & WZ_FMT_BASE_MASK;
-    if (base > WZ_FMT_BGR24) return "unknown base format";
-    const bool yuv = base == WZ_FMT_NV12 || base == WZ_FMT_I420 || base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422;
+    const bool ten = base == WZ_FMT_P010 || base == WZ_FMT_YUV420P10;   // 10-bit 4:2:0: a 16-bit word per sample
+    if (base > WZ_FMT_BGR24 && !ten) return "unknown base format";
+    const bool yuv = base == WZ_FMT_NV12 || base == WZ_FMT_I420 || base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422 || ten;
     if (!yuv && (fmt & (WZ_CSP_BT709 | WZ_RANGE_FULL))) return "WZ_CSP_BT709 / WZ_RANGE_FULL apply to the YUV formats only, not to RGB24, BGR24 or GRAY8";
     if ((base == WZ_FMT_NV12 || base == WZ_FMT_I420) && ((w | h) & 1)) return "NV12 / I420 need even sides";
+    if (ten && ((w | h) & 1)) return "P010 / YUV420P10 need even sides";
     if ((base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422) && (w & 1)) return "YUYV422 / UYVY422 need an even width";
     return nullptr;
 }
@@ -1168,6 +1170,7 @@ extern "C" uint64_t wz_frame_bytes(int w, int h, int fmt) {
     const uint64_t px = (uint64_t)w * h;
     switch (fmt & WZ_FMT_BASE_MASK) {
         case WZ_FMT_RGB24: case WZ_FMT_BGR24: return px * 3;
+        case WZ_FMT_P010: case WZ_FMT_YUV420P10: return px * 3;   // 2 bytes a sample, 1.5 samples a pixel: RGB24's size
         case WZ_FMT_NV12: case WZ_FMT_I420: return px * 3 / 2;
         case WZ_FMT_YUYV422: case WZ_FMT_UYVY422: return px * 2;
         default: return px;   // WZ_FMT_GRAY8
@@ -1203,7 +1206,7 @@ extern "C" int wz_submit_device_fmt(wz_engine_t* e, int slot, int n, const uint8
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipEventSynchronize(e->lanes[slot].done));   // the lane's previous batch has fully drained
     WZCHK(fill_desc(e, slot, n, d_rgb, w, h, fmt, cam));
-    e->lanes[slot].rows = e->pre_rows;
+    e->lanes[slot].rows = e->pre_rows && rows_fit(e, n, w, fmt);
     return run_batch(e, slot, n);
 }
 extern "C" int wz_submit_device(wz_engine_t* e, int slot, int n, const uint8_t* const* d_rgb, const int* w,
@@ -1316,6 +1319,17 @@ const uint8_t* device_view(wz_engine* e, const uint8_t* host, uint64_t bytes) {
 bool read_in_place(const wz_engine* e, int h) {
     return e->host_read == 1 || (e->host_read == 2 && h >= 2 * (int)e->hdr.input_size);
 }
+// The LDS rule of the 10-bit formats.  e->pre_rows_lds is sized by the 8-bit formats (9 bytes a pixel of width: wz_preprocess_rows_lds, which
+// sizes every launch and is left alone), one output row of a 10-bit frame needs 12 (wz_preprocess_rows_need).  A batch that holds a 10-bit
+// frame whose row does not fit -- wider than 3405 pixels with the 40 KiB floor -- may not take the row-staged kernel: all of its frames are
+// staged, none is read in place, and the batch takes the per-pixel kernel.  Every place that sets Lane::rows asks here first.
+bool rows_fit(const wz_engine* e, int n, const int* w, const int* fmt) {
+    for (int i = 0; fmt && i < n; ++i) {
+        const int base = fmt[i] & WZ_FMT_BASE_MASK;
+        if ((base == WZ_FMT_P010 || base == WZ_FMT_YUV420P10) && wz_preprocess_rows_need(w[i], fmt[i]) > (size_t)e->pre_rows_lds) return false;
+    }
+    return true;
+}
 
 int stage_frame(wz_engine* e, Lane& L, int i, const uint8_t* host, uint64_t bytes, const uint8_t** where) {
     uint8_t* dst = L.d_frames + e->frame_stride * i;
@@ -1338,6 +1352,7 @@ extern "C" int wz_submit_host_fmt(wz_engine_t* e, int slot, int n, const uint8_t
     HIPCHK(hipEventSynchronize(L.done));   // the lane's previous batch (and its reads of the staging area) drained
     if (!L.d_frames) return wz_fail(WZ_EINVAL, "wz_submit_host: lane %d has no staging area", slot);
     bool in_place = false;
+    const bool fit = rows_fit(e, n, w, fmt);
     std::vector<const uint8_t*> dptr(n);
     for (int i = 0; i < n; ++i) {
         const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
@@ -1345,7 +1360,7 @@ extern "C" int wz_submit_host_fmt(wz_engine_t* e, int slot, int n, const uint8_t
         const uint64_t bytes = wz_frame_bytes(w[i], h[i], pf);
         if (!bytes) return frame_refusal(e, "frame", i, rgb[i], w[i], h[i], pf, -1, FC_FMT);
         // pageable source: the runtime stages it (slow, synchronous); registered / pinned source: one DMA -- or no copy at all
-        const uint8_t* dv = read_in_place(e, h[i]) ? device_view(e, rgb[i], bytes) : nullptr;
+        const uint8_t* dv = fit && read_in_place(e, h[i]) ? device_view(e, rgb[i], bytes) : nullptr;
         if (dv) {
             dptr[i] = dv;
             in_place = true;
@@ -1354,7 +1369,7 @@ extern "C" int wz_submit_host_fmt(wz_engine_t* e, int slot, int n, const uint8_t
         WZCHK(stage_frame(e, L, i, rgb[i], bytes, &dptr[i]));
     }
     WZCHK(fill_desc(e, slot, n, dptr.data(), w, h, fmt, cam));
-    L.rows = e->pre_rows || in_place;
+    L.rows = fit && (e->pre_rows || in_place);
     return run_batch(e, slot, n);
 }
 
@@ -1428,18 +1443,23 @@ extern "C" int wz_submit_bound(wz_engine_t* e, int slot, int n, const int32_t* e
     bool in_place = false;
     BoundBatch b;
     bound_gather(e, n, entries, b);
+    const bool fit = rows_fit(e, n, b.w, b.fmt);
     for (int i = 0; i < n; ++i) {
         const wz_engine::BoundFrame& f = e->bound[entries[i]];
-        if (f.dev && read_in_place(e, f.h)) {
+        if (fit && f.dev && read_in_place(e, f.h)) {
             b.ptr[i] = f.dev;
             in_place = true;
             continue;
         }
         WZCHK(stage_frame(e, L, i, f.host, f.bytes, &b.ptr[i]));
     }
+#ifdef WZ_DEV_BUILD   // (wz_debug_bound_source: which leg each frame of this batch took)
+    L.bound_src.resize(n);
+    for (int i = 0; i < n; ++i) L.bound_src[i] = b.ptr[i] == e->bound[entries[i]].dev && b.ptr[i] != nullptr;
+#endif
     // (the filter of a frame's camera may have been set for another size since the table was built: fill_desc checks)
     WZCHK(fill_desc(e, slot, n, b.ptr.data(), b.w, b.h, b.fmt, b.cam));
-    L.rows = e->pre_rows || in_place;
+    L.rows = fit && (e->pre_rows || in_place);
     WZCHK(run_batch(e, slot, n));
     L.bound_idx.assign(entries, entries + n);
     return WZ_OK;
@@ -1745,7 +1765,7 @@ extern "C" int wz_stage_preprocess_fmt(wz_engine_t* e, const uint8_t* rgb, int w
     HIPCHK(hipMemcpyAsync(e->lanes[0].d_desc, e->lanes[0].h_desc, sizeof(WzFrameDesc), hipMemcpyHostToDevice, e->stream));
     const int S = (int)e->hdr.input_size;
     wz_launch_preprocess(e->lanes[0].d_desc, 1, S, e->lanes[0].tptr[input_tensor_index(e)], e->stream, input_is_pair(e), nullptr,
-                         e->hdr.resize_mode == 1, nullptr, e->pre_rows ? e->pre_rows_lds : 0);
+                         e->hdr.resize_mode == 1, nullptr, e->pre_rows && rows_fit(e, 1, &w, &fmt) ? e->pre_rows_lds : 0);
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipMemcpy(out_half, e->lanes[0].tptr[input_tensor_index(e)], tensor_frame_bytes(e, input_tensor_index(e)),
                      hipMemcpyDeviceToHost));

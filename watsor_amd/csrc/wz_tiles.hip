@@ -86,6 +86,7 @@ static const char* tile_refusal(const wz_tile_t& t, int w, int h, int fmt) {
     if ((int64_t)t.x0 + t.w > w || (int64_t)t.y0 + t.h > h) return "the rectangle leaves the frame";
     const int base = fmt & WZ_FMT_BASE_MASK;
     if ((base == WZ_FMT_NV12 || base == WZ_FMT_I420) && ((t.x0 | t.y0 | t.w | t.h) & 1)) return "NV12 / I420 need even x0, y0, w and h";
+    if ((base == WZ_FMT_P010 || base == WZ_FMT_YUV420P10) && ((t.x0 | t.y0 | t.w | t.h) & 1)) return "P010 / YUV420P10 need even x0, y0, w and h";
     if ((base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422) && ((t.x0 | t.w) & 1)) return "YUYV422 / UYVY422 need even x0 and w";
     if (!wz_frame_bytes(t.w, t.h, fmt)) return fmt_refusal(t.w, t.h, fmt);
     return nullptr;
@@ -104,6 +105,19 @@ static int tile_fits(const wz_engine* e, const char* what, int id, int w, int h,
 static void tile_planes(const uint8_t* src, int w, int h, int fmt, const wz_tile_t& t, uint8_t* dst, std::vector<WzCropPlane>& out) {
     const int base = fmt & WZ_FMT_BASE_MASK;
     const size_t W = (size_t)w, H = (size_t)h;
+    if (base == WZ_FMT_P010 || base == WZ_FMT_YUV420P10) {   // NV12's / I420's planes with two bytes a sample
+        out.push_back({src + ((size_t)t.y0 * W + t.x0) * 2, dst, w * 2, t.w * 2, t.h, 0});
+        const uint8_t* chroma = src + W * H * 2;
+        uint8_t* dc = dst + (size_t)t.w * t.h * 2;
+        if (base == WZ_FMT_P010) {   // a (U, V) pair of chroma column x0 / 2 is 4 bytes: 2 x0 bytes into its row of 2w
+            out.push_back({chroma + ((size_t)(t.y0 / 2) * W + t.x0) * 2, dc, w * 2, t.w * 2, t.h / 2, 0});
+        } else {
+            const size_t cw = W / 2, ch = H / 2, off = ((size_t)(t.y0 / 2) * cw + t.x0 / 2) * 2;
+            out.push_back({chroma + off, dc, w, t.w, t.h / 2, 0});
+            out.push_back({chroma + cw * ch * 2 + off, dc + (size_t)(t.w / 2) * (t.h / 2) * 2, w, t.w, t.h / 2, 0});
+        }
+        return;
+    }
     if (base == WZ_FMT_NV12 || base == WZ_FMT_I420) {
         out.push_back({src + (size_t)t.y0 * W + t.x0, dst, w, t.w, t.h, 0});
         const uint8_t* chroma = src + W * H;
@@ -125,7 +139,8 @@ static void tile_planes(const uint8_t* src, int w, int h, int fmt, const wz_tile
 static void gate_tile(const uint8_t* src, int w, int fmt, const wz_tile_t& t, WzGateTile& g) {
     const int base = fmt & WZ_FMT_BASE_MASK;
     const bool rgb = base == WZ_FMT_RGB24 || base == WZ_FMT_BGR24, yuy = base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422;
-    const int bpp = rgb ? 3 : yuy ? 2 : 1;   // (NV12 / I420: the luma plane is the frame's first w x h bytes)
+    const bool ten = base == WZ_FMT_P010 || base == WZ_FMT_YUV420P10;   // (the luma plane is the frame's first w x h words)
+    const int bpp = rgb ? 3 : (yuy || ten) ? 2 : 1;   // (NV12 / I420: the luma plane is the frame's first w x h bytes)
     g.src = src + ((size_t)t.y0 * (size_t)w + t.x0) * bpp;
     g.pitch = w * bpp;
     g.row_bytes = t.w * bpp;
@@ -133,8 +148,10 @@ static void gate_tile(const uint8_t* src, int w, int fmt, const wz_tile_t& t, Wz
     g.th = t.h;
     g.cols = (t.w + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
     g.crows = (t.h + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
+    // The 10-bit formats are gated on the top 8 bits of a sample, so that sums and threshold keep their 8-bit meaning: of a P010 word
+    // (sample << 6) that is its second byte -- UYVY's odd bytes --, of a YUV420P10 word bits 2 .. 9 (WZ_GATE_LOW10).
     g.mode = base == WZ_FMT_RGB24 ? WZ_GATE_RGB : base == WZ_FMT_BGR24 ? WZ_GATE_BGR : base == WZ_FMT_YUYV422 ? WZ_GATE_YUYV
-             : base == WZ_FMT_UYVY422 ? WZ_GATE_UYVY : WZ_GATE_GRAY;
+             : (base == WZ_FMT_UYVY422 || base == WZ_FMT_P010) ? WZ_GATE_UYVY : base == WZ_FMT_YUV420P10 ? WZ_GATE_LOW10 : WZ_GATE_GRAY;
 }
 
 // ---- a call, its checks, its plan
@@ -249,7 +266,7 @@ static int run_tiles(wz_engine* e, int slot, const TilePlan& y) {
     Lane& L = e->lanes[slot];
     wz_launch_crop_tiles(y.planes.data(), (int)y.planes.size(), L.stream);
     WZCHK(fill_desc(e, slot, (int)y.tptr.size(), y.tptr.data(), y.tw.data(), y.th.data(), y.tf.data(), nullptr));
-    L.rows = e->pre_rows;
+    L.rows = e->pre_rows && rows_fit(e, (int)y.tptr.size(), y.tw.data(), y.tf.data());
     return run_batch(e, slot, (int)y.tptr.size());
 }
 
@@ -741,7 +758,7 @@ extern "C" int wz_stage_tile_activity(wz_engine_t* e, const uint8_t* frame, int 
 extern "C" int wz_debug_bound_source(wz_engine_t* e, int slot, int32_t* in_place) {
     if (!e || !in_place || slot < 0 || slot >= e->n_lanes) return wz_set_error(WZ_EINVAL, "wz_debug_bound_source: bad argument");
     const Lane& L = e->lanes[slot];
-    if (L.bound_src.empty()) return wz_set_error(WZ_EINVAL, "wz_debug_bound_source: lane %d has seen no tiled or gated bound batch", slot);
+    if (L.bound_src.empty()) return wz_set_error(WZ_EINVAL, "wz_debug_bound_source: lane %d has seen no bound batch", slot);
     memcpy(in_place, L.bound_src.data(), sizeof(int32_t) * L.bound_src.size());
     return WZ_OK;
 }

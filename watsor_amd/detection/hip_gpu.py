@@ -22,17 +22,19 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from ..runtime import (CSP_BT709, FMT_BASE_MASK, FMT_GRAY8, FMT_I420, FMT_NV12, FMT_RGB24, FMT_UYVY422, FMT_YUYV422, RANGE_FULL,
-                       YUV_FORMATS, HipEngine, tile_grid)
+from ..runtime import (CSP_BT709, FMT_BASE_MASK, FMT_GRAY8, FMT_I420, FMT_NV12, FMT_P010, FMT_RGB24, FMT_UYVY422, FMT_YUV420P10,
+                       FMT_YUYV422, RANGE_FULL, TEN_BIT_FORMATS, YUV_FORMATS, HipEngine, tile_grid)
 from .._lib import WZ_MAX_TILES
 from ..share import Detection
 
 # what a decoder's `-pix_fmt` may say (watsor/stream/ffmpeg.py:78-88 reads whatever it writes; the reference's schema asks for
 # rgb24, `watsor/config/schema.py:161` -- NV12 / yuv420p frames are half the bytes and are converted on the GPU, SURVEY 8f-3;
 # yuyv422 / uyvy422 is what USB / V4L2 cameras and capture cards write, gray what IR / thermal cameras do, yuvj420p -- yuv420p with
-# full-range levels -- what MJPEG cameras decode to)
+# full-range levels -- what MJPEG cameras decode to; p010le / yuv420p10le -- 10-bit 4:2:0, a 16-bit word per sample -- what an HEVC
+# Main10 stream decodes to on a hardware / in a software decoder: as many bytes as rgb24, but no conversion on the host)
 PIXEL_FORMATS = {"rgb24": FMT_RGB24, "nv12": FMT_NV12, "yuv420p": FMT_I420, "i420": FMT_I420, "yuyv422": FMT_YUYV422,
-                 "uyvy422": FMT_UYVY422, "gray": FMT_GRAY8, "yuvj420p": FMT_I420 | RANGE_FULL}
+                 "uyvy422": FMT_UYVY422, "gray": FMT_GRAY8, "yuvj420p": FMT_I420 | RANGE_FULL,
+                 "p010le": FMT_P010, "yuv420p10le": FMT_YUV420P10}
 # how a camera's YUV frames turn into RGB (include/watsor_hip.h: the colour flags of the format word)
 COLOR_MATRICES = {"bt601": 0, "bt709": CSP_BT709}
 COLOR_RANGES = {"limited": 0, "full": RANGE_FULL}
@@ -76,7 +78,8 @@ def format_words(options: dict):
 
 def _planar_format(default: int, by_camera: dict) -> int:
     """What a one-channel buffer shaped (H*3/2, W) holds when its camera says RGB24: the one planar 4:2:0 format that is configured
-    (NV12 if none is).  Only NV12 / I420 have that shape -- a configured gray or 4:2:2 camera is never the answer."""
+    (NV12 if none is).  Only NV12 / I420 have that shape -- a configured gray or 4:2:2 camera is never the answer, and neither is a
+    10-bit one (p010le / yuv420p10le are taken by configuration only)."""
     return next((f for f in [default] + list(by_camera.values()) if (f & FMT_BASE_MASK) in (FMT_NV12, FMT_I420)), FMT_NV12)
 
 
@@ -200,10 +203,12 @@ class HipObjectDetector:
         """`options` (third positional argument, what `create_object_detectors` passes in `detector_args`):
         dict(max_batch=, max_width=, max_height=) -- the factory derives the frame size from the cameras' frame buffers;
         the keyword forms and the WATSOR_HIP_MAX_* environment variables are the fallbacks.
-        `options["pixel_format"]`: "rgb24" (default) | "nv12" | "yuv420p" | "yuvj420p" | "yuyv422" | "uyvy422" | "gray", or
-        {camera name: one of these} -- what the cameras' decoders write into their frame buffers.  An NV12 / yuv420p frame is handed
-        over as the (H*3/2, W) uint8 array of its bytes (that is its `image_shape`), a yuyv422 / uyvy422 frame as (H, W, 2) or
-        (H, 2W), a gray frame as (H, W) or (H, W, 1).
+        `options["pixel_format"]`: "rgb24" (default) | "nv12" | "yuv420p" | "yuvj420p" | "yuyv422" | "uyvy422" | "gray" | "p010le" |
+        "yuv420p10le", or {camera name: one of these} -- what the cameras' decoders write into their frame buffers.  An NV12 / yuv420p
+        frame is handed over as the (H*3/2, W) uint8 array of its bytes (that is its `image_shape`), a yuyv422 / uyvy422 frame as
+        (H, W, 2) or (H, 2W), a gray frame as (H, W) or (H, W, 1), a 10-bit p010le / yuv420p10le frame (a 16-bit word per sample: as many
+        bytes as rgb24 -- what it saves is swscale's conversion on the host, not bytes) as (H*3/2, W) uint16 or as its bytes, (H*3/2, W, 2)
+        or (H*3/2, 2W) uint8.
         `options["color_matrix"]`: "bt601" (default) | "bt709", `options["color_range"]`: "limited" (default) | "full", each a single
         value or {camera name: value} -- how the YUV formats are converted (an HD stream tagged bt709; a full-range MJPEG camera);
         "yuvj420p" is "yuv420p" with the full range.
@@ -432,6 +437,14 @@ class HipObjectDetector:
                 if base in (FMT_NV12, FMT_I420):                     # (H * 3 / 2, W) bytes of a W x H picture
                     if channels != 1 or h % 3 or w % 2 or (h // 3 * 2) % 2:
                         raise ValueError("camera %r: an NV12 / I420 frame buffer must be (H*3/2, W, 1) with even H and W" % (name,))
+                    h = h // 3 * 2
+                elif base in TEN_BIT_FORMATS:                        # (H * 3 / 2, W, 2) or (H * 3 / 2, 2W, 1) bytes: a 16-bit word per sample
+                    if channels == 1 and w % 4 == 0:
+                        w //= 2
+                    elif channels != 2:
+                        w = 1                                        # (refused below)
+                    if h % 3 or w % 2 or (h // 3 * 2) % 2:
+                        raise ValueError("camera %r: a P010 / YUV420P10 frame buffer must be (H*3/2, W, 2) or (H*3/2, 2W, 1) with even H and W" % (name,))
                     h = h // 3 * 2
                 elif base in (FMT_YUYV422, FMT_UYVY422):             # (H, W, 2), or (H, 2W, 1)
                     if channels == 1 and w % 4 == 0:

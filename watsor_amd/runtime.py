@@ -19,10 +19,14 @@ ROW_DTYPE = np.dtype([("label", "<i4"), ("zones", "<i4", (10,)), ("_pad", "<i4")
 assert ROW_DTYPE.itemsize == C.sizeof(Detection) == 72
 FMT_RGB24, FMT_NV12, FMT_I420 = _lib.WZ_FMT_RGB24, _lib.WZ_FMT_NV12, _lib.WZ_FMT_I420   # pixel formats of a frame (include/watsor_hip.h)
 FMT_YUYV422, FMT_UYVY422, FMT_GRAY8, FMT_BGR24 = _lib.WZ_FMT_YUYV422, _lib.WZ_FMT_UYVY422, _lib.WZ_FMT_GRAY8, _lib.WZ_FMT_BGR24
-# a frame's format WORD is one of the above or'ed with colour flags (the four YUV formats only): BT.709 matrix instead of BT.601,
+# 10-bit 4:2:0, a little-endian 16-bit word per sample: P010 (ffmpeg's p010le: the sample in the word's high bits) and YUV420P10
+# (yuv420p10le: in its low bits).  3*W*H bytes, as many as RGB24: what they save is the host's conversion, not bytes.
+FMT_P010, FMT_YUV420P10 = _lib.WZ_FMT_P010, _lib.WZ_FMT_YUV420P10
+TEN_BIT_FORMATS = (FMT_P010, FMT_YUV420P10)
+# a frame's format WORD is one of the above or'ed with colour flags (the YUV formats only): BT.709 matrix instead of BT.601,
 # full range (ffmpeg's yuvj*) instead of limited
 CSP_BT709, RANGE_FULL, FMT_BASE_MASK = _lib.WZ_CSP_BT709, _lib.WZ_RANGE_FULL, _lib.WZ_FMT_BASE_MASK
-YUV_FORMATS = (FMT_NV12, FMT_I420, FMT_YUYV422, FMT_UYVY422)
+YUV_FORMATS = (FMT_NV12, FMT_I420, FMT_YUYV422, FMT_UYVY422, FMT_P010, FMT_YUV420P10)
 
 
 def device_count() -> int:
@@ -176,12 +180,14 @@ class HipEngine:
         """(width, height) of a frame array.  `fmt` is a format word: a base format, for the YUV ones or'ed with CSP_BT709 / RANGE_FULL.
         RGB24 / BGR24: (H,W,3) uint8.  NV12 / I420: the usual planar view (H*3/2, W) [or (H*3/2, W, 1)] uint8 -- H rows of luma, then
         H/2 rows holding the subsampled chroma (the bytes a decoder writes with `-pix_fmt nv12` / `yuv420p`).  YUYV422 / UYVY422:
-        (H, W, 2) or (H, 2W), W even.  GRAY8: (H, W) or (H, W, 1).  Raises ValueError for anything else, and for a format word the
+        (H, W, 2) or (H, 2W), W even.  GRAY8: (H, W) or (H, W, 1).  P010 / YUV420P10 (10-bit, a 16-bit word per sample): the planar view
+        as uint16 (H*3/2, W) [or (H*3/2, W, 1)], or its bytes as uint8 (H*3/2, W, 2), (H*3/2, 2W) [or (H*3/2, 2W, 1): a uint8 frame buffer
+        of the reference]; uint16 arrays are these two formats' only.  Raises ValueError for anything else, and for a format word the
         library refuses (unknown bits, a colour flag on a format that is not YUV)."""
-        if f.dtype != np.uint8:
-            raise ValueError("frames are uint8 arrays")
         fmt = int(fmt)
         flags, fmt = fmt & ~FMT_BASE_MASK, fmt & FMT_BASE_MASK
+        if f.dtype != np.uint8 and not (f.dtype == np.uint16 and fmt in TEN_BIT_FORMATS):
+            raise ValueError("frames are uint8 arrays (P010 / YUV420P10 frames: uint8 or uint16)")
         if flags & ~(CSP_BT709 | RANGE_FULL) or fmt < 0:
             raise ValueError("unknown flag bits in pixel format word 0x%x" % (flags | fmt,))
         if flags and fmt not in YUV_FORMATS:
@@ -202,6 +208,20 @@ class HipEngine:
             if f.ndim == 2 and f.shape[1] % 4 == 0:
                 return f.shape[1] // 2, f.shape[0]
             raise ValueError("a YUYV422 / UYVY422 frame must be (H,W,2) or (H,2W) uint8 with even W")
+        if fmt in TEN_BIT_FORMATS:
+            if f.ndim == 3 and f.shape[2] == 1:
+                f = f[:, :, 0]
+            if f.dtype == np.uint16 and f.ndim == 2:
+                rows, w = f.shape
+            elif f.dtype == np.uint8 and f.ndim == 3 and f.shape[2] == 2:
+                rows, w = f.shape[:2]
+            elif f.dtype == np.uint8 and f.ndim == 2 and f.shape[1] % 2 == 0:
+                rows, w = f.shape[0], f.shape[1] // 2
+            else:
+                rows, w = 0, 0
+            if w < 1 or rows < 1 or rows % 3 or (rows // 3 * 2) % 2 or w % 2:
+                raise ValueError("a P010 / YUV420P10 frame must be (H*3/2, W) uint16, or (H*3/2, W, 2) or (H*3/2, 2W) uint8, with even H and W")
+            return w, rows // 3 * 2
         if fmt == FMT_GRAY8:
             if f.ndim == 2 or (f.ndim == 3 and f.shape[2] == 1):
                 return f.shape[1], f.shape[0]
@@ -584,7 +604,7 @@ class HipEngine:
     def stage_preprocess(self, frame: np.ndarray, fmt: int = FMT_RGB24) -> np.ndarray:
         """(S,S,4) float16; for a pair input tensor (S,S,8): hi (r,g,b,0) then lo (r,g,b,0)."""
         self._dev_only("stage_preprocess()")
-        frame = np.ascontiguousarray(frame, np.uint8)
+        frame = np.ascontiguousarray(frame) if frame.dtype == np.uint16 else np.ascontiguousarray(frame, np.uint8)
         w, h = self.frame_geometry(frame, fmt)
         S = self.input_size
         out = np.empty((S, S, 8 if self.tensor_is_pair(0) else 4), np.float16)
