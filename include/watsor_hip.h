@@ -369,6 +369,18 @@ int wz_profile_stages(wz_engine_t* e, int n, const uint8_t* const* d_rgb, const 
 
 /* diagnostics: 16 words per frame written by the NMS kernel of lane 0 (phase timestamps at 100 MHz, counts) */
 int wz_debug_nms(wz_engine_t* e, int n, uint64_t* out);
+/* What the post-processing of the batch last run on lane `slot` left in device memory, read back after that batch was collected; no
+ * kernel is launched.  n = frames of that batch (1 .. max_batch); any output pointer may be null.
+ *   box_enc [n][A][4], logits [n][A][C]    the lane's head outputs
+ *   boxes [n][T][4], scores [n][T], classes [n][T], num [n]    the det_* arrays of the lane's NMS kernel (T = max_total)
+ *   dbg [n][16]    the lane's block of wz_debug_nms words: 8 = candidates of the first band, 9 = rows kept after it, 10 = candidates
+ *                  walked in all, 14 = entries found in the candidate bit map (0: the first band was scanned), 15 = the first band's
+ *                  lower bin as walked (low 32 bits), the hint on entry (bits 32 .. 47) and whether the exact serial walk of a crowded
+ *                  bin ran (bit 48); the rest are timestamps
+ *  Engines with max_total other than 100 are refused (the arrays are laid out [n][T]).
+ *   flags [2]      {decode_fused, cands_listed} of the launches of that batch (0, 0 while the lane has run stage-level calls only) */
+int wz_debug_post_lane(wz_engine_t* e, int slot, int n, float* box_enc, float* logits, float* boxes, float* scores,
+                       int32_t* classes, int32_t* num, uint64_t* dbg, int32_t* flags);
 /* Engines created with WZ_MB_DEBUG=1 in the environment: phase timestamps (100 MHz) of the first and the last
  * workgroup of every fused inverted-residual block, out[n_ops][16]; groups[n_ops] = channel groups launched. */
 int wz_debug_mbconv(wz_engine_t* e, uint64_t* out, int32_t* groups);
@@ -398,6 +410,11 @@ int wz_stage_read_tensor(wz_engine_t* e, int idx, int frame, uint16_t* out_half)
  * boxes [n][100][4] (ymin,xmin,ymax,xmax), scores [n][100], classes [n][100] (1-based), num [n] */
 int wz_stage_postprocess(wz_engine_t* e, int n, const float* box_enc, const float* logits, float* boxes,
                          float* scores, int32_t* classes, int32_t* num);
+/* The post-processing of a real batch on caller-provided head outputs, on lane 0: the values enter as the partial sums of the grouped
+ * head reduce (one K slice, zero bias: they come out bit for bit), which stores them, decodes the boxes and marks the candidates against
+ * the lane's hint; the NMS kernel then reads its first band from that bit map and writes rows [n][100] for frames of size w x h -- the
+ * launches of wz_submit_* behind the head convolutions.  wz_debug_post_lane(e, 0, n, ...) reads back what they left. */
+int wz_stage_post_production(wz_engine_t* e, int n, const float* box_enc, const float* logits, int w, int h, wz_detection_t* rows);
 /* row fill (tensorflow_cpu.py:79-90) for caller-provided detections of one frame of size w x h */
 int wz_stage_rows(wz_engine_t* e, int w, int h, const float* boxes, const float* scores,
                   const int32_t* classes, wz_detection_t* rows);

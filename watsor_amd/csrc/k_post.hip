@@ -836,10 +836,12 @@ __global__ __launch_bounds__(NMS_THREADS) void wz_k_nms(WzPostBuffers b, WzPostC
     NMS_STAMP(1);
     int hi_bin = WZ_HIST_BINS;
     int lo_bin = min((int)b.hint[f], WZ_HIST_BINS - 1);
+    const int hint_in = lo_bin;                        // (diagnostics: dbg slot 15)
     int reach = 4;                                     // bins the next band extends below the current one
     uint32_t first_cnt = 0;
     int first_lo = lo_bin;
     bool first = true;
+    uint32_t serial_ran = 0;                           // (diagnostics: dbg slot 15, bit 48)
     for (;;) {
         uint32_t cnt;
         if (first && listed) {
@@ -904,10 +906,11 @@ __global__ __launch_bounds__(NMS_THREADS) void wz_k_nms(WzPostBuffers b, WzPostC
             first_lo = lo_bin;
             NMS_STAMP(2);
         }
-        if (cnt > WZ_CAND_CAP)                           // one bin holds more than the list: exact serial walk
+        if (cnt > WZ_CAND_CAP) {                         // one bin holds more than the list: exact serial walk
+            serial_ran = 1u;
             kept = wz_nms_band_serial(S, b, k, f, kept, (unsigned long long)((uint32_t)lo_bin << 20) << 32,
                                       (unsigned long long)((uint32_t)hi_bin << 20) << 32);
-        else if (cnt > 0)
+        } else if (cnt > 0)
             kept = wz_nms_band<CLIP, COUNT>(S, b, k, f, (int)cnt, kept);
         processed += cnt;
         if (first) { NMS_STAMP(3); if (tid == 0) { b.dbg[(size_t)f * 16 + 8] = cnt; b.dbg[(size_t)f * 16 + 9] = kept; } }
@@ -980,7 +983,15 @@ __global__ __launch_bounds__(NMS_THREADS) void wz_k_nms(WzPostBuffers b, WzPostC
                     rows + (size_t)f * WZ_MAX_DETECTIONS + tid, pass + (size_t)f * WZ_MAX_DETECTIONS + tid);
     }
     NMS_STAMP(4);
-    if (tid == 0) b.dbg[(size_t)f * 16 + 10] = processed;
+    if (tid == 0) {
+        b.dbg[(size_t)f * 16 + 10] = processed;
+        // the two slots no stamp uses: 14 = entries found in the bit map (0: the first band was scanned; S->pad[0] is written by the listed
+        // branch alone), 15 = the first band's lower edge as walked (low word), the hint on entry (bits 32 .. 47) and, bit 48, whether
+        // wz_nms_band_serial walked a bin
+        b.dbg[(size_t)f * 16 + 14] = listed ? (unsigned long long)(uint32_t)S->pad[0] : 0ull;
+        b.dbg[(size_t)f * 16 + 15] = (unsigned long long)(uint32_t)first_lo | ((unsigned long long)(uint32_t)hint_in << 32) |
+                                     ((unsigned long long)serial_ran << 48);
+    }
 #if WZ_LANE_STAMPS
     if (b.stamps_host && tid == 0) b.stamps_host[2 * (b.stamps_n + f) + 1] = wall_clock64();
 #endif

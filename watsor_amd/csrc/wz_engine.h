@@ -109,6 +109,7 @@ struct wz_engine {
         int launch_failed = 0;               // op index + 1 of a block no kernel took at launch time (enqueue_network), else 0
         bool decode_fused = false;           // set by enqueue_network: the grouped head reduce decoded the boxes
         bool cands_listed = false;           // ... and listed the candidates of the NMS kernel's first band
+        std::map<int, int> post_modes;       // development library: graph key -> decode_fused | cands_listed << 1 of the batch enqueued or captured under it
         uint8_t* d_frames = nullptr;         // staging for host frames of this lane [max_batch][frame_stride] (lazy)
         std::map<int, int> graph_nodes;      // batch size -> nodes of the captured graph (kernels + the descriptor copy)
         WzPostBuffers post;

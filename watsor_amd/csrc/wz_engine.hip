@@ -514,6 +514,9 @@ static void enqueue_batch(wz_engine* e, Lane& L, int n, StageTimer* t, int inner
     if (t) t->mark();
     enqueue_network(e, L, n, t);
     wz_launch_repeat = 1;
+#ifdef WZ_DEV_BUILD
+    L.post_modes[n | (L.rows ? 1 << 16 : 0)] = (L.decode_fused ? 1 : 0) | (L.cands_listed ? 2 : 0);   // (wz_debug_post_lane: a replayed graph keeps what it captured)
+#endif
     enqueue_post(e, L, true, n, t, L.decode_fused, L.cands_listed);
 }
 
@@ -1615,6 +1618,29 @@ extern "C" int wz_debug_nms(wz_engine_t* e, int n, uint64_t* out) {
     return WZ_OK;
 }
 
+extern "C" int wz_debug_post_lane(wz_engine_t* e, int slot, int n, float* box_enc, float* logits, float* boxes, float* scores,
+                                  int32_t* classes, int32_t* num, uint64_t* dbg, int32_t* flags) {
+    if (!e || slot < 0 || slot >= e->n_lanes || n < 1 || n > e->max_batch) return wz_fail(WZ_EINVAL, "wz_debug_post_lane: bad argument");
+    HIPCHK(hipSetDevice(e->device));
+    const Lane& L = e->lanes[slot];
+    HIPCHK(hipStreamSynchronize(L.stream));
+    const size_t A = e->hdr.num_anchors, C = e->hdr.num_classes, T = e->hdr.max_total;
+    if (T != WZ_MAX_DETECTIONS) return wz_fail(WZ_EINVAL, "wz_debug_post_lane: max_total %zu, expected %d", T, WZ_MAX_DETECTIONS);
+    if (box_enc) HIPCHK(hipMemcpy(box_enc, L.d_box_enc, n * A * 16, hipMemcpyDeviceToHost));
+    if (logits) HIPCHK(hipMemcpy(logits, L.d_logits, n * A * C * 4, hipMemcpyDeviceToHost));
+    if (boxes) HIPCHK(hipMemcpy(boxes, L.post.det_boxes, n * T * 16, hipMemcpyDeviceToHost));
+    if (scores) HIPCHK(hipMemcpy(scores, L.post.det_scores, n * T * 4, hipMemcpyDeviceToHost));
+    if (classes) HIPCHK(hipMemcpy(classes, L.post.det_classes, n * T * 4, hipMemcpyDeviceToHost));
+    if (num) HIPCHK(hipMemcpy(num, L.post.det_num, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (dbg) HIPCHK(hipMemcpy(dbg, L.post.dbg, (size_t)n * 16 * 8, hipMemcpyDeviceToHost));
+    if (flags) {   // of the batch last run: the launches of its graph key, whether they were issued one by one or replayed
+        const auto it = L.post_modes.find(L.key);   // (no batch yet, only stage-level calls: 0, 0)
+        flags[0] = it == L.post_modes.end() ? 0 : it->second & 1;
+        flags[1] = it == L.post_modes.end() ? 0 : (it->second >> 1) & 1;
+    }
+    return WZ_OK;
+}
+
 extern "C" int wz_debug_mbconv(wz_engine_t* e, uint64_t* out, int32_t* groups) {
     if (!e || !out || !e->d_mbdbg) return wz_fail(WZ_EINVAL, "wz_debug_mbconv: create the engine with WZ_MB_DEBUG=1");
     HIPCHK(hipSetDevice(e->device));
@@ -1821,6 +1847,90 @@ extern "C" int wz_stage_postprocess(wz_engine_t* e, int n, const float* box_enc,
     if (classes) HIPCHK(hipMemcpy(classes, e->lanes[0].post.det_classes, n * T * 4, hipMemcpyDeviceToHost));
     if (num) HIPCHK(hipMemcpy(num, e->lanes[0].post.det_num, n * 4, hipMemcpyDeviceToHost));
     return WZ_OK;
+}
+
+// The post-processing a real batch runs, on caller-provided head outputs: everything behind the head convolutions, by the launches
+// of enqueue_batch.  The given values go in as the single K slice of every head's partial sums (zero bias: 0 + x + 0 is x, bit for
+// bit), the grouped reduce finishes them -- stores them, decodes the boxes, marks the candidates against lane 0's hint_logit -- and
+// the NMS kernel reads its first band from the bit map and writes the rows.
+extern "C" int wz_stage_post_production(wz_engine_t* e, int n, const float* box_enc, const float* logits, int w, int h,
+                                        wz_detection_t* rows) {
+    if (!e || !box_enc || !logits || !rows) return wz_fail(WZ_EINVAL, "wz_stage_post_production: null argument");
+    if (n < 1 || n > e->max_batch) return wz_fail(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
+    if (e->hdr.max_total != WZ_MAX_DETECTIONS) return wz_fail(WZ_EINVAL, "wz_stage_post_production: max_total %d, expected %d", (int)e->hdr.max_total, WZ_MAX_DETECTIONS);
+    HIPCHK(hipSetDevice(e->device));
+    Lane& L = e->lanes[0];
+    HIPCHK(hipStreamSynchronize(L.stream));
+    const size_t A = e->hdr.num_anchors, C = e->hdr.num_classes;
+    WzReduceGroup g;
+    memset(&g, 0, sizeof(g));
+    std::vector<float> host;
+    std::vector<size_t> offs;
+    size_t covered = 0;
+    for (int i = 0; i < (int)e->hdr.n_ops; ++i) {
+        const WzOpDesc& op = e->ops[i];
+        if (op.out_mode == WZ_OUT_ACT) continue;
+        const int apl = op.anchors_per_loc, hw = op.hout * op.wout;
+        if (op.out_mode != WZ_OUT_HEAD || g.n >= WZ_REDUCE_GROUP_MAX || op.n_box != apl * 4 || op.cout != apl * (4 + (int)C) ||
+            op.n_pad < op.cout || (size_t)op.n_pad * 4 > 4096 || (size_t)op.anchor_off + (size_t)hw * apl > A)
+            return wz_fail(WZ_EINVAL, "wz_stage_post_production: op %d (%s) is no [box | class] head this entry can feed", i, op.name);
+        WzConvArgs a;
+        memset(&a, 0, sizeof(a));
+        a.bias = reinterpret_cast<const float*>(e->d_zeros);   // 4 KiB of zeros: n_pad floats at most (checked above)
+        a.M = n * hw;
+        a.hout = op.hout; a.wout = op.wout; a.cout = op.cout; a.n_pad = op.n_pad;
+        a.act = op.act; a.out_mode = op.out_mode;
+        a.splitk = 1;
+        a.out = L.d_box_enc;
+        a.out_batch_stride = (int64_t)A * 4;
+        a.out_off = (int64_t)op.anchor_off * 4;
+        a.out2 = L.d_logits;
+        a.out2_batch_stride = (int64_t)A * C;
+        a.out2_off = (int64_t)op.anchor_off * C;
+        a.n_box = op.n_box;
+        offs.push_back(host.size());
+        host.resize(host.size() + (size_t)a.M * a.n_pad, 0.0f);
+        float* part = host.data() + offs.back();
+        for (int b = 0; b < n; ++b)
+            for (int pix = 0; pix < hw; ++pix) {
+                float* row = part + ((size_t)b * hw + pix) * a.n_pad;
+                const size_t an0 = (size_t)b * A + op.anchor_off + (size_t)pix * apl;
+                memcpy(row, box_enc + an0 * 4, sizeof(float) * apl * 4);
+                memcpy(row + apl * 4, logits + an0 * C, sizeof(float) * apl * C);
+            }
+        wz_reduce_group_add(g, a, nullptr);
+        covered += (size_t)hw * apl;
+    }
+    if (g.n == 0 || covered != A) return wz_fail(WZ_EINVAL, "wz_stage_post_production: the heads cover %zu of %zu anchors", covered, A);
+    float* d_part = nullptr;
+    HIPCHK(hipMalloc((void**)&d_part, host.size() * sizeof(float)));
+    auto done = [&](int rc) { (void)hipFree(d_part); return rc; };
+    if (hipMemcpy(d_part, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return done(wz_fail(WZ_EHIP, "wz_stage_post_production: upload"));
+    for (int i = 0; i < g.n; ++i) g.ws[i] = d_part + offs[i];
+    g.decode = 1;
+    g.list = 1;
+    g.cbits_words = (int)((A * C + 31) >> 5);
+    g.hint_logit = L.post.hint_logit;
+    g.cbits = L.post.cbits;
+    g.pc = e->pc;
+    g.anchors = L.post.anchors;
+    g.boxes = L.post.boxes;
+    g.valid = L.post.valid;
+    for (int i = 0; i < n; ++i) {
+        WzFrameDesc& d = L.h_desc[i];
+        memset(&d, 0, sizeof(d));
+        d.w = w;
+        d.h = h;
+        d.cam = -1;
+    }
+    if (hipMemcpyAsync(L.d_desc, L.h_desc, sizeof(WzFrameDesc) * n, hipMemcpyHostToDevice, L.stream) != hipSuccess) return done(wz_fail(WZ_EHIP, "wz_stage_post_production: descriptors"));
+    wz_launch_splitk_reduce_group(g, L.stream);
+    enqueue_post(e, L, true, n, nullptr, true, true);
+    L.key = n;
+    L.post_modes[L.key] = 3;   // (wz_debug_post_lane: these launches decoded in the reduce and listed the candidates)
+    if (hipStreamSynchronize(L.stream) != hipSuccess || hipGetLastError() != hipSuccess) return done(wz_fail(WZ_EHIP, "wz_stage_post_production: launch"));
+    memcpy(rows, L.h_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS * n);
+    return done(WZ_OK);
 }
 
 extern "C" int wz_stage_rows(wz_engine_t* e, int w, int h, const float* boxes, const float* scores,

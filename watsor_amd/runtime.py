@@ -651,6 +651,41 @@ class HipEngine:
             C.c_void_p(scores.ctypes.data), C.c_void_p(classes.ctypes.data), C.c_void_p(num.ctypes.data)))
         return boxes, scores, classes, num
 
+    def stage_post_lane(self, slot: int, n: int) -> dict:
+        """What the post-processing of the batch of `n` frames last run -- and collected -- on lane `slot` left in device memory
+        (include/watsor_hip.h: wz_debug_post_lane; no kernel is launched): box_enc [n,A,4], logits [n,A,C], boxes [n,100,4],
+        scores [n,100], classes [n,100], num [n], dbg uint64 [n,16] and the two flags decode_fused, cands_listed.  The counts among
+        the dbg words, unpacked: first_cnt (slot 8), first_kept (9), processed (10), listed (14), first_lo, hint_in and serial -- the
+        exact serial walk of a crowded bin ran -- (15).  Engines with max_total other than 100 are refused."""
+        self._dev_only("stage_post_lane()")
+        A, Cn = self.num_anchors, self.num_classes
+        out = dict(box_enc=np.empty((n, A, 4), np.float32), logits=np.empty((n, A, Cn), np.float32),
+                   boxes=np.empty((n, MAX_DETECTIONS, 4), np.float32), scores=np.empty((n, MAX_DETECTIONS), np.float32),
+                   classes=np.empty((n, MAX_DETECTIONS), np.int32), num=np.empty((n,), np.int32), dbg=np.zeros((n, 16), np.uint64))
+        flags = (C.c_int32 * 2)()
+        self._ck(self._lib.wz_debug_post_lane(self._h, int(slot), int(n), *[C.c_void_p(out[k].ctypes.data) for k in
+                                              ("box_enc", "logits", "boxes", "scores", "classes", "num", "dbg")], C.byref(flags)))
+        d = out["dbg"]
+        out.update(decode_fused=bool(flags[0]), cands_listed=bool(flags[1]),
+                   first_cnt=d[:, 8].astype(np.int64), first_kept=d[:, 9].astype(np.int64), processed=d[:, 10].astype(np.int64),
+                   listed=d[:, 14].astype(np.int64), first_lo=(d[:, 15] & np.uint64(0xFFFFFFFF)).astype(np.int64),
+                   hint_in=((d[:, 15] >> np.uint64(32)) & np.uint64(0xFFFF)).astype(np.int64),
+                   serial=((d[:, 15] >> np.uint64(48)) & np.uint64(1)).astype(bool))
+        return out
+
+    def stage_post_production(self, box_enc: np.ndarray, logits: np.ndarray, width: int, height: int) -> np.ndarray:
+        """The post-processing of a real batch on caller-provided head outputs [n,A,4], [n,A,C], on lane 0 (include/watsor_hip.h:
+        wz_stage_post_production): rows ROW_DTYPE [n,100] of frames width x height; `stage_post_lane(0, n)` reads back the rest."""
+        self._dev_only("stage_post_production()")
+        be = np.ascontiguousarray(box_enc, np.float32)
+        lg = np.ascontiguousarray(logits, np.float32)
+        n = be.shape[0]
+        assert be.shape == (n, self.num_anchors, 4) and lg.shape == (n, self.num_anchors, self.num_classes)
+        rows = np.zeros((n, MAX_DETECTIONS), ROW_DTYPE)
+        self._ck(self._lib.wz_stage_post_production(self._h, n, C.c_void_p(be.ctypes.data), C.c_void_p(lg.ctypes.data), int(width),
+                                                    int(height), C.c_void_p(rows.ctypes.data)))
+        return rows
+
     def stage_crop_tile(self, frame: np.ndarray, tile, fmt: int = FMT_RGB24) -> np.ndarray:
         """The bytes of rectangle `tile` = (x0, y0, w, h) of `frame` as the crop kernel writes them (a flat uint8 array).  The frame
         is read where it lies: a view at an odd address reaches the kernel at an odd address."""
