@@ -59,8 +59,9 @@ def grids_of(frame, w, h, fmt, rects):
 
 
 # ---- 1. the activity kernel -----------------------------------------------------------------------------------------------------------
-def check_activity(eng, frame, w, h, fmt, rect, seed):
-    want = go.cell_sums(frame, w, h, fmt, rect)
+def check_activity(eng, frame, w, h, fmt, rect, seed, thrs=(0, 3), oracle=None):
+    """oracle: (frame, format word) the oracle sums instead -- for a 10-bit frame, the 8-bit frame of its samples' top eight bits"""
+    want = go.cell_sums(frame, w, h, fmt, rect) if oracle is None else go.cell_sums(oracle[0], w, h, oracle[1], rect)
     got, changed = eng.stage_tile_activity(frame, rect, fmt)
     assert got.dtype == np.uint16 and got.shape == want.shape and got.tobytes() == want.tobytes(), (fmt, rect)
     assert changed == 0
@@ -68,7 +69,7 @@ def check_activity(eng, frame, w, h, fmt, rect, seed):
     rng = np.random.default_rng(seed)
     ref = want.astype(np.int64) + rng.integers(-4, 5, want.shape) * go.cell_pixels(rect) + rng.integers(-1, 2, want.shape)
     ref = np.clip(ref, 0, 65535).astype(np.uint16)
-    for thr in (0, 3):
+    for thr in thrs:
         got, changed = eng.stage_tile_activity(frame, rect, fmt, ref=ref, pixel_thr=thr)
         assert got.tobytes() == want.tobytes(), (fmt, rect, thr)
         assert changed == go.activity(want, ref, rect, thr), (fmt, rect, thr)
