@@ -122,47 +122,7 @@ void wz_launch_dw(const half_t* in, const half_t* w, const float* bias, half_t* 
 // implicit-GEMM convolution on MFMA.  Workgroup = 4 waves; wave = (MT*16 pixels) x (NT*16 channels).
 // --------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ void wz_epilogue4(const WzConvArgs& a, int m, int n4, float4_t v) {
-    // v = 4 consecutive output channels n4..n4+3 of output pixel m (bias not yet added)
-    if (m >= a.M || n4 >= a.cout) return;
-    const float4_t bv = *reinterpret_cast<const float4_t*>(a.bias + n4);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        float x = v[r] + bv[r];
-        if (a.act == WZ_ACT_RELU6) x = fminf(fmaxf(x, 0.0f), 6.0f);
-        v[r] = x;
-    }
-    if (a.out_mode == WZ_OUT_ACT) {
-        const size_t o = (size_t)m * a.cout + n4;
-        if (a.res) {
-            const half4_t rv = *reinterpret_cast<const half4_t*>(a.res + o);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] += (float)rv[r];
-        }
-        half4_t h = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
-        // (a channel slice of a wider tensor: an Inception branch writing its part of the module's concat)
-        const size_t os = a.out_cstride ? (size_t)m * a.out_cstride + a.out_coff + n4 : o;
-        *reinterpret_cast<half4_t*>(reinterpret_cast<half_t*>(a.out) + os) = h;
-    } else {
-        const int hw = a.hout * a.wout;
-        const int b = m / hw, pix = m - b * hw;
-        float* o;
-        int cols, n0;
-        if (a.out_mode == WZ_OUT_HEAD && n4 >= a.n_box) {   // n_box is a multiple of 4: no group straddles
-            cols = a.cout - a.n_box;
-            n0 = n4 - a.n_box;
-            o = a.out2 + (size_t)b * a.out2_batch_stride + a.out2_off;
-        } else {
-            cols = (a.out_mode == WZ_OUT_HEAD) ? a.n_box : a.cout;
-            n0 = n4;
-            o = reinterpret_cast<float*>(a.out) + (size_t)b * a.out_batch_stride + a.out_off;
-        }
-        o += (size_t)pix * cols + n0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (n0 + r < cols) o[r] = v[r];
-    }
-}
+// (wz_epilogue4 -- bias, ReLU6, residual, the one fp16 rounding, the head scatter -- lives in wz_common.h: k_gemm_1x1.hip ends in it as well)
 
 // The reductions of several convolutions in one launch: a workgroup finds its entry from the prefix table, then does
 // exactly what wz_k_splitk_reduce does (same order over the splits: bit-identical results).
@@ -650,9 +610,14 @@ bool wz_conv_ws_applies(const WzConvArgs& a) {
     return on && a.out_mode == WZ_OUT_ACT && a.M <= 1024 && a.kchunks >= 8 && a.n_pad % 32 == 0;
 }
 void wz_launch_conv_ws(const WzConvArgs& a, hipStream_t s) {
-    // Many pixels x many channels (Conv_1: 800 x 1 280 at batch 8): 1 000 tiles of 32 x 32 at 173 registers are one workgroup per CU and FOUR
+    // Conv_1 of the MobileNet-v2 programs (320 -> 1 280) no longer arrives here from two frames on: the engine hands every convolution that
+    // wz_gemm_1x1_applies() accepts (1x1, K staged = 320, N >= 1 024, M >= 200) to k_gemm_1x1.hip before it asks for K slices, at every larger M as
+    // well (batches 11 .. 32 used to leave for the LDS tile kernel, 11 with a reduce launch behind it).  Conv_1 at ONE frame (M = 100) still takes the
+    // 32 x 32 tiles below, and any other 1x1 with many pixels x many channels the 32 x 64 ones, which were chosen on Conv_1:
+    // many pixels x many channels (800 x 1 280): 1 000 tiles of 32 x 32 at 173 registers are one workgroup per CU and FOUR
     // rounds of workgroups that each wait out their operands' latency (13.3 us with split weights, K = 640).  32 x 64 tiles, K in four slices,
-    // two chunks per load group (109 registers: two workgroups per CU) are 500 workgroups in ONE round: 6.9 us.  Measured beside it
+    // two chunks per load group (109 registers: two workgroups per CU) are 500 workgroups in ONE round: 6.9 us then, 8.6 us when the GEMM kernel was
+    // measured against it (profiles/gemm_1x1_kernel_stats_lanes1.txt).  Measured beside it
     // (profiles/r04_conv1_tiles.txt): 32 x 32 at 109 registers 8.1 us, 64 x 64 (K in halves) 11.9 us, 64 x 64 at 173 registers 12.8 us (260
     // workgroups on 256 CUs: a second round for four of them).  WZ_CONV_WS64=0: the 32 x 32 tiles everywhere.
     static const int wide_tiles = wz_dev_env_int("WZ_CONV_WS64", 1);

@@ -66,8 +66,55 @@ struct WzConvArgs {
     int32_t frag_ws;            // the K slices' partial sums lie in FRAGMENT order: [z][M / 16][n_pad / 16][64 lanes][4] (wide tile kernel -> grouped reduce)
     int32_t out_coff, out_cstride;   // WZ_OUT_ACT: the output is channels [out_coff, out_coff + cout) of a tensor with out_cstride channels per
                                      // pixel (0: cout -- the whole tensor); the residual keeps the cout pitch
+    int32_t dup_k;              // 1x1 GEMM kernel (k_gemm_1x1.hip): the source tensor holds its cin / 2 values twice per pixel (the op that wrote it has
+                                // WZ_OPF_DUP_OUT) and the weights are [hi | lo] along K: the first copy is read, for both weight halves
 };
 
+
+#ifdef __HIPCC__
+// The epilogue of every fp16 convolution kernel (k_conv.hip, k_conv_rs.h, k_gemm_1x1.hip): one definition, one arithmetic.
+__device__ __forceinline__ void wz_epilogue4(const WzConvArgs& a, int m, int n4, float4_t v) {
+    // v = 4 consecutive output channels n4..n4+3 of output pixel m (bias not yet added)
+    if (m >= a.M || n4 >= a.cout) return;
+    const float4_t bv = *reinterpret_cast<const float4_t*>(a.bias + n4);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float x = v[r] + bv[r];
+        if (a.act == WZ_ACT_RELU6) x = fminf(fmaxf(x, 0.0f), 6.0f);
+        v[r] = x;
+    }
+    if (a.out_mode == WZ_OUT_ACT) {
+        const size_t o = (size_t)m * a.cout + n4;
+        if (a.res) {
+            const half4_t rv = *reinterpret_cast<const half4_t*>(a.res + o);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] += (float)rv[r];
+        }
+        half4_t h = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
+        // (a channel slice of a wider tensor: an Inception branch writing its part of the module's concat)
+        const size_t os = a.out_cstride ? (size_t)m * a.out_cstride + a.out_coff + n4 : o;
+        *reinterpret_cast<half4_t*>(reinterpret_cast<half_t*>(a.out) + os) = h;
+    } else {
+        const int hw = a.hout * a.wout;
+        const int b = m / hw, pix = m - b * hw;
+        float* o;
+        int cols, n0;
+        if (a.out_mode == WZ_OUT_HEAD && n4 >= a.n_box) {   // n_box is a multiple of 4: no group straddles
+            cols = a.cout - a.n_box;
+            n0 = n4 - a.n_box;
+            o = a.out2 + (size_t)b * a.out2_batch_stride + a.out2_off;
+        } else {
+            cols = (a.out_mode == WZ_OUT_HEAD) ? a.n_box : a.cout;
+            n0 = n4;
+            o = reinterpret_cast<float*>(a.out) + (size_t)b * a.out_batch_stride + a.out_off;
+        }
+        o += (size_t)pix * cols + n0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (n0 + r < cols) o[r] = v[r];
+    }
+}
+#endif
 
 struct WzPostConsts {
     int32_t num_anchors, num_classes;   // classes incl. background
@@ -267,6 +314,9 @@ struct WzConvGroup {
 // split-K across the waves of a workgroup (no partials in HBM, no reduce launch): the extras chain
 bool wz_conv_ws_applies(const WzConvArgs& a);
 void wz_launch_conv_ws(const WzConvArgs& a, hipStream_t s);
+// Conv_1 as a dense GEMM with the pixel tile shared through LDS (k_gemm_1x1.hip); applies: a pure function of the shape and a.dup_k
+bool wz_gemm_1x1_applies(const WzConvArgs& a);
+void wz_launch_gemm_1x1(const WzConvArgs& a, hipStream_t s);
 bool wz_conv_groupable(const WzConvArgs& a);
 void wz_conv_group_add(WzConvGroup& g, const WzConvArgs& a);
 void wz_launch_conv_group(const WzConvGroup& g, hipStream_t s);

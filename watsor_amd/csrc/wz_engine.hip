@@ -419,6 +419,18 @@ static void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool wi
                 continue;
             }
             a.frag_ws = 0;   // (only the wide kernel and the grouped reduce behind it know that order)
+            // Conv_1 behind a block that stores its output twice (the robust program): the GEMM kernel reads one copy for both weight halves
+            a.dup_k = 0;
+            for (uint32_t j = 0; j < i; ++j)
+                if (e->ops[j].dst == op.src && (e->ops[j].flags & WZ_OPF_DUP_OUT)) a.dup_k = 1;
+            if (wz_gemm_1x1_applies(a)) {   // one launch, all of K per wave: no K split, nothing to reduce
+                a.splitk = 1;
+                a.out = final_out;
+                WZ_STAMP_ARG(a);
+                wz_launch_gemm_1x1(a, s);
+                if (t) { t->mark(); t->mark(); }
+                continue;
+            }
             if ((sk > 1 || a.M < 128) && wz_conv_ws_applies(a)) {   // the K split happens inside the workgroups: nothing to reduce
                 // (on the 2x2 and 1x1 maps also where one wave per tile would walk all of K alone)
                 a.splitk = 1;
