@@ -1,5 +1,7 @@
-// Internal to the runtime: struct wz_engine, and what wz_tiles.hip (tiled, gated and tiled frame-table detection) takes from
-// wz_engine.hip (everything else).  Nothing here is part of the C ABI: these functions keep their C++ names.
+// Internal to the runtime: struct wz_engine, and what its three files take from each other -- wz_engine.hip (lifecycle, submits,
+// filters, the batch around the network), wz_network.hip (what a batch launches for the engine's ops: enqueue_network and its
+// load-time twins) and wz_tiles.hip (tiled, gated and tiled frame-table detection).  Nothing here is part of the C ABI: these
+// functions keep their C++ names.
 #pragma once
 #include <map>
 #include <string>
@@ -199,9 +201,40 @@ struct wz_engine {
     };
     std::map<int, GateCam> gate_cams;
 
-    std::vector<std::string> stage_names;
+    std::vector<std::string> stage_names;   // stage_slots(op) names per op, between the fixed ones (wz_create)
+    // what the op list alone says about op i (network_prepare): the next op is the only reader of its output (the extras pair's
+    // structural precondition); its source tensor holds every value twice (its writer has WZ_OPF_DUP_OUT)
+    struct OpFacts { uint8_t sole_next, dup_k; };
+    std::vector<OpFacts> op_facts;
 };
 typedef wz_engine::Lane Lane;
+
+static inline int input_tensor_index(const wz_engine* e) { return e->ops[0].src; }
+static inline bool tensor_is_pair(const wz_engine* e, int idx) { return (e->tensors[idx].flags & WZ_TENSOR_HP) != 0; }
+static inline bool input_is_pair(const wz_engine* e) { return tensor_is_pair(e, input_tensor_index(e)); }
+
+// wz_profile_stages: one event per mark, a stage = the bracket between two marks
+struct StageTimer {
+    std::vector<hipEvent_t> ev;
+    size_t used = 0;
+    hipStream_t s = nullptr;
+    void mark() {
+        if (used == ev.size()) {
+            hipEvent_t e;
+            (void)hipEventCreate(&e);
+            ev.push_back(e);
+        }
+        (void)hipEventRecord(ev[used++], s);
+    }
+};
+
+// ---- wz_network.hip, for wz_engine.hip ---------------------------------------------------------------------------------------------
+int stage_slots(const WzOpDesc& op);   // stage-timer brackets an op owns: 2 (launch, reduce) for a convolution or a fused block, else 1
+int op_kernel_check(wz_engine* e, const WzOpDesc& op, const char* path);   // load_blob: a kernel exists for the op's shape, or WZ_EFORMAT
+void network_prepare(wz_engine* e);    // wz_create: kernel attributes on the engine's device, op_facts
+WzConvArgs conv_args(wz_engine* e, const Lane& L, const WzOpDesc& op, int n);
+void head_outputs(wz_engine* e, const Lane& L, const WzOpDesc& op, WzConvArgs& a);
+void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool with_post = true);
 
 // ---- wz_engine.hip, for wz_tiles.hip --------------------------------------------------------------------------------------------
 const char* fmt_refusal(int w, int h, int fmt);

@@ -50,42 +50,13 @@ int wz_set_error(int code, const char* fmt, ...) {
 }
 static int (*const wz_fail)(int, const char*, ...) = wz_set_error;   // (this file's older name for it)
 
-struct StageTimer {
-    std::vector<hipEvent_t> ev;
-    size_t used = 0;
-    hipStream_t s = nullptr;
-    void mark() {
-        if (used == ev.size()) {
-            hipEvent_t e;
-            (void)hipEventCreate(&e);
-            ev.push_back(e);
-        }
-        (void)hipEventRecord(ev[used++], s);
-    }
-};
-
-static int input_tensor_index(wz_engine* e) { return e->ops[0].src; }
-
-// lane stamps: the block of the next launch of the batch being enqueued (nullptr in every build but `make stamps`)
+// lane stamps (`make stamps` only): what the batch being enqueued launches is noted where run_batch points the sink
 #if WZ_LANE_STAMPS
 static thread_local std::vector<WzLaunchNote>* g_launch_sink = nullptr;
 void wz_note_launch(const void* func, dim3 grid, dim3 block, size_t lds) {
     if (g_launch_sink) g_launch_sink->push_back({func, {grid.x, grid.y, grid.z}, {block.x, block.y, block.z}, (unsigned)lds});
 }
-static unsigned long long* next_stamp(wz_engine::Lane& L) {
-    if (!L.d_stamps || L.stamp_next > WZ_STAMP_SLOTS) return nullptr;
-    return L.d_stamps + (size_t)(L.stamp_next++ - 1) * WZ_STAMP_WORDS;
-}
-#define WZ_STAMP_ARG(a) ((a).dbg = next_stamp(L))
-#define WZ_STAMP_ARG2(a) ((a).dbg2 = next_stamp(L))
-#define WZ_STAMP_GROUP(g) ((g).stamp = next_stamp(L))
-#else
-#define WZ_STAMP_ARG(a) ((void)0)
-#define WZ_STAMP_ARG2(a) ((void)0)
-#define WZ_STAMP_GROUP(g) ((void)0)
 #endif
-static bool tensor_is_pair(wz_engine* e, int idx) { return (e->tensors[idx].flags & WZ_TENSOR_HP) != 0; }
-static bool input_is_pair(wz_engine* e) { return tensor_is_pair(e, input_tensor_index(e)); }
 // bytes of one frame of tensor idx (pair tensors hold two halves per value; the input tensor is fp16 in both engines)
 static size_t tensor_frame_bytes(wz_engine* e, int idx) {
     const WzTensorDesc& t = e->tensors[idx];
@@ -96,396 +67,6 @@ static size_t tensor_frame_bytes(wz_engine* e, int idx) {
 // ------------------------------------------------------------------------------------------------
 // pipeline
 // ------------------------------------------------------------------------------------------------
-static WzMbArgs mb_args(wz_engine* e, const Lane& L, const WzOpDesc& op) {
-    const uint8_t* wbase = e->d_weights;
-    WzMbArgs a;
-    memset(&a, 0, sizeof(a));
-    a.in = L.tptr.empty() ? nullptr : L.tptr[op.src];
-    a.we = (op.cin0 > 0 || op.stem) ? (const half_t*)(wbase + op.we_off) : nullptr;
-    a.be = (op.cin0 > 0 || op.stem) ? (const float*)(wbase + op.be_off) : nullptr;
-    a.wd = (const half_t*)(wbase + op.wd_off);
-    a.bd = (const float*)(wbase + op.bd_off);
-    a.wp = (const half_t*)(wbase + op.w_off);
-    a.bp = (const float*)(wbase + op.b_off);
-    a.res = (op.res >= 0 && !L.tptr.empty()) ? L.tptr[op.res] : nullptr;
-    a.out = L.tptr.empty() ? nullptr : L.tptr[op.dst];
-    a.hin = op.hin; a.win = op.win; a.hout = op.hout; a.wout = op.wout;
-    a.cin0 = op.cin0; a.kc0 = op.kc0; a.nmid_pad = op.nmid_pad;
-    a.cmid = op.cmid; a.cmid_pad = op.cmid_pad; a.kc = op.kc;
-    a.cout = op.cout; a.n_pad = op.n_pad;
-    a.stride = op.stride; a.pad_t = op.pad_t; a.pad_l = op.pad_l;
-    a.hp = (op.flags & WZ_OPF_HP) ? 1 : 0;
-    a.hp_out = (op.flags & WZ_OPF_HP_OUT) ? 1 : (op.flags & WZ_OPF_DUP_OUT) ? 2 : 0;
-    a.qenc = (op.flags & WZ_OPF_QENC) ? 1 : 0;
-    a.out2 = (op.dst2 > 0 && !L.tptr.empty()) ? L.tptr[op.dst2 - 1] : nullptr;
-    a.has_out2 = op.dst2 > 0 ? 1 : 0;
-    if (a.hp) {
-        a.we_lo = (const half_t*)(wbase + op.we_lo_off);
-        a.wp_lo = (const half_t*)(wbase + op.w_lo_off);
-    }
-    a.stem = op.stem;
-    if (op.stem) {
-        const WzTensorDesc& in = e->tensors[op.src];
-        a.sin_h = in.h; a.sin_w = in.w;
-        a.spad_t = op.stem_pad >> 16; a.spad_l = op.stem_pad & 0xffff;
-    }
-    return a;
-}
-
-// one separable layer (WZ_OP_DWSEP); `L` without tensors (load-time check): the pointers stay null
-static WzDwsepArgs dwsep_args(wz_engine* e, const Lane& L, const WzOpDesc& op, int n) {
-    const uint8_t* wbase = e->d_weights;
-    WzDwsepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.in = L.tptr.empty() ? nullptr : L.tptr[op.src];
-    a.out = L.tptr.empty() ? nullptr : L.tptr[op.dst];
-    a.wd = (const half_t*)(wbase + op.wd_off);
-    a.bd = (const float*)(wbase + op.bd_off);
-    a.wp = (const half_t*)(wbase + op.w_off);
-    a.bp = (const float*)(wbase + op.b_off);
-    a.M = n * op.hout * op.wout;
-    a.hin = op.hin; a.win = op.win; a.hout = op.hout; a.wout = op.wout;
-    a.cin = op.cin; a.kc = op.kc; a.cout = op.cout; a.n_pad = op.n_pad;
-    a.stride = op.stride; a.pad_t = op.pad_t; a.pad_l = op.pad_l;
-    return a;
-}
-
-// with_post: the post-processing chain follows in the same stream (it consumes -- and resets -- the candidate list)
-static void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool with_post = true) {
-    hipStream_t s = L.stream;
-    const bool f32 = e->hdr.precision == 32;
-    // The heads write only into the box / logit buffers that the post kernels read at the very end, so their partial
-    // sums can wait: each head's slab is parked at the top of the workspace and ONE launch reduces them all after the
-    // last op (six launches fewer per batch).  Everything else uses the workspace below `ws_top`.
-    size_t ws_top = e->ws_bytes;
-    WzReduceGroup heads;
-    heads.n = 0;
-    heads.first[0] = 0;
-    heads.decode = 0;
-    int box_ops = 0, box_ops_grouped = 0;   // ops that produce box encodings / how many of them went into `heads`
-    int head_ops = 0;                       // ops that write box encodings or class logits
-    // ... and the small heads themselves (3x3 ... 1x1 maps: a handful of workgroups each) share one launch as well
-    WzConvGroup small, big;
-    small.n = big.n = 0;
-    small.first[0] = big.first[0] = 0;
-    // The heads with a long K loop run on the wide tile kernel (k_conv_wide.hip), all in one launch; their K slices are chosen
-    // together, for the whole launch (one round over the CUs, slices of equal length), before the first one is enqueued.
-    WzConvGroup wide;
-    wide.n = 0;
-    wide.first[0] = 0;
-    int wide_T = 0;   // K steps per slice (0: no head goes there)
-    if (!f32 && e->conv_wide && e->use_splitk && e->defer_heads) {
-        int tiles[WZ_CONV_GROUP_MAX], steps[WZ_CONV_GROUP_MAX], cnt = 0;
-        long long tile_bytes[WZ_CONV_GROUP_MAX];
-        for (uint32_t i = 0; i < e->hdr.n_ops && cnt < WZ_CONV_GROUP_MAX; ++i) {
-            const WzOpDesc& op = e->ops[i];
-            if (op.kind != WZ_OP_CONV) continue;
-            WzConvArgs a;
-            memset(&a, 0, sizeof(a));
-            a.M = n * op.hout * op.wout;
-            a.cin = op.cin; a.cout = op.cout; a.n_pad = op.n_pad; a.ksize = op.ksize; a.kc = op.kc;
-            a.out_mode = op.out_mode;
-            a.kchunks = op.ksize * op.ksize * op.kc;
-            a.zeros = e->d_zeros;
-            if (!wz_conv_wide_applies(a) || a.M < e->wide_min_m) continue;
-            wz_conv_wide_shape(a, &tiles[cnt], &steps[cnt]);
-            tile_bytes[cnt] = 128ll * 4 * (((a.cout + 15) & ~15) / (((a.cout + 15) / 16 + WZ_WIDE_TILES - 1) / WZ_WIDE_TILES));
-            ++cnt;
-        }
-        // (K slices sized for HALF the chip when other lanes are there to use the rest: at batch 8 T = 27 -> 41 steps per slice, 179 -> ~120
-        // workgroups of this one-wave-per-SIMD kernel, a third fewer fp32 partial tiles: 49.8 k -> 50.5 k frames/s, p50 +8 us)
-        // (two workgroups of that kernel share a CU: twice the slots in the same part of the chip)
-        if (cnt > 0) wide_T = e->wide_T > 0 ? e->wide_T : wz_choose_wide_T(tiles, steps, tile_bytes, cnt, (e->n_lanes > 1 ? e->wide_cus : e->num_cus) * 2);
-    }
-    for (uint32_t i = 0; i < e->hdr.n_ops; ++i) {
-        const WzOpDesc& op = e->ops[i];
-        const uint8_t* wbase = e->d_weights;
-        if (f32 && op.kind == WZ_OP_STEM) {
-            wz_launch_stem_f32(L.tptr[op.src], (const float*)(wbase + op.w_off), (const float*)(wbase + op.b_off),
-                               (float*)L.tptr[op.dst], n, op.hin, op.win, op.hout, op.wout, op.pad_t, op.pad_l, s, input_is_pair(e));
-        } else if (f32 && op.kind == WZ_OP_DW) {
-            wz_launch_dw_f32((const float*)L.tptr[op.src], (const float*)(wbase + op.w_off), (const float*)(wbase + op.b_off),
-                             (float*)L.tptr[op.dst], n, op.hin, op.win, op.cin, op.hout, op.wout, op.stride, op.pad_t,
-                             op.pad_l, op.act, s);
-        } else if (op.kind == WZ_OP_STEM) {
-            wz_launch_stem(L.tptr[op.src], (const float*)(wbase + op.w_off), (const float*)(wbase + op.b_off),
-                           L.tptr[op.dst], n, op.hin, op.win, op.hout, op.wout, op.pad_t, op.pad_l, s);
-        } else if (op.kind == WZ_OP_DW) {
-            wz_launch_dw(L.tptr[op.src], (const half_t*)(wbase + op.w_off), (const float*)(wbase + op.b_off),
-                         L.tptr[op.dst], n, op.hin, op.win, op.cin, op.hout, op.wout, op.stride, op.pad_t,
-                         op.pad_l, op.act, s);
-        } else if (op.kind == WZ_OP_POOL) {   // (Inception: writes its slice of the module tensor, or a tensor of its own)
-            const int cs = op.dst_c ? op.dst_c : op.cout;
-            const bool is_max = !(op.flags & WZ_OPF_POOL_AVG);
-            if (f32)
-                wz_launch_pool3_f32((const float*)L.tptr[op.src], (float*)L.tptr[op.dst], n, op.hin, op.win, op.cin, op.hout, op.wout,
-                                    op.stride, op.pad_t, op.pad_l, is_max, cs, op.dst_coff, s);
-            else
-                wz_launch_pool3(L.tptr[op.src], L.tptr[op.dst], n, op.hin, op.win, op.cin, op.hout, op.wout, op.stride, op.pad_t,
-                                op.pad_l, is_max, cs, op.dst_coff, s);
-        } else if (op.kind == WZ_OP_STEM7) {
-            const int cs = op.dst_c ? op.dst_c : op.cout;
-            if (f32)
-                wz_launch_stem7_f32(L.tptr[op.src], (const float*)(wbase + op.w_off), (const float*)(wbase + op.b_off), (float*)L.tptr[op.dst],
-                                    n, op.hin, op.win, op.hout, op.wout, op.pad_t, op.pad_l, cs, op.dst_coff, input_is_pair(e), s);
-            else
-                wz_launch_stem7(L.tptr[op.src], (const half_t*)(wbase + op.w_off), (const float*)(wbase + op.b_off), L.tptr[op.dst], n,
-                                op.hin, op.win, op.hout, op.wout, op.pad_t, op.pad_l, cs, op.dst_coff, s);
-        } else if (op.kind == WZ_OP_DWSEP) {   // (load_blob refused every shape wz_launch_dwsep does not cover)
-            WzDwsepArgs a = dwsep_args(e, L, op, n);
-            WZ_STAMP_ARG(a);
-            if (wz_launch_dwsep(a, s, false) != 0) L.launch_failed = (int)i + 1;
-        } else if (op.kind == WZ_OP_MBCONV) {
-            WzMbArgs a = mb_args(e, L, op);
-            a.M = n * op.hout * op.wout;
-            a.lone = L.lone ? 1 : 0;
-            a.ws = (e->use_splitk || a.hp) ? L.d_ws : nullptr;   // (split-K partials of the plain blocks; the two-launch split blocks' project fragments)
-            a.ws_bytes = ws_top;
-            a.dbg = e->d_mbdbg ? e->d_mbdbg + (size_t)i * 16 : nullptr;
-            WZ_STAMP_ARG(a);
-            if (a.hp && wz_mbconv_hp2_applies(a, n)) {
-                // the 10x10 split blocks of the robust program: two GEMM-shaped launches (k_mbconv_hp2.hip); the stage timer books the second one
-                // on the op's (otherwise empty) reduce slot
-                WZ_STAMP_ARG2(a);
-                int r2 = wz_launch_mbconv_hp2(a, n, s, false, 1);
-                if (t) t->mark();
-                if (r2 >= 0) r2 = wz_launch_mbconv_hp2(a, n, s, false, 2);
-                if (r2 < 0) L.launch_failed = (int)i + 1;
-                if (e->d_mbdbg) e->mb_groups[i] = 1;
-                if (t) t->mark();
-                continue;
-            }
-            int groups = a.hp ? wz_launch_mbconv_hp(a, n, s, false)   // split-operand blocks (the `-p 16` program's first 13)
-                              : wz_launch_mbconv_wave(a, n, s, false);   // large maps: one wavefront per pixel tile
-            if (a.hp && groups < 0) L.launch_failed = (int)i + 1;   // nothing was enqueued for a split-operand block: run_batch reports it
-            if (groups == -2 && (e->use_splitk || a.has_out2)) groups = wz_launch_mbconv_cs(a, n, s, false);   // small maps: channels over waves
-            if (a.has_out2 && groups < 0) L.launch_failed = (int)i + 1;   // only the chunk-split kernel stores a second output
-            if (groups == -2) groups = wz_launch_mbconv(a, n, s, false);
-            if (e->d_mbdbg) e->mb_groups[i] = groups;
-            if (t) t->mark();
-            if (groups > 1) {   // sum the channel groups' partials in a fixed order, + bias, + residual, -> fp16
-                WzConvArgs r;
-                memset(&r, 0, sizeof(r));
-                r.bias = a.bp; r.res = a.res; r.out = a.out;
-                r.M = a.M; r.hout = op.hout; r.wout = op.wout; r.cout = op.cout; r.n_pad = op.n_pad;
-                r.act = WZ_ACT_NONE; r.out_mode = WZ_OUT_ACT; r.splitk = groups;
-                WZ_STAMP_ARG(r);
-                wz_launch_splitk_reduce(r, L.d_ws, s);
-            }
-        } else {
-            // Two convolutions of the extras chain in one launch (k_extras_pair.hip): a 1x1 whose output only the 3x3 stride-2 convolution behind it
-            // reads, on the 5x5 / 3x3 / 2x2 maps -- three launches and three boundaries less per batch
-            // (not for slice outputs: the pair kernel stores whole tensors)
-            if (!f32 && op.out_mode == WZ_OUT_ACT && op.ksize == 1 && op.dst_c == 0 && i + 1 < e->hdr.n_ops) {
-                const WzOpDesc& nx = e->ops[i + 1];
-                bool only = nx.kind == WZ_OP_CONV && nx.src == op.dst && nx.out_mode == WZ_OUT_ACT && op.res < 0 && nx.res < 0 &&
-                            nx.dst_c == 0;
-                for (uint32_t j = 0; only && j < e->hdr.n_ops; ++j)
-                    if (j != i + 1 && (e->ops[j].src == op.dst || e->ops[j].res == op.dst)) only = false;
-                if (only) {
-                    auto conv_args = [&](const WzOpDesc& o) {
-                        WzConvArgs c;
-                        memset(&c, 0, sizeof(c));
-                        c.in = L.tptr[o.src];
-                        c.w = (const half_t*)(wbase + o.w_off);
-                        c.bias = (const float*)(wbase + o.b_off);
-                        c.out = L.tptr[o.dst];
-                        c.M = n * o.hout * o.wout;
-                        c.hin = o.hin; c.win = o.win; c.cin = o.cin;
-                        c.hout = o.hout; c.wout = o.wout; c.cout = o.cout; c.n_pad = o.n_pad;
-                        c.ksize = o.ksize; c.stride = o.stride; c.pad_t = o.pad_t; c.pad_l = o.pad_l; c.kc = o.kc;
-                        c.act = o.act; c.out_mode = o.out_mode;
-                        c.kchunks = o.ksize * o.ksize * o.kc;
-                        c.splitk = 1;
-                        return c;
-                    };
-                    WzConvArgs pa = conv_args(op);
-                    const WzConvArgs pb = conv_args(nx);
-                    if (wz_extras_pair_applies(pa, pb)) {
-                        WZ_STAMP_ARG(pa);
-                        wz_launch_extras_pair(pa, pb, n, s);
-                        if (t) { t->mark(); t->mark(); t->mark(); t->mark(); }   // (both ops' slots; the launch is booked on the first)
-                        ++i;
-                        continue;
-                    }
-                }
-            }
-            WzConvArgs a;
-            memset(&a, 0, sizeof(a));
-            a.in = L.tptr[op.src];
-            a.w = (const half_t*)(wbase + op.w_off);
-            a.bias = (const float*)(wbase + op.b_off);
-            a.res = op.res >= 0 ? L.tptr[op.res] : nullptr;
-            a.M = n * op.hout * op.wout;
-            a.hin = op.hin; a.win = op.win; a.cin = op.cin;
-            a.hout = op.hout; a.wout = op.wout; a.cout = op.cout; a.n_pad = op.n_pad;
-            a.ksize = op.ksize; a.stride = op.stride; a.pad_t = op.pad_t; a.pad_l = op.pad_l; a.kc = op.kc;
-            a.act = op.act; a.out_mode = op.out_mode;
-            a.kchunks = op.ksize * op.ksize * op.kc;
-            if (op.out_mode == WZ_OUT_ACT && op.dst_c != 0) {   // a channel slice of the output tensor (load_blob checked it)
-                a.out_cstride = op.dst_c;
-                a.out_coff = op.dst_coff;
-            }
-            void* final_out;
-            if (op.out_mode == WZ_OUT_ACT) {
-                final_out = L.tptr[op.dst];
-            } else if (op.out_mode == WZ_OUT_BOX) {
-                final_out = L.d_box_enc;
-                a.out_batch_stride = (int64_t)e->hdr.num_anchors * 4;
-                a.out_off = (int64_t)op.anchor_off * 4;
-            } else if (op.out_mode == WZ_OUT_CLS) {
-                final_out = L.d_logits;
-                a.out_batch_stride = (int64_t)e->hdr.num_anchors * e->hdr.num_classes;
-                a.out_off = (int64_t)op.anchor_off * e->hdr.num_classes;
-            } else {   // WZ_OUT_HEAD: box columns -> d_box_enc, class columns -> d_logits
-                final_out = L.d_box_enc;
-                a.out_batch_stride = (int64_t)e->hdr.num_anchors * 4;
-                a.out_off = (int64_t)op.anchor_off * 4;
-                a.out2 = L.d_logits;
-                a.out2_batch_stride = (int64_t)e->hdr.num_anchors * e->hdr.num_classes;
-                a.out2_off = (int64_t)op.anchor_off * e->hdr.num_classes;
-                a.n_box = op.n_box;
-            }
-            a.zeros = e->d_zeros;
-            a.dbg = e->d_mbdbg ? e->d_mbdbg + (size_t)i * 16 : nullptr;
-            const bool makes_boxes = op.out_mode == WZ_OUT_HEAD || op.out_mode == WZ_OUT_BOX;
-            if (makes_boxes) ++box_ops;
-            if (op.out_mode != WZ_OUT_ACT) ++head_ops;
-            if (f32) {   // a.kc / a.kchunks count 16-channel chunks here
-                int sk = !e->use_splitk ? 1 : wz_conv_f32_use_rs(a) ? wz_choose_splitk_rs_f32(a.M, a.n_pad, a.kchunks) : wz_choose_splitk(a.M, a.n_pad, a.kchunks / 2);
-                const size_t slab32 = (((size_t)sk * a.M * a.n_pad * 4) + 255) & ~(size_t)255;
-                if (sk > 1 && e->defer_heads && op.out_mode != WZ_OUT_ACT && heads.n < WZ_REDUCE_GROUP_MAX &&
-                    slab32 + (e->ws_bytes >> 1) <= ws_top) {
-                    // the heads' outputs are fp32 in both engines and their epilogue is the same: the partial sums are
-                    // parked and reduced (+ decoded, + candidates marked) by the same grouped launch as in the fp16 engine
-                    ws_top -= slab32;
-                    float* const park = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(L.d_ws) + ws_top);
-                    a.splitk = sk;
-                    a.ws = park;
-                    a.out = final_out;
-                    wz_launch_conv_f32(a, s, false);
-                    if (t) { t->mark(); t->mark(); }
-                    wz_reduce_group_add(heads, a, park);
-                    if (makes_boxes) ++box_ops_grouped;
-                    continue;
-                }
-                if (wz_conv_ws_f32_applies(a)) {   // the extras chain: K split across the waves of a workgroup, no reduce
-                    a.splitk = 1;
-                    a.out = final_out;
-                    wz_launch_conv_ws_f32(a, s);
-                    if (t) { t->mark(); t->mark(); }
-                    continue;
-                }
-                while (sk > 1 && (size_t)sk * a.M * a.n_pad * 4 > ws_top) --sk;
-                a.splitk = sk;
-                a.ws = L.d_ws;
-                a.out = final_out;
-                wz_launch_conv_f32(a, s);
-                if (t) { t->mark(); t->mark(); }
-                continue;
-            }
-            int sk = 1;
-            if (e->use_splitk)
-                sk = wz_conv_use_lds(a) ? wz_choose_splitk_lds(a.M, a.n_pad, a.kchunks) : wz_choose_splitk(a.M, a.n_pad, a.kchunks);
-            bool to_wide = wide_T > 0 && wide.n < WZ_CONV_GROUP_MAX && wz_conv_wide_applies(a) && a.M >= e->wide_min_m;
-            const size_t m16 = ((size_t)a.M + 15) & ~(size_t)15;   // (the wide kernel's partials are whole 16-pixel fragments)
-            if (to_wide) {   // its partial sums always go through the grouped reduce, also with a single K slice
-                const int wsk = ((a.kchunks >> 1) + wide_T - 1) / wide_T;
-                if (heads.n < WZ_REDUCE_GROUP_MAX && ((((size_t)wsk * m16 * a.n_pad * 4) + 255) & ~(size_t)255) + (e->ws_bytes >> 1) <= ws_top)
-                    sk = wsk;
-                else
-                    to_wide = false;
-            }
-            a.frag_ws = to_wide ? 1 : 0;
-            const size_t slab = (((size_t)sk * (to_wide ? m16 : (size_t)a.M) * a.n_pad * 4) + 255) & ~(size_t)255;
-            if ((sk > 1 || to_wide) && e->defer_heads && op.out_mode != WZ_OUT_ACT && heads.n < WZ_REDUCE_GROUP_MAX &&
-                slab + (e->ws_bytes >> 1) <= ws_top) {   // keep at least half of the workspace for the other ops
-                ws_top -= slab;
-                float* const park = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(L.d_ws) + ws_top);
-                a.splitk = sk;
-                a.out = park;
-                if (to_wide) {
-                    wz_conv_wide_group_add(wide, a);
-                } else if (small.n < WZ_CONV_GROUP_MAX && wz_conv_groupable(a)) {
-                    wz_conv_group_add(small, a);   // launched with the other small heads after the last op
-                } else if (!(wz_conv_rs_groupable(a) && wz_conv_rs_group_add(big, a))) {   // (the heads on the tile kernel: one launch, too)
-                    WZ_STAMP_ARG(a);
-                    wz_launch_conv(a, s);
-                }
-                if (t) { t->mark(); t->mark(); }   // its own reduce slot stays empty
-                a.out = final_out;
-                wz_reduce_group_add(heads, a, park);
-                if (makes_boxes) ++box_ops_grouped;
-                continue;
-            }
-            a.frag_ws = 0;   // (only the wide kernel and the grouped reduce behind it know that order)
-            // Conv_1 behind a block that stores its output twice (the robust program): the GEMM kernel reads one copy for both weight halves
-            a.dup_k = 0;
-            for (uint32_t j = 0; j < i; ++j)
-                if (e->ops[j].dst == op.src && (e->ops[j].flags & WZ_OPF_DUP_OUT)) a.dup_k = 1;
-            if (wz_gemm_1x1_applies(a)) {   // one launch, all of K per wave: no K split, nothing to reduce
-                a.splitk = 1;
-                a.out = final_out;
-                WZ_STAMP_ARG(a);
-                wz_launch_gemm_1x1(a, s);
-                if (t) { t->mark(); t->mark(); }
-                continue;
-            }
-            if ((sk > 1 || a.M < 128) && wz_conv_ws_applies(a)) {   // the K split happens inside the workgroups: nothing to reduce
-                // (on the 2x2 and 1x1 maps also where one wave per tile would walk all of K alone)
-                a.splitk = 1;
-                a.out = final_out;
-                WZ_STAMP_ARG(a);
-                wz_launch_conv_ws(a, s);
-                if (t) { t->mark(); t->mark(); }
-                continue;
-            }
-            while (sk > 1 && (size_t)sk * a.M * a.n_pad * 4 > ws_top) --sk;
-            a.splitk = sk;
-            if (sk > 1) {
-                a.out = L.d_ws;
-                WZ_STAMP_ARG(a);
-                wz_launch_conv(a, s);
-                if (t) t->mark();
-                a.out = final_out;
-                WZ_STAMP_ARG(a);
-                wz_launch_splitk_reduce(a, L.d_ws, s);
-            } else {
-                a.out = final_out;
-                WZ_STAMP_ARG(a);
-                wz_launch_conv(a, s);
-                if (t) t->mark();
-            }
-        }
-        if (t) t->mark();
-    }
-    // every box encoding is finished by the grouped reduce: let it decode the boxes as well (one launch less)
-    L.decode_fused = heads.n > 0 && box_ops > 0 && box_ops == box_ops_grouped && e->fuse_decode;
-    // ... and list the class logits that can reach the NMS kernel's first band
-    L.cands_listed = with_post && L.decode_fused && head_ops == heads.n;
-    wide.stamp = big.stamp = small.stamp = heads.stamp = nullptr;   // (set per launch in the stamps build only)
-    if (wide.n > 0) { WZ_STAMP_GROUP(wide); wz_launch_conv_wide_group(wide, s); }
-    if (big.n > 0) { WZ_STAMP_GROUP(big); wz_launch_conv_rs_group(big, s); }
-    if (t) t->mark();
-    if (small.n > 0) { WZ_STAMP_GROUP(small); wz_launch_conv_group(small, s); }
-    if (t) t->mark();
-    if (L.decode_fused) {
-        heads.decode = 1;
-        heads.pc = e->pc;
-        heads.anchors = L.post.anchors;
-        heads.boxes = L.post.boxes;
-        heads.valid = L.post.valid;
-    }
-    heads.list = L.cands_listed ? 1 : 0;
-    if (L.cands_listed) {
-        heads.hint_logit = L.post.hint_logit;
-        heads.cbits = L.post.cbits;
-        heads.cbits_words = (e->pc.num_anchors * e->pc.num_classes + 31) >> 5;
-    }
-    if (heads.n > 0) { WZ_STAMP_GROUP(heads); wz_launch_splitk_reduce_group(heads, s); }
-    if (t) t->mark();
-}
-
 static void enqueue_post(wz_engine* e, Lane& L, bool rows, int n, StageTimer* t, bool decode_done = false, bool listed = false) {
     hipStream_t s = L.stream;
     if (!decode_done) wz_launch_decode(L.post, e->pc, n, s);
@@ -806,9 +387,6 @@ static int load_blob(wz_engine* e, const char* path) {
                 op.we_lo_off <= 0 || (uint64_t)op.we_lo_off >= h.weights_bytes || op.w_lo_off <= 0 ||
                 (uint64_t)op.w_lo_off >= h.weights_bytes || (op.stem && e->tensors[op.src].c != 4))
                 return wz_fail(WZ_EFORMAT, "%s: op %u (%s): malformed split-operand block", path, i, op.name);
-            wz_engine::Lane none;
-            if (wz_launch_mbconv_hp(mb_args(e, none, op), 1, nullptr, true) != 0)
-                return wz_fail(WZ_EFORMAT, "%s: op %u (%s): no split-operand kernel for this shape", path, i, op.name);
         } else if ((op.kind == WZ_OP_STEM || op.kind == WZ_OP_STEM7) && h.precision == 32 && (e->tensors[op.src].flags & WZ_TENSOR_HP) &&
                    !(op.dst >= 0 && (e->tensors[op.dst].flags & WZ_TENSOR_HP))) {
             // the fp32 program's stem reads the network input as a hi + lo pair (wz_k_stem_f32)
@@ -816,8 +394,8 @@ static int load_blob(wz_engine* e, const char* path) {
                    (op.res >= 0 && (e->tensors[op.res].flags & WZ_TENSOR_HP))) {
             return wz_fail(WZ_EFORMAT, "%s: op %u (%s) touches a pair tensor but is not a split-operand block", path, i, op.name);
         } else if (op.kind == WZ_OP_DWSEP) {
-            // every bound the kernel indexes by: the tensors it reads and writes, both weight blocks, then the shapes it covers --
-            // evaluated here with the predicate of the launch, so that an uncovered shape never reaches run_batch
+            // every bound the kernel indexes by: the tensors it reads and writes, both weight blocks; the shapes it covers are
+            // op_kernel_check's, evaluated with the predicate of the launch, so that an uncovered shape never reaches run_batch
             const WzTensorDesc& in = e->tensors[op.src];
             const WzTensorDesc* out = op.dst >= 0 ? &e->tensors[op.dst] : nullptr;
             const uint64_t wb = h.weights_bytes;
@@ -828,23 +406,12 @@ static int load_blob(wz_engine* e, const char* path) {
                 (uint64_t)op.bd_off + 4ull * op.cin > wb || (uint64_t)op.w_off + 64ull * op.n_pad * op.kc > wb || op.b_off < 0 ||
                 (uint64_t)op.b_off + 4ull * op.n_pad > wb)
                 return wz_fail(WZ_EFORMAT, "%s: op %u (%s): malformed depthwise-separable layer", path, i, op.name);
-            wz_engine::Lane none;
-            if (wz_launch_dwsep(dwsep_args(e, none, op, 1), nullptr, true) != 0)
-                return wz_fail(WZ_EFORMAT, "%s: op %u (%s): no depthwise-separable kernel for this shape (cin %d, cout %d, n_pad %d, %dx%d "
-                               "stride %d)", path, i, op.name, op.cin, op.cout, op.n_pad, op.hin, op.win, op.stride);
         } else if (op.kind == WZ_OP_MBCONV && op.stem) {
             if (e->tensors[op.src].c != 4 || op.cin0 != 32 || op.kc0 != 1 || (e->tensors[op.src].h + 1) / 2 != op.hin ||
                 (e->tensors[op.src].w + 1) / 2 != op.win)
                 return wz_fail(WZ_EFORMAT, "%s: op %u (%s): malformed stem fusion", path, i, op.name);
-            wz_engine::Lane none;
-            if (wz_launch_mbconv_wave(mb_args(e, none, op), 1, nullptr, true) < 0)
-                return wz_fail(WZ_EFORMAT, "%s: op %u (%s): no stem-fused kernel for this shape", path, i, op.name);
-        } else if (op.kind == WZ_OP_MBCONV) {
-            wz_engine::Lane none;
-            if (op.dst2 > 0 ? wz_launch_mbconv_cs(mb_args(e, none, op), 1, nullptr, true) != 0
-                            : wz_launch_mbconv(mb_args(e, none, op), 1, nullptr, true) != 0)
-                return wz_fail(WZ_EFORMAT, "%s: op %u (%s): no fused-block kernel for this shape", path, i, op.name);
         }
+        WZCHK(op_kernel_check(e, op, path));   // the op is well-formed: is there a kernel for its shape?
     }
     return WZ_OK;
 }
@@ -932,17 +499,7 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
     wz_device_name_of(device, nm, sizeof(nm));
     e->name = nm;
     wz_post_init();
-    for (uint32_t i = 0; i < e->hdr.n_ops; ++i)   // kernel attributes of the fused-block kernels, on THIS device
-        if (e->ops[i].kind == WZ_OP_MBCONV) {
-            wz_engine::Lane none;
-            if (e->ops[i].flags & WZ_OPF_HP) {
-                (void)wz_launch_mbconv_hp(mb_args(e, none, e->ops[i]), max_batch, nullptr, true);
-                continue;
-            }
-            if (!e->ops[i].stem) (void)wz_launch_mbconv(mb_args(e, none, e->ops[i]), max_batch, nullptr, true);
-            (void)wz_launch_mbconv_wave(mb_args(e, none, e->ops[i]), max_batch, nullptr, true);
-            (void)wz_launch_mbconv_cs(mb_args(e, none, e->ops[i]), max_batch, nullptr, true);
-        }
+    network_prepare(e);   // kernel attributes of the fused-block kernels, on THIS device; what the op list says about every op
 
     // the lanes' streams before anything is copied: the set-up copies below ride lane 0's (lane0_copy)
     for (int li = 0; li < e->n_streams; ++li) {
@@ -1101,9 +658,8 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
     e->stage_names.push_back("h2d_descriptors");
     e->stage_names.push_back("preprocess");
     for (uint32_t i = 0; i < h.n_ops; ++i) {
-        e->stage_names.push_back(e->ops[i].name);
-        if (e->ops[i].kind == WZ_OP_CONV || e->ops[i].kind == WZ_OP_MBCONV)
-            e->stage_names.push_back(std::string(e->ops[i].name) + "#splitk_reduce");
+        e->stage_names.push_back(e->ops[i].name);   // stage_slots(op) names per op: enqueue_network marks as many
+        for (int k = 1; k < stage_slots(e->ops[i]); ++k) e->stage_names.push_back(std::string(e->ops[i].name) + "#splitk_reduce");
     }
     e->stage_names.push_back("heads#big_convs");
     e->stage_names.push_back("heads#small_convs");
@@ -1886,20 +1442,10 @@ extern "C" int wz_stage_post_production(wz_engine_t* e, int n, const float* box_
         if (op.out_mode != WZ_OUT_HEAD || g.n >= WZ_REDUCE_GROUP_MAX || op.n_box != apl * 4 || op.cout != apl * (4 + (int)C) ||
             op.n_pad < op.cout || (size_t)op.n_pad * 4 > 4096 || (size_t)op.anchor_off + (size_t)hw * apl > A)
             return wz_fail(WZ_EINVAL, "wz_stage_post_production: op %d (%s) is no [box | class] head this entry can feed", i, op.name);
-        WzConvArgs a;
-        memset(&a, 0, sizeof(a));
+        WzConvArgs a = conv_args(e, L, op, n);   // (the grouped reduce reads the epilogue's part of it)
+        head_outputs(e, L, op, a);
         a.bias = reinterpret_cast<const float*>(e->d_zeros);   // 4 KiB of zeros: n_pad floats at most (checked above)
-        a.M = n * hw;
-        a.hout = op.hout; a.wout = op.wout; a.cout = op.cout; a.n_pad = op.n_pad;
-        a.act = op.act; a.out_mode = op.out_mode;
         a.splitk = 1;
-        a.out = L.d_box_enc;
-        a.out_batch_stride = (int64_t)A * 4;
-        a.out_off = (int64_t)op.anchor_off * 4;
-        a.out2 = L.d_logits;
-        a.out2_batch_stride = (int64_t)A * C;
-        a.out2_off = (int64_t)op.anchor_off * C;
-        a.n_box = op.n_box;
         offs.push_back(host.size());
         host.resize(host.size() + (size_t)a.M * a.n_pad, 0.0f);
         float* part = host.data() + offs.back();
