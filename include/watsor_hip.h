@@ -221,6 +221,51 @@ int wz_submit_gated_device(wz_engine_t* e, int slot, int n, const uint8_t* const
                            const int* cam, double iou_thr, double ios_thr);
 int wz_gate_stats(wz_engine_t* e, int slot, int n, uint64_t* ran_mask /* [n], bit t: tile t ran */,
                   int32_t* activity /* [sum of tiles]; 0 for a tile without a reference; may be NULL */);
+/* ---- motion regions.  The rectangles of a tiled or gated call are fixed in advance; a motion call finds them: it
+ * cuts a rectangle at the camera's own resolution around every part of the picture that changed since the camera's previous motion
+ * call -- plain frame differencing -- and runs the detector there, beside the squeezed whole frame if the camera asks for it.  The
+ * activity launch of a gated call writes the whole frame's grid of WZ_GATE_CELL x WZ_GATE_CELL luma sums (cells and luma exactly as
+ * above); a second launch, one workgroup per camera, turns the changed cells into at most WZ_MOTION_MAX_REGIONS ranked rectangles in
+ * the lane's page-locked block; the host waits once, reads them, and everything behind is the tiled call on those rectangles.
+ *   reference        the grid of the camera's previous ACCEPTED motion call, replaced on every accepted call (two grids per camera,
+ *                    swapped by pointer).  Without one -- first call, after wz_reset_camera_motion, after wz_set_camera_motion --
+ *                    no cell has changed.  A camera's motion state shares nothing with its gate tiles; it may have both.
+ *   changed cell     C = 1 iff |S_now - S_ref| > pixel_thr * (pixels of the cell)
+ *   dilation         D = 1 iff some C = 1 lies within `dilate` cells in x and in y
+ *   components       the 8-connected components of D; id = the smallest y * columns + x of its cells, weight n = its cells with C = 1
+ *                    (dilated cells do not count), cell box = the bounding box of its D cells
+ *   candidates       the components with n >= min_cells by n descending, then id ascending; the first 64 are looked at
+ *   the walk         in that order.  Tight rectangle: the cell box in pixels, clipped to the frame, grown by `pad` on every side and
+ *                    clipped again.  A candidate whose tight rectangle lies wholly inside the FINAL rectangle of a region already
+ *                    accepted is dropped.  Otherwise each axis is grown evenly to min(min_side, frame) pixels (the odd pixel goes
+ *                    right / down) and shifted back into the frame; for NV12 / I420 / P010 / YUV420P10 x0, y0 go down and x1, y1 up
+ *                    to even numbers (clipped), for YUYV422 / UYVY422 x0 and x1; the rectangle is accepted; max_regions end the walk.
+ *   tile list        [the whole frame, if whole_frame] + the regions in the order they were accepted
+ *   result           bit for bit what ONE wz_detect_tiled call of the same frames with these tile lists gives.  A frame whose list is
+ *                    empty (whole_frame 0, nothing moved) gets the engine's 100 padding rows and pass bytes 0 whatever its camera's
+ *                    filter says; if no frame of a call has a tile neither a crop nor a batch is launched.
+ * wz_set_camera_motion waits for every lane and allocates the camera's two grids; on failure the camera keeps what it had.  Refused
+ * with WZ_EINVAL: pixel_thr outside 0 .. 255, min_cells < 1, dilate outside 0 .. 2, max_regions outside 1 .. WZ_MOTION_MAX_REGIONS,
+ * min_side < 16, pad outside 0 .. 64, whole_frame other than 0 / 1, a size or format wz_frame_bytes() refuses; with WZ_ELIMIT: a frame
+ * larger than max_width x max_height, more than WZ_MOTION_MAX_CELLS cells, whole_frame + max_regions > max_batch.
+ * A motion call is refused, with nothing enqueued, no row written and no state changed: cam NULL, a camera id of -1 or without
+ * settings, a frame whose size or base format differs from the settings', the same camera twice, thresholds a tiled call refuses
+ * (WZ_EINVAL); the CONFIGURED whole_frame + max_regions of the call's cameras summing to more than max_batch (WZ_ELIMIT) -- never the
+ * regions found: a refusal does not depend on pixels.  wz_submit_motion_device returns once the rectangles are read: both
+ * state-touching launches have finished by then, so no other lane ever holds a camera's motion state in flight; the slot is collected
+ * like any tiled slot.  wz_motion_stats: what the last motion call accepted on `slot` found for its n frames. */
+#define WZ_MOTION_MAX_REGIONS 16
+#define WZ_MOTION_MAX_CELLS   32768
+typedef struct wz_motion { int32_t pixel_thr, min_cells, dilate, max_regions, min_side, pad, whole_frame, _reserved; } wz_motion_t;
+int wz_set_camera_motion(wz_engine_t* e, int cam, int width, int height, int fmt, const wz_motion_t* motion);
+int wz_reset_camera_motion(wz_engine_t* e, int cam);    /* forget the reference, keep the settings */
+int wz_clear_camera_motion(wz_engine_t* e, int cam);
+int wz_detect_motion(wz_engine_t* e, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt, const int* cam,
+                     double iou_thr, double ios_thr, wz_detection_t* const* out, uint8_t* const* pass, float* ms);
+int wz_submit_motion_device(wz_engine_t* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
+                            const int* cam, double iou_thr, double ios_thr);
+int wz_motion_stats(wz_engine_t* e, int slot, int n, int32_t* n_tiles /* [n] */, wz_tile_t* tiles /* [n][1 + WZ_MOTION_MAX_REGIONS] */,
+                    int32_t* cells /* [n][WZ_MOTION_MAX_REGIONS]: n of every region */, int32_t* components /* [n]: those with n >= min_cells */);
 /* ---- the worker's frame table.  The reference worker resolves every payload to `frame_buffers[sender].frames[index]`, asks
  * the frame for a numpy view of its pixels and hands the frame header's `Detection[100]` array to the plugin
  * (watsor/detection/detector.py:102-109); pixels, size and rows of a Frame never move after the FrameBuffers are created
@@ -438,6 +483,15 @@ int wz_stage_tile_activity(wz_engine_t* e, const uint8_t* frame, int w, int h, i
  * issued them (the call runs first, with whatever state its cameras have); empty_ms: the same bracket around nothing */
 int wz_profile_gated(wz_engine_t* e, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt, const int* cam,
                      double iou_thr, double ios_thr, int reps, float* activity_ms, float* commit_ms, float* empty_ms);
+/* the region kernel alone on two caller-provided grids ([cell rows][cell columns] uint16 of a w x h frame of format fmt; ref NULL: no
+ * reference), synchronous: the regions in the order they were accepted, every region's n, the components with n >= min_cells */
+int wz_stage_motion_regions(wz_engine_t* e, const uint16_t* now, const uint16_t* ref, int w, int h, int fmt, const wz_motion_t* motion,
+                            int32_t* n_regions, wz_tile_t* regions /* [WZ_MOTION_MAX_REGIONS] */, int32_t* cells /* [WZ_MOTION_MAX_REGIONS] */,
+                            int32_t* components);
+/* HIP-event time (ms, mean of reps) of the region launch alone on these two grids, and of the whole-frame activity launch of a w x h frame
+ * of format fmt (device memory of undefined content) alone; empty_ms: the same bracket around nothing */
+int wz_profile_motion(wz_engine_t* e, const uint16_t* now, const uint16_t* ref, int w, int h, int fmt, const wz_motion_t* motion, int reps,
+                      float* regions_ms, float* activity_ms, float* empty_ms, int32_t* rounds /* rounds of the labelling; 0: no changed cell */);
 /* in_place[i] = 1 where frame i of the last wz_submit_bound on `slot` -- untiled, tiled or gated -- was read in place through its device view,
  * 0 where it was staged by DMA (n values: the frames of that batch); WZ_EINVAL when the lane has seen no such batch */
 int wz_debug_bound_source(wz_engine_t* e, int slot, int32_t* in_place /* [n] */);

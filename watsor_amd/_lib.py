@@ -27,6 +27,7 @@ WZ_NUM_LABELS = 91
 WZ_MAX_CAMS = 256
 WZ_MAX_TILES = 64
 WZ_GATE_CELL = 16
+WZ_MOTION_MAX_REGIONS, WZ_MOTION_MAX_CELLS, WZ_MOTION_CANDIDATES = 16, 32768, 64
 WZ_SCHEDULE_THROUGHPUT, WZ_SCHEDULE_LATENCY = 0, 1
 
 c_u8p = C.POINTER(C.c_uint8)
@@ -71,6 +72,14 @@ SIGNATURES = {
     "wz_submit_gated_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, C.c_double,
                                          C.c_double]),
     "wz_gate_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "wz_set_camera_motion": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "wz_reset_camera_motion": (C.c_int, [C.c_void_p, C.c_int]),
+    "wz_clear_camera_motion": (C.c_int, [C.c_void_p, C.c_int]),
+    "wz_detect_motion": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, C.c_double, C.c_double,
+                                   C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_f32p]),
+    "wz_submit_motion_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, C.c_double,
+                                          C.c_double]),
+    "wz_motion_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "wz_collect": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "wz_bind_frames": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, C.POINTER(C.c_void_p)]),
     "wz_bind_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int]),
@@ -141,6 +150,9 @@ DEV_SIGNATURES = {
     "wz_profile_gated": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, C.c_double, C.c_double, C.c_int,
                                    c_f32p, c_f32p, c_f32p]),
     "wz_debug_bound_source": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "wz_stage_motion_regions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "wz_profile_motion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, c_f32p, c_f32p, c_f32p, c_i32p]),
     "wz_stage_merge_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                                        C.c_void_p, C.c_void_p]),
 }

@@ -457,3 +457,25 @@ struct WzGateCommit {      // one tile of a gated call, in tile order
 void wz_launch_tile_activity(const WzGateTile* tiles, int n, int max_crows, int max_cols, int32_t* counters, int32_t* activity, hipStream_t s);
 // the tiles that ran: new grid -> reference, batch_rows[fresh] -> cache; every tile: fresh or cached rows -> out[t][100]
 void wz_launch_gate_commit(const WzGateCommit* tiles, int n, const wz_detection_t* batch_rows, wz_detection_t* out, hipStream_t s);
+
+// ---- motion regions (k_motion.hip): behind the whole-frame activity launch, one workgroup per camera turns the grid of
+// changed cells into ranked rectangles
+#define WZ_MOTION_CANDIDATES 64   // components looked at, by rank
+#define WZ_MOTION_THREADS 1024
+struct WzMotionCam {
+    const uint16_t* now;   // the frame's grid [gh][gw], as the activity launch wrote it
+    const uint16_t* ref;   // the previous call's grid, or nullptr: no cell has changed
+    uint32_t* scratch;     // device memory, gw * gh words: the keys of the components (read only when there are more than the kernel ranks in LDS)
+    int32_t W, H, gw, gh, thr, min_cells, dilate, max_regions, min_side, pad;
+    int32_t even_x, even_y;   // the format cuts at even x / y only
+};
+struct WzMotionOut {       // what the host reads, in the lane's page-locked block
+    int32_t n_regions, components;   // regions accepted; components with n >= min_cells
+    wz_tile_t regions[WZ_MOTION_MAX_REGIONS];
+    int32_t cells[WZ_MOTION_MAX_REGIONS];   // n of every region
+    int32_t rounds, _pad;                   // rounds the labelling took (0: the picture was still), for the profiling entry point
+};
+// cams[n] (device-readable) -> out[n]; max_cells: the most cells any of the n grids has (at most WZ_MOTION_MAX_CELLS)
+void wz_launch_motion_regions(const WzMotionCam* cams, int n, int max_cells, WzMotionOut* out, hipStream_t s);
+// behind the merge and filter launches of a motion call: a frame without a tile (frames[f].n_tiles == 0) gets the padding rows and pass bytes 0
+void wz_launch_motion_still(const WzMergeFrame* frames, int n, wz_detection_t* rows, uint8_t* pass, hipStream_t s);

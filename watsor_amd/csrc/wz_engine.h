@@ -52,6 +52,18 @@ struct GateLane {
     int alloc(wz_engine* e);
     void release();
 };
+// motion regions (wz_submit_motion_device / wz_detect_motion): allocated the first time the lane sees a motion call
+struct MotionLane {
+    uint32_t* d_mscratch = nullptr;      // the region kernel's scratch [max_batch][cam_words]
+    int32_t* d_mcount = nullptr;         // the activity kernel's counters [max_batch][2]
+    uint8_t* h_mmeta = nullptr;          // pinned, device-mapped: WzGateTile[max_batch], WzMotionCam[max_batch], WzMotionOut[max_batch], int32[max_batch]
+    uint8_t* m_mmeta = nullptr;          // ... as the device sees it
+    size_t cam_words = 0;
+    std::vector<int32_t> s_ntiles, s_cells, s_comps;   // the last motion call accepted on this lane (wz_motion_stats): per frame its tiles,
+    std::vector<wz_tile_t> s_tiles;                    // [n][1 + WZ_MOTION_MAX_REGIONS], its regions' n [n][WZ_MOTION_MAX_REGIONS], its components
+    int alloc(wz_engine* e);             // (wz_tiles.hip) lazy; all or nothing
+    void release();
+};
 
 struct wz_engine {
     int device = 0;
@@ -131,6 +143,7 @@ struct wz_engine {
         std::vector<int32_t> bound_src;      // the last tiled or gated bound batch accepted on this lane (development library: the last bound batch of any kind): 1 = frame i was read in place, 0 = staged
         TileLane tile;
         GateLane gate;
+        MotionLane motion;
         hipEvent_t done = nullptr;
         int n = 0;
         bool rows = false;                       // the batch being enqueued runs the row-staged resize kernel (a frame of it is read in place)
@@ -200,6 +213,18 @@ struct wz_engine {
         void release();                          // (wz_tiles.hip) frees the two device blocks
     };
     std::map<int, GateCam> gate_cams;
+    // motion regions: a camera's settings and its two whole-frame grids (wz_set_camera_motion); empty until a camera is set.  The grid the
+    // last accepted call wrote is the reference of the next one: the two are swapped by pointer, nothing is copied.
+    struct MotionCam {
+        int w = 0, h = 0, base = 0, fmt = 0;     // the frames the settings were made for
+        int gw = 0, gh = 0;                      // cells of the whole frame
+        wz_motion_t p = {0, 1, 0, 1, 16, 0, 0, 0};
+        uint16_t* d_grid[2] = {nullptr, nullptr};
+        int cur = 0;                             // d_grid[cur] is the reference, d_grid[cur ^ 1] takes the next call's grid
+        bool has_ref = false;
+        void release();                          // (wz_tiles.hip) frees the two grids
+    };
+    std::map<int, MotionCam> motion_cams;
 
     std::vector<std::string> stage_names;   // stage_slots(op) names per op, between the fixed ones (wz_create)
     // what the op list alone says about op i (network_prepare): the next op is the only reader of its output (the extras pair's

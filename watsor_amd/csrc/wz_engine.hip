@@ -689,6 +689,7 @@ extern "C" void wz_destroy(wz_engine_t* e) {
     for (int32_t* p : e->cam_sat)
         if (p) (void)hipFree(p);
     for (auto& kv : e->gate_cams) kv.second.release();
+    for (auto& kv : e->motion_cams) kv.second.release();
     void* devp[] = {e->d_weights, e->d_zeros, e->d_mbdbg, e->d_anchors, e->d_frames, e->d_cams, e->d_tmp_rows, e->d_tmp_pass};
     for (void* p : devp)
         if (p) (void)hipFree(p);
@@ -709,6 +710,7 @@ extern "C" void wz_destroy(wz_engine_t* e) {
         if (L.h_stamps) (void)hipHostFree(L.h_stamps);
         L.tile.release();
         L.gate.release();
+        L.motion.release();
         if (L.done) (void)hipEventDestroy(L.done);
         if (L.stream && L.owns_stream) (void)hipStreamDestroy(L.stream);
     }

@@ -1,6 +1,7 @@
-// Tiled, gated and tiled frame-table detection (include/watsor_hip.h; DESIGN.md sections 15 - 17): eager launches of k_tiles.hip and
-// k_gate.hip around run_batch.  wz_engine.hip knows nothing of this file but TileLane / GateLane / GateCam's release, the lane's
-// `tile.tiled` and submit_bound_tiles (wz_engine.h).
+// Tiled, gated, motion-region and tiled frame-table detection (include/watsor_hip.h; DESIGN.md sections 15 - 17 and 19): eager launches of
+// k_tiles.hip, k_gate.hip and k_motion.hip around run_batch.  wz_engine.hip knows nothing of this file but TileLane / GateLane / MotionLane /
+// GateCam's and MotionCam's release, the lane's `tile.tiled` and submit_bound_tiles (wz_engine.h).
+#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -272,13 +273,15 @@ static int run_tiles(wz_engine* e, int slot, const TilePlan& y) {
 
 // ... and behind it: the merge of `src` (every tile's rows, in tile order), each frame's camera filter on its merged rows exactly as
 // wz_filter_rows applies it, and the lane's event (run_batch recorded it behind the batch: wz_wait / wz_collect must see the merge)
-static int merge_tail(wz_engine* e, Lane& L, const TileCall& c, int most, const wz_detection_t* src) {
+// still: a motion call with a frame that has no tile -- no filter runs on it, it gets the padding rows and pass bytes 0 (k_motion.hip)
+static int merge_tail(wz_engine* e, Lane& L, const TileCall& c, int most, const wz_detection_t* src, bool still = false) {
     TileLane& T = L.tile;
     const int32_t* m_origins = reinterpret_cast<const int32_t*>(T.m_tmeta + e->max_batch);
     wz_launch_merge_tiles(T.m_tmeta, m_origins, src, T.d_tcand, c.n, most, c.iou, c.ios, T.m_trows, T.m_tpass, L.stream);
     for (int i = 0; i < c.n; ++i)
-        if (c.cam && c.cam[i] >= 0 && e->h_cams[c.cam[i]].enabled)
+        if (c.cam && c.cam[i] >= 0 && e->h_cams[c.cam[i]].enabled && !(still && c.n_tiles[i] == 0))
             wz_launch_filter_rows(e->d_cams, c.cam[i], T.m_trows + (size_t)i * WZ_MAX_DETECTIONS, T.m_tpass + (size_t)i * WZ_MAX_DETECTIONS, L.stream);
+    if (still) wz_launch_motion_still(T.m_tmeta, c.n, T.m_trows, T.m_tpass, L.stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(L.done, L.stream));
     T.tiled = c.n;
@@ -385,19 +388,208 @@ static int gated_enqueue(wz_engine* e, int slot, const TileCall& call) {
     return WZ_OK;
 }
 
-// ---- the entry points of both kinds
-static int enqueue(wz_engine* e, int slot, const TileCall& c, bool gated) { return gated ? gated_enqueue(e, slot, c) : tiled_enqueue(e, slot, c); }
+
+// ---- motion regions: whole-frame activity launch -> region launch -> the host reads the rectangles -> a tiled call on them (k_motion.hip,
+// DESIGN.md section 19)
+typedef wz_engine::MotionCam MotionCam;
+
+void MotionCam::release() {
+    for (uint16_t*& g : d_grid) {
+        if (g) (void)hipFree(g);
+        g = nullptr;
+    }
+}
+
+static size_t motion_cam_words(const wz_engine* e) { return std::min((size_t)WZ_MOTION_MAX_CELLS, gate_cells_of(e->max_w, e->max_h)); }
+// the pinned block of a lane: the activity launch's whole-frame tiles, the region launch's cameras, what it found, the activity counts (unused)
+static WzGateTile* motion_tiles(uint8_t* meta) { return reinterpret_cast<WzGateTile*>(meta); }
+static WzMotionCam* motion_descs(const wz_engine* e, uint8_t* meta) { return reinterpret_cast<WzMotionCam*>(motion_tiles(meta) + e->max_batch); }
+static WzMotionOut* motion_outs(const wz_engine* e, uint8_t* meta) { return reinterpret_cast<WzMotionOut*>(motion_descs(e, meta) + e->max_batch); }
+static int32_t* motion_activity(const wz_engine* e, uint8_t* meta) { return reinterpret_cast<int32_t*>(motion_outs(e, meta) + e->max_batch); }
+static_assert(sizeof(WzGateTile) % 8 == 0 && sizeof(WzMotionCam) % 8 == 0 && sizeof(WzMotionOut) % 8 == 0, "the block's parts stay aligned");
+
+int MotionLane::alloc(wz_engine* e) {
+    if (d_mscratch) return WZ_OK;
+    const size_t nb = (size_t)e->max_batch, words = motion_cam_words(e);
+    MotionLane m;
+    hipError_t err = hipMalloc((void**)&m.d_mscratch, words * 4 * nb);
+    if (err == hipSuccess) err = hipMalloc((void**)&m.d_mcount, 8 * nb);
+    if (err == hipSuccess) err = lane0_fill(e, m.d_mcount, 0, 8 * nb);
+    if (err == hipSuccess) err = hipHostMalloc((void**)&m.h_mmeta, (sizeof(WzGateTile) + sizeof(WzMotionCam) + sizeof(WzMotionOut) + 8) * nb, hipHostMallocMapped);
+    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&m.m_mmeta, m.h_mmeta, 0);
+    if (err != hipSuccess) {
+        m.release();
+        return wz_set_error(WZ_EHIP, "motion scratch of a lane: %s", hipGetErrorString(err));
+    }
+    d_mscratch = m.d_mscratch; d_mcount = m.d_mcount; h_mmeta = m.h_mmeta; m_mmeta = m.m_mmeta; cam_words = words;
+    return WZ_OK;
+}
+void MotionLane::release() {
+    if (d_mscratch) (void)hipFree(d_mscratch);
+    if (d_mcount) (void)hipFree(d_mcount);
+    if (h_mmeta) (void)hipHostFree(h_mmeta);
+    d_mscratch = nullptr; d_mcount = nullptr; h_mmeta = m_mmeta = nullptr;
+}
+
+// Why these settings are refused for a w x h frame of format word fmt (wz_last_error is set), or WZ_OK; e null: the engine's limits are not looked at
+static int motion_refusal(const wz_engine* e, const char* who, int w, int h, int fmt, const wz_motion_t& p) {
+    if (!wz_frame_bytes(w, h, fmt)) return wz_set_error(WZ_EINVAL, "%s: pixel format 0x%x at %dx%d: %s", who, fmt, w, h, fmt_refusal(w, h, fmt));
+    if (p.pixel_thr < 0 || p.pixel_thr > 255 || p.min_cells < 1 || p.dilate < 0 || p.dilate > 2 || p.max_regions < 1 || p.max_regions > WZ_MOTION_MAX_REGIONS ||
+        p.min_side < WZ_GATE_CELL || p.pad < 0 || p.pad > 64 || (p.whole_frame != 0 && p.whole_frame != 1))
+        return wz_set_error(WZ_EINVAL, "%s: motion (%d, %d, %d, %d, %d, %d, %d): pixel_thr must be 0 .. 255, min_cells >= 1, dilate 0 .. 2, max_regions 1 .. %d, "
+                            "min_side >= %d, pad 0 .. 64, whole_frame 0 or 1", who, p.pixel_thr, p.min_cells, p.dilate, p.max_regions, p.min_side, p.pad,
+                            p.whole_frame, WZ_MOTION_MAX_REGIONS, WZ_GATE_CELL);
+    if (e && (w > e->max_w || h > e->max_h || (size_t)w * h * 3 > e->frame_stride))
+        return wz_set_error(WZ_ELIMIT, "%s: the frame is %dx%d, engine was created for at most %dx%d", who, w, h, e->max_w, e->max_h);
+    if (gate_cells_of(w, h) > (size_t)WZ_MOTION_MAX_CELLS)
+        return wz_set_error(WZ_ELIMIT, "%s: a %dx%d frame has %zu cells, a motion camera takes at most %d", who, w, h, gate_cells_of(w, h), WZ_MOTION_MAX_CELLS);
+    if (e && p.whole_frame + p.max_regions > e->max_batch)
+        return wz_set_error(WZ_ELIMIT, "%s: whole_frame + max_regions = %d tiles exceed max_batch %d", who, p.whole_frame + p.max_regions, e->max_batch);
+    return WZ_OK;
+}
+
+// what the region kernel gets for a w x h frame of format word fmt
+static void motion_desc(int w, int h, int fmt, const wz_motion_t& p, const uint16_t* now, const uint16_t* ref, uint32_t* scratch, WzMotionCam& d) {
+    const int base = fmt & WZ_FMT_BASE_MASK;
+    const bool planar = base == WZ_FMT_NV12 || base == WZ_FMT_I420 || base == WZ_FMT_P010 || base == WZ_FMT_YUV420P10;
+    d.now = now; d.ref = ref; d.scratch = scratch;
+    d.W = w; d.H = h;
+    d.gw = (w + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
+    d.gh = (h + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
+    d.thr = p.pixel_thr; d.min_cells = p.min_cells; d.dilate = p.dilate; d.max_regions = p.max_regions; d.min_side = p.min_side; d.pad = p.pad;
+    d.even_x = (planar || base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422) ? 1 : 0;
+    d.even_y = planar ? 1 : 0;
+}
+
+// Every refusal of a motion call (include/watsor_hip.h), before anything is enqueued, written or found
+static int motion_check(wz_engine* e, const char* who, int slot, TileCall& c, bool host) {
+    int rc = call_refusal(e, who, slot, c, false);
+    if (rc != WZ_OK) return rc;
+    const int* cam = c.cam;
+    if (!cam) return wz_set_error(WZ_EINVAL, "%s: a motion call needs the frames' camera ids", who);
+    int64_t sum = 0;
+    for (int i = 0; i < c.n; ++i) {
+        const int w = c.w[i], h = c.h[i], pf = c.pf(i);
+        auto refused = [&](unsigned checks) { return (rc = frame_refusal(e, "frame", i, c.frames[i], w, h, pf, cam[i], checks)) != WZ_OK; };
+        if (refused(FC_PTR)) return rc;
+        auto it = cam[i] < 0 ? e->motion_cams.end() : e->motion_cams.find(cam[i]);
+        if (it == e->motion_cams.end()) return wz_set_error(WZ_EINVAL, "frame %d: camera %d has no motion settings (wz_set_camera_motion first)", i, cam[i]);
+        for (int j = 0; j < i; ++j)
+            if (cam[j] == cam[i]) return wz_set_error(WZ_EINVAL, "frames %d and %d are both camera %d's: one frame of a camera per motion call", j, i, cam[i]);
+        const MotionCam& m = it->second;
+        if (refused(FC_FMT)) return rc;
+        if (w != m.w || h != m.h || (pf & WZ_FMT_BASE_MASK) != m.base)
+            return wz_set_error(WZ_EINVAL, "frame %d is %dx%d in base format %d but camera %d's motion settings were made for %dx%d in base format %d", i, w, h,
+                                pf & WZ_FMT_BASE_MASK, cam[i], m.w, m.h, m.base);
+        if (refused((host ? FC_LIMIT : 0) | FC_CAM_FILTER)) return rc;
+        sum += m.p.whole_frame + m.p.max_regions;
+    }
+    if (sum > e->max_batch)
+        return wz_set_error(WZ_ELIMIT, "the %lld tiles configured for the cameras of one call (whole_frame + max_regions) exceed max_batch %d", (long long)sum,
+                            e->max_batch);
+    c.total = 0;
+    return thresholds_refusal(who, c);
+}
+
+// A checked motion call on a drained lane, frames in device memory.  Returns once the rectangles are read: the two launches that touch the
+// cameras' grids have finished by then (no other lane can hold a camera's motion state in flight); crop, batch, merge and filters are
+// enqueued behind, and the lane's event behind them.
+static int motion_enqueue(wz_engine* e, int slot, const TileCall& call) {
+    Lane& L = e->lanes[slot];
+    MotionLane& M = L.motion;
+    WZCHK(L.tile.alloc(e));
+    WZCHK(M.alloc(e));
+    const int n = call.n;
+    constexpr int PER = 1 + WZ_MOTION_MAX_REGIONS;
+    std::vector<MotionCam*> cams(n);
+    // 1. the whole frame's grid of every camera, one launch; 2. its regions, one launch; then the one wait of the call
+    WzGateTile* gt = motion_tiles(M.h_mmeta);
+    WzMotionCam* md = motion_descs(e, M.h_mmeta);
+    WzMotionOut* mo = motion_outs(e, M.h_mmeta);
+    int crows = 0, cols = 0, cells = 0;
+    for (int i = 0; i < n; ++i) {
+        MotionCam& m = *(cams[i] = &e->motion_cams.find(call.cam[i])->second);
+        const wz_tile_t whole = {0, 0, m.w, m.h};
+        uint16_t* now = m.d_grid[m.cur ^ 1];
+        gate_tile(call.frames[i], m.w, call.pf(i), whole, gt[i]);
+        gt[i].ref = nullptr;   // (the region launch compares: this launch only sums)
+        gt[i].now = now;
+        gt[i].thr = 0;
+        motion_desc(m.w, m.h, call.pf(i), m.p, now, m.has_ref ? m.d_grid[m.cur] : nullptr, M.d_mscratch + M.cam_words * i, md[i]);
+        crows = std::max(crows, gt[i].crows);
+        cols = std::max(cols, gt[i].cols);
+        cells = std::max(cells, m.gw * m.gh);
+        mo[i].n_regions = -1;
+    }
+    wz_launch_tile_activity(motion_tiles(M.m_mmeta), n, crows, cols, M.d_mcount, motion_activity(e, M.m_mmeta), L.stream);
+    wz_launch_motion_regions(motion_descs(e, M.m_mmeta), n, cells, motion_outs(e, M.m_mmeta), L.stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(L.stream));   // the batch size is a host-side quantity: the plan waits for the rectangles
+    // 3. the tile lists; the cameras' state changes only once everything is enqueued
+    std::vector<wz_tile_t> tiles((size_t)n * PER);
+    std::vector<int32_t> nt(n), comps(n), ncell((size_t)n * WZ_MOTION_MAX_REGIONS, 0);
+    std::vector<const wz_tile_t*> tp(n);
+    int total = 0;
+    bool still = false;
+    for (int i = 0; i < n; ++i) {
+        const MotionCam& m = *cams[i];
+        const WzMotionOut& o = mo[i];
+        if (o.n_regions < 0 || o.n_regions > m.p.max_regions) return wz_set_error(WZ_EHIP, "frame %d: the region launch reported %d regions", i, o.n_regions);
+        wz_tile_t* t = &tiles[(size_t)i * PER];
+        int k = 0;
+        if (m.p.whole_frame) t[k++] = {0, 0, m.w, m.h};
+        for (int r = 0; r < o.n_regions; ++r, ++k) {
+            t[k] = o.regions[r];
+            ncell[(size_t)i * WZ_MOTION_MAX_REGIONS + r] = o.cells[r];
+        }
+        for (int j = 0; j < k; ++j) WZCHK(tile_fits(e, "frame", i, m.w, m.h, call.pf(i), j, t[j]));
+        nt[i] = k;
+        tp[i] = t;
+        comps[i] = o.components;
+        total += k;
+        still = still || k == 0;
+    }
+    TileCall c = call;   // ... a tiled call on these lists
+    c.n_tiles = nt.data();
+    c.tiles = tp.data();
+    c.total = total;
+    TilePlan y;
+    tile_plan(e, L, c, nullptr, y);
+    if (!y.tptr.empty()) {
+        WZCHK(run_tiles(e, slot, y));
+    } else {
+        L.bound_idx.clear();
+        L.n = 0;   // (no tile: no crop, no batch, no status word is this call's)
+    }
+    WZCHK(merge_tail(e, L, c, y.most, L.m_rows, still));
+    // 4. the grid this call wrote is the next call's reference; what wz_motion_stats reports
+    for (int i = 0; i < n; ++i) {
+        cams[i]->cur ^= 1;
+        cams[i]->has_ref = true;
+    }
+    M.s_ntiles.swap(nt);
+    M.s_tiles.swap(tiles);
+    M.s_cells.swap(ncell);
+    M.s_comps.swap(comps);
+    return WZ_OK;
+}
+
+// ---- the entry points of the three kinds
+enum { KIND_TILED = 0, KIND_GATED = 1, KIND_MOTION = 2 };
+static int enqueue(wz_engine* e, int slot, const TileCall& c, int kind) {
+    return kind == KIND_MOTION ? motion_enqueue(e, slot, c) : kind == KIND_GATED ? gated_enqueue(e, slot, c) : tiled_enqueue(e, slot, c);
+}
 
 // a checked call of frames in device memory, on its lane once the lane's previous batch has fully drained
-static int submit_device(wz_engine* e, int slot, const TileCall& c, bool gated) {
+static int submit_device(wz_engine* e, int slot, const TileCall& c, int kind) {
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipEventSynchronize(e->lanes[slot].done));
-    return enqueue(e, slot, c, gated);
+    return enqueue(e, slot, c, kind);
 }
 
 // a checked call of host frames on lane 0, start to rows: every frame whole into the lane's staging area, as wz_submit_host_fmt stages it
 // (the tiles are cut from that copy), enqueue, collect, the wall time into ms
-static int detect_staged(wz_engine* e, TileCall& c, bool gated, wz_detection_t* const* out, uint8_t* const* pass, float* ms) {
+static int detect_staged(wz_engine* e, TileCall& c, int kind, wz_detection_t* const* out, uint8_t* const* pass, float* ms) {
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(hipSetDevice(e->device));
     Lane& L = e->lanes[0];
@@ -405,7 +597,7 @@ static int detect_staged(wz_engine* e, TileCall& c, bool gated, wz_detection_t* 
     std::vector<const uint8_t*> dptr(c.n);
     for (int i = 0; i < c.n; ++i) WZCHK(stage_frame(e, L, i, c.frames[i], wz_frame_bytes(c.w[i], c.h[i], c.pf(i)), &dptr[i]));
     c.frames = dptr.data();
-    WZCHK(enqueue(e, 0, c, gated));
+    WZCHK(enqueue(e, 0, c, kind));
     const int rc = wz_collect(e, 0, out, pass);
     if (rc != WZ_OK && rc != WZ_EINCOMPLETE) return rc;
     const float el = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -419,26 +611,26 @@ extern "C" int wz_submit_tiled_device(wz_engine_t* e, int slot, int n, const uin
                                       double iou_thr, double ios_thr) {
     TileCall c = {n, d_frames, w, h, fmt, cam, n_tiles, tiles, iou_thr, ios_thr, 0};
     WZCHK(tiled_check(e, "wz_submit_tiled_device", slot, c, false));
-    return submit_device(e, slot, c, false);
+    return submit_device(e, slot, c, KIND_TILED);
 }
 extern "C" int wz_detect_tiled(wz_engine_t* e, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt,
                                const int* cam, const int* n_tiles, const wz_tile_t* const* tiles, double iou_thr, double ios_thr,
                                wz_detection_t* const* out, uint8_t* const* pass, float* ms) {
     TileCall c = {n, frames, w, h, fmt, cam, n_tiles, tiles, iou_thr, ios_thr, 0};
     WZCHK(tiled_check(e, "wz_detect_tiled", 0, c, true));
-    return detect_staged(e, c, false, out, pass, ms);
+    return detect_staged(e, c, KIND_TILED, out, pass, ms);
 }
 extern "C" int wz_submit_gated_device(wz_engine_t* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
                                       const int* cam, double iou_thr, double ios_thr) {
     TileCall c = {n, d_frames, w, h, fmt, cam, nullptr, nullptr, iou_thr, ios_thr, 0};
     WZCHK(gated_check(e, "wz_submit_gated_device", slot, c, false));
-    return submit_device(e, slot, c, true);
+    return submit_device(e, slot, c, KIND_GATED);
 }
 extern "C" int wz_detect_gated(wz_engine_t* e, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt, const int* cam,
                                double iou_thr, double ios_thr, wz_detection_t* const* out, uint8_t* const* pass, float* ms) {
     TileCall c = {n, frames, w, h, fmt, cam, nullptr, nullptr, iou_thr, ios_thr, 0};
     WZCHK(gated_check(e, "wz_detect_gated", 0, c, true));
-    return detect_staged(e, c, true, out, pass, ms);
+    return detect_staged(e, c, KIND_GATED, out, pass, ms);
 }
 
 extern "C" int wz_gate_stats(wz_engine_t* e, int slot, int n, uint64_t* ran_mask, int32_t* activity) {
@@ -448,6 +640,79 @@ extern "C" int wz_gate_stats(wz_engine_t* e, int slot, int n, uint64_t* ran_mask
         return wz_set_error(WZ_EINVAL, "wz_gate_stats: the last gated call on lane %d had %d frames, not %d", slot, (int)G.g_ran.size(), n);
     memcpy(ran_mask, G.g_ran.data(), sizeof(uint64_t) * n);
     if (activity) memcpy(activity, G.g_act.data(), sizeof(int32_t) * G.g_act.size());
+    return WZ_OK;
+}
+
+
+// ---- a camera's motion settings, and the motion calls
+extern "C" int wz_set_camera_motion(wz_engine_t* e, int cam, int width, int height, int fmt, const wz_motion_t* motion) {
+    if (!e || !motion) return wz_set_error(WZ_EINVAL, "wz_set_camera_motion: null argument");
+    if (cam < 0 || cam >= WZ_MAX_CAMS) return wz_set_error(WZ_ELIMIT, "camera id %d out of range [0,%d)", cam, WZ_MAX_CAMS);
+    char who[48];
+    snprintf(who, sizeof who, "camera %d", cam);
+    WZCHK(motion_refusal(e, who, width, height, fmt, *motion));
+    MotionCam m;
+    m.w = width; m.h = height; m.fmt = fmt; m.base = fmt & WZ_FMT_BASE_MASK;
+    m.gw = (width + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
+    m.gh = (height + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
+    m.p = *motion;
+    m.p._reserved = 0;
+    HIPCHK(hipSetDevice(e->device));
+    WZCHK(sync_all(e));
+    // the new grids are allocated aside: a failure leaves the camera with the settings (and the reference) it had
+    hipError_t err = hipMalloc((void**)&m.d_grid[0], (size_t)m.gw * m.gh * 2);
+    if (err == hipSuccess) err = hipMalloc((void**)&m.d_grid[1], (size_t)m.gw * m.gh * 2);
+    if (err != hipSuccess) {
+        m.release();
+        return wz_set_error(WZ_EHIP, "wz_set_camera_motion: %s (camera %d keeps its previous settings)", hipGetErrorString(err), cam);
+    }
+    auto it = e->motion_cams.find(cam);
+    if (it != e->motion_cams.end()) it->second.release();   // nothing in flight reads the old grids: every lane was synchronised above
+    e->motion_cams[cam] = m;
+    return WZ_OK;
+}
+
+extern "C" int wz_reset_camera_motion(wz_engine_t* e, int cam) {
+    if (!e) return wz_set_error(WZ_EINVAL, "wz_reset_camera_motion: null engine");
+    auto it = e->motion_cams.find(cam);
+    if (it == e->motion_cams.end()) return wz_set_error(WZ_EINVAL, "camera %d has no motion settings (wz_set_camera_motion first)", cam);
+    it->second.has_ref = false;   // (a motion call leaves no launch in flight that reads the grids: nothing to wait for)
+    return WZ_OK;
+}
+
+extern "C" int wz_clear_camera_motion(wz_engine_t* e, int cam) {
+    if (!e || cam < 0 || cam >= WZ_MAX_CAMS) return wz_set_error(WZ_EINVAL, "wz_clear_camera_motion: bad argument");
+    auto it = e->motion_cams.find(cam);
+    if (it == e->motion_cams.end()) return WZ_OK;
+    HIPCHK(hipSetDevice(e->device));
+    WZCHK(sync_all(e));
+    it->second.release();
+    e->motion_cams.erase(it);
+    return WZ_OK;
+}
+
+extern "C" int wz_submit_motion_device(wz_engine_t* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
+                                       const int* cam, double iou_thr, double ios_thr) {
+    TileCall c = {n, d_frames, w, h, fmt, cam, nullptr, nullptr, iou_thr, ios_thr, 0};
+    WZCHK(motion_check(e, "wz_submit_motion_device", slot, c, false));
+    return submit_device(e, slot, c, KIND_MOTION);
+}
+extern "C" int wz_detect_motion(wz_engine_t* e, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt, const int* cam,
+                                double iou_thr, double ios_thr, wz_detection_t* const* out, uint8_t* const* pass, float* ms) {
+    TileCall c = {n, frames, w, h, fmt, cam, nullptr, nullptr, iou_thr, ios_thr, 0};
+    WZCHK(motion_check(e, "wz_detect_motion", 0, c, true));
+    return detect_staged(e, c, KIND_MOTION, out, pass, ms);
+}
+
+extern "C" int wz_motion_stats(wz_engine_t* e, int slot, int n, int32_t* n_tiles, wz_tile_t* tiles, int32_t* cells, int32_t* components) {
+    if (!e || !n_tiles || slot < 0 || slot >= e->n_lanes) return wz_set_error(WZ_EINVAL, "wz_motion_stats: bad argument");
+    const MotionLane& M = e->lanes[slot].motion;
+    if (n < 1 || n != (int)M.s_ntiles.size())
+        return wz_set_error(WZ_EINVAL, "wz_motion_stats: the last motion call on lane %d had %d frames, not %d", slot, (int)M.s_ntiles.size(), n);
+    memcpy(n_tiles, M.s_ntiles.data(), sizeof(int32_t) * n);
+    if (tiles) memcpy(tiles, M.s_tiles.data(), sizeof(wz_tile_t) * M.s_tiles.size());
+    if (cells) memcpy(cells, M.s_cells.data(), sizeof(int32_t) * M.s_cells.size());
+    if (components) memcpy(components, M.s_comps.data(), sizeof(int32_t) * n);
     return WZ_OK;
 }
 
@@ -624,7 +889,7 @@ int submit_bound_tiles(wz_engine* e, int slot, int n, const int32_t* entries) {
         }
         WZCHK(stage_frame(e, L, i, f.host, f.bytes, &b.ptr[i]));
     }
-    WZCHK(enqueue(e, slot, c, gated));
+    WZCHK(enqueue(e, slot, c, gated ? KIND_GATED : KIND_TILED));
     L.bound_idx.assign(entries, entries + n);   // (L.tile.tiled == n says that their rows are the merged ones)
     L.bound_src.swap(src);
     return WZ_OK;
@@ -819,5 +1084,93 @@ extern "C" int wz_profile_gated(wz_engine_t* e, int n, const uint8_t* const* d_f
                      activity_ms));
     WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_gate_commit(gate_commits(e, G.m_gmeta), G.g_tiles, L.m_rows, G.d_grows, L.stream); }, commit_ms));
     return bracket_ms(L.stream, reps, [] {}, empty_ms);
+}
+
+// Two caller-provided grids of a w x h frame, the region kernel's descriptor, its scratch and its output in one device block
+struct MotionStage {
+    uint8_t* d = nullptr;
+    WzMotionCam* cam = nullptr;
+    WzMotionOut* out = nullptr;
+    int cells = 0;
+    size_t off_free = 0, all = 0;   // bytes behind the output that the caller may use (256)
+    ~MotionStage() { if (d) (void)hipFree(d); }
+};
+static int motion_stage(wz_engine* e, const char* who, const uint16_t* now, const uint16_t* ref, int w, int h, int fmt, const wz_motion_t* p, MotionStage& s) {
+    if (!e || !now || !p) return wz_set_error(WZ_EINVAL, "%s: null argument", who);
+    WZCHK(motion_refusal(nullptr, who, w, h, fmt, *p));
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const size_t cells = gate_cells_of(w, h), grid = (cells * 2 + 15) & ~(size_t)15;
+    const size_t off_scratch = 2 * grid, off_cam = off_scratch + ((cells * 4 + 15) & ~(size_t)15), off_out = off_cam + 80, off_free = off_out + 336, all = off_free + 256;
+    static_assert(sizeof(WzMotionCam) <= 80 && sizeof(WzMotionOut) <= 336, "the descriptor's and the output's slots");
+    HIPCHK(hipMalloc((void**)&s.d, all));
+    WzMotionCam d;
+    motion_desc(w, h, fmt, *p, reinterpret_cast<const uint16_t*>(s.d), ref ? reinterpret_cast<const uint16_t*>(s.d + grid) : nullptr,
+                reinterpret_cast<uint32_t*>(s.d + off_scratch), d);
+    HIPCHK(hipMemset(s.d, 0, all));
+    HIPCHK(hipMemcpy(s.d, now, cells * 2, hipMemcpyHostToDevice));
+    if (ref) HIPCHK(hipMemcpy(s.d + grid, ref, cells * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s.d + off_cam, &d, sizeof(d), hipMemcpyHostToDevice));
+    s.cam = reinterpret_cast<WzMotionCam*>(s.d + off_cam);
+    s.out = reinterpret_cast<WzMotionOut*>(s.d + off_out);
+    s.cells = (int)cells;
+    s.off_free = off_free;
+    s.all = all;
+    return WZ_OK;
+}
+
+// wz_k_motion_regions alone on two caller-provided grids
+extern "C" int wz_stage_motion_regions(wz_engine_t* e, const uint16_t* now, const uint16_t* ref, int w, int h, int fmt, const wz_motion_t* motion,
+                                       int32_t* n_regions, wz_tile_t* regions, int32_t* cells, int32_t* components) {
+    if (!n_regions || !regions || !cells || !components) return wz_set_error(WZ_EINVAL, "wz_stage_motion_regions: null argument");
+    MotionStage s;
+    WZCHK(motion_stage(e, "wz_stage_motion_regions", now, ref, w, h, fmt, motion, s));
+    wz_launch_motion_regions(s.cam, 1, s.cells, s.out, e->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
+    WzMotionOut o;
+    HIPCHK(hipMemcpy(&o, s.out, sizeof(o), hipMemcpyDeviceToHost));
+    *n_regions = o.n_regions;
+    *components = o.components;
+    memcpy(regions, o.regions, sizeof(o.regions));
+    memcpy(cells, o.cells, sizeof(o.cells));
+    return WZ_OK;
+}
+
+// HIP-event time of the region launch alone on these grids, and of the whole-frame activity launch of such a frame (constant bytes) alone
+extern "C" int wz_profile_motion(wz_engine_t* e, const uint16_t* now, const uint16_t* ref, int w, int h, int fmt, const wz_motion_t* motion, int reps,
+                                 float* regions_ms, float* activity_ms, float* empty_ms, int32_t* rounds) {
+    if (reps < 1 || !rounds || !regions_ms || !activity_ms || !empty_ms) return wz_set_error(WZ_EINVAL, "wz_profile_motion: bad argument");
+    MotionStage s;
+    WZCHK(motion_stage(e, "wz_profile_motion", now, ref, w, h, fmt, motion, s));
+    WZCHK(bracket_ms(e->stream, reps, [&] { wz_launch_motion_regions(s.cam, 1, s.cells, s.out, e->stream); }, regions_ms));
+    WzMotionOut o;
+    HIPCHK(hipMemcpy(&o, s.out, sizeof(o), hipMemcpyDeviceToHost));
+    *rounds = o.rounds;
+    const uint64_t bytes = wz_frame_bytes(w, h, fmt);
+    uint8_t* d_frame = nullptr;
+    uint16_t* d_grid = nullptr;
+    hipError_t err = hipMalloc((void**)&d_frame, bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&d_grid, (size_t)s.cells * 2);
+    if (err == hipSuccess) err = hipMemset(d_frame, 0x55, bytes);
+    int rc = WZ_OK;
+    if (err == hipSuccess) {
+        static_assert(sizeof(WzGateTile) <= 64, "the descriptor's slot");
+        const wz_tile_t whole = {0, 0, w, h};
+        WzGateTile g;
+        gate_tile(d_frame, w, fmt, whole, g);
+        g.ref = nullptr;
+        g.now = d_grid;
+        g.thr = 0;
+        WzGateTile* d_g = reinterpret_cast<WzGateTile*>(s.d + s.off_free);                // (64 bytes, then the counters and the count: zero)
+        int32_t* cnt = reinterpret_cast<int32_t*>(s.d + s.off_free + 64);
+        err = hipMemcpy(d_g, &g, sizeof(g), hipMemcpyHostToDevice);
+        if (err == hipSuccess) rc = bracket_ms(e->stream, reps, [&] { wz_launch_tile_activity(d_g, 1, g.crows, g.cols, cnt, cnt + 2, e->stream); }, activity_ms);
+    }
+    if (d_frame) (void)hipFree(d_frame);
+    if (d_grid) (void)hipFree(d_grid);
+    if (err != hipSuccess) return wz_set_error(WZ_EHIP, "wz_profile_motion: %s", hipGetErrorString(err));
+    WZCHK(rc);
+    return bracket_ms(e->stream, reps, [] {}, empty_ms);
 }
 #endif   // WZ_DEV_BUILD

@@ -32,7 +32,8 @@ differences, all inside the worker process:
     batch costs the worker one call with a list of table indices and one call to collect;
   * a detector with a `tiles` option goes through `detect_batch()`, one call at a time -- or, with `kwargs['hip_tiled_table']`, stays
     asynchronous: its frame table carries the tiles (`wz_bind_tiles`), a batch is cut by the detector's `plan_bound()` into tiled / gated
-    calls, each on a lane of its own.
+    calls, each on a lane of its own;
+  * a detector with a `motion` option goes through `detect_batch()` as well (motion regions keep a reference per camera).
 
 This module needs the reference package (`watsor.stream`) at run time -- it is a drop-in for an
 installed Watsor, see INTEGRATION.md.  Everything below `detect_batch()` does not.
@@ -117,6 +118,11 @@ class BatchedWorkerMixin:
                     # form, the frame table only on request (`hip_tiled_table`), and nothing may be detected untiled in silence
                     st["asynchronous"] = False
                     self._info("tiles are configured: batches go through detect_batch(), one call at a time")
+            if st["asynchronous"] and getattr(object_detector, "motion", False):
+                # motion regions (plugin option `motion`) keep a reference per camera and go through detect_batch() with camera ids: neither
+                # the asynchronous host path nor the frame table has a form for them
+                st["asynchronous"] = False
+                self._info("motion is configured: batches go through detect_batch(), one call at a time")
             lanes = getattr(object_detector, "num_lanes", 1)
             st["lanes"] = max(1, min(int(kwargs.get("hip_lanes", lanes)), lanes))
         if st["asynchronous"] and st["plan"] is None and kwargs.get("hip_frame_table", True) and hasattr(object_detector, "bind_frame_table"):

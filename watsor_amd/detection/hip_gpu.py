@@ -24,7 +24,7 @@ import numpy as np
 
 from ..runtime import (CSP_BT709, FMT_BASE_MASK, FMT_GRAY8, FMT_I420, FMT_NV12, FMT_P010, FMT_RGB24, FMT_UYVY422, FMT_YUV420P10,
                        FMT_YUYV422, RANGE_FULL, TEN_BIT_FORMATS, YUV_FORMATS, HipEngine, tile_grid)
-from .._lib import WZ_MAX_TILES
+from .._lib import WZ_MAX_TILES, WZ_MOTION_MAX_REGIONS
 from ..share import Detection
 
 # what a decoder's `-pix_fmt` may say (watsor/stream/ffmpeg.py:78-88 reads whatever it writes; the reference's schema asks for
@@ -170,6 +170,69 @@ def tile_options(options: dict):
     return None, {str(name): _tile_spec(spec, "tiles[%r]" % (name,)) for name, spec in v.items()}
 
 
+_MOTION_KEYS = {"threshold", "min_cells", "dilate", "max_regions", "min_side", "pad", "whole_frame", "iou", "ios"}
+# key -> (default, smallest, largest or None) of the whole numbers of a `motion` description
+_MOTION_RANGES = {"threshold": (None, 0, 255), "min_cells": (1, 1, None), "dilate": (1, 0, 2), "max_regions": (3, 1, WZ_MOTION_MAX_REGIONS),
+                  "min_side": (300, 16, None), "pad": (8, 0, 64)}
+
+
+def _motion_spec(spec, where: str) -> dict:
+    """One checked `motion` option: {"threshold": 0 .. 255, "min_cells": >= 1 (default 1), "dilate": 0 .. 2 (1), "max_regions": 1 .. 16 (3),
+    "min_side": >= 16 (300), "pad": 0 .. 64 (8), "whole_frame": true | false (true), "iou": ..., "ios": ...} -- find the parts of the picture
+    that moved since the camera's previous frame and run the detector there at the camera's own resolution
+    (`HipEngine.set_camera_motion`).  Anything else raises ValueError."""
+    if not isinstance(spec, dict) or "threshold" not in spec:
+        raise ValueError("%s: expected {\"threshold\": 0 .. 255, \"min_cells\": >= 1, \"dilate\": 0 .. 2, \"max_regions\": 1 .. %d, \"min_side\": >= 16, "
+                         "\"pad\": 0 .. 64, \"whole_frame\": true | false}, got %r" % (where, WZ_MOTION_MAX_REGIONS, spec))
+    if set(spec) - _MOTION_KEYS:
+        raise ValueError("%s: unknown key(s) %s" % (where, ", ".join(sorted(map(str, set(spec) - _MOTION_KEYS)))))
+    out = {"iou": spec.get("iou"), "ios": spec.get("ios")}
+    for k in ("iou", "ios"):
+        v = out[k]
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float)) or not v >= 0):
+            raise ValueError("%s: %s %r, expected a number >= 0" % (where, k, v))
+    for k, (default, low, high) in _MOTION_RANGES.items():
+        v = spec.get(k, default)
+        if not isinstance(v, int) or isinstance(v, bool):
+            raise ValueError("%s: %s %r, expected a whole number" % (where, k, v))
+        if v < low or (high is not None and v > high):
+            raise ValueError("%s: %s %r, expected %s" % (where, k, v, ">= %d" % low if high is None else "%d .. %d" % (low, high)))
+        out[k] = v
+    whole = spec.get("whole_frame", True)
+    if not isinstance(whole, bool):
+        raise ValueError("%s: whole_frame %r, expected true or false" % (where, whole))
+    out.update(whole_frame=whole, count=(1 if whole else 0) + out["max_regions"])
+    return out
+
+
+def motion_options(options: dict):
+    """(the detector's motion settings or None, {camera name: settings}) from the plugin option `motion`: one description (see
+    `_motion_spec`) for every camera, or {camera name: description}.  Bad options raise ValueError."""
+    v = options.get("motion")
+    if v is None:
+        return None, {}
+    if isinstance(v, dict) and "threshold" in v:
+        return _motion_spec(v, "motion"), {}
+    if not isinstance(v, dict) or not v or not all(isinstance(d, dict) for d in v.values()):
+        raise ValueError("motion: expected a description of the motion settings or {camera name: description}, got %r" % (v,))
+    return None, {str(name): _motion_spec(d, "motion[%r]" % (name,)) for name, d in v.items()}
+
+
+def check_motion_options(motion_default, motion_by_name: dict, tiles_default, tiles_by_name: dict, max_batch: int) -> None:
+    """What `motion_options` cannot see on its own: the settings' whole_frame + max_regions must fit max_batch, and a camera takes `motion`
+    or `tiles`, not both.  Raises ValueError; the message begins with the option at fault."""
+    for where, spec in [("motion", motion_default)] + [("motion[%r]" % n, m) for n, m in motion_by_name.items()]:
+        if spec is not None and spec["count"] > max_batch:
+            raise ValueError("%s: whole_frame + max_regions = %d tiles per frame exceed max_batch %d" % (where, spec["count"], max_batch))
+    if motion_default is not None and (tiles_default is not None or tiles_by_name):
+        raise ValueError("motion: set for every camera together with tiles: a camera takes one of the two")
+    if tiles_default is not None and motion_by_name:
+        raise ValueError("motion[%r]: tiles are set for every camera: a camera takes one of the two" % (sorted(motion_by_name)[0],))
+    both = sorted(set(motion_by_name) & set(tiles_by_name))
+    if both:
+        raise ValueError("motion[%r]: the camera has tiles too: a camera takes one of the two" % (both[0],))
+
+
 def plan_bound(descriptions, entries, max_batch: int):
     """Cuts a list of frame-table indices into the calls `wz_submit_bound` accepts, in order (include/watsor_hip.h): every call holds one
     kind -- untiled, tiled or gated -- and one pair of merge thresholds, at most max_batch frames whose tiles (gated: their cameras'
@@ -224,6 +287,14 @@ class HipObjectDetector:
         per pixel, in `min_cells` cells; `max_age` > 0 runs a tile after that many skipped calls whatever it shows) and reuses the
         other tiles' rows; a frame without a camera id runs every tile as before.  The batched worker's frame table
         takes tiles through `bind_tiled_frame_table` (the worker's `hip_tiled_table`); `bind_frame_table` raises for a camera with tiles.
+        `options["motion"]`: run the detector at the camera's own resolution where the picture moved since the camera's previous
+        frame (include/watsor_hip.h: wz_detect_motion): {"threshold": 0 .. 255, "min_cells": 1, "dilate": 1, "max_regions": 3, "min_side": 300,
+        "pad": 8, "whole_frame": True, "iou": ..., "ios": ...} or {camera name: one of these}.  A 16 x 16 cell has changed when its luma sum
+        moved by more than `threshold` per pixel; changed cells, dilated by `dilate` cells, are joined into components, and the heaviest
+        components with at least `min_cells` changed cells become up to `max_regions` rectangles of at least `min_side` pixels a side,
+        `pad` pixels around the cells; `whole_frame` runs the squeezed whole frame beside them; "iou" / "ios" merge as for `tiles`.  A
+        camera takes `motion` or `tiles`, not both; its frames need a camera id and go through `detect_batch` (cut into calls whose
+        configured whole_frame + max_regions fit max_batch); `bind_frame_table` / `bind_tiled_frame_table` raise for such a camera.
         `options["schedule"]`: "latency" | "throughput" | "auto" (default) -- the launch shapes of this detector PROCESS
         (include/watsor_hip.h: wz_set_schedule).  "latency" makes a lone batch finish soonest -- the reference's normal load is one
         frame at a time (`_next_frame`, detector.py:102-112); "throughput" gets the most frames per second out of four batches in
@@ -269,9 +340,13 @@ class HipObjectDetector:
         self.__tile_rects = {}
         self.__gate_layouts = {}        # camera id -> what its tiles were last set for: (width, height, base format, rectangles, gate)
         self.bound_descriptions = []    # per frame-table entry: (kind, iou, ios, tiles, camera id), see `plan_bound`
+        self.__motion_default, self.__motion_by_name = motion_options(options)
+        self.__motion_by_cam = {}
+        self.__motion_layouts = {}      # camera id -> what its motion settings were last made for: (width, height, base format, settings)
         for where, spec in [("tiles", self.__tiles_default)] + [("tiles[%r]" % n, t) for n, t in self.__tiles_by_name.items()]:
             if spec is not None and spec["count"] > max_batch:
                 raise ValueError("%s: %d tiles per frame exceed max_batch %d" % (where, spec["count"], max_batch))
+        check_motion_options(self.__motion_default, self.__motion_by_name, self.__tiles_default, self.__tiles_by_name, max_batch)
         self._warn_short_of_queues()
         self.__engine = HipEngine(engine_path, device, max_batch, max_width, max_height, schedule=schedule)
         self.__device = device
@@ -319,6 +394,11 @@ class HipObjectDetector:
         return self.__tiles_default is not None or bool(self.__tiles_by_name)
 
     @property
+    def motion(self) -> bool:
+        """A `motion` option is set (for every camera or for some): frames go through `detect_batch()` with camera ids."""
+        return self.__motion_default is not None or bool(self.__motion_by_name)
+
+    @property
     def engine(self) -> HipEngine:
         return self.__engine
 
@@ -364,7 +444,9 @@ class HipObjectDetector:
         from .._lib import WZ_MAX_CAMS
         names = sorted(frame_buffers, key=str)
         gate_all = self.__tiles_default is not None and "gate" in self.__tiles_default      # (a gate keeps state per camera: every camera needs an id)
-        need = [n for n in names if gate_all or n in (camera_configs or {}) or str(n) in self.__fmt_by_name or str(n) in self.__tiles_by_name]
+        motion_all = self.__motion_default is not None                                      # (and so does the motion reference)
+        need = [n for n in names if gate_all or motion_all or n in (camera_configs or {}) or str(n) in self.__fmt_by_name
+                or str(n) in self.__tiles_by_name or str(n) in self.__motion_by_name]
         if len(need) > WZ_MAX_CAMS:
             raise ValueError("%d cameras with GPU filters / pixel formats of their own on one detector: the engine has %d slots"
                              % (len(need), WZ_MAX_CAMS))
@@ -372,6 +454,7 @@ class HipObjectDetector:
         ids.update({name: i for i, name in enumerate(need)})
         self.__fmt_by_cam = {i: self.__fmt_by_name.get(str(name), self.__fmt_default) for name, i in ids.items() if i >= 0}
         self.__tiles_by_cam = {i: self.__tiles_by_name[str(name)] for name, i in ids.items() if i >= 0 and str(name) in self.__tiles_by_name}
+        self.__motion_by_cam = {i: self.__motion_by_name[str(name)] for name, i in ids.items() if i >= 0 and str(name) in self.__motion_by_name}
         for name, cfg in (camera_configs or {}).items():
             if name in ids:
                 self.__filters.append(HipCameraFilter(self.__engine, ids[name], cfg, drop=drop))
@@ -422,6 +505,9 @@ class HipObjectDetector:
             if not tiled and (self.__tiles_default is not None or str(name) in self.__tiles_by_name):
                 raise ValueError("camera %r has tiles configured: tiled detection does not go through the worker's frame table "
                                  "(bind_frame_table / submit_bound); use detect() / detect_batch() for it" % (name,))
+            if self.__motion_default is not None or str(name) in self.__motion_by_name:
+                raise ValueError("camera %r has motion configured: motion regions do not go through the worker's frame table "
+                                 "(bind_frame_table / bind_tiled_frame_table / submit_bound); use detect_batch() for it" % (name,))
             cam = ids.get(name, -1)
             fmt0 = self.__fmt_by_cam.get(cam, self.__fmt_default) if cam >= 0 else self.__fmt_default
             latches = []
@@ -512,6 +598,9 @@ class HipObjectDetector:
         if self.tiled:
             raise ValueError("this detector has tiles configured: the asynchronous host path (submit_host / collect) detects untiled; "
                              "use detect() / detect_batch()")
+        if self.motion:
+            raise ValueError("this detector has motion configured: the asynchronous host path (submit_host / collect) detects untiled; "
+                             "use detect_batch()")
         self.__engine.submit_host(lane, images, cameras, self._formats(images, cameras))
 
     def collect(self, lane: int, detections: Sequence) -> None:
@@ -536,14 +625,55 @@ class HipObjectDetector:
                                                        even=(fmt & FMT_BASE_MASK) in YUV_FORMATS)
         return rects
 
+    def _detect_motion(self, frames, detections, cameras, passes, formats, moving):
+        """The frames `moving` = [(index, settings), ...] through `detect_motion`: frames with the same thresholds share a call while their
+        cameras' configured whole_frame + max_regions fit max_batch, one frame per camera and call."""
+        pick = lambda seq, idx: None if seq is None else [seq[i] for i in idx]      # noqa: E731
+        ms, call, used, key = 0.0, [], 0, None
+
+        def flush():
+            nonlocal ms
+            if call:
+                ms += self.__engine.detect_motion(pick(frames, call), pick(cameras, call), pick(detections, call), pick(passes, call),
+                                                  pick(formats, call), iou=key[0], ios=key[1])
+        for i, m in moving:
+            if cameras is None or cameras[i] < 0:
+                raise ValueError("motion: frame %d comes without a camera id: the reference is kept per camera (detect_batch(..., cameras=...))" % i)
+            fmt = formats[i] if formats is not None else FMT_RGB24
+            k = (m["iou"], m["ios"])
+            if call and (used + m["count"] > self.max_batch or k != key or cameras[i] in [cameras[j] for j in call]):
+                flush()
+                call, used = [], 0
+            w, h = self.__engine.frame_geometry(frames[i], fmt)
+            layout = (w, h, fmt & FMT_BASE_MASK, id(m))
+            if self.__motion_layouts.get(cameras[i]) != layout:      # the first frame of the camera, or another size or format
+                self.__engine.set_camera_motion(cameras[i], w, h, m["threshold"], m["min_cells"], m["dilate"], m["max_regions"], m["min_side"],
+                                                m["pad"], m["whole_frame"], fmt)
+                self.__motion_layouts[cameras[i]] = layout
+            key = k
+            call.append(i)
+            used += m["count"]
+        flush()
+        return ms
+
     def _detect(self, frames, detections, cameras, passes):
         formats = self._formats(frames, cameras)
+        ms = 0.0
+        if self.motion:      # frames of a camera with motion settings go their own way; the rest as without the option
+            spec_of = lambda i: (self.__motion_by_cam.get(cameras[i]) if cameras is not None else None) or self.__motion_default      # noqa: E731
+            moving = [(i, spec_of(i)) for i in range(len(frames)) if spec_of(i) is not None]
+            if moving:
+                ms += self._detect_motion(frames, detections, cameras, passes, formats, moving)
+                rest = [i for i in range(len(frames)) if i not in {j for j, _ in moving}]
+                if not rest:
+                    return ms
+                pick = lambda seq: None if seq is None else [seq[i] for i in rest]      # noqa: E731
+                frames, detections, cameras, passes, formats = pick(frames), pick(detections), pick(cameras), pick(passes), pick(formats)
         specs = [self.__tiles_by_cam.get(cameras[i], self.__tiles_default) if cameras is not None else self.__tiles_default
                  for i in range(len(frames))]
         if not any(s is not None for s in specs):
-            return self.__engine.detect_batch(frames, detections, cameras, passes, formats)
+            return ms + self.__engine.detect_batch(frames, detections, cameras, passes, formats)
         pick = lambda seq, idx: None if seq is None else [seq[i] for i in idx]      # noqa: E731
-        ms = 0.0
         plain = [i for i, s in enumerate(specs) if s is None]
         if plain:
             ms += self.__engine.detect_batch(pick(frames, plain), pick(detections, plain), pick(cameras, plain), pick(passes, plain),

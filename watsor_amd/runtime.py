@@ -128,6 +128,8 @@ class HipEngine:
         self._dev_allocs: List[int] = []
         self._gate_tiles = {}                              # camera id -> tiles of its layout (set_camera_tiles)
         self._gate_last = {}                               # lane -> the camera ids of the last gated call accepted on it
+        self._motion_whole = {}                            # camera id -> whole_frame of its motion settings (set_camera_motion)
+        self._motion_last = {}                             # lane -> the camera ids of the last motion call accepted on it
         self._bound_arrays = {}                            # (submit_bound before any bind_frames: the engine's EINVAL, not an AttributeError)
         self._bound_last = {}                              # lane -> frames of the last bound batch accepted on it (bound_source)
         self._bound_cams = []                              # camera id of every table entry (bind_frames) ...
@@ -369,6 +371,71 @@ class HipEngine:
         self._ck(self._lib.wz_gate_stats(self._h, slot, n, C.byref(ran), C.byref(act)))
         flat = np.array(act[:sum(counts)], np.int32)
         return [int(m) for m in ran], [a.copy() for a in np.split(flat, np.cumsum(counts)[:-1])]
+
+    # -- motion regions (include/watsor_hip.h: wz_set_camera_motion / wz_detect_motion) -------------------------
+    @staticmethod
+    def _motion_words(threshold, min_cells, dilate, max_regions, min_side, pad, whole_frame):
+        return (C.c_int32 * 8)(int(threshold), int(min_cells), int(dilate), int(max_regions), int(min_side), int(pad), int(bool(whole_frame)), 0)
+
+    def set_camera_motion(self, cam: int, width: int, height: int, threshold: int, min_cells: int = 1, dilate: int = 1, max_regions: int = 3,
+                          min_side: int = 300, pad: int = 8, whole_frame: bool = True, fmt: int = FMT_RGB24) -> None:
+        """Camera `cam` detects in the parts of its width x height frames of format `fmt` that moved since its previous motion call: a cell
+        of 16 x 16 pixels has changed when its luma sum moved by more than `threshold` (0 .. 255) per pixel; changed cells are dilated by
+        `dilate` (0 .. 2) cells and joined into 8-connected components; the heaviest components with at least `min_cells` changed cells
+        become at most `max_regions` (1 .. 16) rectangles, `pad` (0 .. 64) pixels around the cells and at least `min_side` (>= 16) pixels
+        a side, that run at the camera's own resolution -- beside the whole frame if `whole_frame`.  Waits for every lane; the camera
+        starts without a reference (its next motion call sees no motion)."""
+        words = self._motion_words(threshold, min_cells, dilate, max_regions, min_side, pad, whole_frame)
+        self._ck(self._lib.wz_set_camera_motion(self._h, int(cam), int(width), int(height), int(fmt), C.byref(words)))
+        self._motion_whole[int(cam)] = 1 if whole_frame else 0
+
+    def reset_camera_motion(self, cam: int) -> None:
+        """Forget the reference of camera `cam` (its next motion call sees no motion); the settings stay."""
+        self._ck(self._lib.wz_reset_camera_motion(self._h, int(cam)))
+
+    def clear_camera_motion(self, cam: int) -> None:
+        self._ck(self._lib.wz_clear_camera_motion(self._h, int(cam)))
+        self._motion_whole.pop(int(cam), None)
+
+    def detect_motion(self, frames: Sequence[np.ndarray], cams: Sequence[int], out_rows: Sequence,
+                      passes: Optional[Sequence[np.ndarray]] = None, formats: Optional[Sequence[int]] = None,
+                      iou: Optional[float] = None, ios: Optional[float] = None) -> float:
+        """`detect_tiled` on the rectangles the engine finds itself: per frame the whole frame (if its camera's settings say so) and the
+        regions that changed since the camera's previous motion call.  One frame per camera and call; the cameras' configured whole_frame +
+        max_regions together at most max_batch.  A frame without any tile gets padding rows and pass bytes 0.  Returns the wall time in
+        ms; `motion_stats()` tells which rectangles ran."""
+        n, (ptrs, ws, hs, outs, keep) = len(frames), self._host_frames(frames, formats, out_rows)
+        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
+        camv = (C.c_int32 * n)(*[int(c) for c in cams])
+        passv = (C.c_void_p * n)(*[p.ctypes.data for p in passes]) if passes is not None else None
+        ms = (C.c_float * n)()
+        self._ck(self._lib.wz_detect_motion(self._h, n, ptrs, ws, hs, fmtv, camv, *self._thresholds(iou, ios), outs, passv, ms))
+        self._motion_last[0] = [int(c) for c in cams]
+        return float(ms[0])
+
+    def submit_motion_device(self, slot: int, d_frames: Sequence[int], widths: Sequence[int], heights: Sequence[int], cams: Sequence[int],
+                             formats: Optional[Sequence[int]] = None, iou: Optional[float] = None, ios: Optional[float] = None) -> None:
+        """`detect_motion` of frames resident in HBM on lane `slot`.  Returns once the engine has read the rectangles (it waits for the
+        activity and the region launch); the batch behind is asynchronous and collected like a tiled slot's."""
+        n = len(d_frames)
+        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
+        self._ck(self._lib.wz_submit_motion_device(self._h, slot, n, (C.c_void_p * n)(*d_frames), (C.c_int32 * n)(*widths), (C.c_int32 * n)(*heights),
+                                                   fmtv, (C.c_int32 * n)(*[int(c) for c in cams]), *self._thresholds(iou, ios)))
+        self._motion_last[slot] = [int(c) for c in cams]
+
+    def motion_stats(self, slot: int = 0):
+        """What the last motion call accepted on lane `slot` found: ([per frame: its tile list [(x0, y0, w, h), ...] -- the whole frame first
+        if configured, then the regions in rank order], [per frame: the changed cells of every region], [per frame: the components with
+        at least min_cells changed cells])."""
+        cams = self._motion_last.get(slot)
+        if not cams:
+            raise ValueError("no motion call was made on lane %d" % slot)
+        n, per, most = len(cams), 1 + _lib.WZ_MOTION_MAX_REGIONS, _lib.WZ_MOTION_MAX_REGIONS
+        counts, tiles, cells, comps = (C.c_int32 * n)(), (Tile * (n * per))(), (C.c_int32 * (n * most))(), (C.c_int32 * n)()
+        self._ck(self._lib.wz_motion_stats(self._h, slot, n, C.byref(counts), C.byref(tiles), C.byref(cells), C.byref(comps)))
+        lists = [[(t.x0, t.y0, t.w, t.h) for t in tiles[i * per:i * per + counts[i]]] for i in range(n)]
+        regions = [counts[i] - self._motion_whole[c] for i, c in enumerate(cams)]
+        return lists, [[int(v) for v in cells[i * most:i * most + regions[i]]] for i in range(n)], [int(v) for v in comps]
 
     def submit_device(self, slot: int, d_frames: Sequence[int], widths: Sequence[int], heights: Sequence[int],
                       cams: Optional[Sequence[int]] = None, formats: Optional[Sequence[int]] = None) -> None:
@@ -719,6 +786,40 @@ class HipEngine:
                                                   C.c_void_p(ref.ctypes.data) if ref is not None else None, int(pixel_thr),
                                                   C.c_void_p(sums.ctypes.data), C.byref(changed)))
         return sums, int(changed.value)
+
+    def stage_motion_regions(self, now: np.ndarray, ref: Optional[np.ndarray], width: int, height: int, threshold: int, min_cells: int = 1,
+                             dilate: int = 1, max_regions: int = 3, min_side: int = 300, pad: int = 8, fmt: int = FMT_RGB24):
+        """The region kernel alone on two grids of luma sums (uint16 [cell rows, cell columns] of a width x height frame of format `fmt`; ref
+        None: no reference): ([(x0, y0, w, h), ...] in rank order, the changed cells of every region, the components with at least
+        min_cells changed cells)."""
+        self._dev_only("stage_motion_regions()")
+        shape = (-(-int(height) // _lib.WZ_GATE_CELL), -(-int(width) // _lib.WZ_GATE_CELL))
+        now = np.ascontiguousarray(now, np.uint16)
+        ref = None if ref is None else np.ascontiguousarray(ref, np.uint16)
+        for name, g in (("now", now), ("ref", ref)):
+            if g is not None and g.shape != shape:
+                raise ValueError("%s: expected a uint16 grid of shape %r, got %r" % (name, shape, g.shape))
+        words = self._motion_words(threshold, min_cells, dilate, max_regions, min_side, pad, False)
+        most = _lib.WZ_MOTION_MAX_REGIONS
+        n, comps, tiles, cells = C.c_int32(-1), C.c_int32(-1), (Tile * most)(), (C.c_int32 * most)()
+        self._ck(self._lib.wz_stage_motion_regions(self._h, C.c_void_p(now.ctypes.data), C.c_void_p(ref.ctypes.data) if ref is not None else None,
+                                                   int(width), int(height), int(fmt), C.byref(words), C.byref(n), C.byref(tiles), C.byref(cells),
+                                                   C.byref(comps)))
+        return [(t.x0, t.y0, t.w, t.h) for t in tiles[:n.value]], [int(v) for v in cells[:n.value]], int(comps.value)
+
+    def profile_motion(self, now: np.ndarray, ref: Optional[np.ndarray], width: int, height: int, threshold: int, min_cells: int = 1,
+                       dilate: int = 1, max_regions: int = 3, min_side: int = 300, pad: int = 8, fmt: int = FMT_RGB24, reps: int = 100):
+        """(ms of the region launch alone on these grids, ms of the whole-frame activity launch of such a frame alone, ms of an empty
+        bracket, rounds the labelling took): HIP-event brackets, the mean of `reps` each."""
+        self._dev_only("profile_motion()")
+        now = np.ascontiguousarray(now, np.uint16)
+        ref = None if ref is None else np.ascontiguousarray(ref, np.uint16)
+        words = self._motion_words(threshold, min_cells, dilate, max_regions, min_side, pad, False)
+        reg, act, empty, rounds = C.c_float(), C.c_float(), C.c_float(), C.c_int32()
+        self._ck(self._lib.wz_profile_motion(self._h, C.c_void_p(now.ctypes.data), C.c_void_p(ref.ctypes.data) if ref is not None else None,
+                                             int(width), int(height), int(fmt), C.byref(words), int(reps), C.byref(reg), C.byref(act), C.byref(empty),
+                                             C.byref(rounds)))
+        return float(reg.value), float(act.value), float(empty.value), int(rounds.value)
 
     def profile_gated(self, d_frames: Sequence[int], widths: Sequence[int], heights: Sequence[int], cams: Sequence[int],
                       formats: Optional[Sequence[int]] = None, iou: Optional[float] = None, ios: Optional[float] = None, reps: int = 50):
