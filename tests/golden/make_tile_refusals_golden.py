@@ -1,8 +1,8 @@
 """Generates tests/golden/tile_refusals.json: the (return code, wz_last_error text) of every case in the refusal tables of
-tests/test_gpu_tiled.py, tests/test_gpu_gated.py and tests/test_gpu_bound_tiles.py, as the library built from the tree says them.
+tests/test_gpu_tiled.py, tests/test_gpu_gated.py, tests/test_gpu_bound_tiles.py and tests/test_gpu_motion.py, as the library built from the tree says them.
 
 Needs the GPU (a refusal is checked on a live engine):   python tests/golden/make_tile_refusals_golden.py
-It runs those three tests with tests/refusal_golden.py recording instead of comparing, so the tables exist once -- in the tests.
+It runs those four tests with tests/refusal_golden.py recording instead of comparing, so the tables exist once -- in the tests.
 Record on the commit whose texts are to be kept, i.e. BEFORE a change that must not alter them.
 """
 import json
@@ -20,7 +20,8 @@ import refusal_golden                                        # noqa: E402
 
 TABLES = ["test_gpu_tiled.py::test_refusals_write_nothing_and_leave_the_engine_usable",
           "test_gpu_gated.py::test_refusals_write_nothing_and_keep_the_state",
-          "test_gpu_bound_tiles.py::test_refusals_name_the_numbers_and_change_nothing"]
+          "test_gpu_bound_tiles.py::test_refusals_name_the_numbers_and_change_nothing",
+          "test_gpu_motion.py::test_refusals_write_nothing_and_keep_the_state"]
 
 
 def main():

@@ -1,6 +1,6 @@
-"""The refusals of the tiled, gated and frame-table entry points, pinned verbatim: every case of the refusal tables of
-test_gpu_tiled.py, test_gpu_gated.py and test_gpu_bound_tiles.py compares its (return code, wz_last_error text) with
-tests/golden/tile_refusals.json, which tests/golden/make_tile_refusals_golden.py records by running those three tests."""
+"""The refusals of the tiled, gated, motion and frame-table entry points, pinned verbatim: every case of the refusal tables of
+test_gpu_tiled.py, test_gpu_gated.py, test_gpu_bound_tiles.py and test_gpu_motion.py compares its (return code, wz_last_error text) with
+tests/golden/tile_refusals.json, which tests/golden/make_tile_refusals_golden.py records by running those four tests."""
 import json
 import os
 

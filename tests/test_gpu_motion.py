@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import motion_oracle as mo
+import refusal_golden
 import tile_oracle as to
 from conftest import make_engine
 from test_gpu_tiled import nv12_of
@@ -223,7 +224,7 @@ def test_refusals_write_nothing_and_keep_the_state(eng, cams):
         ([A], [cams[0]], None, 0.6, -1.0, _lib.WZ_EINVAL),
         ([], [], None, 0.6, 1.0, _lib.WZ_ELIMIT),
     ]
-    for frames, cam_ids, formats, iou, ios, code in bad:
+    for case, (frames, cam_ids, formats, iou, ios, code) in enumerate(bad):
         before = eng.motion_stats(0)
         n, m = len(frames), max(len(frames), 1)
         rows = np.full((m, 100 * ROW_DTYPE.itemsize), 0xA5, np.uint8)
@@ -237,26 +238,33 @@ def test_refusals_write_nothing_and_keep_the_state(eng, cams):
         pv = (C.c_void_p * m)(*[p.ctypes.data for p in passes])
         rc = lib.wz_detect_motion(h, n, fptr, ws, hs, fmtv, camv, iou, ios, outs, pv, None)
         assert rc == code and _lib.last_error(lib), (cam_ids, formats, iou, ios, _lib.last_error(lib))
+        refusal_golden.check("motion", "%d/wz_detect_motion" % case, rc, _lib.last_error(lib))
         assert (rows == 0xA5).all() and (passes == 0xA5).all()
         # the device entry point refuses the same way (host pointers stand in: a refused call reads no frame) and enqueues nothing
         rc = lib.wz_submit_motion_device(h, 0, n, fptr, ws, hs, fmtv, camv, iou, ios)
         assert rc == code, (cam_ids, formats, iou, ios, _lib.last_error(lib))
+        refusal_golden.check("motion", "%d/wz_submit_motion_device" % case, rc, _lib.last_error(lib))
         assert eng.motion_stats(0) == before
     # the reference is intact: it is still A's
     assert len(check_call(eng, states[:1], [B], cams[:1])[2][0]) == 3
     # settings the engine refuses leave the camera with the ones it had
     ok = dict(threshold=THR, min_cells=1, dilate=1, max_regions=3, min_side=128, pad=8, whole_frame=True)
-    for change, width, code in ((dict(threshold=256), W, _lib.WZ_EINVAL), (dict(threshold=-1), W, _lib.WZ_EINVAL), (dict(min_cells=0), W, _lib.WZ_EINVAL),
+    for case, (change, width, code) in enumerate(((dict(threshold=256), W, _lib.WZ_EINVAL), (dict(threshold=-1), W, _lib.WZ_EINVAL), (dict(min_cells=0), W, _lib.WZ_EINVAL),
                                 (dict(dilate=3), W, _lib.WZ_EINVAL), (dict(dilate=-1), W, _lib.WZ_EINVAL), (dict(max_regions=0), W, _lib.WZ_EINVAL),
                                 (dict(max_regions=17), W, _lib.WZ_EINVAL), (dict(min_side=15), W, _lib.WZ_EINVAL), (dict(pad=65), W, _lib.WZ_EINVAL),
                                 (dict(pad=-1), W, _lib.WZ_EINVAL), (dict(whole_frame=2), W, _lib.WZ_EINVAL), ({}, 0, _lib.WZ_EINVAL),
-                                ({}, 656, _lib.WZ_ELIMIT), (dict(max_regions=8), W, _lib.WZ_ELIMIT)):
+                                ({}, 656, _lib.WZ_ELIMIT), (dict(max_regions=8), W, _lib.WZ_ELIMIT))):
         p = dict(ok, **change)
         words = (C.c_int32 * 8)(p["threshold"], p["min_cells"], p["dilate"], p["max_regions"], p["min_side"], p["pad"], p["whole_frame"], 0)
         rc = lib.wz_set_camera_motion(h, cams[0], width, H, FMT_RGB24, C.byref(words))
         assert rc == code and _lib.last_error(lib), (change, width, _lib.last_error(lib))
-    assert lib.wz_set_camera_motion(h, cams[0], W, H, FMT_NV12 | 0x400, C.byref(words)) == _lib.WZ_EINVAL      # a format word the engine does not take
-    assert lib.wz_set_camera_motion(h, 256, W, H, FMT_RGB24, C.byref(words)) == _lib.WZ_ELIMIT
+        refusal_golden.check("motion", "settings/%d" % case, rc, _lib.last_error(lib))
+    rc = lib.wz_set_camera_motion(h, cams[0], W, H, FMT_NV12 | 0x400, C.byref(words))                         # a format word the engine does not take
+    refusal_golden.check("motion", "settings/format", rc, _lib.last_error(lib))
+    assert rc == _lib.WZ_EINVAL
+    rc = lib.wz_set_camera_motion(h, 256, W, H, FMT_RGB24, C.byref(words))
+    refusal_golden.check("motion", "settings/camera", rc, _lib.last_error(lib))
+    assert rc == _lib.WZ_ELIMIT
     assert len(check_call(eng, states[:1], [A], cams[:1])[2][0]) == 3          # still B's reference, still the old settings
     eng.clear_camera_motion(cams[0])
     with pytest.raises(ValueError, match="no motion settings"):

@@ -5,6 +5,7 @@
 #pragma once
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "wz_common.h"
@@ -25,44 +26,121 @@
 
 struct wz_engine;
 
+// Scratch with one owner: a hipMalloc block of T[n], and a page-locked block the device sees too (host pointer and device view).  Move-only:
+// a lane's or a camera's scratch is built aside and moved in, all or nothing; what is left behind, or never moved, frees itself.
+template <class T>
+struct DevBlock {
+    T* p = nullptr;
+    DevBlock() = default;
+    DevBlock(DevBlock&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBlock& operator=(DevBlock&& o) noexcept { std::swap(p, o.p); return *this; }   // (o takes the old block with it)
+    ~DevBlock() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc((void**)&p, sizeof(T) * n); }
+    operator T*() const { return p; }
+};
+template <class T>
+struct MappedBlock {
+    T *h = nullptr, *d = nullptr;
+    MappedBlock() = default;
+    MappedBlock(MappedBlock&& o) noexcept : h(o.h), d(o.d) { o.h = o.d = nullptr; }
+    MappedBlock& operator=(MappedBlock&& o) noexcept { std::swap(h, o.h); std::swap(d, o.d); return *this; }
+    ~MappedBlock() { if (h) (void)hipHostFree(h); }
+    hipError_t alloc(size_t n) {
+        const hipError_t err = hipHostMalloc((void**)&h, sizeof(T) * n, hipHostMallocMapped);
+        return err == hipSuccess ? hipHostGetDevicePointer((void**)&d, h, 0) : err;
+    }
+};
+// A block handed out in typed parts, in order, each at a boundary of `align` bytes (8: every part here holds pointers or 32-bit words).
+// On a null base it only measures -- bytes() is what to allocate --; on the host and on the device pointer of one block it gives the two
+// views of one layout.
+struct Carve {
+    uintptr_t base;
+    size_t off = 0;
+    explicit Carve(const void* b) : base(reinterpret_cast<uintptr_t>(b)) {}
+    template <class T>
+    T* take(size_t n, size_t align = 8) {
+        off = (off + align - 1) & ~(align - 1);
+        T* part = reinterpret_cast<T*>(base + off);
+        off += sizeof(T) * n;
+        return part;
+    }
+    size_t bytes() const { return (off + 7) & ~(size_t)7; }
+};
+// A lane's page-locked block of max_batch descriptors of each part of a view V (V::carve), as the host (h) and as the device (m) sees it
+template <class V>
+struct MetaBlock {
+    MappedBlock<uint8_t> block;
+    V h = {}, m = {};
+    hipError_t alloc(size_t nb) {
+        const hipError_t err = block.alloc(h.carve(nullptr, nb));
+        if (err == hipSuccess) { h.carve(block.h, nb); m.carve(block.d, nb); }
+        return err;
+    }
+};
+
 // tiled detection (wz_submit_tiled_device / wz_detect_tiled): a lane's share, allocated the first time the lane sees a tiled call
+struct TileMeta {
+    WzMergeFrame* frames;                // the merge launch's frames [max_batch]
+    int32_t* origins;                    // the tiles' origins (x0, y0) [max_batch][2]
+    size_t carve(const void* base, size_t nb) {
+        Carve c(base);
+        frames = c.take<WzMergeFrame>(nb); origins = c.take<int32_t>(2 * nb);
+        return c.bytes();
+    }
+};
 struct TileLane {
-    uint8_t* d_tiles = nullptr;          // tile staging [max_batch][frame_stride]: the crop launch's output, the batch's frames
-    WzMergeCand* d_tcand = nullptr;      // the merge kernel's scratch [max_batch][100]
-    wz_detection_t* h_trows = nullptr;   // pinned, device-mapped: the merged rows [max_batch][100] ...
-    uint8_t* h_tpass = nullptr;          // ... and their pass bytes, written by the merge launch (and the filter launches behind it)
-    WzMergeFrame* h_tmeta = nullptr;     // pinned, device-mapped: WzMergeFrame[max_batch], then the tiles' origins int32[max_batch][2]
-    wz_detection_t* m_trows = nullptr;   // device addresses of the three
-    uint8_t* m_tpass = nullptr;
-    WzMergeFrame* m_tmeta = nullptr;
-    int tiled = 0;                       // frames of the tiled batch in flight (its rows are in h_trows); 0: the batch is not tiled
+    DevBlock<uint8_t> d_tiles;           // tile staging [max_batch][frame_stride]: the crop launch's output, the batch's frames
+    DevBlock<WzMergeCand> d_tcand;       // the merge kernel's scratch [max_batch][100]
+    MappedBlock<wz_detection_t> trows;   // the merged rows [max_batch][100] ...
+    MappedBlock<uint8_t> tpass;          // ... and their pass bytes, written by the merge launch (and the filter launches behind it)
+    MetaBlock<TileMeta> meta;
+    int tiled = 0;                       // frames of the tiled batch in flight (its rows are in trows.h); 0: the batch is not tiled
     int alloc(wz_engine* e);             // (wz_tiles.hip) lazy; all or nothing
-    void release();
+    void release() { *this = TileLane(); }
 };
 // gated tiled detection (wz_submit_gated_device / wz_detect_gated): allocated the first time the lane sees a gated call
+struct GateMeta {
+    WzGateTile* tiles;                   // the activity launch's tiles [max_batch]
+    WzGateCommit* commits;               // the commit launch's [max_batch]
+    int32_t* activity;                   // the activity counts [max_batch]
+    size_t carve(const void* base, size_t nb) {
+        Carve c(base);
+        tiles = c.take<WzGateTile>(nb); commits = c.take<WzGateCommit>(nb); activity = c.take<int32_t>(nb);
+        return c.bytes();
+    }
+};
 struct GateLane {
-    uint16_t* d_gnow = nullptr;          // the activity launch's new grids [max_batch][gate_cells]
-    wz_detection_t* d_grows = nullptr;   // fresh or cached rows of every tile of the call, in tile order [max_batch][100]: what the merge reads
-    int32_t* d_gcount = nullptr;         // the activity kernel's counters [max_batch][2]
-    WzGateTile* h_gmeta = nullptr;       // pinned, device-mapped: WzGateTile[max_batch], WzGateCommit[max_batch], activity int32[max_batch]
-    WzGateTile* m_gmeta = nullptr;       // ... as the device sees it
+    DevBlock<uint16_t> d_gnow;           // the activity launch's new grids [max_batch][gate_cells]
+    DevBlock<wz_detection_t> d_grows;    // fresh or cached rows of every tile of the call, in tile order [max_batch][100]: what the merge reads
+    DevBlock<int32_t> d_gcount;          // the activity kernel's counters [max_batch][2]
+    MetaBlock<GateMeta> meta;
     std::vector<uint64_t> g_ran;         // the last gated call accepted on this lane (wz_gate_stats): per frame, bit t = tile t ran ...
     std::vector<int32_t> g_act;          // ... and every tile's activity, in tile order
     int g_tiles = 0, g_crows = 0, g_cols = 0;   // that call's launches: tiles, the most cell rows / columns of a tile
     int alloc(wz_engine* e);
-    void release();
+    void release() { *this = GateLane(); }
 };
 // motion regions (wz_submit_motion_device / wz_detect_motion): allocated the first time the lane sees a motion call
+struct MotionMeta {
+    WzGateTile* tiles;                   // the activity launch's whole-frame tiles [max_batch]
+    WzMotionCam* cams;                   // the region launch's cameras [max_batch]
+    WzMotionOut* outs;                   // what it found [max_batch]
+    int32_t* activity;                   // the activity counts [max_batch] (unused)
+    size_t carve(const void* base, size_t nb) {
+        Carve c(base);
+        tiles = c.take<WzGateTile>(nb); cams = c.take<WzMotionCam>(nb); outs = c.take<WzMotionOut>(nb); activity = c.take<int32_t>(nb);
+        return c.bytes();
+    }
+};
 struct MotionLane {
-    uint32_t* d_mscratch = nullptr;      // the region kernel's scratch [max_batch][cam_words]
-    int32_t* d_mcount = nullptr;         // the activity kernel's counters [max_batch][2]
-    uint8_t* h_mmeta = nullptr;          // pinned, device-mapped: WzGateTile[max_batch], WzMotionCam[max_batch], WzMotionOut[max_batch], int32[max_batch]
-    uint8_t* m_mmeta = nullptr;          // ... as the device sees it
+    DevBlock<uint32_t> d_mscratch;       // the region kernel's scratch [max_batch][cam_words]
+    DevBlock<int32_t> d_mcount;          // the activity kernel's counters [max_batch][2]
+    MetaBlock<MotionMeta> meta;
     size_t cam_words = 0;
     std::vector<int32_t> s_ntiles, s_cells, s_comps;   // the last motion call accepted on this lane (wz_motion_stats): per frame its tiles,
     std::vector<wz_tile_t> s_tiles;                    // [n][1 + WZ_MOTION_MAX_REGIONS], its regions' n [n][WZ_MOTION_MAX_REGIONS], its components
     int alloc(wz_engine* e);             // (wz_tiles.hip) lazy; all or nothing
-    void release();
+    void release() { *this = MotionLane(); }
 };
 
 struct wz_engine {
@@ -205,12 +283,12 @@ struct wz_engine {
         std::vector<wz_tile_t> tiles;
         std::vector<int> cols, crows;            // cells of every tile
         std::vector<size_t> grid_off;            // first cell of every tile's reference grid in d_ref
-        uint16_t* d_ref = nullptr;               // the tiles' reference grids, one after the other
-        wz_detection_t* d_rows = nullptr;        // the tiles' cached rows [tiles][100]
+        DevBlock<uint16_t> d_ref;                // the tiles' reference grids, one after the other
+        DevBlock<wz_detection_t> d_rows;         // the tiles' cached rows [tiles][100]
         std::vector<uint8_t> has_ref;            // the tile has a reference (and cached rows)
         std::vector<int> skipped;                // gated calls of this camera in a row that skipped the tile
         int lane = -1;                           // the lane whose gated batch last wrote this state
-        void release();                          // (wz_tiles.hip) frees the two device blocks
+        void release() { *this = GateCam(); }    // frees the two device blocks
     };
     std::map<int, GateCam> gate_cams;
     // motion regions: a camera's settings and its two whole-frame grids (wz_set_camera_motion); empty until a camera is set.  The grid the
@@ -219,10 +297,10 @@ struct wz_engine {
         int w = 0, h = 0, base = 0, fmt = 0;     // the frames the settings were made for
         int gw = 0, gh = 0;                      // cells of the whole frame
         wz_motion_t p = {0, 1, 0, 1, 16, 0, 0, 0};
-        uint16_t* d_grid[2] = {nullptr, nullptr};
+        DevBlock<uint16_t> d_grid[2];
         int cur = 0;                             // d_grid[cur] is the reference, d_grid[cur ^ 1] takes the next call's grid
         bool has_ref = false;
-        void release();                          // (wz_tiles.hip) frees the two grids
+        void release() { *this = MotionCam(); }  // frees the two grids
     };
     std::map<int, MotionCam> motion_cams;
 

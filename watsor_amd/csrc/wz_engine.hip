@@ -807,7 +807,7 @@ static int lane_status(wz_engine* e, int slot) {
 // (the tiles that ran; none: 0; lane_status still looks at every tile).
 struct LaneResult { int n; const wz_detection_t* rows; const uint8_t* pass; };
 static LaneResult lane_result(const Lane& L) {
-    return L.tile.tiled ? LaneResult{L.tile.tiled, L.tile.h_trows, L.tile.h_tpass} : LaneResult{L.n, L.h_rows, L.h_pass};
+    return L.tile.tiled ? LaneResult{L.tile.tiled, L.tile.trows.h, L.tile.tpass.h} : LaneResult{L.n, L.h_rows, L.h_pass};
 }
 
 extern "C" const wz_detection_t* wz_slot_rows(wz_engine_t* e, int slot) {

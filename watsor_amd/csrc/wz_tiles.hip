@@ -1,83 +1,65 @@
 // Tiled, gated, motion-region and tiled frame-table detection (include/watsor_hip.h; DESIGN.md sections 15 - 17 and 19): eager launches of
 // k_tiles.hip, k_gate.hip and k_motion.hip around run_batch.  wz_engine.hip knows nothing of this file but TileLane / GateLane / MotionLane /
-// GateCam's and MotionCam's release, the lane's `tile.tiled` and submit_bound_tiles (wz_engine.h).
+// GateCam's and MotionCam's release, the lane's `tile.tiled` and merged rows (`tile.trows`, `tile.tpass`) and submit_bound_tiles (wz_engine.h).
 #include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
 #include <chrono>
+#include <numeric>
 
 #include "wz_engine.h"
 
 typedef wz_engine::GateCam GateCam;
+typedef wz_engine::MotionCam MotionCam;
 
-// ---- lane and camera state
-// Everything a lane needs for tiled calls, allocated the first time it sees one (an engine that never does uses no byte of it).
+static int cells_of(int px) { return (px + WZ_GATE_CELL - 1) / WZ_GATE_CELL; }
+static size_t gate_cells_of(int w, int h) { return (size_t)cells_of(w) * (size_t)cells_of(h); }
+
+// ---- lane state
+// Everything a lane needs for one kind of call, allocated the first time it sees one (an engine that never does uses no byte of it): built
+// aside and moved in, so that a failure leaves the lane without any of it (wz_engine.h: DevBlock, MappedBlock, MetaBlock).
 int TileLane::alloc(wz_engine* e) {
     if (d_tiles) return WZ_OK;
     const size_t nb = (size_t)e->max_batch, rows = nb * WZ_MAX_DETECTIONS;
     TileLane t;
-    hipError_t err = hipMalloc((void**)&t.d_tiles, e->frame_stride * nb);
-    if (err == hipSuccess) err = hipMalloc((void**)&t.d_tcand, sizeof(WzMergeCand) * rows);
-    if (err == hipSuccess) err = hipHostMalloc((void**)&t.h_trows, sizeof(wz_detection_t) * rows, hipHostMallocMapped);
-    if (err == hipSuccess) err = hipHostMalloc((void**)&t.h_tpass, rows, hipHostMallocMapped);
-    if (err == hipSuccess) err = hipHostMalloc((void**)&t.h_tmeta, (sizeof(WzMergeFrame) + 8) * nb, hipHostMallocMapped);
-    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&t.m_trows, t.h_trows, 0);
-    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&t.m_tpass, t.h_tpass, 0);
-    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&t.m_tmeta, t.h_tmeta, 0);
-    if (err != hipSuccess) {
-        t.release();
-        return wz_set_error(WZ_EHIP, "tile staging of a lane (%zu bytes): %s", e->frame_stride * nb, hipGetErrorString(err));
-    }
+    hipError_t err = t.d_tiles.alloc(e->frame_stride * nb);
+    if (err == hipSuccess) err = t.d_tcand.alloc(rows);
+    if (err == hipSuccess) err = t.trows.alloc(rows);
+    if (err == hipSuccess) err = t.tpass.alloc(rows);
+    if (err == hipSuccess) err = t.meta.alloc(nb);
+    if (err != hipSuccess) return wz_set_error(WZ_EHIP, "tile staging of a lane (%zu bytes): %s", e->frame_stride * nb, hipGetErrorString(err));
     t.tiled = tiled;
-    *this = t;
+    *this = std::move(t);
     return WZ_OK;
 }
-void TileLane::release() {
-    if (d_tiles) (void)hipFree(d_tiles);
-    if (d_tcand) (void)hipFree(d_tcand);
-    if (h_trows) (void)hipHostFree(h_trows);
-    if (h_tpass) (void)hipHostFree(h_tpass);
-    if (h_tmeta) (void)hipHostFree(h_tmeta);
-    *this = TileLane();
-}
-
-static size_t gate_cells_of(int w, int h) {
-    return (size_t)((w + WZ_GATE_CELL - 1) / WZ_GATE_CELL) * (size_t)((h + WZ_GATE_CELL - 1) / WZ_GATE_CELL);
-}
-// the pinned block of a lane: the activity launch's tiles, the commit launch's tiles, the activity counts
-static WzGateCommit* gate_commits(wz_engine* e, WzGateTile* meta) { return reinterpret_cast<WzGateCommit*>(meta + e->max_batch); }
-static int32_t* gate_activity(wz_engine* e, WzGateTile* meta) { return reinterpret_cast<int32_t*>(gate_commits(e, meta) + e->max_batch); }
 
 int GateLane::alloc(wz_engine* e) {
     if (d_gnow) return WZ_OK;
-    const size_t nb = (size_t)e->max_batch, cells = gate_cells_of(e->max_w, e->max_h);
+    const size_t nb = (size_t)e->max_batch;
     GateLane g;
-    hipError_t err = hipMalloc((void**)&g.d_gnow, cells * 2 * nb);
-    if (err == hipSuccess) err = hipMalloc((void**)&g.d_grows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS * nb);
-    if (err == hipSuccess) err = hipMalloc((void**)&g.d_gcount, 8 * nb);
+    hipError_t err = g.d_gnow.alloc(gate_cells_of(e->max_w, e->max_h) * nb);
+    if (err == hipSuccess) err = g.d_grows.alloc(WZ_MAX_DETECTIONS * nb);
+    if (err == hipSuccess) err = g.d_gcount.alloc(2 * nb);
     if (err == hipSuccess) err = lane0_fill(e, g.d_gcount, 0, 8 * nb);
-    if (err == hipSuccess) err = hipHostMalloc((void**)&g.h_gmeta, (sizeof(WzGateTile) + sizeof(WzGateCommit) + 4) * nb, hipHostMallocMapped);
-    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&g.m_gmeta, g.h_gmeta, 0);
-    if (err != hipSuccess) {
-        g.release();
-        return wz_set_error(WZ_EHIP, "gate scratch of a lane: %s", hipGetErrorString(err));
-    }
-    d_gnow = g.d_gnow; d_grows = g.d_grows; d_gcount = g.d_gcount; h_gmeta = g.h_gmeta; m_gmeta = g.m_gmeta;
+    if (err == hipSuccess) err = g.meta.alloc(nb);
+    if (err != hipSuccess) return wz_set_error(WZ_EHIP, "gate scratch of a lane: %s", hipGetErrorString(err));
+    *this = std::move(g);
     return WZ_OK;
 }
-void GateLane::release() {
-    if (d_gnow) (void)hipFree(d_gnow);
-    if (d_grows) (void)hipFree(d_grows);
-    if (d_gcount) (void)hipFree(d_gcount);
-    if (h_gmeta) (void)hipHostFree(h_gmeta);
-    d_gnow = nullptr; d_grows = nullptr; d_gcount = nullptr; h_gmeta = m_gmeta = nullptr;
-}
 
-void GateCam::release() {
-    if (d_ref) (void)hipFree(d_ref);
-    if (d_rows) (void)hipFree(d_rows);
-    d_ref = nullptr, d_rows = nullptr;
+int MotionLane::alloc(wz_engine* e) {
+    if (d_mscratch) return WZ_OK;
+    const size_t nb = (size_t)e->max_batch;
+    MotionLane m;
+    m.cam_words = std::min((size_t)WZ_MOTION_MAX_CELLS, gate_cells_of(e->max_w, e->max_h));
+    hipError_t err = m.d_mscratch.alloc(m.cam_words * nb);
+    if (err == hipSuccess) err = m.d_mcount.alloc(2 * nb);
+    if (err == hipSuccess) err = lane0_fill(e, m.d_mcount, 0, 8 * nb);
+    if (err == hipSuccess) err = m.meta.alloc(nb);
+    if (err != hipSuccess) return wz_set_error(WZ_EHIP, "motion scratch of a lane: %s", hipGetErrorString(err));
+    *this = std::move(m);
+    return WZ_OK;
 }
 
 // ---- rectangles
@@ -86,8 +68,9 @@ static const char* tile_refusal(const wz_tile_t& t, int w, int h, int fmt) {
     if (t.w < 1 || t.h < 1 || t.x0 < 0 || t.y0 < 0) return "origin and size must not be negative, the size not zero";
     if ((int64_t)t.x0 + t.w > w || (int64_t)t.y0 + t.h > h) return "the rectangle leaves the frame";
     const int base = fmt & WZ_FMT_BASE_MASK;
-    if ((base == WZ_FMT_NV12 || base == WZ_FMT_I420) && ((t.x0 | t.y0 | t.w | t.h) & 1)) return "NV12 / I420 need even x0, y0, w and h";
-    if ((base == WZ_FMT_P010 || base == WZ_FMT_YUV420P10) && ((t.x0 | t.y0 | t.w | t.h) & 1)) return "P010 / YUV420P10 need even x0, y0, w and h";
+    const bool ten = base == WZ_FMT_P010 || base == WZ_FMT_YUV420P10;
+    if ((ten || base == WZ_FMT_NV12 || base == WZ_FMT_I420) && ((t.x0 | t.y0 | t.w | t.h) & 1))
+        return ten ? "P010 / YUV420P10 need even x0, y0, w and h" : "NV12 / I420 need even x0, y0, w and h";
     if ((base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422) && ((t.x0 | t.w) & 1)) return "YUYV422 / UYVY422 need even x0 and w";
     if (!wz_frame_bytes(t.w, t.h, fmt)) return fmt_refusal(t.w, t.h, fmt);
     return nullptr;
@@ -106,29 +89,18 @@ static int tile_fits(const wz_engine* e, const char* what, int id, int w, int h,
 static void tile_planes(const uint8_t* src, int w, int h, int fmt, const wz_tile_t& t, uint8_t* dst, std::vector<WzCropPlane>& out) {
     const int base = fmt & WZ_FMT_BASE_MASK;
     const size_t W = (size_t)w, H = (size_t)h;
-    if (base == WZ_FMT_P010 || base == WZ_FMT_YUV420P10) {   // NV12's / I420's planes with two bytes a sample
-        out.push_back({src + ((size_t)t.y0 * W + t.x0) * 2, dst, w * 2, t.w * 2, t.h, 0});
-        const uint8_t* chroma = src + W * H * 2;
-        uint8_t* dc = dst + (size_t)t.w * t.h * 2;
-        if (base == WZ_FMT_P010) {   // a (U, V) pair of chroma column x0 / 2 is 4 bytes: 2 x0 bytes into its row of 2w
-            out.push_back({chroma + ((size_t)(t.y0 / 2) * W + t.x0) * 2, dc, w * 2, t.w * 2, t.h / 2, 0});
+    const bool ten = base == WZ_FMT_P010 || base == WZ_FMT_YUV420P10;   // NV12's / I420's planes with two bytes a sample
+    if (ten || base == WZ_FMT_NV12 || base == WZ_FMT_I420) {
+        const int s = ten ? 2 : 1;
+        out.push_back({src + ((size_t)t.y0 * W + t.x0) * s, dst, w * s, t.w * s, t.h, 0});
+        const uint8_t* chroma = src + W * H * s;
+        uint8_t* dc = dst + (size_t)t.w * t.h * s;
+        if (base == WZ_FMT_NV12 || base == WZ_FMT_P010) {   // the (U, V) pair of chroma column x0 / 2 lies x0 samples into its row of w
+            out.push_back({chroma + ((size_t)(t.y0 / 2) * W + t.x0) * s, dc, w * s, t.w * s, t.h / 2, 0});
         } else {
-            const size_t cw = W / 2, ch = H / 2, off = ((size_t)(t.y0 / 2) * cw + t.x0 / 2) * 2;
-            out.push_back({chroma + off, dc, w, t.w, t.h / 2, 0});
-            out.push_back({chroma + cw * ch * 2 + off, dc + (size_t)(t.w / 2) * (t.h / 2) * 2, w, t.w, t.h / 2, 0});
-        }
-        return;
-    }
-    if (base == WZ_FMT_NV12 || base == WZ_FMT_I420) {
-        out.push_back({src + (size_t)t.y0 * W + t.x0, dst, w, t.w, t.h, 0});
-        const uint8_t* chroma = src + W * H;
-        uint8_t* dc = dst + (size_t)t.w * t.h;
-        if (base == WZ_FMT_NV12) {
-            out.push_back({chroma + (size_t)(t.y0 / 2) * W + t.x0, dc, w, t.w, t.h / 2, 0});
-        } else {
-            const size_t cw = W / 2, ch = H / 2, off = (size_t)(t.y0 / 2) * cw + t.x0 / 2;
-            out.push_back({chroma + off, dc, w / 2, t.w / 2, t.h / 2, 0});
-            out.push_back({chroma + cw * ch + off, dc + (size_t)(t.w / 2) * (t.h / 2), w / 2, t.w / 2, t.h / 2, 0});
+            const size_t cw = W / 2, ch = H / 2, off = ((size_t)(t.y0 / 2) * cw + t.x0 / 2) * s;
+            out.push_back({chroma + off, dc, w / 2 * s, t.w / 2 * s, t.h / 2, 0});
+            out.push_back({chroma + cw * ch * s + off, dc + (size_t)(t.w / 2) * (t.h / 2) * s, w / 2 * s, t.w / 2 * s, t.h / 2, 0});
         }
         return;
     }
@@ -147,8 +119,8 @@ static void gate_tile(const uint8_t* src, int w, int fmt, const wz_tile_t& t, Wz
     g.row_bytes = t.w * bpp;
     g.tw = t.w;
     g.th = t.h;
-    g.cols = (t.w + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
-    g.crows = (t.h + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
+    g.cols = cells_of(t.w);
+    g.crows = cells_of(t.h);
     // The 10-bit formats are gated on the top 8 bits of a sample, so that sums and threshold keep their 8-bit meaning: of a P010 word
     // (sample << 6) that is its second byte -- UYVY's odd bytes --, of a YUV420P10 word bits 2 .. 9 (WZ_GATE_LOW10).
     g.mode = base == WZ_FMT_RGB24 ? WZ_GATE_RGB : base == WZ_FMT_BGR24 ? WZ_GATE_BGR : base == WZ_FMT_YUYV422 ? WZ_GATE_YUYV
@@ -157,7 +129,8 @@ static void gate_tile(const uint8_t* src, int w, int fmt, const wz_tile_t& t, Wz
 
 // ---- a call, its checks, its plan
 // A tiled or gated call.  fmt and (tiled) cam may be null; a tiled call brings n_tiles / tiles, a gated one gets them from its cameras'
-// layouts when it is enqueued; `total`, all its tiles, is what its check leaves.
+// layouts when it is enqueued, a motion one from the region launch; `total`, all its tiles, is what its check leaves (a motion call's: the most
+// it can have).
 struct TileCall {
     int n;
     const uint8_t* const* frames;
@@ -200,31 +173,42 @@ static int tiled_check(wz_engine* e, const char* who, int slot, TileCall& c, boo
     return thresholds_refusal(who, c);
 }
 
-// Every refusal of a gated call (include/watsor_hip.h), before anything is enqueued, written or decided
-static int gated_check(wz_engine* e, const char* who, int slot, TileCall& c, bool host) {
+// What the two kinds of per-camera call -- gated, motion -- bring to their check: the words of its texts, and (by the type of its cameras)
+// what a frame of a camera costs in tiles
+struct CamKind { const char *name, *what, *setter, *made, *sum; };
+static const CamKind GATED = {"gated", "tiles", "wz_set_camera_tiles", "set", ""};
+static const CamKind MOTION = {"motion", "motion settings", "wz_set_camera_motion", "made", " (whole_frame + max_regions)"};
+static int64_t tiles_of(const GateCam& g) { return (int64_t)g.tiles.size(); }
+static int64_t tiles_of(const MotionCam& m) { return m.p.whole_frame + m.p.max_regions; }
+
+// Every refusal of a gated or motion call (include/watsor_hip.h), before anything is enqueued, written, decided or found.  known: the
+// engine's cameras of that kind (e may still be null here)
+template <class Cam>
+static int camera_check(wz_engine* e, std::map<int, Cam> wz_engine::*known, const CamKind& kind, const char* who, int slot, TileCall& c, bool host) {
     int rc = call_refusal(e, who, slot, c, false);
     if (rc != WZ_OK) return rc;
     const int* cam = c.cam;
-    if (!cam) return wz_set_error(WZ_EINVAL, "%s: a gated call needs the frames' camera ids", who);
+    if (!cam) return wz_set_error(WZ_EINVAL, "%s: a %s call needs the frames' camera ids", who, kind.name);
     int64_t sum = 0;
     for (int i = 0; i < c.n; ++i) {
         const int w = c.w[i], h = c.h[i], pf = c.pf(i);
         auto refused = [&](unsigned checks) { return (rc = frame_refusal(e, "frame", i, c.frames[i], w, h, pf, cam[i], checks)) != WZ_OK; };
         if (refused(FC_PTR)) return rc;
-        auto it = cam[i] < 0 ? e->gate_cams.end() : e->gate_cams.find(cam[i]);
-        if (it == e->gate_cams.end()) return wz_set_error(WZ_EINVAL, "frame %d: camera %d has no tiles (wz_set_camera_tiles first)", i, cam[i]);
+        const auto it = (e->*known).find(cam[i]);
+        if (it == (e->*known).end()) return wz_set_error(WZ_EINVAL, "frame %d: camera %d has no %s (%s first)", i, cam[i], kind.what, kind.setter);
         for (int j = 0; j < i; ++j)
-            if (cam[j] == cam[i]) return wz_set_error(WZ_EINVAL, "frames %d and %d are both camera %d's: one frame of a camera per gated call", j, i, cam[i]);
-        const GateCam& g = it->second;
+            if (cam[j] == cam[i])
+                return wz_set_error(WZ_EINVAL, "frames %d and %d are both camera %d's: one frame of a camera per %s call", j, i, cam[i], kind.name);
+        const Cam& s = it->second;
         if (refused(FC_FMT)) return rc;
-        if (w != g.w || h != g.h || (pf & WZ_FMT_BASE_MASK) != g.base)
-            return wz_set_error(WZ_EINVAL, "frame %d is %dx%d in base format %d but camera %d's tiles were set for %dx%d in base format %d", i, w, h,
-                                pf & WZ_FMT_BASE_MASK, cam[i], g.w, g.h, g.base);
+        if (w != s.w || h != s.h || (pf & WZ_FMT_BASE_MASK) != s.base)
+            return wz_set_error(WZ_EINVAL, "frame %d is %dx%d in base format %d but camera %d's %s were %s for %dx%d in base format %d", i, w, h,
+                                pf & WZ_FMT_BASE_MASK, cam[i], kind.what, kind.made, s.w, s.h, s.base);
         if (refused((host ? FC_LIMIT : 0) | FC_CAM_FILTER)) return rc;
-        sum += (int64_t)g.tiles.size();
+        sum += tiles_of(s);
     }
     if (sum > e->max_batch)
-        return wz_set_error(WZ_ELIMIT, "the %lld tiles configured for the cameras of one call exceed max_batch %d", (long long)sum, e->max_batch);
+        return wz_set_error(WZ_ELIMIT, "the %lld tiles configured for the cameras of one call%s exceed max_batch %d", (long long)sum, kind.sum, e->max_batch);
     c.total = (int)sum;
     return thresholds_refusal(who, c);
 }
@@ -240,13 +224,13 @@ struct TilePlan {
 };
 // runs: one byte per tile of the call, 0 = the tile does not run (gated calls); null: every tile runs
 static void tile_plan(wz_engine* e, Lane& L, const TileCall& c, const uint8_t* runs, TilePlan& y) {
-    int32_t* origins = reinterpret_cast<int32_t*>(L.tile.h_tmeta + e->max_batch);
+    const TileMeta& meta = L.tile.meta.h;
     y.fresh.assign(c.total, -1);
     y.tptr.reserve(c.total); y.tw.reserve(c.total); y.th.reserve(c.total); y.tf.reserve(c.total);
     int k = 0;
     for (int i = 0; i < c.n; ++i) {
         const int pf = c.pf(i), cam = c.cam ? c.cam[i] : -1;
-        L.tile.h_tmeta[i] = {k, c.n_tiles[i], cam < 0 ? -1 : cam, 0};
+        meta.frames[i] = {k, c.n_tiles[i], cam < 0 ? -1 : cam, 0};
         y.most = std::max(y.most, c.n_tiles[i]);
         for (int t = 0; t < c.n_tiles[i]; ++t, ++k) {
             const wz_tile_t& r = c.tiles[i][t];
@@ -256,15 +240,21 @@ static void tile_plan(wz_engine* e, Lane& L, const TileCall& c, const uint8_t* r
                 tile_planes(c.frames[i], c.w[i], c.h[i], pf, r, dst, y.planes);
                 y.tptr.push_back(dst); y.tw.push_back(r.w); y.th.push_back(r.h); y.tf.push_back(pf);   // (the colour flags of the frame's format word are its tiles')
             }
-            origins[2 * k] = r.x0;
-            origins[2 * k + 1] = r.y0;
+            meta.origins[2 * k] = r.x0;
+            meta.origins[2 * k + 1] = r.y0;
         }
     }
 }
 
-// The plan's tiles as an ordinary batch without cameras: crop, then 100 unfiltered rows per tile, in tile pixel coordinates, in L.h_rows
+// The plan's tiles as an ordinary batch without cameras: crop, then 100 unfiltered rows per tile, in tile pixel coordinates, in L.h_rows.
+// No tile runs (a gated call of still tiles, a motion call of still frames): no crop, no batch, no status word is this call's.
 static int run_tiles(wz_engine* e, int slot, const TilePlan& y) {
     Lane& L = e->lanes[slot];
+    if (y.tptr.empty()) {
+        L.bound_idx.clear();
+        L.n = 0;
+        return WZ_OK;
+    }
     wz_launch_crop_tiles(y.planes.data(), (int)y.planes.size(), L.stream);
     WZCHK(fill_desc(e, slot, (int)y.tptr.size(), y.tptr.data(), y.tw.data(), y.th.data(), y.tf.data(), nullptr));
     L.rows = e->pre_rows && rows_fit(e, (int)y.tptr.size(), y.tw.data(), y.tf.data());
@@ -276,16 +266,31 @@ static int run_tiles(wz_engine* e, int slot, const TilePlan& y) {
 // still: a motion call with a frame that has no tile -- no filter runs on it, it gets the padding rows and pass bytes 0 (k_motion.hip)
 static int merge_tail(wz_engine* e, Lane& L, const TileCall& c, int most, const wz_detection_t* src, bool still = false) {
     TileLane& T = L.tile;
-    const int32_t* m_origins = reinterpret_cast<const int32_t*>(T.m_tmeta + e->max_batch);
-    wz_launch_merge_tiles(T.m_tmeta, m_origins, src, T.d_tcand, c.n, most, c.iou, c.ios, T.m_trows, T.m_tpass, L.stream);
+    wz_launch_merge_tiles(T.meta.m.frames, T.meta.m.origins, src, T.d_tcand, c.n, most, c.iou, c.ios, T.trows.d, T.tpass.d, L.stream);
     for (int i = 0; i < c.n; ++i)
         if (c.cam && c.cam[i] >= 0 && e->h_cams[c.cam[i]].enabled && !(still && c.n_tiles[i] == 0))
-            wz_launch_filter_rows(e->d_cams, c.cam[i], T.m_trows + (size_t)i * WZ_MAX_DETECTIONS, T.m_tpass + (size_t)i * WZ_MAX_DETECTIONS, L.stream);
-    if (still) wz_launch_motion_still(T.m_tmeta, c.n, T.m_trows, T.m_tpass, L.stream);
+            wz_launch_filter_rows(e->d_cams, c.cam[i], T.trows.d + (size_t)i * WZ_MAX_DETECTIONS, T.tpass.d + (size_t)i * WZ_MAX_DETECTIONS, L.stream);
+    if (still) wz_launch_motion_still(T.meta.m.frames, c.n, T.trows.d, T.tpass.d, L.stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(L.done, L.stream));
     T.tiled = c.n;
     return WZ_OK;
+}
+
+// What gated_enqueue and motion_enqueue derive from their checked call: its cameras' state, in frame order ...
+template <class Cam>
+static std::vector<Cam*> cams_of(std::map<int, Cam>& known, const TileCall& c) {
+    std::vector<Cam*> cams(c.n);
+    for (int i = 0; i < c.n; ++i) cams[i] = &known.find(c.cam[i])->second;
+    return cams;
+}
+// ... and, once the frames' rectangles are known, the tiled call on them
+static TileCall with_tiles(const TileCall& call, const std::vector<int>& nt, const std::vector<const wz_tile_t*>& tp) {
+    TileCall c = call;
+    c.n_tiles = nt.data();
+    c.tiles = tp.data();
+    c.total = std::accumulate(nt.begin(), nt.end(), 0);
+    return c;
 }
 
 // ---- tiled detection: crop launch -> an ordinary batch over the tiles -> merge launch (k_tiles.hip)
@@ -314,28 +319,25 @@ static int gated_enqueue(wz_engine* e, int slot, const TileCall& call) {
     WZCHK(L.tile.alloc(e));
     WZCHK(G.alloc(e));
     const int n = call.n, total = call.total;
-    std::vector<GateCam*> cams(n);
+    const std::vector<GateCam*> cams = cams_of(e->gate_cams, call);
     std::vector<int> nt(n);
     std::vector<const wz_tile_t*> tp(n);
     for (int i = 0; i < n; ++i) {
-        cams[i] = &e->gate_cams.find(call.cam[i])->second;
         nt[i] = (int)cams[i]->tiles.size();
         tp[i] = cams[i]->tiles.data();
         // another lane's commit launch may still be writing this camera's references and cached rows
         if (cams[i]->lane >= 0 && cams[i]->lane != slot) HIPCHK(hipEventSynchronize(e->lanes[cams[i]->lane].done));
     }
-    TileCall c = call;   // ... with the cameras' rectangles
-    c.n_tiles = nt.data();
-    c.tiles = tp.data();
+    const TileCall c = with_tiles(call, nt, tp);   // ... with the cameras' rectangles
     // 1. activity of every tile, one launch
     const size_t lane_cells = gate_cells_of(e->max_w, e->max_h);
-    WzGateCommit* commits = gate_commits(e, G.h_gmeta);
-    int32_t* act = gate_activity(e, G.h_gmeta);
+    WzGateCommit* commits = G.meta.h.commits;
+    int32_t* act = G.meta.h.activity;
     int k = 0, crows = 0, cols = 0;
     for (int i = 0; i < n; ++i) {
         GateCam& g = *cams[i];
         for (int t = 0; t < nt[i]; ++t, ++k) {
-            WzGateTile& d = G.h_gmeta[k];
+            WzGateTile& d = G.meta.h.tiles[k];
             gate_tile(c.frames[i], c.w[i], c.pf(i), g.tiles[t], d);
             d.ref = g.has_ref[t] ? g.d_ref + g.grid_off[t] : nullptr;
             d.now = G.d_gnow + lane_cells * k;
@@ -346,7 +348,7 @@ static int gated_enqueue(wz_engine* e, int slot, const TileCall& call) {
             commits[k] = {g.d_ref + g.grid_off[t], d.now, g.d_rows + (size_t)t * WZ_MAX_DETECTIONS, d.cols * d.crows, -1};   // (fresh: step 2)
         }
     }
-    wz_launch_tile_activity(G.m_gmeta, total, crows, cols, G.d_gcount, gate_activity(e, G.m_gmeta), L.stream);
+    wz_launch_tile_activity(G.meta.m.tiles, total, crows, cols, G.d_gcount, G.meta.m.activity, L.stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(L.stream));   // the batch size is a host-side quantity: the decision waits for the counts
     // 2. the decision; the cameras' state changes only once everything is enqueued
@@ -358,14 +360,9 @@ static int gated_enqueue(wz_engine* e, int slot, const TileCall& call) {
     tile_plan(e, L, c, runs.data(), y);
     for (k = 0; k < total; ++k) commits[k].fresh = y.fresh[k];
     // 3. the tiles that run, as an ordinary batch without cameras (none: no crop, no batch)
-    if (!y.tptr.empty()) {
-        WZCHK(run_tiles(e, slot, y));
-    } else {
-        L.bound_idx.clear();
-        L.n = 0;   // (no tile ran: no status word is this call's)
-    }
+    WZCHK(run_tiles(e, slot, y));
     // 4. commit, merge, filters
-    wz_launch_gate_commit(gate_commits(e, G.m_gmeta), total, L.m_rows, G.d_grows, L.stream);
+    wz_launch_gate_commit(G.meta.m.commits, total, L.m_rows, G.d_grows, L.stream);
     WZCHK(merge_tail(e, L, c, y.most, G.d_grows));
     // 5. the state the commit launch leaves behind, and what wz_gate_stats reports
     G.g_ran.assign(n, 0);
@@ -391,46 +388,6 @@ static int gated_enqueue(wz_engine* e, int slot, const TileCall& call) {
 
 // ---- motion regions: whole-frame activity launch -> region launch -> the host reads the rectangles -> a tiled call on them (k_motion.hip,
 // DESIGN.md section 19)
-typedef wz_engine::MotionCam MotionCam;
-
-void MotionCam::release() {
-    for (uint16_t*& g : d_grid) {
-        if (g) (void)hipFree(g);
-        g = nullptr;
-    }
-}
-
-static size_t motion_cam_words(const wz_engine* e) { return std::min((size_t)WZ_MOTION_MAX_CELLS, gate_cells_of(e->max_w, e->max_h)); }
-// the pinned block of a lane: the activity launch's whole-frame tiles, the region launch's cameras, what it found, the activity counts (unused)
-static WzGateTile* motion_tiles(uint8_t* meta) { return reinterpret_cast<WzGateTile*>(meta); }
-static WzMotionCam* motion_descs(const wz_engine* e, uint8_t* meta) { return reinterpret_cast<WzMotionCam*>(motion_tiles(meta) + e->max_batch); }
-static WzMotionOut* motion_outs(const wz_engine* e, uint8_t* meta) { return reinterpret_cast<WzMotionOut*>(motion_descs(e, meta) + e->max_batch); }
-static int32_t* motion_activity(const wz_engine* e, uint8_t* meta) { return reinterpret_cast<int32_t*>(motion_outs(e, meta) + e->max_batch); }
-static_assert(sizeof(WzGateTile) % 8 == 0 && sizeof(WzMotionCam) % 8 == 0 && sizeof(WzMotionOut) % 8 == 0, "the block's parts stay aligned");
-
-int MotionLane::alloc(wz_engine* e) {
-    if (d_mscratch) return WZ_OK;
-    const size_t nb = (size_t)e->max_batch, words = motion_cam_words(e);
-    MotionLane m;
-    hipError_t err = hipMalloc((void**)&m.d_mscratch, words * 4 * nb);
-    if (err == hipSuccess) err = hipMalloc((void**)&m.d_mcount, 8 * nb);
-    if (err == hipSuccess) err = lane0_fill(e, m.d_mcount, 0, 8 * nb);
-    if (err == hipSuccess) err = hipHostMalloc((void**)&m.h_mmeta, (sizeof(WzGateTile) + sizeof(WzMotionCam) + sizeof(WzMotionOut) + 8) * nb, hipHostMallocMapped);
-    if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&m.m_mmeta, m.h_mmeta, 0);
-    if (err != hipSuccess) {
-        m.release();
-        return wz_set_error(WZ_EHIP, "motion scratch of a lane: %s", hipGetErrorString(err));
-    }
-    d_mscratch = m.d_mscratch; d_mcount = m.d_mcount; h_mmeta = m.h_mmeta; m_mmeta = m.m_mmeta; cam_words = words;
-    return WZ_OK;
-}
-void MotionLane::release() {
-    if (d_mscratch) (void)hipFree(d_mscratch);
-    if (d_mcount) (void)hipFree(d_mcount);
-    if (h_mmeta) (void)hipHostFree(h_mmeta);
-    d_mscratch = nullptr; d_mcount = nullptr; h_mmeta = m_mmeta = nullptr;
-}
-
 // Why these settings are refused for a w x h frame of format word fmt (wz_last_error is set), or WZ_OK; e null: the engine's limits are not looked at
 static int motion_refusal(const wz_engine* e, const char* who, int w, int h, int fmt, const wz_motion_t& p) {
     if (!wz_frame_bytes(w, h, fmt)) return wz_set_error(WZ_EINVAL, "%s: pixel format 0x%x at %dx%d: %s", who, fmt, w, h, fmt_refusal(w, h, fmt));
@@ -454,41 +411,11 @@ static void motion_desc(int w, int h, int fmt, const wz_motion_t& p, const uint1
     const bool planar = base == WZ_FMT_NV12 || base == WZ_FMT_I420 || base == WZ_FMT_P010 || base == WZ_FMT_YUV420P10;
     d.now = now; d.ref = ref; d.scratch = scratch;
     d.W = w; d.H = h;
-    d.gw = (w + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
-    d.gh = (h + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
+    d.gw = cells_of(w);
+    d.gh = cells_of(h);
     d.thr = p.pixel_thr; d.min_cells = p.min_cells; d.dilate = p.dilate; d.max_regions = p.max_regions; d.min_side = p.min_side; d.pad = p.pad;
     d.even_x = (planar || base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422) ? 1 : 0;
     d.even_y = planar ? 1 : 0;
-}
-
-// Every refusal of a motion call (include/watsor_hip.h), before anything is enqueued, written or found
-static int motion_check(wz_engine* e, const char* who, int slot, TileCall& c, bool host) {
-    int rc = call_refusal(e, who, slot, c, false);
-    if (rc != WZ_OK) return rc;
-    const int* cam = c.cam;
-    if (!cam) return wz_set_error(WZ_EINVAL, "%s: a motion call needs the frames' camera ids", who);
-    int64_t sum = 0;
-    for (int i = 0; i < c.n; ++i) {
-        const int w = c.w[i], h = c.h[i], pf = c.pf(i);
-        auto refused = [&](unsigned checks) { return (rc = frame_refusal(e, "frame", i, c.frames[i], w, h, pf, cam[i], checks)) != WZ_OK; };
-        if (refused(FC_PTR)) return rc;
-        auto it = cam[i] < 0 ? e->motion_cams.end() : e->motion_cams.find(cam[i]);
-        if (it == e->motion_cams.end()) return wz_set_error(WZ_EINVAL, "frame %d: camera %d has no motion settings (wz_set_camera_motion first)", i, cam[i]);
-        for (int j = 0; j < i; ++j)
-            if (cam[j] == cam[i]) return wz_set_error(WZ_EINVAL, "frames %d and %d are both camera %d's: one frame of a camera per motion call", j, i, cam[i]);
-        const MotionCam& m = it->second;
-        if (refused(FC_FMT)) return rc;
-        if (w != m.w || h != m.h || (pf & WZ_FMT_BASE_MASK) != m.base)
-            return wz_set_error(WZ_EINVAL, "frame %d is %dx%d in base format %d but camera %d's motion settings were made for %dx%d in base format %d", i, w, h,
-                                pf & WZ_FMT_BASE_MASK, cam[i], m.w, m.h, m.base);
-        if (refused((host ? FC_LIMIT : 0) | FC_CAM_FILTER)) return rc;
-        sum += m.p.whole_frame + m.p.max_regions;
-    }
-    if (sum > e->max_batch)
-        return wz_set_error(WZ_ELIMIT, "the %lld tiles configured for the cameras of one call (whole_frame + max_regions) exceed max_batch %d", (long long)sum,
-                            e->max_batch);
-    c.total = 0;
-    return thresholds_refusal(who, c);
 }
 
 // A checked motion call on a drained lane, frames in device memory.  Returns once the rectangles are read: the two launches that touch the
@@ -501,35 +428,34 @@ static int motion_enqueue(wz_engine* e, int slot, const TileCall& call) {
     WZCHK(M.alloc(e));
     const int n = call.n;
     constexpr int PER = 1 + WZ_MOTION_MAX_REGIONS;
-    std::vector<MotionCam*> cams(n);
+    const std::vector<MotionCam*> cams = cams_of(e->motion_cams, call);
     // 1. the whole frame's grid of every camera, one launch; 2. its regions, one launch; then the one wait of the call
-    WzGateTile* gt = motion_tiles(M.h_mmeta);
-    WzMotionCam* md = motion_descs(e, M.h_mmeta);
-    WzMotionOut* mo = motion_outs(e, M.h_mmeta);
+    WzGateTile* gt = M.meta.h.tiles;
+    WzMotionCam* md = M.meta.h.cams;
+    WzMotionOut* mo = M.meta.h.outs;
     int crows = 0, cols = 0, cells = 0;
     for (int i = 0; i < n; ++i) {
-        MotionCam& m = *(cams[i] = &e->motion_cams.find(call.cam[i])->second);
+        MotionCam& m = *cams[i];
         const wz_tile_t whole = {0, 0, m.w, m.h};
         uint16_t* now = m.d_grid[m.cur ^ 1];
         gate_tile(call.frames[i], m.w, call.pf(i), whole, gt[i]);
         gt[i].ref = nullptr;   // (the region launch compares: this launch only sums)
         gt[i].now = now;
         gt[i].thr = 0;
-        motion_desc(m.w, m.h, call.pf(i), m.p, now, m.has_ref ? m.d_grid[m.cur] : nullptr, M.d_mscratch + M.cam_words * i, md[i]);
+        motion_desc(m.w, m.h, call.pf(i), m.p, now, m.has_ref ? m.d_grid[m.cur].p : nullptr, M.d_mscratch + M.cam_words * i, md[i]);
         crows = std::max(crows, gt[i].crows);
         cols = std::max(cols, gt[i].cols);
         cells = std::max(cells, m.gw * m.gh);
         mo[i].n_regions = -1;
     }
-    wz_launch_tile_activity(motion_tiles(M.m_mmeta), n, crows, cols, M.d_mcount, motion_activity(e, M.m_mmeta), L.stream);
-    wz_launch_motion_regions(motion_descs(e, M.m_mmeta), n, cells, motion_outs(e, M.m_mmeta), L.stream);
+    wz_launch_tile_activity(M.meta.m.tiles, n, crows, cols, M.d_mcount, M.meta.m.activity, L.stream);
+    wz_launch_motion_regions(M.meta.m.cams, n, cells, M.meta.m.outs, L.stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(L.stream));   // the batch size is a host-side quantity: the plan waits for the rectangles
     // 3. the tile lists; the cameras' state changes only once everything is enqueued
     std::vector<wz_tile_t> tiles((size_t)n * PER);
     std::vector<int32_t> nt(n), comps(n), ncell((size_t)n * WZ_MOTION_MAX_REGIONS, 0);
     std::vector<const wz_tile_t*> tp(n);
-    int total = 0;
     bool still = false;
     for (int i = 0; i < n; ++i) {
         const MotionCam& m = *cams[i];
@@ -546,21 +472,12 @@ static int motion_enqueue(wz_engine* e, int slot, const TileCall& call) {
         nt[i] = k;
         tp[i] = t;
         comps[i] = o.components;
-        total += k;
         still = still || k == 0;
     }
-    TileCall c = call;   // ... a tiled call on these lists
-    c.n_tiles = nt.data();
-    c.tiles = tp.data();
-    c.total = total;
+    const TileCall c = with_tiles(call, nt, tp);   // ... a tiled call on these lists
     TilePlan y;
     tile_plan(e, L, c, nullptr, y);
-    if (!y.tptr.empty()) {
-        WZCHK(run_tiles(e, slot, y));
-    } else {
-        L.bound_idx.clear();
-        L.n = 0;   // (no tile: no crop, no batch, no status word is this call's)
-    }
+    WZCHK(run_tiles(e, slot, y));
     WZCHK(merge_tail(e, L, c, y.most, L.m_rows, still));
     // 4. the grid this call wrote is the next call's reference; what wz_motion_stats reports
     for (int i = 0; i < n; ++i) {
@@ -623,13 +540,13 @@ extern "C" int wz_detect_tiled(wz_engine_t* e, int n, const uint8_t* const* fram
 extern "C" int wz_submit_gated_device(wz_engine_t* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
                                       const int* cam, double iou_thr, double ios_thr) {
     TileCall c = {n, d_frames, w, h, fmt, cam, nullptr, nullptr, iou_thr, ios_thr, 0};
-    WZCHK(gated_check(e, "wz_submit_gated_device", slot, c, false));
+    WZCHK(camera_check(e, &wz_engine::gate_cams, GATED, "wz_submit_gated_device", slot, c, false));
     return submit_device(e, slot, c, KIND_GATED);
 }
 extern "C" int wz_detect_gated(wz_engine_t* e, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt, const int* cam,
                                double iou_thr, double ios_thr, wz_detection_t* const* out, uint8_t* const* pass, float* ms) {
     TileCall c = {n, frames, w, h, fmt, cam, nullptr, nullptr, iou_thr, ios_thr, 0};
-    WZCHK(gated_check(e, "wz_detect_gated", 0, c, true));
+    WZCHK(camera_check(e, &wz_engine::gate_cams, GATED, "wz_detect_gated", 0, c, true));
     return detect_staged(e, c, KIND_GATED, out, pass, ms);
 }
 
@@ -653,22 +570,17 @@ extern "C" int wz_set_camera_motion(wz_engine_t* e, int cam, int width, int heig
     WZCHK(motion_refusal(e, who, width, height, fmt, *motion));
     MotionCam m;
     m.w = width; m.h = height; m.fmt = fmt; m.base = fmt & WZ_FMT_BASE_MASK;
-    m.gw = (width + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
-    m.gh = (height + WZ_GATE_CELL - 1) / WZ_GATE_CELL;
+    m.gw = cells_of(width);
+    m.gh = cells_of(height);
     m.p = *motion;
     m.p._reserved = 0;
     HIPCHK(hipSetDevice(e->device));
     WZCHK(sync_all(e));
     // the new grids are allocated aside: a failure leaves the camera with the settings (and the reference) it had
-    hipError_t err = hipMalloc((void**)&m.d_grid[0], (size_t)m.gw * m.gh * 2);
-    if (err == hipSuccess) err = hipMalloc((void**)&m.d_grid[1], (size_t)m.gw * m.gh * 2);
-    if (err != hipSuccess) {
-        m.release();
-        return wz_set_error(WZ_EHIP, "wz_set_camera_motion: %s (camera %d keeps its previous settings)", hipGetErrorString(err), cam);
-    }
-    auto it = e->motion_cams.find(cam);
-    if (it != e->motion_cams.end()) it->second.release();   // nothing in flight reads the old grids: every lane was synchronised above
-    e->motion_cams[cam] = m;
+    hipError_t err = m.d_grid[0].alloc((size_t)m.gw * m.gh);
+    if (err == hipSuccess) err = m.d_grid[1].alloc((size_t)m.gw * m.gh);
+    if (err != hipSuccess) return wz_set_error(WZ_EHIP, "wz_set_camera_motion: %s (camera %d keeps its previous settings)", hipGetErrorString(err), cam);
+    e->motion_cams[cam] = std::move(m);   // (m leaves with the old grids: nothing in flight reads them, every lane was synchronised above)
     return WZ_OK;
 }
 
@@ -686,7 +598,6 @@ extern "C" int wz_clear_camera_motion(wz_engine_t* e, int cam) {
     if (it == e->motion_cams.end()) return WZ_OK;
     HIPCHK(hipSetDevice(e->device));
     WZCHK(sync_all(e));
-    it->second.release();
     e->motion_cams.erase(it);
     return WZ_OK;
 }
@@ -694,13 +605,13 @@ extern "C" int wz_clear_camera_motion(wz_engine_t* e, int cam) {
 extern "C" int wz_submit_motion_device(wz_engine_t* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h, const int* fmt,
                                        const int* cam, double iou_thr, double ios_thr) {
     TileCall c = {n, d_frames, w, h, fmt, cam, nullptr, nullptr, iou_thr, ios_thr, 0};
-    WZCHK(motion_check(e, "wz_submit_motion_device", slot, c, false));
+    WZCHK(camera_check(e, &wz_engine::motion_cams, MOTION, "wz_submit_motion_device", slot, c, false));
     return submit_device(e, slot, c, KIND_MOTION);
 }
 extern "C" int wz_detect_motion(wz_engine_t* e, int n, const uint8_t* const* frames, const int* w, const int* h, const int* fmt, const int* cam,
                                 double iou_thr, double ios_thr, wz_detection_t* const* out, uint8_t* const* pass, float* ms) {
     TileCall c = {n, frames, w, h, fmt, cam, nullptr, nullptr, iou_thr, ios_thr, 0};
-    WZCHK(motion_check(e, "wz_detect_motion", 0, c, true));
+    WZCHK(camera_check(e, &wz_engine::motion_cams, MOTION, "wz_detect_motion", 0, c, true));
     return detect_staged(e, c, KIND_MOTION, out, pass, ms);
 }
 
@@ -737,8 +648,8 @@ extern "C" int wz_set_camera_tiles(wz_engine_t* e, int cam, int width, int heigh
         const wz_tile_t& r = tiles[t];
         WZCHK(tile_fits(e, "camera", cam, width, height, fmt, t, r));
         g.tiles.push_back(r);
-        g.cols.push_back((r.w + WZ_GATE_CELL - 1) / WZ_GATE_CELL);
-        g.crows.push_back((r.h + WZ_GATE_CELL - 1) / WZ_GATE_CELL);
+        g.cols.push_back(cells_of(r.w));
+        g.crows.push_back(cells_of(r.h));
         g.grid_off.push_back(cells);
         cells += (gate_cells_of(r.w, r.h) + 7) & ~(size_t)7;   // (every grid begins at a 16-byte boundary)
     }
@@ -747,15 +658,10 @@ extern "C" int wz_set_camera_tiles(wz_engine_t* e, int cam, int width, int heigh
     HIPCHK(hipSetDevice(e->device));
     WZCHK(sync_all(e));
     // the new state is allocated aside: a failure leaves the camera with the layout (and the references) it had
-    hipError_t err = hipMalloc((void**)&g.d_ref, cells * 2);
-    if (err == hipSuccess) err = hipMalloc((void**)&g.d_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS * n_tiles);
-    if (err != hipSuccess) {
-        g.release();
-        return wz_set_error(WZ_EHIP, "wz_set_camera_tiles: %s (camera %d keeps its previous tiles)", hipGetErrorString(err), cam);
-    }
-    auto it = e->gate_cams.find(cam);
-    if (it != e->gate_cams.end()) it->second.release();   // nothing in flight reads the old state: every lane was synchronised above
-    e->gate_cams[cam] = std::move(g);
+    hipError_t err = g.d_ref.alloc(cells);
+    if (err == hipSuccess) err = g.d_rows.alloc((size_t)WZ_MAX_DETECTIONS * n_tiles);
+    if (err != hipSuccess) return wz_set_error(WZ_EHIP, "wz_set_camera_tiles: %s (camera %d keeps its previous tiles)", hipGetErrorString(err), cam);
+    e->gate_cams[cam] = std::move(g);   // (g leaves with the old state: nothing in flight reads it, every lane was synchronised above)
     return WZ_OK;
 }
 
@@ -776,7 +682,6 @@ extern "C" int wz_clear_camera_tiles(wz_engine_t* e, int cam) {
     if (it == e->gate_cams.end()) return WZ_OK;
     HIPCHK(hipSetDevice(e->device));
     WZCHK(sync_all(e));
-    it->second.release();
     e->gate_cams.erase(it);
     return WZ_OK;
 }
@@ -875,7 +780,7 @@ int submit_bound_tiles(wz_engine* e, int slot, int n, const int32_t* entries) {
         tp[i] = e->bound_tiles[entries[i]].tiles.data();
     }
     TileCall c = {n, b.ptr.data(), b.w, b.h, b.fmt, b.cam, nt.data(), tp.data(), d0.iou, d0.ios, 0};
-    WZCHK(gated ? gated_check(e, "wz_submit_bound", slot, c, true) : tiled_check(e, "wz_submit_bound", slot, c, true));
+    WZCHK(gated ? camera_check(e, &wz_engine::gate_cams, GATED, "wz_submit_bound", slot, c, true) : tiled_check(e, "wz_submit_bound", slot, c, true));
     WZCHK(bound_drain(e, slot));
     Lane& L = e->lanes[slot];
     std::vector<int32_t> src(n);
@@ -920,11 +825,10 @@ extern "C" int wz_stage_crop_tile(wz_engine_t* e, const uint8_t* frame, int w, i
     if (bytes >> 31) return wz_set_error(WZ_ELIMIT, "frame too large");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
-    uint8_t* d_src = nullptr;
-    uint8_t* d_dst = nullptr;
+    DevBlock<uint8_t> d_src, d_dst;
     const uint8_t* src = nullptr;
-    hipError_t err = skewed_copy(frame, bytes, &d_src, &src);
-    if (err == hipSuccess) err = hipMalloc((void**)&d_dst, tbytes);
+    hipError_t err = skewed_copy(frame, bytes, &d_src.p, &src);
+    if (err == hipSuccess) err = d_dst.alloc(tbytes);
     if (err == hipSuccess) {
         std::vector<WzCropPlane> planes;
         tile_planes(src, w, h, fmt, *tile, d_dst, planes);
@@ -932,8 +836,6 @@ extern "C" int wz_stage_crop_tile(wz_engine_t* e, const uint8_t* frame, int w, i
         err = hipStreamSynchronize(e->stream);
     }
     if (err == hipSuccess) err = hipMemcpy(out, d_dst, tbytes, hipMemcpyDeviceToHost);
-    if (d_src) (void)hipFree(d_src);
-    if (d_dst) (void)hipFree(d_dst);
     if (err != hipSuccess) return wz_set_error(WZ_EHIP, "wz_stage_crop_tile: %s", hipGetErrorString(err));
     return WZ_OK;
 }
@@ -953,28 +855,30 @@ extern "C" int wz_stage_merge_tiles(wz_engine_t* e, int w, int h, int cam, int n
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     const size_t nr = (size_t)n_tiles * WZ_MAX_DETECTIONS;
-    const size_t off_meta = sizeof(wz_detection_t) * nr, off_org = off_meta + sizeof(WzMergeFrame), off_cand = off_org + 8 * (size_t)n_tiles,
-                 off_rows = off_cand + sizeof(WzMergeCand) * nr, off_pass = off_rows + sizeof(wz_detection_t) * WZ_MAX_DETECTIONS,
-                 all = off_pass + WZ_MAX_DETECTIONS;   // (every block's size is a multiple of 8: the offsets stay aligned)
-    uint8_t* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, all));
+    struct Parts { wz_detection_t* in; WzMergeFrame* frame; int32_t* org; WzMergeCand* cand; wz_detection_t* rows; uint8_t* pass; size_t bytes; };
+    auto carve = [&](const void* base) {   // one device block: the tiles' rows, the frame, its origins, the scratch, the merged rows, their pass bytes
+        Carve c(base);
+        Parts p = {c.take<wz_detection_t>(nr), c.take<WzMergeFrame>(1), c.take<int32_t>(2 * (size_t)n_tiles), c.take<WzMergeCand>(nr),
+                   c.take<wz_detection_t>(WZ_MAX_DETECTIONS), c.take<uint8_t>(WZ_MAX_DETECTIONS), 0};
+        p.bytes = c.bytes();
+        return p;
+    };
+    DevBlock<uint8_t> d;
+    HIPCHK(d.alloc(carve(nullptr).bytes));
+    const Parts p = carve(d);
     const WzMergeFrame fr = {0, n_tiles, cam < 0 ? -1 : cam, 0};
     std::vector<int32_t> org(2 * (size_t)n_tiles);
     for (int t = 0; t < n_tiles; ++t) org[2 * t] = tiles[t].x0, org[2 * t + 1] = tiles[t].y0;
-    hipError_t err = hipMemcpy(d, tile_rows, off_meta, hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(d + off_meta, &fr, sizeof(fr), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(d + off_org, org.data(), org.size() * 4, hipMemcpyHostToDevice);
+    hipError_t err = hipMemcpy(p.in, tile_rows, sizeof(wz_detection_t) * nr, hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(p.frame, &fr, sizeof(fr), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(p.org, org.data(), org.size() * 4, hipMemcpyHostToDevice);
     if (err == hipSuccess) {
-        wz_detection_t* d_rows = reinterpret_cast<wz_detection_t*>(d + off_rows);
-        wz_launch_merge_tiles(reinterpret_cast<const WzMergeFrame*>(d + off_meta), reinterpret_cast<const int32_t*>(d + off_org),
-                              reinterpret_cast<const wz_detection_t*>(d), reinterpret_cast<WzMergeCand*>(d + off_cand), 1, n_tiles, iou_thr,
-                              ios_thr, d_rows, d + off_pass, e->stream);
-        if (cam >= 0 && e->h_cams[cam].enabled) wz_launch_filter_rows(e->d_cams, cam, d_rows, d + off_pass, e->stream);
+        wz_launch_merge_tiles(p.frame, p.org, p.in, p.cand, 1, n_tiles, iou_thr, ios_thr, p.rows, p.pass, e->stream);
+        if (cam >= 0 && e->h_cams[cam].enabled) wz_launch_filter_rows(e->d_cams, cam, p.rows, p.pass, e->stream);
         err = hipStreamSynchronize(e->stream);
     }
-    if (err == hipSuccess) err = hipMemcpy(rows, d + off_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS, hipMemcpyDeviceToHost);
-    if (err == hipSuccess) err = hipMemcpy(pass, d + off_pass, WZ_MAX_DETECTIONS, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
+    if (err == hipSuccess) err = hipMemcpy(rows, p.rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS, hipMemcpyDeviceToHost);
+    if (err == hipSuccess) err = hipMemcpy(pass, p.pass, WZ_MAX_DETECTIONS, hipMemcpyDeviceToHost);
     if (err != hipSuccess) return wz_set_error(WZ_EHIP, "wz_stage_merge_tiles: %s", hipGetErrorString(err));
     return WZ_OK;
 }
@@ -990,32 +894,35 @@ extern "C" int wz_stage_tile_activity(wz_engine_t* e, const uint8_t* frame, int 
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     const size_t cells = gate_cells_of(tile->w, tile->h);
-    const size_t off_ref = (cells * 2 + 15) & ~(size_t)15, off_desc = 2 * off_ref, off_cnt = off_desc + 64, all = off_cnt + 16;
-    uint8_t* d_src = nullptr;
+    struct Parts { uint16_t *now, *ref; WzGateTile* tile; int32_t* cnt; size_t bytes; };
+    auto carve = [&](const void* base) {   // one device block: new grid, reference grid, the tile's descriptor, the two counters and the count
+        Carve c(base);
+        Parts p = {c.take<uint16_t>(cells, 16), c.take<uint16_t>(cells, 16), c.take<WzGateTile>(1, 16), c.take<int32_t>(4), 0};
+        p.bytes = c.bytes();
+        return p;
+    };
+    const size_t all = carve(nullptr).bytes;
+    DevBlock<uint8_t> d_src, d;
     const uint8_t* src = nullptr;
-    uint8_t* d = nullptr;   // new grid, reference grid, the tile's descriptor, the counters and the count
-    hipError_t err = skewed_copy(frame, bytes, &d_src, &src);
-    if (err == hipSuccess) err = hipMalloc((void**)&d, all);
+    hipError_t err = skewed_copy(frame, bytes, &d_src.p, &src);
+    if (err == hipSuccess) err = d.alloc(all);
     if (err == hipSuccess) err = hipMemset(d, 0, all);
-    if (err == hipSuccess && ref) err = hipMemcpy(d + off_ref, ref, cells * 2, hipMemcpyHostToDevice);
+    const Parts p = carve(d);
+    if (err == hipSuccess && ref) err = hipMemcpy(p.ref, ref, cells * 2, hipMemcpyHostToDevice);
     if (err == hipSuccess) {
-        static_assert(sizeof(WzGateTile) <= 64, "the descriptor's slot");
         WzGateTile g;
         gate_tile(src, w, fmt, *tile, g);
-        g.ref = ref ? reinterpret_cast<const uint16_t*>(d + off_ref) : nullptr;
-        g.now = reinterpret_cast<uint16_t*>(d);
+        g.ref = ref ? p.ref : nullptr;
+        g.now = p.now;
         g.thr = pixel_thr;
-        err = hipMemcpy(d + off_desc, &g, sizeof(g), hipMemcpyHostToDevice);
+        err = hipMemcpy(p.tile, &g, sizeof(g), hipMemcpyHostToDevice);
         if (err == hipSuccess) {
-            int32_t* cnt = reinterpret_cast<int32_t*>(d + off_cnt);
-            wz_launch_tile_activity(reinterpret_cast<const WzGateTile*>(d + off_desc), 1, g.crows, g.cols, cnt, cnt + 2, e->stream);
+            wz_launch_tile_activity(p.tile, 1, g.crows, g.cols, p.cnt, p.cnt + 2, e->stream);
             err = hipStreamSynchronize(e->stream);
         }
     }
-    if (err == hipSuccess) err = hipMemcpy(sums_out, d, cells * 2, hipMemcpyDeviceToHost);
-    if (err == hipSuccess) err = hipMemcpy(changed_out, d + off_cnt + 8, 4, hipMemcpyDeviceToHost);
-    if (d_src) (void)hipFree(d_src);
-    if (d) (void)hipFree(d);
+    if (err == hipSuccess) err = hipMemcpy(sums_out, p.now, cells * 2, hipMemcpyDeviceToHost);
+    if (err == hipSuccess) err = hipMemcpy(changed_out, p.cnt + 2, 4, hipMemcpyDeviceToHost);
     if (err != hipSuccess) return wz_set_error(WZ_EHIP, "wz_stage_tile_activity: %s", hipGetErrorString(err));
     return WZ_OK;
 }
@@ -1064,9 +971,8 @@ extern "C" int wz_profile_tiled(wz_engine_t* e, int n, const uint8_t* const* d_f
     TilePlan y;
     tile_plan(e, L, c, nullptr, y);
     const TileLane& T = L.tile;
-    const int32_t* m_origins = reinterpret_cast<const int32_t*>(T.m_tmeta + e->max_batch);
     WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_crop_tiles(y.planes.data(), (int)y.planes.size(), L.stream); }, crop_ms));
-    WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_merge_tiles(T.m_tmeta, m_origins, L.m_rows, T.d_tcand, n, y.most, iou_thr, ios_thr, T.m_trows, T.m_tpass, L.stream); },
+    WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_merge_tiles(T.meta.m.frames, T.meta.m.origins, L.m_rows, T.d_tcand, n, y.most, iou_thr, ios_thr, T.trows.d, T.tpass.d, L.stream); },
                      merge_ms));
     return bracket_ms(L.stream, reps, [] {}, empty_ms);   // (two event records with nothing between them: the bracket's own cost)
 }
@@ -1080,42 +986,44 @@ extern "C" int wz_profile_gated(wz_engine_t* e, int n, const uint8_t* const* d_f
     WZCHK(wz_wait(e, 0));
     Lane& L = e->lanes[0];
     const GateLane& G = L.gate;
-    WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_tile_activity(G.m_gmeta, G.g_tiles, G.g_crows, G.g_cols, G.d_gcount, gate_activity(e, G.m_gmeta), L.stream); },
-                     activity_ms));
-    WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_gate_commit(gate_commits(e, G.m_gmeta), G.g_tiles, L.m_rows, G.d_grows, L.stream); }, commit_ms));
+    WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_tile_activity(G.meta.m.tiles, G.g_tiles, G.g_crows, G.g_cols, G.d_gcount, G.meta.m.activity, L.stream); }, activity_ms));
+    WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_gate_commit(G.meta.m.commits, G.g_tiles, L.m_rows, G.d_grows, L.stream); }, commit_ms));
     return bracket_ms(L.stream, reps, [] {}, empty_ms);
 }
 
-// Two caller-provided grids of a w x h frame, the region kernel's descriptor, its scratch and its output in one device block
+// Two caller-provided grids of a w x h frame, the region kernel's scratch, descriptor and output, and a whole-frame tile of the activity
+// kernel with its two counters and its count (wz_profile_motion), in one device block
 struct MotionStage {
-    uint8_t* d = nullptr;
+    DevBlock<uint8_t> d;
+    uint16_t *now = nullptr, *ref = nullptr;
+    uint32_t* scratch = nullptr;
     WzMotionCam* cam = nullptr;
     WzMotionOut* out = nullptr;
+    WzGateTile* tile = nullptr;
+    int32_t* cnt = nullptr;
     int cells = 0;
-    size_t off_free = 0, all = 0;   // bytes behind the output that the caller may use (256)
-    ~MotionStage() { if (d) (void)hipFree(d); }
+    size_t carve(const void* base) {
+        Carve c(base);
+        now = c.take<uint16_t>(cells, 16); ref = c.take<uint16_t>(cells, 16); scratch = c.take<uint32_t>(cells, 16);
+        cam = c.take<WzMotionCam>(1, 16); out = c.take<WzMotionOut>(1); tile = c.take<WzGateTile>(1); cnt = c.take<int32_t>(4);
+        return c.bytes();
+    }
 };
 static int motion_stage(wz_engine* e, const char* who, const uint16_t* now, const uint16_t* ref, int w, int h, int fmt, const wz_motion_t* p, MotionStage& s) {
     if (!e || !now || !p) return wz_set_error(WZ_EINVAL, "%s: null argument", who);
     WZCHK(motion_refusal(nullptr, who, w, h, fmt, *p));
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
-    const size_t cells = gate_cells_of(w, h), grid = (cells * 2 + 15) & ~(size_t)15;
-    const size_t off_scratch = 2 * grid, off_cam = off_scratch + ((cells * 4 + 15) & ~(size_t)15), off_out = off_cam + 80, off_free = off_out + 336, all = off_free + 256;
-    static_assert(sizeof(WzMotionCam) <= 80 && sizeof(WzMotionOut) <= 336, "the descriptor's and the output's slots");
-    HIPCHK(hipMalloc((void**)&s.d, all));
+    s.cells = (int)gate_cells_of(w, h);
+    const size_t all = s.carve(nullptr);
+    HIPCHK(s.d.alloc(all));
+    s.carve(s.d);
     WzMotionCam d;
-    motion_desc(w, h, fmt, *p, reinterpret_cast<const uint16_t*>(s.d), ref ? reinterpret_cast<const uint16_t*>(s.d + grid) : nullptr,
-                reinterpret_cast<uint32_t*>(s.d + off_scratch), d);
+    motion_desc(w, h, fmt, *p, s.now, ref ? s.ref : nullptr, s.scratch, d);
     HIPCHK(hipMemset(s.d, 0, all));
-    HIPCHK(hipMemcpy(s.d, now, cells * 2, hipMemcpyHostToDevice));
-    if (ref) HIPCHK(hipMemcpy(s.d + grid, ref, cells * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(s.d + off_cam, &d, sizeof(d), hipMemcpyHostToDevice));
-    s.cam = reinterpret_cast<WzMotionCam*>(s.d + off_cam);
-    s.out = reinterpret_cast<WzMotionOut*>(s.d + off_out);
-    s.cells = (int)cells;
-    s.off_free = off_free;
-    s.all = all;
+    HIPCHK(hipMemcpy(s.now, now, (size_t)s.cells * 2, hipMemcpyHostToDevice));
+    if (ref) HIPCHK(hipMemcpy(s.ref, ref, (size_t)s.cells * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s.cam, &d, sizeof(d), hipMemcpyHostToDevice));
     return WZ_OK;
 }
 
@@ -1148,27 +1056,22 @@ extern "C" int wz_profile_motion(wz_engine_t* e, const uint16_t* now, const uint
     HIPCHK(hipMemcpy(&o, s.out, sizeof(o), hipMemcpyDeviceToHost));
     *rounds = o.rounds;
     const uint64_t bytes = wz_frame_bytes(w, h, fmt);
-    uint8_t* d_frame = nullptr;
-    uint16_t* d_grid = nullptr;
-    hipError_t err = hipMalloc((void**)&d_frame, bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&d_grid, (size_t)s.cells * 2);
+    DevBlock<uint8_t> d_frame;
+    DevBlock<uint16_t> d_grid;
+    hipError_t err = d_frame.alloc(bytes);
+    if (err == hipSuccess) err = d_grid.alloc((size_t)s.cells);
     if (err == hipSuccess) err = hipMemset(d_frame, 0x55, bytes);
     int rc = WZ_OK;
     if (err == hipSuccess) {
-        static_assert(sizeof(WzGateTile) <= 64, "the descriptor's slot");
         const wz_tile_t whole = {0, 0, w, h};
         WzGateTile g;
         gate_tile(d_frame, w, fmt, whole, g);
         g.ref = nullptr;
         g.now = d_grid;
         g.thr = 0;
-        WzGateTile* d_g = reinterpret_cast<WzGateTile*>(s.d + s.off_free);                // (64 bytes, then the counters and the count: zero)
-        int32_t* cnt = reinterpret_cast<int32_t*>(s.d + s.off_free + 64);
-        err = hipMemcpy(d_g, &g, sizeof(g), hipMemcpyHostToDevice);
-        if (err == hipSuccess) rc = bracket_ms(e->stream, reps, [&] { wz_launch_tile_activity(d_g, 1, g.crows, g.cols, cnt, cnt + 2, e->stream); }, activity_ms);
+        err = hipMemcpy(s.tile, &g, sizeof(g), hipMemcpyHostToDevice);   // (the counters and the count behind it are zero)
+        if (err == hipSuccess) rc = bracket_ms(e->stream, reps, [&] { wz_launch_tile_activity(s.tile, 1, g.crows, g.cols, s.cnt, s.cnt + 2, e->stream); }, activity_ms);
     }
-    if (d_frame) (void)hipFree(d_frame);
-    if (d_grid) (void)hipFree(d_grid);
     if (err != hipSuccess) return wz_set_error(WZ_EHIP, "wz_profile_motion: %s", hipGetErrorString(err));
     WZCHK(rc);
     return bracket_ms(e->stream, reps, [] {}, empty_ms);

@@ -17,6 +17,7 @@ config 2: batch = 8), used by `BatchedObjectDetector`.
 """
 from __future__ import annotations
 
+import itertools
 import os
 from typing import List, Optional, Sequence
 
@@ -233,27 +234,39 @@ def check_motion_options(motion_default, motion_by_name: dict, tiles_default, ti
         raise ValueError("motion[%r]: the camera has tiles too: a camera takes one of the two" % (both[0],))
 
 
+def cut_calls(items, max_batch: int):
+    """Cuts a list of frames into the consecutive calls one rule allows: items[i] = (key, cost, camera that may appear once per call, or
+    None); a new call starts when the key changes, when the cost would pass max_batch, or when such a camera appears again.  Returns the
+    calls as lists of indices into `items`, in order.  A pure function."""
+    calls, call, key, used, once = [], [], None, 0, set()
+    for i, (k, cost, cam) in enumerate(items):
+        if call and (k != key or used + cost > max_batch or (cam is not None and cam in once)):
+            calls.append(call)
+            call, used, once = [], 0, set()
+        key = k
+        call.append(i)
+        used += cost
+        if cam is not None:
+            once.add(cam)
+    if call:
+        calls.append(call)
+    return calls
+
+
 def plan_bound(descriptions, entries, max_batch: int):
     """Cuts a list of frame-table indices into the calls `wz_submit_bound` accepts, in order (include/watsor_hip.h): every call holds one
     kind -- untiled, tiled or gated -- and one pair of merge thresholds, at most max_batch frames whose tiles (gated: their cameras'
     configured tiles) together fit max_batch, and at most one frame of a gated camera.  The calls are consecutive pieces of `entries`, so a
     camera's frames keep their order.  descriptions[i] = (kind, iou, ios, tiles, camera id) of table entry i with kind "plain" | "tiled" |
     "gated" (what `bind_tiled_frame_table` recorded); an index beyond them counts as plain.  A pure function."""
-    calls, call, key, used, cams = [], [], None, 0, set()
+    items = []
     for e in entries:
         kind, iou, ios, tiles, cam = descriptions[e] if 0 <= e < len(descriptions) else ("plain", None, None, 1, -1)
-        k = (kind, iou, ios) if kind != "plain" else ("plain",)
-        cost = tiles if kind != "plain" else 1
-        if call and (k != key or used + cost > max_batch or len(call) >= max_batch or (kind == "gated" and cam in cams)):
-            calls.append(call)
-            call, used, cams = [], 0, set()
-        key = k
-        call.append(e)
-        used += cost
-        cams.add(cam)
-    if call:
-        calls.append(call)
-    return calls
+        if kind == "plain":
+            items.append((("plain",), 1, None))      # (a cost of 1 each: at most max_batch frames)
+        else:
+            items.append(((kind, iou, ios), tiles, cam if kind == "gated" else None))
+    return [[entries[i] for i in call] for call in cut_calls(items, max_batch)]
 
 
 class HipObjectDetector:
@@ -629,31 +642,27 @@ class HipObjectDetector:
         """The frames `moving` = [(index, settings), ...] through `detect_motion`: frames with the same thresholds share a call while their
         cameras' configured whole_frame + max_regions fit max_batch, one frame per camera and call."""
         pick = lambda seq, idx: None if seq is None else [seq[i] for i in idx]      # noqa: E731
-        ms, call, used, key = 0.0, [], 0, None
-
-        def flush():
-            nonlocal ms
-            if call:
-                ms += self.__engine.detect_motion(pick(frames, call), pick(cameras, call), pick(detections, call), pick(passes, call),
-                                                  pick(formats, call), iou=key[0], ios=key[1])
-        for i, m in moving:
-            if cameras is None or cameras[i] < 0:
-                raise ValueError("motion: frame %d comes without a camera id: the reference is kept per camera (detect_batch(..., cameras=...))" % i)
-            fmt = formats[i] if formats is not None else FMT_RGB24
-            k = (m["iou"], m["ios"])
-            if call and (used + m["count"] > self.max_batch or k != key or cameras[i] in [cameras[j] for j in call]):
-                flush()
-                call, used = [], 0
-            w, h = self.__engine.frame_geometry(frames[i], fmt)
-            layout = (w, h, fmt & FMT_BASE_MASK, id(m))
-            if self.__motion_layouts.get(cameras[i]) != layout:      # the first frame of the camera, or another size or format
-                self.__engine.set_camera_motion(cameras[i], w, h, m["threshold"], m["min_cells"], m["dilate"], m["max_regions"], m["min_side"],
-                                                m["pad"], m["whole_frame"], fmt)
-                self.__motion_layouts[cameras[i]] = layout
-            key = k
-            call.append(i)
-            used += m["count"]
-        flush()
+        # a frame without a camera id ends the list: the calls before the one it would have joined are made, then the error
+        ok = list(itertools.takewhile(lambda im: cameras is not None and cameras[im[0]] >= 0, moving))
+        calls = cut_calls([((m["iou"], m["ios"]), m["count"], cameras[i]) for i, m in ok], self.max_batch)
+        ms = 0.0
+        for n, call in enumerate(calls):
+            for i, m in (ok[j] for j in call):
+                fmt = formats[i] if formats is not None else FMT_RGB24
+                w, h = self.__engine.frame_geometry(frames[i], fmt)
+                layout = (w, h, fmt & FMT_BASE_MASK, id(m))
+                if self.__motion_layouts.get(cameras[i]) != layout:      # the first frame of the camera, or another size or format
+                    self.__engine.set_camera_motion(cameras[i], w, h, m["threshold"], m["min_cells"], m["dilate"], m["max_regions"], m["min_side"],
+                                                    m["pad"], m["whole_frame"], fmt)
+                    self.__motion_layouts[cameras[i]] = layout
+            if len(ok) < len(moving) and n == len(calls) - 1:
+                break
+            idx, m = [ok[j][0] for j in call], ok[call[0]][1]
+            ms += self.__engine.detect_motion(pick(frames, idx), pick(cameras, idx), pick(detections, idx), pick(passes, idx), pick(formats, idx),
+                                              iou=m["iou"], ios=m["ios"])
+        if len(ok) < len(moving):
+            raise ValueError("motion: frame %d comes without a camera id: the reference is kept per camera (detect_batch(..., cameras=...))"
+                             % moving[len(ok)][0])
         return ms
 
     def _detect(self, frames, detections, cameras, passes):
@@ -680,32 +689,22 @@ class HipObjectDetector:
                                              pick(formats, plain))
         # frames with the same thresholds share a call while their tiles fit max_batch (all the tiles of a call are one batch); frames of a
         # gated description that come with a camera id go through detect_gated, one frame per camera and call
-        call, rects, used, key = [], [], 0, None
-        def flush():
-            nonlocal ms
-            if call and key[2]:
+        tiled = [i for i, s in enumerate(specs) if s is not None]
+        fmt_of = lambda i: formats[i] if formats is not None else FMT_RGB24      # noqa: E731
+        rects = {i: self._rects(specs[i], frames[i], fmt_of(i)) for i in tiled}
+        gated = {i: "gate" in specs[i] and cameras is not None and cameras[i] >= 0 for i in tiled}
+        items = [((specs[i]["iou"], specs[i]["ios"], gated[i]), len(rects[i]), cameras[i] if gated[i] else None) for i in tiled]
+        for call in cut_calls(items, self.max_batch):
+            call = [tiled[j] for j in call]
+            s = specs[call[0]]
+            if gated[call[0]]:
+                for i in call:
+                    self._gate_layout(cameras[i], frames[i], fmt_of(i), rects[i], specs[i]["gate"])
                 ms += self.__engine.detect_gated(pick(frames, call), pick(cameras, call), pick(detections, call), pick(passes, call),
-                                                 pick(formats, call), iou=key[0], ios=key[1])
-            elif call:
-                ms += self.__engine.detect_tiled(pick(frames, call), rects, pick(detections, call), pick(cameras, call), pick(passes, call),
-                                                 pick(formats, call), iou=key[0], ios=key[1])
-        for i, s in enumerate(specs):
-            if s is None:
-                continue
-            fmt = formats[i] if formats is not None else FMT_RGB24
-            r = self._rects(s, frames[i], fmt)
-            gated = "gate" in s and cameras is not None and cameras[i] >= 0
-            k = (s["iou"], s["ios"], gated)
-            if call and (used + len(r) > self.max_batch or k != key or (gated and cameras[i] in [cameras[j] for j in call])):
-                flush()
-                call, rects, used = [], [], 0
-            if gated:
-                self._gate_layout(cameras[i], frames[i], fmt, r, s["gate"])
-            key = k
-            call.append(i)
-            rects.append(r)
-            used += len(r)
-        flush()
+                                                 pick(formats, call), iou=s["iou"], ios=s["ios"])
+            else:
+                ms += self.__engine.detect_tiled(pick(frames, call), [rects[i] for i in call], pick(detections, call), pick(cameras, call),
+                                                 pick(passes, call), pick(formats, call), iou=s["iou"], ios=s["ios"])
         return ms
 
     def _gate_layout(self, cam: int, frame: np.ndarray, fmt: int, rects, gate) -> None:

@@ -65,6 +65,11 @@ def device_name(device: int) -> str:
     return buf.value.decode()
 
 
+def _i32(n: int, values):
+    """An optional per-frame argument (formats, camera ids) as an int32 array of n, None as NULL."""
+    return (C.c_int32 * n)(*[int(v) for v in values]) if values is not None else None
+
+
 class Tile(C.Structure):
     """`wz_tile_t`: a rectangle of a frame, in pixels."""
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
@@ -236,8 +241,8 @@ class HipEngine:
         views, or any other format word `frame_geometry` describes; out_rows[i]: ctypes Detection[100] (or a ROW_DTYPE array of 100) written in place.  Returns the batch wall
         time in ms."""
         n, (ptrs, ws, hs, outs, keep) = len(frames), self._host_frames(frames, formats, out_rows)
-        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
-        camv = (C.c_int32 * n)(*[int(c) for c in cams]) if cams is not None else None
+        fmtv = _i32(n, formats)
+        camv = _i32(n, cams)
         passv = (C.c_void_p * n)(*[p.ctypes.data for p in out_pass]) if out_pass is not None else None
         ms = (C.c_float * n)()
         self._ck(self._lib.wz_detect_batch_fmt(self._h, n, ptrs, ws, hs, fmtv, camv, outs, passv, ms))
@@ -294,8 +299,8 @@ class HipEngine:
         threshold) or by more than `ios` of the smaller box (None: 1.0 = off).  Returns the wall time in ms."""
         n, (ptrs, ws, hs, outs, keep) = len(frames), self._host_frames(frames, formats, out_rows)
         counts, tptrs, tkeep, iou, ios = self._tile_args(tiles, n, iou, ios)
-        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
-        camv = (C.c_int32 * n)(*[int(c) for c in cams]) if cams is not None else None
+        fmtv = _i32(n, formats)
+        camv = _i32(n, cams)
         passv = (C.c_void_p * n)(*[p.ctypes.data for p in passes]) if passes is not None else None
         ms = (C.c_float * n)()
         self._ck(self._lib.wz_detect_tiled(self._h, n, ptrs, ws, hs, fmtv, camv, counts, tptrs, iou, ios, outs, passv, ms))
@@ -308,10 +313,27 @@ class HipEngine:
         merged list of rows per FRAME."""
         n = len(d_frames)
         counts, tptrs, tkeep, iou, ios = self._tile_args(tiles, n, iou, ios)
-        camv = (C.c_int32 * n)(*cams) if cams is not None else None
-        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
+        camv = _i32(n, cams)
+        fmtv = _i32(n, formats)
         self._ck(self._lib.wz_submit_tiled_device(self._h, slot, n, (C.c_void_p * n)(*d_frames), (C.c_int32 * n)(*widths),
                                                   (C.c_int32 * n)(*heights), fmtv, camv, counts, tptrs, iou, ios))
+
+    # -- what the gated and the motion calls share: one frame per camera, the tiles come from the cameras' settings --------
+    def _detect_per_camera(self, fn, last, frames, cams, out_rows, passes, formats, iou, ios) -> float:
+        """The synchronous call `fn` (wz_detect_gated | wz_detect_motion) of host frames; `last` remembers lane 0's cameras for the stats."""
+        n, (ptrs, ws, hs, outs, keep) = len(frames), self._host_frames(frames, formats, out_rows)
+        passv = (C.c_void_p * n)(*[p.ctypes.data for p in passes]) if passes is not None else None
+        ms = (C.c_float * n)()
+        self._ck(fn(self._h, n, ptrs, ws, hs, _i32(n, formats), _i32(n, cams), *self._thresholds(iou, ios), outs, passv, ms))
+        last[0] = [int(c) for c in cams]
+        return float(ms[0])
+
+    def _submit_per_camera(self, fn, last, slot, d_frames, widths, heights, cams, formats, iou, ios) -> None:
+        """... and its twin `fn` (wz_submit_gated_device | wz_submit_motion_device) of frames resident in HBM on lane `slot`."""
+        n = len(d_frames)
+        self._ck(fn(self._h, slot, n, (C.c_void_p * n)(*d_frames), (C.c_int32 * n)(*widths), (C.c_int32 * n)(*heights), _i32(n, formats),
+                    _i32(n, cams), *self._thresholds(iou, ios)))
+        last[slot] = [int(c) for c in cams]
 
     # -- gated tiled detection (include/watsor_hip.h: wz_set_camera_tiles / wz_detect_gated) ----------------
     def set_camera_tiles(self, cam: int, width: int, height: int, tiles, threshold: int, min_cells: int = 1, max_age: int = 0,
@@ -339,24 +361,13 @@ class HipEngine:
         """`detect_tiled` with the tiles `set_camera_tiles` gave the frames' cameras, run only where the picture changed: a tile that
         did not drift from the picture it last ran on contributes the rows it produced then.  One frame per camera and call; the
         cameras' configured tiles together at most max_batch.  Returns the wall time in ms; `gate_stats()` tells which tiles ran."""
-        n, (ptrs, ws, hs, outs, keep) = len(frames), self._host_frames(frames, formats, out_rows)
-        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
-        camv = (C.c_int32 * n)(*[int(c) for c in cams])
-        passv = (C.c_void_p * n)(*[p.ctypes.data for p in passes]) if passes is not None else None
-        ms = (C.c_float * n)()
-        self._ck(self._lib.wz_detect_gated(self._h, n, ptrs, ws, hs, fmtv, camv, *self._thresholds(iou, ios), outs, passv, ms))
-        self._gate_last[0] = [int(c) for c in cams]
-        return float(ms[0])
+        return self._detect_per_camera(self._lib.wz_detect_gated, self._gate_last, frames, cams, out_rows, passes, formats, iou, ios)
 
     def submit_gated_device(self, slot: int, d_frames: Sequence[int], widths: Sequence[int], heights: Sequence[int], cams: Sequence[int],
                             formats: Optional[Sequence[int]] = None, iou: Optional[float] = None, ios: Optional[float] = None) -> None:
         """`detect_gated` of frames resident in HBM on lane `slot`.  Returns once the engine has decided which tiles run (it waits for
         the activity launch); the batch behind is asynchronous and collected like a tiled slot's."""
-        n = len(d_frames)
-        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
-        self._ck(self._lib.wz_submit_gated_device(self._h, slot, n, (C.c_void_p * n)(*d_frames), (C.c_int32 * n)(*widths), (C.c_int32 * n)(*heights),
-                                                  fmtv, (C.c_int32 * n)(*[int(c) for c in cams]), *self._thresholds(iou, ios)))
-        self._gate_last[slot] = [int(c) for c in cams]
+        self._submit_per_camera(self._lib.wz_submit_gated_device, self._gate_last, slot, d_frames, widths, heights, cams, formats, iou, ios)
 
     def gate_stats(self, slot: int = 0):
         """What the last gated call accepted on lane `slot` decided: ([per frame: bit t set = tile t ran], [per frame: the tiles'
@@ -404,24 +415,13 @@ class HipEngine:
         regions that changed since the camera's previous motion call.  One frame per camera and call; the cameras' configured whole_frame +
         max_regions together at most max_batch.  A frame without any tile gets padding rows and pass bytes 0.  Returns the wall time in
         ms; `motion_stats()` tells which rectangles ran."""
-        n, (ptrs, ws, hs, outs, keep) = len(frames), self._host_frames(frames, formats, out_rows)
-        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
-        camv = (C.c_int32 * n)(*[int(c) for c in cams])
-        passv = (C.c_void_p * n)(*[p.ctypes.data for p in passes]) if passes is not None else None
-        ms = (C.c_float * n)()
-        self._ck(self._lib.wz_detect_motion(self._h, n, ptrs, ws, hs, fmtv, camv, *self._thresholds(iou, ios), outs, passv, ms))
-        self._motion_last[0] = [int(c) for c in cams]
-        return float(ms[0])
+        return self._detect_per_camera(self._lib.wz_detect_motion, self._motion_last, frames, cams, out_rows, passes, formats, iou, ios)
 
     def submit_motion_device(self, slot: int, d_frames: Sequence[int], widths: Sequence[int], heights: Sequence[int], cams: Sequence[int],
                              formats: Optional[Sequence[int]] = None, iou: Optional[float] = None, ios: Optional[float] = None) -> None:
         """`detect_motion` of frames resident in HBM on lane `slot`.  Returns once the engine has read the rectangles (it waits for the
         activity and the region launch); the batch behind is asynchronous and collected like a tiled slot's."""
-        n = len(d_frames)
-        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
-        self._ck(self._lib.wz_submit_motion_device(self._h, slot, n, (C.c_void_p * n)(*d_frames), (C.c_int32 * n)(*widths), (C.c_int32 * n)(*heights),
-                                                   fmtv, (C.c_int32 * n)(*[int(c) for c in cams]), *self._thresholds(iou, ios)))
-        self._motion_last[slot] = [int(c) for c in cams]
+        self._submit_per_camera(self._lib.wz_submit_motion_device, self._motion_last, slot, d_frames, widths, heights, cams, formats, iou, ios)
 
     def motion_stats(self, slot: int = 0):
         """What the last motion call accepted on lane `slot` found: ([per frame: its tile list [(x0, y0, w, h), ...] -- the whole frame first
@@ -443,8 +443,8 @@ class HipEngine:
         ptrs = (C.c_void_p * n)(*d_frames)
         ws = (C.c_int32 * n)(*widths)
         hs = (C.c_int32 * n)(*heights)
-        camv = (C.c_int32 * n)(*cams) if cams is not None else None
-        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
+        camv = _i32(n, cams)
+        fmtv = _i32(n, formats)
         self._ck(self._lib.wz_submit_device_fmt(self._h, slot, n, ptrs, ws, hs, fmtv, camv))
 
     def submit_host(self, slot: int, frames: Sequence[np.ndarray], cams: Optional[Sequence[int]] = None,
@@ -462,8 +462,8 @@ class HipEngine:
             if not f.flags["C_CONTIGUOUS"]:
                 raise ValueError("frame %d must be C-contiguous (it is read in place, asynchronously)" % i)
         ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
-        camv = (C.c_int32 * n)(*cams) if cams is not None else None
-        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
+        camv = _i32(n, cams)
+        fmtv = _i32(n, formats)
         self._ck(self._lib.wz_submit_host_fmt(self._h, slot, n, ptrs, ws, hs, fmtv, camv))
 
     def host_register(self, arr: np.ndarray) -> None:
@@ -827,7 +827,7 @@ class HipEngine:
         brackets, the mean of `reps` each."""
         self._dev_only("profile_gated()")
         n = len(d_frames)
-        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
+        fmtv = _i32(n, formats)
         act, commit, empty = C.c_float(), C.c_float(), C.c_float()
         self._ck(self._lib.wz_profile_gated(self._h, n, (C.c_void_p * n)(*d_frames), (C.c_int32 * n)(*widths), (C.c_int32 * n)(*heights), fmtv,
                                             (C.c_int32 * n)(*[int(c) for c in cams]), *self._thresholds(iou, ios), int(reps), C.byref(act),
@@ -855,7 +855,7 @@ class HipEngine:
         self._dev_only("profile_tiled()")
         n = len(d_frames)
         counts, tptrs, tkeep, iou, ios = self._tile_args(tiles, n, iou, ios)
-        fmtv = (C.c_int32 * n)(*[int(x) for x in formats]) if formats is not None else None
+        fmtv = _i32(n, formats)
         crop, merge, empty = C.c_float(), C.c_float(), C.c_float()
         self._ck(self._lib.wz_profile_tiled(self._h, n, (C.c_void_p * n)(*d_frames), (C.c_int32 * n)(*widths), (C.c_int32 * n)(*heights),
                                               fmtv, counts, tptrs, iou, ios, int(reps), C.byref(crop), C.byref(merge), C.byref(empty)))
