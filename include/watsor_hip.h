@@ -451,6 +451,12 @@ int wz_stage_forward(wz_engine_t* e, int n, const uint16_t* in_half, float* box_
  * comes back as stored, 2c halves per pixel).
  * Only meaningful when the engine was created with WZ_NO_BUFFER_REUSE=1 in the environment. */
 int wz_stage_read_tensor(wz_engine_t* e, int idx, int frame, uint16_t* out_half);
+/* one fused block (op `op` of wz_op_info) of the last forward again, for its n frames, with its source tensor read at the device
+ * address `d_in` (wz_dev_alloc / wz_dev_upload: n frames as wz_stage_read_tensor returns them, back to back) -- the caller decides
+ * what lies in front of and behind the tensor.  The block's outputs land where the network puts them.  launch_frames > 0: a
+ * split-operand block goes out as launches of at most that many frames (what a batch of 2^31 bytes of block input and more gets);
+ * 0: as the network launches it. */
+int wz_stage_block_at(wz_engine_t* e, int op, int n, const void* d_in, int launch_frames);
 /* decode + sigmoid + NMS + top-k on caller-provided head outputs:
  * boxes [n][100][4] (ymin,xmin,ymax,xmax), scores [n][100], classes [n][100] (1-based), num [n] */
 int wz_stage_postprocess(wz_engine_t* e, int n, const float* box_enc, const float* logits, float* boxes,

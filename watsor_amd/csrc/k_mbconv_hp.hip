@@ -114,6 +114,18 @@ __global__ __launch_bounds__(NW * 64, OCC) void wz_k_mbconv_hp(const WzMbArgs a)
     const int P = hh_ * hw_;
     const int iy_base = oy0 * s - a.pad_t, ix_base = ox0 * s - a.pad_l;
     const half8_t zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    // The block's input is read through ONE buffer descriptor per launch (as the heads' activations are, k_conv_wide.hip): it covers
+    // exactly the nb frames of the input tensor and is built from kernel arguments alone, so it lives in scalar registers.  A halo
+    // pixel is a 32-bit byte offset, worked out once; whatever a lane must NOT read -- a pixel outside the frame or beyond the tile's
+    // halo, a dead wave's, a channel chunk beyond cin0, a stem tap outside the network input -- gets bit 31 set in its offset, which lies
+    // beyond every descriptor the launcher builds (nb x frame bytes < 2^31): the load returns zeros.  Validity always comes from that
+    // bit, never from the descriptor's range: a tap above row 0 of frame 1 lies inside the descriptor, in frame 0.
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)a.in, 0, STEM ? a.nb * a.sin_h * a.sin_w * 16 : a.nb * a.hin * a.win * a.cin0 * 4, 0x00020000);
+    constexpr unsigned OOB = 0x80000000u;
+    auto gather = [&](unsigned voff, int soff) -> half8_t {
+        return __builtin_bit_cast(half8_t, __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)voff, soff, 0));
+    };
 
     int hp0[MQW], opix[MQW];
 #pragma unroll
@@ -135,39 +147,82 @@ __global__ __launch_bounds__(NW * 64, OCC) void wz_k_mbconv_hp(const WzMbArgs a)
     half8_t xh[MPW][KCI], xl[MPW][KCI];
     bool inimg[MPW];
     const float rcp_hw = 1.0f / (float)hw_;   // p < 96, hw_ <= 10: floor((p + 0.5) / hw_) is exact in fp32 (no integer division)
+    // what of an offset belongs to the lane, not to the pixel: worked out once
+    // K order of the stem GEMM in this program (engine.py: stem_k_rows): k = tap*4 + c for taps 0 .. 7, i.e. lane group
+    // g holds the 4-channel pixels of taps 2g and 2g+1 exactly as they lie in the input pair tensor, and the ninth
+    // tap's three channels sit in the always-zero fourth-channel slots of taps 0, 1, 2 (k = 3, 7, 11: groups 0 and 1).
+    // The lane's three taps: their bit in the pixel's tap mask (groups 2 and 3 have no ninth tap: they take bit 9, which is always
+    // set) and their byte offset from tap (0, 0).
+    unsigned tap_bit[3], tap_off[3];
 #pragma unroll
-    for (int i = 0; i < MPW; ++i) {
-        const int p = i * 16 + r16;
+    for (int q = 0; q < 3; ++q) {
+        const int tq = q < 2 ? 2 * g + q : (g <= 1 ? 8 : 9);
+        const int ky = tq / 3, kx = tq - ky * 3;
+        tap_bit[q] = (unsigned)tq;
+        tap_off[q] = (unsigned)((ky * a.sin_w + kx) * 16);
+    }
+    // ... and, per K chunk of a block input, bit 31 for the lanes whose 8 channels lie beyond cin0
+    unsigned chunk_out[KCI];
+#pragma unroll
+    for (int c = 0; c < KCI; ++c) chunk_out[c] = c * 32 + g * 8 < a.cin0 ? 0u : OOB;
+    const int pix_bytes = a.cin0 * 4;         // a pixel of a pair tensor: cin0 hi halves, then cin0 lo halves
+    // The tile's halo pixels, each worked out ONCE per wave: by the lane of its number (pass k: pixel k * 64 + lane).  The 16 lanes
+    // r16 of m-tile i fetch pixel i * 16 + r16's words from there with ds_bpermute (a tile's 16 pixels lie in one pass).
+    //   hoff  a block input: the pixel's byte offset, or bit 31 for a pixel that is not to be read; the stem: the offset of the pixel's
+    //         tap (0, 0), which may lie in front of the tensor -- only its sums with a valid tap's offset are ever used
+    //   hout  the stem: bit t set = tap t reads zeros; bit 9 always set; bit 10 set = the pixel itself is not in the frame.  A tap's
+    //         validity is separable: three row bits, three column bits, one compare each (unsigned: below zero is above the limit).
+    constexpr int NPASS = (MPW * 16 + 63) / 64;
+    unsigned hoff[NPASS], hout[NPASS];
+#pragma unroll
+    for (int k = 0; k < NPASS; ++k) {
+        const int p = k * 64 + lane;
         const int hy = (int)(((float)p + 0.5f) * rcp_hw), hx = p - hy * hw_;
         const int iy = iy_base + hy, ix = ix_base + hx;
-        const bool ok = live && p < P && iy >= 0 && iy < a.hin && ix >= 0 && ix < a.win;
-        inimg[i] = ok;
+        const bool ok = live & (p < P) & ((unsigned)iy < (unsigned)a.hin) & ((unsigned)ix < (unsigned)a.win);   // (no short circuit: three compares, no branch)
+        if constexpr (STEM) {   // stride 2 on the input image
+            const int sy0 = iy * 2 - a.spad_t, sx0 = ix * 2 - a.spad_l;
+            unsigned cols = 0, taps_in = 0;
+#pragma unroll
+            for (int t = 0; t < 3; ++t) cols |= ((unsigned)(sx0 + t) < (unsigned)a.sin_w ? 1u : 0u) << t;
+#pragma unroll
+            for (int t = 0; t < 3; ++t) taps_in |= ((unsigned)(sy0 + t) < (unsigned)a.sin_h ? cols : 0u) << (3 * t);
+            hoff[k] = (unsigned)(((b * a.sin_h + sy0) * a.sin_w + sx0) * 16);
+            hout[k] = ~(ok ? taps_in | 0x400u : 0u);
+        } else {
+            hoff[k] = ok ? (unsigned)(((b * a.hin + iy) * a.win + ix) * pix_bytes) : OOB;
+            hout[k] = 0u;
+        }
+    }
+    const int src16 = r16 * 4;   // ds_bpermute addresses lanes in bytes
+    auto halo_word = [&](int i, const unsigned (&tab)[NPASS]) -> unsigned {   // of pixel i * 16 + r16
+        const unsigned w = (NPASS > 1 && i >= 4) ? tab[NPASS - 1] : tab[0];
+        return (unsigned)__builtin_amdgcn_ds_bpermute(((i & 3) * 16) * 4 + src16, (int)w);
+    };
+#pragma unroll
+    for (int i = 0; i < MPW; ++i) {
+        const unsigned pix = halo_word(i, hoff);
         if constexpr (STEM) {
-            // K order of the stem GEMM in this program (engine.py: stem_k_rows): k = tap*4 + c for taps 0 .. 7, i.e. lane group
-            // g holds the 4-channel pixels of taps 2g and 2g+1 exactly as they lie in the input pair tensor, and the ninth
-            // tap's three channels sit in the always-zero fourth-channel slots of taps 0, 1, 2 (k = 3, 7, 11: groups 0 and 1)
-            auto tap = [&](int tq, bool want) -> half8_t {
-                const int ky = tq / 3, kx = tq - ky * 3;
-                const int sy = iy * 2 - a.spad_t + ky, sx = ix * 2 - a.spad_l + kx;   // stem: stride 2 on the input image
-                const bool in = want && ok && sy >= 0 && sy < a.sin_h && sx >= 0 && sx < a.sin_w;
-                const int cy = min(max(sy, 0), a.sin_h - 1), cx = min(max(sx, 0), a.sin_w - 1);
-                const half8_t v = *reinterpret_cast<const half8_t*>(a.in + ((size_t)(b * a.sin_h + cy) * a.sin_w + cx) * 8);
-                return in ? v : zero8;
-            };
-            const half8_t va = tap(2 * g, true), vb = tap(2 * g + 1, true), v8 = tap(8, g <= 1);
+            const unsigned taps_out = halo_word(i, hout);
+            inimg[i] = !(taps_out & 0x400u);
+            half8_t v[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) v[q] = gather((pix + tap_off[q]) | ((taps_out >> tap_bit[q]) << 31), 0);
+            const half8_t va = v[0], vb = v[1], v8 = v[2];   // (v8: zeros in groups 2 and 3)
             const half_t z16 = (half_t)0.0f;
-            const half_t e0h = g == 0 ? v8[0] : g == 1 ? v8[2] : z16, e1h = g == 0 ? v8[1] : z16;
-            const half_t e0l = g == 0 ? v8[4] : g == 1 ? v8[6] : z16, e1l = g == 0 ? v8[5] : z16;
+            const half_t e0h = g == 0 ? v8[0] : v8[2], e1h = g == 0 ? v8[1] : z16;
+            const half_t e0l = g == 0 ? v8[4] : v8[6], e1l = g == 0 ? v8[5] : z16;
             xh[i][0] = (half8_t){va[0], va[1], va[2], e0h, vb[0], vb[1], vb[2], e1h};
             xl[i][0] = (half8_t){va[4], va[5], va[6], e0l, vb[4], vb[5], vb[6], e1l};
-        } else if constexpr (!CS) {
-            const half_t* src = a.in + ((size_t)(b * a.hin + (ok ? iy : 0)) * a.win + (ok ? ix : 0)) * (2 * a.cin0);
+        } else {
+            inimg[i] = (int)pix >= 0;
+            if constexpr (!CS) {
 #pragma unroll
-            for (int c = 0; c < KCI; ++c) {
-                const int k0 = c * 32 + g * 8;
-                const bool kok = ok && k0 < a.cin0;
-                xh[i][c] = kok ? *reinterpret_cast<const half8_t*>(src + k0) : zero8;
-                xl[i][c] = kok ? *reinterpret_cast<const half8_t*>(src + a.cin0 + k0) : zero8;
+                for (int c = 0; c < KCI; ++c) {
+                    const unsigned voff = (pix + g * 16) | chunk_out[c];
+                    xh[i][c] = gather(voff, c * 64);                     // (the chunk's and the lo half's displacement: scalar / immediate offset)
+                    xl[i][c] = gather(voff, a.cin0 * 2 + c * 64);
+                }
             }
         }
     }
@@ -183,17 +238,12 @@ __global__ __launch_bounds__(NW * 64, OCC) void wz_k_mbconv_hp(const WzMbArgs a)
         static_assert(!STEM, "the stem block runs one wave per tile");
 #pragma unroll
         for (int k = 0; k < PERW; ++k) {
-            const int f = wave + k * NW;     // wave-uniform
+            const int f = __builtin_amdgcn_readfirstlane(wave + k * NW);     // wave-uniform, and known to be: the fragment's displacement is a scalar offset
             part[k] = zero8;
             if (f < NFRAG) {
                 const int i = f / (KCI * 2), c = (f >> 1) % KCI, lo = f & 1;
-                const int p = i * 16 + r16;
-                const int hy = (int)(((float)p + 0.5f) * rcp_hw), hx = p - hy * hw_;
-                const int iy = iy_base + hy, ix = ix_base + hx;
-                const int k0 = c * 32 + g * 8;
-                const bool kok = live && p < P && iy >= 0 && iy < a.hin && ix >= 0 && ix < a.win && k0 < a.cin0;
-                const half_t* src = a.in + ((size_t)(b * a.hin + (kok ? iy : 0)) * a.win + (kok ? ix : 0)) * (2 * a.cin0);
-                if (kok) part[k] = *reinterpret_cast<const half8_t*>(src + (lo ? a.cin0 : 0) + k0);
+                const unsigned voff = (halo_word(i, hoff) + g * 16) | (c * 32 + g * 8 < a.cin0 ? 0u : OOB);
+                part[k] = gather(voff, (lo ? a.cin0 * 2 : 0) + c * 64);
             }
         }
     }
@@ -684,8 +734,24 @@ static int wz_hp_launch(WzMbArgs a, int n, hipStream_t s, bool prepare) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         return lds <= 160 * 1024 ? 0 : -1;
     }
-    const int tiles = a.tiles_x * a.tiles_y * n;
-    WZ_LAUNCH(k, dim3(CS ? tiles * a.nsplit : (tiles + 3) / 4), dim3(NW * 64), lds, s, a);
+    // The kernel addresses its input through one buffer descriptor with 32-bit offsets, bit 31 of which means "read zeros": a launch takes
+    // the frames whose input stays below 2^31 bytes -- every batch below ~990 frames whole (the largest input, block 2's, is 2.16 MB a
+    // frame); a larger one goes out as several launches of whole frames, each with a descriptor of its own frames (a tile's values do not
+    // depend on the launch it is in).  WzMbArgs::launch_frames caps the frames of a launch: how wz_stage_block_at has this tested.
+    const size_t in_frame = STEM ? (size_t)a.sin_h * a.sin_w * 16 : (size_t)a.hin * a.win * a.cin0 * 4;
+    int per = (int)(((size_t)0x7fffffff) / in_frame);
+    if (a.launch_frames > 0 && a.launch_frames < per) per = a.launch_frames;
+    if (per < 1) return -1;
+    const size_t out_frame = (size_t)a.hout * a.wout * (a.hp_out ? 2 * a.cout : a.cout);   // in halves
+    for (int f0 = 0; f0 < n; f0 += per) {
+        WzMbArgs c = a;
+        c.nb = n - f0 < per ? n - f0 : per;
+        c.in = a.in + (size_t)f0 * (in_frame / 2);
+        c.out = a.out + (size_t)f0 * out_frame;
+        if (a.res) c.res = a.res + (size_t)f0 * a.hout * a.wout * 2 * a.cout;
+        const int tiles = a.tiles_x * a.tiles_y * c.nb;
+        WZ_LAUNCH(k, dim3(CS ? tiles * a.nsplit : (tiles + 3) / 4), dim3(NW * 64), lds, s, c);
+    }
     return 1;
 }
 

@@ -158,6 +158,8 @@ struct WzMbArgs {
     unsigned long long* dbg2;   // two-launch form (k_mbconv_hp2.hip): the second launch's stamp block (WZ_LANE_STAMPS builds), else nullptr
     int32_t lone;               // the batch is being launched kernel by kernel because every other lane is idle (run_batch): launch shapes may use the whole chip
                                 // (only shapes whose results are bit-identical to the throughput shapes' may depend on it)
+    int32_t launch_frames;      // split-operand kernel: most frames ONE launch takes (0: as many as its input descriptor addresses, i.e. every batch
+                                // below 2^31 bytes of block input whole); set by wz_stage_block_at only
 };
 
 // One separable layer of MobileNet-v1 (k_dwsep.hip): depthwise 3x3 + ReLU6 -> 1x1 pointwise + ReLU6.  cin = depthwise channels = pointwise K.

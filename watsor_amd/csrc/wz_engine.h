@@ -338,6 +338,9 @@ void network_prepare(wz_engine* e);    // wz_create: kernel attributes on the en
 WzConvArgs conv_args(wz_engine* e, const Lane& L, const WzOpDesc& op, int n);
 void head_outputs(wz_engine* e, const Lane& L, const WzOpDesc& op, WzConvArgs& a);
 void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool with_post = true);
+#ifdef WZ_DEV_BUILD
+int enqueue_block_at(wz_engine* e, Lane& L, int n, uint32_t op_index, const void* d_in, int launch_frames);   // one fused block, its source tensor at d_in; -1: not a block / no kernel
+#endif
 
 // ---- wz_engine.hip, for wz_tiles.hip --------------------------------------------------------------------------------------------
 const char* fmt_refusal(int w, int h, int fmt);

@@ -1390,6 +1390,17 @@ extern "C" int wz_stage_forward(wz_engine_t* e, int n, const uint16_t* in_half, 
     return WZ_OK;
 }
 
+extern "C" int wz_stage_block_at(wz_engine_t* e, int op, int n, const void* d_in, int launch_frames) {
+    if (!e || !d_in || op < 0 || op >= (int)e->hdr.n_ops || launch_frames < 0) return wz_fail(WZ_EINVAL, "wz_stage_block_at: bad argument");
+    if (n < 1 || n > e->max_batch) return wz_fail(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (enqueue_block_at(e, e->lanes[0], n, (uint32_t)op, d_in, launch_frames) != 0) return wz_fail(WZ_EINVAL, "wz_stage_block_at: op %d is not a fused block with a kernel", op);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipGetLastError());
+    return WZ_OK;
+}
+
 extern "C" int wz_stage_read_tensor(wz_engine_t* e, int idx, int frame, uint16_t* out_half) {
     if (!e || !out_half || idx < 0 || idx >= (int)e->hdr.n_tensors || frame < 0 || frame >= e->max_batch)
         return wz_fail(WZ_EINVAL, "wz_stage_read_tensor: bad argument");

@@ -290,6 +290,7 @@ struct Net {   // the batch being enqueued
     StageTimer* t;
     hipStream_t s;
     HeadPark park;   // (started by enqueue_network: nothing of it is zeroed per batch)
+    int launch_frames = 0;   // WzMbArgs::launch_frames of the fused blocks (enqueue_block_at)
     Net(wz_engine* e_, Lane& L_, int n_, StageTimer* t_) : e(e_), L(L_), n(n_), t(t_), s(L_.stream) {}
     void mark() { if (t) t->mark(); }
 };
@@ -356,7 +357,8 @@ static void enqueue_mbconv(Net& x, uint32_t i, const WzOpDesc& op) {
     WzMbArgs a = mb_args(e, L, op);
     a.M = n * op.hout * op.wout;
     a.lone = L.lone ? 1 : 0;
-    a.ws = (e->use_splitk || a.hp) ? L.d_ws : nullptr;   // (split-K partials of the plain blocks; the two-launch split blocks' project fragments)
+    a.launch_frames = x.launch_frames;
+    a.ws =(e->use_splitk || a.hp) ? L.d_ws : nullptr;   // (split-K partials of the plain blocks; the two-launch split blocks' project fragments)
     a.ws_bytes = x.park.ws_top;
     a.dbg = e->d_mbdbg ? e->d_mbdbg + (size_t)i * 16 : nullptr;
     WZ_STAMP_ARG(a);
@@ -505,6 +507,25 @@ static int enqueue_conv_f16(Net& x, uint32_t i, const WzOpDesc& op) {
     }
     return 1;
 }
+
+#ifdef WZ_DEV_BUILD
+// One fused block of the network on its own, its source tensor read at `d_in` instead of where the engine keeps it (wz_stage_block_at:
+// the caller decides what lies around the tensor; a residual that IS the source tensor is read there too).  Everything else -- weights,
+// outputs, launch shapes -- as in the network.  launch_frames > 0: a split-operand block takes at most that many frames per launch.
+int enqueue_block_at(wz_engine* e, Lane& L, int n, uint32_t i, const void* d_in, int launch_frames) {
+    const WzOpDesc& op = e->ops[i];
+    if (op.kind != WZ_OP_MBCONV) return -1;
+    Net x(e, L, n, nullptr);
+    x.park.start(e, L, n);
+    x.launch_frames = launch_frames;
+    half_t* const kept = L.tptr[op.src];
+    L.tptr[op.src] = static_cast<half_t*>(const_cast<void*>(d_in));
+    L.launch_failed = 0;
+    enqueue_mbconv(x, i, op);
+    L.tptr[op.src] = kept;
+    return L.launch_failed ? -1 : 0;
+}
+#endif
 
 // with_post: the post-processing chain follows in the same stream (it consumes -- and resets -- the candidate list)
 void enqueue_network(wz_engine* e, Lane& L, int n, StageTimer* t, bool with_post) {

@@ -704,6 +704,13 @@ class HipEngine:
             return out[..., :c].astype(np.float32) + out[..., c:].astype(np.float32)
         return out
 
+    def stage_block_at(self, op: int, n: int, d_in: int, launch_frames: int = 0) -> None:
+        """Fused block `op` (index into ops()) of the last forward again for its n frames, its source tensor read at the device
+        address `d_in` (`upload`); the outputs land where the network puts them (stage_read_tensor).  launch_frames > 0: a
+        split-operand block in launches of at most that many frames."""
+        self._dev_only("stage_block_at()")
+        self._ck(self._lib.wz_stage_block_at(self._h, int(op), int(n), C.c_void_p(d_in), int(launch_frames)))
+
     def stage_postprocess(self, box_enc: np.ndarray, logits: np.ndarray):
         self._dev_only("stage_postprocess()")
         be = np.ascontiguousarray(box_enc, np.float32)
