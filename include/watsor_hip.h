@@ -252,8 +252,9 @@ int wz_gate_stats(wz_engine_t* e, int slot, int n, uint64_t* ran_mask /* [n], bi
  * settings, a frame whose size or base format differs from the settings', the same camera twice, thresholds a tiled call refuses
  * (WZ_EINVAL); the CONFIGURED whole_frame + max_regions of the call's cameras summing to more than max_batch (WZ_ELIMIT) -- never the
  * regions found: a refusal does not depend on pixels.  wz_submit_motion_device returns once the rectangles are read: both
- * state-touching launches have finished by then, so no other lane ever holds a camera's motion state in flight; the slot is collected
- * like any tiled slot.  wz_motion_stats: what the last motion call accepted on `slot` found for its n frames. */
+ * launches that touch the grids have finished by then, so no lane ever holds the motion state of a camera WITHOUT A HOLD (below) in
+ * flight; the slot is collected like any tiled slot.  wz_motion_stats: what the last motion call accepted on `slot` found for its n
+ * frames. */
 #define WZ_MOTION_MAX_REGIONS 16
 #define WZ_MOTION_MAX_CELLS   32768
 typedef struct wz_motion { int32_t pixel_thr, min_cells, dilate, max_regions, min_side, pad, whole_frame, _reserved; } wz_motion_t;
@@ -266,6 +267,33 @@ int wz_submit_motion_device(wz_engine_t* e, int slot, int n, const uint8_t* cons
                             const int* cam, double iou_thr, double ios_thr);
 int wz_motion_stats(wz_engine_t* e, int slot, int n, int32_t* n_tiles /* [n] */, wz_tile_t* tiles /* [n][1 + WZ_MOTION_MAX_REGIONS] */,
                     int32_t* cells /* [n][WZ_MOTION_MAX_REGIONS]: n of every region */, int32_t* components /* [n]: those with n >= min_cells */);
+/* ---- motion hold.  Frame differencing forgets: a person who stops moving leaves the regions one call later, and
+ * what never moved never gets one.  A camera with motion settings may ALSO have a hold: a grid G of ages, one byte per cell of the same
+ * 16 x 16-pixel cells, in device memory; all zero at first, after wz_reset_camera_motion and after new hold settings.  On every ACCEPTED
+ * motion call of the camera, with C the changed cells as above (all 0 without a reference):
+ *   active cells     A = C or (G > 0).  Regions, every region's n and `components` are exactly those above with A in the place of C (D is
+ *                    A dilated, n counts the A cells of a component): a call without a reference can have regions, where G > 0.
+ *   decay            G1 = max(hold if C else 0, G - 1 if G > 0 else 0)
+ *   stamp            behind the merge, the camera filter and the padding rows: for every one of the frame's 100 merged rows whose final
+ *                    pass byte is 1, with x0 = max(x_min, 0), x1 = min(x_max, width - 1) and the same in y, unless x0 > x1 or y0 > y1,
+ *                    every cell with x0 >> 4 <= cx <= x1 >> 4 and y0 >> 4 <= cy <= y1 >> 4 gets G2 = max(G1, object_hold).  With
+ *                    object_hold = 0 nothing is stamped.  What passes is what the camera's filter lets pass: confidence, area, zones.
+ *   next call        G2 is its G.  A refused call changes nothing.
+ * So a changed cell stays active for `hold` further calls, a cell under a passing detection for `object_hold` further calls, refreshed
+ * while the detection recurs.  The rows of a call are, as before, one wz_detect_tiled call on the reported tile lists.
+ * wz_set_camera_motion_hold waits for every lane and allocates the camera's two age grids (swapped like its two luma grids); on failure
+ * the camera keeps what it had; hold = object_hold = 0 removes the hold and frees them.  Refused with WZ_EINVAL: a null argument, a
+ * camera without motion settings, a value outside 0 .. 255.  wz_set_camera_motion replaces the camera and thereby DROPS its hold: set
+ * the hold after it.  An engine that never sets a hold allocates nothing for it, and the calls of a camera without one launch and wait
+ * for nothing more than before.
+ * In flight: the stamp launch of a camera with a hold is still running when wz_submit_motion_device returns.  The next motion call of that
+ * camera on ANOTHER lane waits for the lane that stamped it before it launches anything (as a gated call does for its camera's commit
+ * launch); on the same lane the stream orders them.
+ * wz_motion_hold_stats: per frame of the last motion call accepted on `slot`, its active cells and those of them that did not change
+ * (active - held changed); 0 and 0 for a frame whose camera has no hold. */
+typedef struct wz_motion_hold { int32_t hold, object_hold, _reserved[2]; } wz_motion_hold_t;
+int wz_set_camera_motion_hold(wz_engine_t* e, int cam, const wz_motion_hold_t* hold);   /* both 0: remove the hold, free its grids */
+int wz_motion_hold_stats(wz_engine_t* e, int slot, int n, int32_t* active /* [n] */, int32_t* held /* [n] */);
 /* ---- the worker's frame table.  The reference worker resolves every payload to `frame_buffers[sender].frames[index]`, asks
  * the frame for a numpy view of its pixels and hands the frame header's `Detection[100]` array to the plugin
  * (watsor/detection/detector.py:102-109); pixels, size and rows of a Frame never move after the FrameBuffers are created
@@ -498,6 +526,22 @@ int wz_stage_motion_regions(wz_engine_t* e, const uint16_t* now, const uint16_t*
  * of format fmt (device memory of undefined content) alone; empty_ms: the same bracket around nothing */
 int wz_profile_motion(wz_engine_t* e, const uint16_t* now, const uint16_t* ref, int w, int h, int fmt, const wz_motion_t* motion, int reps,
                       float* regions_ms, float* activity_ms, float* empty_ms, int32_t* rounds /* rounds of the labelling; 0: no changed cell */);
+/* the region kernel alone as a camera with a hold runs it: wz_stage_motion_regions plus the ages age_in ([cell rows][cell columns] uint8;
+ * NULL: all zero) and `hold` (0 .. 255); ref NULL: no cell has changed.  Also returns the active cells, those of them that did not change,
+ * and the decayed ages age_out[cell rows][cell columns] */
+int wz_stage_motion_hold(wz_engine_t* e, const uint16_t* now, const uint16_t* ref, const uint8_t* age_in, int w, int h, int fmt,
+                         const wz_motion_t* motion, int hold, int32_t* n_regions, wz_tile_t* regions /* [WZ_MOTION_MAX_REGIONS] */,
+                         int32_t* cells /* [WZ_MOTION_MAX_REGIONS] */, int32_t* components, int32_t* active, int32_t* held, uint8_t* age_out);
+/* the stamp kernel alone on the ages of a w x h frame, 100 rows and their 100 pass bytes: age_out = the ages behind it */
+int wz_stage_motion_stamp(wz_engine_t* e, const uint8_t* age_in, const wz_detection_t* rows /* [100] */, const uint8_t* pass /* [100] */, int w, int h,
+                          int object_hold, uint8_t* age_out);
+/* waits for every lane, then copies the current age grid of camera `cam` ([cell rows][cell columns] uint8); WZ_EINVAL if it has no hold */
+int wz_debug_motion_age(wz_engine_t* e, int cam, uint8_t* out);
+/* HIP-event time (ms, mean of reps) of the region launch alone with these ages (age_in NULL: all zero) and of the stamp launch alone on the
+ * ages it leaves, with these 100 rows and pass bytes; empty_ms: the same bracket around nothing */
+int wz_profile_motion_hold(wz_engine_t* e, const uint16_t* now, const uint16_t* ref, const uint8_t* age_in, int w, int h, int fmt,
+                           const wz_motion_t* motion, int hold, const wz_detection_t* rows, const uint8_t* pass, int object_hold, int reps,
+                           float* regions_ms, float* stamp_ms, float* empty_ms);
 /* in_place[i] = 1 where frame i of the last wz_submit_bound on `slot` -- untiled, tiled or gated -- was read in place through its device view,
  * 0 where it was staged by DMA (n values: the frames of that batch); WZ_EINVAL when the lane has seen no such batch */
 int wz_debug_bound_source(wz_engine_t* e, int slot, int32_t* in_place /* [n] */);

@@ -8,9 +8,13 @@
              region: a batch of two), against `submit_tiled_device` + wait of the same frames on the same two rectangles -- code this
              feature does not touch; the difference is what finding the rectangle costs.  Alternating `--rounds` times in one process.
 
+  --hold     instead of the two above: what a camera with a hold pays on top -- the region launch with ages, with
+             ages that are all zero and without, on still / blob / noise, and the stamp launch alone with 0 / 1 / 100 passing rows
+
 Prints one JSON line; --out appends a readable summary.
 
-    python tools/motion_bench.py [--steps 200] [--rounds 3] [--out profiles/motion_regions.txt]"""
+    python tools/motion_bench.py [--steps 200] [--rounds 3] [--out profiles/motion_regions.txt]
+    python tools/motion_bench.py --hold [--out profiles/motion_hold.txt]"""
 import argparse
 import json
 import os
@@ -58,12 +62,88 @@ def host_labelling_us(C, dilate, reps=200):
     return round(float(np.median(lat)), 1)
 
 
+def hold_leg(args):
+    """--hold: what a camera with a hold pays on top, on the same 120 x 68 grid.  The region launch with ages -- 2 %
+    of the cells hold a seeded age of 1 .. 255 -- against the same launch without, on still / blob / noise; the stamp launch alone with 0, 1
+    and 100 passing rows (100 seeded boxes of up to 600 x 400 pixels).  HIP-event brackets, mean of 100, the empty bracket beside it, three
+    measurements each."""
+    import motion_hold_oracle as ho
+    import motion_oracle as mo
+    from watsor_amd import engine
+    from watsor_amd.runtime import ROW_DTYPE, HipEngine
+    from watsor_amd.synth import synthetic_weights
+    gh, gw = mo.grid_shape(WIDTH, HEIGHT)
+    rng = np.random.default_rng(19)
+    blob = np.zeros((gh, gw), bool)
+    blob[20:26, 50:58] = True
+    grids = {"still": np.zeros((gh, gw), bool), "blob": blob, "noise": rng.random((gh, gw)) < 0.02}
+    age = np.where(rng.random((gh, gw)) < 0.02, rng.integers(1, 256, (gh, gw)), 0).astype(np.uint8)
+    rows = np.zeros(100, ROW_DTYPE)
+    rows["label"] = 1
+    rows["x_min"], rows["y_min"] = rng.integers(0, WIDTH - 600, 100), rng.integers(0, HEIGHT - 400, 100)
+    rows["x_max"], rows["y_max"] = rows["x_min"] + rng.integers(16, 600, 100), rows["y_min"] + rng.integers(16, 400, 100)
+    med = lambda v: float(np.median(v))      # noqa: E731
+    us = lambda v: round(v * 1e3, 2)         # noqa: E731
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "mi355x.bin")
+        engine.save_engine(engine.build_engine(synthetic_weights(1234), robust=True), path)
+        dev = HipEngine(path, 0, BATCH, WIDTH, HEIGHT, dev=True)
+        launches, stamps = {}, {}
+        try:
+            for name, C in grids.items():
+                now, ref = mo.grids_for(C, WIDTH, HEIGHT, THR)
+                found = dev.stage_motion_hold(now, ref, age, WIDTH, HEIGHT, THR, 5, **SETTINGS)
+                want = ho.step(now, ref, age, WIDTH, HEIGHT, 0, THR, 5, **SETTINGS)
+                assert found[:5] == want[:5] and (found[5] == want[5]).all(), name
+                aged = [dev.profile_motion_hold(now, ref, age, rows, np.zeros(100, np.uint8), WIDTH, HEIGHT, THR, 5, 3, reps=100, **SETTINGS) for _ in range(3)]
+                zero = [dev.profile_motion_hold(now, ref, np.zeros_like(age), rows, np.zeros(100, np.uint8), WIDTH, HEIGHT, THR, 5, 3, reps=100, **SETTINGS)
+                        for _ in range(3)]      # ages that are all zero: the same regions as without, plus the age byte's load and store
+                plain = [dev.profile_motion(now, ref, WIDTH, HEIGHT, THR, reps=100, **SETTINGS) for _ in range(3)]
+                launches[name] = dict(changed_cells=int(C.sum()), active=found[3], held=found[4], components=found[2],
+                                      with_ages_us=[us(r[0]) for r in aged], with_ages_empty_us=[us(r[2]) for r in aged],
+                                      zero_ages_us=[us(r[0]) for r in zero], zero_ages_empty_us=[us(r[2]) for r in zero],
+                                      without_us=[us(r[0]) for r in plain], without_empty_us=[us(r[2]) for r in plain],
+                                      plain_changed_components=dev.stage_motion_regions(now, ref, WIDTH, HEIGHT, THR, **SETTINGS)[2])
+            now, ref = mo.grids_for(grids["blob"], WIDTH, HEIGHT, THR)
+            for passing in (0, 1, 100):
+                ok = np.zeros(100, np.uint8)
+                ok[:passing] = 1
+                got = dev.stage_motion_stamp(age, rows, ok, WIDTH, HEIGHT, 3)
+                assert (got == ho.stamp(age, rows, ok, WIDTH, HEIGHT, 3)).all(), passing
+                runs = [dev.profile_motion_hold(now, ref, age, rows, ok, WIDTH, HEIGHT, THR, 5, 3, reps=100, **SETTINGS) for _ in range(3)]
+                stamps[str(passing)] = dict(cells_raised=int((got != age).sum()), stamp_us=[us(r[1]) for r in runs], empty_us=[us(r[2]) for r in runs])
+        finally:
+            dev.close()
+    out = dict(metric="motion_hold", grid="%d x %d cells (%dx%d)" % (gw, gh, WIDTH, HEIGHT), threshold=THR, settings=SETTINGS, hold=5, object_hold=3,
+               aged_cells=int((age > 0).sum()), launches=launches, stamp=stamps)
+    print(json.dumps(out), flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write("tools/motion_bench.py --hold on an MI355X: %s, threshold %d, %s, hold 5, object_hold 3, %d cells with a seeded age\n"
+                    % (out["grid"], THR, SETTINGS, out["aged_cells"]))
+            f.write("  HIP-event time of one launch alone, mean of 100, three measurements (us); the bracket around nothing beside it\n")
+            for name, r in launches.items():
+                f.write("  %-6s %4d changed + %3d held cells, %3d components (%d without ages): region launch with ages %s (empty %s), with ages all zero %s (empty %s), "
+                        "without %s (empty %s) -> %.2f / %.2f / %.2f us above the bracket\n"
+                        % (name, r["changed_cells"], r["held"], r["components"], r["plain_changed_components"], r["with_ages_us"], r["with_ages_empty_us"],
+                           r["zero_ages_us"], r["zero_ages_empty_us"], r["without_us"], r["without_empty_us"],
+                           med(r["with_ages_us"]) - med(r["with_ages_empty_us"]), med(r["zero_ages_us"]) - med(r["zero_ages_empty_us"]),
+                           med(r["without_us"]) - med(r["without_empty_us"])))
+            for passing, r in stamps.items():
+                f.write("  stamp launch, %3s passing rows (%4d cells raised the first time): %s (empty %s) -> %.2f us above the bracket\n"
+                        % (passing, r["cells_raised"], r["stamp_us"], r["empty_us"], med(r["stamp_us"]) - med(r["empty_us"])))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--hold", action="store_true", help="only the motion-hold leg: the region launch with ages, the stamp launch (DESIGN.md section 19b)")
     args = ap.parse_args(argv)
+    if args.hold:
+        return hold_leg(args)
     import motion_oracle as mo
     from watsor_amd import engine
     from watsor_amd.runtime import HipEngine

@@ -5,6 +5,11 @@
 //                        n is its number of C cells; the 64 heaviest components with n >= min_cells are ranked; one wave walks them and
 //                        writes at most WZ_MOTION_MAX_REGIONS rectangles into the lane's page-locked block.
 //   wz_k_motion_still    behind the merge of a motion call: a frame without a tile gets the padding rows and pass bytes 0.
+//   wz_k_motion_stamp    last of a motion call with a camera that holds under detections: the cells under every
+//                        passing row are raised to object_hold in the camera's age grid.
+// A camera with a hold (WzMotionCam::age_out) runs wz_k_motion_regions<true>: step 1 reads the cell's age beside its two sums, votes
+// "changed or age > 0" into the bit map and writes the decayed age; everything behind step 1 reads the bit map and is the same code.  A
+// camera without one takes, in either instantiation, the path it always took.
 // Integers only.  Nothing depends on scheduling: a component's id is the SMALLEST linear index of its cells, ties in n are broken by id,
 // sums and minima may be taken in any order (tests/motion_oracle.py restates all of it with numpy).
 //
@@ -71,11 +76,15 @@ struct WzMotionWalk {
     }
 };
 
+// AGE: the launch has a camera with a hold.  `aged`, below, is this workgroup's camera having one; "changed" then reads "active" in every
+// comment behind step 1.  The ages go from device memory to device memory: none of them is ever in LDS.
+template <bool AGE>
 __global__ __launch_bounds__(WZ_MOTION_THREADS) void wz_k_motion_regions(const WzMotionCam* __restrict__ cams, WzMotionOut* __restrict__ outs) {
     // C, one bit a cell: 2 * ceil(cells / 64) words; the labels, uint16 a cell; the counts, uint16 a cell (a component's n, at its root)
     extern __shared__ uint32_t wz_motion_lds[];
     __shared__ int again, row_lo, row_hi;   // row_lo .. row_hi: the rows of cells that hold a changed cell
     __shared__ uint32_t n_keys;
+    __shared__ uint32_t n_active, n_held;   // (AGE) the popcounts of step 1's votes: active cells, and those of them that did not change
     __shared__ uint32_t near_keys[WZ_MOTION_NEAR_KEYS];   // the first keys found, where ranking by counting reads them
     __shared__ uint32_t cand_key[WZ_MOTION_CANDIDATES];   // the ranked keys: n << 15 | (32767 - id)
     __shared__ int32_t box[WZ_MOTION_CANDIDATES][4];      // their cell boxes: cx0, cx1, cy0, cy1
@@ -85,7 +94,8 @@ __global__ __launch_bounds__(WZ_MOTION_THREADS) void wz_k_motion_regions(const W
     const WzMotionCam c = cams[blockIdx.x];
     const int tid = threadIdx.x, lane = tid & 63;
     uint32_t* const out_words = reinterpret_cast<uint32_t*>(outs + blockIdx.x);
-    if (!c.ref) {   // no reference: nothing has changed (the same for every thread of the workgroup)
+    const bool aged = AGE && c.age_out != nullptr;
+    if (!c.ref && !aged) {   // no reference: nothing has changed (the same for every thread of the workgroup)
         if (tid < RESULT_WORDS) out_words[tid] = 0u;
         return;
     }
@@ -103,15 +113,22 @@ __global__ __launch_bounds__(WZ_MOTION_THREADS) void wz_k_motion_regions(const W
     // 1. C: a wave holds 64 consecutive cells, its vote is two words of the bit map (four steps' loads are in flight together)
     if (tid < WZ_MOTION_CANDIDATES) cand_key[tid] = 0u;
     if (tid == 0) n_keys = 0u, row_lo = INT_MAX, row_hi = -1;
+    if (AGE && tid == 0) n_active = n_held = 0u;
     for (int i = tid; i < lwords; i += WZ_MOTION_THREADS) count2[i] = 0u;
     __syncthreads();
+    // (AGE) with a hold the age byte is the third load of a step, the vote is "changed or age > 0", and every cell's decayed age is written
+    // here, before any early exit: max(hold where the cell changed, age - 1 where there was one)
+    const uint8_t* __restrict__ const age_in = c.age_in;
+    const bool has_ref = !AGE || ref != nullptr, has_age = aged && age_in != nullptr;
+    int active = 0, held = 0;   // lane 0 of a wave: its votes' popcounts
     for (int base = 0; base < span; base += 4 * WZ_MOTION_THREADS) {
-        int a[4], b[4];
+        int a[4], b[4], g[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int i = base + u * WZ_MOTION_THREADS + tid;
             a[u] = i < cells ? (int)now[i] : 0;
-            b[u] = i < cells ? (int)ref[i] : 0;
+            b[u] = i < cells && has_ref ? (int)ref[i] : 0;
+            g[u] = AGE && has_age && i < cells ? (int)age_in[i] : 0;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -119,8 +136,14 @@ __global__ __launch_bounds__(WZ_MOTION_THREADS) void wz_k_motion_regions(const W
             const int y = i / gw, x = i - y * gw;
             const int npix = min(WZ_GATE_CELL, c.W - WZ_GATE_CELL * x) * min(WZ_GATE_CELL, c.H - WZ_GATE_CELL * y);
             const int d = a[u] - b[u];
-            const bool changed = i < cells && (d < 0 ? -d : d) > c.thr * npix;
-            const unsigned long long vote = __ballot(changed);
+            const bool changed = i < cells && has_ref && (d < 0 ? -d : d) > c.thr * npix;
+            const unsigned long long vote = __ballot(changed || (AGE && g[u] > 0));
+            if (AGE && aged) {
+                if (i < cells) c.age_out[i] = (uint8_t)max(changed ? c.hold : 0, g[u] > 0 ? g[u] - 1 : 0);
+                const unsigned long long moved = __ballot(changed);
+                active += __popcll(vote);
+                held += __popcll(vote & ~moved);
+            }
             const int w0 = (i - lane) >> 5;
             if (lane == 0 && w0 < cwords) {
                 cbits[w0] = (uint32_t)vote;
@@ -131,6 +154,10 @@ __global__ __launch_bounds__(WZ_MOTION_THREADS) void wz_k_motion_regions(const W
                 }
             }
         }
+    }
+    if (AGE && aged && lane == 0) {
+        atomicAdd(&n_active, (uint32_t)active);
+        atomicAdd(&n_held, (uint32_t)held);
     }
     __syncthreads();
     if (row_hi < 0) {   // a still picture (read behind the barrier: the same for every thread)
@@ -318,6 +345,8 @@ __global__ __launch_bounds__(WZ_MOTION_THREADS) void wz_k_motion_regions(const W
             result.n_regions = nr;
             result.components = n_comp;
             result.rounds = rounds + 1;
+            result.active = aged ? (int32_t)n_active : 0;
+            result.held = aged ? (int32_t)n_held : 0;
             result._pad = 0;
         }
         if (tid >= nr && tid < WZ_MOTION_MAX_REGIONS) {
@@ -329,11 +358,12 @@ __global__ __launch_bounds__(WZ_MOTION_THREADS) void wz_k_motion_regions(const W
     if (tid < RESULT_WORDS) out_words[tid] = reinterpret_cast<const uint32_t*>(&result)[tid];
 }
 
-void wz_launch_motion_regions(const WzMotionCam* cams, int n, int max_cells, WzMotionOut* out, hipStream_t s) {
+void wz_launch_motion_regions(const WzMotionCam* cams, int n, int max_cells, WzMotionOut* out, hipStream_t s, bool with_age) {
     const size_t lds = (size_t)(((max_cells + 63) >> 6) * 2) * 4 + (((size_t)max_cells + 1) & ~(size_t)1) * 4;   // bits, labels, counts
+    const auto kernel = with_age ? wz_k_motion_regions<true> : wz_k_motion_regions<false>;
     if (lds > 48 * 1024)   // (more than 11 k cells: past what a launch gets without asking; a CU of gfx950 has 160 KiB)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wz_k_motion_regions), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(wz_k_motion_regions, dim3((unsigned)n), dim3(WZ_MOTION_THREADS), lds, s, cams, out);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(WZ_MOTION_THREADS), lds, s, cams, out);
 }
 
 // One workgroup per frame of the call; only a frame without a tile is touched.
@@ -354,4 +384,37 @@ __global__ __launch_bounds__(128) void wz_k_motion_still(const WzMergeFrame* __r
 
 void wz_launch_motion_still(const WzMergeFrame* frames, int n, wz_detection_t* rows, uint8_t* pass, hipStream_t s) {
     hipLaunchKernelGGL(wz_k_motion_still, dim3((unsigned)n), dim3(128), 0, s, frames, rows, pass);
+}
+
+// One workgroup per frame of the call; a frame whose camera has no age grid or whose object_hold is 0 does nothing.  Waves take rows, lanes
+// stride over the cells of the row's box, clamped to the frame: x1 <= W - 1 gives a column below gw, y1 <= H - 1 a row below gh.
+// Rows overlap, so several lanes, of one wave or of several, may meet at a cell.  Each of them stores ONE BYTE, and every one of them the
+// same value, object_hold, over an age that only the region launch -- finished long before -- and such stores have written: whichever
+// store lands last, the byte ends as max(age, object_hold), and a neighbouring byte is never touched.  The result does not depend on
+// scheduling; no atomics, no scratch.
+#define WZ_MOTION_STAMP_THREADS 256
+__global__ __launch_bounds__(WZ_MOTION_STAMP_THREADS) void wz_k_motion_stamp(const WzMotionCam* __restrict__ cams, const wz_detection_t* __restrict__ rows,
+                                                                      const uint8_t* __restrict__ pass) {
+    const int f = blockIdx.x, lane = threadIdx.x & 63;
+    uint8_t* const age = cams[f].age_out;
+    const int to = cams[f].object_hold;
+    if (!age || to <= 0) return;
+    const int W = cams[f].W, H = cams[f].H, gw = cams[f].gw;
+    for (int r = threadIdx.x >> 6; r < WZ_MAX_DETECTIONS; r += WZ_MOTION_STAMP_THREADS / 64) {
+        const size_t at = (size_t)f * WZ_MAX_DETECTIONS + r;
+        if (pass[at] != 1) continue;
+        const int x0 = max(rows[at].x_min, 0), x1 = min(rows[at].x_max, W - 1);
+        const int y0 = max(rows[at].y_min, 0), y1 = min(rows[at].y_max, H - 1);
+        if (x0 > x1 || y0 > y1) continue;
+        const int cx0 = x0 >> 4, cy0 = y0 >> 4, bw = (x1 >> 4) - cx0 + 1, n = bw * ((y1 >> 4) - cy0 + 1);
+        for (int k = lane; k < n; k += 64) {
+            const int y = k / bw, i = (cy0 + y) * gw + cx0 + (k - y * bw);
+            if ((int)age[i] < to) age[i] = (uint8_t)to;
+        }
+    }
+}
+static_assert(WZ_GATE_CELL == 16, "wz_k_motion_stamp turns pixels into cells with >> 4");
+
+void wz_launch_motion_stamp(const WzMotionCam* cams, int n, const wz_detection_t* rows, const uint8_t* pass, hipStream_t s) {
+    hipLaunchKernelGGL(wz_k_motion_stamp, dim3((unsigned)n), dim3(WZ_MOTION_STAMP_THREADS), 0, s, cams, rows, pass);
 }

@@ -470,14 +470,23 @@ struct WzMotionCam {
     uint32_t* scratch;     // device memory, gw * gh words: the keys of the components (read only when there are more than the kernel ranks in LDS)
     int32_t W, H, gw, gh, thr, min_cells, dilate, max_regions, min_side, pad;
     int32_t even_x, even_y;   // the format cuts at even x / y only
+    // motion hold: the camera's age grids [gh][gw], one byte a cell.  age_out nullptr: the camera has no hold, and
+    // the kernel does exactly what it did before there was one
+    const uint8_t* age_in;    // the previous call's ages, or nullptr: all zero
+    uint8_t* age_out;         // the ages this call leaves (decayed by the region launch, raised by the stamp launch)
+    int32_t hold, object_hold;   // the age of a changed cell; the age of a cell under a passing detection (0: no stamp)
 };
 struct WzMotionOut {       // what the host reads, in the lane's page-locked block
     int32_t n_regions, components;   // regions accepted; components with n >= min_cells
     wz_tile_t regions[WZ_MOTION_MAX_REGIONS];
     int32_t cells[WZ_MOTION_MAX_REGIONS];   // n of every region
-    int32_t rounds, _pad;                   // rounds the labelling took (0: the picture was still), for the profiling entry point
+    int32_t rounds;                         // rounds the labelling took (0: the picture was still), for the profiling entry point
+    int32_t active, held, _pad;             // a camera with a hold: its active cells (changed or age > 0), those of them that did not change
 };
-// cams[n] (device-readable) -> out[n]; max_cells: the most cells any of the n grids has (at most WZ_MOTION_MAX_CELLS)
-void wz_launch_motion_regions(const WzMotionCam* cams, int n, int max_cells, WzMotionOut* out, hipStream_t s);
+// cams[n] (device-readable) -> out[n]; max_cells: the most cells any of the n grids has (at most WZ_MOTION_MAX_CELLS); with_age: some
+// camera of the launch has age_out
+void wz_launch_motion_regions(const WzMotionCam* cams, int n, int max_cells, WzMotionOut* out, hipStream_t s, bool with_age = false);
 // behind the merge and filter launches of a motion call: a frame without a tile (frames[f].n_tiles == 0) gets the padding rows and pass bytes 0
 void wz_launch_motion_still(const WzMergeFrame* frames, int n, wz_detection_t* rows, uint8_t* pass, hipStream_t s);
+// last of a motion call: every cell of cams[f].age_out under a row of frame f whose pass byte is 1 is raised to cams[f].object_hold
+void wz_launch_motion_stamp(const WzMotionCam* cams, int n, const wz_detection_t* rows, const uint8_t* pass, hipStream_t s);

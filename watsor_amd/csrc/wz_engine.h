@@ -139,6 +139,7 @@ struct MotionLane {
     size_t cam_words = 0;
     std::vector<int32_t> s_ntiles, s_cells, s_comps;   // the last motion call accepted on this lane (wz_motion_stats): per frame its tiles,
     std::vector<wz_tile_t> s_tiles;                    // [n][1 + WZ_MOTION_MAX_REGIONS], its regions' n [n][WZ_MOTION_MAX_REGIONS], its components
+    std::vector<int32_t> s_active, s_held;             // ... and (wz_motion_hold_stats) its active cells and those of them that did not change
     int alloc(wz_engine* e);             // (wz_tiles.hip) lazy; all or nothing
     void release() { *this = MotionLane(); }
 };
@@ -293,6 +294,8 @@ struct wz_engine {
     std::map<int, GateCam> gate_cams;
     // motion regions: a camera's settings and its two whole-frame grids (wz_set_camera_motion); empty until a camera is set.  The grid the
     // last accepted call wrote is the reference of the next one: the two are swapped by pointer, nothing is copied.
+    // A camera with a hold (wz_set_camera_motion_hold) has two age grids beside them, swapped by the same `cur`: the region launch reads
+    // d_age[cur] and writes d_age[cur ^ 1], the stamp launch -- still in flight when the call returns -- raises d_age[cur ^ 1].
     struct MotionCam {
         int w = 0, h = 0, base = 0, fmt = 0;     // the frames the settings were made for
         int gw = 0, gh = 0;                      // cells of the whole frame
@@ -300,7 +303,11 @@ struct wz_engine {
         DevBlock<uint16_t> d_grid[2];
         int cur = 0;                             // d_grid[cur] is the reference, d_grid[cur ^ 1] takes the next call's grid
         bool has_ref = false;
-        void release() { *this = MotionCam(); }  // frees the two grids
+        DevBlock<uint8_t> d_age[2];              // null: the camera has no hold
+        bool has_age = false;                    // d_age[cur] holds ages (false: they are all zero, whatever the grid says)
+        int hold = 0, object_hold = 0;
+        int lane = -1;                           // the lane whose motion call last stamped d_age
+        void release() { *this = MotionCam(); }  // frees the grids
     };
     std::map<int, MotionCam> motion_cams;
 

@@ -264,13 +264,16 @@ static int run_tiles(wz_engine* e, int slot, const TilePlan& y) {
 // ... and behind it: the merge of `src` (every tile's rows, in tile order), each frame's camera filter on its merged rows exactly as
 // wz_filter_rows applies it, and the lane's event (run_batch recorded it behind the batch: wz_wait / wz_collect must see the merge)
 // still: a motion call with a frame that has no tile -- no filter runs on it, it gets the padding rows and pass bytes 0 (k_motion.hip)
-static int merge_tail(wz_engine* e, Lane& L, const TileCall& c, int most, const wz_detection_t* src, bool still = false) {
+// stamp: a motion call with a camera that holds under detections -- the region launch's cameras; last, the cells under the rows that
+// passed all of the above are raised in those cameras' age grids
+static int merge_tail(wz_engine* e, Lane& L, const TileCall& c, int most, const wz_detection_t* src, bool still = false, const WzMotionCam* stamp = nullptr) {
     TileLane& T = L.tile;
     wz_launch_merge_tiles(T.meta.m.frames, T.meta.m.origins, src, T.d_tcand, c.n, most, c.iou, c.ios, T.trows.d, T.tpass.d, L.stream);
     for (int i = 0; i < c.n; ++i)
         if (c.cam && c.cam[i] >= 0 && e->h_cams[c.cam[i]].enabled && !(still && c.n_tiles[i] == 0))
             wz_launch_filter_rows(e->d_cams, c.cam[i], T.trows.d + (size_t)i * WZ_MAX_DETECTIONS, T.tpass.d + (size_t)i * WZ_MAX_DETECTIONS, L.stream);
     if (still) wz_launch_motion_still(T.meta.m.frames, c.n, T.trows.d, T.tpass.d, L.stream);
+    if (stamp) wz_launch_motion_stamp(stamp, c.n, T.trows.d, T.tpass.d, L.stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(L.done, L.stream));
     T.tiled = c.n;
@@ -416,11 +419,19 @@ static void motion_desc(int w, int h, int fmt, const wz_motion_t& p, const uint1
     d.thr = p.pixel_thr; d.min_cells = p.min_cells; d.dilate = p.dilate; d.max_regions = p.max_regions; d.min_side = p.min_side; d.pad = p.pad;
     d.even_x = (planar || base == WZ_FMT_YUYV422 || base == WZ_FMT_UYVY422) ? 1 : 0;
     d.even_y = planar ? 1 : 0;
+    d.age_in = nullptr; d.age_out = nullptr;   // (no hold; motion_hold_desc adds one)
+    d.hold = d.object_hold = 0;
+}
+// ... and of a camera with a hold on top of it: the ages it reads (null: all zero) and the grid that takes the ages it leaves
+static void motion_hold_desc(const uint8_t* age_in, uint8_t* age_out, int hold, int object_hold, WzMotionCam& d) {
+    d.age_in = age_in; d.age_out = age_out;
+    d.hold = hold; d.object_hold = object_hold;
 }
 
 // A checked motion call on a drained lane, frames in device memory.  Returns once the rectangles are read: the two launches that touch the
-// cameras' grids have finished by then (no other lane can hold a camera's motion state in flight); crop, batch, merge and filters are
-// enqueued behind, and the lane's event behind them.
+// cameras' luma grids have finished by then; crop, batch, merge and filters are enqueued behind, and the lane's event behind them.  No
+// other lane can hold the motion state of a camera WITHOUT a hold in flight.  A camera with one has its stamp launch -- the last of the
+// call, behind the filters -- in flight when this returns: its next call on another lane waits for this lane first, as a gated call does.
 static int motion_enqueue(wz_engine* e, int slot, const TileCall& call) {
     Lane& L = e->lanes[slot];
     MotionLane& M = L.motion;
@@ -434,6 +445,9 @@ static int motion_enqueue(wz_engine* e, int slot, const TileCall& call) {
     WzMotionCam* md = M.meta.h.cams;
     WzMotionOut* mo = M.meta.h.outs;
     int crows = 0, cols = 0, cells = 0;
+    bool aged = false, stamps = false;   // some camera of the call has a hold; ... and holds under detections
+    for (const MotionCam* m : cams)      // another lane's stamp launch may still be writing this camera's ages
+        if (m->d_age[0] && m->lane >= 0 && m->lane != slot) HIPCHK(hipEventSynchronize(e->lanes[m->lane].done));
     for (int i = 0; i < n; ++i) {
         MotionCam& m = *cams[i];
         const wz_tile_t whole = {0, 0, m.w, m.h};
@@ -443,18 +457,23 @@ static int motion_enqueue(wz_engine* e, int slot, const TileCall& call) {
         gt[i].now = now;
         gt[i].thr = 0;
         motion_desc(m.w, m.h, call.pf(i), m.p, now, m.has_ref ? m.d_grid[m.cur].p : nullptr, M.d_mscratch + M.cam_words * i, md[i]);
+        if (m.d_age[0]) {
+            motion_hold_desc(m.has_age ? m.d_age[m.cur].p : nullptr, m.d_age[m.cur ^ 1], m.hold, m.object_hold, md[i]);
+            aged = true;
+            stamps = stamps || m.object_hold > 0;
+        }
         crows = std::max(crows, gt[i].crows);
         cols = std::max(cols, gt[i].cols);
         cells = std::max(cells, m.gw * m.gh);
         mo[i].n_regions = -1;
     }
     wz_launch_tile_activity(M.meta.m.tiles, n, crows, cols, M.d_mcount, M.meta.m.activity, L.stream);
-    wz_launch_motion_regions(M.meta.m.cams, n, cells, M.meta.m.outs, L.stream);
+    wz_launch_motion_regions(M.meta.m.cams, n, cells, M.meta.m.outs, L.stream, aged);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(L.stream));   // the batch size is a host-side quantity: the plan waits for the rectangles
     // 3. the tile lists; the cameras' state changes only once everything is enqueued
     std::vector<wz_tile_t> tiles((size_t)n * PER);
-    std::vector<int32_t> nt(n), comps(n), ncell((size_t)n * WZ_MOTION_MAX_REGIONS, 0);
+    std::vector<int32_t> nt(n), comps(n), ncell((size_t)n * WZ_MOTION_MAX_REGIONS, 0), active(n), held(n);
     std::vector<const wz_tile_t*> tp(n);
     bool still = false;
     for (int i = 0; i < n; ++i) {
@@ -472,22 +491,30 @@ static int motion_enqueue(wz_engine* e, int slot, const TileCall& call) {
         nt[i] = k;
         tp[i] = t;
         comps[i] = o.components;
+        active[i] = o.active;
+        held[i] = o.held;
         still = still || k == 0;
     }
     const TileCall c = with_tiles(call, nt, tp);   // ... a tiled call on these lists
     TilePlan y;
     tile_plan(e, L, c, nullptr, y);
     WZCHK(run_tiles(e, slot, y));
-    WZCHK(merge_tail(e, L, c, y.most, L.m_rows, still));
-    // 4. the grid this call wrote is the next call's reference; what wz_motion_stats reports
+    WZCHK(merge_tail(e, L, c, y.most, L.m_rows, still, stamps ? M.meta.m.cams : nullptr));
+    // 4. the grids this call wrote are the next call's reference and ages; what wz_motion_stats and wz_motion_hold_stats report
     for (int i = 0; i < n; ++i) {
         cams[i]->cur ^= 1;
         cams[i]->has_ref = true;
+        if (cams[i]->d_age[0]) {
+            cams[i]->has_age = true;
+            cams[i]->lane = slot;
+        }
     }
     M.s_ntiles.swap(nt);
     M.s_tiles.swap(tiles);
     M.s_cells.swap(ncell);
     M.s_comps.swap(comps);
+    M.s_active.swap(active);
+    M.s_held.swap(held);
     return WZ_OK;
 }
 
@@ -589,6 +616,32 @@ extern "C" int wz_reset_camera_motion(wz_engine_t* e, int cam) {
     auto it = e->motion_cams.find(cam);
     if (it == e->motion_cams.end()) return wz_set_error(WZ_EINVAL, "camera %d has no motion settings (wz_set_camera_motion first)", cam);
     it->second.has_ref = false;   // (a motion call leaves no launch in flight that reads the grids: nothing to wait for)
+    it->second.has_age = false;   // (a stamp launch in flight writes a grid nobody reads any more; the camera's next call is ordered behind it)
+    return WZ_OK;
+}
+
+// A camera's hold: its two age grids, allocated aside behind sync_all -- a failure leaves the camera with what it had
+extern "C" int wz_set_camera_motion_hold(wz_engine_t* e, int cam, const wz_motion_hold_t* hold) {
+    if (!e || !hold) return wz_set_error(WZ_EINVAL, "wz_set_camera_motion_hold: null argument");
+    auto it = e->motion_cams.find(cam);
+    if (it == e->motion_cams.end()) return wz_set_error(WZ_EINVAL, "camera %d has no motion settings (wz_set_camera_motion first, then its hold)", cam);
+    if (hold->hold < 0 || hold->hold > 255 || hold->object_hold < 0 || hold->object_hold > 255)
+        return wz_set_error(WZ_EINVAL, "camera %d: motion hold (%d, %d): hold and object_hold must be 0 .. 255", cam, hold->hold, hold->object_hold);
+    MotionCam& m = it->second;
+    HIPCHK(hipSetDevice(e->device));
+    WZCHK(sync_all(e));
+    DevBlock<uint8_t> age[2];   // (both 0: the camera's grids leave with these two, empty)
+    if (hold->hold || hold->object_hold) {
+        hipError_t err = age[0].alloc((size_t)m.gw * m.gh);
+        if (err == hipSuccess) err = age[1].alloc((size_t)m.gw * m.gh);
+        if (err != hipSuccess) return wz_set_error(WZ_EHIP, "wz_set_camera_motion_hold: %s (camera %d keeps its previous hold)", hipGetErrorString(err), cam);
+    }
+    m.d_age[0] = std::move(age[0]);
+    m.d_age[1] = std::move(age[1]);
+    m.hold = hold->hold;
+    m.object_hold = hold->object_hold;
+    m.has_age = false;
+    m.lane = -1;
     return WZ_OK;
 }
 
@@ -624,6 +677,16 @@ extern "C" int wz_motion_stats(wz_engine_t* e, int slot, int n, int32_t* n_tiles
     if (tiles) memcpy(tiles, M.s_tiles.data(), sizeof(wz_tile_t) * M.s_tiles.size());
     if (cells) memcpy(cells, M.s_cells.data(), sizeof(int32_t) * M.s_cells.size());
     if (components) memcpy(components, M.s_comps.data(), sizeof(int32_t) * n);
+    return WZ_OK;
+}
+
+extern "C" int wz_motion_hold_stats(wz_engine_t* e, int slot, int n, int32_t* active, int32_t* held) {
+    if (!e || !active || !held || slot < 0 || slot >= e->n_lanes) return wz_set_error(WZ_EINVAL, "wz_motion_hold_stats: bad argument");
+    const MotionLane& M = e->lanes[slot].motion;
+    if (n < 1 || n != (int)M.s_active.size())
+        return wz_set_error(WZ_EINVAL, "wz_motion_hold_stats: the last motion call on lane %d had %d frames, not %d", slot, (int)M.s_active.size(), n);
+    memcpy(active, M.s_active.data(), sizeof(int32_t) * n);
+    memcpy(held, M.s_held.data(), sizeof(int32_t) * n);
     return WZ_OK;
 }
 
@@ -1002,16 +1065,26 @@ struct MotionStage {
     WzGateTile* tile = nullptr;
     int32_t* cnt = nullptr;
     int cells = 0;
+    // with_hold (the hold's entry points): + two age grids, and the 100 rows and pass bytes of the stamp kernel
+    bool with_hold = false;
+    uint8_t *age_in = nullptr, *age_out = nullptr, *pass = nullptr;
+    wz_detection_t* rows = nullptr;
     size_t carve(const void* base) {
         Carve c(base);
         now = c.take<uint16_t>(cells, 16); ref = c.take<uint16_t>(cells, 16); scratch = c.take<uint32_t>(cells, 16);
         cam = c.take<WzMotionCam>(1, 16); out = c.take<WzMotionOut>(1); tile = c.take<WzGateTile>(1); cnt = c.take<int32_t>(4);
+        if (with_hold) {
+            age_in = c.take<uint8_t>(cells, 16); age_out = c.take<uint8_t>(cells, 16);
+            rows = c.take<wz_detection_t>(WZ_MAX_DETECTIONS, 16); pass = c.take<uint8_t>(WZ_MAX_DETECTIONS, 16);
+        }
         return c.bytes();
     }
 };
-static int motion_stage(wz_engine* e, const char* who, const uint16_t* now, const uint16_t* ref, int w, int h, int fmt, const wz_motion_t* p, MotionStage& s) {
+static int motion_stage(wz_engine* e, const char* who, const uint16_t* now, const uint16_t* ref, int w, int h, int fmt, const wz_motion_t* p, MotionStage& s,
+                        const uint8_t* age = nullptr, int hold = 0, int object_hold = 0) {
     if (!e || !now || !p) return wz_set_error(WZ_EINVAL, "%s: null argument", who);
     WZCHK(motion_refusal(nullptr, who, w, h, fmt, *p));
+    if (hold < 0 || hold > 255 || object_hold < 0 || object_hold > 255) return wz_set_error(WZ_EINVAL, "%s: hold and object_hold must be 0 .. 255", who);
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     s.cells = (int)gate_cells_of(w, h);
@@ -1020,9 +1093,11 @@ static int motion_stage(wz_engine* e, const char* who, const uint16_t* now, cons
     s.carve(s.d);
     WzMotionCam d;
     motion_desc(w, h, fmt, *p, s.now, ref ? s.ref : nullptr, s.scratch, d);
+    if (s.with_hold) motion_hold_desc(age ? s.age_in : nullptr, s.age_out, hold, object_hold, d);
     HIPCHK(hipMemset(s.d, 0, all));
     HIPCHK(hipMemcpy(s.now, now, (size_t)s.cells * 2, hipMemcpyHostToDevice));
     if (ref) HIPCHK(hipMemcpy(s.ref, ref, (size_t)s.cells * 2, hipMemcpyHostToDevice));
+    if (s.with_hold && age) HIPCHK(hipMemcpy(s.age_in, age, (size_t)s.cells, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(s.cam, &d, sizeof(d), hipMemcpyHostToDevice));
     return WZ_OK;
 }
@@ -1074,6 +1149,99 @@ extern "C" int wz_profile_motion(wz_engine_t* e, const uint16_t* now, const uint
     }
     if (err != hipSuccess) return wz_set_error(WZ_EHIP, "wz_profile_motion: %s", hipGetErrorString(err));
     WZCHK(rc);
+    return bracket_ms(e->stream, reps, [] {}, empty_ms);
+}
+
+// ---- motion hold
+// wz_k_motion_regions<true> alone on two caller-provided grids and the caller's ages
+extern "C" int wz_stage_motion_hold(wz_engine_t* e, const uint16_t* now, const uint16_t* ref, const uint8_t* age_in, int w, int h, int fmt,
+                                    const wz_motion_t* motion, int hold, int32_t* n_regions, wz_tile_t* regions, int32_t* cells, int32_t* components,
+                                    int32_t* active, int32_t* held, uint8_t* age_out) {
+    if (!n_regions || !regions || !cells || !components || !active || !held || !age_out) return wz_set_error(WZ_EINVAL, "wz_stage_motion_hold: null argument");
+    MotionStage s;
+    s.with_hold = true;
+    WZCHK(motion_stage(e, "wz_stage_motion_hold", now, ref, w, h, fmt, motion, s, age_in, hold, 0));
+    wz_launch_motion_regions(s.cam, 1, s.cells, s.out, e->stream, true);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
+    WzMotionOut o;
+    HIPCHK(hipMemcpy(&o, s.out, sizeof(o), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(age_out, s.age_out, (size_t)s.cells, hipMemcpyDeviceToHost));
+    *n_regions = o.n_regions;
+    *components = o.components;
+    *active = o.active;
+    *held = o.held;
+    memcpy(regions, o.regions, sizeof(o.regions));
+    memcpy(cells, o.cells, sizeof(o.cells));
+    return WZ_OK;
+}
+
+// The ages, rows and pass bytes of one w x h frame in a MotionStage, and the stamp kernel's camera: what wz_k_motion_stamp reads
+static int stamp_stage(wz_engine* e, const char* who, const uint8_t* age, const wz_detection_t* rows, const uint8_t* pass, int w, int h, int object_hold,
+                       MotionStage& s) {
+    if (!e || !age || !rows || !pass) return wz_set_error(WZ_EINVAL, "%s: null argument", who);
+    if (w < 1 || h < 1 || object_hold < 0 || object_hold > 255) return wz_set_error(WZ_EINVAL, "%s: a frame of %dx%d, object_hold %d (0 .. 255)", who, w, h, object_hold);
+    if (gate_cells_of(w, h) > (size_t)WZ_MOTION_MAX_CELLS)
+        return wz_set_error(WZ_ELIMIT, "%s: a %dx%d frame has %zu cells, a motion camera takes at most %d", who, w, h, gate_cells_of(w, h), WZ_MOTION_MAX_CELLS);
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    s.with_hold = true;
+    s.cells = (int)gate_cells_of(w, h);
+    const size_t all = s.carve(nullptr);
+    HIPCHK(s.d.alloc(all));
+    s.carve(s.d);
+    WzMotionCam d = {};
+    d.W = w; d.H = h;
+    d.gw = cells_of(w);
+    d.gh = cells_of(h);
+    motion_hold_desc(nullptr, s.age_out, 0, object_hold, d);
+    HIPCHK(hipMemset(s.d, 0, all));
+    HIPCHK(hipMemcpy(s.age_out, age, (size_t)s.cells, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s.rows, rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s.pass, pass, WZ_MAX_DETECTIONS, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s.cam, &d, sizeof(d), hipMemcpyHostToDevice));
+    return WZ_OK;
+}
+
+// wz_k_motion_stamp alone on caller-provided ages, rows and pass bytes
+extern "C" int wz_stage_motion_stamp(wz_engine_t* e, const uint8_t* age_in, const wz_detection_t* rows, const uint8_t* pass, int w, int h, int object_hold,
+                                     uint8_t* age_out) {
+    if (!age_out) return wz_set_error(WZ_EINVAL, "wz_stage_motion_stamp: null argument");
+    MotionStage s;
+    WZCHK(stamp_stage(e, "wz_stage_motion_stamp", age_in, rows, pass, w, h, object_hold, s));
+    wz_launch_motion_stamp(s.cam, 1, s.rows, s.pass, e->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(age_out, s.age_out, (size_t)s.cells, hipMemcpyDeviceToHost));
+    return WZ_OK;
+}
+
+extern "C" int wz_debug_motion_age(wz_engine_t* e, int cam, uint8_t* out) {
+    if (!e || !out) return wz_set_error(WZ_EINVAL, "wz_debug_motion_age: null argument");
+    const auto it = e->motion_cams.find(cam);
+    if (it == e->motion_cams.end() || !it->second.d_age[0]) return wz_set_error(WZ_EINVAL, "camera %d has no motion hold (wz_set_camera_motion_hold first)", cam);
+    const MotionCam& m = it->second;
+    HIPCHK(hipSetDevice(e->device));
+    WZCHK(sync_all(e));
+    const size_t cells = (size_t)m.gw * m.gh;
+    if (!m.has_age) memset(out, 0, cells);
+    else HIPCHK(hipMemcpy(out, m.d_age[m.cur], cells, hipMemcpyDeviceToHost));
+    return WZ_OK;
+}
+
+// HIP-event time of the region launch alone with these ages, and of the stamp launch alone on the ages it left (the stamp raises the same
+// cells to the same value every time: every repetition reads and writes what the first did, except that the first finds them lower)
+extern "C" int wz_profile_motion_hold(wz_engine_t* e, const uint16_t* now, const uint16_t* ref, const uint8_t* age_in, int w, int h, int fmt,
+                                      const wz_motion_t* motion, int hold, const wz_detection_t* rows, const uint8_t* pass, int object_hold, int reps,
+                                      float* regions_ms, float* stamp_ms, float* empty_ms) {
+    if (reps < 1 || !rows || !pass || !regions_ms || !stamp_ms || !empty_ms) return wz_set_error(WZ_EINVAL, "wz_profile_motion_hold: bad argument");
+    MotionStage s;
+    s.with_hold = true;
+    WZCHK(motion_stage(e, "wz_profile_motion_hold", now, ref, w, h, fmt, motion, s, age_in, hold, object_hold));
+    HIPCHK(hipMemcpy(s.rows, rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s.pass, pass, WZ_MAX_DETECTIONS, hipMemcpyHostToDevice));
+    WZCHK(bracket_ms(e->stream, reps, [&] { wz_launch_motion_regions(s.cam, 1, s.cells, s.out, e->stream, true); }, regions_ms));
+    WZCHK(bracket_ms(e->stream, reps, [&] { wz_launch_motion_stamp(s.cam, 1, s.rows, s.pass, e->stream); }, stamp_ms));
     return bracket_ms(e->stream, reps, [] {}, empty_ms);
 }
 #endif   // WZ_DEV_BUILD

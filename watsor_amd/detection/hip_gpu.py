@@ -234,6 +234,51 @@ def check_motion_options(motion_default, motion_by_name: dict, tiles_default, ti
         raise ValueError("motion[%r]: the camera has tiles too: a camera takes one of the two" % (both[0],))
 
 
+_MOTION_HOLD_KEYS = ("hold", "object_hold")
+
+
+def _motion_hold_spec(spec, where: str) -> dict:
+    """One checked `motion_hold` option: {"hold": 0 .. 255 (default 0), "object_hold": 0 .. 255 (0)}, not both 0."""
+    if not isinstance(spec, dict):
+        raise ValueError("%s: expected {\"hold\": 0 .. 255, \"object_hold\": 0 .. 255}, got %r" % (where, spec))
+    if set(spec) - set(_MOTION_HOLD_KEYS):
+        raise ValueError("%s: unknown key(s) %s" % (where, ", ".join(sorted(map(str, set(spec) - set(_MOTION_HOLD_KEYS))))))
+    out = {}
+    for k in _MOTION_HOLD_KEYS:
+        v = spec.get(k, 0)
+        if not isinstance(v, int) or isinstance(v, bool):
+            raise ValueError("%s: %s %r, expected a whole number" % (where, k, v))
+        if v < 0 or v > 255:
+            raise ValueError("%s: %s %r, expected 0 .. 255" % (where, k, v))
+        out[k] = v
+    if not any(out.values()):
+        raise ValueError("%s: hold and object_hold are both 0: leave the option out for a camera without a hold" % where)
+    return out
+
+
+def motion_hold_options(options: dict, motion_default, motion_by_name: dict):
+    """(the detector's hold or None, {camera name: hold}) from the plugin option `motion_hold`: {"hold": 0 .. 255, "object_hold": 0 .. 255}
+    for every camera with motion settings, or {camera name: such a description} -- a motion camera keeps a cell in its regions for `hold`
+    further frames after it changed, and for `object_hold` further frames after a detection that passed the camera's filters covered it
+    (`HipEngine.set_camera_motion_hold`).  motion_default, motion_by_name: what `motion_options` returned -- a hold needs motion settings.
+    Bad options raise ValueError; the message begins with the option at fault."""
+    v = options.get("motion_hold")
+    if v is None:
+        return None, {}
+    if isinstance(v, dict) and v and not any(isinstance(d, dict) for d in v.values()):
+        spec = _motion_hold_spec(v, "motion_hold")
+        if motion_default is None and not motion_by_name:
+            raise ValueError("motion_hold: there is no motion option: a hold keeps motion regions alive")
+        return spec, {}
+    if not isinstance(v, dict) or not v or not all(isinstance(d, dict) for d in v.values()):
+        raise ValueError("motion_hold: expected {\"hold\": 0 .. 255, \"object_hold\": 0 .. 255} or {camera name: such a description}, got %r" % (v,))
+    by_name = {str(name): _motion_hold_spec(d, "motion_hold[%r]" % (name,)) for name, d in v.items()}
+    for name in by_name:
+        if motion_default is None and name not in motion_by_name:
+            raise ValueError("motion_hold[%r]: the camera has no motion option: a hold keeps motion regions alive" % (name,))
+    return None, by_name
+
+
 def cut_calls(items, max_batch: int):
     """Cuts a list of frames into the consecutive calls one rule allows: items[i] = (key, cost, camera that may appear once per call, or
     None); a new call starts when the key changes, when the cost would pass max_batch, or when such a camera appears again.  Returns the
@@ -308,6 +353,10 @@ class HipObjectDetector:
         `pad` pixels around the cells; `whole_frame` runs the squeezed whole frame beside them; "iou" / "ios" merge as for `tiles`.  A
         camera takes `motion` or `tiles`, not both; its frames need a camera id and go through `detect_batch` (cut into calls whose
         configured whole_frame + max_regions fit max_batch); `bind_frame_table` / `bind_tiled_frame_table` raise for such a camera.
+        `options["motion_hold"]`: {"hold": 0 .. 255, "object_hold": 0 .. 255} (not both 0) for every camera with `motion`, or {camera name:
+        one of these}: a cell stays part of the camera's regions for `hold` further frames after it changed, and for `object_hold`
+        further frames after a detection that passed the camera's filters covered it -- a person who stops moving, a parked car the
+        whole-frame tile found (include/watsor_hip.h: wz_set_camera_motion_hold).  A camera without `motion` cannot have one.
         `options["schedule"]`: "latency" | "throughput" | "auto" (default) -- the launch shapes of this detector PROCESS
         (include/watsor_hip.h: wz_set_schedule).  "latency" makes a lone batch finish soonest -- the reference's normal load is one
         frame at a time (`_next_frame`, detector.py:102-112); "throughput" gets the most frames per second out of four batches in
@@ -356,6 +405,8 @@ class HipObjectDetector:
         self.__motion_default, self.__motion_by_name = motion_options(options)
         self.__motion_by_cam = {}
         self.__motion_layouts = {}      # camera id -> what its motion settings were last made for: (width, height, base format, settings)
+        self.__hold_default, self.__hold_by_name = motion_hold_options(options, self.__motion_default, self.__motion_by_name)
+        self.__hold_by_cam = {}
         for where, spec in [("tiles", self.__tiles_default)] + [("tiles[%r]" % n, t) for n, t in self.__tiles_by_name.items()]:
             if spec is not None and spec["count"] > max_batch:
                 raise ValueError("%s: %d tiles per frame exceed max_batch %d" % (where, spec["count"], max_batch))
@@ -468,6 +519,7 @@ class HipObjectDetector:
         self.__fmt_by_cam = {i: self.__fmt_by_name.get(str(name), self.__fmt_default) for name, i in ids.items() if i >= 0}
         self.__tiles_by_cam = {i: self.__tiles_by_name[str(name)] for name, i in ids.items() if i >= 0 and str(name) in self.__tiles_by_name}
         self.__motion_by_cam = {i: self.__motion_by_name[str(name)] for name, i in ids.items() if i >= 0 and str(name) in self.__motion_by_name}
+        self.__hold_by_cam = {i: self.__hold_by_name[str(name)] for name, i in ids.items() if i >= 0 and str(name) in self.__hold_by_name}
         for name, cfg in (camera_configs or {}).items():
             if name in ids:
                 self.__filters.append(HipCameraFilter(self.__engine, ids[name], cfg, drop=drop))
@@ -654,6 +706,9 @@ class HipObjectDetector:
                 if self.__motion_layouts.get(cameras[i]) != layout:      # the first frame of the camera, or another size or format
                     self.__engine.set_camera_motion(cameras[i], w, h, m["threshold"], m["min_cells"], m["dilate"], m["max_regions"], m["min_side"],
                                                     m["pad"], m["whole_frame"], fmt)
+                    hold = self.__hold_by_cam.get(cameras[i]) or self.__hold_default      # (new motion settings drop the hold: it is set behind them)
+                    if hold is not None:
+                        self.__engine.set_camera_motion_hold(cameras[i], hold["hold"], hold["object_hold"])
                     self.__motion_layouts[cameras[i]] = layout
             if len(ok) < len(moving) and n == len(calls) - 1:
                 break

@@ -135,6 +135,7 @@ class HipEngine:
         self._gate_last = {}                               # lane -> the camera ids of the last gated call accepted on it
         self._motion_whole = {}                            # camera id -> whole_frame of its motion settings (set_camera_motion)
         self._motion_last = {}                             # lane -> the camera ids of the last motion call accepted on it
+        self._motion_grid = {}                             # camera id -> (cell rows, cell columns) of its motion settings
         self._bound_arrays = {}                            # (submit_bound before any bind_frames: the engine's EINVAL, not an AttributeError)
         self._bound_last = {}                              # lane -> frames of the last bound batch accepted on it (bound_source)
         self._bound_cams = []                              # camera id of every table entry (bind_frames) ...
@@ -399,14 +400,24 @@ class HipEngine:
         words = self._motion_words(threshold, min_cells, dilate, max_regions, min_side, pad, whole_frame)
         self._ck(self._lib.wz_set_camera_motion(self._h, int(cam), int(width), int(height), int(fmt), C.byref(words)))
         self._motion_whole[int(cam)] = 1 if whole_frame else 0
+        self._motion_grid[int(cam)] = (-(-int(height) // _lib.WZ_GATE_CELL), -(-int(width) // _lib.WZ_GATE_CELL))
+
+    def set_camera_motion_hold(self, cam: int, hold: int = 0, object_hold: int = 0) -> None:
+        """Camera `cam`, which has motion settings, keeps a cell active -- part of its regions -- for `hold` (0 .. 255) further motion calls
+        after it changed, and for `object_hold` (0 .. 255) further calls after a detection that passed the camera's filter covered it
+        (include/watsor_hip.h: wz_set_camera_motion_hold).  Both 0: the camera has no hold any more.  Waits for every lane; the ages start
+        at zero.  `set_camera_motion` drops the hold: set it after the motion settings."""
+        words = (C.c_int32 * 4)(int(hold), int(object_hold), 0, 0)
+        self._ck(self._lib.wz_set_camera_motion_hold(self._h, int(cam), C.byref(words)))
 
     def reset_camera_motion(self, cam: int) -> None:
-        """Forget the reference of camera `cam` (its next motion call sees no motion); the settings stay."""
+        """Forget the reference (and the ages of a hold) of camera `cam`: its next motion call sees no motion; the settings stay."""
         self._ck(self._lib.wz_reset_camera_motion(self._h, int(cam)))
 
     def clear_camera_motion(self, cam: int) -> None:
         self._ck(self._lib.wz_clear_camera_motion(self._h, int(cam)))
         self._motion_whole.pop(int(cam), None)
+        self._motion_grid.pop(int(cam), None)
 
     def detect_motion(self, frames: Sequence[np.ndarray], cams: Sequence[int], out_rows: Sequence,
                       passes: Optional[Sequence[np.ndarray]] = None, formats: Optional[Sequence[int]] = None,
@@ -436,6 +447,17 @@ class HipEngine:
         lists = [[(t.x0, t.y0, t.w, t.h) for t in tiles[i * per:i * per + counts[i]]] for i in range(n)]
         regions = [counts[i] - self._motion_whole[c] for i, c in enumerate(cams)]
         return lists, [[int(v) for v in cells[i * most:i * most + regions[i]]] for i in range(n)], [int(v) for v in comps]
+
+    def motion_hold_stats(self, slot: int = 0):
+        """Per frame of the last motion call accepted on lane `slot`: ([its active cells: changed, or held by an age], [those of them that
+        did not change]); 0 and 0 for a frame whose camera has no hold."""
+        cams = self._motion_last.get(slot)
+        if not cams:
+            raise ValueError("no motion call was made on lane %d" % slot)
+        n = len(cams)
+        active, held = (C.c_int32 * n)(), (C.c_int32 * n)()
+        self._ck(self._lib.wz_motion_hold_stats(self._h, slot, n, C.byref(active), C.byref(held)))
+        return [int(v) for v in active], [int(v) for v in held]
 
     def submit_device(self, slot: int, d_frames: Sequence[int], widths: Sequence[int], heights: Sequence[int],
                       cams: Optional[Sequence[int]] = None, formats: Optional[Sequence[int]] = None) -> None:
@@ -827,6 +849,78 @@ class HipEngine:
                                              int(width), int(height), int(fmt), C.byref(words), int(reps), C.byref(reg), C.byref(act), C.byref(empty),
                                              C.byref(rounds)))
         return float(reg.value), float(act.value), float(empty.value), int(rounds.value)
+
+    @staticmethod
+    def _motion_grids(shape, **grids):
+        """the named grids (None stays None) as contiguous arrays of their dtype, checked against the cell grid's shape"""
+        out = []
+        for name, (g, dtype) in grids.items():
+            g = None if g is None else np.ascontiguousarray(g, dtype)
+            if g is not None and g.shape != shape:
+                raise ValueError("%s: expected a %s grid of shape %r, got %r" % (name, np.dtype(dtype).name, shape, g.shape))
+            out.append(g)
+        return out
+
+    @staticmethod
+    def _rows_and_passes(rows, passes):
+        rows, passes = np.ascontiguousarray(rows, ROW_DTYPE), np.ascontiguousarray(passes, np.uint8)
+        if rows.shape != (100,) or passes.shape != (100,):
+            raise ValueError("expected 100 rows and 100 pass bytes, got %r and %r" % (rows.shape, passes.shape))
+        return rows, passes
+
+    def stage_motion_hold(self, now: np.ndarray, ref: Optional[np.ndarray], age: Optional[np.ndarray], width: int, height: int, threshold: int,
+                          hold: int, min_cells: int = 1, dilate: int = 1, max_regions: int = 3, min_side: int = 300, pad: int = 8,
+                          fmt: int = FMT_RGB24):
+        """The region kernel alone as a camera with a hold runs it: `stage_motion_regions` plus the ages `age` (uint8 [cell rows, cell columns];
+        None: all zero) and `hold`: (rectangles, the active cells of every region, components, active cells, those of them that did not
+        change, the decayed ages)."""
+        self._dev_only("stage_motion_hold()")
+        shape = (-(-int(height) // _lib.WZ_GATE_CELL), -(-int(width) // _lib.WZ_GATE_CELL))
+        now, ref, age = self._motion_grids(shape, now=(now, np.uint16), ref=(ref, np.uint16), age=(age, np.uint8))
+        words = self._motion_words(threshold, min_cells, dilate, max_regions, min_side, pad, False)
+        most = _lib.WZ_MOTION_MAX_REGIONS
+        n, comps, active, held = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+        tiles, cells, out = (Tile * most)(), (C.c_int32 * most)(), np.full(shape, 0xA5, np.uint8)
+        ptr = lambda g: C.c_void_p(g.ctypes.data) if g is not None else None      # noqa: E731
+        self._ck(self._lib.wz_stage_motion_hold(self._h, ptr(now), ptr(ref), ptr(age), int(width), int(height), int(fmt), C.byref(words), int(hold),
+                                                C.byref(n), C.byref(tiles), C.byref(cells), C.byref(comps), C.byref(active), C.byref(held), ptr(out)))
+        return ([(t.x0, t.y0, t.w, t.h) for t in tiles[:n.value]], [int(v) for v in cells[:n.value]], int(comps.value), int(active.value),
+                int(held.value), out)
+
+    def stage_motion_stamp(self, age: np.ndarray, rows: np.ndarray, passes: np.ndarray, width: int, height: int, object_hold: int) -> np.ndarray:
+        """The stamp kernel alone: the ages (uint8 [cell rows, cell columns] of a width x height frame) behind 100 rows (ROW_DTYPE) with their
+        100 pass bytes."""
+        self._dev_only("stage_motion_stamp()")
+        shape = (-(-int(height) // _lib.WZ_GATE_CELL), -(-int(width) // _lib.WZ_GATE_CELL))
+        age, = self._motion_grids(shape, age=(age, np.uint8))
+        rows, passes = self._rows_and_passes(rows, passes)
+        out = np.full(shape, 0xA5, np.uint8)
+        self._ck(self._lib.wz_stage_motion_stamp(self._h, C.c_void_p(age.ctypes.data), C.c_void_p(rows.ctypes.data), C.c_void_p(passes.ctypes.data),
+                                                 int(width), int(height), int(object_hold), C.c_void_p(out.ctypes.data)))
+        return out
+
+    def debug_motion_age(self, cam: int) -> np.ndarray:
+        """The current ages of camera `cam`'s hold (uint8 [cell rows, cell columns]), once every lane has drained; ValueError if it has none."""
+        self._dev_only("debug_motion_age()")
+        out = np.full(self._motion_grid.get(int(cam), (1, 1)), 0xA5, np.uint8)
+        self._ck(self._lib.wz_debug_motion_age(self._h, int(cam), C.c_void_p(out.ctypes.data)))
+        return out
+
+    def profile_motion_hold(self, now: np.ndarray, ref: Optional[np.ndarray], age: Optional[np.ndarray], rows: np.ndarray, passes: np.ndarray,
+                            width: int, height: int, threshold: int, hold: int, object_hold: int, min_cells: int = 1, dilate: int = 1,
+                            max_regions: int = 3, min_side: int = 300, pad: int = 8, fmt: int = FMT_RGB24, reps: int = 100):
+        """(ms of the region launch alone with these ages, ms of the stamp launch alone with these rows and pass bytes, ms of an empty
+        bracket): HIP-event brackets, the mean of `reps` each."""
+        self._dev_only("profile_motion_hold()")
+        shape = (-(-int(height) // _lib.WZ_GATE_CELL), -(-int(width) // _lib.WZ_GATE_CELL))
+        now, ref, age = self._motion_grids(shape, now=(now, np.uint16), ref=(ref, np.uint16), age=(age, np.uint8))
+        rows, passes = self._rows_and_passes(rows, passes)
+        words = self._motion_words(threshold, min_cells, dilate, max_regions, min_side, pad, False)
+        reg, stamp, empty = C.c_float(), C.c_float(), C.c_float()
+        ptr = lambda g: C.c_void_p(g.ctypes.data) if g is not None else None      # noqa: E731
+        self._ck(self._lib.wz_profile_motion_hold(self._h, ptr(now), ptr(ref), ptr(age), int(width), int(height), int(fmt), C.byref(words), int(hold),
+                                                  ptr(rows), ptr(passes), int(object_hold), int(reps), C.byref(reg), C.byref(stamp), C.byref(empty)))
+        return float(reg.value), float(stamp.value), float(empty.value)
 
     def profile_gated(self, d_frames: Sequence[int], widths: Sequence[int], heights: Sequence[int], cams: Sequence[int],
                       formats: Optional[Sequence[int]] = None, iou: Optional[float] = None, ios: Optional[float] = None, reps: int = 50):
