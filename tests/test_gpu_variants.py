@@ -330,3 +330,47 @@ def test_kernel_by_kernel_launches_write_the_same_rows_as_the_captured_graph(mod
     # graph of its size is captured at that first use all the same (the capture stall belongs to the first batch of a size, not to the first
     # moment of contention: ADVICE r5), it is only not replayed
     assert res[None]["nodes"] >= 25 and res[None]["rows"] == res["1"]["rows"]
+
+
+def test_both_resize_forms_of_one_batch_size_replay_on_one_lane(model_dir_robust, tmp_path):
+    """A lane keeps one captured graph per (batch size, resize form).  Batches of 2, 2, 3, 2, 3 frames on lane 0 alternate between the two
+    forms: 1280 x 720 frames inside a page-locked arena are read in place (vertical down-scale >= 2), which takes the row-staged resize
+    kernel; 640 x 480 frames outside it are staged, which takes the per-pixel one.  The keys `n` and `n | 1 << 16` of the same n are so both
+    captured, and both replayed -- descriptors rewritten in the captured resize node -- after the other one was.  `WZ_GRAPH=1` and
+    `WZ_GRAPH=0` (kernel by kernel) write byte-identical rows, batch after batch."""
+    import json
+    import os
+    import subprocess
+    import sys
+    script = (
+        "import sys, json, numpy as np\n"
+        "sys.path.insert(0, %r)\n"
+        "from watsor_amd.runtime import HipEngine, ROW_DTYPE\n"
+        "from watsor_amd.synth import synthetic_frame\n"
+        "e = HipEngine(%r, 0, 3, 1280, 720)\n"
+        "arena = np.zeros((3, 720, 1280, 3), np.uint8)\n"
+        "e.host_register(arena)\n"
+        "out = []\n"
+        "for k, n in enumerate((2, 2, 3, 2, 3)):\n"
+        "    if k %% 2 == 0:\n"
+        "        for i in range(n):\n"
+        "            arena[i] = synthetic_frame(1280, 720, 9500 + 10 * k + i)\n"
+        "        frames = [arena[i] for i in range(n)]\n"
+        "    else:\n"
+        "        frames = [synthetic_frame(640, 480, 9500 + 10 * k + i) for i in range(n)]\n"
+        "    rows = [np.zeros(100, ROW_DTYPE) for _ in frames]\n"
+        "    e.submit_host(0, frames)\n"
+        "    e.collect(0, rows)\n"
+        "    out.append(np.stack(rows).tobytes().hex())\n"
+        "print(json.dumps(dict(nodes=e.graph_nodes(0), rows=out)))\n"
+        "e.host_unregister(arena)\n"
+        "e.close()\n" % (conftest.ROOT, os.path.join(model_dir_robust, "mi355x.bin")))
+    res = {}
+    base = {k: v for k, v in os.environ.items() if k not in ("WZ_GRAPH", "WZ_SCHEDULE")}
+    for g in ("1", "0"):
+        p = subprocess.run([sys.executable, "-c", script], env=dict(base, WZ_GRAPH=g), capture_output=True, text=True, timeout=120)
+        assert p.returncode == 0, p.stderr[-1500:]
+        res[g] = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert res["1"]["nodes"] > 0 and res["0"]["nodes"] == 0
+    assert len(res["1"]["rows"]) == 5 and res["1"]["rows"] == res["0"]["rows"]
+    assert len(set(res["1"]["rows"])) == 5                              # (five different batches: no batch handed over another one's rows)

@@ -519,33 +519,21 @@ size_t wz_preprocess_rows_need(int w, int fmt) {
     return 12 * (size_t)w + 32 * runs;
 }
 
-// the kernels' last argument: bit 0 = half-pixel centres, bits 8 ..: the row-staged kernel's LDS budget in units of 256 bytes
-int wz_preprocess_flags(bool half_pixel, int rows_lds) { return (half_pixel ? 1 : 0) | ((rows_lds >> 8) << 8); }
+// Which kernel, at what shape, with what last argument (bit 0 = half-pixel centres, bits 8 ..: the row-staged kernel's LDS budget in units
+// of 256 bytes): the row-staged form is one workgroup per output row, the per-pixel form one thread per output pixel
+WzPreLaunch wz_preprocess_launch(bool hp, int n, int size, int rows_lds, bool half_pixel) {
+    const int flags = (half_pixel ? 1 : 0) | ((rows_lds >> 8) << 8);
+    if (rows_lds > 0)
+        return {hp ? reinterpret_cast<const void*>(wz_k_preprocess_rows<true>) : reinterpret_cast<const void*>(wz_k_preprocess_rows<false>),
+                dim3(size, n), dim3(WZ_PRE_ROWS_THREADS), (unsigned)rows_lds, flags};
+    return {hp ? reinterpret_cast<const void*>(wz_k_preprocess<true>) : reinterpret_cast<const void*>(wz_k_preprocess<false>),
+            dim3((size * size + 255) / 256, n), dim3(256), 0, flags};
+}
 
 void wz_launch_preprocess(const WzFrameDesc* d_frames, int n, int size, half_t* out, hipStream_t s, bool hp, WzFrameDesc* keep,
                           bool half_pixel, const WzFrameDesc* by_value, int rows_lds) {
-    dim3 grid((size * size + 255) / 256, n);
-    WzDescPack pack;
-    memset(&pack, 0, sizeof(pack));
-    if (by_value && n <= WZ_DESC_PACK) {
-        memcpy(pack.d, by_value, sizeof(WzFrameDesc) * n);
-        d_frames = nullptr;
-    }
-    if (rows_lds > 0) {   // the row-staged form: one workgroup per output row
-        dim3 rgrid(size, n);
-        if (hp)
-            WZ_LAUNCH(wz_k_preprocess_rows<true>, rgrid, dim3(WZ_PRE_ROWS_THREADS), rows_lds, s, d_frames, pack, size, out, keep, wz_preprocess_flags(half_pixel, rows_lds));
-        else
-            WZ_LAUNCH(wz_k_preprocess_rows<false>, rgrid, dim3(WZ_PRE_ROWS_THREADS), rows_lds, s, d_frames, pack, size, out, keep, wz_preprocess_flags(half_pixel, rows_lds));
-        return;
-    }
-    if (hp)
-        WZ_LAUNCH(wz_k_preprocess<true>, grid, dim3(256), 0, s, d_frames, pack, size, out, keep, half_pixel ? 1 : 0);
-    else
-        WZ_LAUNCH(wz_k_preprocess<false>, grid, dim3(256), 0, s, d_frames, pack, size, out, keep, half_pixel ? 1 : 0);
+    const WzPreLaunch d = wz_preprocess_launch(hp, n, size, rows_lds, half_pixel);
+    WzPreArgs a;
+    a.set(d_frames, by_value, n, size, out, keep, d.flags);
+    WZ_LAUNCH_DESCRIBED(d, a.params(), s);
 }
-const void* wz_preprocess_func(bool hp, bool rows) {
-    if (rows) return hp ? reinterpret_cast<const void*>(wz_k_preprocess_rows<true>) : reinterpret_cast<const void*>(wz_k_preprocess_rows<false>);
-    return hp ? reinterpret_cast<const void*>(wz_k_preprocess<true>) : reinterpret_cast<const void*>(wz_k_preprocess<false>);
-}
-int wz_preprocess_rows_threads() { return WZ_PRE_ROWS_THREADS; }

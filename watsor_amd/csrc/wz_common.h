@@ -4,6 +4,7 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "../../include/watsor_hip.h"
 #include "wz_program.h"
@@ -242,6 +243,8 @@ struct WzLaunchNote { const void* func; unsigned grid[3], block[3]; unsigned lds
 void wz_note_launch(const void* func, dim3 grid, dim3 block, size_t lds);
 #define WZ_LAUNCH(kern, grid, block, lds, s, ...) do { wz_note_launch(reinterpret_cast<const void*>(kern), grid, block, lds); \
         for (int _wz_r = 0; _wz_r < wz_launch_repeat; ++_wz_r) hipLaunchKernelGGL(kern, grid, block, lds, s, __VA_ARGS__); } while (0)
+#define WZ_LAUNCH_DESCRIBED(d, params, s) do { wz_note_launch((d).func, (d).grid, (d).block, (d).lds); \
+        for (int _wz_r = 0; _wz_r < wz_launch_repeat; ++_wz_r) (void)hipLaunchKernel((d).func, (d).grid, (d).block, params, (d).lds, s); } while (0)
 #ifdef __HIPCC__
 struct WzLaneStamp {
     unsigned long long* p;
@@ -262,20 +265,56 @@ struct WzLaneStamp {
 #endif
 #else
 #define WZ_LAUNCH(...) do { for (int _wz_r = 0; _wz_r < wz_launch_repeat; ++_wz_r) hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+#define WZ_LAUNCH_DESCRIBED(d, params, s) \
+    do { for (int _wz_r = 0; _wz_r < wz_launch_repeat; ++_wz_r) (void)hipLaunchKernel((d).func, (d).grid, (d).block, params, (d).lds, s); } while (0)
 #define WZ_LANE_STAMP(ptr) do { } while (0)
 #endif
 // hp: the input tensor is a hi + lo pair (8 halves per pixel: r g b 0 | r g b 0)
 #define WZ_DESC_PACK 16
 struct WzDescPack { WzFrameDesc d[WZ_DESC_PACK]; };   // frame descriptors as kernel arguments (512 bytes)
+// The resize launch, described once (k_preprocess.hip).  WzPreArgs: the kernels' six arguments in parameter order, and the void*[6] over
+// them.  WzPreLaunch: which kernel takes them, at what shape.  wz_launch_preprocess launches from the two; the replay of a captured batch
+// rewrites the resize node's arguments from the same two (wz_engine.hip: run_batch).
+struct WzPreArgs {
+    const WzFrameDesc* frames;
+    WzDescPack pack;
+    int size;
+    half_t* out;
+    WzFrameDesc* keep;
+    int flags;
+    void* kp[6];
+    // by_value (host descriptors, taken when n <= WZ_DESC_PACK): they travel in `pack` and the kernel is given no `frames`
+    void set(const WzFrameDesc* d_frames, const WzFrameDesc* by_value, int n, int size_, half_t* out_, WzFrameDesc* keep_, int flags_) {
+        const bool packed = by_value && n <= WZ_DESC_PACK;
+        memset(&pack, 0, sizeof(pack));
+        if (packed) memcpy(pack.d, by_value, sizeof(WzFrameDesc) * n);
+        frames = packed ? nullptr : d_frames;
+        size = size_; out = out_; keep = keep_; flags = flags_;
+    }
+    void** params() {
+        kp[0] = &frames; kp[1] = &pack; kp[2] = &size; kp[3] = &out; kp[4] = &keep; kp[5] = &flags;
+        return kp;
+    }
+};
+struct WzPreLaunch {
+    const void* func;   // the kernel's host-side address (also what finds its node in a captured graph)
+    dim3 grid, block;
+    unsigned lds;
+    int flags;          // the kernels' last argument
+    hipKernelNodeParams node_params(WzPreArgs& a) const {
+        hipKernelNodeParams kp;
+        memset(&kp, 0, sizeof(kp));
+        kp.func = const_cast<void*>(func); kp.gridDim = grid; kp.blockDim = block; kp.sharedMemBytes = lds; kp.kernelParams = a.params();
+        return kp;
+    }
+};
+// rows_lds > 0: the row-staged form of the kernel (one workgroup per output row, `rows_lds` bytes of LDS = wz_preprocess_rows_lds(widest frame))
+WzPreLaunch wz_preprocess_launch(bool hp, int n, int size, int rows_lds, bool half_pixel);
 // keep, half_pixel, by_value (host descriptors to pass as kernel arguments when n <= WZ_DESC_PACK): see k_preprocess.hip
 void wz_launch_preprocess(const WzFrameDesc* d_frames, int n, int size, half_t* out, hipStream_t s, bool hp = false,
                           WzFrameDesc* keep = nullptr, bool half_pixel = false, const WzFrameDesc* by_value = nullptr, int rows_lds = 0);
-// rows_lds > 0: the row-staged form of the kernel (one workgroup per output row, `rows_lds` bytes of LDS = wz_preprocess_rows_lds(widest frame))
 size_t wz_preprocess_rows_lds(int max_w);
 size_t wz_preprocess_rows_need(int w, int fmt);   // LDS bytes of one output row of a frame `w` wide in a 10-bit format (the host's rule: wz_engine.hip: rows_fit)
-int wz_preprocess_flags(bool half_pixel, int rows_lds);   // the resize kernels' last argument (k_preprocess.hip)
-int wz_preprocess_rows_threads();
-const void* wz_preprocess_func(bool hp, bool rows = false);   // the kernel's host-side address (to find its node in a captured graph)
 void wz_launch_stem(const half_t* in, const float* w, const float* bias, half_t* out, int n, int hin, int win,
                     int hout, int wout, int pad_t, int pad_l, hipStream_t s);
 void wz_launch_dw(const half_t* in, const half_t* w, const float* bias, half_t* out, int n, int hin, int win,

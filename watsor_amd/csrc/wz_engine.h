@@ -2,7 +2,13 @@
 // filters, the batch around the network), wz_network.hip (what a batch launches for the engine's ops: enqueue_network and its
 // load-time twins) and wz_tiles.hip (tiled, gated and tiled frame-table detection).  Nothing here is part of the C ABI: these
 // functions keep their C++ names.
+//
+// Ownership: every block of device or page-locked memory is a DevBlock / MappedBlock member of what uses it -- the engine, a lane, a
+// camera, a lane's tile / gate / motion share -- and frees itself with it; what several parts share on purpose is one block handed out
+// with Carve.  A lane's captured graphs are GraphForm records, which destroy their HIP objects.  State is built aside and moved in.
+// wz_destroy lists nothing: it synchronises, destroys the events and the streams, and deletes the engine.
 #pragma once
+#include <chrono>
 #include <map>
 #include <string>
 #include <utility>
@@ -45,9 +51,16 @@ struct MappedBlock {
     MappedBlock(MappedBlock&& o) noexcept : h(o.h), d(o.d) { o.h = o.d = nullptr; }
     MappedBlock& operator=(MappedBlock&& o) noexcept { std::swap(h, o.h); std::swap(d, o.d); return *this; }
     ~MappedBlock() { if (h) (void)hipHostFree(h); }
-    hipError_t alloc(size_t n) {
-        const hipError_t err = hipHostMalloc((void**)&h, sizeof(T) * n, hipHostMallocMapped);
-        return err == hipSuccess ? hipHostGetDevicePointer((void**)&d, h, 0) : err;
+    // mapped (hipHostMallocMapped): the device must see the block.  Not mapped (hipHostMallocDefault): d is its device view where the
+    // platform gives one, else null
+    hipError_t alloc(size_t n, bool mapped = true) {
+        hipError_t err = hipHostMalloc((void**)&h, sizeof(T) * n, mapped ? hipHostMallocMapped : hipHostMallocDefault);
+        if (err != hipSuccess) return err;
+        err = hipHostGetDevicePointer((void**)&d, h, 0);
+        if (err == hipSuccess || mapped) return err;
+        (void)hipGetLastError();
+        d = nullptr;
+        return hipSuccess;
     }
 };
 // A block handed out in typed parts, in order, each at a boundary of `align` bytes (8: every part here holds pointers or 32-bit words).
@@ -75,6 +88,30 @@ struct MetaBlock {
         const hipError_t err = block.alloc(h.carve(nullptr, nb));
         if (err == hipSuccess) { h.carve(block.h, nb); m.carve(block.d, nb); }
         return err;
+    }
+};
+
+// Everything a lane knows about one graph key (batch size | row-staged resize kernel << 16).  Owns its HIP objects; move-only.
+struct GraphForm {
+    hipGraphExec_t exec = nullptr;       // the instantiated graph; null: nothing was captured under the key (yet)
+    hipGraph_t src = nullptr;            // the captured graph itself, kept where one of its node handles is ...
+    hipGraphNode_t pre_node = nullptr;   // ... the resize kernel's node: its arguments carry the frame descriptors and are rewritten
+                                         // before every replay, if it takes them by value
+    int nodes = 0;                       // nodes of the captured graph (kernels + the descriptor copy)
+    int post_mode = 0;                   // development library: decode_fused | cands_listed << 1 of the batch enqueued or captured under the key
+    std::vector<WzLaunchNote> notes;     // stamps build: what was launched, in order (grid, block, LDS, kernel)
+    bool noted = false;                  // ... taken: at capture, or at the key's first kernel-by-kernel enqueue
+    WzPreArgs args;                      // storage behind the node's kernelParams
+    GraphForm() = default;
+    GraphForm(GraphForm&& o) noexcept { *this = std::move(o); }
+    GraphForm& operator=(GraphForm&& o) noexcept {   // (o takes the old objects with it)
+        std::swap(exec, o.exec); std::swap(src, o.src); std::swap(pre_node, o.pre_node); std::swap(nodes, o.nodes);
+        std::swap(post_mode, o.post_mode); notes.swap(o.notes); std::swap(noted, o.noted);
+        return *this;
+    }
+    ~GraphForm() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (src) (void)hipGraphDestroy(src);
     }
 };
 
@@ -175,13 +212,12 @@ struct wz_engine {
     int wide_cus = 128;        // CUs the wide head kernel's K slices are sized for when several lanes are in flight (WZ_WIDE_CUS)
     int num_cus = 256;         // compute units of the device (the wide head kernel sizes its K slices for one round over them)
 
-    uint8_t* d_weights = nullptr;
-    half_t* d_zeros = nullptr;               // 4 KiB of zeros
-    unsigned long long* d_mbdbg = nullptr;   // WZ_MB_DEBUG=1: [n_ops][16] phase timestamps of the fused-block kernels
+    DevBlock<uint8_t> d_weights;
+    DevBlock<half_t> d_zeros;                // 4 KiB of zeros
+    DevBlock<unsigned long long> d_mbdbg;    // WZ_MB_DEBUG=1: [n_ops][16] phase timestamps of the fused-block kernels
     std::vector<int> mb_groups;
-    float* d_anchors = nullptr;
-    uint8_t* d_frames = nullptr;             // staging for host frames [max_batch][max_w*max_h*3]
-    size_t frame_stride = 0;
+    DevBlock<float> d_anchors;
+    size_t frame_stride = 0;                 // bytes of one frame of a lane's staging area (max_w * max_h * 3, rounded up to 256)
     WzPostConsts pc;
     size_t post_scratch_bytes = 0;
     size_t ws_bytes = 0;       // split-K / channel-group workspace per lane: 32 MiB per frame of max_batch, at least 64 MiB (the heads'
@@ -194,30 +230,30 @@ struct wz_engine {
     struct Lane {
         hipStream_t stream = nullptr;
         bool owns_stream = false;            // false: the stream belongs to lane (index mod n_streams)
-        std::vector<void*> bufs;             // owned activation buffers
+        std::vector<DevBlock<uint8_t>> bufs; // the activation buffers
         std::vector<half_t*> tptr;           // tensor index -> device pointer
-        float* d_box_enc = nullptr;
-        float* d_logits = nullptr;
-        float* d_ws = nullptr;
+        DevBlock<float> d_box_enc, d_logits, d_ws;
         int launch_failed = 0;               // op index + 1 of a block no kernel took at launch time (enqueue_network), else 0
         bool decode_fused = false;           // set by enqueue_network: the grouped head reduce decoded the boxes
         bool cands_listed = false;           // ... and listed the candidates of the NMS kernel's first band
-        std::map<int, int> post_modes;       // development library: graph key -> decode_fused | cands_listed << 1 of the batch enqueued or captured under it
-        uint8_t* d_frames = nullptr;         // staging for host frames of this lane [max_batch][frame_stride] (lazy)
-        std::map<int, int> graph_nodes;      // batch size -> nodes of the captured graph (kernels + the descriptor copy)
-        WzPostBuffers post;
-        void* d_post_scratch = nullptr;      // post.hint, post.hint_logit, post.cbits
-        WzFrameDesc* h_desc = nullptr;       // pinned
-        WzFrameDesc* h_desc_dev = nullptr;   // ... and its address as the device sees it (nullptr: not mapped)
+        DevBlock<uint8_t> d_frames;          // staging for host frames of this lane [max_batch][frame_stride]
+        WzPostBuffers post;                  // what the kernels take: views of the blocks below (and of d_box_enc, d_logits, the engine's anchors)
+        DevBlock<uint32_t> d_post_scratch;   // post.hint, post.hint_logit, post.cbits
+        DevBlock<float> d_boxes, d_det_boxes, d_det_scores;
+        DevBlock<uint8_t> d_valid;
+        DevBlock<int32_t> d_det_classes, d_det_num;
+        DevBlock<unsigned long long> d_dbg;
+        MappedBlock<WzFrameDesc> desc;       // page-locked, not mapped: desc.d is null where the device does not see it
+        // the descriptors in device memory.  WZ_LANE_STAMPS builds (wz_common.h): the lane's launch blocks [WZ_STAMP_SLOTS][WZ_STAMP_WORDS], the
+        // resize kernel's block and the descriptors behind it are ONE block, carved (lane_parts)
+        DevBlock<uint8_t> d_parts;
         WzFrameDesc* d_desc = nullptr;
-        wz_detection_t* d_rows = nullptr;
-        uint8_t* d_pass = nullptr;
-        wz_detection_t* h_rows = nullptr;    // pinned, device-mapped: wz_k_rows writes it directly
-        uint8_t* h_pass = nullptr;
-        wz_detection_t* m_rows = nullptr;    // device addresses of h_rows / h_pass
-        uint8_t* m_pass = nullptr;
-        uint32_t* h_status = nullptr;        // pinned, device-mapped: one word per frame, non-zero = the frame's rows may be short (wz_k_nms)
-        uint32_t* m_status = nullptr;
+        unsigned long long* d_stamps = nullptr;
+        unsigned long long* d_stamps_pre = nullptr;
+        MappedBlock<wz_detection_t> hrows;   // page-locked, device-mapped: the NMS kernel writes the rows straight into it ...
+        MappedBlock<uint8_t> hpass;          // ... and their pass bytes
+        MappedBlock<uint32_t> hstatus;       // one word per frame, non-zero = the frame's rows may be short (wz_k_nms)
+        MappedBlock<unsigned long long> hstamps;   // stamps build: the page-locked pairs the host reads
         std::vector<int32_t> bound_idx;      // frame-table entries of the batch in flight (empty: not a bound batch)
         std::vector<int32_t> bound_src;      // the last tiled or gated bound batch accepted on this lane (development library: the last bound batch of any kind): 1 = frame i was read in place, 0 = staged
         TileLane tile;
@@ -227,26 +263,9 @@ struct wz_engine {
         int n = 0;
         bool rows = false;                       // the batch being enqueued runs the row-staged resize kernel (a frame of it is read in place)
         int key = 0;                             // graph key of the batch in flight: batch size | rows << 16
-        std::map<int, hipGraphExec_t> graphs;    // key = batch size | (row-staged resize kernel) << 16
-        std::map<int, hipGraph_t> graph_src;     // the captured graph itself, kept where one of its node handles is
-        std::map<int, hipGraphNode_t> pre_nodes; // ... and the resize kernel's node in that graph (its arguments carry the frame
-                                                 // descriptors and are rewritten before every replay), if it takes them by value
-        // WZ_LANE_STAMPS builds (wz_common.h): the lane's launch blocks [WZ_STAMP_SLOTS][WZ_STAMP_WORDS], the resize kernel's block and the
-        // descriptors behind it in ONE allocation; the page-locked pairs the host reads; launches stamped so far in the batch being enqueued
-        unsigned char* d_stamp_raw = nullptr;
-        unsigned long long* d_stamps = nullptr;
-        unsigned long long* d_stamps_pre = nullptr;
-        unsigned long long* h_stamps = nullptr;
-        unsigned long long* m_stamps = nullptr;
-        int stamp_next = 1;
+        std::map<int, GraphForm> forms;          // graph key -> its record
+        int stamp_next = 1;                      // stamps build: launches stamped so far in the batch being enqueued
         bool lone = false;                       // the batch being enqueued goes kernel by kernel because the other lanes are idle (run_batch)
-        std::map<int, std::vector<WzLaunchNote>> launch_notes;   // graph key -> what was launched, in order (grid, block, LDS, kernel)
-        WzDescPack pack;                         // storage behind that node's kernelParams
-        const WzFrameDesc* pre_frames = nullptr;
-        int pre_size = 0, pre_half_pixel = 0;
-        half_t* pre_out = nullptr;
-        WzFrameDesc* pre_keep = nullptr;
-        void* pre_kp[6];
     };
     Lane lanes[WZ_SLOTS];
     int n_lanes = 4;   // default; WZ_LANES overrides (1..WZ_SLOTS)
@@ -272,10 +291,10 @@ struct wz_engine {
     std::vector<BoundTiles> bound_tiles;   // [bound.size()] or empty
 
     std::vector<WzCamFilter> h_cams;
-    WzCamFilter* d_cams = nullptr;
-    std::vector<int32_t*> cam_sat;
-    wz_detection_t* d_tmp_rows = nullptr;
-    uint8_t* d_tmp_pass = nullptr;
+    DevBlock<WzCamFilter> d_cams;
+    std::vector<DevBlock<int32_t>> cam_sat;   // the summed-area tables of the cameras' zone masks (WzCamFilter::sat points into them)
+    DevBlock<wz_detection_t> d_tmp_rows;      // one frame's rows and pass bytes in device memory (wz_filter_rows, wz_stage_rows)
+    DevBlock<uint8_t> d_tmp_pass;
 
     // gated tiled detection: a camera's tile layout and its state in device memory (wz_set_camera_tiles); empty until a camera is set
     struct GateCam {
@@ -354,6 +373,7 @@ const char* fmt_refusal(int w, int h, int fmt);
 int fill_desc(wz_engine* e, int slot, int n, const uint8_t* const* d_rgb, const int* w, const int* h, const int* fmt, const int* cam);
 int run_batch(wz_engine* e, int slot, int n);
 int stage_frame(wz_engine* e, Lane& L, int i, const uint8_t* host, uint64_t bytes, const uint8_t** where);
+int collect_timed(wz_engine* e, int n, wz_detection_t* const* out, uint8_t* const* pass, float* ms, std::chrono::steady_clock::time_point t0);
 const uint8_t* device_view(wz_engine* e, const uint8_t* host, uint64_t bytes);
 bool read_in_place(const wz_engine* e, int h);
 bool rows_fit(const wz_engine* e, int n, const int* w, const int* fmt);
@@ -362,6 +382,13 @@ hipError_t lane0_fill(wz_engine* e, void* dst, int value, size_t bytes);
 // ---- wz_tiles.hip, for wz_submit_bound: a batch with a tiled or gated entry ---------------------------------------------------------
 int submit_bound_tiles(wz_engine* e, int slot, int n, const int32_t* entries);
 
+// Why a call's lane or batch size is refused (wz_last_error is set, the code returned), or WZ_OK: the checks named in `checks`, in this order
+enum { BC_SLOT = 1, BC_N = 2 };
+static inline int batch_refusal(const wz_engine* e, int slot, int n, unsigned checks = BC_SLOT | BC_N) {
+    if ((checks & BC_SLOT) && (slot < 0 || slot >= e->n_lanes)) return wz_set_error(WZ_EINVAL, "slot %d out of range [0,%d)", slot, e->n_lanes);
+    if ((checks & BC_N) && (n < 1 || n > e->max_batch)) return wz_set_error(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
+    return WZ_OK;
+}
 // Why frame i of a call is refused (wz_last_error is set, the code returned), or WZ_OK: the checks named in `checks`, in this order.
 // what: "frame" | "frame-table entry"; p: the frame's pointer, null also when another pointer of the frame is; pf: its format word.
 enum { FC_PTR = 1, FC_FMT = 2, FC_LIMIT = 4, FC_CAM_ID = 8, FC_CAM_FILTER = 16 };
@@ -397,6 +424,5 @@ static inline void bound_gather(const wz_engine* e, int n, const int32_t* entrie
 static inline int bound_drain(wz_engine* e, int slot) {
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipEventSynchronize(e->lanes[slot].done));
-    if (!e->lanes[slot].d_frames) return wz_set_error(WZ_EINVAL, "wz_submit_bound: lane %d has no staging area", slot);
     return WZ_OK;
 }

@@ -1,9 +1,9 @@
 // Runtime + C ABI of libwatsor_hip.so (see include/watsor_hip.h for the contract of every entry point).
 //
-// One engine = one MI355X = one HIP stream.  A batch is one dependent chain of kernels
-// (pre-process -> ~70 conv ops -> post-process -> rows) captured once per (slot, batch size) into a
-// hipGraph and replayed; frame descriptors travel through a pinned host block that the graph's first
-// node copies to HBM, results come back through a pinned row block that its last nodes fill.
+// One engine = one MI355X = a few lanes (wz_engine.h).  A batch is one dependent chain of kernels
+// (pre-process -> ~70 conv ops -> post-process -> rows) captured once per (lane, batch size, resize form) into a
+// hipGraph and replayed; the frame descriptors travel as the resize kernel's arguments, rewritten in the captured node
+// before every replay, results come back through a page-locked row block that the last kernel fills.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -48,7 +48,6 @@ int wz_set_error(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
-static int (*const wz_fail)(int, const char*, ...) = wz_set_error;   // (this file's older name for it)
 
 // lane stamps (`make stamps` only): what the batch being enqueued launches is noted where run_batch points the sink
 #if WZ_LANE_STAMPS
@@ -75,20 +74,25 @@ static void enqueue_post(wz_engine* e, Lane& L, bool rows, int n, StageTimer* t,
     // with `rows` the NMS kernel also fills the Detection rows (straight into the lane's pinned, device-mapped host
     // block: no D2H copy node, no separate row kernel); the "post/rows" stage slot stays empty
 #if WZ_LANE_STAMPS
-    L.post.stamps_n = rows && L.m_stamps ? L.stamp_next : 0;   // launches stamped in front of the NMS kernel (launch 0 = the resize kernel)
-    L.post.stamps_host = rows && L.post.stamps_n ? L.m_stamps : nullptr;
+    L.post.stamps_n = rows && L.hstamps.d ? L.stamp_next : 0;   // launches stamped in front of the NMS kernel (launch 0 = the resize kernel)
+    L.post.stamps_host = rows && L.post.stamps_n ? L.hstamps.d : nullptr;
 #endif
     if (rows)
-        wz_launch_nms(L.post, e->pc, n, s, L.d_desc, e->d_cams, L.m_rows, L.m_pass, listed, L.m_status);
+        wz_launch_nms(L.post, e->pc, n, s, L.d_desc, e->d_cams, L.hrows.d, L.hpass.d, listed, L.hstatus.d);
     else
         wz_launch_nms(L.post, e->pc, n, s, nullptr, nullptr, nullptr, nullptr, listed);
     if (t) t->mark();
     if (rows && t) t->mark();
 }
 
-// everything between "descriptors are in h_desc[slot]" and "rows are in h_rows[slot]"
+// the resize launch of a batch of n on lane L: which kernel, its shape, its last argument (k_preprocess.hip)
+static WzPreLaunch pre_launch(const wz_engine* e, const Lane& L, int n) {
+    return wz_preprocess_launch(input_is_pair(e), n, (int)e->hdr.input_size, L.rows ? e->pre_rows_lds : 0, e->hdr.resize_mode == 1);
+}
+
+// everything between "descriptors are in desc.h" and "rows are in hrows.h"; F: the record of the batch's graph key
 // inner > 1 (profiling only): every kernel of the pre-processing and the network is enqueued `inner` times back to back
-static void enqueue_batch(wz_engine* e, Lane& L, int n, StageTimer* t, int inner = 1) {
+static void enqueue_batch(wz_engine* e, Lane& L, GraphForm& F, int n, StageTimer* t, int inner = 1) {
     hipStream_t s = L.stream;
     if (t) t->mark();   // "(empty)": two event records with nothing between them = the bracket's own cost
     // the descriptors: read by the resize kernel straight out of the lane's page-locked host block (and left in d_desc for the
@@ -96,33 +100,90 @@ static void enqueue_batch(wz_engine* e, Lane& L, int n, StageTimer* t, int inner
     // (by value: the descriptors are the resize kernel's arguments -- no copy, no PCIe read; batches of more than WZ_DESC_PACK frames
     // and WZ_DESC_ARGS=0 take one of the older routes)
     const bool by_value = e->desc_by_value && n <= WZ_DESC_PACK;
-    const bool zero_copy = !by_value && e->desc_zero_copy && L.h_desc_dev;
-    if (!by_value && !zero_copy) (void)hipMemcpyAsync(L.d_desc, L.h_desc, sizeof(WzFrameDesc) * n, hipMemcpyHostToDevice, s);
+    const bool zero_copy = !by_value && e->desc_zero_copy && L.desc.d;
+    if (!by_value && !zero_copy) (void)hipMemcpyAsync(L.d_desc, L.desc.h, sizeof(WzFrameDesc) * n, hipMemcpyHostToDevice, s);
     if (t) t->mark();
     wz_launch_repeat = inner;
     L.stamp_next = 1;   // (lane stamps: launch 0 is the resize kernel, whose block lies in front of the descriptors it leaves behind)
-    wz_launch_preprocess(zero_copy ? L.h_desc_dev : L.d_desc, n, (int)e->hdr.input_size, L.tptr[input_tensor_index(e)], s,
+    wz_launch_preprocess(zero_copy ? L.desc.d : L.d_desc, n, (int)e->hdr.input_size, L.tptr[input_tensor_index(e)], s,
                          input_is_pair(e), (zero_copy || by_value) ? L.d_desc : nullptr, e->hdr.resize_mode == 1,
-                         by_value ? L.h_desc : nullptr, L.rows ? e->pre_rows_lds : 0);
+                         by_value ? L.desc.h : nullptr, L.rows ? e->pre_rows_lds : 0);
     if (t) t->mark();
     enqueue_network(e, L, n, t);
     wz_launch_repeat = 1;
-#ifdef WZ_DEV_BUILD
-    L.post_modes[n | (L.rows ? 1 << 16 : 0)] = (L.decode_fused ? 1 : 0) | (L.cands_listed ? 2 : 0);   // (wz_debug_post_lane: a replayed graph keeps what it captured)
-#endif
+    F.post_mode = (L.decode_fused ? 1 : 0) | (L.cands_listed ? 2 : 0);   // (wz_debug_post_lane: a replayed graph keeps what it captured)
     enqueue_post(e, L, true, n, t, L.decode_fused, L.cands_listed);
+}
+// ... with what it launches noted in F, once per key (stamps build): at capture, or at the key's first kernel-by-kernel enqueue
+static void enqueue_noted(wz_engine* e, Lane& L, GraphForm& F, int n) {
+#if WZ_LANE_STAMPS
+    if (!F.noted) g_launch_sink = &F.notes;
+    F.noted = true;
+#endif
+    enqueue_batch(e, L, F, n, nullptr);
+#if WZ_LANE_STAMPS
+    g_launch_sink = nullptr;
+#endif
+}
+
+// a split-operand block no kernel took (the load-time check prepared batch 1 only): nothing may run on stale data
+static int launch_refusal(wz_engine* e, Lane& L, int n) {
+    const int op = L.launch_failed - 1;
+    L.launch_failed = 0;
+    return wz_set_error(WZ_EFORMAT, "no %s kernel took op %d (%s) at batch %d",
+                        e->ops[op].kind == WZ_OP_DWSEP ? "depthwise-separable" : "split-operand", op, e->ops[op].name, n);
+}
+
+// The graph of (lane, batch size, resize form): the batch captured, the resize kernel's node found in it where its arguments are this
+// batch's descriptors, the graph instantiated.  Built aside: F takes all of it or stays as it was.
+static int capture_form(wz_engine* e, Lane& L, int n, GraphForm& F) {
+    GraphForm fresh;
+    HIPCHK(hipStreamBeginCapture(L.stream, hipStreamCaptureModeThreadLocal));
+    L.lone = false;   // (a captured graph is what runs while the other lanes are busy)
+    enqueue_noted(e, L, fresh, n);
+    HIPCHK(hipStreamEndCapture(L.stream, &fresh.src));
+    if (L.launch_failed) return launch_refusal(e, L, n);
+    size_t nodes = 0;
+    if (hipGraphGetNodes(fresh.src, nullptr, &nodes) == hipSuccess) fresh.nodes = (int)nodes;
+    const bool by_value = e->desc_by_value && n <= WZ_DESC_PACK && nodes > 0;
+    if (by_value) {
+        std::vector<hipGraphNode_t> all(nodes);
+        const void* want = pre_launch(e, L, n).func;
+        if (hipGraphGetNodes(fresh.src, all.data(), &nodes) == hipSuccess)
+            for (size_t k = 0; k < nodes && !fresh.pre_node; ++k) {
+                hipGraphNodeType ty;
+                hipKernelNodeParams kp;
+                if (hipGraphNodeGetType(all[k], &ty) == hipSuccess && ty == hipGraphNodeTypeKernel &&
+                    hipGraphKernelNodeGetParams(all[k], &kp) == hipSuccess && kp.func == want)
+                    fresh.pre_node = all[k];
+            }
+        if (!fresh.pre_node) return wz_set_error(WZ_EHIP, "the resize kernel's node was not found in the captured graph");
+    }
+    HIPCHK(hipGraphInstantiate(&fresh.exec, fresh.src, nullptr, nullptr, 0));
+    if (!fresh.pre_node) {   // (a node handle lives as long as the graph it belongs to: without one the graph is not kept)
+        (void)hipGraphDestroy(fresh.src);
+        fresh.src = nullptr;
+    }
+    F = std::move(fresh);
+    return WZ_OK;
+}
+
+// this batch's descriptors into the arguments of the captured resize node, then the replay
+static int replay_form(wz_engine* e, Lane& L, int n, GraphForm& F) {
+    if (F.pre_node) {
+        const WzPreLaunch d = pre_launch(e, L, n);
+        F.args.set(nullptr, L.desc.h, n, (int)e->hdr.input_size, L.tptr[input_tensor_index(e)], L.d_desc, d.flags);
+        const hipKernelNodeParams kp = d.node_params(F.args);
+        HIPCHK(hipGraphExecKernelNodeSetParams(F.exec, F.pre_node, &kp));
+    }
+    HIPCHK(hipGraphLaunch(F.exec, L.stream));
+    return WZ_OK;
 }
 
 int run_batch(wz_engine* e, int slot, int n) {
     Lane& L = e->lanes[slot];
-    auto failed = [&]() -> int {   // a split-operand block no kernel took (the load-time check prepared batch 1 only): nothing may run on stale data
-        const int op = L.launch_failed - 1;
-        L.launch_failed = 0;
-        return wz_fail(WZ_EFORMAT, "no %s kernel took op %d (%s) at batch %d",
-                       e->ops[op].kind == WZ_OP_DWSEP ? "depthwise-separable" : "split-operand", op, e->ops[op].name, n);
-    };
-    const int key = n | (L.rows ? 1 << 16 : 0);
-    L.key = key;
+    L.key = n | (L.rows ? 1 << 16 : 0);
+    GraphForm& F = L.forms[L.key];
     bool graph = e->use_graph;
     if (graph && e->graph_adaptive) {
         // a LONE batch -- nothing in flight on any other lane -- is launched kernel by kernel: the GPU starts on the first kernel while the host issues the
@@ -133,103 +194,19 @@ int run_batch(wz_engine* e, int slot, int n) {
             if (li != slot && e->lanes[li].done && hipEventQuery(e->lanes[li].done) == hipErrorNotReady) graph = true;
         (void)hipGetLastError();
     }
-    // the captured graph of (lane, batch size, resize form): captured and instantiated the first time the key is seen -- also when that first batch itself
-    // goes kernel by kernel (adaptive launch): the several ms of capture + instantiation then land on the first batch of a size, not on the first moment
-    // another lane happens to be busy
-    auto ensure_graph = [&]() -> int {
-        if (L.graphs.count(key)) return WZ_OK;
-        hipGraph_t g = nullptr;
-        HIPCHK(hipStreamBeginCapture(L.stream, hipStreamCaptureModeThreadLocal));
-#if WZ_LANE_STAMPS
-        L.launch_notes[key].clear();
-        g_launch_sink = &L.launch_notes[key];
-#endif
-        L.lone = false;   // (a captured graph is what runs while the other lanes are busy)
-        enqueue_batch(e, L, n, nullptr);
-#if WZ_LANE_STAMPS
-        g_launch_sink = nullptr;
-#endif
-        HIPCHK(hipStreamEndCapture(L.stream, &g));
-        if (L.launch_failed) {
-            (void)hipGraphDestroy(g);
-            return failed();
-        }
-        size_t nodes = 0;
-        if (hipGraphGetNodes(g, nullptr, &nodes) == hipSuccess) L.graph_nodes[key] = (int)nodes;
-        if (e->desc_by_value && n <= WZ_DESC_PACK && nodes > 0) {   // the resize kernel's node: its arguments are this batch's descriptors
-            std::vector<hipGraphNode_t> all(nodes);
-            const void* want = wz_preprocess_func(input_is_pair(e), L.rows);
-            if (hipGraphGetNodes(g, all.data(), &nodes) == hipSuccess)
-                for (size_t k = 0; k < nodes; ++k) {
-                    hipGraphNodeType ty;
-                    hipKernelNodeParams kp;
-                    if (hipGraphNodeGetType(all[k], &ty) == hipSuccess && ty == hipGraphNodeTypeKernel &&
-                        hipGraphKernelNodeGetParams(all[k], &kp) == hipSuccess && kp.func == want) {
-                        L.pre_nodes[key] = all[k];
-                        break;
-                    }
-                }
-            if (!L.pre_nodes.count(key)) {
-                (void)hipGraphDestroy(g);
-                return wz_fail(WZ_EHIP, "the resize kernel's node was not found in the captured graph");
-            }
-        }
-        hipGraphExec_t ge = nullptr;
-        HIPCHK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-        if (L.pre_nodes.count(key)) L.graph_src[key] = g;   // (the node handle lives as long as the graph it belongs to)
-        else (void)hipGraphDestroy(g);
-        L.graphs.emplace(key, ge);
-        return WZ_OK;
-    };
-    if (graph || (e->use_graph && !L.graphs.count(key))) {
-        const int rc = ensure_graph();
-        if (rc != WZ_OK) return rc;
-    }
+    // captured and instantiated the first time the key is seen -- also when that first batch itself goes kernel by kernel (adaptive launch): the several
+    // ms of capture + instantiation then land on the first batch of a size, not on the first moment another lane happens to be busy
+    if (e->use_graph && !F.exec) WZCHK(capture_form(e, L, n, F));
     if (graph) {
-        auto it = L.graphs.find(key);
-        auto pn = L.pre_nodes.find(key);
-        if (pn != L.pre_nodes.end()) {   // this batch's descriptors into the node's arguments
-            memset(&L.pack, 0, sizeof(L.pack));
-            memcpy(L.pack.d, L.h_desc, sizeof(WzFrameDesc) * n);
-            L.pre_frames = nullptr;
-            L.pre_size = (int)e->hdr.input_size;
-            L.pre_out = L.tptr[input_tensor_index(e)];
-            L.pre_keep = L.d_desc;
-            L.pre_half_pixel = wz_preprocess_flags(e->hdr.resize_mode == 1, L.rows ? e->pre_rows_lds : 0);
-            L.pre_kp[0] = &L.pre_frames; L.pre_kp[1] = &L.pack; L.pre_kp[2] = &L.pre_size;
-            L.pre_kp[3] = &L.pre_out; L.pre_kp[4] = &L.pre_keep; L.pre_kp[5] = &L.pre_half_pixel;
-            hipKernelNodeParams kp;
-            memset(&kp, 0, sizeof(kp));
-            kp.func = const_cast<void*>(wz_preprocess_func(input_is_pair(e), L.rows));
-            if (L.rows) {
-                kp.gridDim = dim3((unsigned)L.pre_size, n);
-                kp.blockDim = dim3(wz_preprocess_rows_threads());
-                kp.sharedMemBytes = (unsigned)e->pre_rows_lds;
-            } else {
-                kp.gridDim = dim3(((unsigned)L.pre_size * L.pre_size + 255) / 256, n);
-                kp.blockDim = dim3(256);
-            }
-            kp.kernelParams = L.pre_kp;
-            HIPCHK(hipGraphExecKernelNodeSetParams(it->second, pn->second, &kp));
-        }
-        HIPCHK(hipGraphLaunch(it->second, L.stream));
+        WZCHK(replay_form(e, L, n, F));
     } else {
-#if WZ_LANE_STAMPS
-        if (!L.launch_notes.count(key)) {   // (what was launched: also without a captured graph -- WZ_GRAPH=0, one lane)
-            L.launch_notes[key].clear();
-            g_launch_sink = &L.launch_notes[key];
-        }
-#endif
         L.lone = true;    // kernel by kernel: the other lanes are idle (adaptive launch), or the process runs without graphs (latency schedule, WZ_GRAPH=0)
-        enqueue_batch(e, L, n, nullptr);
+        enqueue_noted(e, L, F, n);   // (what was launched: also without a captured graph -- WZ_GRAPH=0, one lane)
         L.lone = false;
-#if WZ_LANE_STAMPS
-        g_launch_sink = nullptr;
-#endif
         HIPCHK(hipGetLastError());
         if (L.launch_failed) {
             (void)hipStreamSynchronize(L.stream);
-            return failed();
+            return launch_refusal(e, L, n);
         }
     }
     HIPCHK(hipEventRecord(L.done, L.stream));
@@ -260,27 +237,27 @@ bool wz_latency_schedule() {
     return s == WZ_SCHEDULE_LATENCY;
 }
 extern "C" int wz_set_schedule(int schedule) {
-    if (schedule != WZ_SCHEDULE_THROUGHPUT && schedule != WZ_SCHEDULE_LATENCY) return wz_fail(WZ_EINVAL, "wz_set_schedule: unknown schedule %d", schedule);
+    if (schedule != WZ_SCHEDULE_THROUGHPUT && schedule != WZ_SCHEDULE_LATENCY) return wz_set_error(WZ_EINVAL, "wz_set_schedule: unknown schedule %d", schedule);
     int expect = -1;
     if (g_schedule.compare_exchange_strong(expect, schedule) || expect == schedule) return WZ_OK;
-    return wz_fail(WZ_EINVAL, "wz_set_schedule: the launch shapes of this process were already fixed for the %s schedule (set it before the first wz_create)",
+    return wz_set_error(WZ_EINVAL, "wz_set_schedule: the launch shapes of this process were already fixed for the %s schedule (set it before the first wz_create)",
                    expect == WZ_SCHEDULE_LATENCY ? "latency" : "throughput");
 }
 extern "C" int wz_get_schedule(void) { return wz_latency_schedule() ? WZ_SCHEDULE_LATENCY : WZ_SCHEDULE_THROUGHPUT; }
 
 // "0000:c1:00.0" of a device: what /sys/bus/pci/devices/<id>/{numa_node,local_cpulist} are keyed by (watsor_amd/numa.py)
 extern "C" int wz_device_pci_bus_id(int device, char* buf, int buflen) {
-    if (!buf || buflen < 16) return wz_fail(WZ_EINVAL, "wz_device_pci_bus_id: buffer of at least 16 bytes expected");
+    if (!buf || buflen < 16) return wz_set_error(WZ_EINVAL, "wz_device_pci_bus_id: buffer of at least 16 bytes expected");
     if (hipDeviceGetPCIBusId(buf, buflen, device) != hipSuccess) {
         (void)hipGetLastError();
-        return wz_fail(WZ_ENODEV, "no HIP device %d", device);
+        return wz_set_error(WZ_ENODEV, "no HIP device %d", device);
     }
     return WZ_OK;
 }
 
 extern "C" int wz_device_name_of(int device, char* buf, int buflen) {
     hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, device) != hipSuccess) return wz_fail(WZ_ENODEV, "no HIP device %d", device);
+    if (hipGetDeviceProperties(&p, device) != hipSuccess) return wz_set_error(WZ_ENODEV, "no HIP device %d", device);
     snprintf(buf, buflen, "%s (%s)", p.name, p.gcnArchName);
     return WZ_OK;
 }
@@ -319,38 +296,38 @@ static bool slice_op_ok(const wz_engine* e, const WzOpDesc& op) {
 
 static int load_blob(wz_engine* e, const char* path) {
     FILE* f = fopen(path, "rb");
-    if (!f) return wz_fail(WZ_ENOENT, "engine file not found: %s", path);
+    if (!f) return wz_set_error(WZ_ENOENT, "engine file not found: %s", path);
     fseek(f, 0, SEEK_END);
     long sz = ftell(f);
     fseek(f, 0, SEEK_SET);
     if (sz < (long)sizeof(WzBlobHeader)) {
         fclose(f);
-        return wz_fail(WZ_EFORMAT, "engine file %s is truncated", path);
+        return wz_set_error(WZ_EFORMAT, "engine file %s is truncated", path);
     }
     e->blob.resize(sz);
     size_t rd = fread(e->blob.data(), 1, sz, f);
     fclose(f);
-    if (rd != (size_t)sz) return wz_fail(WZ_EFORMAT, "short read on %s", path);
+    if (rd != (size_t)sz) return wz_set_error(WZ_EFORMAT, "short read on %s", path);
     memcpy(&e->hdr, e->blob.data(), sizeof(WzBlobHeader));
     const WzBlobHeader& h = e->hdr;
-    if (h.magic != WZ_MAGIC) return wz_fail(WZ_EFORMAT, "%s is not an mi355x engine (bad magic)", path);
+    if (h.magic != WZ_MAGIC) return wz_set_error(WZ_EFORMAT, "%s is not an mi355x engine (bad magic)", path);
     if (h.version == WZ_FORMAT_VERSION && (h.resize_mode > 1 || h.post_flags > 1))
-        return wz_fail(WZ_EFORMAT, "%s: unknown resize mode %u / post-processing flags %u", path, h.resize_mode, h.post_flags);
+        return wz_set_error(WZ_EFORMAT, "%s: unknown resize mode %u / post-processing flags %u", path, h.resize_mode, h.post_flags);
     if (h.version != WZ_FORMAT_VERSION)
-        return wz_fail(WZ_EFORMAT, "%s: engine format %u, runtime expects %u -- rebuild it with watsor_amd.engine",
+        return wz_set_error(WZ_EFORMAT, "%s: engine format %u, runtime expects %u -- rebuild it with watsor_amd.engine",
                        path, h.version, WZ_FORMAT_VERSION);
     if (h.total_bytes != (uint64_t)sz || (h.precision != 16 && h.precision != 32) || h.max_total > WZ_MAX_DETECTIONS || h.max_total < 1 ||
         h.num_classes > 4096 || h.n_ops == 0 || h.weights_off + h.weights_bytes > (uint64_t)sz ||
         h.tensors_off + (uint64_t)h.n_tensors * sizeof(WzTensorDesc) > (uint64_t)sz ||
         h.ops_off + (uint64_t)h.n_ops * sizeof(WzOpDesc) > (uint64_t)sz ||
         h.anchors_off + (uint64_t)h.num_anchors * 16 > (uint64_t)sz)
-        return wz_fail(WZ_EFORMAT, "%s: inconsistent engine header", path);
+        return wz_set_error(WZ_EFORMAT, "%s: inconsistent engine header", path);
     e->tensors = reinterpret_cast<const WzTensorDesc*>(e->blob.data() + h.tensors_off);
     e->ops = reinterpret_cast<const WzOpDesc*>(e->blob.data() + h.ops_off);
     for (uint32_t i = 0; i < h.n_ops; ++i) {
         const WzOpDesc& op = e->ops[i];
         if (op.kind < WZ_OP_STEM || op.kind > WZ_OP_DWSEP)   // (an unknown kind would otherwise run as a conv)
-            return wz_fail(WZ_EFORMAT, "%s: op %u (%s) has kind %d, which this runtime does not know", path, i, op.name, op.kind);
+            return wz_set_error(WZ_EFORMAT, "%s: op %u (%s) has kind %d, which this runtime does not know", path, i, op.name, op.kind);
         if (op.src < 0 || op.src >= (int)h.n_tensors || op.dst >= (int)h.n_tensors || op.res >= (int)h.n_tensors ||
             (op.out_mode == WZ_OUT_ACT && op.dst < 0) || op.w_off < 0 || (uint64_t)op.w_off >= h.weights_bytes ||
             (op.kind == WZ_OP_CONV && (op.n_pad % 32 != 0 || op.cin % 8 != 0 || op.n_pad < op.cout ||
@@ -366,19 +343,19 @@ static int load_blob(wz_engine* e, const char* path) {
               (op.cin0 != 0 && (op.cin0 % 8 != 0 || op.kc0 != (op.cin0 + 31) / 32 || op.nmid_pad % 16 != 0 ||
                                 op.nmid_pad < op.cmid || op.we_off < 0 || (uint64_t)op.we_off >= h.weights_bytes ||
                                 op.be_off < 0 || (uint64_t)op.be_off >= h.weights_bytes)))))
-            return wz_fail(WZ_EFORMAT, "%s: op %u (%s) is malformed", path, i, op.name);
+            return wz_set_error(WZ_EFORMAT, "%s: op %u (%s) is malformed", path, i, op.name);
         if (!slice_op_ok(e, op))
-            return wz_fail(WZ_EFORMAT, "%s: op %u (%s): malformed pool / 7x7 stem / channel-slice output", path, i, op.name);
+            return wz_set_error(WZ_EFORMAT, "%s: op %u (%s): malformed pool / 7x7 stem / channel-slice output", path, i, op.name);
         if (op.dst2 != 0) {
             const WzTensorDesc* t2 = (op.dst2 > 0 && op.dst2 <= (int64_t)h.n_tensors) ? &e->tensors[op.dst2 - 1] : nullptr;
             if (op.kind != WZ_OP_MBCONV || !t2 || op.cin0 <= 0 || t2->h != op.hin || t2->w != op.win ||
                 t2->c != op.cmid || (t2->flags & WZ_TENSOR_HP) || op.dst2 - 1 == op.dst || op.dst2 - 1 == op.src)
-                return wz_fail(WZ_EFORMAT, "%s: op %u (%s): malformed second output", path, i, op.name);
+                return wz_set_error(WZ_EFORMAT, "%s: op %u (%s): malformed second output", path, i, op.name);
         }
         if (op.kind == WZ_OP_MBCONV && h.precision != 16)
-            return wz_fail(WZ_EFORMAT, "%s: fused blocks exist for the fp16 engine only", path);
+            return wz_set_error(WZ_EFORMAT, "%s: fused blocks exist for the fp16 engine only", path);
         if (h.precision == 32 && ((op.kind == WZ_OP_CONV && op.cin % 4 != 0) || (op.kind == WZ_OP_DW && op.cin % 4 != 0)))
-            return wz_fail(WZ_EFORMAT, "%s: op %u (%s) is malformed", path, i, op.name);
+            return wz_set_error(WZ_EFORMAT, "%s: op %u (%s) is malformed", path, i, op.name);
         if (op.kind == WZ_OP_MBCONV && (op.flags & WZ_OPF_HP)) {
             if (!(e->tensors[op.src].flags & WZ_TENSOR_HP) || (op.res >= 0 && op.res != op.src) ||
                 ((op.flags & WZ_OPF_HP_OUT) != 0) != ((e->tensors[op.dst].flags & WZ_TENSOR_HP) != 0) ||
@@ -386,13 +363,13 @@ static int load_blob(wz_engine* e, const char* path) {
                 (!(op.flags & WZ_OPF_DUP_OUT) && e->tensors[op.dst].c != op.cout) ||
                 op.we_lo_off <= 0 || (uint64_t)op.we_lo_off >= h.weights_bytes || op.w_lo_off <= 0 ||
                 (uint64_t)op.w_lo_off >= h.weights_bytes || (op.stem && e->tensors[op.src].c != 4))
-                return wz_fail(WZ_EFORMAT, "%s: op %u (%s): malformed split-operand block", path, i, op.name);
+                return wz_set_error(WZ_EFORMAT, "%s: op %u (%s): malformed split-operand block", path, i, op.name);
         } else if ((op.kind == WZ_OP_STEM || op.kind == WZ_OP_STEM7) && h.precision == 32 && (e->tensors[op.src].flags & WZ_TENSOR_HP) &&
                    !(op.dst >= 0 && (e->tensors[op.dst].flags & WZ_TENSOR_HP))) {
             // the fp32 program's stem reads the network input as a hi + lo pair (wz_k_stem_f32)
         } else if ((e->tensors[op.src].flags & WZ_TENSOR_HP) || (op.dst >= 0 && (e->tensors[op.dst].flags & WZ_TENSOR_HP)) ||
                    (op.res >= 0 && (e->tensors[op.res].flags & WZ_TENSOR_HP))) {
-            return wz_fail(WZ_EFORMAT, "%s: op %u (%s) touches a pair tensor but is not a split-operand block", path, i, op.name);
+            return wz_set_error(WZ_EFORMAT, "%s: op %u (%s) touches a pair tensor but is not a split-operand block", path, i, op.name);
         } else if (op.kind == WZ_OP_DWSEP) {
             // every bound the kernel indexes by: the tensors it reads and writes, both weight blocks; the shapes it covers are
             // op_kernel_check's, evaluated with the predicate of the launch, so that an uncovered shape never reaches run_batch
@@ -405,11 +382,11 @@ static int load_blob(wz_engine* e, const char* path) {
                 out->w != op.wout || op.wd_off < 0 || (uint64_t)op.wd_off + 9ull * op.cin * 2 > wb || op.bd_off < 0 ||
                 (uint64_t)op.bd_off + 4ull * op.cin > wb || (uint64_t)op.w_off + 64ull * op.n_pad * op.kc > wb || op.b_off < 0 ||
                 (uint64_t)op.b_off + 4ull * op.n_pad > wb)
-                return wz_fail(WZ_EFORMAT, "%s: op %u (%s): malformed depthwise-separable layer", path, i, op.name);
+                return wz_set_error(WZ_EFORMAT, "%s: op %u (%s): malformed depthwise-separable layer", path, i, op.name);
         } else if (op.kind == WZ_OP_MBCONV && op.stem) {
             if (e->tensors[op.src].c != 4 || op.cin0 != 32 || op.kc0 != 1 || (e->tensors[op.src].h + 1) / 2 != op.hin ||
                 (e->tensors[op.src].w + 1) / 2 != op.win)
-                return wz_fail(WZ_EFORMAT, "%s: op %u (%s): malformed stem fusion", path, i, op.name);
+                return wz_set_error(WZ_EFORMAT, "%s: op %u (%s): malformed stem fusion", path, i, op.name);
         }
         WZCHK(op_kernel_check(e, op, path));   // the op is well-formed: is there a kernel for its shape?
     }
@@ -428,26 +405,9 @@ hipError_t lane0_fill(wz_engine* e, void* dst, int value, size_t bytes) {
     return err == hipSuccess ? hipStreamSynchronize(e->stream) : err;
 }
 
-extern "C" int wz_create(const char* engine_path, int device, int max_batch, int max_width, int max_height,
-                         wz_engine_t** out) {
-    if (!engine_path || !out || max_batch < 1 || max_batch > 4095 || max_width < 1 || max_height < 1)
-        return wz_fail(WZ_EINVAL, "wz_create: bad argument");
-    *out = nullptr;
-    wz_engine* e = new wz_engine();
-    int rc = load_blob(e, engine_path);
-    if (rc != WZ_OK) {
-        delete e;
-        return rc;
-    }
-    int ndev = wz_device_count();
-    if (device < 0 || device >= ndev) {
-        delete e;
-        return wz_fail(WZ_ENODEV, "HIP device %d not present (%d visible)", device, ndev);
-    }
-    e->device = device;
-    e->max_batch = max_batch;
-    e->max_w = max_width;
-    e->max_h = max_height;
+// what the environment says about an engine for frames up to max_width wide (the product library reads WZ_GRAPH, WZ_LANES, WZ_STREAMS and
+// the schedule; the development library its knobs as well), and the device's compute units
+static void read_options(wz_engine* e, int max_width) {
     const char* env;
     e->no_reuse = (env = wz_dev_getenv("WZ_NO_BUFFER_REUSE")) && atoi(env) != 0;
     // WZ_GRAPH=0|1 decides when set.  Unset: captured graphs under the throughput schedule WHILE ANOTHER LANE IS BUSY (a batch is handed over in 10.5 us: one
@@ -473,56 +433,143 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
     if (e->pre_rows_lds > 60 * 1024) e->pre_rows = false, e->host_read = 0;   // (frames wider than ~6 800 pixels need more LDS than a launch gets by default: the per-pixel form, staged)
     e->wide_T = (env = wz_dev_getenv("WZ_WIDE_T")) ? atoi(env) : 0;
     e->wide_min_m = (env = wz_dev_getenv("WZ_WIDE_MIN_M")) ? atoi(env) : 1;
-    {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
-            e->num_cus = cus;
-        e->wide_cus = wz_latency_schedule() ? e->num_cus : e->num_cus / 2;
-        if ((env = wz_dev_getenv("WZ_WIDE_CUS")) && atoi(env) > 0) e->wide_cus = atoi(env);
-    }
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
+        e->num_cus = cus;
+    e->wide_cus = wz_latency_schedule() ? e->num_cus : e->num_cus / 2;
+    if ((env = wz_dev_getenv("WZ_WIDE_CUS")) && atoi(env) > 0) e->wide_cus = atoi(env);
     if ((env = getenv("WZ_LANES")) && atoi(env) >= 1 && atoi(env) <= WZ_SLOTS) e->n_lanes = atoi(env);
     if ((env = getenv("WZ_STREAMS")) && atoi(env) >= 1 && atoi(env) <= WZ_SLOTS) e->n_streams = atoi(env);
     if (e->n_streams > e->n_lanes) e->n_streams = e->n_lanes;
+}
 
-#define CK(expr)                                                                                        \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess) {                                                                         \
-            wz_fail(WZ_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);       \
-            wz_destroy(e);                                                                              \
-            return WZ_EHIP;                                                                             \
-        }                                                                                               \
-    } while (0)
+// A lane's descriptors in device memory -- in the stamps build behind its launch blocks and the resize kernel's block: one block, carved
+static size_t lane_parts(Lane& L, const void* base, size_t nb) {
+    Carve c(base);
+#if WZ_LANE_STAMPS
+    L.d_stamps = c.take<unsigned long long>((size_t)WZ_STAMP_SLOTS * WZ_STAMP_WORDS);
+    L.d_stamps_pre = c.take<unsigned long long>(WZ_STAMP_PRE_BYTES / 8);
+#endif
+    L.d_desc = c.take<WzFrameDesc>(nb);
+    return c.bytes();
+}
 
-    CK(hipSetDevice(device));
+// Lane li of a new engine, whose streams exist: every block the lane owns, WzPostBuffers as views of them, its event
+static int build_lane(wz_engine* e, int li) {
+    Lane& L = e->lanes[li];
+    const WzBlobHeader& h = e->hdr;
+    const size_t nb = (size_t)e->max_batch;
+    // More lanes than streams (WZ_STREAMS, default 4 = what this stack runs side by side): lane i rides the stream of lane
+    // i mod streams, with buffers, graph and host blocks of its own -- the stream always has the next batch queued behind the one
+    // it is running, so the host's turnaround between a batch's end and the next submit is not idle time on that queue.
+    if (li >= e->n_streams) L.stream = e->lanes[li % e->n_streams].stream;   // (the first n_streams lanes own theirs)
+    // activation buffers: one per slot (tensors with disjoint lifetimes share), or one per tensor
+    std::vector<size_t> buf_bytes(e->no_reuse ? h.n_tensors : h.n_slots, 0);
+    for (uint32_t i = 0; i < h.n_tensors; ++i) {
+        size_t& b = buf_bytes[e->no_reuse ? i : (uint32_t)e->tensors[i].slot];
+        b = std::max(b, nb * tensor_frame_bytes(e, i) + 256);
+    }
+    L.bufs.resize(buf_bytes.size());
+    for (size_t k = 0; k < buf_bytes.size(); ++k) HIPCHK(L.bufs[k].alloc(buf_bytes[k]));
+    L.tptr.assign(h.n_tensors, nullptr);
+    for (uint32_t i = 0; i < h.n_tensors; ++i) L.tptr[i] = reinterpret_cast<half_t*>(L.bufs[e->no_reuse ? i : (uint32_t)e->tensors[i].slot].p);
+    HIPCHK(L.d_box_enc.alloc(nb * h.num_anchors * 4));
+    HIPCHK(L.d_logits.alloc(nb * h.num_anchors * h.num_classes));
+    HIPCHK(L.d_ws.alloc(e->ws_bytes / sizeof(float)));
+    HIPCHK(L.d_frames.alloc(e->frame_stride * nb));
+    WzPostBuffers& pb = L.post;
+    pb.box_enc = L.d_box_enc;
+    pb.logits = L.d_logits;
+    pb.anchors = e->d_anchors;
+    HIPCHK(L.d_boxes.alloc(nb * h.num_anchors * 4));
+    HIPCHK(L.d_valid.alloc(nb * h.num_anchors));
+    HIPCHK(L.d_post_scratch.alloc(e->post_scratch_bytes / 4));
+    pb.boxes = L.d_boxes;
+    pb.valid = L.d_valid;
+    pb.hint = L.d_post_scratch;
+    {   // first band of the NMS kernel: start at score 0.25 until the frame slot has a history
+        const uint32_t bin0 = 0x3E800000u >> 20;
+        std::vector<uint32_t> hint0(nb, bin0);
+        HIPCHK(lane0_copy(e, pb.hint, hint0.data(), hint0.size() * 4, hipMemcpyHostToDevice));
+        pb.hint_logit = reinterpret_cast<float*>(pb.hint + nb);
+        uint32_t sbits = bin0 << 20;
+        float s0;
+        memcpy(&s0, &sbits, 4);
+        const float l0 = logf(s0 / (1.0f - s0));   // wz_logit_floor(bin0), k_post.hip
+        std::vector<float> hl0(nb, l0 - 0.01f - 1e-3f * fabsf(l0));
+        HIPCHK(lane0_copy(e, pb.hint_logit, hl0.data(), hl0.size() * 4, hipMemcpyHostToDevice));
+        pb.cbits = reinterpret_cast<uint32_t*>(pb.hint_logit + nb);
+        HIPCHK(lane0_fill(e, pb.cbits, 0, nb * ((h.num_anchors * h.num_classes + 31) >> 5) * 4));
+    }
+    HIPCHK(L.d_det_boxes.alloc(nb * h.max_total * 4));
+    HIPCHK(L.d_det_scores.alloc(nb * h.max_total));
+    HIPCHK(L.d_det_classes.alloc(nb * h.max_total));
+    HIPCHK(L.d_det_num.alloc(nb));
+    HIPCHK(L.d_dbg.alloc(nb * 16));
+    HIPCHK(lane0_fill(e, L.d_dbg, 0, nb * 16 * 8));
+    pb.det_boxes = L.d_det_boxes;
+    pb.det_scores = L.d_det_scores;
+    pb.det_classes = L.d_det_classes;
+    pb.det_num = L.d_det_num;
+    pb.dbg = L.d_dbg;
+    HIPCHK(L.desc.alloc(nb, false));
+    HIPCHK(L.d_parts.alloc(lane_parts(L, nullptr, nb)));
+    lane_parts(L, L.d_parts, nb);
+#if WZ_LANE_STAMPS
+    {   // the launch blocks and the resize kernel's block: every pair starts as (entry = max, exit = 0)
+        std::vector<unsigned long long> init((size_t)(WZ_STAMP_SLOTS + 1) * WZ_STAMP_WORDS, 0ull);
+        for (size_t k = 0; k < init.size(); k += WZ_STAMP_WORDS)
+            for (int j = 0; j < 64; ++j) init[k + WZ_STAMP_ENTRY + j] = ~0ull;
+        HIPCHK(lane0_copy(e, L.d_parts, init.data(), init.size() * 8, hipMemcpyHostToDevice));
+        const size_t host_words = (size_t)(WZ_STAMP_SLOTS + 1 + nb) * 2;
+        HIPCHK(L.hstamps.alloc(host_words));
+        memset(L.hstamps.h, 0, host_words * 8);
+    }
+#endif
+    pb.stamps = L.d_stamps;
+    pb.stamps_pre = L.d_stamps_pre;
+    pb.stamps_host = nullptr;
+    pb.stamps_n = 0;
+    pb._stamps_pad = 0;
+    HIPCHK(L.hrows.alloc((size_t)WZ_MAX_DETECTIONS * nb));
+    HIPCHK(L.hpass.alloc((size_t)WZ_MAX_DETECTIONS * nb));
+    HIPCHK(L.hstatus.alloc(nb));
+    memset(L.hstatus.h, 0, sizeof(uint32_t) * nb);
+    HIPCHK(hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
+    return WZ_OK;
+}
+
+// the engine on its device: streams, the engine-wide blocks, the lanes, the stage names
+static int build_engine(wz_engine* e) {
+    const WzBlobHeader& h = e->hdr;
+    HIPCHK(hipSetDevice(e->device));
     char nm[256];
-    wz_device_name_of(device, nm, sizeof(nm));
+    wz_device_name_of(e->device, nm, sizeof(nm));
     e->name = nm;
     wz_post_init();
     network_prepare(e);   // kernel attributes of the fused-block kernels, on THIS device; what the op list says about every op
 
     // the lanes' streams before anything is copied: the set-up copies below ride lane 0's (lane0_copy)
     for (int li = 0; li < e->n_streams; ++li) {
-        CK(hipStreamCreateWithFlags(&e->lanes[li].stream, hipStreamNonBlocking));
+        HIPCHK(hipStreamCreateWithFlags(&e->lanes[li].stream, hipStreamNonBlocking));
         e->lanes[li].owns_stream = true;
     }
     e->stream = e->lanes[0].stream;
 
-    const WzBlobHeader& h = e->hdr;
-    CK(hipMalloc((void**)&e->d_weights, h.weights_bytes));
-    CK(lane0_copy(e, e->d_weights, e->blob.data() + h.weights_off, h.weights_bytes, hipMemcpyHostToDevice));
+    HIPCHK(e->d_weights.alloc(h.weights_bytes));
+    HIPCHK(lane0_copy(e, e->d_weights, e->blob.data() + h.weights_off, h.weights_bytes, hipMemcpyHostToDevice));
+    const char* env;
     if ((env = wz_dev_getenv("WZ_MB_DEBUG")) && atoi(env) != 0) {
-        CK(hipMalloc((void**)&e->d_mbdbg, (size_t)h.n_ops * 16 * 8));
-        CK(lane0_fill(e, e->d_mbdbg, 0, (size_t)h.n_ops * 16 * 8));
+        HIPCHK(e->d_mbdbg.alloc((size_t)h.n_ops * 16));
+        HIPCHK(lane0_fill(e, e->d_mbdbg, 0, (size_t)h.n_ops * 16 * 8));
         e->mb_groups.assign(h.n_ops, 0);
     }
-    CK(hipMalloc((void**)&e->d_zeros, 4096));
-    CK(lane0_fill(e, e->d_zeros, 0, 4096));
-    CK(hipMalloc((void**)&e->d_anchors, (size_t)h.num_anchors * 16));
-    CK(lane0_copy(e, e->d_anchors, e->blob.data() + h.anchors_off, (size_t)h.num_anchors * 16, hipMemcpyHostToDevice));
-    e->frame_stride = ((size_t)max_width * max_height * 3 + 255) & ~(size_t)255;
-    e->ws_bytes = std::max<size_t>((size_t)64 << 20, (size_t)max_batch * ((size_t)32 << 20));
-    CK(hipMalloc((void**)&e->d_frames, e->frame_stride * max_batch));
+    HIPCHK(e->d_zeros.alloc(4096 / sizeof(half_t)));
+    HIPCHK(lane0_fill(e, e->d_zeros, 0, 4096));
+    HIPCHK(e->d_anchors.alloc((size_t)h.num_anchors * 4));
+    HIPCHK(lane0_copy(e, e->d_anchors, e->blob.data() + h.anchors_off, (size_t)h.num_anchors * 16, hipMemcpyHostToDevice));
+    e->frame_stride = ((size_t)e->max_w * e->max_h * 3 + 255) & ~(size_t)255;
+    e->ws_bytes = std::max<size_t>((size_t)64 << 20, (size_t)e->max_batch * ((size_t)32 << 20));
 
     e->pc.num_anchors = h.num_anchors;
     e->pc.num_classes = h.num_classes;
@@ -533,145 +580,51 @@ extern "C" int wz_create(const char* engine_path, int device, int max_batch, int
     e->pc.scale_y = h.scale_y; e->pc.scale_x = h.scale_x; e->pc.scale_h = h.scale_h; e->pc.scale_w = h.scale_w;
     e->pc.clip_after = (h.post_flags & WZ_POSTF_CLIP_AFTER) ? 1 : 0;
     e->pc._pad = 0;
-    e->post_scratch_bytes = (size_t)max_batch * (2 + ((h.num_anchors * h.num_classes + 31) >> 5)) * 4;   // hint, hint_logit, cbits
+    e->post_scratch_bytes = (size_t)e->max_batch * (2 + ((h.num_anchors * h.num_classes + 31) >> 5)) * 4;   // hint, hint_logit, cbits
 
     for (uint32_t i = 0; i < h.n_tensors; ++i)
-        if (e->tensors[i].slot < 0 || e->tensors[i].slot >= (int)h.n_slots) {
-            wz_fail(WZ_EFORMAT, "tensor %u has a bad slot", i);
-            wz_destroy(e);
-            return WZ_EFORMAT;
-        }
-
-    for (int li = 0; li < e->n_lanes; ++li) {
-        Lane& L = e->lanes[li];
-        // More lanes than streams (WZ_STREAMS, default 4 = what this stack runs side by side): lane i rides the stream of lane
-        // i mod streams, with buffers, graph and host blocks of its own -- the stream always has the next batch queued behind the one
-        // it is running, so the host's turnaround between a batch's end and the next submit is not idle time on that queue.
-        if (li >= e->n_streams) L.stream = e->lanes[li % e->n_streams].stream;   // (the first n_streams lanes own theirs: created above)
-        // activation buffers: one per slot (tensors with disjoint lifetimes share), or one per tensor
-        L.tptr.assign(h.n_tensors, nullptr);
-        if (e->no_reuse) {
-            for (uint32_t i = 0; i < h.n_tensors; ++i) {
-                const WzTensorDesc& t = e->tensors[i];
-                void* p = nullptr;
-                (void)t;
-                CK(hipMalloc(&p, (size_t)max_batch * tensor_frame_bytes(e, i) + 256));
-                L.bufs.push_back(p);
-                L.tptr[i] = (half_t*)p;
-            }
-        } else {
-            std::vector<size_t> slot_bytes(h.n_slots, 0);
-            for (uint32_t i = 0; i < h.n_tensors; ++i) {
-                const WzTensorDesc& t = e->tensors[i];
-                const size_t b = (size_t)max_batch * tensor_frame_bytes(e, i) + 256;
-                if (b > slot_bytes[t.slot]) slot_bytes[t.slot] = b;
-            }
-            for (uint32_t sidx = 0; sidx < h.n_slots; ++sidx) {
-                void* p = nullptr;
-                CK(hipMalloc(&p, slot_bytes[sidx]));
-                L.bufs.push_back(p);
-            }
-            for (uint32_t i = 0; i < h.n_tensors; ++i) L.tptr[i] = (half_t*)L.bufs[e->tensors[i].slot];
-        }
-        CK(hipMalloc((void**)&L.d_box_enc, (size_t)max_batch * h.num_anchors * 4 * 4));
-        CK(hipMalloc((void**)&L.d_logits, (size_t)max_batch * h.num_anchors * h.num_classes * 4));
-        CK(hipMalloc((void**)&L.d_ws, e->ws_bytes));
-        CK(hipMalloc((void**)&L.d_frames, e->frame_stride * max_batch));
-        WzPostBuffers& pb = L.post;
-        pb.box_enc = L.d_box_enc;
-        pb.logits = L.d_logits;
-        pb.anchors = e->d_anchors;
-        CK(hipMalloc((void**)&pb.boxes, (size_t)max_batch * h.num_anchors * 16));
-        CK(hipMalloc((void**)&pb.valid, (size_t)max_batch * h.num_anchors));
-        CK(hipMalloc(&L.d_post_scratch, e->post_scratch_bytes));
-        pb.hint = (uint32_t*)L.d_post_scratch;
-        {   // first band of the NMS kernel: start at score 0.25 until the frame slot has a history
-            const uint32_t bin0 = 0x3E800000u >> 20;
-            std::vector<uint32_t> hint0((size_t)max_batch, bin0);
-            CK(lane0_copy(e, pb.hint, hint0.data(), hint0.size() * 4, hipMemcpyHostToDevice));
-            pb.hint_logit = reinterpret_cast<float*>(pb.hint + max_batch);
-            uint32_t sbits = bin0 << 20;
-            float s0;
-            memcpy(&s0, &sbits, 4);
-            const float l0 = logf(s0 / (1.0f - s0));   // wz_logit_floor(bin0), k_post.hip
-            std::vector<float> hl0((size_t)max_batch, l0 - 0.01f - 1e-3f * fabsf(l0));
-            CK(lane0_copy(e, pb.hint_logit, hl0.data(), hl0.size() * 4, hipMemcpyHostToDevice));
-            pb.cbits = reinterpret_cast<uint32_t*>(pb.hint_logit + max_batch);
-            CK(lane0_fill(e, pb.cbits, 0, (size_t)max_batch * ((h.num_anchors * h.num_classes + 31) >> 5) * 4));
-        }
-        CK(hipMalloc((void**)&pb.det_boxes, (size_t)max_batch * h.max_total * 16));
-        CK(hipMalloc((void**)&pb.det_scores, (size_t)max_batch * h.max_total * 4));
-        CK(hipMalloc((void**)&pb.det_classes, (size_t)max_batch * h.max_total * 4));
-        CK(hipMalloc((void**)&pb.det_num, (size_t)max_batch * 4));
-        CK(hipMalloc((void**)&pb.dbg, (size_t)max_batch * 16 * 8));
-        CK(lane0_fill(e, pb.dbg, 0, (size_t)max_batch * 16 * 8));
-        CK(hipHostMalloc((void**)&L.h_desc, sizeof(WzFrameDesc) * max_batch, hipHostMallocDefault));
-        if (hipHostGetDevicePointer((void**)&L.h_desc_dev, L.h_desc, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            L.h_desc_dev = nullptr;
-        }
-#if WZ_LANE_STAMPS
-        {   // [launch blocks][the resize kernel's block][descriptors]: every pair starts as (entry = max, exit = 0)
-            const size_t blocks = (size_t)WZ_STAMP_SLOTS * WZ_STAMP_WORDS * 8;
-            CK(hipMalloc((void**)&L.d_stamp_raw, blocks + WZ_STAMP_PRE_BYTES + sizeof(WzFrameDesc) * max_batch));
-            L.d_stamps = reinterpret_cast<unsigned long long*>(L.d_stamp_raw);
-            L.d_stamps_pre = reinterpret_cast<unsigned long long*>(L.d_stamp_raw + blocks);
-            L.d_desc = reinterpret_cast<WzFrameDesc*>(L.d_stamp_raw + blocks + WZ_STAMP_PRE_BYTES);
-            std::vector<unsigned long long> init((blocks + WZ_STAMP_PRE_BYTES) / 8, 0ull);
-            for (size_t k = 0; k < init.size(); k += WZ_STAMP_WORDS)
-                for (int j = 0; j < 64; ++j) init[k + WZ_STAMP_ENTRY + j] = ~0ull;
-            CK(lane0_copy(e, L.d_stamp_raw, init.data(), init.size() * 8, hipMemcpyHostToDevice));
-            const size_t host_pairs = (size_t)(WZ_STAMP_SLOTS + 1 + max_batch) * 2 * 8;
-            CK(hipHostMalloc((void**)&L.h_stamps, host_pairs, hipHostMallocMapped));
-            memset(L.h_stamps, 0, host_pairs);
-            CK(hipHostGetDevicePointer((void**)&L.m_stamps, L.h_stamps, 0));
-        }
-#else
-        CK(hipMalloc((void**)&L.d_desc, sizeof(WzFrameDesc) * max_batch));
-#endif
-        pb.stamps = L.d_stamps;
-        pb.stamps_pre = L.d_stamps_pre;
-        pb.stamps_host = nullptr;
-        pb.stamps_n = 0;
-        pb._stamps_pad = 0;
-        CK(hipMalloc((void**)&L.d_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS * max_batch));
-        CK(hipMalloc((void**)&L.d_pass, (size_t)WZ_MAX_DETECTIONS * max_batch));
-        CK(hipHostMalloc((void**)&L.h_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS * max_batch, hipHostMallocMapped));
-        CK(hipHostMalloc((void**)&L.h_pass, (size_t)WZ_MAX_DETECTIONS * max_batch, hipHostMallocMapped));
-        CK(hipHostGetDevicePointer((void**)&L.m_rows, L.h_rows, 0));
-        CK(hipHostGetDevicePointer((void**)&L.m_pass, L.h_pass, 0));
-        CK(hipHostMalloc((void**)&L.h_status, sizeof(uint32_t) * max_batch, hipHostMallocMapped));
-        memset(L.h_status, 0, sizeof(uint32_t) * max_batch);
-        CK(hipHostGetDevicePointer((void**)&L.m_status, L.h_status, 0));
-        CK(hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
-    }
+        if (e->tensors[i].slot < 0 || e->tensors[i].slot >= (int)h.n_slots) return wz_set_error(WZ_EFORMAT, "tensor %u has a bad slot", i);
+    for (int li = 0; li < e->n_lanes; ++li) WZCHK(build_lane(e, li));
 
     e->h_cams.resize(WZ_MAX_CAMS);
     memset(e->h_cams.data(), 0, sizeof(WzCamFilter) * WZ_MAX_CAMS);
-    e->cam_sat.assign(WZ_MAX_CAMS, nullptr);
-    CK(hipMalloc((void**)&e->d_cams, sizeof(WzCamFilter) * WZ_MAX_CAMS));
-    CK(lane0_fill(e, e->d_cams, 0, sizeof(WzCamFilter) * WZ_MAX_CAMS));
-    CK(hipMalloc((void**)&e->d_tmp_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS));
-    CK(hipMalloc((void**)&e->d_tmp_pass, WZ_MAX_DETECTIONS));
+    e->cam_sat.resize(WZ_MAX_CAMS);
+    HIPCHK(e->d_cams.alloc(WZ_MAX_CAMS));
+    HIPCHK(lane0_fill(e, e->d_cams, 0, sizeof(WzCamFilter) * WZ_MAX_CAMS));
+    HIPCHK(e->d_tmp_rows.alloc(WZ_MAX_DETECTIONS));
+    HIPCHK(e->d_tmp_pass.alloc(WZ_MAX_DETECTIONS));
 
-    e->stage_names.push_back("(empty)");
-    e->stage_names.push_back("h2d_descriptors");
-    e->stage_names.push_back("preprocess");
+    e->stage_names = {"(empty)", "h2d_descriptors", "preprocess"};
     for (uint32_t i = 0; i < h.n_ops; ++i) {
         e->stage_names.push_back(e->ops[i].name);   // stage_slots(op) names per op: enqueue_network marks as many
         for (int k = 1; k < stage_slots(e->ops[i]); ++k) e->stage_names.push_back(std::string(e->ops[i].name) + "#splitk_reduce");
     }
-    e->stage_names.push_back("heads#big_convs");
-    e->stage_names.push_back("heads#small_convs");
-    e->stage_names.push_back("heads#splitk_reduce");
-    e->stage_names.push_back("post/decode");
-    e->stage_names.push_back("post/nms");
-    e->stage_names.push_back("post/rows");
-    if (sync_all(e) != WZ_OK) {
-        wz_destroy(e);
-        return WZ_EHIP;
+    for (const char* name : {"heads#big_convs", "heads#small_convs", "heads#splitk_reduce", "post/decode", "post/nms", "post/rows"})
+        e->stage_names.push_back(name);
+    return sync_all(e);
+}
+
+extern "C" int wz_create(const char* engine_path, int device, int max_batch, int max_width, int max_height,
+                         wz_engine_t** out) {
+    if (!engine_path || !out || max_batch < 1 || max_batch > 4095 || max_width < 1 || max_height < 1)
+        return wz_set_error(WZ_EINVAL, "wz_create: bad argument");
+    *out = nullptr;
+    wz_engine* e = new wz_engine();
+    int rc = load_blob(e, engine_path);
+    const int ndev = rc == WZ_OK ? wz_device_count() : 0;
+    if (rc == WZ_OK && (device < 0 || device >= ndev)) rc = wz_set_error(WZ_ENODEV, "HIP device %d not present (%d visible)", device, ndev);
+    if (rc == WZ_OK) {
+        e->device = device;
+        e->max_batch = max_batch;
+        e->max_w = max_width;
+        e->max_h = max_height;
+        read_options(e, max_width);
+        rc = build_engine(e);
     }
-#undef CK
+    if (rc != WZ_OK) {   // the one failure exit: whatever exists by now frees itself
+        wz_destroy(e);
+        return rc;
+    }
     *out = e;
     return WZ_OK;
 }
@@ -682,35 +635,16 @@ int sync_all(wz_engine* e) {
     return WZ_OK;
 }
 
+// Every block frees itself with the engine (wz_engine.h); what is destroyed here by hand is what has no owner type: the lanes' events and
+// streams.  A lane's graphs go before the stream they were launched on; a lane that rides another lane's stream destroys none.
 extern "C" void wz_destroy(wz_engine_t* e) {
     if (!e) return;
-    (void)hipSetDevice(e->device);
-    (void)sync_all(e);
-    for (int32_t* p : e->cam_sat)
-        if (p) (void)hipFree(p);
-    for (auto& kv : e->gate_cams) kv.second.release();
-    for (auto& kv : e->motion_cams) kv.second.release();
-    void* devp[] = {e->d_weights, e->d_zeros, e->d_mbdbg, e->d_anchors, e->d_frames, e->d_cams, e->d_tmp_rows, e->d_tmp_pass};
-    for (void* p : devp)
-        if (p) (void)hipFree(p);
-    for (int li = 0; li < WZ_SLOTS; ++li) {
-        Lane& L = e->lanes[li];
-        for (auto& kv : L.graphs) (void)hipGraphExecDestroy(kv.second);
-        for (auto& kv : L.graph_src) (void)hipGraphDestroy(kv.second);
-        for (void* p : L.bufs) (void)hipFree(p);
-        void* lp[] = {L.d_frames, L.d_box_enc, L.d_logits, L.d_ws, L.post.boxes, L.post.valid, L.d_post_scratch,
-                      L.post.det_boxes, L.post.det_scores, L.post.det_classes, L.post.det_num, L.post.dbg,
-                      L.d_stamp_raw ? (void*)L.d_stamp_raw : (void*)L.d_desc, L.d_rows, L.d_pass};
-        for (void* p : lp)
-            if (p) (void)hipFree(p);
-        if (L.h_desc) (void)hipHostFree(L.h_desc);
-        if (L.h_rows) (void)hipHostFree(L.h_rows);
-        if (L.h_pass) (void)hipHostFree(L.h_pass);
-        if (L.h_status) (void)hipHostFree(L.h_status);
-        if (L.h_stamps) (void)hipHostFree(L.h_stamps);
-        L.tile.release();
-        L.gate.release();
-        L.motion.release();
+    if (e->lanes[0].stream) {   // (nothing is made on the device before the first stream)
+        (void)hipSetDevice(e->device);
+        (void)sync_all(e);
+    }
+    for (Lane& L : e->lanes) {
+        L.forms.clear();
         if (L.done) (void)hipEventDestroy(L.done);
         if (L.stream && L.owns_stream) (void)hipStreamDestroy(L.stream);
     }
@@ -751,8 +685,7 @@ extern "C" uint64_t wz_frame_bytes(int w, int h, int fmt) {
 }
 
 int fill_desc(wz_engine* e, int slot, int n, const uint8_t* const* d_rgb, const int* w, const int* h, const int* fmt, const int* cam) {
-    if (slot < 0 || slot >= e->n_lanes) return wz_fail(WZ_EINVAL, "slot %d out of range [0,%d)", slot, e->n_lanes);
-    if (n < 1 || n > e->max_batch) return wz_fail(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
+    WZCHK(batch_refusal(e, slot, n));
     const float size = (float)e->hdr.input_size;
     e->lanes[slot].bound_idx.clear();
     e->lanes[slot].tile.tiled = 0;
@@ -760,7 +693,7 @@ int fill_desc(wz_engine* e, int slot, int n, const uint8_t* const* d_rgb, const 
         const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
         const int c = cam ? cam[i] : -1;
         WZCHK(frame_refusal(e, "frame", i, d_rgb[i], w[i], h[i], pf, c, FC_PTR | FC_FMT | FC_CAM_ID | FC_CAM_FILTER));
-        WzFrameDesc& d = e->lanes[slot].h_desc[i];
+        WzFrameDesc& d = e->lanes[slot].desc.h[i];
         d.rgb = d_rgb[i];
         d.w = w[i];
         d.h = h[i];
@@ -774,8 +707,8 @@ int fill_desc(wz_engine* e, int slot, int n, const uint8_t* const* d_rgb, const 
 
 extern "C" int wz_submit_device_fmt(wz_engine_t* e, int slot, int n, const uint8_t* const* d_rgb, const int* w,
                                     const int* h, const int* fmt, const int* cam) {
-    if (!e || !d_rgb || !w || !h) return wz_fail(WZ_EINVAL, "wz_submit_device: null argument");
-    if (slot < 0 || slot >= e->n_lanes) return wz_fail(WZ_EINVAL, "slot %d out of range [0,%d)", slot, e->n_lanes);
+    if (!e || !d_rgb || !w || !h) return wz_set_error(WZ_EINVAL, "wz_submit_device: null argument");
+    WZCHK(batch_refusal(e, slot, n, BC_SLOT));
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipEventSynchronize(e->lanes[slot].done));   // the lane's previous batch has fully drained
     WZCHK(fill_desc(e, slot, n, d_rgb, w, h, fmt, cam));
@@ -788,7 +721,7 @@ extern "C" int wz_submit_device(wz_engine_t* e, int slot, int n, const uint8_t* 
 }
 
 extern "C" int wz_wait(wz_engine_t* e, int slot) {
-    if (!e || slot < 0 || slot >= e->n_lanes) return wz_fail(WZ_EINVAL, "wz_wait: bad argument");
+    if (!e || slot < 0 || slot >= e->n_lanes) return wz_set_error(WZ_EINVAL, "wz_wait: bad argument");
     HIPCHK(hipEventSynchronize(e->lanes[slot].done));
     return WZ_OK;
 }
@@ -797,8 +730,8 @@ extern "C" int wz_wait(wz_engine_t* e, int slot) {
 static int lane_status(wz_engine* e, int slot) {
     const Lane& L = e->lanes[slot];
     for (int i = 0; i < L.n; ++i)
-        if (L.h_status && L.h_status[i])
-            return wz_fail(WZ_EINCOMPLETE, "frame %d of the batch on lane %d: more than %d selected boxes lie entirely outside the image, "
+        if (L.hstatus.h[i])
+            return wz_set_error(WZ_EINCOMPLETE, "frame %d of the batch on lane %d: more than %d selected boxes lie entirely outside the image, "
                                            "its rows may be incomplete", i, slot, WZ_NMS_KEEP_MAX - (int)e->hdr.max_total);
     return WZ_OK;
 }
@@ -807,7 +740,7 @@ static int lane_status(wz_engine* e, int slot) {
 // (the tiles that ran; none: 0; lane_status still looks at every tile).
 struct LaneResult { int n; const wz_detection_t* rows; const uint8_t* pass; };
 static LaneResult lane_result(const Lane& L) {
-    return L.tile.tiled ? LaneResult{L.tile.tiled, L.tile.trows.h, L.tile.tpass.h} : LaneResult{L.n, L.h_rows, L.h_pass};
+    return L.tile.tiled ? LaneResult{L.tile.tiled, L.tile.trows.h, L.tile.tpass.h} : LaneResult{L.n, L.hrows.h, L.hpass.h};
 }
 
 extern "C" const wz_detection_t* wz_slot_rows(wz_engine_t* e, int slot) {
@@ -831,13 +764,37 @@ extern "C" int wz_num_slots(wz_engine_t* e) { return e ? e->n_lanes : 0; }
 extern "C" int wz_graph_nodes(wz_engine_t* e, int slot) {
     if (!e || slot < 0 || slot >= e->n_lanes) return 0;
     const Lane& L = e->lanes[slot];
-    auto it = L.graph_nodes.find(L.key);
-    return it == L.graph_nodes.end() ? 0 : it->second;
+    const auto it = L.forms.find(L.key);
+    return it == L.forms.end() ? 0 : it->second.nodes;
 }
 
 extern "C" int wz_sync(wz_engine_t* e) {
-    if (!e) return wz_fail(WZ_EINVAL, "wz_sync: null engine");
+    if (!e) return wz_set_error(WZ_EINVAL, "wz_sync: null engine");
     return sync_all(e);
+}
+
+// The host frames of a batch going onto lane L, placed: ptr[i] comes in as frame i's host address and leaves as where the device finds
+// the frame -- the frame itself, read in place, where `may_read` and read_in_place allow it and the device sees it (*in_place: one is), else its
+// copy in the lane's staging area.  entries: the frames are these entries of the frame table (null: plain pointers, looked up).
+static int place_frames(wz_engine* e, Lane& L, int n, const uint8_t** ptr, const int* w, const int* h, const int* fmt, const int32_t* entries,
+                        bool may_read, bool* in_place) {
+    *in_place = false;
+    for (int i = 0; i < n; ++i) {
+        const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
+        const char* what = entries ? "frame-table entry" : "frame";
+        WZCHK(frame_refusal(e, what, i, ptr[i], w[i], h[i], pf, -1, FC_PTR | FC_LIMIT));
+        const uint64_t bytes = entries ? e->bound[entries[i]].bytes : wz_frame_bytes(w[i], h[i], pf);
+        if (!bytes) return frame_refusal(e, what, i, ptr[i], w[i], h[i], pf, -1, FC_FMT);
+        // pageable source: the runtime stages it (slow, synchronous); registered / pinned source: one DMA -- or no copy at all
+        const uint8_t* dv = !(may_read && read_in_place(e, h[i])) ? nullptr : entries ? e->bound[entries[i]].dev : device_view(e, ptr[i], bytes);
+        if (dv) {
+            ptr[i] = dv;
+            *in_place = true;
+        } else {
+            WZCHK(stage_frame(e, L, i, ptr[i], bytes, &ptr[i]));
+        }
+    }
+    return WZ_OK;
 }
 
 extern "C" int wz_detect_batch(wz_engine_t* e, int n, const uint8_t* const* rgb, const int* w, const int* h,
@@ -846,29 +803,26 @@ extern "C" int wz_detect_batch(wz_engine_t* e, int n, const uint8_t* const* rgb,
 }
 extern "C" int wz_detect_batch_fmt(wz_engine_t* e, int n, const uint8_t* const* rgb, const int* w, const int* h, const int* fmt,
                                    const int* cam, wz_detection_t* const* out, uint8_t* const* pass, float* ms) {
-    if (!e || !rgb || !w || !h) return wz_fail(WZ_EINVAL, "wz_detect_batch: null argument");
-    if (n < 1 || n > e->max_batch) return wz_fail(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
+    if (!e || !rgb || !w || !h) return wz_set_error(WZ_EINVAL, "wz_detect_batch: null argument");
+    WZCHK(batch_refusal(e, 0, n, BC_N));
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipEventSynchronize(e->lanes[0].done));
-    std::vector<const uint8_t*> dptr(n);
-    for (int i = 0; i < n; ++i) {
-        const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
-        WZCHK(frame_refusal(e, "frame", i, rgb[i], w[i], h[i], pf, -1, FC_PTR | FC_LIMIT));
-        const uint64_t bytes = wz_frame_bytes(w[i], h[i], pf);
-        if (!bytes) return frame_refusal(e, "frame", i, rgb[i], w[i], h[i], pf, -1, FC_FMT);
-        uint8_t* dst = e->d_frames + e->frame_stride * i;
-        HIPCHK(hipMemcpyAsync(dst, rgb[i], bytes, hipMemcpyHostToDevice, e->lanes[0].stream));
-        dptr[i] = dst;
-    }
-    int rc = wz_submit_device_fmt(e, 0, n, dptr.data(), w, h, fmt, cam);
-    if (rc != WZ_OK) return rc;
-    rc = wz_collect(e, 0, out, pass);
+    std::vector<const uint8_t*> dptr(rgb, rgb + n);
+    bool in_place;
+    WZCHK(place_frames(e, e->lanes[0], n, dptr.data(), w, h, fmt, nullptr, false, &in_place));   // (every frame staged, none read in place)
+    WZCHK(wz_submit_device_fmt(e, 0, n, dptr.data(), w, h, fmt, cam));
+    return collect_timed(e, n, out, pass, ms, t0);
+}
+// lane 0's rows handed over and the wall time since t0 into ms[n].  WZ_OK, or WZ_EINCOMPLETE: the rows are written (and timed), one
+// frame's may be short
+int collect_timed(wz_engine* e, int n, wz_detection_t* const* out, uint8_t* const* pass, float* ms, std::chrono::steady_clock::time_point t0) {
+    const int rc = wz_collect(e, 0, out, pass);
     if (rc != WZ_OK && rc != WZ_EINCOMPLETE) return rc;
     const float el = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (ms)
         for (int i = 0; i < n; ++i) ms[i] = el;
-    return rc;   // WZ_OK, or WZ_EINCOMPLETE: the rows are written (and timed), one frame's may be short
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -910,37 +864,21 @@ int stage_frame(wz_engine* e, Lane& L, int i, const uint8_t* host, uint64_t byte
     *where = dst;
     return WZ_OK;
 }
-
 extern "C" int wz_submit_host(wz_engine_t* e, int slot, int n, const uint8_t* const* rgb, const int* w, const int* h,
                               const int* cam) {
     return wz_submit_host_fmt(e, slot, n, rgb, w, h, nullptr, cam);
 }
 extern "C" int wz_submit_host_fmt(wz_engine_t* e, int slot, int n, const uint8_t* const* rgb, const int* w, const int* h,
                                   const int* fmt, const int* cam) {
-    if (!e || !rgb || !w || !h) return wz_fail(WZ_EINVAL, "wz_submit_host: null argument");
-    if (slot < 0 || slot >= e->n_lanes) return wz_fail(WZ_EINVAL, "slot %d out of range [0,%d)", slot, e->n_lanes);
-    if (n < 1 || n > e->max_batch) return wz_fail(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
+    if (!e || !rgb || !w || !h) return wz_set_error(WZ_EINVAL, "wz_submit_host: null argument");
+    WZCHK(batch_refusal(e, slot, n));
     HIPCHK(hipSetDevice(e->device));
     Lane& L = e->lanes[slot];
     HIPCHK(hipEventSynchronize(L.done));   // the lane's previous batch (and its reads of the staging area) drained
-    if (!L.d_frames) return wz_fail(WZ_EINVAL, "wz_submit_host: lane %d has no staging area", slot);
-    bool in_place = false;
+    bool in_place;
     const bool fit = rows_fit(e, n, w, fmt);
-    std::vector<const uint8_t*> dptr(n);
-    for (int i = 0; i < n; ++i) {
-        const int pf = fmt ? fmt[i] : WZ_FMT_RGB24;
-        WZCHK(frame_refusal(e, "frame", i, rgb[i], w[i], h[i], pf, -1, FC_PTR | FC_LIMIT));
-        const uint64_t bytes = wz_frame_bytes(w[i], h[i], pf);
-        if (!bytes) return frame_refusal(e, "frame", i, rgb[i], w[i], h[i], pf, -1, FC_FMT);
-        // pageable source: the runtime stages it (slow, synchronous); registered / pinned source: one DMA -- or no copy at all
-        const uint8_t* dv = fit && read_in_place(e, h[i]) ? device_view(e, rgb[i], bytes) : nullptr;
-        if (dv) {
-            dptr[i] = dv;
-            in_place = true;
-            continue;
-        }
-        WZCHK(stage_frame(e, L, i, rgb[i], bytes, &dptr[i]));
-    }
+    std::vector<const uint8_t*> dptr(rgb, rgb + n);
+    WZCHK(place_frames(e, L, n, dptr.data(), w, h, fmt, nullptr, fit, &in_place));
     WZCHK(fill_desc(e, slot, n, dptr.data(), w, h, fmt, cam));
     L.rows = fit && (e->pre_rows || in_place);
     return run_batch(e, slot, n);
@@ -949,7 +887,7 @@ extern "C" int wz_submit_host_fmt(wz_engine_t* e, int slot, int n, const uint8_t
 // Page-lock a host range (e.g. a FrameBuffer arena, watsor/stream/share.py:35-41) so that frames inside it go to
 // the GPU by DMA at PCIe rate instead of through the runtime's bounce buffer.
 extern "C" int wz_host_register(wz_engine_t* e, void* ptr, uint64_t bytes) {
-    if (!e || !ptr || !bytes) return wz_fail(WZ_EINVAL, "wz_host_register: bad argument");
+    if (!e || !ptr || !bytes) return wz_set_error(WZ_EINVAL, "wz_host_register: bad argument");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipHostRegister(ptr, bytes, hipHostRegisterMapped));
     void* dev = nullptr;
@@ -963,7 +901,7 @@ extern "C" int wz_host_register(wz_engine_t* e, void* ptr, uint64_t bytes) {
     return WZ_OK;
 }
 extern "C" int wz_host_unregister(wz_engine_t* e, void* ptr) {
-    if (!e || !ptr) return wz_fail(WZ_EINVAL, "wz_host_unregister: bad argument");
+    if (!e || !ptr) return wz_set_error(WZ_EINVAL, "wz_host_unregister: bad argument");
     HIPCHK(hipSetDevice(e->device));
     (void)sync_all(e);   // a copy (or a resize kernel reading in place) in flight may still be reading the range
     for (size_t k = 0; k < e->host_ranges.size(); ++k)
@@ -984,7 +922,7 @@ extern "C" int wz_host_unregister(wz_engine_t* e, void* ptr) {
 // ------------------------------------------------------------------------------------------------
 extern "C" int wz_bind_frames(wz_engine_t* e, int n, const uint8_t* const* pixels, const int* w, const int* h, const int* fmt,
                               const int* cam, wz_detection_t* const* rows) {
-    if (!e || n < 0 || (n && (!pixels || !w || !h || !rows))) return wz_fail(WZ_EINVAL, "wz_bind_frames: bad argument");
+    if (!e || n < 0 || (n && (!pixels || !w || !h || !rows))) return wz_set_error(WZ_EINVAL, "wz_bind_frames: bad argument");
     HIPCHK(hipSetDevice(e->device));
     WZCHK(sync_all(e));   // no batch in flight refers to the old table
     std::vector<wz_engine::BoundFrame> tbl((size_t)n);
@@ -1002,30 +940,21 @@ extern "C" int wz_bind_frames(wz_engine_t* e, int n, const uint8_t* const* pixel
 }
 
 extern "C" int wz_submit_bound(wz_engine_t* e, int slot, int n, const int32_t* entries) {
-    if (!e || !entries) return wz_fail(WZ_EINVAL, "wz_submit_bound: null argument");
-    if (slot < 0 || slot >= e->n_lanes) return wz_fail(WZ_EINVAL, "slot %d out of range [0,%d)", slot, e->n_lanes);
-    if (n < 1 || n > e->max_batch) return wz_fail(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
+    if (!e || !entries) return wz_set_error(WZ_EINVAL, "wz_submit_bound: null argument");
+    WZCHK(batch_refusal(e, slot, n));
     for (int i = 0; i < n; ++i)
         if (entries[i] < 0 || (size_t)entries[i] >= e->bound.size())
-            return wz_fail(WZ_EINVAL, "frame-table entry %d out of range [0,%zu)", entries[i], e->bound.size());
+            return wz_set_error(WZ_EINVAL, "frame-table entry %d out of range [0,%zu)", entries[i], e->bound.size());
     if (!e->bound_tiles.empty())           // some entry of the table has a tiled description (wz_bind_tiles): does one of these?
         for (int i = 0; i < n; ++i)
             if (e->bound_tiles[entries[i]].kind != wz_engine::BOUND_PLAIN) return submit_bound_tiles(e, slot, n, entries);
     WZCHK(bound_drain(e, slot));
     Lane& L = e->lanes[slot];
-    bool in_place = false;
+    bool in_place;
     BoundBatch b;
     bound_gather(e, n, entries, b);
     const bool fit = rows_fit(e, n, b.w, b.fmt);
-    for (int i = 0; i < n; ++i) {
-        const wz_engine::BoundFrame& f = e->bound[entries[i]];
-        if (fit && f.dev && read_in_place(e, f.h)) {
-            b.ptr[i] = f.dev;
-            in_place = true;
-            continue;
-        }
-        WZCHK(stage_frame(e, L, i, f.host, f.bytes, &b.ptr[i]));
-    }
+    WZCHK(place_frames(e, L, n, b.ptr.data(), b.w, b.h, b.fmt, entries, fit, &in_place));
 #ifdef WZ_DEV_BUILD   // (wz_debug_bound_source: which leg each frame of this batch took)
     L.bound_src.resize(n);
     for (int i = 0; i < n; ++i) L.bound_src[i] = b.ptr[i] == e->bound[entries[i]].dev && b.ptr[i] != nullptr;
@@ -1042,7 +971,7 @@ extern "C" int wz_collect_bound(wz_engine_t* e, int slot) {
     WZCHK(wz_wait(e, slot));
     Lane& L = e->lanes[slot];
     const LaneResult r = lane_result(L);
-    if (L.bound_idx.empty() || (int)L.bound_idx.size() != r.n) return wz_fail(WZ_EINVAL, "wz_collect_bound: lane %d holds no bound batch", slot);
+    if (L.bound_idx.empty() || (int)L.bound_idx.size() != r.n) return wz_set_error(WZ_EINVAL, "wz_collect_bound: lane %d holds no bound batch", slot);
     for (int i = 0; i < r.n; ++i)
         memcpy(e->bound[L.bound_idx[i]].rows, r.rows + (size_t)i * WZ_MAX_DETECTIONS, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS);
     L.bound_idx.clear();
@@ -1055,10 +984,10 @@ extern "C" int wz_collect_bound(wz_engine_t* e, int slot) {
 extern "C" int wz_set_camera_filter(wz_engine_t* e, int cam, int width, int height, const double* conf_thr,
                                     const double* area_thr, int n_zones, const uint8_t* zone_allow,
                                     const uint8_t* zone_fill) {
-    if (!e || !conf_thr || !area_thr || width < 1 || height < 1) return wz_fail(WZ_EINVAL, "wz_set_camera_filter: bad argument");
-    if (cam < 0 || cam >= WZ_MAX_CAMS) return wz_fail(WZ_ELIMIT, "camera id %d out of range [0,%d)", cam, WZ_MAX_CAMS);
-    if (n_zones < 0 || n_zones > WZ_MAX_ZONES_PER_CAM) return wz_fail(WZ_ELIMIT, "%d zones > %d", n_zones, WZ_MAX_ZONES_PER_CAM);
-    if (n_zones > 0 && !zone_fill) return wz_fail(WZ_EINVAL, "zone_fill is null");
+    if (!e || !conf_thr || !area_thr || width < 1 || height < 1) return wz_set_error(WZ_EINVAL, "wz_set_camera_filter: bad argument");
+    if (cam < 0 || cam >= WZ_MAX_CAMS) return wz_set_error(WZ_ELIMIT, "camera id %d out of range [0,%d)", cam, WZ_MAX_CAMS);
+    if (n_zones < 0 || n_zones > WZ_MAX_ZONES_PER_CAM) return wz_set_error(WZ_ELIMIT, "%d zones > %d", n_zones, WZ_MAX_ZONES_PER_CAM);
+    if (n_zones > 0 && !zone_fill) return wz_set_error(WZ_EINVAL, "zone_fill is null");
     HIPCHK(hipSetDevice(e->device));
     WZCHK(sync_all(e));
     // the new state is built aside and committed only when all of it exists: a failure (e.g. no memory for the
@@ -1073,38 +1002,31 @@ extern "C" int wz_set_camera_filter(wz_engine_t* e, int cam, int width, int heig
     memcpy(c.area_thr, area_thr, sizeof(double) * WZ_NUM_LABELS);
     for (int l = 0; l < WZ_NUM_LABELS; ++l)
         for (int z = 0; z < n_zones; ++z) c.allow[l][z] = zone_allow ? (zone_allow[(size_t)l * n_zones + z] ? 1 : 0) : 1;
-    int32_t* sat = nullptr;
+    auto kept = [&](hipError_t err) { return wz_set_error(WZ_EHIP, "wz_set_camera_filter: %s (camera %d keeps its previous filter)", hipGetErrorString(err), cam); };
+    DevBlock<int32_t> sat;
     if (n_zones > 0) {
-        const size_t plane = (size_t)(width + 1) * (height + 1);
-        uint8_t* d_fill = nullptr;
-        hipError_t err = hipMalloc((void**)&sat, plane * n_zones * 4);
-        if (err == hipSuccess) err = hipMalloc((void**)&d_fill, (size_t)width * height * n_zones);
-        if (err == hipSuccess) err = lane0_copy(e, d_fill, zone_fill, (size_t)width * height * n_zones, hipMemcpyHostToDevice);
+        const size_t plane = (size_t)(width + 1) * (height + 1), fill = (size_t)width * height * n_zones;
+        DevBlock<uint8_t> d_fill;
+        hipError_t err = sat.alloc(plane * n_zones);
+        if (err == hipSuccess) err = d_fill.alloc(fill);
+        if (err == hipSuccess) err = lane0_copy(e, d_fill, zone_fill, fill, hipMemcpyHostToDevice);
         if (err == hipSuccess) {
             wz_launch_sat(d_fill, sat, width, height, n_zones, e->stream);
             err = hipStreamSynchronize(e->stream);
         }
-        if (d_fill) (void)hipFree(d_fill);
-        if (err != hipSuccess) {
-            if (sat) (void)hipFree(sat);
-            return wz_fail(WZ_EHIP, "wz_set_camera_filter: %s (camera %d keeps its previous filter)", hipGetErrorString(err), cam);
-        }
+        if (err != hipSuccess) return kept(err);
         c.sat = sat;
     }
-    hipError_t err = lane0_copy(e, e->d_cams + cam, &c, sizeof(WzCamFilter), hipMemcpyHostToDevice);
-    if (err != hipSuccess) {
-        if (sat) (void)hipFree(sat);
-        return wz_fail(WZ_EHIP, "wz_set_camera_filter: %s (camera %d keeps its previous filter)", hipGetErrorString(err), cam);
-    }
-    if (e->cam_sat[cam]) (void)hipFree(e->cam_sat[cam]);   // nothing in flight reads it: every lane was synchronised above
-    e->cam_sat[cam] = sat;
+    const hipError_t err = lane0_copy(e, e->d_cams + cam, &c, sizeof(WzCamFilter), hipMemcpyHostToDevice);
+    if (err != hipSuccess) return kept(err);
+    e->cam_sat[cam] = std::move(sat);   // (the old tables leave with `sat`; nothing in flight reads them: every lane was synchronised above)
     e->h_cams[cam] = c;
     return WZ_OK;
 }
 
 extern "C" int wz_set_camera_drop(wz_engine_t* e, int cam, int drop) {
-    if (!e || cam < 0 || cam >= WZ_MAX_CAMS) return wz_fail(WZ_EINVAL, "wz_set_camera_drop: bad argument");
-    if (!(e->h_cams[cam].enabled & 1)) return wz_fail(WZ_EINVAL, "camera %d has no filter (wz_set_camera_filter first)", cam);
+    if (!e || cam < 0 || cam >= WZ_MAX_CAMS) return wz_set_error(WZ_EINVAL, "wz_set_camera_drop: bad argument");
+    if (!(e->h_cams[cam].enabled & 1)) return wz_set_error(WZ_EINVAL, "camera %d has no filter (wz_set_camera_filter first)", cam);
     HIPCHK(hipSetDevice(e->device));
     WZCHK(sync_all(e));
     e->h_cams[cam].enabled = (e->h_cams[cam].enabled & ~2) | (drop ? 2 : 0);
@@ -1113,20 +1035,17 @@ extern "C" int wz_set_camera_drop(wz_engine_t* e, int cam, int drop) {
 }
 
 extern "C" int wz_clear_camera_filter(wz_engine_t* e, int cam) {
-    if (!e || cam < 0 || cam >= WZ_MAX_CAMS) return wz_fail(WZ_EINVAL, "wz_clear_camera_filter: bad argument");
+    if (!e || cam < 0 || cam >= WZ_MAX_CAMS) return wz_set_error(WZ_EINVAL, "wz_clear_camera_filter: bad argument");
     HIPCHK(hipSetDevice(e->device));
     WZCHK(sync_all(e));
     memset(&e->h_cams[cam], 0, sizeof(WzCamFilter));
     HIPCHK(lane0_copy(e, e->d_cams + cam, &e->h_cams[cam], sizeof(WzCamFilter), hipMemcpyHostToDevice));
-    if (e->cam_sat[cam]) {
-        (void)hipFree(e->cam_sat[cam]);
-        e->cam_sat[cam] = nullptr;
-    }
+    e->cam_sat[cam] = DevBlock<int32_t>();
     return WZ_OK;
 }
 
 extern "C" int wz_filter_rows(wz_engine_t* e, int cam, wz_detection_t* rows, uint8_t* pass) {
-    if (!e || !rows || !pass || cam < 0 || cam >= WZ_MAX_CAMS) return wz_fail(WZ_EINVAL, "wz_filter_rows: bad argument");
+    if (!e || !rows || !pass || cam < 0 || cam >= WZ_MAX_CAMS) return wz_set_error(WZ_EINVAL, "wz_filter_rows: bad argument");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemcpyAsync(e->d_tmp_rows, rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS, hipMemcpyHostToDevice, e->stream));
     wz_launch_filter_rows(e->d_cams, cam, e->d_tmp_rows, e->d_tmp_pass, e->stream);
@@ -1151,7 +1070,7 @@ extern "C" int wz_num_tensors(wz_engine_t* e) { return e ? (int)e->hdr.n_tensors
 extern "C" int wz_num_ops(wz_engine_t* e) { return e ? (int)e->hdr.n_ops : 0; }
 
 extern "C" int wz_tensor_info(wz_engine_t* e, int idx, char* name, int namelen, int* h, int* w, int* c) {
-    if (!e || idx < 0 || idx >= (int)e->hdr.n_tensors) return wz_fail(WZ_EINVAL, "tensor index %d", idx);
+    if (!e || idx < 0 || idx >= (int)e->hdr.n_tensors) return wz_set_error(WZ_EINVAL, "tensor index %d", idx);
     const WzTensorDesc& t = e->tensors[idx];
     if (name && namelen > 0) snprintf(name, namelen, "%s", t.name);
     if (h) *h = t.h;
@@ -1161,13 +1080,13 @@ extern "C" int wz_tensor_info(wz_engine_t* e, int idx, char* name, int namelen, 
 }
 
 extern "C" int wz_tensor_flags(wz_engine_t* e, int idx) {
-    if (!e || idx < 0 || idx >= (int)e->hdr.n_tensors) return wz_fail(WZ_EINVAL, "tensor index %d", idx);
+    if (!e || idx < 0 || idx >= (int)e->hdr.n_tensors) return wz_set_error(WZ_EINVAL, "tensor index %d", idx);
     return e->tensors[idx].flags;
 }
 
 
 extern "C" int wz_op_info(wz_engine_t* e, int idx, char* name, int namelen, int* dims) {
-    if (!e || idx < 0 || idx >= (int)e->hdr.n_ops) return wz_fail(WZ_EINVAL, "op index %d", idx);
+    if (!e || idx < 0 || idx >= (int)e->hdr.n_ops) return wz_set_error(WZ_EINVAL, "op index %d", idx);
     const WzOpDesc& o = e->ops[idx];
     if (name && namelen > 0) snprintf(name, namelen, "%s", o.name);
     if (dims) {
@@ -1181,7 +1100,7 @@ extern "C" int wz_op_info(wz_engine_t* e, int idx, char* name, int namelen, int*
 }
 
 extern "C" int wz_debug_nms(wz_engine_t* e, int n, uint64_t* out) {
-    if (!e || !out || n < 1 || n > e->max_batch) return wz_fail(WZ_EINVAL, "wz_debug_nms: bad argument");
+    if (!e || !out || n < 1 || n > e->max_batch) return wz_set_error(WZ_EINVAL, "wz_debug_nms: bad argument");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipMemcpy(out, e->lanes[0].post.dbg, (size_t)n * 16 * 8, hipMemcpyDeviceToHost));
@@ -1190,12 +1109,12 @@ extern "C" int wz_debug_nms(wz_engine_t* e, int n, uint64_t* out) {
 
 extern "C" int wz_debug_post_lane(wz_engine_t* e, int slot, int n, float* box_enc, float* logits, float* boxes, float* scores,
                                   int32_t* classes, int32_t* num, uint64_t* dbg, int32_t* flags) {
-    if (!e || slot < 0 || slot >= e->n_lanes || n < 1 || n > e->max_batch) return wz_fail(WZ_EINVAL, "wz_debug_post_lane: bad argument");
+    if (!e || slot < 0 || slot >= e->n_lanes || n < 1 || n > e->max_batch) return wz_set_error(WZ_EINVAL, "wz_debug_post_lane: bad argument");
     HIPCHK(hipSetDevice(e->device));
     const Lane& L = e->lanes[slot];
     HIPCHK(hipStreamSynchronize(L.stream));
     const size_t A = e->hdr.num_anchors, C = e->hdr.num_classes, T = e->hdr.max_total;
-    if (T != WZ_MAX_DETECTIONS) return wz_fail(WZ_EINVAL, "wz_debug_post_lane: max_total %zu, expected %d", T, WZ_MAX_DETECTIONS);
+    if (T != WZ_MAX_DETECTIONS) return wz_set_error(WZ_EINVAL, "wz_debug_post_lane: max_total %zu, expected %d", T, WZ_MAX_DETECTIONS);
     if (box_enc) HIPCHK(hipMemcpy(box_enc, L.d_box_enc, n * A * 16, hipMemcpyDeviceToHost));
     if (logits) HIPCHK(hipMemcpy(logits, L.d_logits, n * A * C * 4, hipMemcpyDeviceToHost));
     if (boxes) HIPCHK(hipMemcpy(boxes, L.post.det_boxes, n * T * 16, hipMemcpyDeviceToHost));
@@ -1204,15 +1123,15 @@ extern "C" int wz_debug_post_lane(wz_engine_t* e, int slot, int n, float* box_en
     if (num) HIPCHK(hipMemcpy(num, L.post.det_num, (size_t)n * 4, hipMemcpyDeviceToHost));
     if (dbg) HIPCHK(hipMemcpy(dbg, L.post.dbg, (size_t)n * 16 * 8, hipMemcpyDeviceToHost));
     if (flags) {   // of the batch last run: the launches of its graph key, whether they were issued one by one or replayed
-        const auto it = L.post_modes.find(L.key);   // (no batch yet, only stage-level calls: 0, 0)
-        flags[0] = it == L.post_modes.end() ? 0 : it->second & 1;
-        flags[1] = it == L.post_modes.end() ? 0 : (it->second >> 1) & 1;
+        const auto it = L.forms.find(L.key);   // (no batch yet, only stage-level calls: 0, 0)
+        flags[0] = it == L.forms.end() ? 0 : it->second.post_mode & 1;
+        flags[1] = it == L.forms.end() ? 0 : (it->second.post_mode >> 1) & 1;
     }
     return WZ_OK;
 }
 
 extern "C" int wz_debug_mbconv(wz_engine_t* e, uint64_t* out, int32_t* groups) {
-    if (!e || !out || !e->d_mbdbg) return wz_fail(WZ_EINVAL, "wz_debug_mbconv: create the engine with WZ_MB_DEBUG=1");
+    if (!e || !out || !e->d_mbdbg) return wz_set_error(WZ_EINVAL, "wz_debug_mbconv: create the engine with WZ_MB_DEBUG=1");
     HIPCHK(hipSetDevice(e->device));
     WZCHK(sync_all(e));
     HIPCHK(hipMemcpy(out, e->d_mbdbg, (size_t)e->hdr.n_ops * 16 * 8, hipMemcpyDeviceToHost));
@@ -1223,32 +1142,32 @@ extern "C" int wz_debug_mbconv(wz_engine_t* e, uint64_t* out, int32_t* groups) {
 // ---- lane stamps (`make stamps`; tools/lane_overlap.py): entry / exit of every launch of the batch last run on `slot`, 100 MHz ticks
 extern "C" int wz_debug_lane_stamps(wz_engine_t* e, int slot, uint64_t* out, int cap) {
 #if WZ_LANE_STAMPS
-    if (!e || !out || slot < 0 || slot >= e->n_lanes) return wz_fail(WZ_EINVAL, "wz_debug_lane_stamps: bad argument");
+    if (!e || !out || slot < 0 || slot >= e->n_lanes) return wz_set_error(WZ_EINVAL, "wz_debug_lane_stamps: bad argument");
     const Lane& L = e->lanes[slot];
     const int k = L.post.stamps_n;          // launches in front of the NMS kernel; its own pairs (one per frame) follow and are folded here
-    if (!L.h_stamps || k <= 0 || cap < k + 1) return wz_fail(WZ_EINVAL, "wz_debug_lane_stamps: no stamped batch on lane %d (or cap %d < %d)", slot, cap, k + 1);
-    for (int i = 0; i < 2 * k; ++i) out[i] = L.h_stamps[i];
+    if (!L.hstamps.h || k <= 0 || cap < k + 1) return wz_set_error(WZ_EINVAL, "wz_debug_lane_stamps: no stamped batch on lane %d (or cap %d < %d)", slot, cap, k + 1);
+    for (int i = 0; i < 2 * k; ++i) out[i] = L.hstamps.h[i];
     uint64_t t0 = ~0ull, t1 = 0;
     for (int f = 0; f < L.n; ++f) {
-        t0 = std::min<uint64_t>(t0, L.h_stamps[2 * (k + f)]);
-        t1 = std::max<uint64_t>(t1, L.h_stamps[2 * (k + f) + 1]);
+        t0 = std::min<uint64_t>(t0, L.hstamps.h[2 * (k + f)]);
+        t1 = std::max<uint64_t>(t1, L.hstamps.h[2 * (k + f) + 1]);
     }
     out[2 * k] = t0;
     out[2 * k + 1] = t1;
     return k + 1;
 #else
     (void)e; (void)slot; (void)out; (void)cap;
-    return wz_fail(WZ_EINVAL, "wz_debug_lane_stamps: this library was not built with -DWZ_LANE_STAMPS=1 (`make stamps`)");
+    return wz_set_error(WZ_EINVAL, "wz_debug_lane_stamps: this library was not built with -DWZ_LANE_STAMPS=1 (`make stamps`)");
 #endif
 }
 // launch `idx` of that batch: kernel name, dims = {workgroups, threads per workgroup, LDS bytes (static + dynamic), workgroups a CU holds}
 extern "C" int wz_debug_lane_launch(wz_engine_t* e, int slot, int idx, char* name, int namelen, int* dims) {
 #if WZ_LANE_STAMPS
-    if (!e || slot < 0 || slot >= e->n_lanes || !dims) return wz_fail(WZ_EINVAL, "wz_debug_lane_launch: bad argument");
+    if (!e || slot < 0 || slot >= e->n_lanes || !dims) return wz_set_error(WZ_EINVAL, "wz_debug_lane_launch: bad argument");
     Lane& L = e->lanes[slot];
-    auto it = L.launch_notes.find(L.key);
-    if (it == L.launch_notes.end() || idx < 0 || idx >= (int)it->second.size()) return wz_fail(WZ_EINVAL, "wz_debug_lane_launch: no launch %d", idx);
-    const WzLaunchNote& ln = it->second[idx];
+    const auto it = L.forms.find(L.key);
+    if (it == L.forms.end() || idx < 0 || idx >= (int)it->second.notes.size()) return wz_set_error(WZ_EINVAL, "wz_debug_lane_launch: no launch %d", idx);
+    const WzLaunchNote& ln = it->second.notes[idx];
     HIPCHK(hipSetDevice(e->device));
     const char* nm = hipKernelNameRefByPtr(ln.func, L.stream);
     if (name && namelen > 0) snprintf(name, namelen, "%s", nm ? nm : "?");
@@ -1263,16 +1182,16 @@ extern "C" int wz_debug_lane_launch(wz_engine_t* e, int slot, int idx, char* nam
     dims[2] = (int)fa.sharedSizeBytes + (int)ln.lds;
     dims[3] = per_cu;
     dims[4] = fa.numRegs;
-    return (int)it->second.size();
+    return (int)it->second.notes.size();
 #else
     (void)e; (void)slot; (void)idx; (void)name; (void)namelen; (void)dims;
-    return wz_fail(WZ_EINVAL, "wz_debug_lane_launch: this library was not built with -DWZ_LANE_STAMPS=1 (`make stamps`)");
+    return wz_set_error(WZ_EINVAL, "wz_debug_lane_launch: this library was not built with -DWZ_LANE_STAMPS=1 (`make stamps`)");
 #endif
 }
 
 extern "C" int wz_num_stages(wz_engine_t* e) { return e ? (int)e->stage_names.size() : 0; }
 extern "C" int wz_stage_name(wz_engine_t* e, int stage, char* name, int namelen) {
-    if (!e || stage < 0 || stage >= (int)e->stage_names.size()) return wz_fail(WZ_EINVAL, "stage index %d", stage);
+    if (!e || stage < 0 || stage >= (int)e->stage_names.size()) return wz_set_error(WZ_EINVAL, "stage index %d", stage);
     snprintf(name, namelen, "%s", e->stage_names[stage].c_str());
     return WZ_OK;
 }
@@ -1284,7 +1203,7 @@ extern "C" int wz_profile_device(wz_engine_t* e, int n, const uint8_t* const* d_
 
 extern "C" int wz_profile_stages(wz_engine_t* e, int n, const uint8_t* const* d_rgb, const int* w, const int* h,
                                  int reps, int inner, float* stage_ms) {
-    if (!e || !stage_ms || reps < 1 || inner < 1 || inner > 64) return wz_fail(WZ_EINVAL, "wz_profile_stages: bad argument");
+    if (!e || !stage_ms || reps < 1 || inner < 1 || inner > 64) return wz_set_error(WZ_EINVAL, "wz_profile_stages: bad argument");
     HIPCHK(hipSetDevice(e->device));
     WZCHK(sync_all(e));
     WZCHK(fill_desc(e, 0, n, d_rgb, w, h, nullptr, nullptr));
@@ -1296,9 +1215,9 @@ extern "C" int wz_profile_stages(wz_engine_t* e, int n, const uint8_t* const* d_
     for (int r = 0; r < reps + 1; ++r) {   // first repetition is an untimed warm-up
         t.used = 0;
         t.mark();
-        enqueue_batch(e, e->lanes[0], n, &t, inner);
+        enqueue_batch(e, e->lanes[0], e->lanes[0].forms[n | (e->lanes[0].rows ? 1 << 16 : 0)], n, &t, inner);
         HIPCHK(hipStreamSynchronize(e->stream));
-        if (t.used != ns + 1) return wz_fail(WZ_EINVAL, "profile: %zu marks for %zu stages", t.used, ns);
+        if (t.used != ns + 1) return wz_set_error(WZ_EINVAL, "profile: %zu marks for %zu stages", t.used, ns);
         if (r == 0) continue;
         for (size_t i = 0; i < ns; ++i) {
             float ms = 0.f;
@@ -1317,25 +1236,25 @@ extern "C" int wz_profile_stages(wz_engine_t* e, int n, const uint8_t* const* d_
 // device memory helpers
 // ------------------------------------------------------------------------------------------------
 extern "C" int wz_dev_alloc(wz_engine_t* e, uint64_t bytes, void** d_ptr) {
-    if (!e || !d_ptr) return wz_fail(WZ_EINVAL, "wz_dev_alloc: null argument");
+    if (!e || !d_ptr) return wz_set_error(WZ_EINVAL, "wz_dev_alloc: null argument");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMalloc(d_ptr, bytes));
     return WZ_OK;
 }
 extern "C" int wz_dev_free(wz_engine_t* e, void* d_ptr) {
-    if (!e) return wz_fail(WZ_EINVAL, "wz_dev_free: null engine");
+    if (!e) return wz_set_error(WZ_EINVAL, "wz_dev_free: null engine");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipFree(d_ptr));
     return WZ_OK;
 }
 extern "C" int wz_dev_upload(wz_engine_t* e, void* d_dst, const void* h_src, uint64_t bytes) {
-    if (!e) return wz_fail(WZ_EINVAL, "wz_dev_upload: null engine");
+    if (!e) return wz_set_error(WZ_EINVAL, "wz_dev_upload: null engine");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(lane0_copy(e, d_dst, h_src, bytes, hipMemcpyHostToDevice));
     return WZ_OK;
 }
 extern "C" int wz_dev_download(wz_engine_t* e, void* h_dst, const void* d_src, uint64_t bytes) {
-    if (!e) return wz_fail(WZ_EINVAL, "wz_dev_download: null engine");
+    if (!e) return wz_set_error(WZ_EINVAL, "wz_dev_download: null engine");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(lane0_copy(e, h_dst, d_src, bytes, hipMemcpyDeviceToHost));
     return WZ_OK;
@@ -1349,16 +1268,16 @@ extern "C" int wz_stage_preprocess(wz_engine_t* e, const uint8_t* rgb, int w, in
     return wz_stage_preprocess_fmt(e, rgb, w, h, WZ_FMT_RGB24, out_half);
 }
 extern "C" int wz_stage_preprocess_fmt(wz_engine_t* e, const uint8_t* rgb, int w, int h, int fmt, uint16_t* out_half) {
-    if (!e || !rgb || !out_half) return wz_fail(WZ_EINVAL, "wz_stage_preprocess: null argument");
-    if (w > e->max_w || h > e->max_h || (size_t)w * h * 3 > e->frame_stride) return wz_fail(WZ_ELIMIT, "frame too large");
+    if (!e || !rgb || !out_half) return wz_set_error(WZ_EINVAL, "wz_stage_preprocess: null argument");
+    if (w > e->max_w || h > e->max_h || (size_t)w * h * 3 > e->frame_stride) return wz_set_error(WZ_ELIMIT, "frame too large");
     const uint64_t bytes = wz_frame_bytes(w, h, fmt);
-    if (!bytes) return wz_fail(WZ_EINVAL, "pixel format 0x%x at %dx%d: %s", fmt, w, h, fmt_refusal(w, h, fmt));
+    if (!bytes) return wz_set_error(WZ_EINVAL, "pixel format 0x%x at %dx%d: %s", fmt, w, h, fmt_refusal(w, h, fmt));
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(e->d_frames, rgb, bytes, hipMemcpyHostToDevice));
-    const uint8_t* p = e->d_frames;
+    HIPCHK(hipMemcpy(e->lanes[0].d_frames, rgb, bytes, hipMemcpyHostToDevice));   // (lane 0's staging area: its stream was drained above)
+    const uint8_t* p = e->lanes[0].d_frames;
     WZCHK(fill_desc(e, 0, 1, &p, &w, &h, &fmt, nullptr));
-    HIPCHK(hipMemcpyAsync(e->lanes[0].d_desc, e->lanes[0].h_desc, sizeof(WzFrameDesc), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->lanes[0].d_desc, e->lanes[0].desc.h, sizeof(WzFrameDesc), hipMemcpyHostToDevice, e->stream));
     const int S = (int)e->hdr.input_size;
     wz_launch_preprocess(e->lanes[0].d_desc, 1, S, e->lanes[0].tptr[input_tensor_index(e)], e->stream, input_is_pair(e), nullptr,
                          e->hdr.resize_mode == 1, nullptr, e->pre_rows && rows_fit(e, 1, &w, &fmt) ? e->pre_rows_lds : 0);
@@ -1369,8 +1288,8 @@ extern "C" int wz_stage_preprocess_fmt(wz_engine_t* e, const uint8_t* rgb, int w
 }
 
 extern "C" int wz_stage_forward(wz_engine_t* e, int n, const uint16_t* in_half, float* box_enc, float* logits) {
-    if (!e || !in_half) return wz_fail(WZ_EINVAL, "wz_stage_forward: null argument");
-    if (n < 1 || n > e->max_batch) return wz_fail(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
+    if (!e || !in_half) return wz_set_error(WZ_EINVAL, "wz_stage_forward: null argument");
+    WZCHK(batch_refusal(e, 0, n, BC_N));
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     const int S = (int)e->hdr.input_size;
@@ -1391,11 +1310,11 @@ extern "C" int wz_stage_forward(wz_engine_t* e, int n, const uint16_t* in_half, 
 }
 
 extern "C" int wz_stage_block_at(wz_engine_t* e, int op, int n, const void* d_in, int launch_frames) {
-    if (!e || !d_in || op < 0 || op >= (int)e->hdr.n_ops || launch_frames < 0) return wz_fail(WZ_EINVAL, "wz_stage_block_at: bad argument");
-    if (n < 1 || n > e->max_batch) return wz_fail(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
+    if (!e || !d_in || op < 0 || op >= (int)e->hdr.n_ops || launch_frames < 0) return wz_set_error(WZ_EINVAL, "wz_stage_block_at: bad argument");
+    WZCHK(batch_refusal(e, 0, n, BC_N));
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (enqueue_block_at(e, e->lanes[0], n, (uint32_t)op, d_in, launch_frames) != 0) return wz_fail(WZ_EINVAL, "wz_stage_block_at: op %d is not a fused block with a kernel", op);
+    if (enqueue_block_at(e, e->lanes[0], n, (uint32_t)op, d_in, launch_frames) != 0) return wz_set_error(WZ_EINVAL, "wz_stage_block_at: op %d is not a fused block with a kernel", op);
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipGetLastError());
     return WZ_OK;
@@ -1403,7 +1322,7 @@ extern "C" int wz_stage_block_at(wz_engine_t* e, int op, int n, const void* d_in
 
 extern "C" int wz_stage_read_tensor(wz_engine_t* e, int idx, int frame, uint16_t* out_half) {
     if (!e || !out_half || idx < 0 || idx >= (int)e->hdr.n_tensors || frame < 0 || frame >= e->max_batch)
-        return wz_fail(WZ_EINVAL, "wz_stage_read_tensor: bad argument");
+        return wz_set_error(WZ_EINVAL, "wz_stage_read_tensor: bad argument");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     const size_t per = tensor_frame_bytes(e, idx);   // a pair tensor: 2c halves per pixel, hi then lo
@@ -1413,8 +1332,8 @@ extern "C" int wz_stage_read_tensor(wz_engine_t* e, int idx, int frame, uint16_t
 
 extern "C" int wz_stage_postprocess(wz_engine_t* e, int n, const float* box_enc, const float* logits, float* boxes,
                                     float* scores, int32_t* classes, int32_t* num) {
-    if (!e || !box_enc || !logits) return wz_fail(WZ_EINVAL, "wz_stage_postprocess: null argument");
-    if (n < 1 || n > e->max_batch) return wz_fail(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
+    if (!e || !box_enc || !logits) return wz_set_error(WZ_EINVAL, "wz_stage_postprocess: null argument");
+    WZCHK(batch_refusal(e, 0, n, BC_N));
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     const size_t A = e->hdr.num_anchors, C = e->hdr.num_classes, T = e->hdr.max_total;
@@ -1436,9 +1355,9 @@ extern "C" int wz_stage_postprocess(wz_engine_t* e, int n, const float* box_enc,
 // the NMS kernel reads its first band from the bit map and writes the rows.
 extern "C" int wz_stage_post_production(wz_engine_t* e, int n, const float* box_enc, const float* logits, int w, int h,
                                         wz_detection_t* rows) {
-    if (!e || !box_enc || !logits || !rows) return wz_fail(WZ_EINVAL, "wz_stage_post_production: null argument");
-    if (n < 1 || n > e->max_batch) return wz_fail(WZ_ELIMIT, "batch %d exceeds max_batch %d", n, e->max_batch);
-    if (e->hdr.max_total != WZ_MAX_DETECTIONS) return wz_fail(WZ_EINVAL, "wz_stage_post_production: max_total %d, expected %d", (int)e->hdr.max_total, WZ_MAX_DETECTIONS);
+    if (!e || !box_enc || !logits || !rows) return wz_set_error(WZ_EINVAL, "wz_stage_post_production: null argument");
+    WZCHK(batch_refusal(e, 0, n, BC_N));
+    if (e->hdr.max_total != WZ_MAX_DETECTIONS) return wz_set_error(WZ_EINVAL, "wz_stage_post_production: max_total %d, expected %d", (int)e->hdr.max_total, WZ_MAX_DETECTIONS);
     HIPCHK(hipSetDevice(e->device));
     Lane& L = e->lanes[0];
     HIPCHK(hipStreamSynchronize(L.stream));
@@ -1454,10 +1373,10 @@ extern "C" int wz_stage_post_production(wz_engine_t* e, int n, const float* box_
         const int apl = op.anchors_per_loc, hw = op.hout * op.wout;
         if (op.out_mode != WZ_OUT_HEAD || g.n >= WZ_REDUCE_GROUP_MAX || op.n_box != apl * 4 || op.cout != apl * (4 + (int)C) ||
             op.n_pad < op.cout || (size_t)op.n_pad * 4 > 4096 || (size_t)op.anchor_off + (size_t)hw * apl > A)
-            return wz_fail(WZ_EINVAL, "wz_stage_post_production: op %d (%s) is no [box | class] head this entry can feed", i, op.name);
+            return wz_set_error(WZ_EINVAL, "wz_stage_post_production: op %d (%s) is no [box | class] head this entry can feed", i, op.name);
         WzConvArgs a = conv_args(e, L, op, n);   // (the grouped reduce reads the epilogue's part of it)
         head_outputs(e, L, op, a);
-        a.bias = reinterpret_cast<const float*>(e->d_zeros);   // 4 KiB of zeros: n_pad floats at most (checked above)
+        a.bias = reinterpret_cast<const float*>(e->d_zeros.p);   // 4 KiB of zeros: n_pad floats at most (checked above)
         a.splitk = 1;
         offs.push_back(host.size());
         host.resize(host.size() + (size_t)a.M * a.n_pad, 0.0f);
@@ -1472,11 +1391,10 @@ extern "C" int wz_stage_post_production(wz_engine_t* e, int n, const float* box_
         wz_reduce_group_add(g, a, nullptr);
         covered += (size_t)hw * apl;
     }
-    if (g.n == 0 || covered != A) return wz_fail(WZ_EINVAL, "wz_stage_post_production: the heads cover %zu of %zu anchors", covered, A);
-    float* d_part = nullptr;
-    HIPCHK(hipMalloc((void**)&d_part, host.size() * sizeof(float)));
-    auto done = [&](int rc) { (void)hipFree(d_part); return rc; };
-    if (hipMemcpy(d_part, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return done(wz_fail(WZ_EHIP, "wz_stage_post_production: upload"));
+    if (g.n == 0 || covered != A) return wz_set_error(WZ_EINVAL, "wz_stage_post_production: the heads cover %zu of %zu anchors", covered, A);
+    DevBlock<float> d_part;
+    HIPCHK(d_part.alloc(host.size()));
+    if (hipMemcpy(d_part, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return wz_set_error(WZ_EHIP, "wz_stage_post_production: upload");
     for (int i = 0; i < g.n; ++i) g.ws[i] = d_part + offs[i];
     g.decode = 1;
     g.list = 1;
@@ -1488,40 +1406,40 @@ extern "C" int wz_stage_post_production(wz_engine_t* e, int n, const float* box_
     g.boxes = L.post.boxes;
     g.valid = L.post.valid;
     for (int i = 0; i < n; ++i) {
-        WzFrameDesc& d = L.h_desc[i];
+        WzFrameDesc& d = L.desc.h[i];
         memset(&d, 0, sizeof(d));
         d.w = w;
         d.h = h;
         d.cam = -1;
     }
-    if (hipMemcpyAsync(L.d_desc, L.h_desc, sizeof(WzFrameDesc) * n, hipMemcpyHostToDevice, L.stream) != hipSuccess) return done(wz_fail(WZ_EHIP, "wz_stage_post_production: descriptors"));
+    if (hipMemcpyAsync(L.d_desc, L.desc.h, sizeof(WzFrameDesc) * n, hipMemcpyHostToDevice, L.stream) != hipSuccess) return wz_set_error(WZ_EHIP, "wz_stage_post_production: descriptors");
     wz_launch_splitk_reduce_group(g, L.stream);
     enqueue_post(e, L, true, n, nullptr, true, true);
     L.key = n;
-    L.post_modes[L.key] = 3;   // (wz_debug_post_lane: these launches decoded in the reduce and listed the candidates)
-    if (hipStreamSynchronize(L.stream) != hipSuccess || hipGetLastError() != hipSuccess) return done(wz_fail(WZ_EHIP, "wz_stage_post_production: launch"));
-    memcpy(rows, L.h_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS * n);
-    return done(WZ_OK);
+    L.forms[L.key].post_mode = 3;   // (wz_debug_post_lane: these launches decoded in the reduce and listed the candidates)
+    if (hipStreamSynchronize(L.stream) != hipSuccess || hipGetLastError() != hipSuccess) return wz_set_error(WZ_EHIP, "wz_stage_post_production: launch");
+    memcpy(rows, L.hrows.h, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS * n);
+    return WZ_OK;
 }
 
 extern "C" int wz_stage_rows(wz_engine_t* e, int w, int h, const float* boxes, const float* scores,
                              const int32_t* classes, wz_detection_t* rows) {
-    if (!e || !boxes || !scores || !classes || !rows) return wz_fail(WZ_EINVAL, "wz_stage_rows: null argument");
+    if (!e || !boxes || !scores || !classes || !rows) return wz_set_error(WZ_EINVAL, "wz_stage_rows: null argument");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     const size_t T = e->hdr.max_total;
     HIPCHK(hipMemcpy(e->lanes[0].post.det_boxes, boxes, T * 16, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->lanes[0].post.det_scores, scores, T * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->lanes[0].post.det_classes, classes, T * 4, hipMemcpyHostToDevice));
-    WzFrameDesc& d = e->lanes[0].h_desc[0];
+    WzFrameDesc& d = e->lanes[0].desc.h[0];
     memset(&d, 0, sizeof(d));
     d.w = w;
     d.h = h;
     d.cam = -1;
-    HIPCHK(hipMemcpyAsync(e->lanes[0].d_desc, e->lanes[0].h_desc, sizeof(WzFrameDesc), hipMemcpyHostToDevice, e->stream));
-    wz_launch_rows(e->lanes[0].post, e->lanes[0].d_desc, e->d_cams, 1, e->pc.max_total, e->lanes[0].d_rows, e->lanes[0].d_pass, e->stream);
+    HIPCHK(hipMemcpyAsync(e->lanes[0].d_desc, e->lanes[0].desc.h, sizeof(WzFrameDesc), hipMemcpyHostToDevice, e->stream));
+    wz_launch_rows(e->lanes[0].post, e->lanes[0].d_desc, e->d_cams, 1, e->pc.max_total, e->d_tmp_rows, e->d_tmp_pass, e->stream);
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(rows, e->lanes[0].d_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rows, e->d_tmp_rows, sizeof(wz_detection_t) * WZ_MAX_DETECTIONS, hipMemcpyDeviceToHost));
     return WZ_OK;
 }
 #endif   // WZ_DEV_BUILD

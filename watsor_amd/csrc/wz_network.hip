@@ -241,7 +241,7 @@ struct HeadPark {
         bytes = (bytes + 255) & ~(size_t)255;
         if (!e->defer_heads || op.out_mode == WZ_OUT_ACT || heads.n >= WZ_REDUCE_GROUP_MAX || bytes + (e->ws_bytes >> 1) > ws_top) return nullptr;
         ws_top -= bytes;
-        return reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(L.d_ws) + ws_top);
+        return reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(L.d_ws.p) + ws_top);
     }
     // ... and the reduce of what was parked there: `a` with its final outputs
     void reduce_later(const WzOpDesc& op, const WzConvArgs& a, const float* parked) {

@@ -144,9 +144,7 @@ struct TileCall {
 
 static int call_refusal(const wz_engine* e, const char* who, int slot, const TileCall& c, bool tiled) {
     if (!e || !c.frames || !c.w || !c.h || (tiled && (!c.n_tiles || !c.tiles))) return wz_set_error(WZ_EINVAL, "%s: null argument", who);
-    if (slot < 0 || slot >= e->n_lanes) return wz_set_error(WZ_EINVAL, "slot %d out of range [0,%d)", slot, e->n_lanes);
-    if (c.n < 1 || c.n > e->max_batch) return wz_set_error(WZ_ELIMIT, "batch %d exceeds max_batch %d", c.n, e->max_batch);
-    return WZ_OK;
+    return batch_refusal(e, slot, c.n);
 }
 static int thresholds_refusal(const char* who, const TileCall& c) {
     if (!(c.iou >= 0.0) || !(c.ios >= 0.0)) return wz_set_error(WZ_EINVAL, "%s: the merge thresholds must be numbers >= 0", who);
@@ -246,7 +244,7 @@ static void tile_plan(wz_engine* e, Lane& L, const TileCall& c, const uint8_t* r
     }
 }
 
-// The plan's tiles as an ordinary batch without cameras: crop, then 100 unfiltered rows per tile, in tile pixel coordinates, in L.h_rows.
+// The plan's tiles as an ordinary batch without cameras: crop, then 100 unfiltered rows per tile, in tile pixel coordinates, in L.hrows.h.
 // No tile runs (a gated call of still tiles, a motion call of still frames): no crop, no batch, no status word is this call's.
 static int run_tiles(wz_engine* e, int slot, const TilePlan& y) {
     Lane& L = e->lanes[slot];
@@ -304,7 +302,7 @@ static int tiled_enqueue(wz_engine* e, int slot, const TileCall& c) {
     TilePlan y;
     tile_plan(e, L, c, nullptr, y);
     WZCHK(run_tiles(e, slot, y));
-    return merge_tail(e, L, c, y.most, L.m_rows);
+    return merge_tail(e, L, c, y.most, L.hrows.d);
 }
 
 // ---- gated tiled detection: activity launch -> the host decides which tiles run -> crop + batch of those -> commit + merge (k_gate.hip,
@@ -365,7 +363,7 @@ static int gated_enqueue(wz_engine* e, int slot, const TileCall& call) {
     // 3. the tiles that run, as an ordinary batch without cameras (none: no crop, no batch)
     WZCHK(run_tiles(e, slot, y));
     // 4. commit, merge, filters
-    wz_launch_gate_commit(G.meta.m.commits, total, L.m_rows, G.d_grows, L.stream);
+    wz_launch_gate_commit(G.meta.m.commits, total, L.hrows.d, G.d_grows, L.stream);
     WZCHK(merge_tail(e, L, c, y.most, G.d_grows));
     // 5. the state the commit launch leaves behind, and what wz_gate_stats reports
     G.g_ran.assign(n, 0);
@@ -499,7 +497,7 @@ static int motion_enqueue(wz_engine* e, int slot, const TileCall& call) {
     TilePlan y;
     tile_plan(e, L, c, nullptr, y);
     WZCHK(run_tiles(e, slot, y));
-    WZCHK(merge_tail(e, L, c, y.most, L.m_rows, still, stamps ? M.meta.m.cams : nullptr));
+    WZCHK(merge_tail(e, L, c, y.most, L.hrows.d, still, stamps ? M.meta.m.cams : nullptr));
     // 4. the grids this call wrote are the next call's reference and ages; what wz_motion_stats and wz_motion_hold_stats report
     for (int i = 0; i < n; ++i) {
         cams[i]->cur ^= 1;
@@ -542,12 +540,7 @@ static int detect_staged(wz_engine* e, TileCall& c, int kind, wz_detection_t* co
     for (int i = 0; i < c.n; ++i) WZCHK(stage_frame(e, L, i, c.frames[i], wz_frame_bytes(c.w[i], c.h[i], c.pf(i)), &dptr[i]));
     c.frames = dptr.data();
     WZCHK(enqueue(e, 0, c, kind));
-    const int rc = wz_collect(e, 0, out, pass);
-    if (rc != WZ_OK && rc != WZ_EINCOMPLETE) return rc;
-    const float el = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (ms)
-        for (int i = 0; i < c.n; ++i) ms[i] = el;
-    return rc;   // WZ_OK, or WZ_EINCOMPLETE: the merged rows are written, the rows of a tile that ran in this call may have been short
+    return collect_timed(e, c.n, out, pass, ms, t0);   // WZ_OK, or WZ_EINCOMPLETE: the merged rows are written, the rows of a tile that ran in this call may have been short
 }
 
 extern "C" int wz_submit_tiled_device(wz_engine_t* e, int slot, int n, const uint8_t* const* d_frames, const int* w, const int* h,
@@ -1035,7 +1028,7 @@ extern "C" int wz_profile_tiled(wz_engine_t* e, int n, const uint8_t* const* d_f
     tile_plan(e, L, c, nullptr, y);
     const TileLane& T = L.tile;
     WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_crop_tiles(y.planes.data(), (int)y.planes.size(), L.stream); }, crop_ms));
-    WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_merge_tiles(T.meta.m.frames, T.meta.m.origins, L.m_rows, T.d_tcand, n, y.most, iou_thr, ios_thr, T.trows.d, T.tpass.d, L.stream); },
+    WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_merge_tiles(T.meta.m.frames, T.meta.m.origins, L.hrows.d, T.d_tcand, n, y.most, iou_thr, ios_thr, T.trows.d, T.tpass.d, L.stream); },
                      merge_ms));
     return bracket_ms(L.stream, reps, [] {}, empty_ms);   // (two event records with nothing between them: the bracket's own cost)
 }
@@ -1050,7 +1043,7 @@ extern "C" int wz_profile_gated(wz_engine_t* e, int n, const uint8_t* const* d_f
     Lane& L = e->lanes[0];
     const GateLane& G = L.gate;
     WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_tile_activity(G.meta.m.tiles, G.g_tiles, G.g_crows, G.g_cols, G.d_gcount, G.meta.m.activity, L.stream); }, activity_ms));
-    WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_gate_commit(G.meta.m.commits, G.g_tiles, L.m_rows, G.d_grows, L.stream); }, commit_ms));
+    WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_gate_commit(G.meta.m.commits, G.g_tiles, L.hrows.d, G.d_grows, L.stream); }, commit_ms));
     return bracket_ms(L.stream, reps, [] {}, empty_ms);
 }
 
