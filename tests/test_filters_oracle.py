@@ -177,3 +177,113 @@ def test_thin_zone_raises_zero_division_like_the_reference():
         zones_from_alpha(alpha)
     with pytest.raises(ZeroDivisionError):
         oz.zone_polygons(alpha)
+
+
+# ---- zones at the frame's edges, the zone limit and the order of equal keys ----------------------------------------------------
+def assert_zones_match_oracle(alpha):
+    """Fill, order and centroids of `zones_from_alpha` against the oracle's polygons; returns the product's (fill, centroids)."""
+    fill, cent = zones_from_alpha(alpha)
+    ofill = oz.zone_fill(alpha)
+    assert fill.shape == ofill.shape
+    np.testing.assert_array_equal(fill, ofill)
+    for z, poly in enumerate(oz.zone_polygons(alpha)):
+        m00, m10, m01 = oz.contour_moments(poly)
+        assert (int(m10 / m00), int(m01 / m00)) == tuple(cent[z])
+    return fill, cent
+
+
+def blank(h, w):
+    return np.full((h, w), 100, np.uint8)
+
+
+def test_zones_in_all_four_frame_corners():
+    alpha = blank(16, 20)
+    alpha[:3, :3] = alpha[:3, -4:] = alpha[-2:, :3] = alpha[-3:, -3:] = 255
+    fill, _ = assert_zones_match_oracle(alpha)
+    assert fill.shape[0] == 4 and fill[0][0, 0] and fill[:, 0, 19].any() and fill[:, 15, 0].any() and fill[3][15, 19]
+    assert sorted(int(f.sum()) for f in fill) == [6, 9, 9, 12]
+
+
+def test_all_opaque_frame_and_two_by_two():
+    for h, w in ((5, 7), (2, 2), (2, 9), (9, 2)):
+        fill, cent = assert_zones_match_oracle(np.full((h, w), 255, np.uint8))
+        assert fill.shape[0] == 1 and fill.all()
+    assert tuple(cent[0]) == (0, 4)                                      # int(0.5), int(4.0)
+
+
+def test_ring_along_the_border_with_an_island_is_one_zone():
+    alpha = blank(10, 12)
+    alpha[0, :] = alpha[-1, :] = alpha[:, 0] = alpha[:, -1] = 255
+    alpha[4:6, 5:8] = 255                                                # nested in the ring's hole: RETR_EXTERNAL does not report it
+    fill, _ = assert_zones_match_oracle(alpha)
+    assert fill.shape[0] == 1 and fill.all()
+
+
+def test_u_open_to_the_top_edge_is_not_filled():
+    alpha = blank(9, 11)
+    alpha[0:7, 2] = alpha[0:7, 8] = 255
+    alpha[6, 2:9] = 255
+    fill, _ = assert_zones_match_oracle(alpha)
+    assert fill.shape[0] == 1 and int(fill.sum()) == 7 + 7 + 5 and not fill[0][3, 5]
+    alpha[0, 2:9] = 255                                                  # closed: now the inside belongs to the zone
+    fill, _ = assert_zones_match_oracle(alpha)
+    assert fill.shape[0] == 1 and int(fill.sum()) == 7 * 7
+
+
+def test_equal_keys_the_later_found_zone_first():
+    alpha = blank(16, 16)
+    alpha[2:5, 10:13] = 255                                              # centroid (11, 3), found first
+    alpha[10:13, 2:5] = 255                                              # centroid (3, 11): the same key
+    fill, cent = assert_zones_match_oracle(alpha)
+    assert [tuple(c) for c in cent] == [(3, 11), (11, 3)] and fill[0][11, 3] and fill[1][3, 11]
+
+
+def test_forty_zones_and_forty_one_refused():
+    import filter_cases as fc
+    fill, cent = assert_zones_match_oracle(fc.cap_alpha(40))
+    assert fill.shape[0] == 40 and [tuple(c) for c in cent] == [(4 * k + 1, 4) for k in range(40)]
+    assert len(oz.zone_polygons(fc.cap_alpha(41))) == 41
+    with pytest.raises(ValueError):
+        zones_from_alpha(fc.cap_alpha(41))
+
+
+def test_ellipses_with_centres_on_the_border():
+    h, w = 40, 56
+    yy, xx = np.mgrid[0:h, 0:w]
+    compared = touching = 0
+    for seed in range(8):
+        rng = np.random.default_rng(300 + seed)
+        alpha = blank(h, w)
+        for _ in range(4):
+            cy, cx = int(rng.choice([0, h - 1, rng.integers(0, h)])), int(rng.choice([0, w - 1, rng.integers(0, w)]))
+            ry, rx = int(rng.integers(2, h // 4)), int(rng.integers(2, w // 4))
+            alpha[((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 <= 1] = 255
+        try:
+            oz.zone_polygons(alpha)
+        except ZeroDivisionError:                                        # a sliver of an ellipse: the reference raises, so must the product
+            with pytest.raises(ZeroDivisionError):
+                zones_from_alpha(alpha)
+            continue
+        fill, _ = assert_zones_match_oracle(alpha)
+        compared += 1
+        touching += int(fill[:, 0, :].any() or fill[:, -1, :].any() or fill[:, :, 0].any() or fill[:, :, -1].any())
+    assert compared >= 6 and touching >= 6
+
+
+def test_checkerboard_is_one_eight_connected_zone():
+    yy, xx = np.mgrid[0:8, 0:10]
+    alpha = np.where((yy + xx) % 2 == 0, 255, 100).astype(np.uint8)
+    fill, _ = assert_zones_match_oracle(alpha)
+    assert fill.shape[0] == 1
+    inner = fill[0][1:-1, 1:-1]
+    assert inner.all() and fill[0][alpha == 255].all() and not fill[0][0, 1] and not fill[0][1, 0]
+
+
+def test_one_pixel_frame_and_diagonal_line_raise_zero_division():
+    line = blank(12, 12)
+    line[np.arange(2, 9), np.arange(2, 9)] = 255
+    for alpha in (np.full((1, 1), 255, np.uint8), line):
+        with pytest.raises(ZeroDivisionError):
+            zones_from_alpha(alpha)
+        with pytest.raises(ZeroDivisionError):
+            oz.zone_polygons(alpha)

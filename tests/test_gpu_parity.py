@@ -398,6 +398,43 @@ def test_row_fill_bit_exact(eng, head_outputs, wh):
     assert not rows["zones"].any() and not rows["_pad"].any()
 
 
+def _coordinates_outside_the_unit_square(dim):
+    """float32 box values for one axis of a `dim`-pixel frame: below 0, above 1, signed zero, and for integers k on both sides of 0 and
+    of dim - 1 the float32 neighbours of k / (dim - 1).  The row fill takes float32 boxes and their product with dim - 1 is exact in
+    double (24 + 12 bits), so these neighbours are the closest a product can come to an integer from either side -- no float32 value
+    puts it one float64 ulp away."""
+    f = np.float32
+    vals = [f(-0.3), f(-1e-7), f(-0.0), f(1) + f(2.0 ** -23), f(2.5), f(-3.75), f(0.0), f(1.0)]
+    m = dim - 1
+    for k in (1, 2, m // 3, m - 1, m, m + 1, 2 * m + 1, -1, -2, -m, -m - 1, -3 * m - 2) if m else ():
+        v = f(k / m)
+        vals += [np.nextafter(v, f(-np.inf)), v, np.nextafter(v, f(np.inf))]
+    return np.array(vals, f)
+
+
+@pytest.mark.parametrize("wh", [(1, 1), (2, 2), (640, 480), (3840, 2160)])
+def test_row_fill_outside_the_unit_square(eng, wh):
+    """`wz_make_row` clamps nothing (tensorflow_cpu.py:79-90 does not either): boxes below 0 and above 1 truncate toward zero."""
+    xs, ys = _coordinates_outside_the_unit_square(wh[0]), _coordinates_outside_the_unit_square(wh[1])
+    assert len(xs) <= 100 and len(ys) <= 100
+    i = np.arange(100)
+    boxes = np.stack([ys[i % len(ys)], xs[i % len(xs)], ys[(i + 5) % len(ys)], xs[(i + 11) % len(xs)]], 1)
+    scores = np.linspace(1, 0, 100, dtype=np.float32)
+    classes = (1 + i % 90).astype(np.float32)
+    ref = odet.rows_as_array((wh[1], wh[0], 3), boxes, classes, scores)
+    exact = boxes.astype(np.float64) * np.array([wh[1] - 1, wh[0] - 1, wh[1] - 1, wh[0] - 1], np.float64)
+    assert np.abs(exact).max() < 2 ** 31
+    if wh[0] > 2:                                                 # products on both sides of integers, negative ones included
+        frac = exact - np.trunc(exact)
+        assert (frac > 0.999).any() and ((frac > 0) & (frac < 0.001)).any() and (frac < -0.999).any() and ((frac < 0) & (frac > -0.001)).any()
+        assert (ref["box"] < 0).any() and (ref["box"][:, 0] >= wh[0]).any() and (ref["box"][:, 1] >= wh[1]).any()
+    rows = eng.stage_rows(wh[0], wh[1], boxes, scores, classes)
+    np.testing.assert_array_equal(rows["label"], ref["label"])
+    np.testing.assert_array_equal(rows["confidence"], ref["confidence"])
+    np.testing.assert_array_equal(np.stack([rows["x_min"], rows["y_min"], rows["x_max"], rows["y_max"]], 1), ref["box"])
+    assert not rows["zones"].any() and not rows["_pad"].any()
+
+
 def test_detect_end_to_end_matches_oracle_detector(model_dir, synth_weights, frames_640):
     """`detect()` through the plugin class on full-resolution frames vs the oracle plugin: the north star's tolerance
     (|dscore| <= 1e-3 on every matched detection row, boxes within `box_tolerance_px`, no unexplained row) on 9 frames over

@@ -1015,8 +1015,14 @@ __device__ void wz_apply_filter(const WzCamFilter& cf, wz_detection_t& d, uint8_
     }
     if (ok) {
         const double at = cf.area_thr[d.label];            // area.py:19-26
-        long long ar = (long long)(d.x_max - d.x_min + 1) * (long long)(d.y_max - d.y_min + 1);
-        if (ar < 0) ar = -ar;
+        // the reference multiplies Python integers: each extent is widened BEFORE the subtraction (any two int32 corners give
+        // |extent| <= 2^32), the magnitudes are multiplied as unsigned 64-bit words and a product past INT64_MAX (2^64 at most)
+        // saturates there -- (double)INT64_MAX = 2^63 is >= every threshold below 2^63, so the comparison stays exact
+        const long long ex = (long long)d.x_max - (long long)d.x_min + 1, ey = (long long)d.y_max - (long long)d.y_min + 1;
+        const unsigned long long ax = ex < 0 ? 0ull - (unsigned long long)ex : (unsigned long long)ex;
+        const unsigned long long ay = ey < 0 ? 0ull - (unsigned long long)ey : (unsigned long long)ey;
+        const unsigned long long lo = ax * ay, hi = __umul64hi(ax, ay);
+        const long long ar = (hi != 0ull || lo > 0x7fffffffffffffffull) ? 0x7fffffffffffffffll : (long long)lo;
         ok = (at == at) && (double)ar >= at;
     }
     if (ok && (cf.n_zones > 0 || (cf.enabled & 4))) {      // mask.py:44-59 (bit 2: a mask WITHOUT zones -- nothing can hit)
