@@ -167,6 +167,9 @@ def test_frame_geometry_of_10_bit_frames():
                     z8(720, 641, 2), z8(722, 1280), z16(720), z8(720, 640, 2, 1), z16(720, 640).astype(np.int16), z16(720, 640).astype(np.float32)):
             with pytest.raises(ValueError):
                 g(bad, word)
+        for bad in (z8(6, 4, 0), z16(6, 4, 0), z8(720, 1280, 0), z16(0, 0), z8(0, 0), z8(0, 4, 2), z16(3, 0), z8(3, 0, 2)):   # empty arrays hold no frame
+            with pytest.raises(ValueError):
+                g(bad, word)
     # uint16 is these two formats' only; unknown bases and bits stay refused
     for word in (FMT_RGB24, FMT_NV12, FMT_I420, FMT_YUYV422, 5, 6):
         with pytest.raises(ValueError):
@@ -175,6 +178,31 @@ def test_frame_geometry_of_10_bit_frames():
         for f in (z16(720, 640), z8(720, 1280)):
             with pytest.raises(ValueError):
                 g(f, word)
+
+
+def test_the_one_shape_rule_behind_arrays_and_frame_buffers():
+    """`runtime.frame_shape`: what `frame_geometry` asks with an array's shape (channels None: no channel axis) and the frame table with a
+    frame buffer's header (its one-channel image counts as 2-D).  Known answers per format, the shapes only one of the two takes, and
+    a channel axis of length 0 -- an empty array, never "no channel axis"."""
+    from watsor_amd.runtime import FMT_BGR24, FMT_GRAY8, FMT_UYVY422, FMT_YUYV422, frame_shape as fs
+    assert fs(FMT_RGB24, 480, 640, 3, 1) == fs(FMT_BGR24, 480, 640, 3, 1) == (640, 480)
+    assert fs(FMT_RGB24, 480, 640, None, 1) is None and fs(FMT_RGB24, 480, 640, 1, 1) is None and fs(FMT_RGB24, 480, 640, 3, 2) is None
+    assert fs(FMT_GRAY8, 481, 643, None, 1) == fs(FMT_GRAY8, 481, 643, 1, 1) == (643, 481) and fs(FMT_GRAY8, 481, 643, 3, 1) is None
+    for f in (FMT_YUYV422, FMT_UYVY422):
+        assert fs(f, 481, 640, 2, 1) == (640, 481) and fs(f, 481, 1280, None, 1) == (640, 481)
+        assert fs(f, 481, 641, 2, 1) is None and fs(f, 481, 1282, None, 1) is None
+        assert fs(f, 481, 1280, 1, 1) is None                  # (H, 2W, 1) is no ARRAY of 4:2:2; the frame table passes None for its one channel
+    for f in (FMT_NV12, FMT_I420):
+        assert fs(f, 720, 640, None, 1) == fs(f, 720, 640, 1, 1) == (640, 480)
+        assert all(fs(f, r, c, ch, 1) is None for r, c, ch in ((721, 640, None), (722, 640, None), (720, 641, None), (720, 640, 2), (720, 640, 3)))
+        assert fs(f, 720, 640, None, 2) is None                # 16-bit items are the 10-bit formats' only
+    for f in (FMT_P010, FMT_YUV420P10):
+        assert fs(f, 720, 640, None, 2) == fs(f, 720, 640, 1, 2) == fs(f, 720, 640, 2, 1) == fs(f, 720, 1280, None, 1) == fs(f, 720, 1280, 1, 1) == (640, 480)
+        assert all(fs(f, r, c, ch, i) is None for r, c, ch, i in ((720, 640, 2, 2), (720, 1282, None, 1), (720, 1281, 1, 1), (720, 641, 2, 1),
+                                                                 (722, 1280, None, 1), (720, 640, 3, 1), (720, 640, None, 4)))
+    assert fs(7, 480, 640, 3, 1) is None and fs(0x12, 720, 640, None, 2) is None
+    for f in (FMT_RGB24, FMT_BGR24, FMT_GRAY8, FMT_YUYV422, FMT_UYVY422, FMT_NV12, FMT_I420, FMT_P010, FMT_YUV420P10):
+        assert fs(f, 6, 4, 0, 1) is None and fs(f, 6, 4, 0, 2) is None and fs(f, 720, 1280, 0, 1) is None, f
 
 
 class _Frame:
@@ -217,3 +245,12 @@ def test_frame_table_of_10_bit_cameras(tmp_path, monkeypatch):
                         ("hw", _Frame(130, 72, 1, nb + 999))):
         with pytest.raises(ValueError):
             det.bind_frame_table(dict(buffers, **{name: fb(frame)}), ids)
+    # a header with 0 channels is no one-channel image: each family's own refusal, as before the shape rule was shared
+    for name, frame, text in (("hw", _Frame(128, 72, 0, nb), "P010 / YUV420P10 frame buffer must be"), ("door", _Frame(64, 48, 0, nb), "must have 3 channels")):
+        with pytest.raises(ValueError, match=text):
+            det.bind_frame_table(dict(buffers, **{name: fb(frame)}), ids)
+    # a base format the library does not know: held to three channels, then the library's sizing refuses it in its own words
+    det._HipObjectDetector__fmt_by_cam[0] = 9
+    for channels, text in ((3, "pixel format word 0x9 is not taken at 64x48"), (1, "must have 3 channels")):
+        with pytest.raises(ValueError, match=text):
+            det.bind_frame_table(dict(buffers, hw=fb(_Frame(64, 48, channels, nb))), ids)

@@ -116,13 +116,14 @@ def test_frame_geometry_of_the_new_shapes():
     for word in (FMT_YUYV422, FMT_UYVY422, FMT_YUYV422 | CSP_BT709, FMT_UYVY422 | RANGE_FULL | CSP_BT709):
         assert g(z(480, 640, 2), word) == (640, 480)
         assert g(z(481, 1280), word) == (640, 481)                               # (H, 2W), odd height
-        for bad in (z(480, 641, 2), z(480, 1282), z(480, 640, 3), z(480, 640, 1)):
+        for bad in (z(480, 641, 2), z(480, 1282), z(480, 640, 3), z(480, 640, 1), z(6, 4, 0), z(480, 1280, 0)):
             with pytest.raises(ValueError):
                 g(bad, word)
     assert g(z(481, 643), FMT_GRAY8) == (643, 481) and g(z(481, 643, 1), FMT_GRAY8) == (643, 481)
     assert g(z(481, 643, 3), FMT_BGR24) == (643, 481)
     assert g(z(720, 640), FMT_NV12 | CSP_BT709) == (640, 480) and g(z(720, 640), FMT_I420 | RANGE_FULL) == (640, 480)
-    for bad, word in ((z(480, 640, 3), FMT_GRAY8), (z(480, 640), FMT_BGR24), (z(480, 640, 3), FMT_RGB24 | CSP_BT709),
+    for bad, word in ((z(6, 4, 0), FMT_GRAY8), (z(6, 4, 0), FMT_NV12), (z(6, 4, 0), FMT_I420), (z(6, 4, 0), FMT_RGB24), (z(6, 4, 0), FMT_BGR24),
+                      (z(480, 640, 3), FMT_GRAY8), (z(480, 640), FMT_BGR24), (z(480, 640, 3), FMT_RGB24 | CSP_BT709),
                       (z(480, 640), FMT_GRAY8 | RANGE_FULL), (z(480, 640, 3), FMT_BGR24 | CSP_BT709), (z(720, 640), FMT_NV12 | 0x400),
                       (z(480, 640, 3), 9), (z(480, 640, 3), 7), (z(480, 640, 2).astype(np.float32), FMT_YUYV422)):
         with pytest.raises(ValueError):

@@ -23,8 +23,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from ..runtime import (CSP_BT709, FMT_BASE_MASK, FMT_GRAY8, FMT_I420, FMT_NV12, FMT_P010, FMT_RGB24, FMT_UYVY422, FMT_YUV420P10,
-                       FMT_YUYV422, RANGE_FULL, TEN_BIT_FORMATS, YUV_FORMATS, HipEngine, tile_grid)
+from ..runtime import (CSP_BT709, FMT_BASE_MASK, FMT_BGR24, FMT_GRAY8, FMT_I420, FMT_NV12, FMT_P010, FMT_RGB24, FMT_UYVY422, FMT_YUV420P10,
+                       FMT_YUYV422, RANGE_FULL, TEN_BIT_FORMATS, YUV_FORMATS, HipEngine, frame_shape, tile_grid)
 from .._lib import WZ_MAX_TILES, WZ_MOTION_MAX_REGIONS
 from ..share import Detection
 
@@ -82,6 +82,15 @@ def _planar_format(default: int, by_camera: dict) -> int:
     (NV12 if none is).  Only NV12 / I420 have that shape -- a configured gray or 4:2:2 camera is never the answer, and neither is a
     10-bit one (p010le / yuv420p10le are taken by configuration only)."""
     return next((f for f in [default] + list(by_camera.values()) if (f & FMT_BASE_MASK) in (FMT_NV12, FMT_I420)), FMT_NV12)
+
+
+_TABLE_SHAPES = {   # what the frame table says of a frame buffer whose header is no frame of its camera's format (runtime.frame_shape)
+    **dict.fromkeys((FMT_NV12, FMT_I420), "an NV12 / I420 frame buffer must be (H*3/2, W, 1) with even H and W"),
+    **dict.fromkeys(TEN_BIT_FORMATS, "a P010 / YUV420P10 frame buffer must be (H*3/2, W, 2) or (H*3/2, 2W, 1) with even H and W"),
+    **dict.fromkeys((FMT_YUYV422, FMT_UYVY422), "a YUYV422 / UYVY422 frame buffer must be (H, W, 2) or (H, 2W, 1) with even W"),
+    FMT_GRAY8: "a gray frame buffer must have 1 channel",
+    **dict.fromkeys((FMT_RGB24, FMT_BGR24), "an RGB24 / BGR24 frame buffer must have 3 channels"),
+}
 
 
 def frame_formats(frames: Sequence[np.ndarray], cameras: Optional[Sequence[int]], default: int, by_camera: dict):
@@ -584,29 +593,13 @@ class HipObjectDetector:
                 channels = int(hdr.channels)
                 if fmt == FMT_RGB24 and channels == 1:               # a planar buffer read as RGB24: the configured planar YUV format
                     fmt = yuv
-                base = fmt & FMT_BASE_MASK
-                if base in (FMT_NV12, FMT_I420):                     # (H * 3 / 2, W) bytes of a W x H picture
-                    if channels != 1 or h % 3 or w % 2 or (h // 3 * 2) % 2:
-                        raise ValueError("camera %r: an NV12 / I420 frame buffer must be (H*3/2, W, 1) with even H and W" % (name,))
-                    h = h // 3 * 2
-                elif base in TEN_BIT_FORMATS:                        # (H * 3 / 2, W, 2) or (H * 3 / 2, 2W, 1) bytes: a 16-bit word per sample
-                    if channels == 1 and w % 4 == 0:
-                        w //= 2
-                    elif channels != 2:
-                        w = 1                                        # (refused below)
-                    if h % 3 or w % 2 or (h // 3 * 2) % 2:
-                        raise ValueError("camera %r: a P010 / YUV420P10 frame buffer must be (H*3/2, W, 2) or (H*3/2, 2W, 1) with even H and W" % (name,))
-                    h = h // 3 * 2
-                elif base in (FMT_YUYV422, FMT_UYVY422):             # (H, W, 2), or (H, 2W, 1)
-                    if channels == 1 and w % 4 == 0:
-                        w //= 2
-                    elif channels != 2 or w % 2:
-                        raise ValueError("camera %r: a YUYV422 / UYVY422 frame buffer must be (H, W, 2) or (H, 2W, 1) with even W" % (name,))
-                elif base == FMT_GRAY8:
-                    if channels != 1:
-                        raise ValueError("camera %r: a gray frame buffer must have 1 channel" % (name,))
-                elif channels != 3:
-                    raise ValueError("camera %r: an RGB24 / BGR24 frame buffer must have 3 channels" % (name,))
+                # a frame buffer's one-channel image is a 2-D array of bytes: (H*3/2, W, 1) planar, (H, 2W, 1) packed 4:2:2, (H*3/2, 2W, 1) 10-bit.
+                # (A base the library does not know is held to RGB24's three channels here and refused by the library's sizing below.)
+                base = fmt & FMT_BASE_MASK if fmt & FMT_BASE_MASK in _TABLE_SHAPES else FMT_RGB24
+                geo = frame_shape(base, h, w, None if channels == 1 else channels, 1)
+                if geo is None:
+                    raise ValueError("camera %r: %s" % (name, _TABLE_SHAPES[base]))
+                w, h = geo
                 need = int(frame_bytes(w, h, fmt))
                 if not need:
                     raise ValueError("camera %r: pixel format word 0x%x is not taken at %dx%d" % (name, fmt, w, h))

@@ -29,6 +29,44 @@ CSP_BT709, RANGE_FULL, FMT_BASE_MASK = _lib.WZ_CSP_BT709, _lib.WZ_RANGE_FULL, _l
 YUV_FORMATS = (FMT_NV12, FMT_I420, FMT_YUYV422, FMT_UYVY422, FMT_P010, FMT_YUV420P10)
 
 
+def frame_shape(base: int, rows: int, cols: int, channels: Optional[int], itemsize: int):
+    """(width, height) of a `rows` x `cols` array with `channels` items of `itemsize` bytes per position (None: the array has no channel
+    axis -- not 0, which is an empty array and no frame) read as a frame of base format `base`, or None when that shape is no frame of it.  The one rule behind `HipEngine.frame_geometry`
+    (arrays) and the plugin's frame table (frame buffers).  RGB24 / BGR24: (H, W, 3).  GRAY8: (H, W[, 1]).  YUYV422 / UYVY422: (H, W, 2)
+    or (H, 2W), W even.  NV12 / I420: the planar view (H*3/2, W[, 1]), H and W even.  P010 / YUV420P10: the planar view in 16-bit words,
+    (H*3/2, W[, 1]), or its bytes, (H*3/2, W, 2) or (H*3/2, 2W[, 1]); 16-bit items are these two formats' only."""
+    if itemsize != 1 and not (itemsize == 2 and base in TEN_BIT_FORMATS):
+        return None
+    flat = channels is None or channels == 1
+    if base in (FMT_RGB24, FMT_BGR24):
+        return (cols, rows) if channels == 3 else None
+    if base == FMT_GRAY8:
+        return (cols, rows) if flat else None
+    if base in (FMT_YUYV422, FMT_UYVY422):
+        if channels == 2 and cols % 2 == 0:
+            return cols, rows
+        return (cols // 2, rows) if channels is None and cols % 4 == 0 else None
+    if base in TEN_BIT_FORMATS:
+        if itemsize == 1 and flat and cols % 2 == 0:
+            cols //= 2                                   # two bytes a word
+        elif not (flat if itemsize == 2 else channels == 2):
+            return None
+    elif base not in (FMT_NV12, FMT_I420) or not flat:
+        return None
+    if rows % 3 or (rows // 3 * 2) % 2 or cols % 2:      # 4:2:0: H rows of luma, H/2 of chroma
+        return None
+    return cols, rows // 3 * 2
+
+
+_FRAME_SHAPES = {   # what `HipEngine.frame_geometry` says of an array that is no frame of its format
+    **dict.fromkeys((FMT_RGB24, FMT_BGR24), "an RGB24 / BGR24 frame must be (H,W,3) uint8"),
+    **dict.fromkeys((FMT_NV12, FMT_I420), "an NV12 / I420 frame must be (H*3/2, W) uint8 with even H and W"),
+    **dict.fromkeys((FMT_YUYV422, FMT_UYVY422), "a YUYV422 / UYVY422 frame must be (H,W,2) or (H,2W) uint8 with even W"),
+    **dict.fromkeys(TEN_BIT_FORMATS, "a P010 / YUV420P10 frame must be (H*3/2, W) uint16, or (H*3/2, W, 2) or (H*3/2, 2W) uint8, with even H and W"),
+    FMT_GRAY8: "a GRAY8 frame must be (H,W) or (H,W,1) uint8",
+}
+
+
 def device_count() -> int:
     return int(_lib.load().wz_device_count())
 
@@ -200,41 +238,12 @@ class HipEngine:
             raise ValueError("unknown flag bits in pixel format word 0x%x" % (flags | fmt,))
         if flags and fmt not in YUV_FORMATS:
             raise ValueError("colour flags (BT.709 / full range) apply to the YUV pixel formats only")
-        if fmt in (FMT_RGB24, FMT_BGR24):
-            if f.ndim != 3 or f.shape[2] != 3:
-                raise ValueError("an RGB24 / BGR24 frame must be (H,W,3) uint8")
-            return f.shape[1], f.shape[0]
-        if fmt in (FMT_NV12, FMT_I420):
-            if f.ndim == 3 and f.shape[2] == 1:      # (H*3/2, W, 1): a one-"channel" frame buffer of the reference (share.py:37-40)
-                f = f[:, :, 0]
-            if f.ndim != 2 or f.shape[0] % 3 or (f.shape[0] // 3 * 2) % 2 or f.shape[1] % 2:
-                raise ValueError("an NV12 / I420 frame must be (H*3/2, W) uint8 with even H and W")
-            return f.shape[1], f.shape[0] // 3 * 2
-        if fmt in (FMT_YUYV422, FMT_UYVY422):
-            if f.ndim == 3 and f.shape[2] == 2 and f.shape[1] % 2 == 0:
-                return f.shape[1], f.shape[0]
-            if f.ndim == 2 and f.shape[1] % 4 == 0:
-                return f.shape[1] // 2, f.shape[0]
-            raise ValueError("a YUYV422 / UYVY422 frame must be (H,W,2) or (H,2W) uint8 with even W")
-        if fmt in TEN_BIT_FORMATS:
-            if f.ndim == 3 and f.shape[2] == 1:
-                f = f[:, :, 0]
-            if f.dtype == np.uint16 and f.ndim == 2:
-                rows, w = f.shape
-            elif f.dtype == np.uint8 and f.ndim == 3 and f.shape[2] == 2:
-                rows, w = f.shape[:2]
-            elif f.dtype == np.uint8 and f.ndim == 2 and f.shape[1] % 2 == 0:
-                rows, w = f.shape[0], f.shape[1] // 2
-            else:
-                rows, w = 0, 0
-            if w < 1 or rows < 1 or rows % 3 or (rows // 3 * 2) % 2 or w % 2:
-                raise ValueError("a P010 / YUV420P10 frame must be (H*3/2, W) uint16, or (H*3/2, W, 2) or (H*3/2, 2W) uint8, with even H and W")
-            return w, rows // 3 * 2
-        if fmt == FMT_GRAY8:
-            if f.ndim == 2 or (f.ndim == 3 and f.shape[2] == 1):
-                return f.shape[1], f.shape[0]
-            raise ValueError("a GRAY8 frame must be (H,W) or (H,W,1) uint8")
-        raise ValueError("unknown pixel format %r" % (fmt,))
+        if fmt not in _FRAME_SHAPES:
+            raise ValueError("unknown pixel format %r" % (fmt,))
+        geo = frame_shape(fmt, f.shape[0], f.shape[1], f.shape[2] if f.ndim == 3 else None, f.itemsize) if f.ndim in (2, 3) else None
+        if geo is None or (fmt in TEN_BIT_FORMATS and min(geo) < 1):
+            raise ValueError(_FRAME_SHAPES[fmt])
+        return geo
 
     def detect_batch(self, frames: Sequence[np.ndarray], out_rows: Sequence, cams: Optional[Sequence[int]] = None,
                      out_pass: Optional[Sequence[np.ndarray]] = None, formats: Optional[Sequence[int]] = None) -> float:
