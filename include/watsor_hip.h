@@ -294,6 +294,40 @@ int wz_motion_stats(wz_engine_t* e, int slot, int n, int32_t* n_tiles /* [n] */,
 typedef struct wz_motion_hold { int32_t hold, object_hold, _reserved[2]; } wz_motion_hold_t;
 int wz_set_camera_motion_hold(wz_engine_t* e, int cam, const wz_motion_hold_t* hold);   /* both 0: remove the hold, free its grids */
 int wz_motion_hold_stats(wz_engine_t* e, int slot, int n, int32_t* active /* [n] */, int32_t* held /* [n] */);
+/* ---- ignore masks.  A real camera burns a clock into its picture, shows a flag, a hedge in the wind, a road behind
+ * the fence: pixels that change on every frame and are no motion.  A camera with motion settings, a gate layout or both may have one IGNORE
+ * PLANE: height x width bytes, nonzero = ignore.  From it the engine derives one bit per 16 x 16-pixel cell of every grid the camera
+ * compares; a changed cell whose bit is set does not count.  Nothing else about a call changes.
+ *   cell rule   a cell is ignored iff AT LEAST ONE pixel of it is ignored in the plane.  A cell is WZ_GATE_CELL square; the last column and row
+ *               of cells of a grid are partial.  What was painted never leaks as motion; the price is a margin of at most 15 pixels around the
+ *               painted area in which change is ignored too.  A motion camera's grid is anchored at the frame's origin.  A gated camera has
+ *               one grid per tile, anchored at the TILE's origin: tile origins need not be multiples of 16, so a tile's cell bits are derived
+ *               from the plane for that tile and are not a window of the frame's.  wz_ignore_cells is the one place the rule is written.
+ *   motion      with C the changed cells as defined above and M the ignored cells, C' = C and not M.  Every later definition reads C' where it
+ *               reads C: dilation, components, a region's n, candidates, the walk.  With a hold: A = C' or (G > 0), and the decay uses C' -- an
+ *               ignored cell never receives `hold` from change.  The stamp is untouched: a cell under a passing detection is held even if it
+ *               is ignored (the mask silences change, not the detector's findings), and such a cell stays active while its age lasts.  The
+ *               grid of luma sums is written and becomes the next call's reference as before, ignored cells included.
+ *               ignored = |C and M|, the changed cells that the mask removed; 0 without a reference.
+ *   gate        a tile's activity is its number of changed cells that are not ignored.  "A tile runs iff" is unchanged in every other clause:
+ *               no reference, max_age, min_cells.  wz_gate_stats' activity is the count after masking.
+ *   no mask     a camera without a mask behaves bit for bit as before, and a call none of whose cameras has one launches the kernels it
+ *               launched before there were masks.
+ * wz_ignore_cells: host only, no engine needed.  cells[cell rows][cell columns] of `rect` (NULL: the whole frame) get 0 / 1.  WZ_EINVAL: a
+ * null plane or output, a size below 1, a rect that is empty or not inside the frame.
+ * wz_set_camera_ignore waits for every lane and applies to what the camera has at the time of the call: its motion settings get the frame
+ * grid's bits, its gate layout every tile's bits.  Refused with WZ_EINVAL: a camera that has neither; a plane whose size differs from the
+ * size either was set for.  On failure the camera keeps what it had.  ignore = NULL removes the mask (width and height are not looked at).
+ * The lifecycle follows the hold's: wz_set_camera_motion replaces the camera's motion state and thereby drops the motion part of the mask,
+ * wz_set_camera_tiles the gate part -- set the mask after them (wz_set_camera_motion_hold keeps it); wz_reset_camera_* keeps the mask;
+ * wz_clear_camera_* frees its part.  An engine that never sets a mask allocates nothing for it.
+ * wz_motion_ignore_stats: per frame of the last motion call accepted on `slot`, the changed cells that the mask removed; 0 for a frame whose
+ * camera has no mask.  The frame-table path (wz_bind_tiles(..., gated = 1) + wz_submit_bound) looks the camera's layout up at submit time and
+ * honours the mask like wz_detect_gated. */
+int wz_ignore_cells(const uint8_t* ignore, int width, int height, const wz_tile_t* rect /* NULL: the whole frame */,
+                    uint8_t* cells /* [cell rows][cell columns], 0 / 1 */);
+int wz_set_camera_ignore(wz_engine_t* e, int cam, int width, int height, const uint8_t* ignore /* [height][width], nonzero: ignore; NULL: remove */);
+int wz_motion_ignore_stats(wz_engine_t* e, int slot, int n, int32_t* ignored /* [n] */);
 /* ---- the worker's frame table.  The reference worker resolves every payload to `frame_buffers[sender].frames[index]`, asks
  * the frame for a numpy view of its pixels and hands the frame header's `Detection[100]` array to the plugin
  * (watsor/detection/detector.py:102-109); pixels, size and rows of a Frame never move after the FrameBuffers are created
@@ -542,6 +576,21 @@ int wz_debug_motion_age(wz_engine_t* e, int cam, uint8_t* out);
 int wz_profile_motion_hold(wz_engine_t* e, const uint16_t* now, const uint16_t* ref, const uint8_t* age_in, int w, int h, int fmt,
                            const wz_motion_t* motion, int hold, const wz_detection_t* rows, const uint8_t* pass, int object_hold, int reps,
                            float* regions_ms, float* stamp_ms, float* empty_ms);
+/* ---- ignore masks: the kernels' masked instantiations alone.  cells_ignored: [cell rows][cell columns] bytes as
+ * wz_ignore_cells writes them (nonzero: ignored), or NULL: the camera / tile has no mask but runs in a launch that has one.
+ * The activity kernel: wz_stage_tile_activity's arguments plus the tile's cell mask; changed_out counts the changed cells that are not ignored */
+int wz_stage_tile_activity_ignore(wz_engine_t* e, const uint8_t* frame, int w, int h, int fmt, const wz_tile_t* tile, const uint16_t* ref, int pixel_thr,
+                                  const uint8_t* cells_ignored, uint16_t* sums_out, int32_t* changed_out);
+/* the region kernel: wz_stage_motion_hold's arguments plus the grid's cell mask in and `ignored` out.  age_out NULL (then age_in NULL and
+ * hold 0): as a camera without a hold runs it; active and held are then 0 */
+int wz_stage_motion_ignore(wz_engine_t* e, const uint16_t* now, const uint16_t* ref, const uint8_t* age_in, int w, int h, int fmt,
+                           const wz_motion_t* motion, int hold, const uint8_t* cells_ignored, int32_t* n_regions,
+                           wz_tile_t* regions /* [WZ_MOTION_MAX_REGIONS] */, int32_t* cells /* [WZ_MOTION_MAX_REGIONS] */, int32_t* components,
+                           int32_t* active, int32_t* held, int32_t* ignored, uint8_t* age_out);
+/* HIP-event time (ms, mean of reps) of the region launch alone on these two grids with this cell mask (no hold); empty_ms: the same
+ * bracket around nothing.  The masked activity launch is timed by wz_profile_gated on a camera that has a mask */
+int wz_profile_motion_ignore(wz_engine_t* e, const uint16_t* now, const uint16_t* ref, int w, int h, int fmt, const wz_motion_t* motion,
+                             const uint8_t* cells_ignored, int reps, float* regions_ms, float* empty_ms);
 /* in_place[i] = 1 where frame i of the last wz_submit_bound on `slot` -- untiled, tiled or gated -- was read in place through its device view,
  * 0 where it was staged by DMA (n values: the frames of that batch); WZ_EINVAL when the lane has seen no such batch */
 int wz_debug_bound_source(wz_engine_t* e, int slot, int32_t* in_place /* [n] */);

@@ -6,6 +6,8 @@
 //   wz_k_gate_commit    behind the batch: a tile that ran gets its new grid as reference and its fresh rows as cached rows; fresh or
 //                       cached, every tile's rows go into one block, in tile order, for wz_k_merge_tiles.
 // Integer sums only: any order of summation gives the same bytes (tests/gate_oracle.py restates them with numpy).
+// A tile with an ignore mask (WzGateTile::ignore) runs wz_k_tile_activity<true>: a changed cell whose mask bit is set
+// is not counted; the sums are the same.  A launch none of whose tiles has a mask runs <false>, the kernel there was before there was one.
 #include "wz_common.h"
 
 #define WZ_GATE_THREADS 1024   // 16 waves: one wave per pixel row of a strip of cells
@@ -21,6 +23,7 @@ __device__ __forceinline__ uint32_t wz_gate_byte(const uint4& v, int j) {
 // is no wider than a cell's bytes in a row (16, 32 or 48), so its lumas fall into at most two cells: two LDS adds per lane.  A 3-byte pixel
 // that straddles two words is finished by the lane that holds its last byte: the weighted sum of its first bytes comes from the lane
 // before (a shuffle; lane 0 takes it from lane 63 of the wave's previous step along the row).
+template <bool MASK>
 __global__ __launch_bounds__(WZ_GATE_THREADS) void wz_k_tile_activity(const WzGateTile* __restrict__ tiles, int32_t* counters,
                                                                       int32_t* __restrict__ activity) {
     extern __shared__ uint32_t wz_gate_cells[];   // [cols of the widest tile of the launch]
@@ -123,7 +126,7 @@ __global__ __launch_bounds__(WZ_GATE_THREADS) void wz_k_tile_activity(const WzGa
         if (t.ref) {
             const int cw = min(WZ_GATE_CELL, t.tw - c * WZ_GATE_CELL);
             const int d = (int)s - (int)t.ref[at];
-            if ((d < 0 ? -d : d) > t.thr * cw * ch) atomicAdd(&changed, 1);
+            if ((d < 0 ? -d : d) > t.thr * cw * ch && !(MASK && t.ignore && ((t.ignore[at >> 5] >> (at & 31)) & 1u))) atomicAdd(&changed, 1);
         }
     }
     __syncthreads();
@@ -140,8 +143,10 @@ __global__ __launch_bounds__(WZ_GATE_THREADS) void wz_k_tile_activity(const WzGa
     }
 }
 
-void wz_launch_tile_activity(const WzGateTile* tiles, int n, int max_crows, int max_cols, int32_t* counters, int32_t* activity, hipStream_t s) {
-    hipLaunchKernelGGL(wz_k_tile_activity, dim3((unsigned)max_crows, (unsigned)n), dim3(WZ_GATE_THREADS), (size_t)max_cols * 4, s, tiles, counters,
+void wz_launch_tile_activity(const WzGateTile* tiles, int n, int max_crows, int max_cols, int32_t* counters, int32_t* activity, hipStream_t s,
+                             bool with_mask) {
+    const auto kernel = with_mask ? wz_k_tile_activity<true> : wz_k_tile_activity<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)max_crows, (unsigned)n), dim3(WZ_GATE_THREADS), (size_t)max_cols * 4, s, tiles, counters,
                        activity);
 }
 

@@ -10,6 +10,10 @@
 // A camera with a hold (WzMotionCam::age_out) runs wz_k_motion_regions<true>: step 1 reads the cell's age beside its two sums, votes
 // "changed or age > 0" into the bit map and writes the decayed age; everything behind step 1 reads the bit map and is the same code.  A
 // camera without one takes, in either instantiation, the path it always took.
+// A camera with an ignore mask (WzMotionCam::ignore) runs wz_k_motion_regions<.., true>: step 1 reads the wave's 64
+// mask bits -- one aligned 64-bit word, the same address in every lane -- beside its loads and clears the ignored lanes of `changed` before
+// the vote, the age write and the popcounts; what the mask removed is counted into WzMotionOut::ignored.  Four instantiations; a launch
+// none of whose cameras has a mask runs <false, false> or <true, false>, which are the two kernels there were before there was a mask.
 // Integers only.  Nothing depends on scheduling: a component's id is the SMALLEST linear index of its cells, ties in n are broken by id,
 // sums and minima may be taken in any order (tests/motion_oracle.py restates all of it with numpy).
 //
@@ -23,6 +27,7 @@
 // grows with the logarithm of a component's longest path, not with the path (a one-cell serpentine over a 1080p grid is 4047 sweeps of a
 // plain 3 x 3 minimum).
 #include <limits.h>
+#include <stddef.h>
 
 #include "wz_common.h"
 
@@ -78,18 +83,20 @@ struct WzMotionWalk {
 
 // AGE: the launch has a camera with a hold.  `aged`, below, is this workgroup's camera having one; "changed" then reads "active" in every
 // comment behind step 1.  The ages go from device memory to device memory: none of them is ever in LDS.
-template <bool AGE>
+// MASK: the launch has a camera with an ignore mask; a camera of it without one reads no mask word.
+template <bool AGE, bool MASK>
 __global__ __launch_bounds__(WZ_MOTION_THREADS) void wz_k_motion_regions(const WzMotionCam* __restrict__ cams, WzMotionOut* __restrict__ outs) {
     // C, one bit a cell: 2 * ceil(cells / 64) words; the labels, uint16 a cell; the counts, uint16 a cell (a component's n, at its root)
     extern __shared__ uint32_t wz_motion_lds[];
     __shared__ int again, row_lo, row_hi;   // row_lo .. row_hi: the rows of cells that hold a changed cell
     __shared__ uint32_t n_keys;
     __shared__ uint32_t n_active, n_held;   // (AGE) the popcounts of step 1's votes: active cells, and those of them that did not change
+    __shared__ uint32_t n_ignored;          // (MASK) the changed cells that the mask removed
     __shared__ uint32_t near_keys[WZ_MOTION_NEAR_KEYS];   // the first keys found, where ranking by counting reads them
     __shared__ uint32_t cand_key[WZ_MOTION_CANDIDATES];   // the ranked keys: n << 15 | (32767 - id)
     __shared__ int32_t box[WZ_MOTION_CANDIDATES][4];      // their cell boxes: cx0, cx1, cy0, cy1
     __shared__ WzMotionOut result;
-    constexpr int RESULT_WORDS = (int)(sizeof(WzMotionOut) / 4);
+    constexpr int RESULT_WORDS = (int)(sizeof(WzMotionOut) / 4), IGNORED_WORD = (int)(offsetof(WzMotionOut, ignored) / 4);
 
     const WzMotionCam c = cams[blockIdx.x];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -114,6 +121,7 @@ __global__ __launch_bounds__(WZ_MOTION_THREADS) void wz_k_motion_regions(const W
     if (tid < WZ_MOTION_CANDIDATES) cand_key[tid] = 0u;
     if (tid == 0) n_keys = 0u, row_lo = INT_MAX, row_hi = -1;
     if (AGE && tid == 0) n_active = n_held = 0u;
+    if (MASK && tid == 0) n_ignored = 0u;
     for (int i = tid; i < lwords; i += WZ_MOTION_THREADS) count2[i] = 0u;
     __syncthreads();
     // (AGE) with a hold the age byte is the third load of a step, the vote is "changed or age > 0", and every cell's decayed age is written
@@ -121,14 +129,19 @@ __global__ __launch_bounds__(WZ_MOTION_THREADS) void wz_k_motion_regions(const W
     const uint8_t* __restrict__ const age_in = c.age_in;
     const bool has_ref = !AGE || ref != nullptr, has_age = aged && age_in != nullptr;
     int active = 0, held = 0;   // lane 0 of a wave: its votes' popcounts
+    // (MASK) the wave's 64 cells of a step begin at a multiple of 64: their mask bits are word (i - lane) >> 6, bit `lane` this lane's
+    const unsigned long long* __restrict__ const ign = MASK ? c.ignore : nullptr;
+    int ignored = 0;
     for (int base = 0; base < span; base += 4 * WZ_MOTION_THREADS) {
         int a[4], b[4], g[4];
+        unsigned long long m[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int i = base + u * WZ_MOTION_THREADS + tid;
             a[u] = i < cells ? (int)now[i] : 0;
             b[u] = i < cells && has_ref ? (int)ref[i] : 0;
             g[u] = AGE && has_age && i < cells ? (int)age_in[i] : 0;
+            m[u] = MASK && ign && i - lane < cells ? ign[(i - lane) >> 6] : 0ull;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -136,7 +149,10 @@ __global__ __launch_bounds__(WZ_MOTION_THREADS) void wz_k_motion_regions(const W
             const int y = i / gw, x = i - y * gw;
             const int npix = min(WZ_GATE_CELL, c.W - WZ_GATE_CELL * x) * min(WZ_GATE_CELL, c.H - WZ_GATE_CELL * y);
             const int d = a[u] - b[u];
-            const bool changed = i < cells && has_ref && (d < 0 ? -d : d) > c.thr * npix;
+            const bool differs = i < cells && has_ref && (d < 0 ? -d : d) > c.thr * npix;
+            const bool masked = MASK && ((m[u] >> lane) & 1ull) != 0ull;
+            const bool changed = differs && !masked;
+            if (MASK) ignored += __popcll(__ballot(differs && masked));
             const unsigned long long vote = __ballot(changed || (AGE && g[u] > 0));
             if (AGE && aged) {
                 if (i < cells) c.age_out[i] = (uint8_t)max(changed ? c.hold : 0, g[u] > 0 ? g[u] - 1 : 0);
@@ -159,9 +175,10 @@ __global__ __launch_bounds__(WZ_MOTION_THREADS) void wz_k_motion_regions(const W
         atomicAdd(&n_active, (uint32_t)active);
         atomicAdd(&n_held, (uint32_t)held);
     }
+    if (MASK && lane == 0 && ignored) atomicAdd(&n_ignored, (uint32_t)ignored);
     __syncthreads();
-    if (row_hi < 0) {   // a still picture (read behind the barrier: the same for every thread)
-        if (tid < RESULT_WORDS) out_words[tid] = 0u;
+    if (row_hi < 0) {   // a still picture (read behind the barrier: the same for every thread); (MASK) also: every changed cell was ignored
+        if (tid < RESULT_WORDS) out_words[tid] = MASK && tid == IGNORED_WORD ? n_ignored : 0u;
         return;
     }
     // Every step below looks at rows y_lo .. y_hi only: the rows D can reach and one more on either side, whose labels the scan reads.
@@ -347,7 +364,7 @@ __global__ __launch_bounds__(WZ_MOTION_THREADS) void wz_k_motion_regions(const W
             result.rounds = rounds + 1;
             result.active = aged ? (int32_t)n_active : 0;
             result.held = aged ? (int32_t)n_held : 0;
-            result._pad = 0;
+            result.ignored = MASK ? (int32_t)n_ignored : 0;
         }
         if (tid >= nr && tid < WZ_MOTION_MAX_REGIONS) {
             result.regions[tid].x0 = result.regions[tid].y0 = result.regions[tid].w = result.regions[tid].h = 0;
@@ -358,9 +375,10 @@ __global__ __launch_bounds__(WZ_MOTION_THREADS) void wz_k_motion_regions(const W
     if (tid < RESULT_WORDS) out_words[tid] = reinterpret_cast<const uint32_t*>(&result)[tid];
 }
 
-void wz_launch_motion_regions(const WzMotionCam* cams, int n, int max_cells, WzMotionOut* out, hipStream_t s, bool with_age) {
+void wz_launch_motion_regions(const WzMotionCam* cams, int n, int max_cells, WzMotionOut* out, hipStream_t s, bool with_age, bool with_mask) {
     const size_t lds = (size_t)(((max_cells + 63) >> 6) * 2) * 4 + (((size_t)max_cells + 1) & ~(size_t)1) * 4;   // bits, labels, counts
-    const auto kernel = with_age ? wz_k_motion_regions<true> : wz_k_motion_regions<false>;
+    const auto kernel = with_mask ? (with_age ? wz_k_motion_regions<true, true> : wz_k_motion_regions<false, true>)
+                                  : (with_age ? wz_k_motion_regions<true, false> : wz_k_motion_regions<false, false>);
     if (lds > 48 * 1024)   // (more than 11 k cells: past what a launch gets without asking; a CU of gfx950 has 160 KiB)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(WZ_MOTION_THREADS), lds, s, cams, out);

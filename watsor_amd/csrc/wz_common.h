@@ -486,6 +486,9 @@ struct WzGateTile {
     const uint16_t* ref;   // the reference grid [crows][cols], or nullptr: the tile has none (its activity is reported as 0)
     uint16_t* now;         // the new grid [crows][cols]
     int32_t pitch, row_bytes, tw, th, cols, crows, mode, thr;
+    // ignore mask: one bit per cell of the tile's own grid, cell strip * cols + c at bit (.. & 31) of word (.. >> 5);
+    // nullptr: the tile has none.  Read only by wz_k_tile_activity<true>
+    const uint32_t* ignore;
 };
 struct WzGateCommit {      // one tile of a gated call, in tile order
     uint16_t* ref;         // the camera's reference grid of the tile ...
@@ -494,8 +497,10 @@ struct WzGateCommit {      // one tile of a gated call, in tile order
     int32_t cells, fresh;  // fresh: the tile's image in the batch that ran, or -1: the tile was skipped
 };
 // tiles[n] (device-readable) -> every tile's new grid, activity[n] = cells changed against the reference; counters: int32[n][2], zero before the
-// first launch (the kernel leaves them zero); max_crows / max_cols: the most cell rows / columns any of the n tiles has
-void wz_launch_tile_activity(const WzGateTile* tiles, int n, int max_crows, int max_cols, int32_t* counters, int32_t* activity, hipStream_t s);
+// first launch (the kernel leaves them zero); max_crows / max_cols: the most cell rows / columns any of the n tiles has; with_mask: some tile of
+// the launch has `ignore`
+void wz_launch_tile_activity(const WzGateTile* tiles, int n, int max_crows, int max_cols, int32_t* counters, int32_t* activity, hipStream_t s,
+                             bool with_mask = false);
 // the tiles that ran: new grid -> reference, batch_rows[fresh] -> cache; every tile: fresh or cached rows -> out[t][100]
 void wz_launch_gate_commit(const WzGateCommit* tiles, int n, const wz_detection_t* batch_rows, wz_detection_t* out, hipStream_t s);
 
@@ -514,17 +519,22 @@ struct WzMotionCam {
     const uint8_t* age_in;    // the previous call's ages, or nullptr: all zero
     uint8_t* age_out;         // the ages this call leaves (decayed by the region launch, raised by the stamp launch)
     int32_t hold, object_hold;   // the age of a changed cell; the age of a cell under a passing detection (0: no stamp)
+    // ignore mask: one bit per cell of the frame's grid, cell i at bit (i & 63) of word (i >> 6) -- a wave's 64 cells
+    // of step 1 are one word; nullptr: the camera has none.  Read only by wz_k_motion_regions<.., true>
+    const unsigned long long* ignore;
 };
 struct WzMotionOut {       // what the host reads, in the lane's page-locked block
     int32_t n_regions, components;   // regions accepted; components with n >= min_cells
     wz_tile_t regions[WZ_MOTION_MAX_REGIONS];
     int32_t cells[WZ_MOTION_MAX_REGIONS];   // n of every region
     int32_t rounds;                         // rounds the labelling took (0: the picture was still), for the profiling entry point
-    int32_t active, held, _pad;             // a camera with a hold: its active cells (changed or age > 0), those of them that did not change
+    int32_t active, held;                   // a camera with a hold: its active cells (changed or age > 0), those of them that did not change
+    int32_t ignored;                        // a camera with an ignore mask: the changed cells that the mask removed
 };
 // cams[n] (device-readable) -> out[n]; max_cells: the most cells any of the n grids has (at most WZ_MOTION_MAX_CELLS); with_age: some
-// camera of the launch has age_out
-void wz_launch_motion_regions(const WzMotionCam* cams, int n, int max_cells, WzMotionOut* out, hipStream_t s, bool with_age = false);
+// camera of the launch has age_out; with_mask: some camera of the launch has `ignore`
+void wz_launch_motion_regions(const WzMotionCam* cams, int n, int max_cells, WzMotionOut* out, hipStream_t s, bool with_age = false,
+                              bool with_mask = false);
 // behind the merge and filter launches of a motion call: a frame without a tile (frames[f].n_tiles == 0) gets the padding rows and pass bytes 0
 void wz_launch_motion_still(const WzMergeFrame* frames, int n, wz_detection_t* rows, uint8_t* pass, hipStream_t s);
 // last of a motion call: every cell of cams[f].age_out under a row of frame f whose pass byte is 1 is raised to cams[f].object_hold

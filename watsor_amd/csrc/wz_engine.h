@@ -154,6 +154,7 @@ struct GateLane {
     std::vector<uint64_t> g_ran;         // the last gated call accepted on this lane (wz_gate_stats): per frame, bit t = tile t ran ...
     std::vector<int32_t> g_act;          // ... and every tile's activity, in tile order
     int g_tiles = 0, g_crows = 0, g_cols = 0;   // that call's launches: tiles, the most cell rows / columns of a tile
+    bool g_masked = false;                      // ... and whether one of its cameras had an ignore mask
     int alloc(wz_engine* e);
     void release() { *this = GateLane(); }
 };
@@ -177,6 +178,7 @@ struct MotionLane {
     std::vector<int32_t> s_ntiles, s_cells, s_comps;   // the last motion call accepted on this lane (wz_motion_stats): per frame its tiles,
     std::vector<wz_tile_t> s_tiles;                    // [n][1 + WZ_MOTION_MAX_REGIONS], its regions' n [n][WZ_MOTION_MAX_REGIONS], its components
     std::vector<int32_t> s_active, s_held;             // ... and (wz_motion_hold_stats) its active cells and those of them that did not change
+    std::vector<int32_t> s_ignored;                    // ... and (wz_motion_ignore_stats) the changed cells its camera's ignore mask removed
     int alloc(wz_engine* e);             // (wz_tiles.hip) lazy; all or nothing
     void release() { *this = MotionLane(); }
 };
@@ -308,7 +310,10 @@ struct wz_engine {
         std::vector<uint8_t> has_ref;            // the tile has a reference (and cached rows)
         std::vector<int> skipped;                // gated calls of this camera in a row that skipped the tile
         int lane = -1;                           // the lane whose gated batch last wrote this state
-        void release() { *this = GateCam(); }    // frees the two device blocks
+        // ignore mask (wz_set_camera_ignore): every tile's cell bits, one after the other; null: the camera has none
+        DevBlock<uint32_t> d_ignore;
+        std::vector<size_t> ignore_off;          // first 32-bit word of every tile's bits in d_ignore
+        void release() { *this = GateCam(); }    // frees the device blocks
     };
     std::map<int, GateCam> gate_cams;
     // motion regions: a camera's settings and its two whole-frame grids (wz_set_camera_motion); empty until a camera is set.  The grid the
@@ -326,6 +331,7 @@ struct wz_engine {
         bool has_age = false;                    // d_age[cur] holds ages (false: they are all zero, whatever the grid says)
         int hold = 0, object_hold = 0;
         int lane = -1;                           // the lane whose motion call last stamped d_age
+        DevBlock<unsigned long long> d_ignore;   // ignore mask (wz_set_camera_ignore): the frame grid's cell bits; null: the camera has none
         void release() { *this = MotionCam(); }  // frees the grids
     };
     std::map<int, MotionCam> motion_cams;

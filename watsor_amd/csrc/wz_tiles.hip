@@ -15,6 +15,14 @@ typedef wz_engine::MotionCam MotionCam;
 
 static int cells_of(int px) { return (px + WZ_GATE_CELL - 1) / WZ_GATE_CELL; }
 static size_t gate_cells_of(int w, int h) { return (size_t)cells_of(w) * (size_t)cells_of(h); }
+// Ignore masks: wz_ignore_cells' bytes as the kernels read them, cell i at bit (i & 63) of 64-bit word (i >> 6) --
+// which, little-endian, is bit (i & 31) of 32-bit word (i >> 5): wz_k_motion_regions reads the former, wz_k_tile_activity the latter
+static size_t ignore_words_of(size_t cells) { return (cells + 63) >> 6; }
+static void pack_cell_bits(const uint8_t* cells, size_t n, unsigned long long* words) {
+    std::fill(words, words + ignore_words_of(n), 0ull);
+    for (size_t i = 0; i < n; ++i)
+        if (cells[i]) words[i >> 6] |= 1ull << (i & 63);
+}
 
 // ---- lane state
 // Everything a lane needs for one kind of call, allocated the first time it sees one (an engine that never does uses no byte of it): built
@@ -125,6 +133,7 @@ static void gate_tile(const uint8_t* src, int w, int fmt, const wz_tile_t& t, Wz
     // (sample << 6) that is its second byte -- UYVY's odd bytes --, of a YUV420P10 word bits 2 .. 9 (WZ_GATE_LOW10).
     g.mode = base == WZ_FMT_RGB24 ? WZ_GATE_RGB : base == WZ_FMT_BGR24 ? WZ_GATE_BGR : base == WZ_FMT_YUYV422 ? WZ_GATE_YUYV
              : (base == WZ_FMT_UYVY422 || base == WZ_FMT_P010) ? WZ_GATE_UYVY : base == WZ_FMT_YUV420P10 ? WZ_GATE_LOW10 : WZ_GATE_GRAY;
+    g.ignore = nullptr;   // (no mask; a gated camera with one adds its tile's bits)
 }
 
 // ---- a call, its checks, its plan
@@ -335,11 +344,14 @@ static int gated_enqueue(wz_engine* e, int slot, const TileCall& call) {
     WzGateCommit* commits = G.meta.h.commits;
     int32_t* act = G.meta.h.activity;
     int k = 0, crows = 0, cols = 0;
+    bool masked = false;   // some camera of the call has an ignore mask
     for (int i = 0; i < n; ++i) {
         GateCam& g = *cams[i];
+        masked = masked || g.d_ignore;
         for (int t = 0; t < nt[i]; ++t, ++k) {
             WzGateTile& d = G.meta.h.tiles[k];
             gate_tile(c.frames[i], c.w[i], c.pf(i), g.tiles[t], d);
+            if (g.d_ignore) d.ignore = g.d_ignore + g.ignore_off[t];
             d.ref = g.has_ref[t] ? g.d_ref + g.grid_off[t] : nullptr;
             d.now = G.d_gnow + lane_cells * k;
             d.thr = g.gate.pixel_thr;
@@ -349,7 +361,7 @@ static int gated_enqueue(wz_engine* e, int slot, const TileCall& call) {
             commits[k] = {g.d_ref + g.grid_off[t], d.now, g.d_rows + (size_t)t * WZ_MAX_DETECTIONS, d.cols * d.crows, -1};   // (fresh: step 2)
         }
     }
-    wz_launch_tile_activity(G.meta.m.tiles, total, crows, cols, G.d_gcount, G.meta.m.activity, L.stream);
+    wz_launch_tile_activity(G.meta.m.tiles, total, crows, cols, G.d_gcount, G.meta.m.activity, L.stream, masked);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(L.stream));   // the batch size is a host-side quantity: the decision waits for the counts
     // 2. the decision; the cameras' state changes only once everything is enqueued
@@ -368,7 +380,7 @@ static int gated_enqueue(wz_engine* e, int slot, const TileCall& call) {
     // 5. the state the commit launch leaves behind, and what wz_gate_stats reports
     G.g_ran.assign(n, 0);
     G.g_act.assign(act, act + total);
-    G.g_tiles = total; G.g_crows = crows; G.g_cols = cols;
+    G.g_tiles = total; G.g_crows = crows; G.g_cols = cols; G.g_masked = masked;
     k = 0;
     for (int i = 0; i < n; ++i) {
         GateCam& g = *cams[i];
@@ -419,6 +431,7 @@ static void motion_desc(int w, int h, int fmt, const wz_motion_t& p, const uint1
     d.even_y = planar ? 1 : 0;
     d.age_in = nullptr; d.age_out = nullptr;   // (no hold; motion_hold_desc adds one)
     d.hold = d.object_hold = 0;
+    d.ignore = nullptr;                        // (no mask; a camera with one adds its bits)
 }
 // ... and of a camera with a hold on top of it: the ages it reads (null: all zero) and the grid that takes the ages it leaves
 static void motion_hold_desc(const uint8_t* age_in, uint8_t* age_out, int hold, int object_hold, WzMotionCam& d) {
@@ -444,6 +457,7 @@ static int motion_enqueue(wz_engine* e, int slot, const TileCall& call) {
     WzMotionOut* mo = M.meta.h.outs;
     int crows = 0, cols = 0, cells = 0;
     bool aged = false, stamps = false;   // some camera of the call has a hold; ... and holds under detections
+    bool masked = false;                 // some camera of the call has an ignore mask
     for (const MotionCam* m : cams)      // another lane's stamp launch may still be writing this camera's ages
         if (m->d_age[0] && m->lane >= 0 && m->lane != slot) HIPCHK(hipEventSynchronize(e->lanes[m->lane].done));
     for (int i = 0; i < n; ++i) {
@@ -460,18 +474,22 @@ static int motion_enqueue(wz_engine* e, int slot, const TileCall& call) {
             aged = true;
             stamps = stamps || m.object_hold > 0;
         }
+        if (m.d_ignore) {
+            md[i].ignore = m.d_ignore;
+            masked = true;
+        }
         crows = std::max(crows, gt[i].crows);
         cols = std::max(cols, gt[i].cols);
         cells = std::max(cells, m.gw * m.gh);
         mo[i].n_regions = -1;
     }
     wz_launch_tile_activity(M.meta.m.tiles, n, crows, cols, M.d_mcount, M.meta.m.activity, L.stream);
-    wz_launch_motion_regions(M.meta.m.cams, n, cells, M.meta.m.outs, L.stream, aged);
+    wz_launch_motion_regions(M.meta.m.cams, n, cells, M.meta.m.outs, L.stream, aged, masked);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(L.stream));   // the batch size is a host-side quantity: the plan waits for the rectangles
     // 3. the tile lists; the cameras' state changes only once everything is enqueued
     std::vector<wz_tile_t> tiles((size_t)n * PER);
-    std::vector<int32_t> nt(n), comps(n), ncell((size_t)n * WZ_MOTION_MAX_REGIONS, 0), active(n), held(n);
+    std::vector<int32_t> nt(n), comps(n), ncell((size_t)n * WZ_MOTION_MAX_REGIONS, 0), active(n), held(n), ignored(n);
     std::vector<const wz_tile_t*> tp(n);
     bool still = false;
     for (int i = 0; i < n; ++i) {
@@ -491,6 +509,7 @@ static int motion_enqueue(wz_engine* e, int slot, const TileCall& call) {
         comps[i] = o.components;
         active[i] = o.active;
         held[i] = o.held;
+        ignored[i] = o.ignored;
         still = still || k == 0;
     }
     const TileCall c = with_tiles(call, nt, tp);   // ... a tiled call on these lists
@@ -498,7 +517,8 @@ static int motion_enqueue(wz_engine* e, int slot, const TileCall& call) {
     tile_plan(e, L, c, nullptr, y);
     WZCHK(run_tiles(e, slot, y));
     WZCHK(merge_tail(e, L, c, y.most, L.hrows.d, still, stamps ? M.meta.m.cams : nullptr));
-    // 4. the grids this call wrote are the next call's reference and ages; what wz_motion_stats and wz_motion_hold_stats report
+    // 4. the grids this call wrote are the next call's reference and ages; what wz_motion_stats, wz_motion_hold_stats and
+    // wz_motion_ignore_stats report
     for (int i = 0; i < n; ++i) {
         cams[i]->cur ^= 1;
         cams[i]->has_ref = true;
@@ -513,6 +533,7 @@ static int motion_enqueue(wz_engine* e, int slot, const TileCall& call) {
     M.s_comps.swap(comps);
     M.s_active.swap(active);
     M.s_held.swap(held);
+    M.s_ignored.swap(ignored);
     return WZ_OK;
 }
 
@@ -680,6 +701,71 @@ extern "C" int wz_motion_hold_stats(wz_engine_t* e, int slot, int n, int32_t* ac
         return wz_set_error(WZ_EINVAL, "wz_motion_hold_stats: the last motion call on lane %d had %d frames, not %d", slot, (int)M.s_active.size(), n);
     memcpy(active, M.s_active.data(), sizeof(int32_t) * n);
     memcpy(held, M.s_held.data(), sizeof(int32_t) * n);
+    return WZ_OK;
+}
+
+extern "C" int wz_motion_ignore_stats(wz_engine_t* e, int slot, int n, int32_t* ignored) {
+    if (!e || !ignored || slot < 0 || slot >= e->n_lanes) return wz_set_error(WZ_EINVAL, "wz_motion_ignore_stats: bad argument");
+    const MotionLane& M = e->lanes[slot].motion;
+    if (n < 1 || n != (int)M.s_ignored.size())
+        return wz_set_error(WZ_EINVAL, "wz_motion_ignore_stats: the last motion call on lane %d had %d frames, not %d", slot, (int)M.s_ignored.size(), n);
+    memcpy(ignored, M.s_ignored.data(), sizeof(int32_t) * n);
+    return WZ_OK;
+}
+
+// ---- a camera's ignore mask: the cell bits of the frame's grid for its motion settings, of every tile's own grid
+// for its gate layout.  Built aside behind sync_all: a failure leaves the camera with what it had
+extern "C" int wz_set_camera_ignore(wz_engine_t* e, int cam, int width, int height, const uint8_t* ignore) {
+    if (!e) return wz_set_error(WZ_EINVAL, "wz_set_camera_ignore: null engine");
+    const auto mi = e->motion_cams.find(cam);
+    const auto gi = e->gate_cams.find(cam);
+    MotionCam* m = mi == e->motion_cams.end() ? nullptr : &mi->second;
+    GateCam* g = gi == e->gate_cams.end() ? nullptr : &gi->second;
+    if (!m && !g)
+        return wz_set_error(WZ_EINVAL, "camera %d has neither motion settings nor tiles: an ignore mask is set after wz_set_camera_motion / wz_set_camera_tiles", cam);
+    HIPCHK(hipSetDevice(e->device));
+    if (!ignore) {   // remove
+        WZCHK(sync_all(e));
+        if (m) m->d_ignore = DevBlock<unsigned long long>();
+        if (g) g->d_ignore = DevBlock<uint32_t>(), g->ignore_off.clear();
+        return WZ_OK;
+    }
+    if (m && (width != m->w || height != m->h))
+        return wz_set_error(WZ_EINVAL, "camera %d: the ignore plane is %dx%d but the camera's motion settings were made for %dx%d", cam, width, height, m->w, m->h);
+    if (g && (width != g->w || height != g->h))
+        return wz_set_error(WZ_EINVAL, "camera %d: the ignore plane is %dx%d but the camera's tiles were set for %dx%d", cam, width, height, g->w, g->h);
+    WZCHK(sync_all(e));
+    std::vector<uint8_t> cells;
+    std::vector<unsigned long long> words;
+    DevBlock<unsigned long long> d_motion;
+    DevBlock<uint32_t> d_gate;
+    std::vector<size_t> off;
+    hipError_t err = hipSuccess;
+    if (m) {
+        const size_t n = (size_t)m->gw * m->gh;
+        cells.resize(n);
+        words.resize(ignore_words_of(n));
+        if (wz_ignore_cells(ignore, width, height, nullptr, cells.data()) != WZ_OK) return wz_set_error(WZ_EINVAL, "wz_set_camera_ignore: bad plane");
+        pack_cell_bits(cells.data(), n, words.data());
+        err = d_motion.alloc(words.size());
+        if (err == hipSuccess) err = hipMemcpy(d_motion, words.data(), words.size() * 8, hipMemcpyHostToDevice);
+    }
+    if (g && err == hipSuccess) {
+        words.clear();
+        for (size_t t = 0; t < g->tiles.size(); ++t) {   // (every tile's bits begin at a 64-bit word)
+            const size_t n = (size_t)g->cols[t] * g->crows[t], at = words.size();
+            cells.resize(n);
+            words.resize(at + ignore_words_of(n));
+            if (wz_ignore_cells(ignore, width, height, &g->tiles[t], cells.data()) != WZ_OK) return wz_set_error(WZ_EINVAL, "wz_set_camera_ignore: bad plane");
+            pack_cell_bits(cells.data(), n, words.data() + at);
+            off.push_back(2 * at);
+        }
+        err = d_gate.alloc(2 * words.size());
+        if (err == hipSuccess) err = hipMemcpy(d_gate, words.data(), words.size() * 8, hipMemcpyHostToDevice);
+    }
+    if (err != hipSuccess) return wz_set_error(WZ_EHIP, "wz_set_camera_ignore: %s (camera %d keeps its previous mask)", hipGetErrorString(err), cam);
+    if (m) m->d_ignore = std::move(d_motion);   // (the old bits leave with these two: nothing in flight reads them, every lane was synchronised above)
+    if (g) g->d_ignore = std::move(d_gate), g->ignore_off.swap(off);
     return WZ_OK;
 }
 
@@ -939,10 +1025,11 @@ extern "C" int wz_stage_merge_tiles(wz_engine_t* e, int w, int h, int cam, int n
     return WZ_OK;
 }
 
-// wz_k_tile_activity on one rectangle of one host frame
-extern "C" int wz_stage_tile_activity(wz_engine_t* e, const uint8_t* frame, int w, int h, int fmt, const wz_tile_t* tile, const uint16_t* ref,
-                                      int pixel_thr, uint16_t* sums_out, int32_t* changed_out) {
-    if (!e || !frame || !tile || !sums_out || !changed_out) return wz_set_error(WZ_EINVAL, "wz_stage_tile_activity: null argument");
+// wz_k_tile_activity on one rectangle of one host frame; with_mask: wz_k_tile_activity<true>, the tile's cells_ignored (null: the tile has no
+// mask) as its bits
+static int stage_tile_activity(wz_engine_t* e, const char* who, const uint8_t* frame, int w, int h, int fmt, const wz_tile_t* tile, const uint16_t* ref,
+                               int pixel_thr, bool with_mask, const uint8_t* cells_ignored, uint16_t* sums_out, int32_t* changed_out) {
+    if (!e || !frame || !tile || !sums_out || !changed_out) return wz_set_error(WZ_EINVAL, "%s: null argument", who);
     WZCHK(one_tile_check(w, h, fmt, tile));
     const uint64_t bytes = wz_frame_bytes(w, h, fmt);
     if (pixel_thr < 0 || pixel_thr > 255) return wz_set_error(WZ_EINVAL, "pixel_thr %d, expected 0 .. 255", pixel_thr);
@@ -950,10 +1037,11 @@ extern "C" int wz_stage_tile_activity(wz_engine_t* e, const uint8_t* frame, int 
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     const size_t cells = gate_cells_of(tile->w, tile->h);
-    struct Parts { uint16_t *now, *ref; WzGateTile* tile; int32_t* cnt; size_t bytes; };
-    auto carve = [&](const void* base) {   // one device block: new grid, reference grid, the tile's descriptor, the two counters and the count
+    struct Parts { uint16_t *now, *ref; WzGateTile* tile; int32_t* cnt; unsigned long long* ign; size_t bytes; };
+    auto carve = [&](const void* base) {   // one device block: new grid, reference grid, the tile's descriptor, the two counters and the count, the mask bits
         Carve c(base);
-        Parts p = {c.take<uint16_t>(cells, 16), c.take<uint16_t>(cells, 16), c.take<WzGateTile>(1, 16), c.take<int32_t>(4), 0};
+        Parts p = {c.take<uint16_t>(cells, 16), c.take<uint16_t>(cells, 16), c.take<WzGateTile>(1, 16), c.take<int32_t>(4),
+                   c.take<unsigned long long>(ignore_words_of(cells), 16), 0};
         p.bytes = c.bytes();
         return p;
     };
@@ -965,22 +1053,37 @@ extern "C" int wz_stage_tile_activity(wz_engine_t* e, const uint8_t* frame, int 
     if (err == hipSuccess) err = hipMemset(d, 0, all);
     const Parts p = carve(d);
     if (err == hipSuccess && ref) err = hipMemcpy(p.ref, ref, cells * 2, hipMemcpyHostToDevice);
+    if (err == hipSuccess && cells_ignored) {
+        std::vector<unsigned long long> words(ignore_words_of(cells));
+        pack_cell_bits(cells_ignored, cells, words.data());
+        err = hipMemcpy(p.ign, words.data(), words.size() * 8, hipMemcpyHostToDevice);
+    }
     if (err == hipSuccess) {
         WzGateTile g;
         gate_tile(src, w, fmt, *tile, g);
+        if (cells_ignored) g.ignore = reinterpret_cast<const uint32_t*>(p.ign);
         g.ref = ref ? p.ref : nullptr;
         g.now = p.now;
         g.thr = pixel_thr;
         err = hipMemcpy(p.tile, &g, sizeof(g), hipMemcpyHostToDevice);
         if (err == hipSuccess) {
-            wz_launch_tile_activity(p.tile, 1, g.crows, g.cols, p.cnt, p.cnt + 2, e->stream);
+            wz_launch_tile_activity(p.tile, 1, g.crows, g.cols, p.cnt, p.cnt + 2, e->stream, with_mask);
             err = hipStreamSynchronize(e->stream);
         }
     }
     if (err == hipSuccess) err = hipMemcpy(sums_out, p.now, cells * 2, hipMemcpyDeviceToHost);
     if (err == hipSuccess) err = hipMemcpy(changed_out, p.cnt + 2, 4, hipMemcpyDeviceToHost);
-    if (err != hipSuccess) return wz_set_error(WZ_EHIP, "wz_stage_tile_activity: %s", hipGetErrorString(err));
+    if (err != hipSuccess) return wz_set_error(WZ_EHIP, "%s: %s", who, hipGetErrorString(err));
     return WZ_OK;
+}
+extern "C" int wz_stage_tile_activity(wz_engine_t* e, const uint8_t* frame, int w, int h, int fmt, const wz_tile_t* tile, const uint16_t* ref,
+                                      int pixel_thr, uint16_t* sums_out, int32_t* changed_out) {
+    return stage_tile_activity(e, "wz_stage_tile_activity", frame, w, h, fmt, tile, ref, pixel_thr, false, nullptr, sums_out, changed_out);
+}
+// ... and as a launch with a masked tile runs it
+extern "C" int wz_stage_tile_activity_ignore(wz_engine_t* e, const uint8_t* frame, int w, int h, int fmt, const wz_tile_t* tile, const uint16_t* ref,
+                                             int pixel_thr, const uint8_t* cells_ignored, uint16_t* sums_out, int32_t* changed_out) {
+    return stage_tile_activity(e, "wz_stage_tile_activity_ignore", frame, w, h, fmt, tile, ref, pixel_thr, true, cells_ignored, sums_out, changed_out);
 }
 
 extern "C" int wz_debug_bound_source(wz_engine_t* e, int slot, int32_t* in_place) {
@@ -1042,7 +1145,8 @@ extern "C" int wz_profile_gated(wz_engine_t* e, int n, const uint8_t* const* d_f
     WZCHK(wz_wait(e, 0));
     Lane& L = e->lanes[0];
     const GateLane& G = L.gate;
-    WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_tile_activity(G.meta.m.tiles, G.g_tiles, G.g_crows, G.g_cols, G.d_gcount, G.meta.m.activity, L.stream); }, activity_ms));
+    WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_tile_activity(G.meta.m.tiles, G.g_tiles, G.g_crows, G.g_cols, G.d_gcount, G.meta.m.activity, L.stream, G.g_masked); },
+                     activity_ms));
     WZCHK(bracket_ms(L.stream, reps, [&] { wz_launch_gate_commit(G.meta.m.commits, G.g_tiles, L.hrows.d, G.d_grows, L.stream); }, commit_ms));
     return bracket_ms(L.stream, reps, [] {}, empty_ms);
 }
@@ -1062,6 +1166,9 @@ struct MotionStage {
     bool with_hold = false;
     uint8_t *age_in = nullptr, *age_out = nullptr, *pass = nullptr;
     wz_detection_t* rows = nullptr;
+    // with_mask (the ignore mask's entry points): + the grid's cell bits
+    bool with_mask = false;
+    unsigned long long* ignore = nullptr;
     size_t carve(const void* base) {
         Carve c(base);
         now = c.take<uint16_t>(cells, 16); ref = c.take<uint16_t>(cells, 16); scratch = c.take<uint32_t>(cells, 16);
@@ -1070,11 +1177,12 @@ struct MotionStage {
             age_in = c.take<uint8_t>(cells, 16); age_out = c.take<uint8_t>(cells, 16);
             rows = c.take<wz_detection_t>(WZ_MAX_DETECTIONS, 16); pass = c.take<uint8_t>(WZ_MAX_DETECTIONS, 16);
         }
+        if (with_mask) ignore = c.take<unsigned long long>(ignore_words_of((size_t)cells), 16);
         return c.bytes();
     }
 };
 static int motion_stage(wz_engine* e, const char* who, const uint16_t* now, const uint16_t* ref, int w, int h, int fmt, const wz_motion_t* p, MotionStage& s,
-                        const uint8_t* age = nullptr, int hold = 0, int object_hold = 0) {
+                        const uint8_t* age = nullptr, int hold = 0, int object_hold = 0, const uint8_t* cells_ignored = nullptr) {
     if (!e || !now || !p) return wz_set_error(WZ_EINVAL, "%s: null argument", who);
     WZCHK(motion_refusal(nullptr, who, w, h, fmt, *p));
     if (hold < 0 || hold > 255 || object_hold < 0 || object_hold > 255) return wz_set_error(WZ_EINVAL, "%s: hold and object_hold must be 0 .. 255", who);
@@ -1087,7 +1195,13 @@ static int motion_stage(wz_engine* e, const char* who, const uint16_t* now, cons
     WzMotionCam d;
     motion_desc(w, h, fmt, *p, s.now, ref ? s.ref : nullptr, s.scratch, d);
     if (s.with_hold) motion_hold_desc(age ? s.age_in : nullptr, s.age_out, hold, object_hold, d);
+    if (s.with_mask && cells_ignored) d.ignore = s.ignore;
     HIPCHK(hipMemset(s.d, 0, all));
+    if (s.with_mask && cells_ignored) {
+        std::vector<unsigned long long> words(ignore_words_of((size_t)s.cells));
+        pack_cell_bits(cells_ignored, (size_t)s.cells, words.data());
+        HIPCHK(hipMemcpy(s.ignore, words.data(), words.size() * 8, hipMemcpyHostToDevice));
+    }
     HIPCHK(hipMemcpy(s.now, now, (size_t)s.cells * 2, hipMemcpyHostToDevice));
     if (ref) HIPCHK(hipMemcpy(s.ref, ref, (size_t)s.cells * 2, hipMemcpyHostToDevice));
     if (s.with_hold && age) HIPCHK(hipMemcpy(s.age_in, age, (size_t)s.cells, hipMemcpyHostToDevice));
@@ -1235,6 +1349,45 @@ extern "C" int wz_profile_motion_hold(wz_engine_t* e, const uint16_t* now, const
     HIPCHK(hipMemcpy(s.pass, pass, WZ_MAX_DETECTIONS, hipMemcpyHostToDevice));
     WZCHK(bracket_ms(e->stream, reps, [&] { wz_launch_motion_regions(s.cam, 1, s.cells, s.out, e->stream, true); }, regions_ms));
     WZCHK(bracket_ms(e->stream, reps, [&] { wz_launch_motion_stamp(s.cam, 1, s.rows, s.pass, e->stream); }, stamp_ms));
+    return bracket_ms(e->stream, reps, [] {}, empty_ms);
+}
+
+// ---- ignore masks
+// wz_k_motion_regions<.., true> alone on two caller-provided grids, the caller's ages and the caller's cell mask.  age_out null: as a camera
+// without a hold runs it (<false, true>); cells_ignored null: as a camera without a mask runs inside a launch that has one
+extern "C" int wz_stage_motion_ignore(wz_engine_t* e, const uint16_t* now, const uint16_t* ref, const uint8_t* age_in, int w, int h, int fmt,
+                                      const wz_motion_t* motion, int hold, const uint8_t* cells_ignored, int32_t* n_regions, wz_tile_t* regions,
+                                      int32_t* cells, int32_t* components, int32_t* active, int32_t* held, int32_t* ignored, uint8_t* age_out) {
+    if (!n_regions || !regions || !cells || !components || !active || !held || !ignored) return wz_set_error(WZ_EINVAL, "wz_stage_motion_ignore: null argument");
+    if (!age_out && (age_in || hold)) return wz_set_error(WZ_EINVAL, "wz_stage_motion_ignore: ages or a hold but no age_out: without age_out the camera has no hold");
+    MotionStage s;
+    s.with_hold = age_out != nullptr;
+    s.with_mask = true;
+    WZCHK(motion_stage(e, "wz_stage_motion_ignore", now, ref, w, h, fmt, motion, s, age_in, hold, 0, cells_ignored));
+    wz_launch_motion_regions(s.cam, 1, s.cells, s.out, e->stream, s.with_hold, true);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
+    WzMotionOut o;
+    HIPCHK(hipMemcpy(&o, s.out, sizeof(o), hipMemcpyDeviceToHost));
+    if (age_out) HIPCHK(hipMemcpy(age_out, s.age_out, (size_t)s.cells, hipMemcpyDeviceToHost));
+    *n_regions = o.n_regions;
+    *components = o.components;
+    *active = o.active;
+    *held = o.held;
+    *ignored = o.ignored;
+    memcpy(regions, o.regions, sizeof(o.regions));
+    memcpy(cells, o.cells, sizeof(o.cells));
+    return WZ_OK;
+}
+
+// HIP-event time of the region launch alone on these grids with this cell mask (a camera without a hold)
+extern "C" int wz_profile_motion_ignore(wz_engine_t* e, const uint16_t* now, const uint16_t* ref, int w, int h, int fmt, const wz_motion_t* motion,
+                                        const uint8_t* cells_ignored, int reps, float* regions_ms, float* empty_ms) {
+    if (reps < 1 || !cells_ignored || !regions_ms || !empty_ms) return wz_set_error(WZ_EINVAL, "wz_profile_motion_ignore: bad argument");
+    MotionStage s;
+    s.with_mask = true;
+    WZCHK(motion_stage(e, "wz_profile_motion_ignore", now, ref, w, h, fmt, motion, s, nullptr, 0, 0, cells_ignored));
+    WZCHK(bracket_ms(e->stream, reps, [&] { wz_launch_motion_regions(s.cam, 1, s.cells, s.out, e->stream, false, true); }, regions_ms));
     return bracket_ms(e->stream, reps, [] {}, empty_ms);
 }
 #endif   // WZ_DEV_BUILD

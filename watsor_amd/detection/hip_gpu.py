@@ -288,6 +288,79 @@ def motion_hold_options(options: dict, motion_default, motion_by_name: dict):
     return None, by_name
 
 
+_IGNORE_FORMS = "a list of [x, y, w, h] pixel rectangles, an (H, W) uint8 array or the name of a mask file"
+
+
+def _ignore_spec(spec, where: str):
+    """One checked `ignore` description -> ("rects", [(x, y, w, h), ...]) | ("mask", (H, W) uint8 array) | ("file", name)."""
+    if isinstance(spec, np.ndarray):
+        if spec.ndim != 2 or spec.dtype != np.uint8 or 0 in spec.shape:
+            raise ValueError("%s: an array of shape %r and type %s, expected (H, W) uint8" % (where, spec.shape, spec.dtype))
+        return "mask", np.ascontiguousarray(spec)
+    if isinstance(spec, (str, os.PathLike)):
+        return "file", os.fspath(spec)
+    if not isinstance(spec, (list, tuple)) or not spec:
+        raise ValueError("%s: expected %s, got %r" % (where, _IGNORE_FORMS, spec))
+    whole = lambda v: isinstance(v, int) and not isinstance(v, bool)      # noqa: E731
+    rects = []
+    for r in spec:
+        if not isinstance(r, (list, tuple)) or len(r) != 4 or not all(whole(v) for v in r) or r[0] < 0 or r[1] < 0 or r[2] < 1 or r[3] < 1:
+            raise ValueError("%s: rectangle %r, expected [x, y, w, h]: whole numbers, x and y >= 0, w and h >= 1" % (where, r))
+        rects.append(tuple(r))
+    return "rects", rects
+
+
+def ignore_options(options: dict, motion_default, motion_by_name: dict, tiles_default, tiles_by_name: dict) -> dict:
+    """{camera name: checked description} from the plugin option `ignore`: {camera name: a list of [x, y, w, h] pixel rectangles (a
+    burnt-in clock) | an (H, W) uint8 array, nonzero = ignore | the name of a mask file read with `read_mask_alpha`, alpha > 0 = ignore}
+    -- where the camera's picture changes without anything moving (`HipEngine.set_camera_ignore`).  Per camera name only: a mask is a
+    picture of one camera's view.  The other arguments are what `motion_options` and `tile_options` returned: a mask silences change,
+    so its camera needs `motion` or tiles with a "gate".  Bad options raise ValueError; the message begins with the option at fault."""
+    v = options.get("ignore")
+    if v is None:
+        return {}
+    if not isinstance(v, dict) or not v:
+        raise ValueError("ignore: expected {camera name: %s}, got %r" % (_IGNORE_FORMS, v))
+    out = {}
+    for name, spec in v.items():
+        where = "ignore[%r]" % (name,)
+        out[str(name)] = _ignore_spec(spec, where)
+        tiles = tiles_by_name.get(str(name), tiles_default)
+        if motion_default is None and str(name) not in motion_by_name and (tiles is None or "gate" not in tiles):
+            raise ValueError("%s: the camera has neither a motion option nor tiles with a gate: an ignore mask silences change, and nothing "
+                             "of this camera looks for change" % where)
+    return out
+
+
+def check_ignore_cameras(ignore_by_name: dict, names) -> None:
+    """What `ignore_options` cannot see on its own: every camera it names must be one of the detector's cameras `names` (the keys of the
+    worker's frame buffers).  Raises ValueError."""
+    for name in sorted(set(ignore_by_name) - {str(n) for n in names}):
+        raise ValueError("ignore[%r]: unknown camera, this detector's cameras are %s" % (name, ", ".join(repr(str(n)) for n in names) or "none"))
+
+
+def ignore_plane(spec, where: str, width: int, height: int) -> np.ndarray:
+    """The (height, width) uint8 ignore plane, nonzero = ignore, of a checked `ignore` description for a camera's width x height frames.
+    ValueError for a rectangle that does not lie inside the frame and for a mask of another size."""
+    kind, v = spec
+    if kind == "rects":
+        plane = np.zeros((height, width), np.uint8)
+        for x, y, w, h in v:
+            if x + w > width or y + h > height:
+                raise ValueError("%s: rectangle %r does not lie inside the camera's %dx%d frame" % (where, [x, y, w, h], width, height))
+            plane[y:y + h, x:x + w] = 1
+        return plane
+    if kind == "file":
+        from ..filter.hip_filter import read_mask_alpha
+        try:
+            v = (read_mask_alpha(v) > 0).astype(np.uint8)
+        except AssertionError as e:
+            raise ValueError("%s: %s" % (where, e))
+    if v.shape != (height, width):
+        raise ValueError("%s: the mask is %dx%d (width x height) but the camera's frames are %dx%d" % (where, v.shape[1], v.shape[0], width, height))
+    return v
+
+
 def cut_calls(items, max_batch: int):
     """Cuts a list of frames into the consecutive calls one rule allows: items[i] = (key, cost, camera that may appear once per call, or
     None); a new call starts when the key changes, when the cost would pass max_batch, or when such a camera appears again.  Returns the
@@ -366,6 +439,12 @@ class HipObjectDetector:
         one of these}: a cell stays part of the camera's regions for `hold` further frames after it changed, and for `object_hold`
         further frames after a detection that passed the camera's filters covered it -- a person who stops moving, a parked car the
         whole-frame tile found (include/watsor_hip.h: wz_set_camera_motion_hold).  A camera without `motion` cannot have one.
+        `options["ignore"]`: {camera name: [[x, y, w, h], ...] | (H, W) uint8 array | mask file name} -- the parts of that camera's picture
+        that change without anything moving: a burnt-in clock (the rectangles), a flag, a hedge, a road behind the fence (an array,
+        nonzero = ignore, or a 32-bit mask image as the zones use, alpha > 0 = ignore).  A 16 x 16 cell with at least one ignored pixel
+        never counts as changed, neither for `motion` nor for a "gate" (include/watsor_hip.h: wz_set_camera_ignore); detections inside
+        the area are reported as ever.  Per camera name only; the camera needs `motion` or tiles with a "gate", and -- like every
+        per-camera option -- takes effect for the ids `bind_cameras` hands out.
         `options["schedule"]`: "latency" | "throughput" | "auto" (default) -- the launch shapes of this detector PROCESS
         (include/watsor_hip.h: wz_set_schedule).  "latency" makes a lone batch finish soonest -- the reference's normal load is one
         frame at a time (`_next_frame`, detector.py:102-112); "throughput" gets the most frames per second out of four batches in
@@ -416,6 +495,8 @@ class HipObjectDetector:
         self.__motion_layouts = {}      # camera id -> what its motion settings were last made for: (width, height, base format, settings)
         self.__hold_default, self.__hold_by_name = motion_hold_options(options, self.__motion_default, self.__motion_by_name)
         self.__hold_by_cam = {}
+        self.__ignore_by_name = ignore_options(options, self.__motion_default, self.__motion_by_name, self.__tiles_default, self.__tiles_by_name)
+        self.__ignore_by_cam = {}       # camera id -> (camera name, checked description)
         for where, spec in [("tiles", self.__tiles_default)] + [("tiles[%r]" % n, t) for n, t in self.__tiles_by_name.items()]:
             if spec is not None and spec["count"] > max_batch:
                 raise ValueError("%s: %d tiles per frame exceed max_batch %d" % (where, spec["count"], max_batch))
@@ -516,6 +597,7 @@ class HipObjectDetector:
         from ..filter.hip_filter import HipCameraFilter
         from .._lib import WZ_MAX_CAMS
         names = sorted(frame_buffers, key=str)
+        check_ignore_cameras(self.__ignore_by_name, names)
         gate_all = self.__tiles_default is not None and "gate" in self.__tiles_default      # (a gate keeps state per camera: every camera needs an id)
         motion_all = self.__motion_default is not None                                      # (and so does the motion reference)
         need = [n for n in names if gate_all or motion_all or n in (camera_configs or {}) or str(n) in self.__fmt_by_name
@@ -529,6 +611,7 @@ class HipObjectDetector:
         self.__tiles_by_cam = {i: self.__tiles_by_name[str(name)] for name, i in ids.items() if i >= 0 and str(name) in self.__tiles_by_name}
         self.__motion_by_cam = {i: self.__motion_by_name[str(name)] for name, i in ids.items() if i >= 0 and str(name) in self.__motion_by_name}
         self.__hold_by_cam = {i: self.__hold_by_name[str(name)] for name, i in ids.items() if i >= 0 and str(name) in self.__hold_by_name}
+        self.__ignore_by_cam = {i: (str(name), self.__ignore_by_name[str(name)]) for name, i in ids.items() if i >= 0 and str(name) in self.__ignore_by_name}
         for name, cfg in (camera_configs or {}).items():
             if name in ids:
                 self.__filters.append(HipCameraFilter(self.__engine, ids[name], cfg, drop=drop))
@@ -702,6 +785,7 @@ class HipObjectDetector:
                     hold = self.__hold_by_cam.get(cameras[i]) or self.__hold_default      # (new motion settings drop the hold: it is set behind them)
                     if hold is not None:
                         self.__engine.set_camera_motion_hold(cameras[i], hold["hold"], hold["object_hold"])
+                    self._set_ignore(cameras[i], w, h)      # (... and the motion part of the mask)
                     self.__motion_layouts[cameras[i]] = layout
             if len(ok) < len(moving) and n == len(calls) - 1:
                 break
@@ -763,7 +847,14 @@ class HipObjectDetector:
         layout = (w, h, fmt & FMT_BASE_MASK, tuple(rects), gate)
         if self.__gate_layouts.get(cam) != layout:
             self.__engine.set_camera_tiles(cam, w, h, rects, gate[0], gate[1], gate[2], fmt)
+            self._set_ignore(cam, w, h)      # (a new layout drops the gate part of the mask: it is set behind it)
             self.__gate_layouts[cam] = layout
+
+    def _set_ignore(self, cam: int, w: int, h: int) -> None:
+        """Camera `cam`'s ignore mask in the engine, behind every (re)configuration of its motion settings or tiles."""
+        named = self.__ignore_by_cam.get(cam)
+        if named is not None:
+            self.__engine.set_camera_ignore(cam, ignore_plane(named[1], "ignore[%r]" % (named[0],), w, h))
 
     def detect(self, image_shape, image_np, detections: List[Detection]):
         return self._detect([image_np.reshape(image_shape)], [detections], None, None)

@@ -468,6 +468,29 @@ class HipEngine:
         self._ck(self._lib.wz_motion_hold_stats(self._h, slot, n, C.byref(active), C.byref(held)))
         return [int(v) for v in active], [int(v) for v in held]
 
+    # -- ignore masks (include/watsor_hip.h: wz_set_camera_ignore) ------------------------------------------------
+    def set_camera_ignore(self, cam: int, mask: Optional[np.ndarray]) -> None:
+        """Camera `cam`, which has motion settings, a gate layout or both, ignores change where `mask` -- (height, width) uint8, the size
+        its settings were made for -- is nonzero: a 16 x 16-pixel cell with at least one ignored pixel never counts as changed, neither
+        for its motion regions nor for its tiles' activity (`ignore_cells` is the rule).  None removes the mask.  Waits for every lane.
+        `set_camera_motion` drops the motion part and `set_camera_tiles` the gate part: set the mask after them."""
+        if mask is None:
+            self._ck(self._lib.wz_set_camera_ignore(self._h, int(cam), 0, 0, None))
+            return
+        m = _ignore_plane(mask)
+        self._ck(self._lib.wz_set_camera_ignore(self._h, int(cam), m.shape[1], m.shape[0], C.c_void_p(m.ctypes.data)))
+
+    def motion_ignore_stats(self, slot: int = 0):
+        """Per frame of the last motion call accepted on lane `slot`: the changed cells that its camera's ignore mask removed (0 for a
+        camera without one)."""
+        cams = self._motion_last.get(slot)
+        if not cams:
+            raise ValueError("no motion call was made on lane %d" % slot)
+        n = len(cams)
+        ignored = (C.c_int32 * n)()
+        self._ck(self._lib.wz_motion_ignore_stats(self._h, slot, n, C.byref(ignored)))
+        return [int(v) for v in ignored]
+
     def submit_device(self, slot: int, d_frames: Sequence[int], widths: Sequence[int], heights: Sequence[int],
                       cams: Optional[Sequence[int]] = None, formats: Optional[Sequence[int]] = None) -> None:
         n = len(d_frames)
@@ -825,6 +848,66 @@ class HipEngine:
                                                   C.c_void_p(sums.ctypes.data), C.byref(changed)))
         return sums, int(changed.value)
 
+    def stage_tile_activity_ignore(self, frame: np.ndarray, tile, cells_ignored: Optional[np.ndarray], fmt: int = FMT_RGB24,
+                                   ref: Optional[np.ndarray] = None, pixel_thr: int = 0):
+        """`stage_tile_activity` as a launch with a masked tile runs it: `cells_ignored` is the tile's cell mask (uint8 [cell rows, cell
+        columns], nonzero: ignored; None: this tile has none); the count leaves the ignored cells out, the sums are the same."""
+        self._dev_only("stage_tile_activity_ignore()")
+        if not frame.flags["C_CONTIGUOUS"]:
+            frame = np.ascontiguousarray(frame)
+        w, h = self.frame_geometry(frame, fmt)
+        t = Tile(*[int(v) for v in tile])
+        shape = (max(1, -(-t.h // _lib.WZ_GATE_CELL)), max(1, -(-t.w // _lib.WZ_GATE_CELL)))
+        ref, = self._motion_grids(shape, ref=(ref, np.uint16))
+        cells_ignored, = self._motion_grids(shape, cells_ignored=(cells_ignored, np.uint8))
+        sums = np.zeros(shape, np.uint16)
+        changed = C.c_int32(-1)
+        ptr = lambda g: C.c_void_p(g.ctypes.data) if g is not None else None      # noqa: E731
+        self._ck(self._lib.wz_stage_tile_activity_ignore(self._h, C.c_void_p(frame.ctypes.data), w, h, int(fmt), C.byref(t), ptr(ref), int(pixel_thr),
+                                                         ptr(cells_ignored), C.c_void_p(sums.ctypes.data), C.byref(changed)))
+        return sums, int(changed.value)
+
+    def stage_motion_ignore(self, now: np.ndarray, ref: Optional[np.ndarray], cells_ignored: Optional[np.ndarray], width: int, height: int,
+                            threshold: int, hold: Optional[int] = None, age: Optional[np.ndarray] = None, min_cells: int = 1, dilate: int = 1,
+                            max_regions: int = 3, min_side: int = 300, pad: int = 8, fmt: int = FMT_RGB24):
+        """The region kernel alone as a launch with a masked camera runs it: `cells_ignored` is the grid's cell mask (uint8 [cell rows, cell
+        columns], nonzero: ignored; None: this camera has none).  hold None: a camera without a hold -> (rectangles, the changed cells of
+        every region, components, the changed cells the mask removed).  hold an int (with the ages `age`, None: all zero): a camera with
+        one -> `stage_motion_hold`'s tuple with the removed cells as its last element."""
+        self._dev_only("stage_motion_ignore()")
+        shape = (-(-int(height) // _lib.WZ_GATE_CELL), -(-int(width) // _lib.WZ_GATE_CELL))
+        now, ref, age, cells_ignored = self._motion_grids(shape, now=(now, np.uint16), ref=(ref, np.uint16), age=(age, np.uint8),
+                                                          cells_ignored=(cells_ignored, np.uint8))
+        if hold is None and age is not None:
+            raise ValueError("ages without a hold")
+        words = self._motion_words(threshold, min_cells, dilate, max_regions, min_side, pad, False)
+        most = _lib.WZ_MOTION_MAX_REGIONS
+        n, comps, active, held, ignored = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+        tiles, cells = (Tile * most)(), (C.c_int32 * most)()
+        out = None if hold is None else np.full(shape, 0xA5, np.uint8)
+        ptr = lambda g: C.c_void_p(g.ctypes.data) if g is not None else None      # noqa: E731
+        self._ck(self._lib.wz_stage_motion_ignore(self._h, ptr(now), ptr(ref), ptr(age), int(width), int(height), int(fmt), C.byref(words),
+                                                  int(hold or 0), ptr(cells_ignored), C.byref(n), C.byref(tiles), C.byref(cells), C.byref(comps),
+                                                  C.byref(active), C.byref(held), C.byref(ignored), ptr(out)))
+        rects, ns = [(t.x0, t.y0, t.w, t.h) for t in tiles[:n.value]], [int(v) for v in cells[:n.value]]
+        if hold is None:
+            return rects, ns, int(comps.value), int(ignored.value)
+        return rects, ns, int(comps.value), int(active.value), int(held.value), out, int(ignored.value)
+
+    def profile_motion_ignore(self, now: np.ndarray, ref: Optional[np.ndarray], cells_ignored: np.ndarray, width: int, height: int, threshold: int,
+                              min_cells: int = 1, dilate: int = 1, max_regions: int = 3, min_side: int = 300, pad: int = 8,
+                              fmt: int = FMT_RGB24, reps: int = 100):
+        """(ms of the region launch alone on these grids with this cell mask, ms of an empty bracket): HIP-event brackets, the mean of `reps`."""
+        self._dev_only("profile_motion_ignore()")
+        shape = (-(-int(height) // _lib.WZ_GATE_CELL), -(-int(width) // _lib.WZ_GATE_CELL))
+        now, ref, cells_ignored = self._motion_grids(shape, now=(now, np.uint16), ref=(ref, np.uint16), cells_ignored=(cells_ignored, np.uint8))
+        words = self._motion_words(threshold, min_cells, dilate, max_regions, min_side, pad, False)
+        reg, empty = C.c_float(), C.c_float()
+        ptr = lambda g: C.c_void_p(g.ctypes.data) if g is not None else None      # noqa: E731
+        self._ck(self._lib.wz_profile_motion_ignore(self._h, ptr(now), ptr(ref), int(width), int(height), int(fmt), C.byref(words), ptr(cells_ignored),
+                                                    int(reps), C.byref(reg), C.byref(empty)))
+        return float(reg.value), float(empty.value)
+
     def stage_motion_regions(self, now: np.ndarray, ref: Optional[np.ndarray], width: int, height: int, threshold: int, min_cells: int = 1,
                              dilate: int = 1, max_regions: int = 3, min_side: int = 300, pad: int = 8, fmt: int = FMT_RGB24):
         """The region kernel alone on two grids of luma sums (uint16 [cell rows, cell columns] of a width x height frame of format `fmt`; ref
@@ -981,6 +1064,27 @@ class HipEngine:
                                            C.c_void_p(s.ctypes.data), C.c_void_p(c.ctypes.data),
                                            C.c_void_p(rows.ctypes.data)))
         return rows
+
+
+def _ignore_plane(mask) -> np.ndarray:
+    m = np.asarray(mask)
+    if m.ndim != 2 or m.dtype != np.uint8 or m.shape[0] < 1 or m.shape[1] < 1:
+        raise ValueError("an ignore mask is a (height, width) uint8 array, got %s of shape %r" % (m.dtype, m.shape))
+    return np.ascontiguousarray(m)
+
+
+def ignore_cells(mask: np.ndarray, rect=None) -> np.ndarray:
+    """Host-side: the cell rule of an ignore mask (include/watsor_hip.h: wz_ignore_cells).  mask (H, W) uint8, nonzero = ignore -> uint8
+    [cell rows, cell columns] of `rect` = (x0, y0, w, h) (None: the whole frame), 1 where at least one pixel of the 16 x 16-pixel cell
+    -- anchored at the rectangle's origin, the last column and row partial -- is ignored."""
+    m = _ignore_plane(mask)
+    h, w = m.shape
+    t = Tile(0, 0, w, h) if rect is None else Tile(*[int(v) for v in rect])
+    cells = np.zeros((max(1, -(-t.h // _lib.WZ_GATE_CELL)), max(1, -(-t.w // _lib.WZ_GATE_CELL))), np.uint8)
+    rc = _lib.load().wz_ignore_cells(C.c_void_p(m.ctypes.data), w, h, None if rect is None else C.byref(t), C.c_void_p(cells.ctypes.data))
+    if rc != _lib.WZ_OK:
+        raise ValueError("rectangle (%d, %d, %d x %d) is empty or lies outside the %dx%d ignore mask" % (t.x0, t.y0, t.w, t.h, w, h))
+    return cells
 
 
 def zones_from_alpha(alpha: np.ndarray, max_zones: int = 40):
