@@ -552,9 +552,9 @@ def _compare(rep: Report, op, idx: int, what: str, got: np.ndarray, ref: np.ndar
     return worst, max(acc_share, 0.0)
 
 
-def walk(eng, prog: "arch.Program", weights: Dict[str, np.ndarray], x_half: np.ndarray, precision: int = 16,
+def walk(eng, prog: "arch.Program", weights: Dict[str, np.ndarray], x_half: Optional[np.ndarray], precision: int = 16,
          frames: Optional[Sequence[int]] = None, check: bool = True, float_form_upto: int = -1,
-         marks: Optional[Dict[str, dict]] = None) -> Report:
+         marks: Optional[Dict[str, dict]] = None, heads: Optional[tuple] = None) -> Report:
     """One forward pass of `eng` (tensors(), stage_forward(), stage_read_tensor(); every tensor must stay readable) on x_half
     [n,S,S,4] float16, then EVERY op of `prog` on its own: source (and residual) as the engine produced them -> ref, tol -> the
     destination the engine produced.  `frames`: the frames whose references are computed (default: all).  float_form_upto: the last
@@ -568,10 +568,20 @@ def walk(eng, prog: "arch.Program", weights: Dict[str, np.ndarray], x_half: np.n
     exactly 0, so the weight column is zero in both halves and nothing but the bias reaches the store).
     Counts what it covers and asserts that nothing is left out: every op is checked; every channel of every tensor other than the
     input is written by exactly one checked op; every row of the two head outputs by exactly one head.  check=True raises
-    AssertionError naming every failing op; the Report says what was seen."""
-    n = x_half.shape[0]
+    AssertionError naming every failing op; the Report says what was seen.
+    heads = (box_enc [n,A,4], logits [n,A,C]): nothing is run here -- the tensors are those of the batch the caller ran on lane 0
+    (detect_batch / submit + collect on an engine whose tensors stay readable) and these are its head outputs
+    (stage_post_lane(0, n)); x_half is not looked at.  The input tensor is then whatever the resize kernel stored: a pair input's lo
+    half is not zero, and every op that reads a pair outside a fused block (the `-p 32` stems) gets hi + lo summed in float64."""
+    if heads is None:
+        n = x_half.shape[0]
+        be, lg = eng.stage_forward(x_half)
+    else:
+        be, lg = heads
+        n = be.shape[0]
+        assert lg.shape[0] == n and be.shape[1:] == (prog.num_anchors, 4) and lg.shape[1] == prog.num_anchors
     frames = list(range(n)) if frames is None else sorted(set(int(f) for f in frames))
-    be, lg = eng.stage_forward(x_half)
+    assert frames and 0 <= frames[0] and frames[-1] < n
     info = {name: (i, h, w, c) for i, (name, h, w, c) in enumerate(eng.tensors())}
     last_use: Dict[str, int] = {}
     for i, op in enumerate(prog.ops):
@@ -594,6 +604,14 @@ def walk(eng, prog: "arch.Program", weights: Dict[str, np.ndarray], x_half: np.n
             hl = [eng.stage_read_tensor(info[name][0], f, halves=True) for f in frames]
             hcache[name] = (np.stack([h for h, _ in hl]), np.stack([l for _, l in hl]))
         return hcache[name]
+
+    def value(name: str) -> np.ndarray:
+        """What an op outside the fused blocks reads: a pair as the float64 sum of its stored halves (read() would give the float32
+        sum, one rounding that is not the kernel's), any other tensor as stored."""
+        if not prog.tensors[name].hp:
+            return read(name)
+        hi, lo = halves(name)
+        return hi.astype(np.float64) + lo.astype(np.float64)
 
     def record(kind, scope, worst, acc):
         if kind not in rep.worst or worst > rep.worst[kind][0]:
@@ -672,7 +690,7 @@ def walk(eng, prog: "arch.Program", weights: Dict[str, np.ndarray], x_half: np.n
                     del c_[t]
             continue
         try:
-            res = reference(op, weights, read(op.src), read(op.res) if op.res else None, precision)
+            res = reference(op, weights, value(op.src), value(op.res) if op.res else None, precision)
         except AssertionError as e:
             rep.ops_unchecked += 1
             rep.failures.append("op %d (%s): %s" % (idx, op.scope, e))

@@ -616,6 +616,53 @@ def test_walker_passes_the_block_emulator_in_every_order(blocks, form):
     assert set(worst) >= ({"block_plain"} if form == "plain_fp16" else {"block_hp_q"} if form == "float_form" else {"block_hp", "block_hp2"})
 
 
+class RanBefore(BlockEngine):
+    """An engine whose batch was run before the walk (tests/test_gpu_production_walk.py): the input pair holds the lo half it was
+    given.  ignore_lo: the first block computes from the hi half alone, the stored input keeps its lo."""
+
+    def run(self, hi, lo, ignore_lo=False):
+        self.T = {"input": (hi, np.zeros_like(lo) if ignore_lo else lo)}
+        for op in self.prog.ops:
+            self._block(op, None)
+            self.T["input"] = (hi, lo)
+        n = hi.shape[0]
+        return np.zeros((n, 0, 4), F32), np.zeros((n, 0, arch.NUM_CLASSES), F32)
+
+    def stage_forward(self, x_half):
+        raise AssertionError("the walker ran a batch of its own")
+
+
+@pytest.mark.parametrize("form", ["float_form", "unorm16"])
+def test_walker_takes_a_batch_that_ran_before_it_and_its_lo_half(blocks, form):
+    """heads=(box_enc, logits): no stage_forward, the first block's reference from the stored halves.  With a lo half of order one
+    an engine that ignores it is named; with the lo half a resize stores (2^-12 of the input) ignoring it stays inside the first
+    block's bound on this program -- what tests/test_gpu_input_lo.py exists for."""
+    progs, x = blocks
+    prog, W, ffu = progs[form]
+    assert prog.tensors["input"].hp
+    rng = np.random.Generator(np.random.PCG64(41))
+    v = np.zeros(x.shape, F32)
+    v[..., :3] = rng.uniform(-1, 1, x.shape[:3] + (3,)).astype(F32)
+    hi = v.astype(np.float16)
+    small = (v - hi.astype(F32)).astype(np.float16)
+    assert (small[..., :3] != 0).mean() > 0.9
+    for lo, flagged in ((R.noise_input(prog.size, 43, 1.0)[None].repeat(x.shape[0], 0), True), (small, None)):
+        for ignore in (False, True):
+            e = RanBefore(prog, W, ffu, "chunks32")
+            heads = e.run(hi, lo, ignore)
+            rep = R.walk(e, prog, W, None, float_form_upto=ffu, check=False, heads=heads)
+            assert rep.ops_checked == len(prog.ops) and rep.ops_unchecked == 0
+            if not ignore:
+                assert not rep.failures, rep.failures[:3]
+            elif flagged:
+                assert rep.failures and all("(b0," in f for f in rep.failures), rep.failures[:3]
+            else:
+                print("\n%s: the lo half of a resize ignored by block 0: %d failure(s), worst err / tol %.3g"
+                      % (form, len(rep.failures), max(v_[0] for v_ in rep.worst.values())))
+    with pytest.raises(AssertionError):
+        R.walk(e, prog, W, None, float_form_upto=ffu, heads=(heads[0], heads[1][:1]))
+
+
 # defect -> (block it is put into, the forms it exists in)
 STRUCTURAL = {
     "halo_holds_relu6_bias":              ("b2", sorted(FORMS)),

@@ -247,13 +247,16 @@ def _op_record(op, tindex, n_pad, kc, w_off, b_off, mb) -> bytes:
 def assign_slots(prog: "arch.Program", tensor_names: List[str]) -> List[int]:
     """Liveness-based buffer sharing: tensors whose lifetimes do not overlap reuse one HBM buffer.  A tensor written by several ops
     (the concat of an Inception module, one slice per branch) lives from its first writer on; the slot is taken before that op's
-    inputs are released, so no writer's input can share it."""
+    inputs are released, so no writer's input can share it.  A head's convolution may be launched after the last op (the grouped
+    launches of HeadPark::flush, csrc/wz_network.hip): what a head reads lives to the end of the program and its slot is never
+    released.  (Every builder appends the heads last, where nothing is allocated any more: the rule costs today's programs no slot.)"""
     index = {n: i for i, n in enumerate(tensor_names)}
     last_use = {n: -1 for n in tensor_names}
     for oi, op in enumerate(prog.ops):
-        last_use[op.src] = oi
+        at = oi if op.out_mode == arch.OUT_ACT else len(prog.ops)
+        last_use[op.src] = max(last_use[op.src], at)
         if op.res:
-            last_use[op.res] = oi
+            last_use[op.res] = max(last_use[op.res], at)
     size = {n: prog.tensors[n].h * prog.tensors[n].w * (4 if n == "input" else prog.tensors[n].c) * (2 if prog.tensors[n].hp else 1)
             for n in tensor_names}
     slot_of = [-1] * len(tensor_names)
