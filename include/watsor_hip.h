@@ -350,20 +350,33 @@ int wz_bind_frames(wz_engine_t* e, int n, const uint8_t* const* pixels, const in
  *   gated == 0, n_tiles == 0, tiles == NULL   the entries are untiled again.
  * first / count outside the table: WZ_EINVAL. */
 int wz_bind_tiles(wz_engine_t* e, int first, int count, int n_tiles, const wz_tile_t* tiles, double iou_thr, double ios_thr, int gated);
+/* Motion regions through the frame table: entries first .. first + count - 1 of the current table -- the frames of one
+ * motion camera's FrameBuffer -- get a motion description with the merge thresholds iou_thr / ios_thr (wz_detect_motion).  It carries no
+ * rectangles and no settings: settings, hold and ignore mask are the ones wz_set_camera_motion, wz_set_camera_motion_hold and
+ * wz_set_camera_ignore gave the entries' camera, looked up when a batch is submitted -- they may be set or replaced after this call.  Waits
+ * for every lane first; on any refusal no entry changes.  WZ_EINVAL: a null engine; first / count outside the table; entries that do not all
+ * carry one camera id >= 0; a threshold that is NaN or negative.  wz_bind_tiles(e, first, count, 0, NULL, .., 0) makes the entries untiled
+ * again; wz_bind_frames drops the descriptions with the table. */
+int wz_bind_motion(wz_engine_t* e, int first, int count, double iou_thr, double ios_thr);
 /* A batch of table entries on lane `slot`.  All entries untiled: an ordinary batch, as wz_submit_host runs it.  All entries tiled: the
  * tiled call wz_detect_tiled defines, with every refusal of one (the tiles of the batch beyond max_batch: WZ_ELIMIT; a camera filter set
  * for another size: WZ_EINVAL), made before anything is enqueued; the entries' thresholds must be equal (WZ_EINVAL: the merge launch takes one pair).  All entries
  * gated: the gated call wz_detect_gated defines, with its refusals (one frame per camera and call, a camera without a layout or with one
  * of another size or base format: WZ_EINVAL; the configured tile counts beyond max_batch: WZ_ELIMIT) and equal thresholds; the call
- * returns once the decision is made, as wz_submit_gated_device does, and wz_gate_stats describes the slot.  A batch that mixes two of
- * the three kinds: WZ_EINVAL.  A refusal leaves the lane, the cameras' gate state and every row as they were.
+ * returns once the decision is made, as wz_submit_gated_device does, and wz_gate_stats describes the slot.  All entries motion
+ * (wz_bind_motion): the motion call wz_detect_motion defines, with its refusals (one frame per camera and call, a camera without motion
+ * settings or with settings of another size or base format: WZ_EINVAL; the cameras' configured whole_frame + max_regions beyond max_batch:
+ * WZ_ELIMIT) and equal thresholds; the call returns once the rectangles are read, as wz_submit_motion_device does, and wz_motion_stats,
+ * wz_motion_hold_stats and wz_motion_ignore_stats describe the slot.  A batch that mixes two of the four kinds: WZ_EINVAL.  A refusal
+ * leaves the lane, the cameras' gate and motion state and every row as they were.
  * Where the pixels of a tiled or gated entry come from: a frame inside a wz_host_register()ed range is read IN PLACE by the crop and
  * activity kernels (which read the rectangles' rows and nothing else) when the rectangles' bytes -- wz_frame_bytes(tile w, tile h, fmt)
  * summed over the frame's tiles, twice that for a gated entry, whose tiles are measured and then read again when they run -- are at
- * most half of the frame's; otherwise the frame is staged whole by one DMA and cut from that copy. */
+ * most half of the frame's; otherwise the frame is staged whole by one DMA and cut from that copy.  A motion entry is always staged
+ * whole: its activity launch reads every luma pixel of the frame, so what it reads is never at most half of the frame's bytes. */
 int wz_submit_bound(wz_engine_t* e, int slot, int n, const int32_t* entries);
 /* waits for `slot`, writes its rows into the bound frames' rows: the batch's own rows or, after a tiled or gated submit, the frames'
- * merged rows (also when no tile of a gated batch ran).  WZ_EINCOMPLETE is returned after the rows are written, as by wz_collect. */
+ * merged rows (also when no tile of a gated batch ran, and when no frame of a motion batch had a tile: padding rows).  WZ_EINCOMPLETE is returned after the rows are written, as by wz_collect. */
 int wz_collect_bound(wz_engine_t* e, int slot);
 /* Wait for `slot` without copying rows out (rows stay readable via wz_slot_rows). */
 int wz_wait(wz_engine_t* e, int slot);
@@ -592,7 +605,8 @@ int wz_stage_motion_ignore(wz_engine_t* e, const uint16_t* now, const uint16_t* 
 int wz_profile_motion_ignore(wz_engine_t* e, const uint16_t* now, const uint16_t* ref, int w, int h, int fmt, const wz_motion_t* motion,
                              const uint8_t* cells_ignored, int reps, float* regions_ms, float* empty_ms);
 /* in_place[i] = 1 where frame i of the last wz_submit_bound on `slot` -- untiled, tiled or gated -- was read in place through its device view,
- * 0 where it was staged by DMA (n values: the frames of that batch); WZ_EINVAL when the lane has seen no such batch */
+ * 0 where it was staged by DMA (n values: the frames of that batch; every frame of a motion batch: 0); WZ_EINVAL when the lane has seen no
+ * such batch */
 int wz_debug_bound_source(wz_engine_t* e, int slot, int32_t* in_place /* [n] */);
 
 #endif /* WZ_DEV_BUILD */

@@ -88,6 +88,7 @@ SIGNATURES = {
     "wz_collect": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "wz_bind_frames": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i32p, c_i32p, c_i32p, c_i32p, C.POINTER(C.c_void_p)]),
     "wz_bind_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int]),
+    "wz_bind_motion": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]),
     "wz_submit_bound": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_i32p]),
     "wz_collect_bound": (C.c_int, [C.c_void_p, C.c_int]),
     "wz_wait": (C.c_int, [C.c_void_p, C.c_int]),

@@ -257,7 +257,7 @@ struct wz_engine {
         MappedBlock<uint32_t> hstatus;       // one word per frame, non-zero = the frame's rows may be short (wz_k_nms)
         MappedBlock<unsigned long long> hstamps;   // stamps build: the page-locked pairs the host reads
         std::vector<int32_t> bound_idx;      // frame-table entries of the batch in flight (empty: not a bound batch)
-        std::vector<int32_t> bound_src;      // the last tiled or gated bound batch accepted on this lane (development library: the last bound batch of any kind): 1 = frame i was read in place, 0 = staged
+        std::vector<int32_t> bound_src;      // the last tiled, gated or motion bound batch accepted on this lane (development library: the last bound batch of any kind): 1 = frame i was read in place, 0 = staged
         TileLane tile;
         GateLane gate;
         MotionLane motion;
@@ -284,11 +284,12 @@ struct wz_engine {
     std::vector<BoundFrame> bound;
     // the tiled description of a table entry (wz_bind_tiles).  Kept beside the table, and EMPTY while no entry has one: the untiled
     // wz_submit_bound looks at nothing but that.
-    enum { BOUND_PLAIN = 0, BOUND_TILED = 1, BOUND_GATED = 2 };
+    enum { BOUND_PLAIN = 0, BOUND_TILED = 1, BOUND_GATED = 2, BOUND_MOTION = 3 };
     struct BoundTiles {
         int kind = BOUND_PLAIN;
-        std::vector<wz_tile_t> tiles;   // BOUND_TILED: the entry's rectangles (BOUND_GATED: its camera's, looked up at submit)
-        double iou = 0.0, ios = 0.0;    // the merge thresholds of both kinds
+        std::vector<wz_tile_t> tiles;   // BOUND_TILED: the entry's rectangles (BOUND_GATED: its camera's, looked up at submit; BOUND_MOTION
+                                        // (wz_bind_motion): none -- its camera's settings, hold and mask are looked up at submit, the region launch finds the rectangles)
+        double iou = 0.0, ios = 0.0;    // the merge thresholds of the three kinds
     };
     std::vector<BoundTiles> bound_tiles;   // [bound.size()] or empty
 
@@ -385,7 +386,7 @@ bool read_in_place(const wz_engine* e, int h);
 bool rows_fit(const wz_engine* e, int n, const int* w, const int* fmt);
 int sync_all(wz_engine* e);
 hipError_t lane0_fill(wz_engine* e, void* dst, int value, size_t bytes);
-// ---- wz_tiles.hip, for wz_submit_bound: a batch with a tiled or gated entry ---------------------------------------------------------
+// ---- wz_tiles.hip, for wz_submit_bound: a batch with a tiled, gated or motion entry ---------------------------------------------------------
 int submit_bound_tiles(wz_engine* e, int slot, int n, const int32_t* entries);
 
 // Why a call's lane or batch size is refused (wz_last_error is set, the code returned), or WZ_OK: the checks named in `checks`, in this order

@@ -1,4 +1,4 @@
-// Tiled, gated, motion-region and tiled frame-table detection (include/watsor_hip.h; DESIGN.md sections 15 - 17 and 19): eager launches of
+// Tiled, gated, motion-region and tiled frame-table detection (include/watsor_hip.h; DESIGN.md sections 15 - 17b and 19): eager launches of
 // k_tiles.hip, k_gate.hip and k_motion.hip around run_batch.  wz_engine.hip knows nothing of this file but TileLane / GateLane / MotionLane /
 // GateCam's and MotionCam's release, the lane's `tile.tiled` and merged rows (`tile.trows`, `tile.tpass`) and submit_bound_tiles (wz_engine.h).
 #include <stdio.h>
@@ -877,6 +877,32 @@ extern "C" int wz_bind_tiles(wz_engine_t* e, int first, int count, int n_tiles, 
     return WZ_OK;
 }
 
+// ---- the frame table's motion entries
+// Entries first .. first + count - 1 get a motion description (include/watsor_hip.h): the thresholds and nothing else -- the camera's
+// settings, hold and mask are looked up at every submit, as a gated description looks up its layout.  Nothing changes on a refusal.
+extern "C" int wz_bind_motion(wz_engine_t* e, int first, int count, double iou_thr, double ios_thr) {
+    if (!e) return wz_set_error(WZ_EINVAL, "wz_bind_motion: null engine");
+    HIPCHK(hipSetDevice(e->device));
+    WZCHK(sync_all(e));   // no batch in flight was planned with the old descriptions
+    const int64_t size = (int64_t)e->bound.size();
+    if (first < 0 || count < 1 || (int64_t)first + count > size)
+        return wz_set_error(WZ_EINVAL, "wz_bind_motion: entries %d .. %lld lie outside the frame table of %lld entries", first, (long long)first + count - 1,
+                            (long long)size);
+    const int c = e->bound[first].cam;
+    for (int i = first; i < first + count; ++i)
+        if (e->bound[i].cam < 0 || e->bound[i].cam != c)
+            return wz_set_error(WZ_EINVAL, "wz_bind_motion: motion entries %d .. %d must carry one camera id >= 0, entry %d has %d and entry %d has %d", first,
+                                first + count - 1, first, c, i, e->bound[i].cam);
+    if (!(iou_thr >= 0.0) || !(ios_thr >= 0.0)) return wz_set_error(WZ_EINVAL, "wz_bind_motion: the merge thresholds (%g, %g) must be numbers >= 0", iou_thr, ios_thr);
+    wz_engine::BoundTiles d;
+    d.kind = wz_engine::BOUND_MOTION;
+    d.iou = iou_thr;
+    d.ios = ios_thr;
+    if (e->bound_tiles.empty()) e->bound_tiles.resize(e->bound.size());
+    for (int i = first; i < first + count; ++i) e->bound_tiles[i] = d;
+    return WZ_OK;
+}
+
 // The bytes the crop kernel (and, gated, the activity kernel before it) reads of a frame: what decides between reading a page-locked frame in
 // place and staging it whole.  Break-even by bandwidth is near 0.8 of the frame's bytes (a kernel reads mapped memory at 23 GB/s beside the
 // other lanes' kernels, the copies move 29 GB/s: see stage_frame in wz_engine.hip); one half is the margin read_in_place() uses for the resize kernel.
@@ -885,6 +911,9 @@ extern "C" int wz_bind_tiles(wz_engine_t* e, int first, int count, int n_tiles, 
 // 0.15: 5825 in place against 8247 staged, a lone call 0.318 against 0.374 ms.  So at a cost well under one half, reading in place is
 // SLOWER than staging with every lane busy once the whole frame is small (3.1 MB): both in-place legs sit at ~0.175 ms a step whatever
 // they read.  The constant stays at one half here; moving it (or bounding it by the frame's bytes) needs that plateau explained first.
+// A MOTION entry never comes here and host_read is not consulted for it: its activity launch reads every luma pixel of the frame -- at
+// least 2/3 of an NV12 frame's bytes, all of an RGB24 frame's -- before any rectangle is cut, so its cost can never be at most half the
+// frame, and the in-place leg measured slower than staging with every lane busy even far below that.  It is always staged whole.
 static bool tiles_in_place(const wz_engine* e, const wz_engine::BoundFrame& f, const std::vector<wz_tile_t>& tiles, bool gated) {
     if (!f.dev || e->host_read == 0) return false;
     if (e->host_read == 1) return true;
@@ -894,10 +923,13 @@ static bool tiles_in_place(const wz_engine* e, const wz_engine::BoundFrame& f, c
     return e->host_read == 2 && 2 * cost <= f.bytes;
 }
 
-static const char* bound_kind_name(int kind) { return kind == wz_engine::BOUND_TILED ? "tiled" : kind == wz_engine::BOUND_GATED ? "gated" : "untiled"; }
+static const char* bound_kind_name(int kind) {
+    return kind == wz_engine::BOUND_TILED ? "tiled" : kind == wz_engine::BOUND_GATED ? "gated" : kind == wz_engine::BOUND_MOTION ? "motion" : "untiled";
+}
 
-// wz_submit_bound of a batch with a tiled or gated entry (slot, n and the entries' range are checked): one kind, one pair of thresholds,
-// the refusals of the tiled / gated call, then every frame staged whole or handed over in place, then tiled_enqueue / gated_enqueue.
+// wz_submit_bound of a batch with a tiled, gated or motion entry (slot, n and the entries' range are checked): one kind, one pair of
+// thresholds, the refusals of the tiled / gated / motion call, then every frame staged whole or (tiled, gated) handed over in place, then
+// tiled_enqueue / gated_enqueue / motion_enqueue.
 int submit_bound_tiles(wz_engine* e, int slot, int n, const int32_t* entries) {
     const wz_engine::BoundTiles& d0 = e->bound_tiles[entries[0]];
     for (int i = 1; i < n; ++i) {
@@ -912,7 +944,7 @@ int submit_bound_tiles(wz_engine* e, int slot, int n, const int32_t* entries) {
             return wz_set_error(WZ_EINVAL, "wz_submit_bound: frame-table entry %d merges with thresholds (%g, %g) and entry %d with (%g, %g): a batch takes one pair",
                                 entries[0], d0.iou, d0.ios, entries[i], d.iou, d.ios);
     }
-    const bool gated = d0.kind == wz_engine::BOUND_GATED;
+    const bool gated = d0.kind == wz_engine::BOUND_GATED, motion = d0.kind == wz_engine::BOUND_MOTION;
     BoundBatch b;
     bound_gather(e, n, entries, b);
     std::vector<int> nt(n);
@@ -922,21 +954,25 @@ int submit_bound_tiles(wz_engine* e, int slot, int n, const int32_t* entries) {
         tp[i] = e->bound_tiles[entries[i]].tiles.data();
     }
     TileCall c = {n, b.ptr.data(), b.w, b.h, b.fmt, b.cam, nt.data(), tp.data(), d0.iou, d0.ios, 0};
-    WZCHK(gated ? camera_check(e, &wz_engine::gate_cams, GATED, "wz_submit_bound", slot, c, true) : tiled_check(e, "wz_submit_bound", slot, c, true));
+    WZCHK(motion  ? camera_check(e, &wz_engine::motion_cams, MOTION, "wz_submit_bound", slot, c, true)
+          : gated ? camera_check(e, &wz_engine::gate_cams, GATED, "wz_submit_bound", slot, c, true)
+                  : tiled_check(e, "wz_submit_bound", slot, c, true));
     WZCHK(bound_drain(e, slot));
     Lane& L = e->lanes[slot];
     std::vector<int32_t> src(n);
     for (int i = 0; i < n; ++i) {
         const wz_engine::BoundFrame& f = e->bound[entries[i]];
-        const std::vector<wz_tile_t>& tiles = gated ? e->gate_cams.find(f.cam)->second.tiles : e->bound_tiles[entries[i]].tiles;
-        if (tiles_in_place(e, f, tiles, gated)) {
-            b.ptr[i] = f.dev;
-            src[i] = 1;
-            continue;
+        if (!motion) {   // (a motion entry has no in-place leg: see tiles_in_place)
+            const std::vector<wz_tile_t>& tiles = gated ? e->gate_cams.find(f.cam)->second.tiles : e->bound_tiles[entries[i]].tiles;
+            if (tiles_in_place(e, f, tiles, gated)) {
+                b.ptr[i] = f.dev;
+                src[i] = 1;
+                continue;
+            }
         }
         WZCHK(stage_frame(e, L, i, f.host, f.bytes, &b.ptr[i]));
     }
-    WZCHK(enqueue(e, slot, c, gated ? KIND_GATED : KIND_TILED));
+    WZCHK(enqueue(e, slot, c, motion ? KIND_MOTION : gated ? KIND_GATED : KIND_TILED));
     L.bound_idx.assign(entries, entries + n);   // (L.tile.tiled == n says that their rows are the merged ones)
     L.bound_src.swap(src);
     return WZ_OK;

@@ -33,7 +33,10 @@ differences, all inside the worker process:
   * a detector with a `tiles` option goes through `detect_batch()`, one call at a time -- or, with `kwargs['hip_tiled_table']`, stays
     asynchronous: its frame table carries the tiles (`wz_bind_tiles`), a batch is cut by the detector's `plan_bound()` into tiled / gated
     calls, each on a lane of its own;
-  * a detector with a `motion` option goes through `detect_batch()` as well (motion regions keep a reference per camera).
+  * a detector with a `motion` option goes through `detect_batch()` as well (motion regions keep a reference per camera) -- or, with
+    `kwargs['hip_tiled_table']`, stays asynchronous like a tiled one: its cameras' frames are bound as motion entries (`wz_bind_motion`), a
+    batch is cut by `plan_bound()` into motion calls (one frame per camera, the configured whole_frame + max_regions within max_batch),
+    each on a lane of its own; a piece the engine refuses is retried through `detect_batch()`, which continues the camera's sequence.
 
 This module needs the reference package (`watsor.stream`) at run time -- it is a drop-in for an
 installed Watsor, see INTEGRATION.md.  Everything below `detect_batch()` does not.
@@ -104,25 +107,27 @@ class BatchedWorkerMixin:
                               logger=getattr(self, "_logger", None))
         if hasattr(object_detector, "submit_host") and hasattr(object_detector, "collect"):
             st["asynchronous"] = kwargs.get("hip_async", True)
-            if st["asynchronous"] and getattr(object_detector, "tiled", False):
+            tiled, motion = getattr(object_detector, "tiled", False), getattr(object_detector, "motion", False)
+            if st["asynchronous"] and (tiled or motion):
                 if kwargs.get("hip_tiled_table", False) and kwargs.get("hip_frame_table", True) and hasattr(object_detector, "bind_tiled_frame_table"):
-                    # opt-in: the frame table with tiled descriptions (wz_bind_tiles) -- batches stay asynchronous, cut by plan_bound()
+                    # opt-in: the frame table with tiled and motion descriptions (wz_bind_tiles, wz_bind_motion) -- batches stay asynchronous,
+                    # cut by plan_bound()
                     try:
                         st["table"] = object_detector.bind_tiled_frame_table(frame_buffers, st["cams"] or {})
                         st["plan"] = object_detector.plan_bound
-                    except ValueError as e:       # the asynchronous host path detects untiled: a tiled detector never goes there
+                    except ValueError as e:       # the asynchronous host path detects untiled: a tiled or motion detector never goes there
                         st["asynchronous"] = False
                         self._warn("tiled frame table not bound (%s): batches go through detect_batch(), one call at a time" % (e,))
-                else:
+                elif tiled:
                     # tiled detection (plugin option `tiles`) through detect() / detect_batch(): the asynchronous host path has no tiled
                     # form, the frame table only on request (`hip_tiled_table`), and nothing may be detected untiled in silence
                     st["asynchronous"] = False
                     self._info("tiles are configured: batches go through detect_batch(), one call at a time")
-            if st["asynchronous"] and getattr(object_detector, "motion", False):
-                # motion regions (plugin option `motion`) keep a reference per camera and go through detect_batch() with camera ids: neither
-                # the asynchronous host path nor the frame table has a form for them
-                st["asynchronous"] = False
-                self._info("motion is configured: batches go through detect_batch(), one call at a time")
+                else:
+                    # motion regions (plugin option `motion`) keep a reference per camera and go through detect_batch() with camera ids: the
+                    # asynchronous host path has no form for them, the frame table only on request (`hip_tiled_table`)
+                    st["asynchronous"] = False
+                    self._info("motion is configured: batches go through detect_batch(), one call at a time")
             lanes = getattr(object_detector, "num_lanes", 1)
             st["lanes"] = max(1, min(int(kwargs.get("hip_lanes", lanes)), lanes))
         if st["asynchronous"] and st["plan"] is None and kwargs.get("hip_frame_table", True) and hasattr(object_detector, "bind_frame_table"):
@@ -335,7 +340,7 @@ class BatchedWorkerMixin:
 
     def _submit_planned(self, st, payloads, entries, latches, frame_buffers, fps, inference_time, object_detector):
         """A batch of a tiled frame table (`hip_tiled_table`): the detector cuts the indices into the calls the engine accepts -- one kind, one
-        pair of thresholds, tiles within max_batch, one frame of a gated camera -- and every piece goes onto a lane of its own, with the
+        pair of thresholds, tiles within max_batch, one frame of a gated or motion camera -- and every piece goes onto a lane of its own, with the
         latches of its payloads; when every lane is busy the oldest batch is retired first, as between batches."""
         def retry(off, e):                        # nothing was enqueued for this piece or the ones behind it: synchronous retry, frame by frame
             self._warn("asynchronous submit of %d frames failed (%s), falling back to synchronous calls" % (len(payloads) - off, e))
@@ -514,8 +519,9 @@ def create_object_detectors(delegate_class, stop_event, log_queue, frame_queue, 
       hip_lanes    batches kept in flight per GPU by the worker (default: the engine's lanes, 4)
       hip_metric_interval  seconds of batches folded into one `inference_time` observation (default 0.005; 0: one per batch)
       hip_frame_table      False: describe the frames of every batch to the engine instead of binding them once
-      hip_tiled_table      True: a detector with a `tiles` option stays asynchronous -- its frame table carries the tiles (wz_bind_tiles), a
-                           batch is cut into tiled / gated calls on successive lanes (default False: detect_batch(), one call at a time)
+      hip_tiled_table      True: a detector with a `tiles` or a `motion` option stays asynchronous -- its frame table carries the tiles
+                           (wz_bind_tiles) and the motion cameras (wz_bind_motion), a batch is cut into tiled / gated / motion calls on
+                           successive lanes (default False: detect_batch(), one call at a time)
       hip_affinity         True (several AMD GPUs): whole cameras are dealt to the detectors (`camera_affinity`): a detector binds and
                            page-locks only its own cameras' frame buffers; payloads drawn by the wrong detector are passed on"""
     _ref = _require_watsor()

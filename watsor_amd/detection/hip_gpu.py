@@ -382,17 +382,18 @@ def cut_calls(items, max_batch: int):
 
 def plan_bound(descriptions, entries, max_batch: int):
     """Cuts a list of frame-table indices into the calls `wz_submit_bound` accepts, in order (include/watsor_hip.h): every call holds one
-    kind -- untiled, tiled or gated -- and one pair of merge thresholds, at most max_batch frames whose tiles (gated: their cameras'
-    configured tiles) together fit max_batch, and at most one frame of a gated camera.  The calls are consecutive pieces of `entries`, so a
-    camera's frames keep their order.  descriptions[i] = (kind, iou, ios, tiles, camera id) of table entry i with kind "plain" | "tiled" |
-    "gated" (what `bind_tiled_frame_table` recorded); an index beyond them counts as plain.  A pure function."""
+    kind -- untiled, tiled, gated or motion -- and one pair of merge thresholds, at most max_batch frames whose tiles (gated: their cameras'
+    configured tiles; motion: their cameras' configured whole_frame + max_regions) together fit max_batch, and at most one frame of a gated
+    or motion camera.  The calls are consecutive pieces of `entries`, so a camera's frames keep their order.  descriptions[i] = (kind, iou,
+    ios, tiles, camera id) of table entry i with kind "plain" | "tiled" | "gated" | "motion" (what `bind_tiled_frame_table` recorded); an
+    index beyond them counts as plain.  A pure function."""
     items = []
     for e in entries:
         kind, iou, ios, tiles, cam = descriptions[e] if 0 <= e < len(descriptions) else ("plain", None, None, 1, -1)
         if kind == "plain":
             items.append((("plain",), 1, None))      # (a cost of 1 each: at most max_batch frames)
         else:
-            items.append(((kind, iou, ios), tiles, cam if kind == "gated" else None))
+            items.append(((kind, iou, ios), tiles, cam if kind in ("gated", "motion") else None))
     return [[entries[i] for i in call] for call in cut_calls(items, max_batch)]
 
 
@@ -434,7 +435,8 @@ class HipObjectDetector:
         components with at least `min_cells` changed cells become up to `max_regions` rectangles of at least `min_side` pixels a side,
         `pad` pixels around the cells; `whole_frame` runs the squeezed whole frame beside them; "iou" / "ios" merge as for `tiles`.  A
         camera takes `motion` or `tiles`, not both; its frames need a camera id and go through `detect_batch` (cut into calls whose
-        configured whole_frame + max_regions fit max_batch); `bind_frame_table` / `bind_tiled_frame_table` raise for such a camera.
+        configured whole_frame + max_regions fit max_batch) -- or through the batched worker's frame table: `bind_tiled_frame_table` (the
+        worker's `hip_tiled_table`) binds such a camera's frames as motion entries (wz_bind_motion); `bind_frame_table` raises for it.
         `options["motion_hold"]`: {"hold": 0 .. 255, "object_hold": 0 .. 255} (not both 0) for every camera with `motion`, or {camera name:
         one of these}: a cell stays part of the camera's regions for `hold` further frames after it changed, and for `object_hold`
         further frames after a detection that passed the camera's filters covered it -- a person who stops moving, a parked car the
@@ -549,7 +551,8 @@ class HipObjectDetector:
 
     @property
     def motion(self) -> bool:
-        """A `motion` option is set (for every camera or for some): frames go through `detect_batch()` with camera ids."""
+        """A `motion` option is set (for every camera or for some): frames go through `detect_batch()` with camera ids, or through a frame
+        table bound with `bind_tiled_frame_table`."""
         return self.__motion_default is not None or bool(self.__motion_by_name)
 
     @property
@@ -641,11 +644,14 @@ class HipObjectDetector:
         return self._bind_table(frame_buffers, ids, tiled=False)
 
     def bind_tiled_frame_table(self, frame_buffers, ids):
-        """`bind_frame_table` for a detector with a `tiles` option (the worker's `hip_tiled_table`): after the table is bound every camera
-        with a description gets its rectangles -- `tile_grid` of the table's own width, height and format, or the explicit "rects" --
-        through `wz_bind_tiles`; a description with a "gate" on a camera that has an id sets the camera's layout (`set_camera_tiles`) and
-        binds its frames gated; a gate without a camera id is tiled, not gated, as in `detect_batch`.  Batches must then be cut by
-        `plan_bound`.  Returns the same table."""
+        """`bind_frame_table` for a detector with a `tiles` or a `motion` option (the worker's `hip_tiled_table`): after the table is bound
+        every camera with a `tiles` description gets its rectangles -- `tile_grid` of the table's own width, height and format, or the
+        explicit "rects" -- through `wz_bind_tiles`; a description with a "gate" on a camera that has an id sets the camera's layout
+        (`set_camera_tiles`) and binds its frames gated; a gate without a camera id is tiled, not gated, as in `detect_batch`.  A camera
+        with `motion` settings gets them, its hold and its ignore mask for the table's own width, height and format (`set_camera_motion`,
+        `set_camera_motion_hold`, `set_camera_ignore`: its reference starts anew) and its frames a motion description (`wz_bind_motion`);
+        it needs a camera id and one size and format for all its frames (ValueError).  Batches must then be cut by `plan_bound`.  Returns
+        the same table."""
         return self._bind_table(frame_buffers, ids, tiled=True)
 
     def plan_bound(self, entries):
@@ -662,9 +668,9 @@ class HipObjectDetector:
             if not tiled and (self.__tiles_default is not None or str(name) in self.__tiles_by_name):
                 raise ValueError("camera %r has tiles configured: tiled detection does not go through the worker's frame table "
                                  "(bind_frame_table / submit_bound); use detect() / detect_batch() for it" % (name,))
-            if self.__motion_default is not None or str(name) in self.__motion_by_name:
-                raise ValueError("camera %r has motion configured: motion regions do not go through the worker's frame table "
-                                 "(bind_frame_table / bind_tiled_frame_table / submit_bound); use detect_batch() for it" % (name,))
+            if not tiled and (self.__motion_default is not None or str(name) in self.__motion_by_name):
+                raise ValueError("camera %r has motion configured: motion regions do not go through the untiled frame table "
+                                 "(bind_frame_table); use bind_tiled_frame_table() or detect_batch() for it" % (name,))
             cam = ids.get(name, -1)
             fmt0 = self.__fmt_by_cam.get(cam, self.__fmt_default) if cam >= 0 else self.__fmt_default
             latches = []
@@ -699,6 +705,7 @@ class HipObjectDetector:
         self.bound_descriptions = [("plain", None, None, 1, c) for c in cams]
         if tiled:
             self._bind_tiles(frame_buffers, table, ws, hs, fmts, cams)
+            self._bind_motion(frame_buffers, table, ws, hs, fmts, cams)
         self.submit_bound = self.__engine.submit_bound      # (the worker calls these once per batch: no wrapper frames in between)
         self.collect_bound = self.__engine.collect_bound
         return table
@@ -733,6 +740,36 @@ class HipObjectDetector:
                 for i in range(first, last):
                     self.bound_descriptions[i] = ("gated" if gated else "tiled", iou, ios, len(rects), cam)
                 first = last
+
+    def _bind_motion(self, frame_buffers, table, ws, hs, fmts, cams):
+        """The motion descriptions of a freshly bound table: per camera with `motion` settings, the settings, the hold and the ignore mask
+        for the table's own width, height and format -- in the order `_detect_motion` sets them, and recorded as it records them: a piece
+        the engine refuses is retried through `detect_batch()`, which must find the layout current and leave reference, ages and mask
+        alone -- then one `bind_motion` over the camera's frames."""
+        eng = self.__engine
+        for name in sorted(frame_buffers, key=str):
+            base, latches = table[name]
+            m = self.__motion_by_name.get(str(name), self.__motion_default)
+            if m is None or not latches:
+                continue
+            cam, last = cams[base], base + len(latches)
+            if cam < 0:
+                raise ValueError("camera %r: a motion camera needs a camera id: the reference is kept per camera (bind_cameras first)" % (name,))
+            w, h, fmt = ws[base], hs[base], fmts[base]
+            if any((ws[i], hs[i], fmts[i]) != (w, h, fmt) for i in range(base, last)):
+                raise ValueError("camera %r: the frames of a motion camera must share one size and format" % (name,))
+            eng.set_camera_motion(cam, w, h, m["threshold"], m["min_cells"], m["dilate"], m["max_regions"], m["min_side"], m["pad"],
+                                  m["whole_frame"], fmt)
+            hold = self.__hold_by_cam.get(cam) or self.__hold_default      # (new motion settings drop the hold: it is set behind them)
+            if hold is not None:
+                eng.set_camera_motion_hold(cam, hold["hold"], hold["object_hold"])
+            self._set_ignore(cam, w, h)                                     # (... and the motion part of the mask)
+            self.__motion_layouts[cam] = (w, h, fmt & FMT_BASE_MASK, id(m))
+            iou = float(eng.nms_iou if m["iou"] is None else m["iou"])
+            ios = float(1.0 if m["ios"] is None else m["ios"])
+            eng.bind_motion(base, last - base, iou, ios)
+            for i in range(base, last):
+                self.bound_descriptions[i] = ("motion", iou, ios, m["count"], cam)
 
     def submit_host(self, lane: int, images: Sequence[np.ndarray], cameras: Optional[Sequence[int]] = None) -> None:
         """Asynchronous `detect_batch`: the frames (views of shared memory, unchanged until `collect`) are enqueued on `lane`."""

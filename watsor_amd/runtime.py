@@ -178,6 +178,7 @@ class HipEngine:
         self._bound_last = {}                              # lane -> frames of the last bound batch accepted on it (bound_source)
         self._bound_cams = []                              # camera id of every table entry (bind_frames) ...
         self._bound_tiled = {}                             # ... and entry -> its camera id where bind_tiles(gated=True) described it, -1 where rects did
+        self._bound_motion = {}                            # ... and entry -> its camera id where bind_motion described it
 
     def _ck(self, rc: int, what: str = "") -> None:
         if rc:
@@ -547,6 +548,7 @@ class HipEngine:
         self._bound_arrays = {}
         self._bound_cams = [int(c) for c in cams]
         self._bound_tiled = {}
+        self._bound_motion = {}
 
     def bind_tiles(self, first: int, count: int, rects=None, iou: Optional[float] = None, ios: Optional[float] = 1.0, gated: bool = False) -> None:
         """Table entries first .. first + count - 1 (normally one camera's frames) are detected TILED from now on (include/watsor_hip.h:
@@ -557,6 +559,7 @@ class HipEngine:
         arr = C.byref(self._tile_array(rects, "")) if rects is not None else None
         self._ck(self._lib.wz_bind_tiles(self._h, int(first), int(count), n, arr, *self._thresholds(iou, ios), 1 if gated else 0))
         for i in range(int(first), int(first) + int(count)):
+            self._bound_motion.pop(i, None)
             if gated:
                 self._bound_tiled[i] = self._bound_cams[i]
             elif rects is not None:
@@ -564,9 +567,19 @@ class HipEngine:
             else:
                 self._bound_tiled.pop(i, None)
 
+    def bind_motion(self, first: int, count: int, iou: Optional[float] = None, ios: Optional[float] = 1.0) -> None:
+        """Table entries first .. first + count - 1 -- the frames of one camera, which carry its id -- are detected in their MOTION REGIONS
+        from now on (include/watsor_hip.h: wz_bind_motion): settings, hold and ignore mask are the ones `set_camera_motion`,
+        `set_camera_motion_hold` and `set_camera_ignore` gave the camera, looked up at every submit.  iou / ios as in `detect_motion` (None:
+        the engine's own NMS threshold / 1.0).  `bind_tiles(first, count, None)` makes them untiled again.  Waits for every lane."""
+        self._ck(self._lib.wz_bind_motion(self._h, int(first), int(count), *self._thresholds(iou, ios)))
+        for i in range(int(first), int(first) + int(count)):
+            self._bound_tiled.pop(i, None)
+            self._bound_motion[i] = self._bound_cams[i]
+
     def bound_source(self, slot: int) -> List[int]:
-        """Development library: per frame of the last tiled or gated bound batch on lane `slot`, 1 = read in place from page-locked memory,
-        0 = staged by DMA."""
+        """Development library: per frame of the last tiled, gated or motion bound batch on lane `slot`, 1 = read in place from page-locked
+        memory, 0 = staged by DMA (a motion batch: always 0)."""
         self._dev_only("bound_source")
         n = self._bound_last.get(slot, 0)
         out = (C.c_int32 * max(1, n))()
@@ -575,7 +588,8 @@ class HipEngine:
 
     def submit_bound(self, slot: int, entries: Sequence[int]) -> None:
         """Asynchronous detect of the frames with these table indices on lane `slot` (one C call, no per-frame work here).  Entries with a
-        tiled description (`bind_tiles`) run tiled / gated; a batch holds one kind."""
+        tiled description (`bind_tiles`) run tiled / gated, entries with a motion description (`bind_motion`) in their motion regions; a
+        batch holds one kind."""
         n = len(entries)
         arr_t = self._bound_arrays.get(n)
         if arr_t is None:
@@ -589,6 +603,9 @@ class HipEngine:
                 self._bound_last[slot] = n
                 if cam >= 0:
                     self._gate_last[slot] = [self._bound_tiled[i] for i in entries]
+        if self._bound_motion and entries[0] in self._bound_motion:    # (... and motion_stats / motion_hold_stats / motion_ignore_stats)
+            self._bound_last[slot] = n
+            self._motion_last[slot] = [self._bound_motion[i] for i in entries]
 
     def collect_bound(self, slot: int) -> None:
         """Waits for lane `slot`; its rows are written into the bound frames' own `Detection[100]` arrays."""
