@@ -29,6 +29,6 @@ def run_worker(model_dir, frame_buffers, payload_batches, fps, inference_time, c
                 while not q.empty():
                     w._process(q, None, frame_buffers, fps, inference_time, det, **kwargs)
             w.drain(fps, inference_time)
-            result_queue.put(("ok", det.device_name, dict(opts), len(getattr(det, "_HipObjectDetector__pinned"))))
+            result_queue.put(("ok", det.device_name, dict(opts), len(det._pinned)))
     except Exception:
         result_queue.put(("error", traceback.format_exc(), None, 0))

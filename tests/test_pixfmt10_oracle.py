@@ -238,7 +238,7 @@ def test_frame_table_of_10_bit_cameras(tmp_path, monkeypatch):
     nb = 3 * 64 * 48
     buffers = {"hw": fb(_Frame(128, 72, 1, nb)), "sw": fb(_Frame(64, 72, 2, nb)), "door": fb(_Frame(64, 48, 3, nb))}
     ids = {"hw": 0, "sw": 1, "door": -1}
-    det._HipObjectDetector__fmt_by_cam = {i: det._HipObjectDetector__fmt_by_name[n] for n, i in ids.items() if i >= 0}
+    det._adopt_ids(ids)
     det.bind_frame_table(buffers, ids)
     assert det.engine.table == [(64, 48, FMT_RGB24, -1), (64, 48, FMT_P010 | CSP_BT709, 0), (64, 48, FMT_YUV420P10, 1)]
     for name, frame in (("hw", _Frame(128, 72, 1, nb - 1)), ("hw", _Frame(64, 72, 3, nb)), ("sw", _Frame(63, 72, 2, nb)), ("sw", _Frame(64, 73, 2, nb)),
@@ -250,7 +250,7 @@ def test_frame_table_of_10_bit_cameras(tmp_path, monkeypatch):
         with pytest.raises(ValueError, match=text):
             det.bind_frame_table(dict(buffers, **{name: fb(frame)}), ids)
     # a base format the library does not know: held to three channels, then the library's sizing refuses it in its own words
-    det._HipObjectDetector__fmt_by_cam[0] = 9
+    det._cams[0] = det._cams[0]._replace(fmt=9)
     for channels, text in ((3, "pixel format word 0x9 is not taken at 64x48"), (1, "must have 3 channels")):
         with pytest.raises(ValueError, match=text):
             det.bind_frame_table(dict(buffers, hw=fb(_Frame(64, 48, channels, nb))), ids)

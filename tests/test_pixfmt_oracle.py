@@ -187,22 +187,10 @@ def test_plugin_names_and_colour_options():
     assert frame_formats([gray], None, FMT_GRAY8, {}) == [FMT_GRAY8]
 
 
-class _Frame:
-    """What `bind_frame_table` reads of a reference Frame (watsor/stream/share.py:27-73): header, image, latch."""
-    def __init__(self, w, h, channels, nbytes):
-        import ctypes
-        from watsor_amd.share import DetectionArray
-
-        class Header(ctypes.Structure):
-            _fields_ = [("width", ctypes.c_int), ("height", ctypes.c_int), ("channels", ctypes.c_int), ("detections", DetectionArray)]
-        self.header = Header(w, h, channels)
-        self.image = (ctypes.c_uint8 * nbytes)()
-        self.latch = type("Latch", (), {"next": staticmethod(lambda: None)})()
-
-
 def test_frame_table_of_gray_and_packed_cameras(tmp_path, monkeypatch):
     """A configured gray camera's one-channel FrameBuffer is bound as GRAY8 (not as the planar buffer of an NV12 camera), a 4:2:2
     camera's as (H, W, 2) or (H, 2W, 1), and the size check is the library's wz_frame_bytes."""
+    from detector_calls import _Frame, fb
     from watsor_amd.detection import hip_gpu
 
     class Engine:
@@ -217,11 +205,10 @@ def test_frame_table_of_gray_and_packed_cameras(tmp_path, monkeypatch):
     (tmp_path / hip_gpu.ENGINE_FILE).write_bytes(b"stub")
     opts = {"pixel_format": {"ir": "gray", "usb": "yuyv422", "usb2": "uyvy422", "hd": "nv12"}, "color_matrix": {"hd": "bt709"}, "numa": False}
     det = hip_gpu.HipObjectDetector(str(tmp_path), 0, opts)
-    fb = lambda *frames: type("FrameBuffer", (), {"frames": list(frames)})()
     buffers = {"ir": fb(_Frame(64, 48, 1, 64 * 48)), "usb": fb(_Frame(64, 48, 2, 64 * 48 * 2)), "usb2": fb(_Frame(128, 48, 1, 64 * 48 * 2)),
                "hd": fb(_Frame(64, 72, 1, 64 * 48 * 3 // 2)), "door": fb(_Frame(64, 48, 3, 64 * 48 * 3))}
     ids = {"ir": 0, "usb": 1, "usb2": 2, "hd": 3, "door": -1}
-    det._HipObjectDetector__fmt_by_cam = {i: det._HipObjectDetector__fmt_by_name[n] for n, i in ids.items() if i >= 0}
+    det._adopt_ids(ids)
     det.bind_frame_table(buffers, ids)
     assert det.engine.table == [(64, 48, FMT_RGB24, -1), (64, 48, FMT_NV12 | CSP_BT709, 3), (64, 48, FMT_GRAY8, 0), (64, 48, FMT_YUYV422, 1),
                                 (64, 48, FMT_UYVY422, 2)]
